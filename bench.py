@@ -12,6 +12,10 @@ Inputs are synthetic and already resident in HBM (a pool of distinct batches cyc
 pass over one batch.  N>1: one process per GPU (torchrun contract; `python bench.py --gpus N` without a torchrun
 environment re-launches itself under torch.distributed.run), weak scaling, the RCCL world size is printed.
 
+A plain run sets up, warms up, times exactly --steps steps, writes the last timed step's outputs when --dump-outputs DIR is given
+(DIR/<name>.npy, float32: the step's loss and predictions and every trainable variable after its update, a fixed seeded sample of
+the larger ones) and prints the line.  Everything below runs only with --full (the --no-* switches then drop single legs).
+
 Extra lines in the same JSON ("extra", rank 0, N=1 only; each with its own per-family hipEvent times and roofline):
   configs[1]  MoeModel (2 mixtures) on video-level [1024,1152] features, fp32 (>= 200 timed steps: the step is ~1 ms)
   configs[2]  NetVLADModel (64 clusters) on raw uint8 [B,300,1152] frames + MoE head, fp32
@@ -67,6 +71,10 @@ def parse():
                     help="headline workload; default = BASELINE configs[3] (the frame-level config the metric is quoted on)")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (0 = the config's: lstm 128, moe 1024, netvlad 1024)")
     ap.add_argument("--pool", type=int, default=0, help="distinct synthetic batches resident in HBM (0 = per workload)")
+    ap.add_argument("--full", action="store_true", help="after the headline also run the roofline pass, the extra configurations, the "
+                    "cpu_baseline and GAP@20 legs and the placement / data-parallel diagnostics (the --no-* switches drop single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; larger arrays as a fixed seeded sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the configs[1] / configs[2] / bf16-variant extra lines")
@@ -364,9 +372,13 @@ def timed_run(tg, pool, steps, warmup, world, dev, dist):
     tools/bench_diag.py: they wrap this function's `run` from the outside.)"""
 
     def run(k, base):
+        """k steps from pool entry `base`; returns what the last of them returned"""
+        out = None
         for i in range(k):
+            out = None                   # a step's outputs are released before the next step, as when they were not kept
             x, y, nf = pool[(base + i) % len(pool)]
-            tg.step(x, y, nf)
+            out = tg.step(x, y, nf)
+        return out
 
     run(max(warmup, 1), 0)
     torch.cuda.synchronize()
@@ -374,7 +386,7 @@ def timed_run(tg, pool, steps, warmup, world, dev, dist):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run(steps, warmup)
+    run.last = run(steps, warmup)        # the timed path's outputs of its last step (--dump-outputs)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -768,6 +780,34 @@ def library_identity():
             "sha256": h.hexdigest(), "env": {k: v for k, v in sorted(os.environ.items()) if k.startswith("YT8M_")}}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, out, graph, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the step's `loss` and `predictions` and every
+    trainable variable after the step's update (var.<name with / as .>) -- as DIR/<name>.npy in float32.  An array with more elements
+    than its share of `limit_bytes` is written as a fixed sample: sorted indices drawn by a CPU generator seeded from the array's name,
+    the same in every run.  Returns {name: (shape written, shape of the array)}."""
+    import zlib
+    import numpy as np
+    arrays = [("loss", out["loss"]), ("predictions", out["predictions"])]
+    arrays += [("var." + v.name.replace("/", "."), v.data) for v in graph.trainable_variables()]
+    cap = max(1, min(1 << 20, limit_bytes // 4 // len(arrays)))
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    for name, t in arrays:
+        t = t.detach()
+        s = t
+        if t.numel() > cap:
+            gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, t.numel(), (cap,), generator=gen).sort().values
+            s = t.reshape(-1)[idx.to(t.device)]
+        a = s.float().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name] = (list(a.shape), list(t.shape))
+    return written
+
+
 LINE_LIMIT = 8192                    # the driver keeps ~8.9 KB of stdout: the ONE line must fit (VERDICT r4 #1)
 SIDECAR = "bench_extra.json"
 
@@ -946,8 +986,12 @@ def main():
         seq_ops.check_persist_errors()          # a persistent launch that timed out must fail the bench, not skew it
     except Exception as e:                      # ... but every rank's word goes into the line first (a SCALE run must explain itself)
         persist_timeout = repr(e)
+    if a.dump_outputs and rank == 0 and persist_timeout is None:
+        written = dump_outputs(a.dump_outputs, run.last, g)
+        note("outputs of the last timed step: %d arrays under %s" % (len(written), a.dump_outputs))
+    run.last = None
     placement = None
-    if a.workload == "lstm":
+    if a.full and a.workload == "lstm":
         # diagnostics of the timed region (+ warm-up): persistent recurrence workgroups that did not land on the XCD their index
         # suggests lose the L2 sharing of the state fetch -- tells an unlucky placement from a slow kernel
         nl, nw, off = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
@@ -956,7 +1000,7 @@ def main():
     # data-parallel timeline of two more (untimed) steps: when each gradient bucket's collective was enqueued and landed relative to
     # the backward pass, the all-reduce time left exposed behind it -- per rank (parallel.GradReducer.trace)
     dp_trace = None
-    if reducer is not None and reducer.active:
+    if a.full and reducer is not None and reducer.active:
         reducer.trace = True
         run(2, 0)
         dp_trace = reducer.trace_report()
@@ -973,7 +1017,7 @@ def main():
     placement = placement if rank == 0 else None
 
     roof = None
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         fam = profile_pass(lib, run, min(a.steps, 5 if a.workload != "moe" else 20), rank)
         if rank == 0:
             bwd_cus = None
@@ -1021,7 +1065,7 @@ def main():
     torch.cuda.empty_cache()
 
     extra = []
-    if rank == 0 and world == 1 and not a.no_extra and a.workload == "lstm" and not bf16:
+    if a.full and rank == 0 and world == 1 and not a.no_extra and a.workload == "lstm" and not bf16:
         for wl, b16, bb in (("moe", False, None), ("netvlad", False, None), ("lstm", True, None), ("composite", True, None),
                             # per-GPU batch sweep of the headline configuration: more rows per workgroup = more independent
                             # chains per persistent workgroup; tells the 8-GPU run which per-GPU batch to use
@@ -1033,13 +1077,13 @@ def main():
                 extra.append({"workload": WORKLOADS[wl]["name"], "error": repr(e)})
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         note("cpu_baseline starts")
         cpu = cpu_baseline(a.workload, a.cpu_seconds, a.cpu_steps, a.cpu_max_seconds)
         note("cpu_baseline done: %s" % (cpu and cpu.get("sample")))
 
     gap = None
-    if rank == 0 and world == 1 and not a.no_gap and not bf16:
+    if a.full and rank == 0 and world == 1 and not a.no_gap and not bf16:
         try:
             gap = gap_leg(dev)
             state = gap.pop("_state")

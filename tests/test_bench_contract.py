@@ -238,3 +238,73 @@ def test_library_identity_names_the_in_tree_build(monkeypatch):
     ident = b.library_identity()
     assert ident["in_tree_default"] and ident["path"].endswith("libyt8m_hip.so") and len(ident["sha256"]) == 64
     assert ident["env"].get("YT8M_SOME_KNOB") == "7"
+
+
+def test_plain_run_is_the_headline_and_full_is_opt_in(monkeypatch):
+    """`bench.py --gpus 1 --steps N --warmup W` runs the headline only; the other legs need --full; --dump-outputs takes a directory."""
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "outs"])
+    a = b.parse()
+    assert a.full and a.dump_outputs == "outs"
+
+
+def test_timed_run_times_exactly_the_requested_steps(monkeypatch):
+    """--steps is the number of timed steps: W warm-up steps (at least one), then exactly `steps` inside the clock; run.last holds
+    what the last timed step returned."""
+    b = _bench()
+    monkeypatch.setattr(b.torch.cuda, "synchronize", lambda *a: None)
+    calls, clock, real = [], [], b.time.perf_counter
+
+    class TG(object):
+        def step(self, x, y, nf):
+            calls.append((x, real()))
+            return {"n": len(calls)}
+
+    monkeypatch.setattr(b.time, "perf_counter", lambda: clock.append(real()) or clock[-1])
+    pool = [(i, None, None) for i in range(3)]
+    el, run = b.timed_run(TG(), pool, 5, 2, 1, None, None)
+    assert len(calls) == 7 and [c[0] for c in calls] == [0, 1, 2, 0, 1, 2, 0]
+    t0, t1 = clock[-2], clock[-1]
+    assert sum(1 for _, t in calls if t0 <= t <= t1) == 5 and el == t1 - t0
+    assert run.last == {"n": 7}
+
+
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path):
+    """--dump-outputs: loss, predictions and every trainable variable as float32 .npy; arrays above their share of the byte limit
+    become a fixed sample (the same indices in every run) of their own values; the whole dump stays under the limit."""
+    import numpy as np
+    import torch
+    b = _bench()
+
+    class V(object):
+        def __init__(self, name, data, trainable=True):
+            self.name, self.data, self.trainable = name, data, trainable
+
+    class G(object):
+        vars = [V("experts/weights", torch.arange(400000, dtype=torch.float32).view(400, 1000) * 0.5),
+                V("experts/biases", torch.linspace(-1, 1, 1000, dtype=torch.float64)), V("global_step", torch.zeros(1), False)]
+
+        def trainable_variables(self):
+            return [v for v in self.vars if v.trainable]
+
+    out = {"loss": torch.tensor(3.25), "predictions": torch.rand(16, 50, generator=torch.Generator().manual_seed(0))}
+    limit = 1 << 20
+    w1 = b.dump_outputs(str(tmp_path / "a"), out, G(), limit_bytes=limit)
+    w2 = b.dump_outputs(str(tmp_path / "b"), out, G(), limit_bytes=limit)
+    names = {"loss", "predictions", "var.experts.weights", "var.experts.biases"}
+    assert set(w1) == names and w1 == w2 and sorted(os.listdir(str(tmp_path / "a"))) == sorted(n + ".npy" for n in names)
+    total = 0
+    for n in names:
+        x, y = np.load(str(tmp_path / "a" / (n + ".npy"))), np.load(str(tmp_path / "b" / (n + ".npy")))
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+        total += x.nbytes
+    assert total <= limit
+    assert float(np.load(str(tmp_path / "a" / "loss.npy"))) == 3.25
+    assert np.array_equal(np.load(str(tmp_path / "a" / "predictions.npy")), out["predictions"].numpy())
+    assert np.allclose(np.load(str(tmp_path / "a" / "var.experts.biases.npy")), np.linspace(-1, 1, 1000), atol=1e-7)
+    s = np.load(str(tmp_path / "a" / "var.experts.weights.npy"))
+    assert w1["var.experts.weights"] == ([limit // 4 // 4], [400, 1000]) and s.shape == (limit // 16,)
+    assert np.all(np.diff(s) >= 0) and np.all(s * 2 == np.round(s * 2)) and s.max() <= 199999.5 and len(np.unique(s)) > s.size // 2

@@ -7,7 +7,7 @@ O=$R/gpurun_out/prof_r4
 rm -rf $O; mkdir -p $O
 cd /tmp
 # 1. the headline bench line exactly as the driver runs it (un-profiled, all legs incl. the >= 10-step CPU baseline)
-timeout 900 python $R/bench.py --steps 20 --warmup 5 < /dev/null > $O/bench_line.json 2> $O/bench.err
+timeout 900 python $R/bench.py --full --steps 20 --warmup 5 < /dev/null > $O/bench_line.json 2> $O/bench.err
 # 2. the same workload under kernel trace + stats (no CPU / GAP / extra legs: they are not the measured region)
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -o bench -- python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-gap --no-extra < /dev/null > $O/bench_line_profiled.json 2> $O/bench_prof.err
 f=$(find $O/bench -name "*kernel_trace.csv" | head -1)

@@ -16,7 +16,7 @@ timeout 200 rocprofv3 --kernel-trace --pmc SQ_BUSY_CYCLES SQ_WAVES --output-form
 python $R/tools/pmc_mfma_busy.py $(find $O/pmc -name "mfma*counter_collection.csv" | head -1) > $O/mfma_busy.txt 2>&1
 (cd $R && python tools/make_profile_docs_r5.py pmc > $O/pmc_traffic.log 2>&1; cp profiles/r5_pmc_traffic_lstm.json $O/ 2>/dev/null)
 # 2. the headline bench line exactly as the driver runs it (un-profiled, all legs incl. the >= 10-step CPU baseline)
-timeout 900 python $R/bench.py --steps 20 --warmup 5 < /dev/null > $O/bench_line.json 2> $O/bench.err
+timeout 900 python $R/bench.py --full --steps 20 --warmup 5 < /dev/null > $O/bench_line.json 2> $O/bench.err
 cp $R/bench_extra.json $O/bench_extra.json          # the sidecar the line names (full per-family detail of every configuration)
 # 3. the same workload under kernel trace + stats (no CPU / GAP / extra legs: they are not the measured region)
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -o bench -- python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-gap --no-extra < /dev/null > $O/bench_line_profiled.json 2> $O/bench_prof.err

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 run() {
   tag=$1; shift
-  env "$@" python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-gap --no-extra --no-roofline $FLAGS 2>/dev/null > /tmp/fr_line.json
+  env "$@" python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-gap --no-extra --no-roofline $FLAGS 2>/dev/null > /tmp/fr_line.json
   python - "$tag" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/fr_line.json").read())

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 run() {
   tag=$1; shift
-  env "$@" python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-gap --no-extra 2>/dev/null | python -c "
+  env "$@" python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-gap --no-extra 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); f=d['roofline']['families']
 print('%-34s %.3f ms/step  fwd-rec launches/step %.0f  %.2f ms  bwd-rec %.2f ms' % ('$tag', d['ms_per_step'], f['lstm_recurrence'].get('launches_per_step', 0) or 0, f['lstm_recurrence']['ms_per_step'], f['lstm_recurrence_bwd']['ms_per_step']))"
