@@ -654,6 +654,8 @@ int yt8m_lstm_persist_fwd_on_bf16_pipe(int64_t B, int64_t H);
 /* CUs the following forward / backward launches may occupy (0: whole chip, -1: environment / default = whole chip forward, 128
  * backward).  Two forward launches of neighbouring layers run side by side when each takes half the chip. */
 int yt8m_lstm_persist_set_cus(int fwd_cus, int bwd_cus);
+/* The current choice of yt8m_lstm_persist_set_cus (-1: environment / default), so that a caller that caps for a while can restore it. */
+int yt8m_lstm_persist_get_cus(int* fwd_cus, int* bwd_cus);
 /* CUs the library leaves out of its "do these persistent launches fit the chip together" arithmetic: a data-parallel host reserves
  * room for the RCCL kernels of the gradient all-reduce that run beside the backward pass (launches that no longer fit side by side
  * are chained instead of spinning on a partly resident grid).  Env default: YT8M_PERSIST_RESERVED_CUS, else 0. */
@@ -829,6 +831,11 @@ int yt8m_lstm_stack_status(const yt8m_lstm_stack_desc* desc, void* scratch, yt8m
  * each layer's gradient all-reduce from this point instead of the end of the call (W/train.py:624-639 averages the tower
  * gradients after the whole backward pass). */
 int yt8m_lstm_stack_layer_done_wait(int layer, yt8m_stream_t stream);
+/* The library keeps TWO sets of per-device streams for the stack calls; the calling thread's following yt8m_lstm_stack_fwd / _bwd /
+ * _streams / _layer_done_wait use set `set` (0 or 1; 0 until changed), *previous receives the former choice (may be NULL).  Two stacks
+ * issued from different caller streams on different sets -- the forward and backward directions of a bidirectional RNN -- can run side
+ * by side; on one set their launches serialise on the shared layer streams.  Each stack still needs its own scratch. */
+int yt8m_lstm_stack_use_streams(int set, int* previous);
 /* One-shot host callback of the calling thread's next yt8m_lstm_stack_bwd, invoked right after its first backward recurrence is
  * enqueued, with the library's weight-gradient stream: what the callback enqueues there runs while that recurrence holds half the
  * chip and the stream has nothing else to do yet.  hook == NULL clears.  (The training step's own use of this window -- clip + Adam
@@ -891,6 +898,17 @@ int yt8m_lstm_steps_bwd(const float* gates, const float* Wh, int64_t ldw, const 
  * while yt8m_prof_enable(1) is active or with YT8M_NO_GRAPH set in the environment). */
 int yt8m_graph_cache_stats(int64_t* hits, int64_t* captures, int64_t* fallbacks, int64_t* entries);
 int yt8m_graph_cache_clear(void);
+
+/* ---- tf.reverse_sequence over the frame axis (bidirectional_dynamic_rnn: BiLstmModel, BiUniLstmModel) ---------------------------
+ * Per video b with n = num_frames[b] (clamped to [0, F]): row t of y is row n - 1 - t of x for t < n, row t of x otherwise.  The
+ * operation is its own inverse (and its own gradient).  Out of place; 16-byte accesses when the rows allow them.
+ * _u8: the reader's bytes, batch-major [B,F,D] -> [B,F,D] (x != y).
+ * _f32_tm: time-major fp32; H columns of x [F,B,ldx] -> columns [y_col0, y_col0 + H) of y [F,B,ldy]; nothing else of y is written
+ * (the two windows must not overlap). */
+int yt8m_reverse_sequence_u8(const uint8_t* x, const int32_t* num_frames, uint8_t* y, int64_t B, int64_t F, int64_t D,
+                             yt8m_stream_t stream);
+int yt8m_reverse_sequence_f32_tm(const float* x, int64_t ldx, const int32_t* num_frames, float* y, int64_t ldy, int64_t y_col0,
+                                 int64_t F, int64_t B, int64_t H, yt8m_stream_t stream);
 
 /* ---- masked softmax over frames + renormalise (lstm_attention_max_pooling_model.py:59-60) -------
  * act [B,F,A] -> w [B,F,A]: w = mask * softmax_F(act) / sum_F(mask * softmax_F(act)).  bwd: dact from dw. */

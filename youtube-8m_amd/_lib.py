@@ -193,6 +193,7 @@ SIGNATURES = {
     "yt8m_lstm_persist_placement_stats": (c_int, [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_int]),
     "yt8m_lstm_persist_fwd_on_bf16_pipe": (c_int, [c_int64, c_int64]),
     "yt8m_lstm_persist_set_cus": (c_int, [c_int, c_int]),
+    "yt8m_lstm_persist_get_cus": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "yt8m_lstm_persist_status": (c_int, [P, P]),
     "yt8m_lstm_persist_reserve_cus": (c_int, [c_int, ctypes.POINTER(c_int)]),
     "yt8m_lstm_persist_debug_fault": (c_int, [P, P]),
@@ -303,6 +304,9 @@ SIGNATURES = {
     "yt8m_gemm_h2_nt_grouped": (c_int, [c_int, ctypes.POINTER(GemmProblem), ctypes.POINTER(c_float), PP, PP, P, c_int64, P]),
     "yt8m_topk_rows": (c_int, [P, c_int64, c_int64, c_int, P, P, P]),
     "yt8m_perr_rows": (c_int, [P, P, c_int64, c_int64, P, P]),
+    "yt8m_reverse_sequence_u8": (c_int, [P, P, P, c_int64, c_int64, c_int64, P]),
+    "yt8m_reverse_sequence_f32_tm": (c_int, [P, c_int64, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, P]),
+    "yt8m_lstm_stack_use_streams": (c_int, [c_int, ctypes.POINTER(c_int)]),
 }
 
 # The ABI this host binds (include/yt8m_hip.h, yt8m_abi_version): workspace layouts and argument meanings, not just symbols.

@@ -2321,6 +2321,13 @@ extern "C" int yt8m_lstm_persist_set_cus(int fwd_cus, int bwd_cus) {
   return YT8M_OK;
 }
 
+// The values the last yt8m_lstm_persist_set_cus left (-1: environment / default): a caller that caps for a while restores them after.
+extern "C" int yt8m_lstm_persist_get_cus(int* fwd_cus, int* bwd_cus) {
+  if (fwd_cus) *fwd_cus = g_cap_fwd;
+  if (bwd_cus) *bwd_cus = g_cap_bwd;
+  return YT8M_OK;
+}
+
 // CUs to leave out of the gate's "do these persistent launches fit the chip together" arithmetic (0: none; the data-parallel
 // reducer reserves some for the RCCL kernels that run beside the backward pass).  Returns the previous value through *previous.
 extern "C" int yt8m_lstm_persist_reserve_cus(int cus, int* previous) {

@@ -252,7 +252,11 @@ struct DevState {
   int layers_done = 0;
 };
 std::mutex g_mu;
-DevState g_dev[16];
+// Two stream sets per device (yt8m_lstm_stack_use_streams): two stacks whose calls come from different caller streams -- the two
+// directions of a bidirectional RNN -- only overlap on the device when their layer / weight-gradient streams differ too.
+constexpr int NSETS = 2;
+DevState g_dev[NSETS][16];
+thread_local int g_set = 0;
 // One-shot host callback of the NEXT yt8m_lstm_stack_bwd call of this thread (yt8m_lstm_stack_set_prep_hook).
 thread_local yt8m_stream_hook g_prep_hook = nullptr;
 thread_local void* g_prep_user = nullptr;
@@ -288,7 +292,7 @@ int dev_state(int L, DevState** out) {
   int dev = 0;
   YT8M_HIP_CHECK(hipGetDevice(&dev));
   YT8M_REQUIRE(dev >= 0 && dev < 16, YT8M_E_BADARG, "device index out of range");
-  DevState& S = g_dev[dev];
+  DevState& S = g_dev[g_set][dev];
   for (int l = 0; l < L; ++l) { int rc = high_stream(S, &S.rs[l]); if (rc != YT8M_OK) return rc; }
   { int rc = plain_stream(&S.sw); if (rc != YT8M_OK) return rc; }
   if (knob("YT8M_STACK_DX_STREAM", 0))
@@ -360,6 +364,15 @@ extern "C" int yt8m_lstm_stack_streams(int L, yt8m_stream_t* layer_streams, yt8m
   return YT8M_OK;
 }
 
+// Selects the stream set (0 or 1) that the calling thread's following yt8m_lstm_stack_* calls use; returns the previous one through
+// *previous.  Set 1 is created on first use only: a process with one stack per step keeps the four streams of set 0.
+extern "C" int yt8m_lstm_stack_use_streams(int set, int* previous) {
+  YT8M_REQUIRE(set >= 0 && set < NSETS, YT8M_E_BADARG, "stream set must be 0 or 1");
+  if (previous) *previous = g_set;
+  g_set = set;
+  return YT8M_OK;
+}
+
 // Views into the tape after yt8m_lstm_stack_fwd: which = 0 outputs of the layer [F,B,H] (time-major; zeros beyond num_frames),
 // 1 final cell state c [B,H], 2 final hidden state h [B,H] (copy-through beyond num_frames), 3 gate activations [F,B,4H].
 extern "C" int yt8m_lstm_stack_view(const yt8m_lstm_stack_desc* desc, void* tape, int layer, int which, float** out) {
@@ -387,7 +400,7 @@ extern "C" int yt8m_lstm_stack_layer_done_wait(int layer, yt8m_stream_t stream) 
   YT8M_HIP_CHECK(hipGetDevice(&dev));
   YT8M_REQUIRE(dev >= 0 && dev < 16, YT8M_E_BADARG, "device index out of range");
   std::lock_guard<std::mutex> lk(g_mu);
-  DevState& S = g_dev[dev];
+  DevState& S = g_dev[g_set][dev];
   YT8M_REQUIRE(layer >= 0 && layer < S.layers_done && S.layer_done[layer], YT8M_E_BADARG,
                "no backward call on this device has recorded that layer");
   YT8M_HIP_CHECK(hipStreamWaitEvent(as_stream(stream), S.layer_done[layer], 0));
@@ -527,10 +540,15 @@ extern "C" int yt8m_lstm_stack_fwd(const yt8m_lstm_stack_desc* desc, const void*
   // 16-row tiles each on the f16 kernel) so that layer l's chunk c runs beside layer l - 1's chunk c + 1 (needs fwd_chunks > 1:
   // YT8M_LSTM_PERSIST_FWD_CHUNKS).  Measured: profiles/r6_sched_knobs.md.
   static const int fwd_half = knob("YT8M_STACK_FWD_HALF", 0);
-  struct CapGuard {
+  struct CapGuard {                                       // a cap the caller set stays (it is at least as tight); restored after
     bool on;
-    explicit CapGuard(bool o) : on(o) { if (on) yt8m_lstm_persist_set_cus(128, -1); }
-    ~CapGuard() { if (on) yt8m_lstm_persist_set_cus(-1, -1); }
+    int fwd = -1, bwd = -1;
+    explicit CapGuard(bool o) : on(o) {
+      if (!on) return;
+      yt8m_lstm_persist_get_cus(&fwd, &bwd);
+      yt8m_lstm_persist_set_cus(fwd > 0 ? std::min(fwd, 128) : 128, bwd);
+    }
+    ~CapGuard() { if (on) yt8m_lstm_persist_set_cus(fwd, bwd); }
   } cap_guard(fwd_half != 0 && P.L >= 2 && P.nf >= 2);
   for (int c = 0; c < P.nf; ++c) {
     const int64_t t0 = P.fp[c].t0, T = P.fp[c].T, M = T * B;

@@ -1,5 +1,6 @@
 // sequence.hip -- frame-axis kernels: BasicLSTM gate block, attention / assignment softmaxes, per-row top-k.
 // (gfx950, wave64; all HBM/latency-bound pointwise or short-reduction work, wave-shuffle reductions.)
+#include <algorithm>
 #include "common.h"
 
 namespace {
@@ -555,4 +556,93 @@ extern "C" int yt8m_perr_rows(const float* p, const uint8_t* labels, int64_t B, 
   }
   hipLaunchKernelGGL(perr_rows_kernel, dim3((unsigned)B), dim3(256), shm, s, p, labels, V, perr);
   return launch_status("perr_rows_kernel");
+}
+
+// ---- tf.reverse_sequence(x, num_frames, seq_axis = time) for bidirectional_dynamic_rnn (BiLstmModel / BiUniLstmModel) ----------------
+// y[t] = x[n - 1 - t] for t < n, x[t] for t >= n (n = num_frames[b] clamped to [0, F]): an involution, so the same pass is its own
+// gradient.  Pure bandwidth: one row copy per (t, b), 16-byte accesses when every row start is 16-byte aligned, a grid-stride loop
+// over (row, vector) items -- every thread moves one 16-byte vector per iteration, a row's vectors are adjacent threads.
+namespace {
+
+__device__ __forceinline__ int64_t rev_src(int64_t t, int64_t n) { return t < n ? n - 1 - t : t; }
+
+__device__ __forceinline__ int64_t clamp_n(const int32_t* nf, int64_t b, int64_t F) {
+  const int64_t n = nf[b];
+  return n < 0 ? 0 : (n > F ? F : n);
+}
+
+// batch-major bytes [B, F, D]: V = row bytes / 16 (vectorised) or D (bytes)
+template <typename V>
+__global__ __launch_bounds__(256) void reverse_u8_kernel(const V* __restrict__ x, const int32_t* __restrict__ nf, V* __restrict__ y,
+                                                        int64_t B, int64_t F, int64_t nv) {
+  const int64_t total = B * F * nv;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t row = i / nv, v = i - row * nv;          // row = b F + t
+    const int64_t b = row / F, t = row - b * F;
+    y[i] = x[(b * F + rev_src(t, clamp_n(nf, b, F))) * nv + v];
+  }
+}
+
+// time-major fp32 [F, B, *]: H columns of x (leading dimension ldx) -> columns [0, H) of y (leading dimension ldy); all counted in V units
+template <typename V>
+__global__ __launch_bounds__(256) void reverse_f32_tm_kernel(const V* __restrict__ x, int64_t ldx, const int32_t* __restrict__ nf,
+                                                            V* __restrict__ y, int64_t ldy, int64_t F, int64_t B, int64_t nv) {
+  const int64_t total = F * B * nv;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t row = i / nv, v = i - row * nv;          // row = t B + b
+    const int64_t t = row / B, b = row - t * B;
+    y[row * ldy + v] = x[(rev_src(t, clamp_n(nf, b, F)) * B + b) * ldx + v];
+  }
+}
+
+unsigned copy_grid(int64_t items) {
+  const int64_t blocks = (items + 255) / 256;
+  return (unsigned)std::min<int64_t>(blocks, 256 * 32);   // grid-stride beyond ~8 K blocks (32 per CU)
+}
+
+}  // namespace
+
+extern "C" int yt8m_reverse_sequence_u8(const uint8_t* x, const int32_t* num_frames, uint8_t* y, int64_t B, int64_t F, int64_t D,
+                                        yt8m_stream_t stream) {
+  YT8M_REQUIRE(B >= 0 && F >= 0 && D >= 0, YT8M_E_SHAPE, "negative dimension");
+  if (B * F * D == 0) return YT8M_OK;
+  YT8M_REQUIRE(x && num_frames && y, YT8M_E_BADARG, "null operand");
+  // out of place: the pass reads other rows than it writes, so the two [B,F,D] ranges must not overlap at all (as for _f32_tm)
+  const int64_t n = B * F * D;
+  YT8M_REQUIRE(x + n <= y || y + n <= x, YT8M_E_BADARG, "source and destination overlap (the reversal is out of place)");
+  hipStream_t s = as_stream(stream);
+  ProfScope prof(F_ELEMENTWISE, s, 0.0, 2.0 * (double)(B * F * D));
+  const bool vec = D % 16 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+  if (vec) {
+    const int64_t nv = D / 16;
+    hipLaunchKernelGGL(reverse_u8_kernel<uint4>, dim3(copy_grid(B * F * nv)), dim3(256), 0, s, reinterpret_cast<const uint4*>(x),
+                       num_frames, reinterpret_cast<uint4*>(y), B, F, nv);
+  } else {
+    hipLaunchKernelGGL(reverse_u8_kernel<uint8_t>, dim3(copy_grid(B * F * D)), dim3(256), 0, s, x, num_frames, y, B, F, D);
+  }
+  return launch_status("reverse_u8_kernel");
+}
+
+extern "C" int yt8m_reverse_sequence_f32_tm(const float* x, int64_t ldx, const int32_t* num_frames, float* y, int64_t ldy, int64_t y_col0,
+                                            int64_t F, int64_t B, int64_t H, yt8m_stream_t stream) {
+  YT8M_REQUIRE(F >= 0 && B >= 0 && H >= 0 && y_col0 >= 0, YT8M_E_SHAPE, "negative dimension or column offset");
+  YT8M_REQUIRE(ldx >= H && ldy >= y_col0 + H, YT8M_E_SHAPE, "leading dimension smaller than the row window");
+  if (F * B * H == 0) return YT8M_OK;
+  YT8M_REQUIRE(x && num_frames && y, YT8M_E_BADARG, "null operand");
+  float* yc = y + y_col0;
+  // source and destination windows must not overlap (the pass reads other rows than it writes)
+  const char *xb = reinterpret_cast<const char*>(x), *xe = reinterpret_cast<const char*>(x + ((F * B - 1) * ldx + H));
+  const char *yb = reinterpret_cast<const char*>(yc), *ye = reinterpret_cast<const char*>(yc + ((F * B - 1) * ldy + H));
+  YT8M_REQUIRE(xe <= yb || ye <= xb, YT8M_E_BADARG, "source and destination overlap");
+  hipStream_t s = as_stream(stream);
+  ProfScope prof(F_ELEMENTWISE, s, 0.0, 8.0 * (double)(F * B * H));
+  const bool vec = H % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 &&
+                   ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(yc)) & 15) == 0;
+  if (vec) {
+    hipLaunchKernelGGL(reverse_f32_tm_kernel<float4>, dim3(copy_grid(F * B * (H / 4))), dim3(256), 0, s, reinterpret_cast<const float4*>(x),
+                       ldx / 4, num_frames, reinterpret_cast<float4*>(yc), ldy / 4, F, B, H / 4);
+  } else {
+    hipLaunchKernelGGL(reverse_f32_tm_kernel<float>, dim3(copy_grid(F * B * H)), dim3(256), 0, s, x, ldx, num_frames, yc, ldy, F, B, H);
+  }
+  return launch_status("reverse_f32_tm_kernel");
 }

@@ -47,31 +47,41 @@ def _lib_u8_ok(D):
     return bool(_lib.lib().yt8m_u8_proj_supported(int(D)))
 
 
+def _stack_input(model_input, num_frames, dropping=False):
+    """What the native stack reads: the raw reader bytes [B,F,D] where its layer-0 projection consumes them directly (csrc/u8proj.hip:
+    exact bf16 operands, the dequantise / l2-normalise affine folded into the GEMM epilogue -- no fp32 [B,F,D] tensor, no transpose
+    copy), else float frames time-major [F,B,D] (dequantised first when they arrive as bytes)."""
+    if model_input.dtype == torch.uint8:
+        if _lib_u8_ok(model_input.shape[2]) and not dropping:
+            return model_input                                   # [B,F,D] uint8, re-ordered time-major by the conversion pass
+        return ops.dequant_l2norm(model_input, num_frames).transpose(0, 1).contiguous()
+    return model_input.transpose(0, 1).contiguous()              # [F,B,D]   (layout glue)
+
+
+def _lstm_cells(d_in, lstm_size, number_of_layers, multi=True):
+    """BasicLSTMCell variables in the current scope: multi_rnn_cell/cell_<l>/basic_lstm_cell/{weights,biases} for a MultiRNNCell,
+    basic_lstm_cell/{weights,biases} for a lone cell.  Returns [(W_l, b_l)]."""
+    g = get_default_graph()
+    wb = []
+    for l in range(number_of_layers):
+        scope = "multi_rnn_cell/cell_%d/basic_lstm_cell" % l if multi else "basic_lstm_cell"
+        W = g.get_variable(scope + "/weights", (d_in + lstm_size, 4 * lstm_size), xavier_uniform)
+        b = g.get_variable(scope + "/biases", (4 * lstm_size,), zeros)
+        wb.append((W, b))
+        d_in = lstm_size
+    return wb
+
+
 def _lstm_stack(model_input, num_frames, lstm_size, number_of_layers, scope="RNN", input_keep_prob=None):
     """MultiRNNCell([BasicLSTMCell(H, forget_bias=1.0)] * L) under tf.nn.dynamic_rnn inside variable_scope("RNN")
     (W/all_frame_models/lstm_model.py:34-47).  TF-1.0 variable names:
     RNN/multi_rnn_cell/cell_<l>/basic_lstm_cell/{weights,biases}.  Returns time-major outputs of the top layer
     and the per-layer final (c, h)."""
     g = get_default_graph()
-    if model_input.dtype == torch.uint8:
-        # raw reader bytes: the stack's layer-0 projection consumes them directly (csrc/u8proj.hip: exact bf16 operands, the
-        # dequantise / l2-normalise affine folded into the GEMM epilogue); no fp32 [B,F,D] tensor, no transpose copy
-        dropping = input_keep_prob is not None and float(input_keep_prob) < 1.0
-        if _lib_u8_ok(model_input.shape[2]) and not dropping:
-            x_tm = model_input                                   # [B,F,D] uint8, re-ordered time-major by the conversion pass
-        else:
-            x_tm = ops.dequant_l2norm(model_input, num_frames).transpose(0, 1).contiguous()
-    else:
-        x_tm = model_input.transpose(0, 1).contiguous()          # [F,B,D]   (layout glue)
-    wb = []
-    d_in = model_input.shape[2]
+    dropping = input_keep_prob is not None and float(input_keep_prob) < 1.0
+    x_tm = _stack_input(model_input, num_frames, dropping)
     with g.variable_scope(scope):
-        for l in range(number_of_layers):
-            scope = "multi_rnn_cell/cell_%d/basic_lstm_cell" % l
-            W = g.get_variable(scope + "/weights", (d_in + lstm_size, 4 * lstm_size), xavier_uniform)
-            b = g.get_variable(scope + "/biases", (4 * lstm_size,), zeros)
-            wb.append((W, b))
-            d_in = lstm_size
+        wb = _lstm_cells(model_input.shape[2], lstm_size, number_of_layers)
     # all layers in one op: layer l+1 works on time chunk c while layer l is already in chunk c+1 (seq_ops._LstmStack)
     return seq_ops.lstm_stack(x_tm, num_frames, wb, forget_bias=1.0, chunks=FLAGS.lstm_pipeline_chunks,
                               input_keep_prob=input_keep_prob, bf16=FLAGS.compute_dtype == "bfloat16")
@@ -112,6 +122,63 @@ class LstmModel(models.BaseModel):
         state = torch.cat([t for pair in finals for t in pair], dim=1)
         return _head()().create_model(model_input=state, original_input=model_input, vocab_size=vocab_size,
                                       **unused_params)
+
+
+def _bidirectional_stacks(model_input, num_frames, lstm_size, number_of_layers, multi):
+    """tf.nn.bidirectional_dynamic_rnn(cell_fw, cell_bw, x, sequence_length=num_frames) inside variable_scope("RNN") (TF 1.0: the
+    directions live in bidirectional_rnn/fw and bidirectional_rnn/bw).  The bw direction is the ordinary stack on
+    reverse_sequence(x, num_frames): on the byte path the reader's bytes are reversed (csrc/sequence.hip) and go to the stack's byte
+    product as they are, else the float frames are reversed time-major.  Its final state is the state after original frame 0; its
+    outputs come back in REVERSED time (callers that need them in frame order reverse them again: seq_ops.bi_concat).
+    Returns ((out_fw, finals_fw), (out_bw_reversed, finals_bw))."""
+    g = get_default_graph()
+    x_fw = _stack_input(model_input, num_frames)
+    x_bw = seq_ops.reverse_sequence_u8(x_fw, num_frames) if x_fw.dtype == torch.uint8 else seq_ops.reverse_sequence_tm(x_fw, num_frames)
+    d_in = model_input.shape[2]
+    with g.variable_scope("RNN"):
+        with g.variable_scope("bidirectional_rnn"):
+            with g.variable_scope("fw"):
+                wb_fw = _lstm_cells(d_in, lstm_size, number_of_layers, multi)
+            with g.variable_scope("bw"):
+                wb_bw = _lstm_cells(d_in, lstm_size, number_of_layers, multi)
+    return seq_ops.bidirectional_lstm_stacks(x_fw, x_bw, num_frames, wb_fw, wb_bw, forget_bias=1.0, chunks=FLAGS.lstm_pipeline_chunks,
+                                             bf16=FLAGS.compute_dtype == "bfloat16")
+
+
+class BiLstmModel(models.BaseModel):
+    """W/all_frame_models/bilstm_model.py:13-60: MultiRNNCell([BasicLSTMCell(H)] * L, state_is_tuple=False) per direction under
+    tf.nn.bidirectional_dynamic_rnn in variable_scope("RNN"); the head reads [state_fw || state_bw], each [c0||h0||c1||h1...]
+    (2 L 2H wide).  Variable names as TF 1.0 builds them, written from memory (as SURVEY.md Appendix A):
+    RNN/bidirectional_rnn/{fw,bw}/multi_rnn_cell/cell_<l>/basic_lstm_cell/{weights,biases} (pinned in tests/test_bilstm_host.py).
+    accepts_quantized_input: both directions' stacks read the reader's bytes (the bw one reversed per video)."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, **unused_params):
+        lstm_size = int(FLAGS.lstm_cells)
+        (_, fin_fw), (_, fin_bw) = _bidirectional_stacks(model_input, num_frames, lstm_size, FLAGS.lstm_layers, multi=True)
+        state = torch.cat([t for pair in fin_fw + fin_bw for t in pair], dim=1)
+        return _head()().create_model(model_input=state, original_input=model_input, vocab_size=vocab_size, **unused_params)
+
+
+class BiUniLstmModel(models.BaseModel):
+    """W/all_frame_models/biunilstm_model.py:13-60: one BasicLSTMCell(H) per direction under tf.nn.bidirectional_dynamic_rnn, their
+    outputs concatenated ([B,F,2H]: out_fw || reverse_sequence(out_bw)), a third BasicLSTMCell(H) over that (dynamic_rnn with the
+    same sequence_length); the head reads [c_fw||h_fw||c_bw||h_bw||c_2||h_2] (6H).  Variable names (TF 1.0, from memory):
+    RNN/bidirectional_rnn/{fw,bw}/basic_lstm_cell/{weights,biases} and, for the third cell -- a dynamic_rnn without a scope argument,
+    which this project maps to no extra scope (as for LstmModel) -- RNN/basic_lstm_cell/{weights,biases}."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, **unused_params):
+        lstm_size = int(FLAGS.lstm_cells)
+        (out_fw, fin_fw), (out_bw, fin_bw) = _bidirectional_stacks(model_input, num_frames, lstm_size, 1, multi=False)
+        l1 = seq_ops.bi_concat(out_fw, out_bw, num_frames)          # [F,B,2H] time-major, bw half back in frame order
+        g = get_default_graph()
+        with g.variable_scope("RNN"):
+            wb2 = _lstm_cells(2 * lstm_size, lstm_size, 1, multi=False)
+        _, fin2 = seq_ops.lstm_stack(l1, num_frames, wb2, forget_bias=1.0, chunks=FLAGS.lstm_pipeline_chunks,
+                                     bf16=FLAGS.compute_dtype == "bfloat16", slot=2)
+        state = torch.cat([t for pair in fin_fw + fin_bw + fin2 for t in pair], dim=1)
+        return _head()().create_model(model_input=state, original_input=model_input, vocab_size=vocab_size, **unused_params)
 
 
 class LstmMemoryModel(models.BaseModel):

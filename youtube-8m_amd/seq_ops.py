@@ -493,12 +493,16 @@ def _stack_desc(B, F, D, H, L, u8, forget_bias, need_dx, bf16=False, keep_prob=N
     return d
 
 
-def _stack_scratch(dev, main, desc):
+def _stack_scratch(dev, main, desc, slot=0):
     # (the size is part of the key: the library's layout depends on its knobs too -- a test that flips YT8M_STACK_H2 in-process must
-    # not be handed the other layout's buffer)
+    # not be handed the other layout's buffer.)  `slot`: stacks that are alive in one step together -- the two directions of a
+    # bidirectional RNN -- own separate buffers even when their shapes agree: the scratch carries the forward's scale words into the
+    # backward call, so a shared one would hand the second stack's weight maxima to the first one's backward pass
     need = _lib.lib().yt8m_lstm_stack_scratch_bytes(ctypes.byref(desc))
     key = (dev.index, main.cuda_stream, need) + tuple(getattr(desc, f) for f, _ in desc._fields_
                                                       if f not in ("forget_bias", "input_keep_prob", "reserved0", "dropout_seed"))
+    if slot:
+        key += (("slot", int(slot)),)
     ent = _STACK_SCRATCH.get(key)
     if ent is not None:
         _STACK_SCRATCH[key] = _STACK_SCRATCH.pop(key)                # least recently USED goes first (dicts keep insertion order)
@@ -625,6 +629,25 @@ def _early_optimizer_hook(graph, lib):
     return e
 
 
+class _StreamSet(object):
+    """Selects the library's stream set for the native stack calls inside the block (yt8m_lstm_stack_use_streams; 0 = the default)."""
+
+    def __init__(self, lib, stream_set):
+        self.lib, self.set, self.prev = lib, int(stream_set), None
+
+    def __enter__(self):
+        if self.set:
+            prev = ctypes.c_int()
+            _lib.check(self.lib.yt8m_lstm_stack_use_streams(self.set, ctypes.byref(prev)))
+            self.prev = prev.value
+        return self
+
+    def __exit__(self, *exc):
+        if self.prev is not None:
+            _lib.check(self.lib.yt8m_lstm_stack_use_streams(self.prev, None))
+        return False
+
+
 class _LstmStack(torch.autograd.Function):
     """MultiRNNCell([BasicLSTMCell] * L) under tf.nn.dynamic_rnn (W/all_frame_models/lstm_model.py:34-47), time-major, as ONE
     op so that the layers can be pipelined: the sequence is cut into time chunks; layer l's hoisted input projection of
@@ -649,7 +672,7 @@ class _LstmStack(torch.autograd.Function):
       -> (out_top [F,B,H], c_0, h_0, ..., c_{L-1}, h_{L-1})"""
 
     @staticmethod
-    def forward(ctx, x_tm, token, num_frames, forget_bias, chunks, input_keep_prob, seeds, bf16, *wb):
+    def forward(ctx, x_tm, token, num_frames, forget_bias, chunks, input_keep_prob, seeds, bf16, slot, stream_set, *wb):
         lib = _lib.lib()
         nf = _nf(num_frames)
         q_raw = None
@@ -681,7 +704,7 @@ class _LstmStack(torch.autograd.Function):
             desc = _stack_desc(B, F, D0, Hs[0], L, u8, forget_bias, (not u8) and bool(ctx.needs_input_grad[0]), bf16=bool(bf16),
                                keep_prob=input_keep_prob if drop_ else None, seeds=seeds if drop_ else None)
             if (u8 or x_tm.dtype == torch.float32) and wb[0].data.shape[0] == D0 + Hs[0] and lib.yt8m_lstm_stack_supported(ctypes.byref(desc)):
-                return _LstmStack._native_forward(ctx, lib, desc, x_tm, nf, wb)
+                return _LstmStack._native_forward(ctx, lib, desc, x_tm, nf, wb, slot, stream_set)
         if own and PERSIST_FWD_CHUNKS > 0:
             parts = _chunks(F, PERSIST_FWD_CHUNKS)
         bwd_parts = _bwd_parts(F, _chunks(F, chunks), own)
@@ -745,7 +768,7 @@ class _LstmStack(torch.autograd.Function):
                 big = lib.yt8m_lstm_persist_workspace_bytes_steps(B, H, tmax)
                 if big <= PERSIST_STEP_IMAGES_MAX_BYTES:
                     pws = big
-            st["pws"] = _persist_ws(dev, main, l, pws) if pws else None
+            st["pws"] = _persist_ws(dev, main, (slot, l) if slot else l, pws) if pws else None
             layers.append(st)
             inp = st["out"]
         start = torch.cuda.Event()
@@ -855,7 +878,7 @@ class _LstmStack(torch.autograd.Function):
         return tuple(outs)
 
     @staticmethod
-    def _native_forward(ctx, lib, desc, x, nf, wb):
+    def _native_forward(ctx, lib, desc, x, nf, wb, slot=0, stream_set=0):
         x = x.contiguous()
         _dev(x)
         dev = x.device
@@ -865,15 +888,17 @@ class _LstmStack(torch.autograd.Function):
         for l, w in enumerate(Ws):
             assert w.data.is_contiguous() and tuple(w.data.shape) == ((desc.D if l == 0 else H) + H, 4 * H), "cell weights must be [in + H, 4H]"
         tape = torch.empty(lib.yt8m_lstm_stack_tape_bytes(ctypes.byref(desc)), dtype=torch.uint8, device=dev)
-        scratch = _stack_scratch(dev, main, desc)
+        scratch = _stack_scratch(dev, main, desc, slot)
         Wp = (ctypes.c_void_p * L)(*[w.data.data_ptr() for w in Ws])
         bp = (ctypes.c_void_p * L)(*[b.data.data_ptr() for b in bs])
-        _lib.check(lib.yt8m_lstm_stack_fwd(ctypes.byref(desc), _p(x), _p(nf), Wp, bp, _p(tape), tape.numel(), _p(scratch), scratch.numel(),
-                                           _stream()))
+        with _StreamSet(lib, stream_set):
+            _lib.check(lib.yt8m_lstm_stack_fwd(ctypes.byref(desc), _p(x), _p(nf), Wp, bp, _p(tape), tape.numel(), _p(scratch), scratch.numel(),
+                                               _stream()))
         NATIVE_CALLS["fwd"] += 1
         if PERSIST_CHECK:
             _check_stack(scratch, main, desc)
         ctx.native = (desc, tape, scratch, x, nf, Ws, bs)
+        ctx.stream_set = stream_set
         g_ = Ws[0]._graph
         if g_ is not None and torch.is_grad_enabled():
             # the stack's backward pass will follow whatever consumes these outputs: ops that run before it in the backward pass (the
@@ -917,14 +942,24 @@ class _LstmStack(torch.autograd.Function):
         early = _early_optimizer_hook(Ws[0]._graph, lib)
         ok = False
         try:
-            _lib.check(lib.yt8m_lstm_stack_bwd(ctypes.byref(desc), _p(x), _p(nf), Wp, _p(tape), tape.numel(), _p(scratch), scratch.numel(),
-                                               _p(dout_top), arr(dcs), arr(dhs), arr(dW), arr(db), bW, bb, _p(dx), _stream()))
+            with _StreamSet(lib, getattr(ctx, "stream_set", 0)):
+                _lib.check(lib.yt8m_lstm_stack_bwd(ctypes.byref(desc), _p(x), _p(nf), Wp, _p(tape), tape.numel(), _p(scratch), scratch.numel(),
+                                                   _p(dout_top), arr(dcs), arr(dhs), arr(dW), arr(db), bW, bb, _p(dx), _stream()))
             ok = True
         finally:
             if early is not None:
                 early.finish(lib, ok)
         NATIVE_CALLS["bwd"] += 1
         ops.join_side_work(Ws[0]._graph)                             # gradients an earlier op left on a side stream: visible from here on
+        g_ = Ws[0]._graph
+        if getattr(ctx, "stream_set", 0) and g_ is not None:
+            # the overlapped bw direction (bidirectional_lstm_stacks): autograd runs this backward on the side stream its forward ran on,
+            # and nothing else orders the caller's stream after it -- no leaf gradient comes out of it.  Its weight / bias gradients (and
+            # the early clip + Adam it may have enqueued) are joined like any other side work: by the next stack backward or by
+            # TrainGraph.step before the optimiser pass (ops.join_side_work)
+            if getattr(g_, "side_pending", None) is None:
+                g_.side_pending = []
+            g_.side_pending.append(torch.cuda.current_stream(dev))
         if PERSIST_CHECK:
             _check_stack(scratch, torch.cuda.current_stream(dev), desc)
         g = Ws[0]._graph
@@ -944,7 +979,7 @@ class _LstmStack(torch.autograd.Function):
             for v in list(Ws) + list(bs):
                 if v.grad is not None:
                     v.grad_done()
-        return (dx, None, None, None, None, None, None, None) + (None,) * (2 * L)
+        return (dx, None, None, None, None, None, None, None, None, None) + (None,) * (2 * L)
 
     @staticmethod
     def backward(ctx, dout_top, *dfinal):
@@ -1108,19 +1143,143 @@ class _LstmStack(torch.autograd.Function):
                 st["W"].grad_done()
             if st["b"].grad is not None:
                 st["b"].grad_done()
-        return (dx, None, None, None, None, None, None, None) + (None,) * (2 * L)
+        return (dx, None, None, None, None, None, None, None, None, None) + (None,) * (2 * L)
 
 
-def lstm_stack(x_tm, num_frames, weights_biases, forget_bias=1.0, chunks=4, input_keep_prob=None, seeds=None, bf16=False):
+def lstm_stack(x_tm, num_frames, weights_biases, forget_bias=1.0, chunks=4, input_keep_prob=None, seeds=None, bf16=False, slot=0,
+               stream_set=0):
     """weights_biases: [(W_0, b_0), ...] Variables.  Returns (out_top, [(c_l, h_l), ...]).
     input_keep_prob < 1: DropoutWrapper(input_keep_prob) on every layer; seeds = one Philox key per layer (default: the
-    graph's random stream)."""
+    graph's random stream).  slot: which of the stack's cached buffers (native scratch, persistent workspaces) this stack owns --
+    stacks alive in one step together take different slots.  stream_set: the library's stream set of the native calls (0 or 1,
+    see bidirectional_lstm_stacks)."""
     flat = [v for wb in weights_biases for v in wb]
     if input_keep_prob is not None and float(input_keep_prob) < 1.0 and seeds is None:
         seeds = [flat[0]._graph.next_random_seed() for _ in weights_biases]
     res = _LstmStack.apply(x_tm, _token(flat[0]._graph), num_frames, forget_bias, int(chunks), input_keep_prob,
-                           tuple(seeds) if seeds is not None else None, bool(bf16), *flat)
+                           tuple(seeds) if seeds is not None else None, bool(bf16), int(slot), int(stream_set), *flat)
     return res[0], [(res[1 + 2 * l], res[2 + 2 * l]) for l in range(len(weights_biases))]
+
+
+# ---- tf.nn.bidirectional_dynamic_rnn: time reversal per video + the two directions' stacks -----------------------------------------
+def reverse_sequence_u8(q, num_frames):
+    """tf.reverse_sequence(q, num_frames, seq_axis=1) on the reader's bytes [B,F,D] (csrc/sequence.hip): frames 0 .. n_b - 1 of
+    every video reversed, the padding frames left where they are.  The bytes are data: no gradient."""
+    _dev(q)
+    q = q.contiguous()
+    B, F, D = q.shape
+    out = torch.empty_like(q)
+    nf = _nf(num_frames.to(q.device))
+    _lib.check(_lib.lib().yt8m_reverse_sequence_u8(_p(q), _p(nf), _p(out), B, F, D, _stream()))
+    return out
+
+
+def _reverse_tm_into(x, nf, out, col0):
+    """x [F,B,H] fp32 (rows contiguous, any row stride) reversed per video into columns [col0, col0 + H) of out [F,B,ldy]."""
+    F, B, H = x.shape
+    assert x.stride(2) == 1 and x.stride(0) == B * x.stride(1) and out.stride(2) == 1 and out.stride(0) == B * out.stride(1)
+    _lib.check(_lib.lib().yt8m_reverse_sequence_f32_tm(_p(x), x.stride(1), _p(nf), _p(out), out.stride(1), int(col0), F, B, H, _stream()))
+    return out
+
+
+class _ReverseTM(torch.autograd.Function):
+    """tf.reverse_sequence on time-major fp32 [F,B,H]; its own gradient (the reversal is an involution)."""
+
+    @staticmethod
+    def forward(ctx, x, num_frames):
+        _dev(x)
+        x = _f32c(x)
+        ctx.nf = _nf(num_frames.to(x.device))
+        return _reverse_tm_into(x, ctx.nf, torch.empty_like(x), 0)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = _f32c(g)
+        return _reverse_tm_into(g, ctx.nf, torch.empty_like(g), 0), None
+
+
+def reverse_sequence_tm(x, num_frames):
+    return _ReverseTM.apply(x, num_frames)
+
+
+class _BiConcat(torch.autograd.Function):
+    """concat([out_fw, reverse_sequence(out_bw)], axis=2) time-major -> [F,B,2H]: the bw half is written reversed straight into its
+    column window by the reversal kernel (no cat / flip); backward: the left half of the gradient as is, the right half reversed back
+    into a contiguous [F,B,H] by the same kernel."""
+
+    @staticmethod
+    def forward(ctx, out_fw, out_bw, num_frames):
+        _dev(out_fw, out_bw)
+        F, B, H = out_fw.shape
+        ctx.nf, ctx.H = _nf(num_frames.to(out_fw.device)), H
+        l1 = torch.empty((F, B, 2 * H), dtype=torch.float32, device=out_fw.device)
+        l1[:, :, :H].copy_(out_fw)                                  # (layout glue)
+        _reverse_tm_into(_f32c(out_bw), ctx.nf, l1, H)
+        return l1
+
+    @staticmethod
+    def backward(ctx, g):
+        g = _f32c(g)
+        F, B, _ = g.shape
+        H = ctx.H
+        d_fw = g[:, :, :H].contiguous()
+        d_bw = _reverse_tm_into(g[:, :, H:], ctx.nf, torch.empty((F, B, H), dtype=torch.float32, device=g.device), 0)
+        return d_fw, d_bw, None
+
+
+def bi_concat(out_fw, out_bw, num_frames):
+    return _BiConcat.apply(out_fw, out_bw, num_frames)
+
+
+# Overlapped directions (opt-in; measured in DESIGN_LOG.md "BiLstmModel"): the bw stack is issued from a side stream on the library's
+# second stream set, both directions' forward recurrences capped at half the chip.  The library's residency gate (csrc/lstm_persist.hip,
+# PersistGate) admits a persistent launch beside the running ones only while all of them fit the chip together, so two capped
+# recurrences run side by side and nothing whole-chip ever overlaps another persistent launch.
+BI_OVERLAP = _os.environ.get("YT8M_BI_OVERLAP", "0") != "0"
+BI_OVERLAP_RUNS = [0]          # how often the overlapped form ran (tests assert that it engaged)
+_BI_SIDE = {}
+
+
+def _bi_side_stream(dev):
+    st = _BI_SIDE.get(dev)
+    if st is None:
+        st = torch.cuda.Stream(device=dev, priority=REC_STREAM_PRIORITY)
+        _BI_SIDE[dev] = st
+    return st
+
+
+def bidirectional_lstm_stacks(x_fw, x_bw, num_frames, wb_fw, wb_bw, forget_bias=1.0, chunks=4, bf16=False, overlap=None):
+    """The two directions of tf.nn.bidirectional_dynamic_rnn over already reversed bw input (reverse_sequence_u8 / _tm): two independent
+    stacks that own separate scratch (slot 0 / 1).  overlap (default YT8M_BI_OVERLAP): bw on a side stream and the library's second
+    stream set, forward recurrences of both capped at half the chip; False: one after the other on the caller's stream (the reference
+    form).  Returns ((out_fw, finals_fw), (out_bw_reversed_time, finals_bw))."""
+    if overlap is None:
+        overlap = BI_OVERLAP
+    kw = dict(forget_bias=forget_bias, chunks=chunks, bf16=bf16)
+    if not overlap:
+        return lstm_stack(x_fw, num_frames, wb_fw, slot=0, **kw), lstm_stack(x_bw, num_frames, wb_bw, slot=1, **kw)
+    lib = _lib.lib()
+    dev = x_fw.device
+    main = torch.cuda.current_stream(dev)
+    side = _bi_side_stream(dev)
+    side.wait_stream(main)
+    half = torch.cuda.get_device_properties(dev).multi_processor_count // 2
+    prev_f, prev_b = ctypes.c_int(-1), ctypes.c_int(-1)
+    _lib.check(lib.yt8m_lstm_persist_get_cus(ctypes.byref(prev_f), ctypes.byref(prev_b)))
+    # (a tighter cap the caller set stays; the backward launches keep theirs -- half the chip by default)
+    _lib.check(lib.yt8m_lstm_persist_set_cus(min(prev_f.value, half) if prev_f.value > 0 else half, prev_b.value))
+    try:
+        fw = lstm_stack(x_fw, num_frames, wb_fw, slot=0, stream_set=0, **kw)
+        with torch.cuda.stream(side):
+            bw = lstm_stack(x_bw, num_frames, wb_bw, slot=1, stream_set=1, **kw)
+    finally:
+        _lib.check(lib.yt8m_lstm_persist_set_cus(prev_f.value, prev_b.value))   # process-wide: the caller's values, whatever happens
+    main.wait_stream(side)
+    for t in [bw[0]] + [v for pair in bw[1] for v in pair]:
+        t.record_stream(main)                                        # made on the side stream, read on the caller's
+    x_bw.record_stream(side)
+    BI_OVERLAP_RUNS[0] += 1
+    return fw, bw
 
 
 class _AttnSoftmax(torch.autograd.Function):
