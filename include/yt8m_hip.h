@@ -26,6 +26,9 @@ enum yt8m_label_dtype { YT8M_LABEL_U8 = 0, YT8M_LABEL_F32 = 1 };
  * would change behaviour), yt8m_gemm_auto_grouped / yt8m_lstm_stack_* consult the resident weight-image table (yt8m_wimg_*).
  * 4 since round 6: yt8m_lstm_stack_desc grew (input_keep_prob, dropout_seed[8]: a smaller struct from an older host would be read past
  * its end); yt8m_gemm_auto_* read YT8M_GEMM_ROLE_DW in transA (without it a transA product no longer takes the three-f16-product form).
+ * Still 4 after two opt-in entry points left (the K-split pair switch of the f16 LSTM backward recurrence and the persistent GRU
+ * backward): no remaining entry point changed its arguments, its meaning or a workspace layout, and a host that still binds a removed
+ * symbol fails at bind time.
  * A host must check it. */
 int yt8m_abi_version(void);
 const char* yt8m_last_error(void);
@@ -715,30 +718,21 @@ int yt8m_lstm_persist_bwd_h2(const float* gates, const float* Wh, int64_t ldw, c
 int yt8m_lstm_persist_bwd_on_f16_pipe(int64_t B, int64_t H);
 /* Round 6: tf.contrib.rnn.GRUCell under tf.nn.dynamic_rnn as ONE launch per (layer, time range) and direction on the persistent
  * recurrences' exchange protocol (csrc/gru_persist.inl; reference W/all_frame_models/gru_pooling_model.py:34-47 -- replaces the
- * 2 + 3 launches per time step of yt8m_gru_layer_fwd / _bwd).  A GRU step is two dependent products, so a step is two half-steps of the
+ * 2 launches per time step of yt8m_gru_layer_fwd).  A GRU step is two dependent products, so a step is two half-steps of the
  * exchange: the workspace (yt8m_gru_persist_workspace_bytes) holds one exchange image per half-step.
- *   fwd: zg [F,B,2H], zc [F,B,H] = hoisted input projections + biases on entry, activations r|u, c on exit; Wg_h / Wc_h = the recurrent
- *        rows of gates/weights [H, >= 2H] and candidate/weights [H, >= H]; hs [F+1,B,H] with hs[t0] given; rh [F,B,H] = r * h_{t-1};
- *        out [F,B,H] or NULL; rows with t >= num_frames[b] copy their state through and emit zeros.
- *   bwd: steps t0 + T - 1 .. t0; work [B,H] = dL/dh entering the range's last step (in) / dL/dh_{t0-1} (out); writes dzg, dzc.
- * Results equal the per-step entry points up to the K summation order of the recurrent products and the v_exp / v_rcp gate functions
+ *   zg [F,B,2H], zc [F,B,H] = hoisted input projections + biases on entry, activations r|u, c on exit; Wg_h / Wc_h = the recurrent
+ *   rows of gates/weights [H, >= 2H] and candidate/weights [H, >= H]; hs [F+1,B,H] with hs[t0] given; rh [F,B,H] = r * h_{t-1};
+ *   out [F,B,H] or NULL; rows with t >= num_frames[b] copy their state through and emit zeros.
+ * Results equal yt8m_gru_layer_fwd up to the K summation order of the recurrent products and the v_exp / v_rcp gate functions
  * (<= ~1.5e-7 absolute per activation).  yt8m_lstm_persist_status(workspace) reports a timed-out launch, as for the LSTM kernels.
- * Measured at B = 128, H = 1024 (profiles/r6_gru_persist.txt): forward 13.9 us/step against 17.6 for the per-step launches (the host
- * mirror takes it by default), backward 29.0 against 20.3 (opt-in: YT8M_GRU_PERSIST_BWD=1 in the host mirror). */
+ * Measured at B = 128, H = 1024 (profiles/r6_gru_persist.txt): 13.9 us/step against 17.6 for the per-step launches (the host mirror
+ * takes it by default).  The backward runs on the per-step kernels (yt8m_gru_layer_bwd): a persistent form ran at 29.0 us/step
+ * against their 20.3 and was removed. */
 int yt8m_gru_persist_supported(int64_t B, int64_t H);
 int64_t yt8m_gru_persist_workspace_bytes(int64_t B, int64_t H, int64_t T);
 int yt8m_gru_persist_fwd(float* zg, float* zc, const float* Wg_h, int64_t ldg, const float* Wc_h, int64_t ldc, float* hs, float* rh,
                          float* out, const int32_t* num_frames, int64_t t0, int64_t T, int64_t B, int64_t H, void* workspace,
                          int64_t workspace_bytes, yt8m_stream_t stream);
-int yt8m_gru_persist_bwd(const float* zg, const float* zc, const float* Wg_h, int64_t ldg, const float* Wc_h, int64_t ldc,
-                         const float* hs, const float* dout, float* dzg, float* dzc, float* work, const int32_t* num_frames, int64_t t0,
-                         int64_t T, int64_t B, int64_t H, void* workspace, int64_t workspace_bytes, yt8m_stream_t stream);
-/* Round 6: the f16 backward recurrence as K-SPLIT WORKGROUP PAIRS -- the two workgroups that share a line of gates each reduce HALF of
- * K for the pair's 32 units (half the dz a CU draws per step) and hand the partner its partial tile through tagged 8-byte granules.
- * Opt-in (stand-alone 13.7 vs 14.4 us/step, but slower inside the headline step where two recurrences and the dW products share the
- * chip: profiles/r6_recur_ab.txt block 4); available wherever the f16 form runs with <= 8 tiles per workgroup; results equal the unpaired form to fp32 rounding (one more
- * level in the fixed summation tree).  mode -1: environment (YT8M_PERSIST_BWD_PAIR, default 0), 0: off, 1: on.  Process-wide. */
-int yt8m_lstm_persist_set_pair(int mode);
 /* yt8m_lstm_persist_bwd (wh_absmax NULL) / yt8m_lstm_persist_bwd_h2 that also measures, while it writes dz, what the products after it
  * would otherwise measure in passes over dz (105-210 MB each at the headline shape): rowmax[t B + b] = max |dz[t, b, :]| as float bits ([F B]
  * words by absolute frame row, zeroed by the caller; the operand of yt8m_h2_split_rowmax) and / or partmax = max |dz| of the launch (one

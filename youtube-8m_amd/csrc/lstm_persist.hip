@@ -40,29 +40,17 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef YT8M_FWD_POLLQ
-#define YT8M_FWD_POLLQ 2     // where in an item (quarters of its MFMA block) the state of the item PD ahead is requested
-#endif
-#ifndef YT8M_AUX_ST
-#define YT8M_AUX_ST 17
-#endif
-#ifndef YT8M_EPI_PRIO
-#define YT8M_EPI_PRIO 3
-#endif
-#ifndef YT8M_AUX_LD
-#define YT8M_AUX_LD 17
-#endif
+constexpr int FWD_POLLQ = 2;    // where in an item (quarters of its MFMA block) the state of the item PD ahead is requested
+constexpr int EPI_PRIO = 3;     // s_setprio of the epilogue waves
 // aux 17 = sc0 sc1: write-through store / coherent load (MI355X_MICROARCH.md, inter-workgroup visibility)
+constexpr int AUX_STORE = 17, AUX_LOAD = 17;
 constexpr long long SPIN_TIMEOUT = 300000000;  // wall_clock64 ticks (100 MHz): 3 s
 constexpr int CTL_HDR = 32;                    // control block: [0] error word, counters from word 32
 constexpr int CTL_STICKY = 32;                 // words between the sticky error word (workspace word 0) and ctl[0]
-#ifndef YT8M_PERSIST_SHARDS
-#define YT8M_PERSIST_SHARDS 8
-#endif
 // Arrival counter shards per tile, one 128-byte line each (the single polling wave of a workgroup reads all of them with one
 // load instruction).  Measured at B = 128, H = 1024: 8 and 16 shards run alike (10.6 us / step forward), 64 are slower (12.4:
 // the poll costs more than the shorter add queues save).
-constexpr int NSH = YT8M_PERSIST_SHARDS;
+constexpr int NSH = 8;
 
 struct PersistFwdArgs {
   float* z;             // [F,B,4H] hoisted input projection + bias on entry, gate activations on exit
@@ -184,17 +172,12 @@ __global__ __launch_bounds__(256) void hx_pack_kernel(const float* __restrict__ 
 // the per-step kernels -- the epilogue is a single wave's dependent chain on the critical path of the state exchange, and the
 // exact forms cost ~10x the instructions.  Absolute error <= ~1.5e-7 per value (checked against the exact kernels and the fp64
 // oracle by the parity tests; north_star tolerance 1e-3).
-#ifdef YT8M_EPI_FAKE   // timing experiment only (wrong results): how much of the chain is the gate math?
-__device__ __forceinline__ float fast_sigmoid(float x) { return 0.5f + 0.01f * x; }
-__device__ __forceinline__ float fast_tanh(float x) { return 0.01f * x; }
-#else
 __device__ __forceinline__ float fast_sigmoid(float x) {
   return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
 }
 __device__ __forceinline__ float fast_tanh(float x) {
   return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.8853900817779268f * x));
 }
-#endif
 
 // value of lane + N within a row of 16 lanes (DPP row_shl: one VALU op; __shfl_down is a ds_bpermute round trip through LDS)
 template <int N>
@@ -303,7 +286,7 @@ __global__ __launch_bounds__(768) void lstm_persist_fwd_kernel(PersistFwdArgs a)
       const unsigned base = (unsigned)(T * QH) * 1024u + lane_off;
 #pragma unroll
       for (int qg = 0; qg < NQ; ++qg)
-        A[qg] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(hxr, (int)(base + (unsigned)qg * 1024u), 0, SH ? 0 : YT8M_AUX_LD));
+        A[qg] = as_f4(__builtin_amdgcn_raw_buffer_load_b128(hxr, (int)(base + (unsigned)qg * 1024u), 0, SH ? 0 : AUX_LOAD));
     };
     float4 A0[NQ], A1[NQ], A2[NQ];
     if (PD >= 1) load_item(A0, 0, g);                   // items 0 (and 1) read the packed initial state: nothing to wait for
@@ -337,7 +320,7 @@ __global__ __launch_bounds__(768) void lstm_persist_fwd_kernel(PersistFwdArgs a)
       f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int qg = 0; qg < NQ; ++qg) {
-        if (PD >= 1 && qg == (NQ * YT8M_FWD_POLLQ) / 4) {   // request point: the state of item k + PD must be complete now
+        if (PD >= 1 && qg == (NQ * FWD_POLLQ) / 4) {   // request point: the state of item k + PD must be complete now
           if (w == 0) {
             const unsigned tot = shard_sum(pv);
             if (tot < (unsigned)sr * arrivals) wait_tile(a.ctl, Tr, (unsigned)sr * arrivals, lane);
@@ -352,11 +335,6 @@ __global__ __launch_bounds__(768) void lstm_persist_fwd_kernel(PersistFwdArgs a)
         float4 b0, b1;
         if (qg < HQ) { b0 = Wr[qg < HQ ? qg : 0][0]; b1 = Wr[qg < HQ ? qg : 0][1]; }
         else { b0 = Wl[w][qg - HQ][0][lane]; b1 = Wl[w][qg - HQ][1][lane]; }
-#ifdef YT8M_MFMA_CUT   // timing experiment only (wrong results): 3 of 8 MFMAs, the matrix time of six bf16 products
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, b0.x, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, b1.y, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z + av.w, b0.z + b1.w, acc0, 0, 0, 0);
-#else
         acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, b0.x, acc0, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, b1.x, acc1, 0, 0, 0);
         acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, b0.y, acc0, 0, 0, 0);
@@ -365,7 +343,6 @@ __global__ __launch_bounds__(768) void lstm_persist_fwd_kernel(PersistFwdArgs a)
         acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, b1.z, acc1, 0, 0, 0);
         acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, b0.w, acc0, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, b1.w, acc1, 0, 0, 0);
-#endif
       }
       STAMP(2);
       const int slot = k & (NSLOT - 1);
@@ -398,7 +375,7 @@ __global__ __launch_bounds__(768) void lstm_persist_fwd_kernel(PersistFwdArgs a)
   // are its own stores of step s (same wave: program order), never another wave's.
   const int ew = w - 8;
   const int eunit = lane & 7;
-  __builtin_amdgcn_s_setprio(YT8M_EPI_PRIO);             // the epilogue is the latency-critical chain: win VALU issue arbitration
+  __builtin_amdgcn_s_setprio(EPI_PRIO);             // the epilogue is the latency-critical chain: win VALU issue arbitration
   for (int s = 0; s < a.T; ++s) {
     const int t = a.t0 + s;
     for (int it = ew; it < n_it; it += NEPI) {
@@ -469,7 +446,7 @@ __global__ __launch_bounds__(768) void lstm_persist_fwd_kernel(PersistFwdArgs a)
             v.x = __float_as_uint(hn[j]); v.y = __float_as_uint(h1); v.z = __float_as_uint(h2); v.w = __float_as_uint(h3);
             const int erow = 8 * j + (lane >> 3);
             const unsigned off = ((unsigned)(T * QH + (ug >> 1)) * 256u + (unsigned)(erow * 16 + (ug & 1) * 8 + eunit)) * 4u;
-            __builtin_amdgcn_raw_buffer_store_b128(v, image(s + 1), (int)off, 0, YT8M_AUX_ST);
+            __builtin_amdgcn_raw_buffer_store_b128(v, image(s + 1), (int)off, 0, AUX_STORE);
           }
         }
         STAMP(3);
@@ -576,10 +553,7 @@ template <int NKB, int NP = 3, bool F16 = false>
 __global__ __launch_bounds__(768) void lstm_persist_fwd_x3_kernel(PersistFwdArgs a) {
   static_assert(!F16 || NP == 2, "the f16 form has two planes");
   constexpr int NS = 2;                                  // partial-tile slots
-#ifndef YT8M_X3_EPW
-#define YT8M_X3_EPW 2
-#endif
-  constexpr int EPW = YT8M_X3_EPW;                       // epilogue waves per item (1: a whole tile per wave, 2: half a tile each)
+  constexpr int EPW = 2;                                 // epilogue waves per item: half a tile each
   constexpr int NF = NKB * 2 * NP;                       // B fragments of a wave: [K block][column half][plane]
   constexpr int NREG = F16 ? NF : (NF < 10 ? NF : 10), NLDS = NF - NREG;   // (the f16 form's 16 fragments all fit in registers)
   constexpr int HK = NKB / 2;                            // K blocks per half item
@@ -776,20 +750,16 @@ __global__ __launch_bounds__(768) void lstm_persist_fwd_x3_kernel(PersistFwdArgs
   }
 
   // =============================== epilogue waves (as in lstm_persist_fwd_kernel; the publish splits) ===============================
-  // EPW epilogue waves share an item (EPW = 2: wave pair (ew >> 1) owns the tiles it = pair, pair + 2, ...; its two waves take
-  // rows 0-7 / 8-15, ONE (row, unit) pair per lane, so the dependent gate / split / store sequence of the publish is half as long)
+  // EPW = 2 epilogue waves share an item: wave pair (ew >> 1) owns the tiles it = pair, pair + 2, ...; its two waves take rows
+  // 0-7 / 8-15, ONE (row, unit) pair per lane, so the dependent gate / split / store sequence of the publish is half as long
   const int ew = w - 8;
   const int eunit = lane & 7;
   constexpr int JP = 2 / EPW;                            // (row, unit) pairs per lane
-  __builtin_amdgcn_s_setprio(YT8M_EPI_PRIO);
-#ifdef YT8M_FWD_NO_CARRY
-  const bool carry = false;
-#else
+  __builtin_amdgcn_s_setprio(EPI_PRIO);
   const bool carry = F16 && (n_it + NEPI / EPW - 1) / (NEPI / EPW) <= CARRY_T;
-#endif
   for (int s = 0; s < a.T; ++s) {
     const int t = a.t0 + s;
-    for (int it = EPW == 2 ? (ew >> 1) : ew; it < n_it; it += NEPI / EPW) {
+    for (int it = ew >> 1; it < n_it; it += NEPI / EPW) {
       const int li = carry ? it / (NEPI / EPW) : 0;       // this wave's local index of the tile
       const int k = s * n_it + it;
       const int T = g + it * RB;
@@ -798,27 +768,14 @@ __global__ __launch_bounds__(768) void lstm_persist_fwd_x3_kernel(PersistFwdArgs
       bool live[JP], evalid[JP];
 #pragma unroll
       for (int jj = 0; jj < JP; ++jj) {
-        const int j = EPW == 2 ? (ew & 1) : jj;
+        const int j = ew & 1;
         const int brow = T * 16 + 8 * j + (lane >> 3);
         evalid[jj] = brow < B;
         const int br = evalid[jj] ? brow : B - 1;
         const float* zr = a.z + ((long long)t * B + br) * 4 * H + ug * 8 + eunit;
         const long long idx = ((long long)t * B + br) * H + ug * 8 + eunit;
-#if defined(YT8M_FWD_EPI_NOLOAD) || defined(YT8M_FWD_EPI_NOZ)     // timing experiments only (wrong results)
-        for (int g4 = 0; g4 < 4; ++g4) zpre[jj][g4] = 0.1f * (float)(g4 + eunit);
-#elif defined(YT8M_FWD_ZPACK_T)   // timing experiment only (wrong results): the four gates of a (row, unit) pair as ONE 16-byte read, a row's
-        {                             // eight units of this workgroup = one full 128-byte line (layout [row][unit][gate] instead of [row][gate][unit])
-          const float4 zq = *reinterpret_cast<const float4*>(a.z + ((long long)t * B + br) * 4 * H + (ug * 8 + eunit) * 4);
-          zpre[jj][0] = zq.x; zpre[jj][1] = zq.y; zpre[jj][2] = zq.z; zpre[jj][3] = zq.w;
-          (void)zr;
-        }
-#else
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) zpre[jj][g4] = zr[g4 * H];
-#endif
-#if defined(YT8M_FWD_EPI_NOLOAD) || defined(YT8M_FWD_EPI_NOCH)
-        cpre[jj] = 0.2f; hpre[jj] = 0.1f;
-#else
         if (carry && s > 0) {
           cpre[jj] = lds_ch[F16 ? ew : 0][li][0][jj][lane];
           hpre[jj] = lds_ch[F16 ? ew : 0][li][1][jj][lane];
@@ -826,32 +783,15 @@ __global__ __launch_bounds__(768) void lstm_persist_fwd_x3_kernel(PersistFwdArgs
           cpre[jj] = a.cs[idx];
           hpre[jj] = a.hs[idx];
         }
-#endif
         live[jj] = t < lds_nf[it * 16 + 8 * j + (lane >> 3)];
       }
-#ifdef YT8M_FWD_ZPREFETCH   // (opt-in: measured no gain, profiles/r6_recur_ab.txt)
-      // Round 6: z[t] (the hoisted projection, read exactly once) comes from HBM, and the four unit groups that share each of its 128-byte
-      // lines (32 columns of one gate) run on four CUs of one XCD and ask for the line at the same moment: all four hold a slot of their CU's
-      // vector-memory window for the whole HBM round trip (profiles/r6_pmc_recur_tcc.txt: without these reads the step is 26 % shorter;
-      // a CU's 64-request window x latency is what paces the kernel).  Each sharer therefore touches a QUARTER of the next step's lines
-      // one step ahead (rows with row % 4 == ug % 4: one dword per line and gate): three of four demand reads become L2 hits.
-      float zpf = 0.f;
-      if (s + 1 < a.T) {
-        const int j = EPW == 2 ? (ew & 1) : 0;
-        constexpr int NPF = (EPW == 2 ? 2 : 4) * 4;        // rows of this wave with row % 4 == ug % 4, times four gates
-        if (lane < NPF) {
-          const int prow = T * 16 + 8 * j + 4 * (lane >> 2) + (ug & 3);
-          if (prow < B) zpf = a.z[((long long)(t + 1) * B + prow) * 4 * H + (long long)(lane & 3) * H + (ug & ~3) * 8];
-        }
-      }
-#endif
       const int slot = k & (NS - 1);
       lds_wait_ge(&lds_cnt[slot], 8u * (unsigned)(k / NS + 1), a.ctl);
       STAMP(1);
       float4 sum[JP];
 #pragma unroll
       for (int jj = 0; jj < JP; ++jj) {
-        const int j = EPW == 2 ? (ew & 1) : jj;
+        const int j = ew & 1;
         const int erow = 8 * j + (lane >> 3);
         const int ct = eunit >> 2, r = erow & 3, l0 = (erow >> 2) * 16 + (eunit & 3) * 4;
         sum[jj] = *reinterpret_cast<const float4*>(&red[slot][0][ct][r][l0]);
@@ -881,7 +821,7 @@ __global__ __launch_bounds__(768) void lstm_persist_fwd_x3_kernel(PersistFwdArgs
         const __amdgpu_buffer_rsrc_t hxr = image(s + 1);
 #pragma unroll
         for (int jj = 0; jj < JP; ++jj) {
-          const int j = EPW == 2 ? (ew & 1) : jj;
+          const int j = ew & 1;
           unsigned hb[3];
           if constexpr (F16) yt8m_x3::split_h2(hn[jj] * FWD_H2_S, hb[0], hb[1]);
           else if constexpr (NP == 3) split3_bits(hn[jj], hb[0], hb[1], hb[2]);
@@ -896,7 +836,7 @@ __global__ __launch_bounds__(768) void lstm_persist_fwd_x3_kernel(PersistFwdArgs
               u32x4 v;
               v.x = d; v.y = d2; v.z = d4; v.w = d6;
               const unsigned off = ((unsigned)((T * KBH + (ug >> 2)) * NP + p) * 256u + (unsigned)(((ug & 3) * 16 + erow) * 4)) * 4u;
-              __builtin_amdgcn_raw_buffer_store_b128(v, hxr, (int)off, 0, YT8M_AUX_ST);
+              __builtin_amdgcn_raw_buffer_store_b128(v, hxr, (int)off, 0, AUX_STORE);
             }
           }
         }
@@ -909,28 +849,19 @@ __global__ __launch_bounds__(768) void lstm_persist_fwd_x3_kernel(PersistFwdArgs
       }
 #pragma unroll
       for (int jj = 0; jj < JP; ++jj) {
-        const int j = EPW == 2 ? (ew & 1) : jj;
+        const int j = ew & 1;
         if (evalid[jj]) {
           const int brow = T * 16 + 8 * j + (lane >> 3);
           const long long idx1 = ((long long)(t + 1) * B + brow) * H + ug * 8 + eunit;
-#ifndef YT8M_FWD_EPI_NOSTORE  // timing experiment only (wrong results)
           if (live[jj]) {
-#ifdef YT8M_FWD_ZPACK_T
-            *reinterpret_cast<float4*>(a.z + ((long long)t * B + brow) * 4 * H + (ug * 8 + eunit) * 4) = make_float4(gi[jj], gj[jj], gf[jj], go[jj]);
-#else
             float* zr = a.z + ((long long)t * B + brow) * 4 * H + ug * 8 + eunit;
             zr[0] = gi[jj]; zr[H] = gj[jj]; zr[2 * H] = gf[jj]; zr[3 * H] = go[jj];
-#endif
           }
           a.cs[idx1] = cn[jj];
           a.hs[idx1] = hn[jj];
           if (a.out) a.out[((long long)t * B + brow) * H + ug * 8 + eunit] = live[jj] ? hn[jj] : 0.f;
-#endif
         }
       }
-#ifdef YT8M_FWD_ZPREFETCH
-      asm volatile("" ::"v"(zpf));                          // (keeps the touch alive; its value is never used)
-#endif
     }
   }
   if (ew == 0 && lane == 0) { check_placement(a.ctl, a.stats); propagate_error(a.ctl); }
@@ -972,9 +903,6 @@ struct PersistBwdArgs {
   unsigned* rowmax;     // rotated epilogue, or null: max |dz[t, b, :]| as float bits by absolute frame row t B + b (atomicMax over the 64
                         // producer workgroups of a row; zeroed by the caller) -- what yt8m_h2_rowscales would measure in a pass over dz
   unsigned* partmax;    // ... or null: max |dz| of the whole launch into one word (atomicMax; what yt8m_h2_absmax would measure)
-  unsigned* px;         // P2 (K-split workgroup pairs): partial-tile hand-off slots [2 parities][NT16][NUB][64 lanes][8 dwords] = {value, tag} granules
-  unsigned px_bytes;
-  unsigned nonce;       // ... a number no earlier launch on this workspace used: the tags of this launch are nonce * 8191 + step + 1
   unsigned long long* dbg;
   // IMG (rotated epilogue only): the operand images of this launch's dz written by the epilogue itself -- what yt8m_x3_split would
   // make of dz[t0 .. t0 + T) in separate passes (csrc/gemm_x3.hip image layout: 1 KiB blocks of 32 rows x 16 k per plane).
@@ -1031,30 +959,18 @@ __device__ __forceinline__ void p_split3(float x, unsigned& h1, unsigned& h2, un
 //   K slot (block 2 p + uh, k-group kg, j) of the exchange = producer p's value (unit 8 uh + 2 kg + j / 4, gate j % 4): a lane of the
 //   epilogue (one unit x four gates per row) and its neighbour fill one 16-byte A fragment piece -- one DPP move per dword instead of the
 //   one-plane form's three-step gather.
-// P2 (round 6): K-SPLIT WORKGROUP PAIRS of the H2 form.  What paces the H2 kernel is the CU's vector-memory window: 64 line requests in
-// flight x ~270 cycles each = ~31 B/clk, and every workgroup draws the dz of its 64 rows -- 1 MiB per step -- through it
-// (profiles/r6_pmc_recur_tcc.txt).  The two workgroups (pair, kh = 0 / 1) that share a 128-byte line of gates (same XCD) now share the
-// WORK differently: both compute the partial dh of the pair's 32 units, each over HALF of K (kh's 2H of the 4H dz columns = the producers
-// [32 kh, 32 kh + 32)) -- the same 256 KiB weight footprint ([2H x 32] instead of [4H x 16]: hi plane in registers, lo plane in LDS),
-// the same 48 MFMAs per item and wave, HALF the dz bytes per CU.  The price is one hand-off per item: each workgroup finishes its own 16
-// units and needs the partner's partial tile for them -- 1 KiB as sixty-four {value, tag} granule quads written with sc0 sc1 stores into
-// a slot the partner's epilogue wave polls with sc0 sc1 loads (no flag, no fence: the tag IS the arrival; MI355X_MICROARCH.md
-// "handoff-1to1").  Sum order: K-half 0 + K-half 1, whichever workgroup finishes the unit -- bitwise reproducible run to run.
-template <int NQB, bool PF, bool SH, bool ROT, bool IMG = false, bool BF = false, bool H2 = false, bool P2 = false>
+template <int NQB, bool PF, bool SH, bool ROT, bool IMG = false, bool BF = false, bool H2 = false>
 __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a) {
-  static_assert(!P2 || (H2 && (NQB % 16) == 0), "K-split pairs are a form of the two-half-plane kernel");
   static_assert(!IMG || ROT, "the operand images are written by the rotated epilogue");
   static_assert(!BF || (PF && SH && ROT && !IMG && (NQB % 4) == 0), "the bf16-operand form: prefetching, one image per step, rotated epilogue");
   static_assert(!H2 || (PF && SH && ROT && !IMG && !BF && (NQB % 8) == 0), "the two-half-plane form: prefetching, one image per step, rotated epilogue");
   constexpr int HALF = NQB / 2;                          // q-groups per wave in registers (= in LDS = ring slots)
   constexpr unsigned EPW = ROT ? 1u : 4u;                // epilogue waves that read a partial-tile slot / publish a tile
-  constexpr int NSL = P2 ? 2 : NSLOT_B;                    // partial-tile slots (P2: two tiles of 16 x 32 per wave -> 16 KB per slot)
-  constexpr int NRR = P2 ? 8 : 4;                          // accumulator registers a wave leaves per item
-  __shared__ __attribute__((aligned(16))) float4 Wl[8][BF ? 1 : (P2 ? HALF - 1 : HALF)][64];  // LDS-resident half of the weights: 8 * HALF KB (BF: none; P2: one fragment per wave moves to registers)
-  __shared__ __attribute__((aligned(16))) float red[NSL][8][NRR][64];      // [slot][wave][acc reg][lane]: 24 KB (P2: 32 KB)
+  __shared__ __attribute__((aligned(16))) float4 Wl[8][BF ? 1 : HALF][64];  // LDS-resident half of the weights: 8 * HALF KB (BF: none)
+  __shared__ __attribute__((aligned(16))) float red[NSLOT_B][8][4][64];      // [slot][wave][acc reg][lane]: 24 KB
   __shared__ unsigned lds_cnt[NSLOT_B], lds_free[NSLOT_B];
   __shared__ unsigned lds_seen[MAX_LOCAL_TILES];           // see the forward kernel: only matrix wave 0 polls memory
-  __shared__ int lds_nf[ROT ? (P2 ? 8 : MAX_LOCAL_TILES) * 16 : 1];   // rotated epilogue: num_frames of the workgroup's rows, read once (as the forward kernel)
+  __shared__ int lds_nf[ROT ? MAX_LOCAL_TILES * 16 : 1];   // rotated epilogue: num_frames of the workgroup's rows, read once (as the forward kernel)
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   int ub, g;
@@ -1075,7 +991,7 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
   const unsigned img_bytes = (unsigned)NT16 * (unsigned)H * (BF ? 32u : 64u) * 4u;     // BF: 2 bytes per dz element
   const long long img_f = (long long)NT16 * H * (BF ? 32 : 64);
   auto image = [&](int s) -> __amdgpu_buffer_rsrc_t { return make_rsrc(a.dzx + (SH ? s : (s & 1)) * img_f, img_bytes); };
-  constexpr int AUX_LD = SH ? 0 : YT8M_AUX_LD;
+  constexpr int AUX_LD = SH ? 0 : AUX_LOAD;
   const unsigned arrivals = (unsigned)a.NUB * EPW;       // per (tile, publish): EPW epilogue waves per workgroup
   const int i16 = lane & 15, kq = lane >> 4;
   note_placement(a.ctl);
@@ -1091,10 +1007,9 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
   // (global block kbp = w NQB / 2 + kbl: producer kbp / 2, unit half kbp % 2), W_h[16 ub + n][gate (j % 4) H + 16 producer + 8 uh + 2 kg + j / 4]
   float h2_sw = 1.f;
   if constexpr (H2) h2_sw = yt8m_x3::pow2_scale_for(__uint_as_float(a.wword[0]), 14);
-  // P2: fragment f = 2 kbl + nt of a wave = K block kh 2 NQB + w NQB / 4 + kbl of the pair's unit tile nt (units 16 (2 pair + nt) ..)
   auto w_frag_h2 = [&](int kbl, u32x4& fhi, u32x4& flo) {
-    const int kbp = P2 ? (ub & 1) * 2 * NQB + w * (NQB / 4) + (kbl >> 1) : w * (NQB / 2) + kbl;
-    const int urow = P2 ? ((ub & ~1) + (kbl & 1)) * 16 + i16 : ub * 16 + i16;
+    const int kbp = w * (NQB / 2) + kbl;
+    const int urow = ub * 16 + i16;
     const float* q = a.Wh + (long long)urow * a.ldw + 16 * (kbp >> 1) + 8 * (kbp & 1) + 2 * kq;
     unsigned hb[8], lb[8];
 #pragma unroll
@@ -1105,7 +1020,7 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
   if constexpr (H2) {
     if (w < 8) {
 #pragma unroll
-      for (int kbl = 0; kbl < (P2 ? HALF - 1 : HALF); ++kbl) {   // the lo plane of the whole slice lives in LDS, the hi plane in registers
+      for (int kbl = 0; kbl < HALF; ++kbl) {   // the lo plane of the whole slice lives in LDS, the hi plane in registers
         u32x4 fhi, flo;
         w_frag_h2(kbl, fhi, flo);
         Wl[w][kbl][lane] = as_f4(flo);
@@ -1208,134 +1123,6 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
       }
       return;
     }
-  } else if constexpr (H2 && P2) {
-    if (w < 8) {
-      // =============================== matrix waves, two half planes, K-split pair ===============================
-      constexpr int KW = NQB / 4, HK = KW / 2;             // K blocks per wave (8 at H = 1024) / per half item
-      constexpr int NPW = KW / 2, PH = NPW / 2;            // producers per wave (a producer = 2 K blocks) / per half item
-      static_assert(HK >= 2 && (HK % 2) == 0, "whole producers per half item");
-      const int kh = ub & 1;
-      u32x4 Wh_[HALF];                                     // hi plane: fragment f = 2 kbl + nt
-      u32x4 Wlast;                                         // lo plane of fragment HALF - 1 (the one that left the LDS)
-#pragma unroll
-      for (int f = 0; f < HALF; ++f) { u32x4 flo; w_frag_h2(f, Wh_[f], flo); if (f == HALF - 1) Wlast = flo; }
-      const float inv_sw = 1.0f / h2_sw;
-      const int lane_off = lane * 16;
-      const int kbp0 = kh * 2 * NQB + w * KW;              // first global K block of this wave
-      auto blk = [&](int T) -> int { return __builtin_amdgcn_readfirstlane((T * QH4 + 2 * kbp0) * 1024); };
-      const __amdgpu_buffer_rsrc_t scr = make_rsrc(a.sc, a.sc_bytes);
-      const int kq_off = kq * 4;
-      auto sc_off = [&](int s, int T, int pl) -> int {
-        return __builtin_amdgcn_readfirstlane(((s * NT16 + T) * a.NUB + (kbp0 >> 1) + pl) * 16);
-      };
-      u32x4 ring[2 * HK];                                  // half an item: HK K blocks x 2 planes
-      unsigned sc[PH];
-      int s_cur = 0, it_cur = 0, slot = 0, gen = 0;
-      auto seen_wait = [&](int it, int T, unsigned target) {
-        if (w == 0) {
-          wait_tile(a.ctl, T, target, lane);
-          if (lane == 0) __hip_atomic_store(&lds_seen[it], target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        } else {
-          lds_wait_ge(&lds_seen[it], target, a.ctl);
-        }
-      };
-      {
-        seen_wait(0, g, arrivals);
-        const int b0 = blk(g);
-        const __amdgpu_buffer_rsrc_t dx0 = image(0);
-#pragma unroll
-        for (int q = 0; q < 2 * HK; ++q) ring[q] = __builtin_amdgcn_raw_buffer_load_b128(dx0, lane_off, b0 + q * 1024, 0);
-#pragma unroll
-        for (int pl = 0; pl < PH; ++pl) sc[pl] = __builtin_amdgcn_raw_buffer_load_b32(scr, kq_off, sc_off(0, g, pl), 0);
-      }
-      auto lo_frag = [&](int f) -> u32x4 { return f == HALF - 1 ? Wlast : as_u4(Wl[w][f < HALF - 1 ? f : 0][lane]); };
-      u32x4 wl0 = lo_frag(0), wl1 = lo_frag(1);            // lo fragments of the NEXT K block (both unit tiles), one block ahead
-      auto rescale = [&](f32x4& acc, const f32x4& tmp, unsigned e4) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = __builtin_fmaf(tmp[r], __uint_as_float(((e4 >> (8 * r)) & 0xFFu) << 23), acc[r]);
-        asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
-      };
-      for (int k = 0; k < total; ++k) {
-        const int s = s_cur, T = g + it_cur * RB;
-        STAMP(0);
-        int s1 = s, it1 = it_cur + 1;
-        if (it1 == n_it) { it1 = 0; ++s1; }
-        const bool have1 = k + 1 < total;
-        const int T1 = have1 ? g + it1 * RB : T;
-        s1 = have1 ? s1 : s;
-        unsigned pv = 0;
-        const int bcur = blk(T);
-        const __amdgpu_buffer_rsrc_t dxr = image(s);
-        if (w == 0 && lane < NSH)
-          pv = __hip_atomic_load(a.ctl + CTL_HDR + (T1 * NSH + lane) * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        f32x4 tmp0 = {0.f, 0.f, 0.f, 0.f}, tmp1 = {0.f, 0.f, 0.f, 0.f};
-        unsigned e_cur = 0;
-        // one K block: its A fragments (hi, lo plane) against both unit tiles -- six MFMAs -- then the in-place refill of its two ring
-        // entries and the lo fragments of the next block
-        auto kblock = [&](int kbl, int kr, const __amdgpu_buffer_rsrc_t& rsrc, int rbase, bool refill, int sc_s, int sc_T, int sc_pl) {
-          const f16x8 ah = __builtin_bit_cast(f16x8, ring[2 * kr]), al = __builtin_bit_cast(f16x8, ring[2 * kr + 1]);
-          const f16x8 bh0 = __builtin_bit_cast(f16x8, Wh_[2 * kbl]), bh1 = __builtin_bit_cast(f16x8, Wh_[2 * kbl + 1]);
-          const f16x8 bl0 = __builtin_bit_cast(f16x8, wl0), bl1 = __builtin_bit_cast(f16x8, wl1);
-          if ((kbl & 1) == 0) e_cur = sc[(kr >> 1)];
-          __builtin_amdgcn_sched_barrier(0);
-          if ((kbl & 1) == 0) {
-            tmp0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh0, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-            tmp1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh1, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-          } else {
-            tmp0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh0, tmp0, 0, 0, 0);
-            tmp1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh1, tmp1, 0, 0, 0);
-          }
-          tmp0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh0, tmp0, 0, 0, 0);
-          tmp1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh1, tmp1, 0, 0, 0);
-          tmp0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl0, tmp0, 0, 0, 0);
-          tmp1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl1, tmp1, 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-          const int fn = (2 * (kbl + 1)) % HALF;             // (the last block of an item fetches block 0's of the next)
-          wl0 = lo_frag(fn);
-          wl1 = lo_frag(fn + 1);
-          if (refill) {
-            ring[2 * kr] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_off, rbase + (2 * kr) * 1024, 0);
-            ring[2 * kr + 1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_off, rbase + (2 * kr + 1) * 1024, 0);
-          }
-          if (kbl & 1) {
-            if (refill) sc[(kr >> 1)] = __builtin_amdgcn_raw_buffer_load_b32(scr, kq_off, sc_off(sc_s, sc_T, sc_pl), 0);
-            rescale(acc0, tmp0, e_cur);
-            rescale(acc1, tmp1, e_cur);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        };
-        // first half: ring entries are refilled with this item's second half
-#pragma unroll
-        for (int kb = 0; kb < HK; ++kb) kblock(kb, kb, dxr, bcur + 2 * HK * 1024, true, s, T, PH + (kb >> 1));
-        {
-          const int it1l = have1 ? it1 : it_cur;
-          if (w == 0) {
-            const unsigned tot = shard_sum(pv);
-            if (tot < (unsigned)(s1 + 1) * arrivals) wait_tile(a.ctl, T1, (unsigned)(s1 + 1) * arrivals, lane);
-            if (lane == 0) __hip_atomic_store(&lds_seen[it1l], (unsigned)(s1 + 1) * arrivals, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          } else {
-            lds_wait_ge(&lds_seen[it1l], (unsigned)(s1 + 1) * arrivals, a.ctl);
-          }
-          STAMP(1);
-        }
-        const int bnext = blk(T1);
-        const __amdgpu_buffer_rsrc_t dxn = image(s1);
-        // second half: refilled with the next item's first half
-#pragma unroll
-        for (int kb = HK; kb < KW; ++kb) kblock(kb, kb - HK, dxn, bnext, true, s1, T1, (kb - HK) >> 1);
-        STAMP(2);
-        if (gen > 0) lds_wait_ge(&lds_free[slot], EPW * (unsigned)gen, a.ctl);
-        float* rw = &red[slot][w][0][lane];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { rw[r * 64] = acc0[r] * inv_sw; rw[(4 + r) * 64] = acc1[r] * inv_sw; }
-        if (lane == 0) __hip_atomic_fetch_add(&lds_cnt[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        STAMP(3);
-        if (++slot == NSL) { slot = 0; ++gen; }
-        if (++it_cur == n_it) { it_cur = 0; ++s_cur; }
-      }
-      return;
-    }
   } else if constexpr (H2) {
     if (w < 8) {
       // =============================== matrix waves, two half planes ===============================
@@ -1347,11 +1134,7 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
       // (addresses: the lane's 16 bytes in the VGPR offset, everything uniform -- tile, wave, block -- in the scalar offset: with the
       // block index folded into per-load VGPR offsets the register allocator keeps a dozen base registers alive)
       const int lane_off = lane * 16;
-#ifdef YT8M_TWIN_TEST    // timing experiment only (wrong results): waves 2j and 2j + 1 fetch the SAME K blocks -- what a twin-wave N = 32 form would move
-      auto blk = [&](int T) -> int { return __builtin_amdgcn_readfirstlane((T * QH4 + (w & ~1) * NQB) * 1024); };
-#else
       auto blk = [&](int T) -> int { return __builtin_amdgcn_readfirstlane((T * QH4 + w * NQB) * 1024); };
-#endif
       const __amdgpu_buffer_rsrc_t scr = make_rsrc(a.sc, a.sc_bytes);
       const int kq_off = kq * 4;
       auto sc_off = [&](int s, int T, int pl) -> int { return __builtin_amdgcn_readfirstlane(((s * NT16 + T) * a.NUB + w * NPW + pl) * 16); };
@@ -1416,10 +1199,8 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
           // refills IN PLACE behind the MFMAs that read the registers (the fp32 form loads ahead into fresh registers: 8 more VGPRs than
           // this form has)
           wlb[kb & 1] = as_u4(Wl[w][kb + 2][lane]);
-#ifndef YT8M_HALF_TEST   // timing experiment only (wrong results): the second half of an item's dz is never fetched -- the data flow of a K-split pair
           ring[2 * kb] = __builtin_amdgcn_raw_buffer_load_b128(dxr, lane_off, bcur + (HALF + 2 * kb) * 1024, 0);
           ring[2 * kb + 1] = __builtin_amdgcn_raw_buffer_load_b128(dxr, lane_off, bcur + (HALF + 2 * kb + 1) * 1024, 0);
-#endif
           if ((kb & 1) == 0) sc[pl] = __builtin_amdgcn_raw_buffer_load_b32(scr, kq_off, sc_off(s, T, PH + pl), 0);
           if (kb & 1) rescale(acc, tmp, e_cur);              // the producer's six MFMAs: its tile times its rows' inverse scales
           __builtin_amdgcn_sched_barrier(0);
@@ -1599,7 +1380,7 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
 
   // =============================== epilogue waves ===============================
   const int ew = w - 8;
-  __builtin_amdgcn_s_setprio(YT8M_EPI_PRIO);
+  __builtin_amdgcn_s_setprio(EPI_PRIO);
   if constexpr (ROT) {
     // lane = (row quad rq, unit): its four pairs are rows 4 rq + r, r = 0..3, of the tile -- exactly the four accumulator registers
     // of that lane in every matrix wave's partial tile (C layout: column = lane & 15, row = 4 (lane >> 4) + r)
@@ -1645,13 +1426,13 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
             vl.x = l0; vl.y = l1; vl.z = l2; vl.w = l3;
             const unsigned off = (((unsigned)(T * (H >> 3)) + 2u * (unsigned)ub + (unsigned)(eunit >> 3)) * 2u) * 1024u +
                                  ((unsigned)((eunit >> 1) & 3) * 16u + (unsigned)(4 * rq + r)) * 16u;
-            __builtin_amdgcn_raw_buffer_store_b128(vh, dxr, (int)off, 0, YT8M_AUX_ST);
-            __builtin_amdgcn_raw_buffer_store_b128(vl, dxr, (int)(off + 1024u), 0, YT8M_AUX_ST);
+            __builtin_amdgcn_raw_buffer_store_b128(vh, dxr, (int)off, 0, AUX_STORE);
+            __builtin_amdgcn_raw_buffer_store_b128(vl, dxr, (int)(off + 1024u), 0, AUX_STORE);
           }
         }
         if (eunit == 0)
           __builtin_amdgcn_raw_buffer_store_b32(ex, scr, (int)((((unsigned)(pub * NT16 + T) * (unsigned)a.NUB + (unsigned)ub) * 4u + (unsigned)rq) * 4u), 0,
-                                                YT8M_AUX_ST);
+                                                AUX_STORE);
         pend_T = T;
         return;
       }
@@ -1673,7 +1454,7 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
               const unsigned kbg = (unsigned)(g4 * (H >> 5) + (ub >> 1));
               const unsigned kgrp = (unsigned)(((ub & 1) << 1) + (eunit >> 3));
               const unsigned off = ((unsigned)(T * (H >> 3)) + kbg) * 1024u + (kgrp * 16u + (unsigned)(4 * rq + r)) * 16u;
-              __builtin_amdgcn_raw_buffer_store_b128(v, dxr, (int)off, 0, YT8M_AUX_ST);
+              __builtin_amdgcn_raw_buffer_store_b128(v, dxr, (int)off, 0, AUX_STORE);
             }
           }
         }
@@ -1690,7 +1471,7 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
             u32x4 v;
             v.x = __float_as_uint(v0); v.y = __float_as_uint(v1); v.z = __float_as_uint(v2); v.w = __float_as_uint(v3);
             const unsigned off = ((unsigned)(T * QH4 + g4 * (H >> 4) + ub) * 256u + (unsigned)((4 * rq + r) * 16 + eunit)) * 4u;
-            __builtin_amdgcn_raw_buffer_store_b128(v, dxr, (int)off, 0, YT8M_AUX_ST);
+            __builtin_amdgcn_raw_buffer_store_b128(v, dxr, (int)off, 0, AUX_STORE);
           }
         }
       }
@@ -1701,31 +1482,16 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
     // step, so what it wrote or read the step before travels in registers instead of through memory: the running (dh, dc) of `work`
     // (two loads + two stores per pair and step) and c_{t+1} = the c_t it read one step earlier.  Every request a CU does not make
     // frees a slot of its 64-request vector-memory window for the dz stream (profiles/r6_pmc_recur_tcc.txt).
-#ifdef YT8M_BWD_NO_CARRY
-    const bool carry = false;
-#else
     const bool carry = !IMG && (n_it == 4);                // (the image-writing epilogue has no registers to spare: it keeps the loads)
-#endif
     float car_base[4] = {0.f, 0.f, 0.f, 0.f}, car_dc[4] = {0.f, 0.f, 0.f, 0.f}, car_cn[4] = {0.f, 0.f, 0.f, 0.f};
     auto gate_load = [&](int t1, int br, int lrow, bool have_cn = false, float cnv = 0.f) -> GateIn {       // lrow: the row's slot in lds_nf (16 it + row of the tile)
       GateIn q;
-#ifdef YT8M_EPI_NOLOAD   // timing experiment only (wrong results): the epilogue's saved-activation reads never reach memory
-      q.gi = 0.5f; q.gj = 0.3f; q.gf = 0.6f; q.go = 0.4f; q.cp = 0.1f * (float)eunit; q.cn = 0.2f; q.dout = 0.01f; q.live = t1 < lds_nf[lrow];
-      return q;
-#endif
       const float* gr = a.gates + ((long long)t1 * B + br) * 4 * H + ub * 16 + eunit;
       const long long idx = (long long)t1 * BH + (long long)br * H + ub * 16 + eunit;
-#if defined(YT8M_EPI_LD_NT)          // experiments: cache policy of the saved-activation reads (each line is read once, from HBM)
-#define EPI_LD(p) __builtin_nontemporal_load(p)
-#elif defined(YT8M_EPI_LD_SC1)
-#define EPI_LD(p) __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#else
-#define EPI_LD(p) (*(p))
-#endif
-      q.gi = EPI_LD(gr); q.gj = EPI_LD(gr + H); q.gf = EPI_LD(gr + 2 * H); q.go = EPI_LD(gr + 3 * H);
-      q.cp = EPI_LD(a.cs + idx);
-      q.cn = have_cn ? cnv : EPI_LD(a.cs + idx + BH);
-      q.dout = a.dout ? EPI_LD(a.dout + idx) : 0.f;
+      q.gi = gr[0]; q.gj = gr[H]; q.gf = gr[2 * H]; q.go = gr[3 * H];
+      q.cp = a.cs[idx];
+      q.cn = have_cn ? cnv : a.cs[idx + BH];
+      q.dout = a.dout ? a.dout[idx] : 0.f;
       q.live = t1 < lds_nf[lrow];
       return q;
     };
@@ -1741,16 +1507,8 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
       base_out = q.live ? 0.f : dh_in;
     };
     auto store_std = [&](int t1, int brow, const float (&dzv)[4], float dc_out, float base_out, int half, bool with_work = true) {
-#ifdef YT8M_EPI_NOSTORE  // timing experiment only (wrong results): no standard-layout dz / running-state stores
-      return;
-#endif
       float* dzr = a.dz + ((long long)t1 * B + brow) * 4 * H + ub * 16 + eunit;
-#ifdef YT8M_EPI_ST_NT
-      __builtin_nontemporal_store(dzv[0], dzr); __builtin_nontemporal_store(dzv[1], dzr + H);
-      __builtin_nontemporal_store(dzv[2], dzr + 2 * H); __builtin_nontemporal_store(dzv[3], dzr + 3 * H);
-#else
       dzr[0] = dzv[0]; dzr[H] = dzv[1]; dzr[2 * H] = dzv[2]; dzr[3 * H] = dzv[3];
-#endif
       if (a.dbrows) {
         float* db = a.dbrows + (long long)brow * 4 * H + ub * 16 + eunit;
         db[0] += dzv[0]; db[H] += dzv[1]; db[2 * H] += dzv[2]; db[3 * H] += dzv[3];
@@ -1890,7 +1648,7 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
       const int half = (a.phase + s + 1) & 1;
       for (int it = ew; it < n_it; it += 4) {
         const int k = s * n_it + it;                      // n_it % 4 == 0: item k is always this wave's
-        const int slot = k % NSL, gen = k / NSL;
+        const int slot = k % NSLOT_B, gen = k / NSLOT_B;
         const int T = g + it * RB;
         STAMP(0);
         float base[4], dc[4];
@@ -1915,59 +1673,6 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
         lds_wait_ge(&lds_cnt[slot], 8u * (unsigned)(gen + 1), a.ctl);
         STAMP(1);
         float p[4];
-        if constexpr (P2) {
-          // this workgroup's K half of BOTH unit tiles: keep the own tile's, hand the other to the partner, take the partner's half of
-          // the own tile.  Slot of (step parity, tile, DESTINATION workgroup): 64 lanes x {p0, tag, p1, tag | p2, tag, p3, tag}.
-          const int kh = ub & 1;
-          float q[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            p[r] = red[slot][0][4 * kh + r][lane];
-            q[r] = red[slot][0][4 * (kh ^ 1) + r][lane];
-#pragma unroll
-            for (int wv = 1; wv < 8; ++wv) { p[r] += red[slot][wv][4 * kh + r][lane]; q[r] += red[slot][wv][4 * (kh ^ 1) + r][lane]; }
-          }
-          if (lane == 0) __hip_atomic_fetch_add(&lds_free[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          const __amdgpu_buffer_rsrc_t pxr = make_rsrc(a.px, a.px_bytes);
-          const unsigned tag = a.nonce * 8191u + (unsigned)s + 1u;
-          const unsigned slot_b = (unsigned)(((s & 1) * NT16 + T) * a.NUB) * 2048u + (unsigned)lane * 32u;
-          {
-            u32x4 v0, v1;
-            v0.x = __float_as_uint(q[0]); v0.y = tag; v0.z = __float_as_uint(q[1]); v0.w = tag;
-            v1.x = __float_as_uint(q[2]); v1.y = tag; v1.z = __float_as_uint(q[3]); v1.w = tag;
-            const unsigned dst = slot_b + (unsigned)(ub ^ 1) * 2048u;
-            __builtin_amdgcn_raw_buffer_store_b128(v0, pxr, (int)dst, 0, YT8M_AUX_ST);
-            __builtin_amdgcn_raw_buffer_store_b128(v1, pxr, (int)(dst + 16u), 0, YT8M_AUX_ST);
-          }
-          const unsigned src = slot_b + (unsigned)ub * 2048u;
-          long long t_start = 0;
-          for (unsigned spins = 0;; ++spins) {
-            const u32x4 v0 = __builtin_amdgcn_raw_buffer_load_b128(pxr, (int)src, 0, YT8M_AUX_LD);
-            const u32x4 v1 = __builtin_amdgcn_raw_buffer_load_b128(pxr, (int)(src + 16u), 0, YT8M_AUX_LD);
-            const bool ok = v0.y == tag && v0.w == tag && v1.y == tag && v1.w == tag;
-            if (__all(ok)) {
-              const float o0 = __uint_as_float(v0.x), o1 = __uint_as_float(v0.z), o2 = __uint_as_float(v1.x), o3 = __uint_as_float(v1.z);
-              if (kh == 0) { p[0] += o0; p[1] += o1; p[2] += o2; p[3] += o3; }       // K half 0 + K half 1, on either side
-              else { p[0] = o0 + p[0]; p[1] = o1 + p[1]; p[2] = o2 + p[2]; p[3] = o3 + p[3]; }
-              break;
-            }
-            if (spins >= 4) {
-              __builtin_amdgcn_s_sleep(2);
-              if ((spins & 63) == 4) {
-                if (__hip_atomic_load(a.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-                const long long now = wall_clock64();
-                if (t_start == 0) t_start = now;
-                else if (now - t_start > SPIN_TIMEOUT) {
-                  if (lane == 0) {
-                    __hip_atomic_store(a.ctl - CTL_STICKY, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(a.ctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                  }
-                  break;
-                }
-              }
-            }
-          }
-        } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           p[r] = red[slot][0][r][lane];
@@ -1975,7 +1680,6 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
           for (int wv = 1; wv < 8; ++wv) p[r] += red[slot][wv][r][lane];
         }
         if (lane == 0) __hip_atomic_fetch_add(&lds_free[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
         STAMP(2);
         if (last) {                                       // dL/dh_{t_lo - 1}: handed to the caller (next chunk / initial state)
 #pragma unroll
@@ -2040,9 +1744,9 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
   // Publishing dz of an item = (1) write-through stores of its image bytes, (2) wait until they have left this CU, (3) one
   // arrival on the tile's counter.  (2) sits right behind (1): ~3.6k cycles of waiting per item in which all four epilogue waves
   // do nothing (tools/persist_timeline.py: epilogue 1.0k reduce + 2.7k gate math + 3.6k drain per item).  Round 3 tried to hide
-  // it (-DYT8M_BWD_DEFER_ARRIVE: go on with the standard-layout stores of item k and the operand loads of item k + 1, arrive for
-  // item k when those loads are back or at once if item k + 1's partial tiles are not there yet): correct, and NO faster (21.5
-  // vs 21.4 us/step stand-alone, 23.3 vs 23.2 ms for the training step) -- the step time is the chain of a tile through ALL 64
+  // it (go on with the standard-layout stores of item k and the operand loads of item k + 1, arrive for item k when those loads
+  // are back or at once if item k + 1's partial tiles are not there yet): correct, and NO faster (21.5 vs 21.4 us/step
+  // stand-alone, 23.3 vs 23.2 ms for the training step; since removed) -- the step time is the chain of a tile through ALL 64
   // unit-group workgroups of its row group (the slowest of 64 publishes gates every consumer), not the epilogue's throughput.
   int pend_T = -1;
   auto publish_stores = [&](int T, int pub, const float (&dzv)[4]) {
@@ -2056,7 +1760,7 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
         u32x4 v;
         v.x = __float_as_uint(v0); v.y = __float_as_uint(v1); v.z = __float_as_uint(v2); v.w = __float_as_uint(v3);
         const unsigned off = ((unsigned)(T * QH4 + g4 * (H >> 4) + ub) * 256u + (unsigned)(erow * 16 + eunit)) * 4u;
-        __builtin_amdgcn_raw_buffer_store_b128(v, dxr, (int)off, 0, YT8M_AUX_ST);
+        __builtin_amdgcn_raw_buffer_store_b128(v, dxr, (int)off, 0, AUX_STORE);
       }
     }
     pend_T = T;
@@ -2136,10 +1840,6 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
       const float base = wk[0], dc = wk[BH];
       GateIn q;
       if (!last) q = gate_load(t1, br);
-#ifdef YT8M_BWD_DEFER_ARRIVE
-      // the previous item's arrival: at once when this item's partial tiles are not there yet (nothing to overlap the drain with)
-      if (pend_T >= 0 && lds_load(&lds_cnt[slot]) < 8u * (unsigned)(gen + 1)) arrive();
-#endif
       lds_wait_ge(&lds_cnt[slot], 8u * (unsigned)(gen + 1), a.ctl);
       STAMP(1);
       // C layout: column = lane & 15 (unit), row = 4 (lane >> 4) + r  ->  pair (row 4 ew + er, unit): register er, lane 16 ew + unit
@@ -2160,9 +1860,7 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
       if (!valid) { dzv[0] = dzv[1] = dzv[2] = dzv[3] = 0.f; }
       STAMP(3);
       publish_stores(T, s + 1, dzv);
-#ifndef YT8M_BWD_DEFER_ARRIVE
-      arrive();                                          // drain right behind the image stores (default; see above)
-#endif
+      arrive();                                          // drain right behind the image stores (see above)
       STAMP(4);
       if (valid) store_std(t1, brow, dzv, dc_out, base_out, half ^ 1);
     }
@@ -2228,7 +1926,6 @@ unsigned* stats_ptr(int dev) {
 
 // CUs a persistent launch may occupy: the whole chip, or YT8M_PERSIST_CUS of them (the rest stays free for kernels of other
 // streams -- the hoisted GEMMs of the layer pipeline -- to run beside the recurrence)
-std::atomic<int> g_pair_mode{-1};        // yt8m_lstm_persist_set_pair
 int g_cap_fwd = -1, g_cap_bwd = -1;      // yt8m_lstm_persist_set_cus (calling thread's choice for its next launches); -1: environment
 // CUs the gate keeps out of its residency arithmetic (yt8m_lstm_persist_reserve_cus): under data parallelism the RCCL kernels of
 // the gradient all-reduce occupy CUs during the backward recurrences -- two half-chip launches admitted side by side would then
@@ -2368,7 +2065,8 @@ extern "C" int64_t yt8m_lstm_persist_workspace_bytes_steps(int64_t B, int64_t H,
   Geometry geo;
   if (!persist_geometry(B, H, &geo)) return 0;
   // (+ the scale words of the f16 form of the backward recurrence: yt8m_lstm_persist_bwd_h2)
-  // ... + the hand-off slots of its K-split pair form (two parities x tiles x H / 16 workgroups x 2 KiB)
+  // ... + two parities x tiles x H / 16 workgroups x 2 KiB that no launch uses any more (the hand-off slots of a removed K-split
+  // form; kept so that the size and the layout of the workspace do not move)
   return ctl_padded(geo.NT16) + std::max<int64_t>(T, 2) * geo.NT16 * 16 * 4 * H * 4 + ((std::max<int64_t>(T, 2) * geo.NT16 * (H / 16) * 16 + 255) / 256) * 256 +
          (int64_t)2 * geo.NT16 * (H / 16) * 2048 + DBG_BYTES;
 }
@@ -2584,8 +2282,7 @@ int launch_bwd_sh(const PersistBwdArgs& a, unsigned grid, hipStream_t s) {
   }
   if constexpr (SH && (NQB == 16 || NQB == 32)) {
     if (a.h2 && rot) {
-      if (a.px) hipLaunchKernelGGL((lstm_persist_bwd_kernel<NQB, true, true, true, false, false, true, true>), dim3(grid), dim3(768), 0, s, a);
-      else hipLaunchKernelGGL((lstm_persist_bwd_kernel<NQB, true, true, true, false, false, true>), dim3(grid), dim3(768), 0, s, a);
+      hipLaunchKernelGGL((lstm_persist_bwd_kernel<NQB, true, true, true, false, false, true>), dim3(grid), dim3(768), 0, s, a);
       return yt8m::launch_status("lstm_persist_bwd_kernel");
     }
   }
@@ -2599,13 +2296,6 @@ int launch_bwd(const PersistBwdArgs& a, unsigned grid, hipStream_t s) {
   return a.nimg >= a.T ? launch_bwd_sh<NQB, true>(a, grid, s) : launch_bwd_sh<NQB, false>(a, grid, s);
 }
 }  // namespace
-
-// K-split workgroup pairs of the f16 backward recurrence (lstm_persist_bwd_kernel<.., P2>): -1 = the environment's choice
-// (YT8M_PERSIST_BWD_PAIR, default OFF: 13.7 vs 14.4 us/step stand-alone, but +0.66 ms on the headline step -- profiles/r6_recur_ab.txt block 4), 0 = off, 1 = on where the launch can take it.  Process-wide; for A/B runs and tests.
-extern "C" int yt8m_lstm_persist_set_pair(int mode) {
-  g_pair_mode.store(mode < 0 ? -1 : (mode ? 1 : 0));
-  return YT8M_OK;
-}
 
 extern "C" int yt8m_lstm_persist_bwd_supported(int64_t B, int64_t H) {
   return (persist_geometry(B, H, nullptr) && persist_geometry_bwd(B, H, nullptr)) ? 1 : 0;
@@ -2737,7 +2427,6 @@ int persist_bwd_impl(const float* gates, const float* Wh, int64_t ldw, const flo
                "row / launch maxima need the rotated backward epilogue on a per-step workspace (yt8m_lstm_persist_bwd_images_rows)");
   // H2: the scale words sit between the last exchange image and the debug tail; taken only when T images still fit in front of them
   a.h2 = 0; a.wword = nullptr; a.sc = nullptr; a.sc_bytes = 0;
-  a.px = nullptr; a.px_bytes = 0; a.nonce = 0;
   if (h2_wword && !img && !bf16 && (H == 512 || H == 1024)) {
     const int64_t scb = h2_scale_bytes(geo.NT16, H, T);
     if (scb < (1LL << 31) && images_in(workspace_bytes - scb, geo.NT16, 4 * H) >= T) {
@@ -2745,21 +2434,6 @@ int persist_bwd_impl(const float* gates, const float* Wh, int64_t ldw, const flo
       a.wword = static_cast<const unsigned*>(h2_wword);
       a.sc = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + workspace_bytes - DBG_BYTES - scb);
       a.sc_bytes = (unsigned)scb;
-      // K-split workgroup pairs (P2): the two workgroups that share a 128-byte line of gates sit on one XCD (the paired block -> unit
-      // group map), every workgroup owns <= 8 tiles, and the hand-off slots fit in front of the scale words.  Opt-in: YT8M_PERSIST_BWD_PAIR=1
-      static const bool pair_env_off = getenv("YT8M_PERSIST_BWD_PAIR") == nullptr || atoi(getenv("YT8M_PERSIST_BWD_PAIR")) == 0;
-      const int pair_mode = g_pair_mode.load();
-      const bool pair_off = pair_mode < 0 ? pair_env_off : pair_mode == 0;
-      const int64_t pxb = (int64_t)2 * geo.NT16 * geo.NUB * 2048;
-      const int n_it_max = (geo.NT16 + geo.RB - 1) / geo.RB;
-      if (!pair_off && bwd_rot(geo.pf, geo.NT16, geo.RB) && geo.per > 0 && (geo.NUB % (2 * geo.per)) == 0 && n_it_max <= 8 &&
-          images_in(workspace_bytes - scb - pxb, geo.NT16, 4 * H) >= T) {
-        static std::atomic<unsigned> g_nonce{1};
-        a.px = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + workspace_bytes - DBG_BYTES - scb - pxb);
-        a.px_bytes = (unsigned)pxb;
-        a.nonce = g_nonce.fetch_add(1) & 0x7FFFFu;           // (nonce * 8191 + step + 1 < 2^32; reuse after 2^19 launches)
-        if (a.nonce == 0) a.nonce = g_nonce.fetch_add(1) & 0x7FFFFu;
-      }
     }
   }
   const unsigned grid = (unsigned)(geo.NUB * geo.RB);
@@ -2789,8 +2463,10 @@ int persist_bwd_impl(const float* gates, const float* Wh, int64_t ldw, const flo
 
 
 // =====================================================================================================================
-// GRUCell on the persistent protocol (gru_persist.inl).  One launch runs T steps = 2T half-steps of a layer; the workspace holds the
-// control block and ONE exchange image per half-step (forward 2T + 1 images of [NT16 16, H]; backward T blocks of [NT16 16, 3H]).
+// GRUCell on the persistent protocol (gru_persist.inl).  One forward launch runs T steps = 2T half-steps of a layer; the workspace
+// holds the control block and ONE exchange image per half-step: 2T + 1 images of [NT16 16, H].  (Its size, 3 max(T, 1) + 3 such
+// images, still covers the T blocks of [NT16 16, 3H] of a persistent backward that has since been removed; kept so that the
+// layout of a caller's workspace does not move.)
 extern "C" int yt8m_gru_persist_supported(int64_t B, int64_t H) {
   static const bool off = getenv("YT8M_GRU_PERSIST") != nullptr && atoi(getenv("YT8M_GRU_PERSIST")) == 0;
   Geometry geo;
@@ -2858,80 +2534,6 @@ extern "C" int yt8m_gru_persist_fwd(float* zg, float* zc, const float* Wg_h, int
     case 6: rc = launch_gru_fwd<6>(a, grid, s); break;
     default: rc = launch_gru_fwd<8>(a, grid, s); break;
   }
-  if (rc != YT8M_OK) return rc;
-  return g_gate.done(dev, (int)grid, s);
-}
-
-// Backward of the same steps, last to first.  work [B,H]: dL/dh flowing into step t0 + T - 1 from later steps on entry (zeros, or
-// the final state's gradient), dL/dh_{t0 - 1} on exit -- launches over consecutive time ranges chain through it.  Writes dzg [F,B,2H]
-// and dzc [F,B,H] of the range (the operands of the hoisted weight-gradient / dx products), as yt8m_gru_layer_bwd does.
-extern "C" int yt8m_gru_persist_bwd(const float* zg, const float* zc, const float* Wg_h, int64_t ldg, const float* Wc_h, int64_t ldc,
-                                    const float* hs, const float* dout, float* dzg, float* dzc, float* work, const int32_t* num_frames,
-                                    int64_t t0, int64_t T, int64_t B, int64_t H, void* workspace, int64_t workspace_bytes,
-                                    yt8m_stream_t stream) {
-  using namespace yt8m;
-  YT8M_REQUIRE(t0 >= 0 && T >= 0 && B >= 0 && H >= 0, YT8M_E_SHAPE, "negative dimension");
-  if (T * B * H == 0) return YT8M_OK;
-  YT8M_REQUIRE(zg && zc && Wg_h && Wc_h && hs && dzg && dzc && work && workspace, YT8M_E_BADARG, "null operand");
-  YT8M_REQUIRE(ldg >= 2 * H && ldc >= H, YT8M_E_SHAPE, "leading dimension too small");
-  Geometry geo;
-  YT8M_REQUIRE(yt8m_gru_persist_supported(B, H) && persist_geometry(B, H, &geo), YT8M_E_SHAPE,
-               "shape not supported by the persistent GRU recurrence (see yt8m_gru_persist_supported)");
-  YT8M_REQUIRE(workspace_bytes >= yt8m_gru_persist_workspace_bytes(B, H, T), YT8M_E_SHAPE, "workspace too small");
-  YT8M_REQUIRE(T < (1 << 19), YT8M_E_SHAPE, "T too large");
-  hipStream_t s = as_stream(stream);
-  GruBwdArgs a;
-  a.zg = zg; a.zc = zc; a.Wg = Wg_h; a.Wc = Wc_h; a.ldg = ldg; a.ldc = ldc; a.hs = hs; a.dout = dout; a.dzg = dzg; a.dzc = dzc;
-  a.work = work; a.nf = num_frames;
-  a.ctl = static_cast<unsigned*>(workspace) + CTL_STICKY;
-  a.hx = reinterpret_cast<float*>(static_cast<char*>(workspace) + ctl_padded(geo.NT16));
-  a.t0 = (int)t0; a.T = (int)T; a.B = (int)B; a.H = (int)H;
-  a.NU = geo.NU; a.RB = geo.RB; a.NT16 = geo.NT16; a.per = geo.per; a.pf = geo.pf;
-  // 16 units per workgroup (H / 16 unit groups, every result column of the MFMA tile used) on HALF the chip by default (YT8M_GRU_BWD_CUS,
-  // the LSTM backward kernel's policy: four tiles = four chains per workgroup at B = 128, the other 128 CUs stay free for the hoisted
-  // products): 29.0 us/step; the whole chip (two chains per workgroup) 31.5; YT8M_GRU_BWD_U=8, the forward geometry (half of every B
-  // fragment zero) on 256 workgroups: 30.3 -- profiles/r6_gru_persist.txt.
-  static const int u_env = getenv("YT8M_GRU_BWD_U") ? atoi(getenv("YT8M_GRU_BWD_U")) : 16;
-  static const int cus_env = getenv("YT8M_GRU_BWD_CUS") ? atoi(getenv("YT8M_GRU_BWD_CUS")) : 128;
-  const bool u16 = u_env == 16;
-  if (u16) {
-    const int cus = device_cus(nullptr);
-    const int budget = (cus_env > 0 && cus_env < cus) ? cus_env : cus;
-    a.NU = (int)(H / 16);
-    int RB = std::max(1, budget / a.NU);
-    if (RB > geo.NT16 / 2) RB = std::max(1, geo.NT16 / 2);
-    a.RB = RB;
-    a.per = (RB <= 8 && (8 % RB) == 0 && (a.NU % (8 / RB)) == 0) ? 8 / RB : 0;
-    YT8M_REQUIRE((geo.NT16 + RB - 1) / RB <= MAX_LOCAL_TILES, YT8M_E_SHAPE, "batch too large for the persistent GRU recurrence");
-  }
-  const unsigned grid = (unsigned)(a.NU * a.RB);
-  int dev = 0;
-  device_cus(&dev);
-  a.stats = stats_ptr(dev);
-  ++g_stat_launches[dev];
-  g_stat_wgs[dev] += grid;
-  ProfScope prof(F_LSTM_BWD, s, 2.0 * (double)T * (double)B * (double)H * 3.0 * (double)H);
-  std::lock_guard<std::mutex> lk(g_gate.mu);
-  const int total_cus = device_cus(nullptr);
-  int grc = g_gate.admit(dev, (int)grid, std::max(0, total_cus - g_reserved_cus), s);
-  if (grc != YT8M_OK) return grc;
-  YT8M_HIP_CHECK(hipMemsetAsync(a.ctl, 0, (size_t)ctl_bytes(geo.NT16), s));
-  if (u16) {
-    switch (geo.NQ) {
-      case 2: hipLaunchKernelGGL((gru_persist_bwd_kernel<2, 16>), dim3(grid), dim3(768), 0, s, a); break;
-      case 4: hipLaunchKernelGGL((gru_persist_bwd_kernel<4, 16>), dim3(grid), dim3(768), 0, s, a); break;
-      case 6: hipLaunchKernelGGL((gru_persist_bwd_kernel<6, 16>), dim3(grid), dim3(768), 0, s, a); break;
-      default: hipLaunchKernelGGL((gru_persist_bwd_kernel<8, 16>), dim3(grid), dim3(768), 0, s, a); break;
-    }
-  } else {
-    switch (geo.NQ) {
-      case 2: hipLaunchKernelGGL((gru_persist_bwd_kernel<2, 8>), dim3(grid), dim3(768), 0, s, a); break;
-      case 4: hipLaunchKernelGGL((gru_persist_bwd_kernel<4, 8>), dim3(grid), dim3(768), 0, s, a); break;
-      case 6: hipLaunchKernelGGL((gru_persist_bwd_kernel<6, 8>), dim3(grid), dim3(768), 0, s, a); break;
-      default: hipLaunchKernelGGL((gru_persist_bwd_kernel<8, 8>), dim3(grid), dim3(768), 0, s, a); break;
-    }
-  }
-  int rc = launch_status("gru_persist_bwd_kernel");
   if (rc != YT8M_OK) return rc;
   return g_gate.done(dev, (int)grid, s);
 }

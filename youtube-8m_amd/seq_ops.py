@@ -116,15 +116,12 @@ class _GruLayer(torch.autograd.Function):
         out = torch.empty((F, B, H), dtype=torch.float32, device=dev)
         nf = _nf(num_frames)
         L = _lib.lib()
-        # one persistent launch per direction (csrc/gru_persist.inl) where the shape allows it, else the per-step kernels (2 + 3 launches
-        # per time step); YT8M_GRU_PERSIST=0 forces the latter
-        ctx.pws = None
-        if F > 0 and L.yt8m_gru_persist_supported(B, H) and (GRU_PERSIST_FWD or GRU_PERSIST_BWD):
-            main = torch.cuda.current_stream(dev)
-            ctx.pws = _persist_ws(dev, main, "gru", L.yt8m_gru_persist_workspace_bytes(B, H, F))
-        if ctx.pws is not None and GRU_PERSIST_FWD:
+        # one persistent forward launch (csrc/gru_persist.inl) where the shape allows it, else the per-step kernels (2 launches per
+        # time step); YT8M_GRU_PERSIST=0 forces the latter
+        if F > 0 and L.yt8m_gru_persist_supported(B, H) and GRU_PERSIST_FWD:
+            pws = _persist_ws(dev, torch.cuda.current_stream(dev), "gru", L.yt8m_gru_persist_workspace_bytes(B, H, F))
             _lib.check(L.yt8m_gru_persist_fwd(_p(zg), _p(zc), _p(Wg.data[Din:]), 2 * H, _p(Wc.data[Din:]), H, _p(hs), _p(rh), _p(out),
-                                              _p(nf), 0, F, B, H, _p(ctx.pws), ctx.pws.numel(), _stream()))
+                                              _p(nf), 0, F, B, H, _p(pws), pws.numel(), _stream()))
         else:
             ws = ops._workspace(dev)
             _lib.check(L.yt8m_gru_layer_fwd(_p(zg), _p(zc), _p(Wg.data[Din:]), 2 * H, _p(Wc.data[Din:]), H, _p(hs), _p(rh),
@@ -150,20 +147,10 @@ class _GruLayer(torch.autograd.Function):
         work = torch.empty((3, B, H), dtype=torch.float32, device=dev)
         dout = None if dout is None else _f32c(dout)
         dh_final = None if dh_final is None else _f32c(dh_final)
-        if ctx.pws is not None and GRU_PERSIST_BWD:
-            if dh_final is not None:
-                work[0].copy_(dh_final)
-            else:
-                work[0].zero_()
-            _lib.check(_lib.lib().yt8m_gru_persist_bwd(_p(zg), _p(zc), _p(Wg.data[Din:]), 2 * H, _p(Wc.data[Din:]), H, _p(hs), _p(dout),
-                                                       _p(dzg), _p(dzc), _p(work), _p(nf), 0, F, B, H, _p(ctx.pws), ctx.pws.numel(),
-                                                       _stream()))
-            ctx.pws = None
-        else:
-            ws = ops._workspace(dev)
-            _lib.check(_lib.lib().yt8m_gru_layer_bwd(_p(zg), _p(zc), _p(Wg.data[Din:]), 2 * H, _p(Wc.data[Din:]), H, _p(hs), _p(dout),
-                                                     _p(dh_final), _p(dzg), _p(dzc), _p(work), _p(nf), F, B, H, _p(ws),
-                                                     ws.numel() * 4, _stream()))
+        ws = ops._workspace(dev)
+        _lib.check(_lib.lib().yt8m_gru_layer_bwd(_p(zg), _p(zc), _p(Wg.data[Din:]), 2 * H, _p(Wc.data[Din:]), H, _p(hs), _p(dout),
+                                                 _p(dh_final), _p(dzg), _p(dzc), _p(work), _p(nf), F, B, H, _p(ws),
+                                                 ws.numel() * 4, _stream()))
         x2 = x_tm.view(F * B, Din) if frames is None else None
         g2, c2 = dzg.view(F * B, 2 * H), dzc.view(F * B, H)
         bf = ctx.bf16
@@ -298,17 +285,15 @@ def lnlstm_layer(x_tm, W, gammas, betas, num_frames, forget_bias=1.0, keep_prob=
 _SIDE = {}
 
 
-def _side_streams(device, L, persistent=False, separate_gemm=False):
+def _side_streams(device, L, persistent=False):
     """Per device: one stream per layer (its projection / dx GEMMs and its recurrence run in order on it) and one for the
     weight-gradient GEMMs.  Measured on the 2-layer BASELINE configs[3] stack (B = 128): a separate GEMM stream per layer is
     no better (51.7 vs 49.0 ms/step).  The layer streams are HIGH priority when the recurrence is the persistent kernel: it needs
     every workgroup resident, and behind a high-priority queue it takes freed CUs before the remaining workgroups of a running
     weight-gradient GEMM do (a partially resident recurrence spins on its CUs while the GEMM crawls on the rest: 28.6 vs 46.6
     ms/step run to run without it).  With the per-step kernels (600 launches) priority queues are far worse (96 ms), so those
-    keep normal streams.  separate_gemm (forward wavefront of half-chip recurrences): the projections get normal-priority streams
-    of their own -- on the layer stream a projection's workgroups compete at high priority with the OTHER layer's recurrence for
-    the CUs it needs (one run in three took 41 instead of 24.6 ms/step)."""
-    pool = _SIDE.setdefault((device, bool(persistent)), dict(r=[], g=[], w=None))
+    keep normal streams."""
+    pool = _SIDE.setdefault((device, bool(persistent)), dict(r=[], w=None))
     if persistent and len(pool["r"]) < L:
         # the library's own streams (csrc/lstm_stack.hip): every stream of a process is multiplexed onto a few hardware queues, and a
         # second set of layer streams next to the native stack's put both layers of this orchestration on ONE queue (bf16 variant of
@@ -322,10 +307,6 @@ def _side_streams(device, L, persistent=False, separate_gemm=False):
         pool["r"].append(torch.cuda.Stream(device=device, priority=REC_STREAM_PRIORITY if persistent else 0))
     if pool["w"] is None:
         pool["w"] = torch.cuda.Stream(device=device)
-    if separate_gemm:
-        while len(pool["g"]) < L:
-            pool["g"].append(torch.cuda.Stream(device=device))
-        return pool["r"][:L], pool["g"][:L], pool["w"]
     return pool["r"][:L], pool["r"][:L], pool["w"]
 
 
@@ -338,22 +319,9 @@ def _chunks(F, n):
 import os as _os
 PERSIST = _os.environ.get("YT8M_LSTM_PERSIST", "1") != "0"        # persistent recurrence kernels (csrc/lstm_persist.hip)
 U8_BETA = 128.0 * 4.0 / 255.0 + (4.0 / 512.0 - 2.0)     # dequantise(q) = (4/255) (q - 128) + U8_BETA
-BWD_CHUNKS = int(_os.environ.get("YT8M_LSTM_BWD_CHUNKS", "0"))    # 0: same partition as the forward pass
-# explicit backward partition as fractions of F in forward-time order, e.g. "1,2,3" -> chunks of F/6, F/3, F/2 (the backward pass
-# runs them last to first: a long first launch, a short last one whose weight-gradient tail is short)
-BWD_PARTS = [float(v) for v in _os.environ.get("YT8M_LSTM_BWD_PARTS", "").split(",") if v]
 
 
 def _bwd_parts(F, fwd_parts, persistent=False):
-    if BWD_PARTS:
-        tot, edges, acc = sum(BWD_PARTS), [0], 0.0
-        for v in BWD_PARTS:
-            acc += v
-            edges.append(min(F, int(round(F * acc / tot))))
-        edges[-1] = F
-        return [(a, b - a) for a, b in zip(edges[:-1], edges[1:]) if b > a]
-    if BWD_CHUNKS > 0:
-        return _chunks(F, BWD_CHUNKS)
     if persistent and PERSIST_BWD_CHUNKS > 0:
         return _chunks(F, PERSIST_BWD_CHUNKS)
     return fwd_parts
@@ -363,13 +331,6 @@ def _bwd_parts(F, fwd_parts, persistent=False):
 # shorter GEMM tail than two; BASELINE configs[3], B = 128: 24.3 ms/step against 24.8 with 2 + 2, 24.4 with 1 + 4).
 PERSIST_FWD_CHUNKS = int(_os.environ.get("YT8M_LSTM_PERSIST_FWD_CHUNKS", "1"))
 PERSIST_BWD_CHUNKS = int(_os.environ.get("YT8M_LSTM_PERSIST_BWD_CHUNKS", "3"))
-PERSIST_DBROWS = False
-# half-chip forward recurrences of two layers side by side (opt-in: 24.6 ms/step against 25.3 at B = 128, H = 1024 when the
-# projections share the high-priority layer streams, but one run in three then took 41 ms; with projection streams of their own --
-# what the code does -- it is stable at 27.9)
-FWD_WAVEFRONT = _os.environ.get("YT8M_LSTM_FWD_WAVEFRONT", "0") != "0"
-FWD_WAVEFRONT_SHARED = _os.environ.get("YT8M_LSTM_FWD_WAVEFRONT", "0") == "2"   # projections on the (high-priority) layer streams
-FWD_WAVEFRONT_CHUNKS = int(_os.environ.get("YT8M_LSTM_FWD_WAVEFRONT_CHUNKS", "10"))
 REC_STREAM_PRIORITY = int(_os.environ.get("YT8M_REC_STREAM_PRIORITY", "-1"))
 PERSIST_STEP_IMAGES = _os.environ.get("YT8M_PERSIST_STEP_IMAGES", "1") != "0"
 PERSIST_STEP_IMAGES_MAX_BYTES = 8 << 30                 # per layer; larger launches keep the two-image exchange
@@ -453,12 +414,11 @@ def check_persist_errors():
     if err is not None:
         raise err
 PERSIST_BWD = _os.environ.get("YT8M_LSTM_PERSIST_BWD", "1") != "0"
-# GRUCell on the persistent protocol (csrc/gru_persist.inl), per direction; the library switch YT8M_GRU_PERSIST=0 turns both off.
-# Measured at B = 128, H = 1024, F = 300 (profiles/r6_gru_persist.txt): forward 13.9 us/step in one launch against 17.6 in 600 -> ON;
-# backward 29.0 us/step against 20.3 for the three per-step launches (two exchange rounds per step on a K = 3H reduction: every
-# item's fragment fetch is exposed with four tiles per workgroup) -> parity-tested, OPT-IN.
+# GRUCell forward on the persistent protocol (csrc/gru_persist.inl); the library switch YT8M_GRU_PERSIST=0 turns it off too.
+# Measured at B = 128, H = 1024, F = 300 (profiles/r6_gru_persist.txt): 13.9 us/step in one launch against 17.6 in 600.  A persistent
+# backward ran at 29.0 us/step against 20.3 for the per-step launches (two exchange rounds per step on a K = 3H reduction: every
+# item's fragment fetch is exposed with four tiles per workgroup) and was removed.
 GRU_PERSIST_FWD = _os.environ.get("YT8M_GRU_PERSIST_FWD", "1") != "0"
-GRU_PERSIST_BWD = _os.environ.get("YT8M_GRU_PERSIST_BWD", "0") != "0"
 PERSIST_CHECK = _os.environ.get("YT8M_PERSIST_CHECK", "0") == "1"  # debug: synchronise + check the timeout word after each launch
 X3 = _os.environ.get("YT8M_GEMM_X3", "1") != "0"      # hoisted fp32 products on the bf16 pipe (three-plane split, csrc/gemm_x3.hip)
 X3_MIN_ROWS = 1024                                      # F * B below which the fp32-MFMA kernel's smaller tiles win
@@ -697,8 +657,8 @@ class _LstmStack(torch.autograd.Function):
         # orchestration below takes over.  YT8M_NATIVE_DROPOUT=0 keeps dropout on the orchestration.)
         u8_in = x_tm.dtype == torch.uint8
         drop_native = drop_ and NATIVE_DROPOUT and not u8_in and not bf16 and L <= 8
-        if (NATIVE_STACK and nat_ok and X3 and PERSIST_BWD and PERSIST_STEP_IMAGES and (not drop_ or drop_native) and not FWD_WAVEFRONT and
-                PERSIST_FWD_CHUNKS > 0 and PERSIST_BWD_CHUNKS > 0 and BWD_CHUNKS == 0 and not BWD_PARTS and len(set(Hs)) == 1):
+        if (NATIVE_STACK and nat_ok and X3 and PERSIST_BWD and PERSIST_STEP_IMAGES and (not drop_ or drop_native) and
+                PERSIST_FWD_CHUNKS > 0 and PERSIST_BWD_CHUNKS > 0 and len(set(Hs)) == 1):
             u8 = x_tm.dtype == torch.uint8
             D0 = x_tm.shape[2]
             desc = _stack_desc(B, F, D0, Hs[0], L, u8, forget_bias, (not u8) and bool(ctx.needs_input_grad[0]), bf16=bool(bf16),
@@ -708,14 +668,6 @@ class _LstmStack(torch.autograd.Function):
         if own and PERSIST_FWD_CHUNKS > 0:
             parts = _chunks(F, PERSIST_FWD_CHUNKS)
         bwd_parts = _bwd_parts(F, _chunks(F, chunks), own)
-        # Wavefront of half-chip forward recurrences (opt-in, see FWD_WAVEFRONT): with the recurrent product on the bf16 pipe a layer's
-        # recurrence is bound by its dependency chain, not by matrix time, so two layers can run side by side on half the chip each
-        # (8 chains per workgroup) at 11.4 us / step and layer against 8.5 on the whole chip one after the other; finer time chunks
-        # shorten the ramps.  The backward pass keeps the caller's partition.
-        half_fwd = (FWD_WAVEFRONT and pers and L >= 2 and PERSIST_STEP_IMAGES and not bf16 and F >= 8 * FWD_WAVEFRONT_CHUNKS and
-                    all(lib.yt8m_lstm_persist_fwd_on_bf16_pipe(B, h) for h in Hs) and _os.environ.get("YT8M_PERSIST_CUS") is None)
-        if half_fwd:
-            parts = _chunks(F, max(int(chunks), FWD_WAVEFRONT_CHUNKS))
         if x_tm.dtype == torch.uint8:
             # raw reader output [B,F,D] (batch-major): the layer-0 projection takes the bytes themselves (csrc/u8proj.hip) --
             # one conversion pass writes (q - 128) as bf16 in time-major order (three copies side by side: the three bf16
@@ -742,7 +694,7 @@ class _LstmStack(torch.autograd.Function):
         assert (F, B) == tuple(x_tm.shape[:2])
         dev = x_tm.device
         main = torch.cuda.current_stream(dev)
-        rs, gs, _ = _side_streams(dev, L, pers, separate_gemm=half_fwd and not FWD_WAVEFRONT_SHARED)
+        rs, gs, _ = _side_streams(dev, L, pers)
         ctx.pers = pers
         bf16 = bool(bf16) and B % 2 == 0 and min(T for _, T in parts) * B >= ops.BF16_MIN_ROWS
         drop = input_keep_prob is not None and float(input_keep_prob) < 1.0
@@ -809,62 +761,56 @@ class _LstmStack(torch.autograd.Function):
                     st["Wp16"] = torch.empty(H_ * 4 * H_, dtype=torch.bfloat16, device=dev)
                     _lib.check(lib.yt8m_lstm_pack_bf16(_p(st["W"].data[st["Din"]:]), 4 * H_, H_, _p(st["Wp16"]), None, _stream()))
         r_done = [[torch.cuda.Event() for _ in parts] for _ in range(L)]
-        if half_fwd:
-            _lib.check(lib.yt8m_lstm_persist_set_cus(torch.cuda.get_device_properties(dev).multi_processor_count // 2, -1))
-        try:
-            for c, (t0, T) in enumerate(parts):
-                for l, st in enumerate(layers):
-                    Din, H = st["Din"], st["H"]
-                    with torch.cuda.stream(gs[l]):                      # hoisted input projection of the chunk
-                        if l > 0:
-                            gs[l].wait_event(r_done[l - 1][c])
-                        if drop:
-                            xc = st["x"][t0:t0 + T]
-                            src = x_tm[t0:t0 + T] if l == 0 else xc
-                            _lib.check(lib.yt8m_dropout_f32(_p(src), _p(xc), xc.numel(), float(input_keep_prob), int(seeds[l]),
-                                                            t0 * B * Din, _stream()))
-                        if "W3T" in st and Qimg is not None:
-                            zc = st["z"][t0:t0 + T].view(T * B, 4 * H)
-                            ws = ops._workspace(dev)
-                            _lib.check(lib.yt8m_gemm_x1x3_nt(T * B, 4 * H, Din, _p(Qimg[(t0 * B // 32) * (Din // 16) * 1024:]), _p(st["W3T"].buf),
-                                                             _p(zc), 4 * H, _p(st["b"].data), _p(rrow[t0 * B:]), _p(st["Wcs"]), U8_BETA,
-                                                             _p(ws), ws.numel() * 4, _stream()))
-                        elif "W3T" in st:
-                            zc = st["z"][t0:t0 + T].view(T * B, 4 * H)
-                            ops.gemm_bf16_nt_grouped([dict(A=Qb[t0 * B:(t0 + T) * B], B=st["W3T"], out=zc)])
-                            _lib.check(lib.yt8m_rowscale_bias_f32(_p(zc), T * B, 4 * H, 4 * H, _p(rrow[t0 * B:]), _p(st["Wcs"]),
-                                                                  U8_BETA, _p(st["b"].data), _stream()))
-                        elif st["bf16"]:
-                            ops.gemm_bf16_nt_grouped([dict(A=ops.cast_bf16(st["x"][t0:t0 + T].view(T * B, Din)), B=st["WxT"],
-                                                           out=st["z"][t0:t0 + T].view(T * B, 4 * H), bias=st["b"].data)])
-                        elif st["x3"]:
-                            xi = ops.x3_split(st["x"][t0:t0 + T].view(T * B, Din))[0]
-                            ops.gemm_x3_grouped([dict(A=xi, B=st["WxT3"], out=st["z"][t0:t0 + T].view(T * B, 4 * H), bias=st["b"].data)])
-                        else:
-                            ops.gemm(st["x"][t0:t0 + T].view(T * B, Din), st["W"].data[:Din], out=st["z"][t0:t0 + T].view(T * B, 4 * H),
-                                     bias=st["b"].data)
-                        g_ev = torch.cuda.Event()
-                        g_ev.record(gs[l])
-                    with torch.cuda.stream(rs[l]):                      # recurrence steps of the chunk
-                        rs[l].wait_event(g_ev)
+        for c, (t0, T) in enumerate(parts):
+            for l, st in enumerate(layers):
+                Din, H = st["Din"], st["H"]
+                with torch.cuda.stream(gs[l]):                      # hoisted input projection of the chunk
+                    if l > 0:
+                        gs[l].wait_event(r_done[l - 1][c])
+                    if drop:
+                        xc = st["x"][t0:t0 + T]
+                        src = x_tm[t0:t0 + T] if l == 0 else xc
+                        _lib.check(lib.yt8m_dropout_f32(_p(src), _p(xc), xc.numel(), float(input_keep_prob), int(seeds[l]),
+                                                        t0 * B * Din, _stream()))
+                    if "W3T" in st and Qimg is not None:
+                        zc = st["z"][t0:t0 + T].view(T * B, 4 * H)
                         ws = ops._workspace(dev)
-                        if st["rec16"]:
-                            _lib.check(lib.yt8m_lstm_steps_fwd_bf16(_p(st["z"]), _p(st["Wp16"]), _p(st["cs"]), _p(st["hs"]), _p(st["hs16"]),
-                                                                    _p(st["out"]), _p(nf), t0, T, B, H, float(forget_bias), _stream()))
-                        elif st["pws"] is not None:
-                            _lib.check(lib.yt8m_lstm_persist_fwd(_p(st["z"]), _p(st["W"].data[Din:]), 4 * H, _p(st["cs"]), _p(st["hs"]),
-                                                                 _p(st["out"]), _p(nf), t0, T, B, H, float(forget_bias), _p(st["pws"]),
-                                                                 st["pws"].numel(), _stream()))
-                            if PERSIST_CHECK:
-                                _lib.check(lib.yt8m_lstm_persist_status(_p(st["pws"]), _stream()))
-                        else:
-                            _lib.check(lib.yt8m_lstm_steps_fwd(_p(st["z"]), _p(st["W"].data[Din:]), 4 * H, _p(st["Wp"]), _p(st["cs"]),
-                                                               _p(st["hs"]), _p(st["out"]), _p(nf), t0, T, B, H, float(forget_bias),
-                                                               _p(ws), ws.numel() * 4, _stream()))
-                        r_done[l][c].record(rs[l])
-        finally:
-            if half_fwd:                                        # process-wide CU budget: restored whatever happens in the loop
-                _lib.check(lib.yt8m_lstm_persist_set_cus(-1, -1))
+                        _lib.check(lib.yt8m_gemm_x1x3_nt(T * B, 4 * H, Din, _p(Qimg[(t0 * B // 32) * (Din // 16) * 1024:]), _p(st["W3T"].buf),
+                                                         _p(zc), 4 * H, _p(st["b"].data), _p(rrow[t0 * B:]), _p(st["Wcs"]), U8_BETA,
+                                                         _p(ws), ws.numel() * 4, _stream()))
+                    elif "W3T" in st:
+                        zc = st["z"][t0:t0 + T].view(T * B, 4 * H)
+                        ops.gemm_bf16_nt_grouped([dict(A=Qb[t0 * B:(t0 + T) * B], B=st["W3T"], out=zc)])
+                        _lib.check(lib.yt8m_rowscale_bias_f32(_p(zc), T * B, 4 * H, 4 * H, _p(rrow[t0 * B:]), _p(st["Wcs"]),
+                                                              U8_BETA, _p(st["b"].data), _stream()))
+                    elif st["bf16"]:
+                        ops.gemm_bf16_nt_grouped([dict(A=ops.cast_bf16(st["x"][t0:t0 + T].view(T * B, Din)), B=st["WxT"],
+                                                       out=st["z"][t0:t0 + T].view(T * B, 4 * H), bias=st["b"].data)])
+                    elif st["x3"]:
+                        xi = ops.x3_split(st["x"][t0:t0 + T].view(T * B, Din))[0]
+                        ops.gemm_x3_grouped([dict(A=xi, B=st["WxT3"], out=st["z"][t0:t0 + T].view(T * B, 4 * H), bias=st["b"].data)])
+                    else:
+                        ops.gemm(st["x"][t0:t0 + T].view(T * B, Din), st["W"].data[:Din], out=st["z"][t0:t0 + T].view(T * B, 4 * H),
+                                 bias=st["b"].data)
+                    g_ev = torch.cuda.Event()
+                    g_ev.record(gs[l])
+                with torch.cuda.stream(rs[l]):                      # recurrence steps of the chunk
+                    rs[l].wait_event(g_ev)
+                    ws = ops._workspace(dev)
+                    if st["rec16"]:
+                        _lib.check(lib.yt8m_lstm_steps_fwd_bf16(_p(st["z"]), _p(st["Wp16"]), _p(st["cs"]), _p(st["hs"]), _p(st["hs16"]),
+                                                                _p(st["out"]), _p(nf), t0, T, B, H, float(forget_bias), _stream()))
+                    elif st["pws"] is not None:
+                        _lib.check(lib.yt8m_lstm_persist_fwd(_p(st["z"]), _p(st["W"].data[Din:]), 4 * H, _p(st["cs"]), _p(st["hs"]),
+                                                             _p(st["out"]), _p(nf), t0, T, B, H, float(forget_bias), _p(st["pws"]),
+                                                             st["pws"].numel(), _stream()))
+                        if PERSIST_CHECK:
+                            _lib.check(lib.yt8m_lstm_persist_status(_p(st["pws"]), _stream()))
+                    else:
+                        _lib.check(lib.yt8m_lstm_steps_fwd(_p(st["z"]), _p(st["W"].data[Din:]), 4 * H, _p(st["Wp"]), _p(st["cs"]),
+                                                           _p(st["hs"]), _p(st["out"]), _p(nf), t0, T, B, H, float(forget_bias),
+                                                           _p(ws), ws.numel() * 4, _stream()))
+                    r_done[l][c].record(rs[l])
         for l in range(L):
             main.wait_event(r_done[l][-1])
         # the backward pass may cut time differently (all buffers are whole-layer): its first recurrence chunk runs with nothing
@@ -1052,12 +998,10 @@ class _LstmStack(torch.autograd.Function):
                                                                 _p(st["dz16"]), _p(st["work"]), st["phase"], _p(nf), t0, T, B, H,
                                                                 _stream()))
                     elif st.get("pws") is not None and PERSIST_BWD and lib.yt8m_lstm_persist_bwd_supported(B, H):
-                        # bias gradient as per-row sums in the epilogue: measured SLOWER (37.1 -> 40.3 ms/step: four more scattered
-                        # read-modify-writes per lane and item sit in the CU's memory queue in front of the exchange loads); off
-                        if PERSIST_DBROWS and "dbrows" not in st and b.grad is not None:
-                            st["dbrows"] = torch.zeros((B, 4 * H), dtype=torch.float32, device=dev)
+                        # (no dbias_rows: the bias gradient as per-row sums in the epilogue measured SLOWER, 37.1 -> 40.3 ms/step --
+                        # four more scattered read-modify-writes per lane and item in front of the exchange loads)
                         _lib.check(lib.yt8m_lstm_persist_bwd(_p(st["z"]), _p(W.data[Din:]), 4 * H, _p(st["cs"]), _p(st["dout"]),
-                                                             _p(st["dz"]), _p(st["work"]), st["phase"], _p(st.get("dbrows")), _p(nf),
+                                                             _p(st["dz"]), _p(st["work"]), st["phase"], None, _p(nf),
                                                              t0, T, B, H, _p(st["pws"]), st["pws"].numel(), _stream()))
                         if PERSIST_CHECK:
                             _lib.check(lib.yt8m_lstm_persist_status(_p(st["pws"]), _stream()))
@@ -1126,13 +1070,12 @@ class _LstmStack(torch.autograd.Function):
                         else:
                             ops.gemm(st["x"][t0:t0 + T].view(T * B, Din), dzc, out=W.grad[:Din], transA=True, beta=beta, role="dw")
                             ops.gemm(st["hs"][t0:t0 + T].view(T * B, H), dzc, out=W.grad[Din:], transA=True, beta=beta, role="dw")
-                    if b.grad is not None and ("dbrows" not in st or c == 0):
+                    if b.grad is not None:
                         beta = wbeta.get(id(b))
                         if beta is None:
                             beta = b.grad_beta()
                             wbeta[id(b)] = 1.0
-                        # persistent backward: the per-row sums are complete after the last (earliest) chunk -> one [B,4H] column sum
-                        ops.colsum(st["dbrows"] if "dbrows" in st else dzc, b.grad.view(-1), beta=beta)
+                        ops.colsum(dzc, b.grad.view(-1), beta=beta)
         fin = torch.cuda.Event()
         fin.record(sw)                                              # sw waited for every recurrence chunk
         main.wait_event(fin)
