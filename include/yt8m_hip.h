@@ -904,6 +904,29 @@ int yt8m_reverse_sequence_u8(const uint8_t* x, const int32_t* num_frames, uint8_
 int yt8m_reverse_sequence_f32_tm(const float* x, int64_t ldx, const int32_t* num_frames, float* y, int64_t ldy, int64_t y_col0,
                                  int64_t F, int64_t B, int64_t H, yt8m_stream_t stream);
 
+/* ---- training-time data augmenters (W/all_data_augmentation; csrc/augment.hip) -----------------------------------------------------
+ * Per video b with n = num_frames[b] clamped to [0, F] and s = max(n / 2, 1) (integer division).
+ * yt8m_half_segments_*: HalfAugmenter (half_augmenter.py:8-45).  x [B,F,D] -> y [3B,F,D] = [originals; first halves; second halves]:
+ *   rows b are x[b] as they are; rows B + b and 2B + b hold frames [0, s) and [s, 2s) of x[b] at positions [0, s) and zeros after them
+ *   (for the bytes: the reader's padding).  num_frames_out [3B] = [num_frames; s; s], written on the device.  Out of place (every
+ *   operand disjoint); 16-byte accesses when the rows allow them.
+ * yt8m_half_segment_means_u8: HalfVideoAugmenter (half_video_augmenter.py:8-16) in one pass over the bytes: x [3B,D] fp32 = the means
+ *   of the dequantised frames of the three row blocks above (sum over the frames / num_frames_out).  Rows with no real frame (n = 0;
+ *   the second half of n = 1) are 0, the reference's 0/0 for n = 0 included (as yt8m_dequant_mean_l2norm_u8).  l2norm != 0 also
+ *   L2-normalises every row (the DefaultTransformer fold); the whole-video rows are then yt8m_dequant_mean_l2norm_u8's bit for bit.
+ *   D <= 2048.
+ * yt8m_dequant_noise_u8: NoiseAugmenter on frames (noise_augmenter.py:8-12): y [B,F,D] fp32 = utils.Dequantize(q) (an fp32 multiply,
+ *   then an add; padding frames 0) + stddev * N(0,1) over EVERY element, with the Philox layout of yt8m_add_noise_f32 at offset 0:
+ *   bit for bit the dequantisation followed by yt8m_add_noise_f32(seed).  stddev = 0: the plain dequantisation. */
+int yt8m_half_segments_u8(const uint8_t* x, const int32_t* num_frames, uint8_t* y, int32_t* num_frames_out, int64_t B, int64_t F,
+                          int64_t D, yt8m_stream_t stream);
+int yt8m_half_segments_f32(const float* x, const int32_t* num_frames, float* y, int32_t* num_frames_out, int64_t B, int64_t F,
+                           int64_t D, yt8m_stream_t stream);
+int yt8m_half_segment_means_u8(const uint8_t* q, const int32_t* num_frames, float* x, int64_t B, int64_t F, int64_t D, int l2norm,
+                               float eps, yt8m_stream_t stream);
+int yt8m_dequant_noise_u8(const uint8_t* q, const int32_t* num_frames, float* y, int64_t B, int64_t F, int64_t D, float stddev,
+                          uint64_t seed, yt8m_stream_t stream);
+
 /* ---- masked softmax over frames + renormalise (lstm_attention_max_pooling_model.py:59-60) -------
  * act [B,F,A] -> w [B,F,A]: w = mask * softmax_F(act) / sum_F(mask * softmax_F(act)).  bwd: dact from dw. */
 int yt8m_attn_softmax_fwd(const float* act, const int32_t* num_frames, float* w, int64_t B, int64_t F,

@@ -305,6 +305,10 @@ SIGNATURES = {
     "yt8m_reverse_sequence_u8": (c_int, [P, P, P, c_int64, c_int64, c_int64, P]),
     "yt8m_reverse_sequence_f32_tm": (c_int, [P, c_int64, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, P]),
     "yt8m_lstm_stack_use_streams": (c_int, [c_int, ctypes.POINTER(c_int)]),
+    "yt8m_half_segments_u8": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, P]),
+    "yt8m_half_segments_f32": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, P]),
+    "yt8m_half_segment_means_u8": (c_int, [P, P, P, c_int64, c_int64, c_int64, c_int, c_float, P]),
+    "yt8m_dequant_noise_u8": (c_int, [P, P, P, c_int64, c_int64, c_int64, c_float, ctypes.c_uint64, P]),
 }
 
 # The ABI this host binds (include/yt8m_hip.h, yt8m_abi_version): workspace layouts and argument meanings, not just symbols.

@@ -29,4 +29,15 @@ __device__ __forceinline__ float uniform_at(uint64_t e, uint64_t key) {
   return u01(w);
 }
 
+// Box-Muller on word pairs: (x, y) -> normals 0, 1 and (z, w) -> normals 2, 3 of the block (random.hip noise_kernel, augment.hip)
+__device__ __forceinline__ void normal4(const U4& r, float z[4]) {
+  const float ra = sqrtf(-2.0f * logf(1.0f - u01(r.x))), th = 6.283185307179586f * u01(r.y);
+  z[0] = ra * cosf(th); z[1] = ra * sinf(th);
+  const float rb = sqrtf(-2.0f * logf(1.0f - u01(r.z))), ph = 6.283185307179586f * u01(r.w);
+  z[2] = rb * cosf(ph); z[3] = rb * sinf(ph);
+}
+
+// x + stddev * z: one definition, so that every caller rounds (contracts) it the same way
+__device__ __forceinline__ float add_normal(float x, float stddev, float z) { return x + stddev * z; }
+
 }  // namespace yt8m_rng

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ 
   }
 }
 
-// Box-Muller on word pairs (x,y) -> elements 0,1 and (z,w) -> elements 2,3 of the block
+// Box-Muller on word pairs (x,y) -> elements 0,1 and (z,w) -> elements 2,3 of the block (yt8m_rng::normal4)
 __global__ __launch_bounds__(256) void noise_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n, float stddev,
                                                     uint64_t seed, int64_t offset) {
   const int64_t g = (offset >> 2) + (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -51,16 +51,11 @@ __global__ __launch_bounds__(256) void noise_kernel(const float* __restrict__ x,
   if (e0 >= n) return;
   const U4 r = philox4x32_10((uint64_t)g, seed);
   float z[4];
-  {
-    const float ra = sqrtf(-2.0f * logf(1.0f - u01(r.x))), th = 6.283185307179586f * u01(r.y);
-    z[0] = ra * cosf(th); z[1] = ra * sinf(th);
-    const float rb = sqrtf(-2.0f * logf(1.0f - u01(r.z))), ph = 6.283185307179586f * u01(r.w);
-    z[2] = rb * cosf(ph); z[3] = rb * sinf(ph);
-  }
+  yt8m_rng::normal4(r, z);
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int64_t e = e0 + k;
-    if (e >= 0 && e < n) y[e] = x[e] + stddev * z[k];
+    if (e >= 0 && e < n) y[e] = yt8m_rng::add_normal(x[e], stddev, z[k]);
   }
 }
 

@@ -562,6 +562,65 @@ def dequant_mean_l2norm(q, num_frames=None, eps=1e-12):
     return x
 
 
+# ---- training-time data augmenters (csrc/augment.hip; data_augmentation.py) --------------------------------------------------------
+def _frames_nf(x, num_frames):
+    """num_frames may be on the host (as the reader hands it over): it is copied to the frames' device."""
+    _dev(x)
+    if x.dim() != 3:
+        raise ValueError("expected frames [B,F,D], got %d dimensions" % x.dim())
+    if num_frames is None:
+        raise ValueError("the frame augmenters need num_frames")
+    return x.contiguous(), num_frames.to(device=x.device, dtype=torch.int32).contiguous()
+
+
+def half_segments(x, num_frames):
+    """HalfAugmenter's gather (W/all_data_augmentation/half_augmenter.py:8-45): uint8 or float32 frames [B,F,D] -> ([3B,F,D] of the
+    same dtype, num_frames [3B] int32 on the device) = [originals; first halves; second halves], zeros past each half's
+    s = max(n // 2, 1) frames.  Frames are data: no gradient."""
+    x, nf = _frames_nf(x, num_frames)
+    B, F, D = x.shape
+    y = torch.empty((3 * B, F, D), dtype=x.dtype, device=x.device)
+    nf_out = torch.empty((3 * B,), dtype=torch.int32, device=x.device)
+    if x.dtype == torch.uint8:
+        fn = _lib.lib().yt8m_half_segments_u8
+    elif x.dtype == torch.float32:
+        fn = _lib.lib().yt8m_half_segments_f32
+    else:
+        raise TypeError("expected uint8 or float32 frames, got %s" % x.dtype)
+    _lib.check(fn(_p(x), _p(nf), _p(y), _p(nf_out), B, F, D, _stream()))
+    return y, nf_out
+
+
+def half_segment_means(q, num_frames, l2norm=False, eps=1e-12):
+    """HalfVideoAugmenter (W/all_data_augmentation/half_video_augmenter.py:8-16) in one pass over the bytes: uint8 [B,F,D] -> float32
+    [3B,D], the means of the dequantised frames of the whole video and of its two halves (0 where there is no real frame).  l2norm:
+    also L2-normalise every row (the DefaultTransformer, folded)."""
+    q, nf = _frames_nf(q, num_frames)
+    if q.dtype != torch.uint8:
+        raise TypeError("expected the reader's uint8 frames, got %s" % q.dtype)
+    B, F, D = q.shape
+    x = torch.empty((3 * B, D), dtype=torch.float32, device=q.device)
+    _lib.check(_lib.lib().yt8m_half_segment_means_u8(_p(q), _p(nf), _p(x), B, F, D, 1 if l2norm else 0, eps, _stream()))
+    return x
+
+
+def dequant_noise(q, num_frames, stddev, seed):
+    """uint8 [B,F,D] -> float32 [B,F,D]: utils.Dequantize with the padding frames 0, plus N(0, stddev^2) over every element (the
+    frame-level NoiseAugmenter); bit for bit the dequantisation followed by add_noise(stddev, seed).  stddev = 0: dequantise only."""
+    q, nf = _frames_nf(q, num_frames)
+    if q.dtype != torch.uint8:
+        raise TypeError("expected the reader's uint8 frames, got %s" % q.dtype)
+    B, F, D = q.shape
+    y = torch.empty((B, F, D), dtype=torch.float32, device=q.device)
+    _lib.check(_lib.lib().yt8m_dequant_noise_u8(_p(q), _p(nf), _p(y), B, F, D, float(stddev), int(seed), _stream()))
+    return y
+
+
+def dequantize_frames(q, num_frames):
+    """uint8 [B,F,D] -> float32 [B,F,D]: what the reference's reader hands over (utils.Dequantize, zero padding frames)."""
+    return dequant_noise(q, num_frames, 0.0, 0)
+
+
 def moe_mix_fwd(Zg, Ze, V, M):
     _dev(Zg, Ze)
     B = Zg.shape[0]

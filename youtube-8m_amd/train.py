@@ -10,7 +10,7 @@ import math
 
 import torch
 
-from . import feature_transform, losses, ops
+from . import data_augmentation, feature_transform, losses, ops
 from .feature_transform import DefaultTransformer
 from .flags import FLAGS, DEFINE_integer, DEFINE_float, DEFINE_string, DEFINE_bool
 from .variables import Graph, get_default_graph, set_default_graph
@@ -77,7 +77,7 @@ class TrainGraph(object):
     """What build_graph() wires, as an object with an eager ``step``."""
 
     def __init__(self, model, label_loss_fn=None, batch_size=1024, base_learning_rate=0.01,
-                 learning_rate_decay_examples=4000000, learning_rate_decay=0.95, transformer_class=None,
+                 learning_rate_decay_examples=4000000, learning_rate_decay=0.95, transformer_class=None, augmenter_class=None,
                  clip_gradient_norm=1.0, regularization_penalty=1, multitask=None, graph=None, reducer=None,
                  beta1=0.9, beta2=0.999, epsilon=1e-8):
         self.model = model
@@ -87,6 +87,7 @@ class TrainGraph(object):
         self.decay_examples = learning_rate_decay_examples
         self.decay = learning_rate_decay
         self.transformer = (transformer_class or feature_transform.DefaultTransformer)()
+        self.augmenter = (augmenter_class or data_augmentation.DefaultAugmenter)()   # training steps only (W/train.py:337-339)
         self.clip = clip_gradient_norm
         self.reg_penalty = regularization_penalty
         self.multitask = FLAGS.multitask if multitask is None else multitask
@@ -94,6 +95,21 @@ class TrainGraph(object):
         self.reducer = reducer                            # parallel.GradReducer or None
         self.global_step = 0
         self.b1, self.b2, self.eps = beta1, beta2, epsilon
+
+    def _augment(self, model_input_raw, labels_batch, num_frames, weights, distill_labels_batch):
+        """W/train.py:337-339: the data augmenter between the reader and the feature transformer, once per training step.  Returns
+        (model_input, labels, num_frames, transformed): transformed = the augmenter already applied the DefaultTransformer (the
+        l2-normalisation folded into HalfVideoAugmenter's pass over the bytes)."""
+        if type(self.augmenter) is data_augmentation.DefaultAugmenter:
+            return model_input_raw, labels_batch, num_frames, False
+        kw = {}
+        if isinstance(self.augmenter, data_augmentation.HalfVideoAugmenter) and FLAGS.fold_dequant \
+                and isinstance(self.transformer, DefaultTransformer):
+            kw["fold_l2norm"] = True
+        x, labels_batch, num_frames = self.augmenter.augment(model_input_raw, num_frames=num_frames, labels_batch=labels_batch,
+                                                             weights=weights, distill_labels_batch=distill_labels_batch,
+                                                             seed=self.graph.augmenter_seed(), **kw)
+        return x, labels_batch, num_frames, bool(kw)
 
     def _transform(self, model_input_raw, num_frames):
         """W/train.py:352-353 feature transform.  Raw uint8 frame blocks go to the model untouched when the model folds
@@ -106,10 +122,12 @@ class TrainGraph(object):
 
     # ---- forward -----------------------------------------------------------------------------------
     def forward(self, model_input_raw, labels_batch=None, num_frames=None, is_training=True, fuse_loss=True,
-                distillation_predictions=None):
+                distillation_predictions=None, transformed=False):
+        """transformed: model_input_raw already went through the feature transformer (step() after an augmenter that folds it).
+        The data augmenter never runs here: forward(is_training=False), eval and inference see the batch as it is."""
         g = set_default_graph(self.graph)
         g.begin_step()
-        model_input, num_frames = self._transform(model_input_raw, num_frames)
+        model_input, num_frames = (model_input_raw, num_frames) if transformed else self._transform(model_input_raw, num_frames)
         kw = {} if is_training else {"is_training": False}
         if not fuse_loss:
             kw["fuse_loss"] = False
@@ -172,12 +190,15 @@ class TrainGraph(object):
         distill = distill_labels_batch if FLAGS.distillation_features else None
         if distill is not None and FLAGS.distillation_type == 2:  # W/train.py:320-327: labels are re-formed up front
             distill = reform_distill_labels(labels_batch, distill, FLAGS.distillation_percent)
+        # W/train.py:337-339: augmented once; the data-parallel first step's second forward pass below reuses these tensors.  The
+        # learning-rate staircase still counts batch_size examples per step (:303-307), whatever the augmenter made of the batch.
+        model_input_raw, labels_batch, num_frames, transformed = self._augment(model_input_raw, labels_batch, num_frames, weights, distill)
         # (the fused mixing + loss of MoeModel is this build's addition: it must not pre-empt weights / distillation)
         # and it computes exactly CrossEntropyLoss: any other configured loss (TrainGraph(label_loss_fn=...), multitask) wins
         fuse = (weights is None and distill is None and not self.multitask
                 and type(self.label_loss_fn) is losses.CrossEntropyLoss)
         result = self.forward(model_input_raw, labels_batch, num_frames, fuse_loss=fuse,
-                              distillation_predictions=distill if FLAGS.distillation_as_input else None)
+                              distillation_predictions=distill if FLAGS.distillation_as_input else None, transformed=transformed)
         label_loss = self.loss(result, labels_batch, weights, distill)
         # W/train.py:435-456: a model may hand back its own "regularization_loss" (added to the final loss with the
         # --regularization_penalty weight; the slim l2 regularisers are applied as l2*w inside the optimiser pass) and
@@ -195,7 +216,7 @@ class TrainGraph(object):
             # weights on every rank (once per run; with identical seeds the values do not change).
             g._rng_step -= 1                                      # the same forward pass again: the same random-op seeds
             result = self.forward(model_input_raw, labels_batch, num_frames, fuse_loss=fuse,
-                                  distillation_predictions=distill if FLAGS.distillation_as_input else None)
+                                  distillation_predictions=distill if FLAGS.distillation_as_input else None, transformed=transformed)
             final_loss = label_loss = self.loss(result, labels_batch, weights, distill)
             if "regularization_loss" in result and torch.is_tensor(result["regularization_loss"]) \
                     and result["regularization_loss"].requires_grad and self.reg_penalty != 0:
@@ -273,6 +294,8 @@ class TrainGraph(object):
 
 def build_graph(model, label_loss_fn=None, batch_size=None, **kw):
     """Name-compatible entry: returns the TrainGraph configured from FLAGS like W/train.py:679-728 does."""
+    if "augmenter_class" not in kw:                               # W/train.py:708
+        kw["augmenter_class"] = find_class_by_name(FLAGS.data_augmenter, [data_augmentation])
     return TrainGraph(model, label_loss_fn=label_loss_fn,
                       batch_size=batch_size or FLAGS.batch_size,
                       base_learning_rate=kw.pop("base_learning_rate", FLAGS.base_learning_rate),

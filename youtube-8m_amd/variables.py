@@ -98,6 +98,9 @@ def random_seed(graph_seed, rank, step, call):
     return z ^ (z >> 31)
 
 
+AUGMENTER_CALL = 1 << 32           # the call number of Graph.augmenter_seed: beyond any forward pass's own count of random ops
+
+
 class Graph(object):
     def __init__(self, device=None, seed=0):
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -159,6 +162,12 @@ class Graph(object):
         s = random_seed(self.seed, self.rank, self._rng_step, self._rng_calls)
         self._rng_calls += 1
         return s
+
+    def augmenter_seed(self):
+        """Key of the data augmenter's random op in the training step about to begin.  TrainGraph.step augments before the step's
+        forward pass begins, so this is call AUGMENTER_CALL of that coming pass: apart from the model's own calls 0, 1, ..., different
+        per step and per rank, and unchanged by the data-parallel first step's second forward pass."""
+        return random_seed(self.seed, self.rank, self._rng_step + 1, AUGMENTER_CALL)
 
     def _generator(self):
         if self._gen is None:
