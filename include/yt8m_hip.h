@@ -785,7 +785,8 @@ typedef struct yt8m_lstm_stack_desc {
                            * --compute_dtype=bfloat16 variant).  A host written against ABI 2 passes 0 / 1 only. */
   float forget_bias;
   int32_t fwd_chunks;     /* time partition of the forward pass; 0 = the library's (1: one persistent launch per layer) */
-  int32_t bwd_chunks;     /* ... of the backward pass; 0 = the library's (3 parts) */
+  int32_t bwd_chunks;     /* ... of the backward pass; 0 = the library's (3 parts).  At most 62 parts (one dz scale word each): a
+                           * larger value is clamped to 62, and yt8m_lstm_stack_partition reports the clamped count */
   int32_t need_dx;        /* backward also produces dL/dx [F,B,D] (float input only) */
   /* ABI >= 4 (a host written against ABI 3 must zero these): tf.contrib.rnn.DropoutWrapper(cell, input_keep_prob) around EVERY layer
    * (W/all_frame_models/lstm_memory_model.py:36-44).  input_keep_prob in (0, 1): the input of layer l (the frames for l = 0, the

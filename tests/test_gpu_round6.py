@@ -706,11 +706,40 @@ def test_moe_head_skips_the_input_gradient_of_its_data_columns(dev, flags, B):
     assert float(xx.grad[:, :k0].abs().max()) == 0.0 and float(xx.grad[:, k0:].abs().max()) > 0.0
 
 
+def _fp64_frames_plugin(which, q, y, nf, P):
+    """The plugins of the test below restated in fp64 on np_ref.dequant_l2norm_folded frames (the reader's dequantise + l2-normalise of
+    the bytes, zero past num_frames): predictions, loss and the gradient of every variable."""
+    from oracle import np_ref, torch_ref
+    T = {k: torch.from_numpy(v.astype(np.float64)).requires_grad_(True) for k, v in P.items()}
+    x = torch.from_numpy(np_ref.dequant_l2norm_folded(q, nf))
+    n = torch.from_numpy(nf.astype(np.int64))
+    if which == "frame_logistic":
+        p = torch_ref.logistic(x.sum(1) / n[:, None].double(), T["fully_connected/weights"], T["fully_connected/biases"])
+    else:
+        if which == "ln_lstm":
+            s = "RNN/multi_rnn_cell/cell_%d/layer_norm_basic_lstm_cell/"
+            gates = ("input", "transform", "forget", "output", "state")
+            layers = [(T[s % l + "weights"], [T[s % l + g + "/gamma"] for g in gates], [T[s % l + g + "/beta"] for g in gates]) for l in range(2)]
+            _, c, _ = torch_ref.lnlstm_stack(x, n, layers)
+            st = torch.cat(c, 1)
+        else:
+            s = "RNN/multi_rnn_cell/cell_%d/gru_cell/"
+            layers = [tuple(T[s % l + k] for k in ("gates/weights", "gates/biases", "candidate/weights", "candidate/biases")) for l in range(2)]
+            out, h = torch_ref.gru_stack(x, n, layers)
+            mean = out.sum(1) / n.clamp(min=1).double()[:, None]
+            st = mean if which == "gru_pool" else torch.cat([mean] + h, 1)
+        p = torch_ref.moe(st, T["gates/weights"], T["experts/weights"], T["experts/biases"], 2)
+    loss = torch_ref.cross_entropy(p, torch.from_numpy(y.astype(np.float64)))
+    loss.backward()
+    return p.detach().numpy(), float(loss), {k: v.grad.numpy() for k, v in T.items()}
+
+
 @pytest.mark.parametrize("which", ["gru_pool", "gru_with_pool", "ln_lstm", "frame_logistic"])
 def test_gru_and_layernorm_lstm_plugins_take_the_raw_uint8_frames(dev, flags, which, monkeypatch):
     """GruPoolingModel / GruWithPoolingModel / LayerNormLstmMemoryModel on the reader's bytes: layer 0's hoisted input projection and
     its weight gradient read the byte images (seq_ops.u8_hoisted_fwd / _dw, the forms of the native LSTM stack's layer 0), no dx for
-    the data.  Against the same plugin on the dequantised float frames with the same weights: predictions, loss, every gradient."""
+    the data.  Against the same plugin on the dequantised float frames with the same weights: predictions, loss, every gradient; and
+    against the fp64 restatement on the folded dequantise + l2-normalise of the bytes (a mistake both device paths share)."""
     import yt8m_amd.frame_level_models as flm
     rs = np.random.RandomState(61)
     B, F, D, Hh, V = 16, 8, 32, 128, 13
@@ -733,3 +762,8 @@ def test_gru_and_layernorm_lstm_plugins_take_the_raw_uint8_frames(dev, flags, wh
     assert np.abs(pa - pb).max() < 2e-5 and abs(la - lb) < 1e-4 * max(1.0, abs(lb))
     for k in ga:
         assert np.abs(ga[k] - gb[k]).max() <= 2e-4 * max(1.0, np.abs(gb[k]).max()), k
+    pr, lr, gr = _fp64_frames_plugin(which, q, y, nf, P)
+    assert set(ga) <= set(gr)
+    assert np.abs(pa - pr).max() < 2e-5 and abs(la - lr) < 1e-4 * max(1.0, abs(lr)), (np.abs(pa - pr).max(), la, lr)
+    for k in ga:
+        assert np.abs(ga[k] - gr[k]).max() <= 2e-4 * max(1.0, np.abs(gr[k]).max()), k

@@ -27,6 +27,9 @@ from yt8m_amd.variables import reset_default_graph  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 PATH = os.path.join(HERE, "golden", "trajectory_kat.json")
+# h2 split elements flushed to zero over the whole replay, as this test prints it ("h2 split passes: 0 clamped, N flushed elements"),
+# measured on an MI355X with the library's default partition and knobs: 6.0 % of the 3.1e9 elements the run splits
+FLUSHED_MEASURED = 184520422
 
 
 def _degraded(reset=False):
@@ -97,10 +100,12 @@ def test_full_size_training_trajectory_matches_the_fp64_restatement(dev, flags):
           % (worst["loss"], worst["norm"], clamped, flushed))
     assert clamped == 0, "an h2 operand outgrew its scale during the run (%d clamped elements)" % clamped
     # flushed elements (more than 2^-38 below their operand's maximum: early time steps of a part whose gradients have decayed, under the
-    # part's one scale word) contribute below 2^-14 ulp of the products' leading terms.  Reported; bounded as a share of what the run
-    # split (per step and layer: dz once per orientation for dx and dW, F B 4H elements each)
+    # part's one scale word) contribute below 2^-14 ulp of the products' leading terms.  Reported; bounded by twice what this replay
+    # flushes on an MI355X (FLUSHED_MEASURED) -- a run that flushes far more has lost the scale of its dz operands -- and, as before, as a
+    # share of what the run split (per step and layer: dz once per orientation for dx and dW, F B 4H elements each)
     split = 2 * 2 * fc.F * B * 4 * fc.H * len(ref["steps"])
     assert flushed <= 0.2 * split, (flushed, split)
+    assert flushed <= 2 * FLUSHED_MEASURED + 1000, (flushed, FLUSHED_MEASURED)
 
 
 def test_h2_split_counts_what_it_clamps_and_flushes(dev):

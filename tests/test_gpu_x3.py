@@ -293,6 +293,31 @@ def test_persistent_partition_defaults(dev, monkeypatch, honour_lstm_chunks):
         assert float((u - v).abs().max()) <= 2e-5 * float(v.abs().max()) + 5e-6
 
 
+def test_backward_partition_beyond_62_parts_is_clamped(dev, honour_lstm_chunks):
+    """bwd_chunks = 64 at F = 64 would cut 64 one-frame backward parts, but each part owns one of the 62 dz scale words of its layer
+    (csrc/lstm_stack.hip): the library clamps the backward partition to at most 62 parts (include/yt8m_hip.h, bwd_chunks), reports the
+    clamped count, and computes what the one-part partition computes to fp32 rounding."""
+    import ctypes
+    import yt8m_amd.seq_ops as seq_ops
+    from test_gpu_round2 import _stack_run
+    lib = L.lib()
+    B, F, D, H = 128, 64, 96, 1024
+    assert lib.yt8m_lstm_persist_supported(B, H)
+    nf = torch.randint(0, F + 1, (B,), device=dev, generator=torch.Generator(device=dev).manual_seed(9), dtype=torch.int32)
+    nf[0], nf[1], nf[2] = F, 0, 1
+    res, parts = {}, {}
+    for n in (64, 1):
+        seq_ops.PERSIST_FWD_CHUNKS, seq_ops.PERSIST_BWD_CHUNKS = 1, n      # (honour_lstm_chunks restores them)
+        nb = ctypes.c_int(0)
+        L.check(lib.yt8m_lstm_stack_partition(ctypes.byref(seq_ops._stack_desc(B, F, D, H, 2, False, 1.0, True)), None, ctypes.byref(nb)))
+        parts[n] = nb.value
+        out, grads, _, _ = _stack_run(dev, B, F, D, H, 2, 1, nf, True)
+        res[n] = out + grads
+    assert 1 < parts[64] <= 62 and parts[1] == 1, parts
+    for u, v in zip(res[64], res[1]):
+        assert float((u - v).abs().max()) <= 2e-5 * float(v.abs().max()) + 5e-6
+
+
 def test_bf16_pipe_forward_recurrence_over_the_full_sequence(dev):
     """F = 300 steps (the BASELINE length) of the forward recurrence with the recurrent product as six bf16 products, against an
     fp64 recurrence on the same inputs: the error does not grow along the sequence (every h_t and the final c within 2e-5),

@@ -31,6 +31,9 @@ using namespace yt8m;
 namespace {
 
 constexpr int MAXL = 8, MAXP = 64;
+// backward parts: each owns one dz scale word of its layer's 256-byte block (word 0 is the forward's max |W_x|, word 63 max |W_h|),
+// so a backward partition has at most 62 parts -- a caller's larger bwd_chunks is clamped to that
+constexpr int MAXBP = 62;
 constexpr float U8_ALPHA = 4.0f / 255.0f;
 constexpr float U8_BETA = 128.0f * (4.0f / 255.0f) + (4.0f / 512.0f - 2.0f);   // dequantise(q) = alpha (q - 128) + beta
 constexpr int64_t X3_MIN_ROWS = 1024;                      // F * B below which the fp32-MFMA kernel's smaller tiles win (seq_ops.py)
@@ -104,7 +107,7 @@ const char* plan(const yt8m_lstm_stack_desc* d, Plan* P) {
   if (p.u8 && p.need_dx) return "no gradient with respect to uint8 frames";
   if (p.FB % 16 != 0) return "F * B must be a multiple of 16 (K ranges of the transposed operand images)";
   p.nf = chunks(p.F, d->fwd_chunks > 0 ? d->fwd_chunks : 1, p.fp);
-  p.nb = chunks(p.F, d->bwd_chunks > 0 ? d->bwd_chunks : 3, p.bp);
+  p.nb = chunks(p.F, std::min(d->bwd_chunks > 0 ? d->bwd_chunks : 3, MAXBP), p.bp);
   // The library's own backward partition (bwd_chunks == 0): parts of relative length 2 : 2 : 1 : 1 in forward-time order (round 3:
   // 3 : 2 : 1).  The
   // backward pass runs them last to first: SHORT first parts (the top layer's recurrence runs alone on half the chip while the
@@ -118,7 +121,7 @@ const char* plan(const yt8m_lstm_stack_desc* d, Plan* P) {
   if (spec) {                                                   // relative lengths in forward-time order
     double w[MAXP], tot = 0;
     int n = 0;
-    for (const char* q = spec; *q && n < MAXP;) { w[n] = atof(q); tot += w[n++]; while (*q && *q != ',') ++q; if (*q) ++q; }
+    for (const char* q = spec; *q && n < MAXBP;) { w[n] = atof(q); tot += w[n++]; while (*q && *q != ',') ++q; if (*q) ++q; }
     if (n >= 1 && tot > 0) {
       int64_t t0 = 0; double acc = 0; int k = 0;
       Part pp[MAXP];
@@ -784,7 +787,7 @@ extern "C" int yt8m_lstm_stack_bwd(const yt8m_lstm_stack_desc* desc, const void*
                                       at<float>(scratch, P.work[l]), phase[l], num_frames, t0, T, B, H,
                                       h2_recur ? at<char>(scratch, P.hsc + 256 * l + 252) : nullptr,
                                       (l >= 1 && h2_dx_rows) ? at<char>(scratch, P.rmax + l * P.rmax_stride) : nullptr,
-                                      at<char>(scratch, P.hsc + 256 * l + 4 * (1 + std::min(c, 61))), at<char>(scratch, P.pws[l]), P.pws_bytes, s));
+                                      at<char>(scratch, P.hsc + 256 * l + 4 * (1 + c)), at<char>(scratch, P.pws[l]), P.pws_bytes, s));
         else if (!bf && h2_recur)
           RC(yt8m_lstm_persist_bwd_h2(at<float>(tape, P.z[l]), W[l] + Din * H4, H4, at<float>(tape, P.cs[l]), dout, dz,
                                       at<float>(scratch, P.work[l]), phase[l], nullptr, num_frames, t0, T, B, H,
@@ -877,7 +880,7 @@ extern "C" int yt8m_lstm_stack_bwd(const yt8m_lstm_stack_desc* desc, const void*
           // layer 0 on uint8 frames as f16 products: ONE pass over this part's dz (after its absmax) writes dz^T and (r (.) dz)^T as h2
           // images + the per-tile column sums; dW_x = (q - 128)^T . (r (.) dz) on two products, dW_h = h^T . dz on three
           const float* rr = at<float>(tape, P.rrow) + t0 * B;
-          float* word = at<float>(scratch, P.hsc) + 1 + std::min(c, 61);
+          float* word = at<float>(scratch, P.hsc) + 1 + c;
           if (!P.emit_max) RC(yt8m_h2_absmax(dzc, M, H4, H4, word, (yt8m_stream_t)sw));
           float* cp = P.colparts ? at<float>(scratch, P.cpart[l]) + (t0 * B / 64) * H4 : nullptr;
           float* cps = P.colparts ? at<float>(scratch, P.cparts) + (t0 * B / 64) * H4 : nullptr;
@@ -912,7 +915,7 @@ extern "C" int yt8m_lstm_stack_bwd(const yt8m_lstm_stack_desc* desc, const void*
         } else if (P.h2) {
           // three f16 products: dz^T of this part under a scale measured on the device (a sum over the part's frame rows: one scale
           // serves it), h^T / out^T under the static 2^13; the bias gradient's per-tile column sums ride on the split as before
-          float* word = at<float>(scratch, P.hsc + 256 * l) + 1 + std::min(c, 61);                             // one word per backward part (zeroed at the start)
+          float* word = at<float>(scratch, P.hsc + 256 * l) + 1 + c;                             // one word per backward part (zeroed at the start)
           if (!P.emit_max) RC(yt8m_h2_absmax(dzc, M, H4, H4, word, (yt8m_stream_t)sw));
           float* cp = (P.colparts && db[l]) ? at<float>(scratch, P.cpart[l]) + (t0 * B / 64) * H4 : nullptr;
           RC(yt8m_h2_split(dzc, M, H4, H4, 1.0f, word, nullptr, at<char>(scratch, P.dzT3[l]), cp, (yt8m_stream_t)sw));
