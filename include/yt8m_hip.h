@@ -1057,6 +1057,33 @@ int yt8m_batchnorm_bwd(const float* x, const float* dy, int64_t N, int64_t C, co
                        const float* save_rstd, int training, float* dx, float* dgamma, float dgamma_beta, float* dbeta,
                        float dbeta_beta, void* workspace, int64_t workspace_bytes, yt8m_stream_t stream);
 
+/* ---- MultiscaleCnnLstmModel: batch norm + ReLU + max over frame pairs on TIME-major rows (csrc/multiscale.hip;
+ * W/all_frame_models/multiscale_cnn_lstm_model.py:38-45,114-131) ---------------------------------------------------
+ * y [F B rows (t B + b), C] fp32 is a CNN's output; all of these want C % 4 == 0, leading dimensions >= C that are multiples of 4 and
+ * 16-byte aligned operands (16-byte loads and stores).  An empty problem is a no-op returning 0.
+ * yt8m_colmoments_f32: training != 0: mean / rstd [C] = column mean and 1 / sqrt(biased variance + eps) over the M rows of y, and
+ *   moving_mean / moving_var updated with `decay` (yt8m_batchnorm_fwd's arithmetic; the column sums are fixed-order partials in the
+ *   workspace); training == 0: mean = moving_mean, rstd from moving_var, y and the workspace are not read.
+ * yt8m_bn_relu_pool2_tm_fwd: ONE pass over y: a [F,B,C] = relu(gamma (y - mean) rstd + beta) and, unless pooled is NULL,
+ *   pooled [F / 2, B, C] with pooled[j] = max(a[2j], a[2j + 1]) (an odd last frame is not pooled).
+ * yt8m_bn_relu_pool2_tm_bwd: da [F,B,C] (gradient at a; may be NULL = zeros) and dp [F / 2, B, C] (gradient at pooled; NULL for the
+ *   last scale), routed to the frame of the pair that attained the maximum (the first one on a tie), times the ReLU mask, are the
+ *   gradient g at the batch norm's output (a and xhat are recomputed from y).  Pass 1 reduces sum g and sum g xhat per column
+ *   (-> dbeta, dgamma; *_beta = 0 overwrites, 1 accumulates); pass 2 writes dy = gamma rstd (g - sum g / M - xhat sum g xhat / M)
+ *   (training == 0: gamma rstd g).  dy may be NULL (parameter gradients only) or da itself (in place).
+ * workspace: yt8m_multiscale_workspace_bytes(C) bytes. */
+int64_t yt8m_multiscale_workspace_bytes(int64_t C);
+int yt8m_colmoments_f32(const float* y, int64_t M, int64_t C, int64_t ldy, float* moving_mean, float* moving_var, int training,
+                        float eps, float decay, float* mean, float* rstd, void* workspace, int64_t workspace_bytes,
+                        yt8m_stream_t stream);
+int yt8m_bn_relu_pool2_tm_fwd(const float* y, int64_t ldy, int64_t F, int64_t B, int64_t C, const float* gamma, const float* beta,
+                              const float* mean, const float* rstd, float* a, int64_t lda, float* pooled, int64_t ldp,
+                              yt8m_stream_t stream);
+int yt8m_bn_relu_pool2_tm_bwd(const float* y, int64_t ldy, int64_t F, int64_t B, int64_t C, const float* gamma, const float* beta,
+                              const float* mean, const float* rstd, int training, const float* da, int64_t ldda, const float* dp,
+                              int64_t lddp, float* dy, int64_t lddy, float* dgamma, float dgamma_beta, float* dbeta,
+                              float dbeta_beta, void* workspace, int64_t workspace_bytes, yt8m_stream_t stream);
+
 /* ---- per-row top-k for the GAP@20 eval path (W/eval_util.py:123-165 top_k_triplets) -------------
  * p [B,V] -> vals [B,k] (descending), idx [B,k] int32; ties broken towards the LOWER class index. k<=64 */
 int yt8m_topk_rows(const float* p, int64_t B, int64_t V, int k, float* vals, int32_t* idx,

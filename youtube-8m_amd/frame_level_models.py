@@ -31,6 +31,8 @@ DEFINE_string("feature_sizes", "1024", "Length of the feature vectors.")     # W
 DEFINE_integer("positional_embedding_size", 32, "Positional embedding dimension use in lstm_positional_attention_max_pooling_model.")
 DEFINE_integer("lstm_attentions", 8, "Attention size in lstm_attention_max_pooling_model.")
 DEFINE_bool("is_training", False, "used in batch normalization.")
+DEFINE_integer("multiscale_cnn_lstm_layers", 1, "number of layers in multiscale cnn_lstm.")          # W/frame_level_models.py:77
+DEFINE_integer("distillchain_relu_cells", 256, "number of relu cells in distillchain model.")        # W/frame_level_models.py:81
 # new (Appendix B)
 DEFINE_integer("netvlad_cluster_size", 64, "Number of NetVLAD clusters.")
 DEFINE_integer("netvlad_hidden_size", 1024, "Width of the FC after the VLAD descriptor.")
@@ -507,6 +509,134 @@ def _batch_norm(x, scope, is_training, eps=1e-3, decay=0.999):
     mm = g.get_variable(scope + "/moving_mean", (n,), zeros, trainable=False)
     mv = g.get_variable(scope + "/moving_variance", (n,), ones, trainable=False)
     return ops.batch_norm(x, gamma, beta, mm, mv, is_training, eps, decay)
+
+
+class MultiscaleCnnLstmModel(models.BaseModel):
+    """W/all_frame_models/multiscale_cnn_lstm_model.py:10-137: --multiscale_cnn_lstm_layers scales; scale k runs the einsum CNN (filter
+    lengths 1, 2, 3 with 256, 256, 512 filters) on its input [B, F_k, D_k], slim.batch_norm over ALL B F_k rows (padding frames included,
+    as the reference), ReLU, one BasicLSTMCell under dynamic_rnn whose final memory c feeds a MoE, and hands the max over frame pairs of
+    the ReLU output (F_{k+1} = F_k // 2, num_frames_{k+1} = max(num_frames_k // 2, 1)) to the next scale.  predictions = mean of the
+    sub-predictions, support_predictions = their concatenation.  Variable names as TF 1.0 builds them, written from memory (as SURVEY.md
+    Appendix A; pinned in tests/test_multiscale_host.py): cnn<k>cnn-filter-len{1,2,3}, cnn<k>cluster_bn/{gamma,beta,moving_mean,
+    moving_variance}, RNN-rnn<k>/basic_lstm_cell/{weights,biases}, gatesmoe<k>/weights, expertsmoe<k>/{weights,biases}.
+
+    Two paths, the same function and gradients.  fused (default on the device): every tensor of a scale stays time-major [F_k B, C]
+    (row t B + b) -- the CNN as products on row windows (seq_ops.u8_cnn_tm on the reader's bytes at scale 1, seq_ops.cnn_tm on floats),
+    batch norm + ReLU + pair maximum in one pass (seq_ops.bn_relu_pool2_tm, csrc/multiscale.hip) whose first output IS the native LSTM
+    stack's input and whose second IS the next scale's.  generic (YT8M_MULTISCALE_FUSED=0, or shapes the fused kernels refuse): composed
+    from ops.linear on shifted / concatenated inputs, ops.batch_norm and torch relu / amax, batch-major as the reference.
+    accepts_quantized_input: scale 1 reads the reader's bytes through seq_ops.U8FrameImages where seq_ops.u8_cnn_supported holds."""
+    accepts_quantized_input = True
+
+    NUM_FILTERS = (256, 256, 512)
+    FILTER_SIZES = (1, 2, 3)
+
+    def _filters(self, D, sub_scope, l2_penalty):
+        g = get_default_graph()
+        return [g.get_variable(sub_scope + "cnn-filter-len%d" % fs, (D * fs, nf), random_normal(0.1), l2=l2_penalty)
+                for nf, fs in zip(self.NUM_FILTERS, self.FILTER_SIZES)]
+
+    def _bn_vars(self, scope, n):
+        g = get_default_graph()
+        return (g.get_variable(scope + "/gamma", (n,), ones), g.get_variable(scope + "/beta", (n,), zeros),
+                g.get_variable(scope + "/moving_mean", (n,), zeros, trainable=False),
+                g.get_variable(scope + "/moving_variance", (n,), ones, trainable=False))
+
+    def _rnn(self, x_tm, num_frames, d_in, lstm_size, layer):
+        g = get_default_graph()
+        with g.variable_scope("RNN-rnn%d" % (layer + 1)):
+            wb = _lstm_cells(d_in, lstm_size, 1, multi=False)
+        _, finals = seq_ops.lstm_stack(x_tm, num_frames, wb, forget_bias=1.0, chunks=FLAGS.lstm_pipeline_chunks,
+                                       bf16=FLAGS.compute_dtype == "bfloat16", slot=layer)     # the L stacks are alive in one step
+        return finals[0][0]                                                                      # state.c
+
+    def moe(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, scopename="", **unused_params):
+        num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
+        return video_level_models.moe_block(model_input, vocab_size, num_mixtures, l2_penalty, "gates" + scopename, "experts" + scopename)
+
+    def _head_input(self, lstm_memory):
+        return lstm_memory
+
+    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, is_training=True, **unused_params):
+        num_layers = FLAGS.multiscale_cnn_lstm_layers
+        lstm_size = int(FLAGS.lstm_cells)
+        is_training = bool(FLAGS.is_training and is_training)
+        features_size = sum(self.NUM_FILTERS)
+        B, F, D = model_input.shape
+        frames = None
+        if model_input.dtype == torch.uint8:
+            if seq_ops.u8_cnn_supported(model_input):
+                frames = seq_ops.U8FrameImages(model_input, num_frames)
+            else:
+                model_input = ops.dequant_l2norm(model_input, num_frames)
+        fused = seq_ops.MULTISCALE_FUSED and seq_ops.bn_relu_pool2_supported(model_input, features_size)
+        nf = num_frames.to(torch.int32)
+        # fused: cnn_input is time-major [F_k B, D_k]; generic: batch-major [B, F_k, D_k]
+        cnn_input = None if frames is not None else (model_input.transpose(0, 1).reshape(F * B, D) if fused else model_input)
+        sub_predictions = []
+        for layer in range(num_layers):
+            scope = "cnn%d" % (layer + 1)
+            fvars = self._filters(D, scope, l2_penalty)
+            gamma, beta, mm, mv = self._bn_vars(scope + "cluster_bn", features_size)
+            last = layer + 1 == num_layers
+            if fused:
+                y = seq_ops.u8_cnn_tm(frames, fvars) if (layer == 0 and frames is not None) else seq_ops.cnn_tm(cnn_input, B, fvars)
+                relu_tm, pooled = seq_ops.bn_relu_pool2_tm(y, gamma, beta, mm, mv, is_training, F, B, want_pool=not last)
+                next_input = None if last else pooled.view((F // 2) * B, features_size)
+            else:
+                if layer == 0 and frames is not None:
+                    cnn_output = seq_ops.u8_cnn(frames, fvars)
+                else:
+                    cnn_output = self.cnn(cnn_input, fvars)
+                bn = ops.batch_norm(cnn_output.reshape(B * F, features_size), gamma, beta, mm, mv, is_training, 1e-3, 0.999)
+                relu = torch.relu(bn).view(B, F, features_size)
+                relu_tm = relu.transpose(0, 1).contiguous()
+                next_input = None if last else relu[:, :(F // 2) * 2].reshape(B, F // 2, 2, features_size).amax(dim=2)
+            lstm_memory = self._rnn(relu_tm, nf, features_size, lstm_size, layer)
+            sub_predictions.append(self.moe(self._head_input(lstm_memory), vocab_size, l2_penalty=l2_penalty,
+                                            scopename="moe%d" % (layer + 1)))
+            cnn_input, F, D = next_input, F // 2, features_size
+            nf = torch.clamp(nf // 2, min=1)                        # tf.maximum(num_frames / pool_size, 1), integer division
+            if F == 0 and not last:
+                raise ValueError("multiscale_cnn_lstm_layers = %d needs more than %d frames" % (num_layers, model_input.shape[1]))
+        support_predictions = torch.cat(sub_predictions, dim=1)
+        predictions = sub_predictions[0]
+        for p in sub_predictions[1:]:
+            predictions = predictions + p
+        return {"predictions": predictions / float(len(sub_predictions)), "support_predictions": support_predictions}
+
+    @staticmethod
+    def cnn(model_input, fvars):
+        """:12-38 as CnnDeepCombineChainModel.cnn composes it: ops.linear on the input concatenated with its 1- and 2-frame shifts."""
+        B, F, D = model_input.shape
+        shift_inputs = [model_input]
+        for i in range(1, max(W.data.shape[0] // D for W in fvars)):       # tf.pad(..., [[0,0],[i,0],[0,0]])[:, :F]
+            shift_inputs.append(torch.cat([model_input.new_zeros(B, min(i, F), D), model_input[:, :max(F - i, 0)]], dim=1))
+        outs = []
+        for W in fvars:
+            fs = W.data.shape[0] // D
+            sub_input = torch.cat(shift_inputs[:fs], dim=2) if fs > 1 else shift_inputs[0]
+            outs.append(ops.linear(sub_input.reshape(B * F, fs * D), W).view(B, F, -1))
+        return torch.cat(outs, dim=2)
+
+
+class DistillchainMultiscaleCnnLstmModel(MultiscaleCnnLstmModel):
+    """W/all_frame_models/distillchain_multiscale_cnn_lstm_model.py:99-150: MultiscaleCnnLstmModel whose every MoE additionally reads the
+    l2-normalised relu projection ("distillrelu", --distillchain_relu_cells wide) of another model's predictions, concatenated behind
+    the LSTM memory."""
+
+    def create_model(self, model_input, vocab_size, num_frames, distillation_predictions=None, l2_penalty=1e-8, **unused_params):
+        assert distillation_predictions is not None, "distillation feature must be used"
+        distill_relu = video_level_models.fully_connected(distillation_predictions.to(torch.float32), FLAGS.distillchain_relu_cells,
+                                                          "distillrelu", activation="relu", l2_penalty=l2_penalty)
+        self._distill_norm = ops.l2_normalize(distill_relu)
+        try:
+            return super().create_model(model_input, vocab_size, num_frames, l2_penalty=l2_penalty, **unused_params)
+        finally:
+            self._distill_norm = None
+
+    def _head_input(self, lstm_memory):
+        return torch.cat([lstm_memory, self._distill_norm], dim=1)
 
 
 class DbofModel(models.BaseModel):

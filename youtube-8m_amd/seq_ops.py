@@ -1594,6 +1594,46 @@ def u8_hoisted_dw(frames, dz2d, gWrows, beta):
                                         _p(csr), U8_BETA / U8_ALPHA, float(beta), _p(ws), ws.numel() * 4, _stream()))
 
 
+def _u8_cnn_dw(frames, filters, dyt):
+    """Weight gradients of _u8_cnn_dense from dyt [F B rows (t B + b), sum N_k]: per filter slice x[.. M - i B]^T . dy_k[i B ..] from the
+    transposed byte image at K offset 0 (the recurrent stack's layer-0 form).  The frames are data: no dx."""
+    B, F, D = frames.B, frames.F, frames.D
+    M = F * B
+    dev = dyt.device
+    lib = _lib.lib()
+    ws = ops._workspace(dev)
+    nb = lambda rows_, K: max(lib.yt8m_x3_image_bytes(rows_, K) // 3 * 2, 16)
+    qT = None
+    c0 = 0
+    for W in filters:
+        fs, N = W.data.shape[0] // D, W.data.shape[1]
+        if W.trainable and W.grad is not None:
+            wbeta = float(W.grad_beta())
+            if qT is None:
+                qT = frames.trans()
+            for i in range(fs):
+                rows = M - i * B
+                gW = W.grad[i * D:(i + 1) * D]
+                if rows <= 0:
+                    if wbeta == 0.0:
+                        gW.zero_()
+                    continue
+                part = dyt[i * B:, c0:c0 + N].contiguous()          # dy of the frames that saw this shift
+                word = ops.h2_absmax(part)
+                dzT = torch.empty(nb(N, rows), dtype=torch.uint8, device=dev)
+                dzTs = torch.empty(nb(N, rows), dtype=torch.uint8, device=dev)
+                ntile = (rows + 63) // 64
+                cp = torch.empty((ntile, N), dtype=torch.float32, device=dev)
+                cps = torch.empty((ntile, N), dtype=torch.float32, device=dev)
+                _lib.check(lib.yt8m_h2_split_ex(_p(part), rows, N, N, 1.0, _p(word), _p(frames.r), None, _p(dzT), _p(dzTs), _p(cp),
+                                                _p(cps), _stream()))
+                csr = cps.sum(0).contiguous()
+                _lib.check(lib.yt8m_gemm_h1x2_nt_ex(D, N, rows, _p(qT), (M + 15) // 16, _p(dzTs), 0, _p(gW), N, None, U8_ALPHA, _p(word),
+                                                    None, _p(csr), U8_BETA / U8_ALPHA, wbeta, _p(ws), ws.numel() * 4, _stream()))
+            W.grad_done()
+        c0 += N
+
+
 class _CnnU8(torch.autograd.Function):
     """cnn_output [B,F,sum N_k] of cnn_deep_combine_chain_model.py:60-82 -- for every filter k of length fs_k, einsum("ijk,kl->ijl") of
     concat(x, x shifted by 1 frame, ..., by fs_k - 1 frames) with W_k [fs_k D, N_k] -- without the concatenations and without a float
@@ -1610,43 +1650,9 @@ class _CnnU8(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         frames, filters = ctx.frames, ctx.filters
-        B, F, D = frames.B, frames.F, frames.D
-        M = F * B
-        dev = dy.device
-        lib = _lib.lib()
-        Ntot = dy.shape[2]
-        dyt = _f32c(dy).transpose(0, 1).contiguous().view(M, Ntot)      # time-major rows, as the images
-        ws = ops._workspace(dev)
-        nb = lambda rows_, K: max(lib.yt8m_x3_image_bytes(rows_, K) // 3 * 2, 16)
-        qT = None
-        c0 = 0
-        for W in filters:
-            fs, N = W.data.shape[0] // D, W.data.shape[1]
-            if W.trainable and W.grad is not None:
-                wbeta = float(W.grad_beta())
-                if qT is None:
-                    qT = frames.trans()
-                for i in range(fs):
-                    rows = M - i * B
-                    gW = W.grad[i * D:(i + 1) * D]
-                    if rows <= 0:
-                        if wbeta == 0.0:
-                            gW.zero_()
-                        continue
-                    part = dyt[i * B:, c0:c0 + N].contiguous()          # dy of the frames that saw this shift
-                    word = ops.h2_absmax(part)
-                    dzT = torch.empty(nb(N, rows), dtype=torch.uint8, device=dev)
-                    dzTs = torch.empty(nb(N, rows), dtype=torch.uint8, device=dev)
-                    ntile = (rows + 63) // 64
-                    cp = torch.empty((ntile, N), dtype=torch.float32, device=dev)
-                    cps = torch.empty((ntile, N), dtype=torch.float32, device=dev)
-                    _lib.check(lib.yt8m_h2_split_ex(_p(part), rows, N, N, 1.0, _p(word), _p(frames.r), None, _p(dzT), _p(dzTs), _p(cp),
-                                                    _p(cps), _stream()))
-                    csr = cps.sum(0).contiguous()
-                    _lib.check(lib.yt8m_gemm_h1x2_nt_ex(D, N, rows, _p(qT), (M + 15) // 16, _p(dzTs), 0, _p(gW), N, None, U8_ALPHA, _p(word),
-                                                        None, _p(csr), U8_BETA / U8_ALPHA, wbeta, _p(ws), ws.numel() * 4, _stream()))
-                W.grad_done()
-            c0 += N
+        M = frames.F * frames.B
+        dyt = _f32c(dy).transpose(0, 1).contiguous().view(M, dy.shape[2])      # time-major rows, as the images
+        _u8_cnn_dw(frames, filters, dyt)
         return (None, None) + (None,) * len(filters)
 
 
@@ -1880,3 +1886,189 @@ class _NetVladPoolU8(torch.autograd.Function):
 
 def netvlad_pool_u8(q, num_frames, Wc, bc, centres, nsplit=2, eps=1e-12, want_q=False):
     return _NetVladPoolU8.apply(q, num_frames, _token(Wc._graph), Wc, bc, centres, int(nsplit), eps, bool(want_q))
+
+
+# ---- MultiscaleCnnLstmModel: CNN -> batch norm -> ReLU -> (LSTM input, pair-max for the next scale), everything time-major ------------
+import os as _os_ms
+
+MULTISCALE_FUSED = _os_ms.environ.get("YT8M_MULTISCALE_FUSED", "1") != "0"   # 0: the plugin composes the scale from ops.linear / ops.batch_norm / torch
+
+
+def bn_relu_pool2_supported(x, C):
+    """The fused scale (csrc/multiscale.hip): a device tensor and C % 4 == 0 (16-byte column accesses)."""
+    return bool(x.is_cuda and C % 4 == 0 and C >= 4)
+
+
+class _CnnU8TM(torch.autograd.Function):
+    """_CnnU8 without the layout glue: the einsum CNN on the reader's bytes with its output LEFT time-major [F B rows (t B + b), sum N_k]
+    (what _u8_cnn_dense writes), the gradient taken time-major too."""
+
+    @staticmethod
+    def forward(ctx, token, frames, *filters):
+        ctx.frames, ctx.filters = frames, filters
+        return _u8_cnn_dense(frames, filters)
+
+    @staticmethod
+    def backward(ctx, dy):
+        _u8_cnn_dw(ctx.frames, ctx.filters, _f32c(dy))
+        return (None, None) + (None,) * len(ctx.filters)
+
+
+def u8_cnn_tm(frames, filters):
+    """frames: U8FrameImages; filters: cnn-filter Variables [fs_k D, N_k] in output-column order -> cnn_output [F B, sum N_k] time-major."""
+    return _CnnU8TM.apply(_token(filters[0]._graph), frames, *filters)
+
+
+def _cnn_role(M, N, K):
+    # the rule ops._Linear applies to a fully-connected layer's forward product
+    return "h2" if (ops.LINEAR_FWD_H2 and ops._linear_h2_size(M, N, K) and N % 4 == 0 and K >= 512) else None
+
+
+class _CnnTM(torch.autograd.Function):
+    """The einsum CNN of W/all_frame_models/multiscale_cnn_lstm_model.py:12-38 on float frames in time-major order, x [F B rows (t B + b), D]:
+    a shift by i frames is a row offset of i B, so filter k's output is
+        y[i B :, cols_k] += x[: M - i B] . W_k[i D : (i + 1) D]          for i < fs_k   (the first i B rows get no term: zero padding)
+    -- one product per (filter, shift) on row windows, no concatenated [., 2 D] / [., 3 D] inputs.  Backward: the slice's weight gradient
+    x[: M - i B]^T . dy[i B :, cols_k] and dx[: M - i B] += dy[i B :, cols_k] . W_k[i D : (i + 1) D]^T."""
+
+    @staticmethod
+    def forward(ctx, x, token, B, *filters):
+        x = _f32c(x)
+        _dev(x)
+        M, D = x.shape
+        Ntot = sum(W.data.shape[1] for W in filters)
+        y = torch.empty((M, Ntot), dtype=torch.float32, device=x.device)
+        fsmax = max(W.data.shape[0] // D for W in filters)
+        for i in range(fsmax):                                     # products of one shift write disjoint column windows: one group
+            rows = M - i * B
+            items, role, c0 = [], "h2", 0
+            for W in filters:
+                fs, N = W.data.shape[0] // D, W.data.shape[1]
+                assert W.data.shape[0] == fs * D, "cnn filter must be [fs * D, N]"
+                if i < fs:
+                    if rows > 0:
+                        items.append(dict(A=x[:rows], B=W.data[i * D:(i + 1) * D], out=y[i * B:, c0:c0 + N], beta=1.0 if i else 0.0))
+                        role = role if _cnn_role(rows, N, D) else None
+                    elif i == 0:
+                        y[:, c0:c0 + N].zero_()
+                c0 += N
+            if items:
+                ops.gemm_grouped(items, role=role)
+        ctx.save_for_backward(x)
+        ctx.filters, ctx.B = filters, B
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        filters, B = ctx.filters, ctx.B
+        dy = _f32c(dy)
+        M, D = x.shape
+        dw, c0 = [], 0
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        first = True
+        for W in filters:
+            fs, N = W.data.shape[0] // D, W.data.shape[1]
+            train = W.trainable and W.grad is not None
+            wbeta = float(W.grad_beta()) if train else 0.0
+            for i in range(fs):
+                rows = M - i * B
+                if rows <= 0:
+                    if train and wbeta == 0.0:
+                        W.grad[i * D:(i + 1) * D].zero_()
+                    continue
+                if train:
+                    dw.append(dict(A=x[:rows], B=dy[i * B:, c0:c0 + N], out=W.grad[i * D:(i + 1) * D], beta=wbeta))
+                if dx is not None:
+                    if first and rows < M:
+                        dx.zero_()
+                    ops.gemm(dy[i * B:, c0:c0 + N], W.data[i * D:(i + 1) * D], out=dx[:rows], transB=True, beta=0.0 if first else 1.0)
+                    first = False
+            c0 += N
+        if dw:
+            ops.gemm_grouped(dw, transA=True, role="dw")               # disjoint gradient slices: one group
+        for W in filters:
+            if W.trainable and W.grad is not None:
+                W.grad_done()
+        if dx is not None and first:
+            dx.zero_()
+        return (dx, None, None) + (None,) * len(filters)
+
+
+def cnn_tm(x_tm2d, B, filters):
+    """x_tm2d [F B, D] float time-major (B videos per frame); filters as u8_cnn_tm -> cnn_output [F B, sum N_k] time-major."""
+    return _CnnTM.apply(x_tm2d, _token(filters[0]._graph), int(B), *filters)
+
+
+_MS_WS = {}
+
+
+def _multiscale_ws(dev, C):
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, int(C))
+    ws = _MS_WS.get(key)
+    if ws is None:
+        ws = torch.empty(_lib.lib().yt8m_multiscale_workspace_bytes(int(C)) // 4, dtype=torch.float32, device=dev)
+        _MS_WS[key] = ws
+    return ws
+
+
+class _BnReluPool2TM(torch.autograd.Function):
+    """slim.batch_norm(center, scale) over all F B rows, ReLU, and the max over frame pairs (2j, 2j + 1) of
+    W/all_frame_models/multiscale_cnn_lstm_model.py:39-45,116,123-127 in ONE pass over the CNN output y [F B, C] (time-major):
+    a [F,B,C] is the LSTM's input as it stands, p [F // 2, B, C] the next scale's (csrc/multiscale.hip).  Backward recomputes a and xhat
+    from y: nothing but y, the column statistics and the two outputs is kept."""
+
+    @staticmethod
+    def forward(ctx, y, token, gamma, beta, mm, mv, is_training, eps, decay, F, B, want_pool):
+        y = _f32c(y)
+        _dev(y)
+        M, C = y.shape
+        assert M == F * B
+        dev = y.device
+        lib = _lib.lib()
+        ws = _multiscale_ws(dev, C)
+        mean = torch.empty((C,), dtype=torch.float32, device=dev)
+        rstd = torch.empty((C,), dtype=torch.float32, device=dev)
+        _lib.check(lib.yt8m_colmoments_f32(_p(y), M, C, C, _p(mm.data), _p(mv.data), int(bool(is_training)), float(eps), float(decay),
+                                           _p(mean), _p(rstd), _p(ws), ws.numel() * 4, _stream()))
+        a = torch.empty((F, B, C), dtype=torch.float32, device=dev)
+        p = torch.empty((F // 2, B, C), dtype=torch.float32, device=dev) if want_pool else None
+        _lib.check(lib.yt8m_bn_relu_pool2_tm_fwd(_p(y), C, F, B, C, _p(gamma.data), _p(beta.data), _p(mean), _p(rstd), _p(a), C,
+                                                 _p(p) if (p is not None and p.numel()) else None, C, _stream()))
+        ctx.save_for_backward(y, mean, rstd)
+        ctx.vars = (gamma, beta, bool(is_training), F, B)
+        if p is None:
+            p = a.new_empty((0,))
+            ctx.mark_non_differentiable(p)
+        return a, p
+
+    @staticmethod
+    def backward(ctx, da, dp):
+        y, mean, rstd = ctx.saved_tensors
+        gamma, beta, is_training, F, B = ctx.vars
+        M, C = y.shape
+        lib = _lib.lib()
+        da = _f32c(da) if da is not None else None
+        dp = _f32c(dp) if (dp is not None and dp.numel()) else None
+        gg, gb = gamma.grad, beta.grad
+        if da is None and dp is None:
+            da = torch.zeros((F, B, C), dtype=torch.float32, device=y.device)
+        ws = _multiscale_ws(y.device, C)
+        dy = torch.empty_like(y) if ctx.needs_input_grad[0] else None
+        bg = gamma.grad_beta() if gg is not None else 0.0
+        bb = beta.grad_beta() if gb is not None else 0.0
+        _lib.check(lib.yt8m_bn_relu_pool2_tm_bwd(_p(y), C, F, B, C, _p(gamma.data), _p(beta.data), _p(mean), _p(rstd), int(is_training),
+                                                 _p(da), C, _p(dp), C, _p(dy), C, _p(gg), float(bg), _p(gb), float(bb), _p(ws),
+                                                 ws.numel() * 4, _stream()))
+        if gg is not None:
+            gamma.grad_done()
+        if gb is not None:
+            beta.grad_done()
+        return (dy,) + (None,) * 11
+
+
+def bn_relu_pool2_tm(y, gamma, beta, moving_mean, moving_variance, is_training, F, B, want_pool=True, eps=1e-3, decay=0.999):
+    """y [F B, C] time-major -> (a [F,B,C], p [F // 2, B, C] or None)."""
+    a, p = _BnReluPool2TM.apply(y, _token(gamma._graph), gamma, beta, moving_mean, moving_variance, bool(is_training), float(eps),
+                                float(decay), int(F), int(B), bool(want_pool))
+    return a, (p if want_pool else None)
