@@ -737,7 +737,7 @@ def _fp64_frames_plugin(which, q, y, nf, P):
 @pytest.mark.parametrize("which", ["gru_pool", "gru_with_pool", "ln_lstm", "frame_logistic"])
 def test_gru_and_layernorm_lstm_plugins_take_the_raw_uint8_frames(dev, flags, which, monkeypatch):
     """GruPoolingModel / GruWithPoolingModel / LayerNormLstmMemoryModel on the reader's bytes: layer 0's hoisted input projection and
-    its weight gradient read the byte images (seq_ops.u8_hoisted_fwd / _dw, the forms of the native LSTM stack's layer 0), no dx for
+    its weight gradient read the byte images (seq_ops.U8FrameImages.project / weight_grad, the forms of the native LSTM stack's layer 0), no dx for
     the data.  Against the same plugin on the dequantised float frames with the same weights: predictions, loss, every gradient; and
     against the fp64 restatement on the folded dequantise + l2-normalise of the bytes (a mistake both device paths share)."""
     import yt8m_amd.frame_level_models as flm

@@ -26,7 +26,7 @@ for mode in ("float", "u8"):
         x = seq_ops.U8FrameImages(q, nf)
         # the projection alone
         z = torch.empty((F * B, 4 * H), device=dev)
-        seq_ops.u8_hoisted_fwd(x, W.data[:D], None, z)
+        x.project(W.data[:D], None, z)
     else:
         x = ops.dequant_l2norm(q, nf).transpose(0, 1).contiguous()
         z = ops.gemm_any(x.view(F * B, D), W.data[:D], role=ops._hoisted_role(F * B, 4 * H, D, False))

@@ -49,15 +49,47 @@ def _lib_u8_ok(D):
     return bool(_lib.lib().yt8m_u8_proj_supported(int(D)))
 
 
+def _bytes_or_floats(model_input, num_frames, supported):
+    """(input, is_bytes): the reader's bytes [B,F,D] where supported(q) says that the calling plugin's byte kernels cover the shape, else
+    the dequantised, l2-normalised float frames the reference's transformer would have handed over (float input passes through)."""
+    if model_input.dtype != torch.uint8:
+        return model_input, False
+    if supported(model_input):
+        return model_input.contiguous(), True
+    return ops.dequant_l2norm(model_input, num_frames), False
+
+
+def _mean_frame(x, num_frames, rs=None, clamp=False):
+    """sum_f x[b, f] / num_frames [B,D] over the video's frames; clamp: / max(num_frames, 1), and all F frames without num_frames.
+    Bytes: one weighted pooling pass over them (rs = seq_ops.u8_frame_scales, 0 on the padding frames; made here unless the plugin has it
+    already).  Floats: masked sum.  The frames are data: no gradient flows here."""
+    B, F, D = x.shape
+    n = None if num_frames is None else num_frames.to(torch.float32)
+    if clamp and n is not None:
+        n = n.clamp(min=1)
+    if x.dtype == torch.uint8:
+        if rs is None:
+            rs = seq_ops.u8_frame_scales(x, num_frames)
+        inv = torch.full((B,), 1.0 / F, dtype=torch.float32, device=x.device) if n is None else 1.0 / n
+        return seq_ops.pool_u8_raw(inv.view(B, 1, 1).expand(B, F, 1).contiguous(), x, rs).view(B, D)
+    if n is None:
+        return x.sum(dim=1) / float(F)
+    mask = (torch.arange(F, device=x.device)[None, :] < num_frames[:, None]).to(x.dtype)
+    return (x * mask[:, :, None]).sum(dim=1) / n.to(x.dtype)[:, None]
+
+
 def _stack_input(model_input, num_frames, dropping=False):
     """What the native stack reads: the raw reader bytes [B,F,D] where its layer-0 projection consumes them directly (csrc/u8proj.hip:
     exact bf16 operands, the dequantise / l2-normalise affine folded into the GEMM epilogue -- no fp32 [B,F,D] tensor, no transpose
-    copy), else float frames time-major [F,B,D] (dequantised first when they arrive as bytes)."""
-    if model_input.dtype == torch.uint8:
-        if _lib_u8_ok(model_input.shape[2]) and not dropping:
-            return model_input                                   # [B,F,D] uint8, re-ordered time-major by the conversion pass
-        return ops.dequant_l2norm(model_input, num_frames).transpose(0, 1).contiguous()
-    return model_input.transpose(0, 1).contiguous()              # [F,B,D]   (layout glue)
+    copy; not under a DropoutWrapper), else float frames time-major [F,B,D] (dequantised first when they arrive as bytes)."""
+    x, u8 = _bytes_or_floats(model_input, num_frames, lambda q: _lib_u8_ok(q.shape[2]) and not dropping)
+    return x if u8 else x.transpose(0, 1).contiguous()          # bytes: re-ordered time-major by the conversion pass; floats: layout glue
+
+
+def _native_stack(x_tm, num_frames, wb, **kwargs):
+    """seq_ops.lstm_stack as every plugin here runs it: BasicLSTMCell(forget_bias=1.0), the flags' pipeline chunks and compute dtype."""
+    return seq_ops.lstm_stack(x_tm, num_frames, wb, forget_bias=1.0, chunks=FLAGS.lstm_pipeline_chunks,
+                              bf16=FLAGS.compute_dtype == "bfloat16", **kwargs)
 
 
 def _lstm_cells(d_in, lstm_size, number_of_layers, multi=True):
@@ -85,8 +117,7 @@ def _lstm_stack(model_input, num_frames, lstm_size, number_of_layers, scope="RNN
     with g.variable_scope(scope):
         wb = _lstm_cells(model_input.shape[2], lstm_size, number_of_layers)
     # all layers in one op: layer l+1 works on time chunk c while layer l is already in chunk c+1 (seq_ops._LstmStack)
-    return seq_ops.lstm_stack(x_tm, num_frames, wb, forget_bias=1.0, chunks=FLAGS.lstm_pipeline_chunks,
-                              input_keep_prob=input_keep_prob, bf16=FLAGS.compute_dtype == "bfloat16")
+    return _native_stack(x_tm, num_frames, wb, input_keep_prob=input_keep_prob)
 
 
 class FrameLevelLogisticModel(models.BaseModel):
@@ -95,16 +126,10 @@ class FrameLevelLogisticModel(models.BaseModel):
     accepts_quantized_input = True
 
     def create_model(self, model_input, vocab_size, num_frames, **unused_params):
-        if model_input.dtype == torch.uint8 and seq_ops.u8_attention_supported(model_input, 1):
-            # the reader's bytes: sum_f x[b, f] / num_frames as one weighted pooling pass over them (rs is 0 on the padding frames)
-            B, F, D = model_input.shape
-            q = model_input.contiguous()
-            rs = seq_ops.u8_frame_scales(q, num_frames)
-            inv = 1.0 / num_frames.to(torch.float32)
-            avg_pooled = seq_ops.pool_u8_raw(inv.view(B, 1, 1).expand(B, F, 1).contiguous(), q, rs).view(B, D)
+        model_input, u8 = _bytes_or_floats(model_input, num_frames, lambda q: seq_ops.u8_attention_supported(q, 1))
+        if u8:
+            avg_pooled = _mean_frame(model_input, num_frames)
         else:
-            if model_input.dtype == torch.uint8:
-                model_input = ops.dequant_l2norm(model_input, num_frames)
             denominators = num_frames.to(torch.float32).unsqueeze(1)
             avg_pooled = model_input.sum(dim=1) / denominators     # input is data: no gradient flows here
         output = video_level_models.fully_connected(avg_pooled, vocab_size, "fully_connected", activation="sigmoid",
@@ -177,8 +202,7 @@ class BiUniLstmModel(models.BaseModel):
         g = get_default_graph()
         with g.variable_scope("RNN"):
             wb2 = _lstm_cells(2 * lstm_size, lstm_size, 1, multi=False)
-        _, fin2 = seq_ops.lstm_stack(l1, num_frames, wb2, forget_bias=1.0, chunks=FLAGS.lstm_pipeline_chunks,
-                                     bf16=FLAGS.compute_dtype == "bfloat16", slot=2)
+        _, fin2 = _native_stack(l1, num_frames, wb2, slot=2)
         state = torch.cat([t for pair in fin_fw + fin_bw + fin2 for t in pair], dim=1)
         return _head()().create_model(model_input=state, original_input=model_input, vocab_size=vocab_size, **unused_params)
 
@@ -201,15 +225,12 @@ class LstmMemoryModel(models.BaseModel):
                                       num_frames=num_frames, **unused_params)
 
 
-def _recurrent_input(model_input, num_frames):
+def _hoisted_input(model_input, num_frames):
     """Layer-0 input of a GRU / LayerNorm-LSTM stack: the reader's bytes as operand images (seq_ops.U8FrameImages: the hoisted input
     projection and its weight gradient read them, no fp32 [B,F,D] tensor) where the byte products cover the shape, else the float
     frames time-major [F,B,D] (dequantised first when they arrive as bytes)."""
-    if model_input.dtype == torch.uint8:
-        if seq_ops.u8_hoisted_supported(model_input):
-            return seq_ops.U8FrameImages(model_input, num_frames)
-        model_input = ops.dequant_l2norm(model_input, num_frames)
-    return model_input.transpose(0, 1).contiguous()          # (layout glue)
+    x, u8 = _bytes_or_floats(model_input, num_frames, seq_ops.u8_hoisted_supported)
+    return seq_ops.U8FrameImages(x, num_frames) if u8 else x.transpose(0, 1).contiguous()          # (layout glue)
 
 
 def _gru_stack(model_input, num_frames, gru_size, number_of_layers):
@@ -217,7 +238,7 @@ def _gru_stack(model_input, num_frames, gru_size, number_of_layers):
     (W/all_frame_models/gru_pooling_model.py:34-47).  TF-1.0 names: RNN/multi_rnn_cell/cell_<l>/gru_cell/{gates,candidate}/
     {weights,biases}; the gate bias starts at 1.  Returns (top outputs time-major [F,B,H], [h_l final])."""
     g = get_default_graph()
-    x_tm = _recurrent_input(model_input, num_frames)
+    x_tm = _hoisted_input(model_input, num_frames)
     finals = []
     d_in = model_input.shape[2]
     with g.variable_scope("RNN"):
@@ -245,7 +266,7 @@ class GruPoolingModel(models.BaseModel):
     """W/all_frame_models/gru_pooling_model.py:13-58: GRU stack, head input = outputs averaged over the video's frames.
     (The reference file divides by tf.maximum(num_frames, tf.ones([batch_size, 1])) with `batch_size` undefined -- it raises
     NameError at graph construction; built here with the evident meaning.)"""
-    accepts_quantized_input = True                         # _recurrent_input: layer 0 reads the reader's bytes
+    accepts_quantized_input = True                         # _hoisted_input: layer 0 reads the reader's bytes
 
     def create_model(self, model_input, vocab_size, num_frames, **unused_params):
         out_tm, _ = _gru_stack(model_input, num_frames, FLAGS.gru_cells, FLAGS.gru_layers)
@@ -257,7 +278,7 @@ class GruPoolingModel(models.BaseModel):
 class GruWithPoolingModel(models.BaseModel):
     """W/all_frame_models/gru_with_pooling_model.py:13-60: head input = [mean-pooled outputs || final state of every layer]
     (state_is_tuple=False: [h_0 || h_1 ...]).  Same `batch_size` NameError in the reference as GruPoolingModel."""
-    accepts_quantized_input = True                         # _recurrent_input: layer 0 reads the reader's bytes
+    accepts_quantized_input = True                         # _hoisted_input: layer 0 reads the reader's bytes
 
     def create_model(self, model_input, vocab_size, num_frames, **unused_params):
         out_tm, finals = _gru_stack(model_input, num_frames, FLAGS.gru_cells, FLAGS.gru_layers)
@@ -273,13 +294,13 @@ class LayerNormLstmMemoryModel(models.BaseModel):
     """W/all_frame_models/layernorm_lstm_memory_model.py:13-72: MultiRNNCell([LayerNormBasicLSTMCell(H)] * L); with --dropout the
     cells get dropout_keep_prob=keep_prob (recurrent dropout on the candidate); head input = concat of the (normalised) c
     states.  TF-1.0 names: RNN/multi_rnn_cell/cell_<l>/layer_norm_basic_lstm_cell/{weights, <gate>/gamma, <gate>/beta}."""
-    accepts_quantized_input = True                         # _recurrent_input: layer 0 reads the reader's bytes
+    accepts_quantized_input = True                         # _hoisted_input: layer 0 reads the reader's bytes
 
     def create_model(self, model_input, vocab_size, num_frames, dropout=False, keep_prob=None, noise_level=None,
                      **unused_params):
         lstm_size = int(FLAGS.lstm_cells)
         g = get_default_graph()
-        x_tm = _recurrent_input(model_input, num_frames)
+        x_tm = _hoisted_input(model_input, num_frames)
         cs = []
         d_in = model_input.shape[2]
         with g.variable_scope("RNN"):
@@ -297,16 +318,6 @@ class LayerNormLstmMemoryModel(models.BaseModel):
             final_state = ops.add_noise(final_state, noise_level)
         return _head()().create_model(model_input=final_state, original_input=model_input, vocab_size=vocab_size,
                                       **unused_params)
-
-
-def _u8_or_float(model_input, num_frames, num_attentions):
-    """(input, True) when the raw uint8 frames can go all the way (the stack's layer-0 projection and the attention FC both read bytes);
-    else the dequantised, l2-normalised float frames the reference's transformer would have handed over."""
-    if model_input.dtype != torch.uint8:
-        return model_input, False
-    if _lib_u8_ok(model_input.shape[2]) and seq_ops.u8_attention_supported(model_input, num_attentions):
-        return model_input.contiguous(), True
-    return ops.dequant_l2norm(model_input, num_frames), False
 
 
 def _attention_fc_u8(q, num_frames, parts, num_outputs, scope, l2_penalty, rs=None):
@@ -332,21 +343,28 @@ class LstmAttentionMaxPoolingModel(models.BaseModel):
         lstm_size = int(FLAGS.lstm_cells)
         number_of_layers = FLAGS.lstm_layers
         num_attentions = FLAGS.lstm_attentions
-        model_input, u8 = _u8_or_float(model_input, num_frames, num_attentions)
+        # bytes: raw reader bytes into the stack AND the attention FC
+        model_input, u8 = _bytes_or_floats(model_input, num_frames, lambda q: _lib_u8_ok(q.shape[2]) and
+                                           seq_ops.u8_attention_supported(q, num_attentions))
         out_tm, _ = _lstm_stack(model_input, num_frames, lstm_size, number_of_layers)
         outputs = out_tm.transpose(0, 1).contiguous()                               # [B,F,H]
-        if u8:                                                                      # raw reader bytes into the stack AND the attention FC
-            attention_activations = _attention_fc_u8(model_input, num_frames, [outputs], num_attentions, "attention-" + sub_scope,
-                                                     l2_penalty)
+        parts, rs = self.attention_parts(model_input, num_frames, l2_penalty)
+        if u8:
+            attention_activations = _attention_fc_u8(model_input, num_frames, parts + [outputs], num_attentions, "attention-" + sub_scope,
+                                                     l2_penalty, rs=rs)
         else:
-            attention_activations = video_level_models.fully_connected_cat(           # :51-56 FC on concat([input, outputs])
-                [model_input, outputs], num_attentions, "attention-" + sub_scope, l2_penalty=l2_penalty)
+            attention_activations = video_level_models.fully_connected_cat(           # :51-56 FC on concat([input, ..., outputs])
+                [model_input] + parts + [outputs], num_attentions, "attention-" + sub_scope, l2_penalty=l2_penalty)
         attention_weights = seq_ops.attention_weights(attention_activations, num_frames)   # [B,F,A]
         attention_outputs = seq_ops.pool_tn(attention_weights, outputs)                    # [B,A,H]
         moe_predictions = self.sub_moe(attention_outputs, vocab_size, sub_scope="sub-moe")
         predictions = moe_predictions.view(-1, num_attentions, vocab_size)
         max_predictions = ops.frame_pool(predictions, "max")          # tf.reduce_max over the attentions
         return {"predictions": max_predictions}
+
+    def attention_parts(self, model_input, num_frames, l2_penalty):
+        """(what the attention FC sees between the frames and the LSTM outputs, the bytes' frame scales if they were needed): nothing."""
+        return [], None
 
     def sub_moe(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", **unused_params):
         num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
@@ -372,10 +390,8 @@ class LstmParallelFinaloutputModel(models.BaseModel):
         states, off = [], 0
         for i, (fs, hs) in enumerate(zip(feature_sizes, lstm_sizes)):
             sub_input = model_input[:, :, off:off + fs].contiguous()
-            if sub_input.dtype != torch.uint8:
+            if sub_input.dtype != torch.uint8:                        # (bytes: _stack_input reads them or dequantises + normalises the slice)
                 sub_input = ops.l2_normalize(sub_input)
-            elif not _lib_u8_ok(fs):                                  # (dequant_l2norm normalises the slice and zeroes the padding frames)
-                sub_input = ops.dequant_l2norm(sub_input, num_frames)
             off += fs
             _, finals = _lstm_stack(sub_input, num_frames, hs, number_of_layers, scope="RNN%d" % i)
             states.extend(h for _, h in finals)
@@ -388,36 +404,38 @@ class LstmPositionalAttentionMaxPoolingModel(LstmAttentionMaxPoolingModel):
     """W/all_frame_models/lstm_positional_attention_max_pooling_model.py:10-87: as LstmAttentionMaxPoolingModel, the
     attention FC additionally sees a learned positional embedding [1,F,E] and the masked mean of the input."""
 
-    def create_model(self, model_input, vocab_size, num_frames, num_mixtures=None, l2_penalty=1e-8, sub_scope="",
-                     original_input=None, **unused_params):
-        lstm_size = int(FLAGS.lstm_cells)
-        num_attentions = FLAGS.lstm_attentions
+    def attention_parts(self, model_input, num_frames, l2_penalty):
         B, F, D = model_input.shape
-        model_input, u8 = _u8_or_float(model_input, num_frames, num_attentions)
-        out_tm, _ = _lstm_stack(model_input, num_frames, lstm_size, FLAGS.lstm_layers)
-        outputs = out_tm.transpose(0, 1).contiguous()                               # [B,F,H]
         g = get_default_graph()
         emb = g.get_variable("positional_embedding", (1, F, FLAGS.positional_embedding_size), xavier_uniform, l2=l2_penalty)
         positional_embedding = ops.as_tensor(emb).expand(B, F, FLAGS.positional_embedding_size)
-        if u8:
-            # raw reader bytes: the masked mean frame from the bytes (rs is 0 on the padding frames), the FC on [x | emb | mean | outputs]
-            # with x read as bytes and the mean as ONE row per video
+        if model_input.dtype == torch.uint8:
+            # raw reader bytes: the masked mean frame from the bytes, the FC on [x | emb | mean | outputs] with x read as bytes and the
+            # mean as ONE row per video
             rs = seq_ops.u8_frame_scales(model_input, num_frames)
-            inv = 1.0 / num_frames.to(torch.float32)
-            mean_input = seq_ops.pool_u8_raw(inv.view(B, 1, 1).expand(B, F, 1).contiguous(), model_input, rs).view(B, D)
-            attention_activations = _attention_fc_u8(model_input, num_frames, [positional_embedding.contiguous(), mean_input, outputs],
-                                                     num_attentions, "attention-" + sub_scope, l2_penalty, rs=rs)
-        else:
-            mask = (torch.arange(F, device=model_input.device)[None, :] < num_frames[:, None]).to(model_input.dtype)
-            mean_input = (model_input * mask[:, :, None]).sum(dim=1) / num_frames.to(model_input.dtype)[:, None]
-            attention_activations = video_level_models.fully_connected_cat(
-                [model_input, positional_embedding, mean_input[:, None, :].expand(B, F, D), outputs],
-                num_attentions, "attention-" + sub_scope, l2_penalty=l2_penalty)
-        attention_weights = seq_ops.attention_weights(attention_activations, num_frames)   # [B,F,A]
-        attention_outputs = seq_ops.pool_tn(attention_weights, outputs)                    # [B,A,H]
-        moe_predictions = self.sub_moe(attention_outputs, vocab_size, sub_scope="sub-moe")
-        predictions = moe_predictions.view(-1, num_attentions, vocab_size)
-        return {"predictions": ops.frame_pool(predictions, "max")}
+            return [positional_embedding.contiguous(), _mean_frame(model_input, num_frames, rs)], rs
+        return [positional_embedding, _mean_frame(model_input, num_frames)[:, None, :].expand(B, F, D)], None
+
+
+def _cnn_filters(D, sub_scope, num_filters, filter_sizes, l2_penalty):
+    g = get_default_graph()
+    return [g.get_variable(sub_scope + "cnn-filter-len%d" % fs, (D * fs, nf), random_normal(0.1), l2=l2_penalty)
+            for nf, fs in zip(num_filters, filter_sizes)]
+
+
+def _einsum_cnn(model_input, fvars):
+    """The reference's `cnn` on float frames [B,F,D] (cnn_deep_combine_chain_model.py:60-82, multiscale_cnn_lstm_model.py:12-38): per
+    filter [fs D, N] one ops.linear on the input concatenated with its 1- .. (fs - 1)-frame shifts."""
+    B, F, D = model_input.shape
+    shift_inputs = [model_input]
+    for i in range(1, max(W.data.shape[0] // D for W in fvars)):       # tf.pad(..., [[0,0],[i,0],[0,0]])[:, :F]
+        shift_inputs.append(torch.cat([model_input.new_zeros(B, min(i, F), D), model_input[:, :max(F - i, 0)]], dim=1))
+    outs = []
+    for W in fvars:
+        fs = W.data.shape[0] // D
+        sub_input = torch.cat(shift_inputs[:fs], dim=2) if fs > 1 else shift_inputs[0]
+        outs.append(ops.linear(sub_input.reshape(B * F, fs * D), W).view(B, F, -1))
+    return torch.cat(outs, dim=2)
 
 
 class CnnDeepCombineChainModel(models.BaseModel):
@@ -431,36 +449,17 @@ class CnnDeepCombineChainModel(models.BaseModel):
 
     def cnn(self, model_input, l2_penalty=1e-8, num_filters=(1024, 1024, 1024), filter_sizes=(1, 2, 3), sub_scope="",
             **unused_params):
-        g = get_default_graph()
-        B, F, D = model_input.shape
-        shift_inputs = [model_input]
-        for i in range(1, max(filter_sizes)):                         # tf.pad(..., [[0,0],[i,0],[0,0]])[:, :F]
-            shift_inputs.append(torch.cat([model_input.new_zeros(B, i, D), model_input[:, :F - i]], dim=1))
-        cnn_outputs = []
-        for nf, fs in zip(num_filters, filter_sizes):
-            sub_input = torch.cat(shift_inputs[:fs], dim=2) if fs > 1 else shift_inputs[0]
-            sub_filter = g.get_variable(sub_scope + "cnn-filter-len%d" % fs, (D * fs, nf), random_normal(0.1), l2=l2_penalty)
-            cnn_outputs.append(ops.linear(sub_input, sub_filter))
-        return torch.cat(cnn_outputs, dim=2)
+        return _einsum_cnn(model_input, _cnn_filters(model_input.shape[2], sub_scope, num_filters, filter_sizes, l2_penalty))
 
     def create_model(self, model_input, vocab_size, num_frames, num_mixtures=None, l2_penalty=1e-8, sub_scope="",
                      original_input=None, **unused_params):
         num_layers = FLAGS.deep_chain_layers
         relu_cells = FLAGS.deep_chain_relu_cells
         B, F, D = model_input.shape
-        frames = None
-        if model_input.dtype == torch.uint8:
-            if seq_ops.u8_cnn_supported(model_input) and seq_ops.u8_attention_supported(model_input, 1):
-                frames = seq_ops.U8FrameImages(model_input, num_frames)         # one byte image for every CNN of the chain
-            else:
-                model_input = ops.dequant_l2norm(model_input, num_frames)
-        if frames is not None:
-            rs = seq_ops.u8_frame_scales(frames.q, num_frames)                  # [B,F]; 0 on the padding frames
-            inv = 1.0 / num_frames.to(torch.float32)
-            mean_input = seq_ops.pool_u8_raw(inv.view(B, 1, 1).expand(B, F, 1).contiguous(), frames.q, rs).view(B, D)
-        else:
-            mask = (torch.arange(F, device=model_input.device)[None, :] < num_frames[:, None]).to(model_input.dtype)
-            mean_input = (model_input * mask[:, :, None]).sum(dim=1) / num_frames.to(model_input.dtype)[:, None]
+        model_input, u8 = _bytes_or_floats(model_input, num_frames, lambda q: seq_ops.u8_cnn_supported(q) and
+                                           seq_ops.u8_attention_supported(q, 1))
+        frames = seq_ops.U8FrameImages(model_input, num_frames) if u8 else None   # one byte image for every CNN of the chain
+        mean_input = _mean_frame(model_input, num_frames)
         mean_relu = video_level_models.fully_connected(mean_input, relu_cells, sub_scope + "mean-relu", activation="relu",
                                                        l2_penalty=l2_penalty)
         relu_layers = [ops.l2_normalize(mean_relu)]
@@ -468,9 +467,7 @@ class CnnDeepCombineChainModel(models.BaseModel):
 
         def pooled_cnn(scope):
             if frames is not None:
-                g = get_default_graph()
-                fvars = [g.get_variable(scope + "cnn-filter-len%d" % fs, (D * fs, nfl), random_normal(0.1), l2=l2_penalty)
-                         for nfl, fs in zip(filters["num_filters"], filters["filter_sizes"])]
+                fvars = _cnn_filters(D, scope, l2_penalty=l2_penalty, **filters)
                 if sum(filters["num_filters"]) % 4 == 0:                          # pooled in time-major order, sparse weight gradient
                     return ops.l2_normalize(seq_ops.u8_cnn_maxpool(frames, fvars))
                 cnn_output = seq_ops.u8_cnn(frames, fvars)
@@ -499,16 +496,17 @@ class CnnDeepCombineChainModel(models.BaseModel):
                                             "gates-" + sub_scope, "experts-" + sub_scope, frozen_cols=frozen_cols)
 
 
+def _bn_vars(scope, n):
+    g = get_default_graph()
+    return (g.get_variable(scope + "/gamma", (n,), ones), g.get_variable(scope + "/beta", (n,), zeros),
+            g.get_variable(scope + "/moving_mean", (n,), zeros, trainable=False),
+            g.get_variable(scope + "/moving_variance", (n,), ones, trainable=False))
+
+
 def _batch_norm(x, scope, is_training, eps=1e-3, decay=0.999):
     """slim.batch_norm(center=True, scale=True): batch moments, moving averages and the backward all in
     csrc/dbof.hip (ops.batch_norm).  Couples the examples of the local batch, like the reference."""
-    g = get_default_graph()
-    n = x.shape[-1]
-    gamma = g.get_variable(scope + "/gamma", (n,), ones)
-    beta = g.get_variable(scope + "/beta", (n,), zeros)
-    mm = g.get_variable(scope + "/moving_mean", (n,), zeros, trainable=False)
-    mv = g.get_variable(scope + "/moving_variance", (n,), ones, trainable=False)
-    return ops.batch_norm(x, gamma, beta, mm, mv, is_training, eps, decay)
+    return ops.batch_norm(x, *_bn_vars(scope, x.shape[-1]), is_training, eps, decay)
 
 
 class MultiscaleCnnLstmModel(models.BaseModel):
@@ -531,23 +529,11 @@ class MultiscaleCnnLstmModel(models.BaseModel):
     NUM_FILTERS = (256, 256, 512)
     FILTER_SIZES = (1, 2, 3)
 
-    def _filters(self, D, sub_scope, l2_penalty):
-        g = get_default_graph()
-        return [g.get_variable(sub_scope + "cnn-filter-len%d" % fs, (D * fs, nf), random_normal(0.1), l2=l2_penalty)
-                for nf, fs in zip(self.NUM_FILTERS, self.FILTER_SIZES)]
-
-    def _bn_vars(self, scope, n):
-        g = get_default_graph()
-        return (g.get_variable(scope + "/gamma", (n,), ones), g.get_variable(scope + "/beta", (n,), zeros),
-                g.get_variable(scope + "/moving_mean", (n,), zeros, trainable=False),
-                g.get_variable(scope + "/moving_variance", (n,), ones, trainable=False))
-
     def _rnn(self, x_tm, num_frames, d_in, lstm_size, layer):
         g = get_default_graph()
         with g.variable_scope("RNN-rnn%d" % (layer + 1)):
             wb = _lstm_cells(d_in, lstm_size, 1, multi=False)
-        _, finals = seq_ops.lstm_stack(x_tm, num_frames, wb, forget_bias=1.0, chunks=FLAGS.lstm_pipeline_chunks,
-                                       bf16=FLAGS.compute_dtype == "bfloat16", slot=layer)     # the L stacks are alive in one step
+        _, finals = _native_stack(x_tm, num_frames, wb, slot=layer)                              # the L stacks are alive in one step
         return finals[0][0]                                                                      # state.c
 
     def moe(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, scopename="", **unused_params):
@@ -563,12 +549,8 @@ class MultiscaleCnnLstmModel(models.BaseModel):
         is_training = bool(FLAGS.is_training and is_training)
         features_size = sum(self.NUM_FILTERS)
         B, F, D = model_input.shape
-        frames = None
-        if model_input.dtype == torch.uint8:
-            if seq_ops.u8_cnn_supported(model_input):
-                frames = seq_ops.U8FrameImages(model_input, num_frames)
-            else:
-                model_input = ops.dequant_l2norm(model_input, num_frames)
+        model_input, u8 = _bytes_or_floats(model_input, num_frames, seq_ops.u8_cnn_supported)
+        frames = seq_ops.U8FrameImages(model_input, num_frames) if u8 else None
         fused = seq_ops.MULTISCALE_FUSED and seq_ops.bn_relu_pool2_supported(model_input, features_size)
         nf = num_frames.to(torch.int32)
         # fused: cnn_input is time-major [F_k B, D_k]; generic: batch-major [B, F_k, D_k]
@@ -576,8 +558,8 @@ class MultiscaleCnnLstmModel(models.BaseModel):
         sub_predictions = []
         for layer in range(num_layers):
             scope = "cnn%d" % (layer + 1)
-            fvars = self._filters(D, scope, l2_penalty)
-            gamma, beta, mm, mv = self._bn_vars(scope + "cluster_bn", features_size)
+            fvars = _cnn_filters(D, scope, self.NUM_FILTERS, self.FILTER_SIZES, l2_penalty)
+            gamma, beta, mm, mv = _bn_vars(scope + "cluster_bn", features_size)
             last = layer + 1 == num_layers
             if fused:
                 y = seq_ops.u8_cnn_tm(frames, fvars) if (layer == 0 and frames is not None) else seq_ops.cnn_tm(cnn_input, B, fvars)
@@ -587,7 +569,7 @@ class MultiscaleCnnLstmModel(models.BaseModel):
                 if layer == 0 and frames is not None:
                     cnn_output = seq_ops.u8_cnn(frames, fvars)
                 else:
-                    cnn_output = self.cnn(cnn_input, fvars)
+                    cnn_output = _einsum_cnn(cnn_input, fvars)
                 bn = ops.batch_norm(cnn_output.reshape(B * F, features_size), gamma, beta, mm, mv, is_training, 1e-3, 0.999)
                 relu = torch.relu(bn).view(B, F, features_size)
                 relu_tm = relu.transpose(0, 1).contiguous()
@@ -604,20 +586,6 @@ class MultiscaleCnnLstmModel(models.BaseModel):
         for p in sub_predictions[1:]:
             predictions = predictions + p
         return {"predictions": predictions / float(len(sub_predictions)), "support_predictions": support_predictions}
-
-    @staticmethod
-    def cnn(model_input, fvars):
-        """:12-38 as CnnDeepCombineChainModel.cnn composes it: ops.linear on the input concatenated with its 1- and 2-frame shifts."""
-        B, F, D = model_input.shape
-        shift_inputs = [model_input]
-        for i in range(1, max(W.data.shape[0] // D for W in fvars)):       # tf.pad(..., [[0,0],[i,0],[0,0]])[:, :F]
-            shift_inputs.append(torch.cat([model_input.new_zeros(B, min(i, F), D), model_input[:, :max(F - i, 0)]], dim=1))
-        outs = []
-        for W in fvars:
-            fs = W.data.shape[0] // D
-            sub_input = torch.cat(shift_inputs[:fs], dim=2) if fs > 1 else shift_inputs[0]
-            outs.append(ops.linear(sub_input.reshape(B * F, fs * D), W).view(B, F, -1))
-        return torch.cat(outs, dim=2)
 
 
 class DistillchainMultiscaleCnnLstmModel(MultiscaleCnnLstmModel):
@@ -713,12 +681,11 @@ class NetVLADModel(models.BaseModel):
         # (1 unless clamped) the finishing kernel hands out, so v = vlad * s with s = rsqrt(max(sum_k q, eps)) per video, and
         # v . W = s * (vlad . W): the scale goes onto the [B, hidden] output (same function and gradients as l2_normalize first).
         want_q = seq_ops.vlad_q_supported(D)
-        if model_input.dtype == torch.uint8 and seq_ops.netvlad_fused_supported(model_input, K):
+        model_input, u8 = _bytes_or_floats(model_input, num_frames, lambda q: seq_ops.netvlad_fused_supported(q, K))
+        if u8:
             nsplit = 1 if FLAGS.compute_dtype == "bfloat16" else 2        # f16 operands vs f16 hi+lo (fp32-class)
             vlad = seq_ops.netvlad_pool_u8(model_input, num_frames, Wc, bc, centres, nsplit, want_q=want_q)
         else:
-            if model_input.dtype == torch.uint8:                          # shapes outside the fused kernels' cover
-                model_input = ops.dequant_l2norm(model_input, num_frames)
             s = ops.linear(model_input, Wc, bc)                           # [B,F,K] assignment logits
             a = seq_ops.masked_softmax_rows(s, num_frames)                # softmax_k * mask
             agg = seq_ops.pool_tn(a, model_input)                         # [B,K,D] = a^T x per video
@@ -763,21 +730,18 @@ class GatedNetVLADAttentionChainModel(GatedNetVLADModel):
         A = FLAGS.lstm_attentions
         B, F, D = model_input.shape
         h = self.descriptor(model_input, num_frames)                                       # [B,Hfc] (uint8 stays fused)
-        if seq_ops.u8_attention_supported(model_input, A):
+        x, u8 = _bytes_or_floats(model_input, num_frames, lambda q: seq_ops.u8_attention_supported(q, A))
+        if u8:
             # raw reader bytes all the way: the logit FC, the pooling and their gradients read uint8 (csrc/gemm_skinny.hip)
-            q = model_input.contiguous()
-            rs = seq_ops.u8_frame_scales(q, num_frames)                                    # [B,F]; 0 on the padding frames
-            inv = (1.0 / num_frames.to(torch.float32).clamp(min=1)) if num_frames is not None else \
-                torch.full((B,), 1.0 / F, dtype=torch.float32, device=q.device)
-            mean_x = seq_ops.pool_u8_raw(inv.view(B, 1, 1).expand(B, F, 1).contiguous(), q, rs).view(B, D)
+            rs = seq_ops.u8_frame_scales(x, num_frames)                                    # [B,F]; 0 on the padding frames
+            mean_x = _mean_frame(x, num_frames, rs, clamp=True)
             g = video_level_models.get_default_graph()
             W = g.get_variable("attention-/weights", (2 * D, A), video_level_models.xavier_uniform, l2=l2_penalty)
             b = g.get_variable("attention-/biases", (A,), video_level_models.zeros)
-            act = seq_ops.attention_logits_u8(q, rs, mean_x, W, b)
+            act = seq_ops.attention_logits_u8(x, rs, mean_x, W, b)
             w = seq_ops.attention_weights(act, num_frames)                                 # [B,F,A]
-            att = seq_ops.pool_tn_u8(w, q, rs)                                             # [B,A,D]
+            att = seq_ops.pool_tn_u8(w, x, rs)                                             # [B,A,D]
         else:
-            x = ops.dequant_l2norm(model_input, num_frames) if model_input.dtype == torch.uint8 else model_input
             nf = num_frames.to(x.dtype).clamp(min=1).view(B, 1, 1) if num_frames is not None else float(F)
             mean_x = (x.sum(dim=1, keepdim=True) / nf).view(B, D)                          # tiled over the frames by the FC
             act = video_level_models.fully_connected_cat([x], A, "attention-", l2_penalty=l2_penalty, group_parts=[mean_x])

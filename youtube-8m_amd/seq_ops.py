@@ -79,6 +79,37 @@ def lstm_layer(x_tm, W, b, num_frames, forget_bias=1.0):
     return _LstmLayer.apply(x_tm, _token(W._graph), W, b, num_frames, forget_bias)
 
 
+class _FloatFrames(object):
+    """Float frames x_tm [F,B,D] as a recurrent layer's hoisted input, behind the surface U8FrameImages offers for the reader's bytes:
+    F, B, D, device, `saved` (the tensor the layer saves for backward), project / weight_grad / dx."""
+
+    def __init__(self, x_tm, bf16):
+        x_tm = _f32c(x_tm)
+        _dev(x_tm)
+        self.F, self.B, self.D = x_tm.shape
+        self.device, self.saved, self.bf16 = x_tm.device, x_tm, bf16
+        self.x2 = x_tm.view(self.F * self.B, self.D)
+
+    def project(self, Wrows, bias, out2d):
+        # the h2 role like the LSTM stack's (l2-normalised frames / recurrent outputs |h| <= 1 against one weight matrix: three f16
+        # products instead of six bf16 ones; ops._hoisted_role)
+        ops.gemm_any(self.x2, Wrows, out=out2d, bias=bias, bf16=self.bf16,
+                     role=ops._hoisted_role(self.F * self.B, Wrows.shape[1], self.D, self.bf16))
+
+    def weight_grad(self, dy2d, gWrows, beta):
+        ops.gemm_any(self.x2, dy2d, out=gWrows, transA=True, beta=beta, role="dw", bf16=self.bf16)
+
+    def dx(self, dy2d, Wrows, into=None):
+        """dx [F,B,D] = dy2d . Wrows^T, added to `into` (an earlier dx of the same frames) where given."""
+        out = None if into is None else into.view(self.F * self.B, self.D)
+        return ops.hoisted_dx(dy2d, Wrows, out=out, beta=0.0 if into is None else 1.0, bf16=self.bf16).view(self.F, self.B, self.D)
+
+
+def _hoisted_input(x_tm, bf16):
+    """The layer-0 input of a GRU / LayerNorm-LSTM layer: the reader's bytes (U8FrameImages) as they are, float frames wrapped."""
+    return x_tm if isinstance(x_tm, U8FrameImages) else _FloatFrames(x_tm, bf16)
+
+
 class _GruLayer(torch.autograd.Function):
     """One tf.contrib.rnn.GRUCell layer under tf.nn.dynamic_rnn (W/all_frame_models/gru_pooling_model.py:34-47), time-major.
     x_tm [F,B,in]; Wg "gates/weights" [in+H, 2H] (r | u), bg "gates/biases" [2H]; Wc "candidate/weights" [in+H, H],
@@ -87,29 +118,15 @@ class _GruLayer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_tm, token, Wg, bg, Wc, bc, num_frames):
-        frames = x_tm if isinstance(x_tm, U8FrameImages) else None     # the reader's bytes (layer 0): see u8_hoisted_fwd
-        if frames is None:
-            x_tm = _f32c(x_tm)
-            _dev(x_tm)
-            F, B, Din = x_tm.shape
-            dev = x_tm.device
-        else:
-            F, B, Din = frames.F, frames.B, frames.D
-            dev = frames.q.device
+        bf = ops.FLAGS.compute_dtype == "bfloat16"
+        frames = _hoisted_input(x_tm, bf)
+        F, B, Din, dev = frames.F, frames.B, frames.D, frames.device
         H = Wc.data.shape[1]
         assert Wg.data.shape == (Din + H, 2 * H) and Wc.data.shape[0] == Din + H, "GRU weights must be [in + H, 2H] / [in + H, H]"
-        x2 = x_tm.view(F * B, Din) if frames is None else None
         zg = torch.empty((F, B, 2 * H), dtype=torch.float32, device=dev)
         zc = torch.empty((F, B, H), dtype=torch.float32, device=dev)
-        bf = ops.FLAGS.compute_dtype == "bfloat16"
-        # the hoisted input projections declare the h2 role like the LSTM stack's (l2-normalised frames / GRU outputs |h| <= 1 against one
-        # weight matrix: three f16 products instead of six bf16 ones; ops._hoisted_role)
-        if frames is not None:
-            u8_hoisted_fwd(frames, Wg.data[:Din], bg.data, zg.view(F * B, 2 * H))
-            u8_hoisted_fwd(frames, Wc.data[:Din], bc.data, zc.view(F * B, H))
-        else:
-            ops.gemm_any(x2, Wg.data[:Din], out=zg.view(F * B, 2 * H), bias=bg.data, bf16=bf, role=ops._hoisted_role(F * B, 2 * H, Din, bf))
-            ops.gemm_any(x2, Wc.data[:Din], out=zc.view(F * B, H), bias=bc.data, bf16=bf, role=ops._hoisted_role(F * B, H, Din, bf))
+        frames.project(Wg.data[:Din], bg.data, zg.view(F * B, 2 * H))
+        frames.project(Wc.data[:Din], bc.data, zc.view(F * B, H))
         hs = torch.empty((F + 1, B, H), dtype=torch.float32, device=dev)
         hs[0].zero_()
         rh = torch.empty((F, B, H), dtype=torch.float32, device=dev)
@@ -126,8 +143,8 @@ class _GruLayer(torch.autograd.Function):
             ws = ops._workspace(dev)
             _lib.check(L.yt8m_gru_layer_fwd(_p(zg), _p(zc), _p(Wg.data[Din:]), 2 * H, _p(Wc.data[Din:]), H, _p(hs), _p(rh),
                                             _p(out), _p(nf), F, B, H, _p(ws), ws.numel() * 4, _stream()))
-        ctx.save_for_backward(x_tm if frames is None else frames.r)
-        ctx.frames, ctx.dims = frames, (F, B, Din)
+        ctx.save_for_backward(frames.saved)
+        ctx.frames = frames
         ctx.state = (zg, zc, hs, rh, nf, Wg, bg, Wc, bc)
         ctx.bf16 = bf
         ctx.set_materialize_grads(False)
@@ -135,13 +152,13 @@ class _GruLayer(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, dh_final):
-        (x_tm,) = ctx.saved_tensors
+        ctx.saved_tensors                                            # (the frames' tensor: checked against in-place changes)
         frames = ctx.frames
         zg, zc, hs, rh, nf, Wg, bg, Wc, bc = ctx.state
-        ctx.state = None
-        F, B, Din = ctx.dims
+        ctx.state = ctx.frames = None
+        F, B, Din = frames.F, frames.B, frames.D
         H = Wc.data.shape[1]
-        dev = x_tm.device
+        dev = frames.device
         dzg = torch.empty((F, B, 2 * H), dtype=torch.float32, device=dev)
         dzc = torch.empty((F, B, H), dtype=torch.float32, device=dev)
         work = torch.empty((3, B, H), dtype=torch.float32, device=dev)
@@ -151,23 +168,16 @@ class _GruLayer(torch.autograd.Function):
         _lib.check(_lib.lib().yt8m_gru_layer_bwd(_p(zg), _p(zc), _p(Wg.data[Din:]), 2 * H, _p(Wc.data[Din:]), H, _p(hs), _p(dout),
                                                  _p(dh_final), _p(dzg), _p(dzc), _p(work), _p(nf), F, B, H, _p(ws),
                                                  ws.numel() * 4, _stream()))
-        x2 = x_tm.view(F * B, Din) if frames is None else None
         g2, c2 = dzg.view(F * B, 2 * H), dzc.view(F * B, H)
         bf = ctx.bf16
         if Wg.grad is not None:
             beta = Wg.grad_beta()
-            if frames is not None:
-                u8_hoisted_dw(frames, g2, Wg.grad[:Din], beta)
-            else:
-                ops.gemm_any(x2, g2, out=Wg.grad[:Din], transA=True, beta=beta, role="dw", bf16=bf)
+            frames.weight_grad(g2, Wg.grad[:Din], beta)
             ops.gemm_any(hs[:F].view(F * B, H), g2, out=Wg.grad[Din:], transA=True, beta=beta, role="dw", bf16=bf)
             Wg.grad_done()
         if Wc.grad is not None:
             beta = Wc.grad_beta()
-            if frames is not None:
-                u8_hoisted_dw(frames, c2, Wc.grad[:Din], beta)
-            else:
-                ops.gemm_any(x2, c2, out=Wc.grad[:Din], transA=True, beta=beta, role="dw", bf16=bf)
+            frames.weight_grad(c2, Wc.grad[:Din], beta)
             ops.gemm_any(rh.view(F * B, H), c2, out=Wc.grad[Din:], transA=True, beta=beta, role="dw", bf16=bf)
             Wc.grad_done()
         if bg.grad is not None:
@@ -177,10 +187,8 @@ class _GruLayer(torch.autograd.Function):
             ops.colsum(c2, bc.grad.view(-1), beta=bc.grad_beta())
             bc.grad_done()
         dx = None
-        if ctx.needs_input_grad[0] and frames is None:
-            dx = ops.hoisted_dx(g2, Wg.data[:Din], bf16=bf)
-            ops.hoisted_dx(c2, Wc.data[:Din], out=dx, beta=1.0, bf16=bf)
-            dx = dx.view(F, B, Din)
+        if ctx.needs_input_grad[0]:
+            dx = frames.dx(c2, Wc.data[:Din], into=frames.dx(g2, Wg.data[:Din]))
         return dx, None, None, None, None, None, None
 
 
@@ -197,23 +205,13 @@ class _LnLstmLayer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_tm, token, W, gammas, betas, num_frames, forget_bias, keep_prob, seed):
-        frames = x_tm if isinstance(x_tm, U8FrameImages) else None     # the reader's bytes (layer 0): see u8_hoisted_fwd
-        if frames is None:
-            x_tm = _f32c(x_tm)
-            _dev(x_tm)
-            F, B, Din = x_tm.shape
-            dev = x_tm.device
-        else:
-            F, B, Din = frames.F, frames.B, frames.D
-            dev = frames.q.device
+        bf = ops.FLAGS.compute_dtype == "bfloat16"
+        frames = _hoisted_input(x_tm, bf)
+        F, B, Din, dev = frames.F, frames.B, frames.D, frames.device
         H = W.data.shape[1] // 4
         assert W.data.shape[0] == Din + H, "cell weights must be [in + H, 4H]"
-        bf = ops.FLAGS.compute_dtype == "bfloat16"
-        if frames is not None:
-            z = torch.empty((F, B, 4 * H), dtype=torch.float32, device=dev)
-            u8_hoisted_fwd(frames, W.data[:Din], None, z.view(F * B, 4 * H))
-        else:
-            z = ops.gemm_any(x_tm.view(F * B, Din), W.data[:Din], bf16=bf, role=ops._hoisted_role(F * B, 4 * H, Din, bf)).view(F, B, 4 * H)
+        z = torch.empty((F, B, 4 * H), dtype=torch.float32, device=dev)
+        frames.project(W.data[:Din], None, z.view(F * B, 4 * H))
         gamma = torch.stack([v.data for v in gammas]).contiguous()
         beta = torch.stack([v.data for v in betas]).contiguous()
         stats = torch.zeros((F, B, 10), dtype=torch.float32, device=dev)
@@ -227,8 +225,8 @@ class _LnLstmLayer(torch.autograd.Function):
         _lib.check(_lib.lib().yt8m_lnlstm_layer_fwd(_p(z), _p(W.data[Din:]), 4 * H, _p(gamma), _p(beta), _p(stats), _p(cs), _p(hs),
                                                     _p(out), _p(nf), F, B, H, float(forget_bias), float(keep_prob), int(seed),
                                                     _p(ws), ws.numel() * 4, _stream()))
-        ctx.save_for_backward(x_tm if frames is None else frames.r)
-        ctx.frames, ctx.dims = frames, (F, B, Din)
+        ctx.save_for_backward(frames.saved)
+        ctx.frames = frames
         ctx.state = (z, gamma, beta, stats, cs, hs, nf, W, gammas, betas, float(forget_bias), float(keep_prob), int(seed))
         ctx.bf16 = bf
         ctx.set_materialize_grads(False)
@@ -236,13 +234,13 @@ class _LnLstmLayer(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, dc_final, dh_final):
-        (x_tm,) = ctx.saved_tensors
+        ctx.saved_tensors                                            # (the frames' tensor: checked against in-place changes)
         frames = ctx.frames
         z, gamma, beta, stats, cs, hs, nf, W, gammas, betas, fb, keep, seed = ctx.state
-        ctx.state = None
-        F, B, Din = ctx.dims
+        ctx.state = ctx.frames = None
+        F, B, Din = frames.F, frames.B, frames.D
         H = W.data.shape[1] // 4
-        dev = x_tm.device
+        dev = frames.device
         dz = torch.empty((F, B, 4 * H), dtype=torch.float32, device=dev)
         dyb = torch.empty((F, B, 5 * H), dtype=torch.float32, device=dev)
         dyg = torch.empty((F, B, 5 * H), dtype=torch.float32, device=dev)
@@ -257,10 +255,7 @@ class _LnLstmLayer(torch.autograd.Function):
         dz2 = dz.view(F * B, 4 * H)
         if W.grad is not None:
             b = W.grad_beta()
-            if frames is not None:
-                u8_hoisted_dw(frames, dz2, W.grad[:Din], b)
-            else:
-                ops.gemm_any(x_tm.view(F * B, Din), dz2, out=W.grad[:Din], transA=True, beta=b, role="dw", bf16=ctx.bf16)
+            frames.weight_grad(dz2, W.grad[:Din], b)
             ops.gemm_any(hs[:F].view(F * B, H), dz2, out=W.grad[Din:], transA=True, beta=b, role="dw", bf16=ctx.bf16)
             W.grad_done()
         yb, yg = dyb.view(F * B, 5 * H), dyg.view(F * B, 5 * H)
@@ -270,8 +265,8 @@ class _LnLstmLayer(torch.autograd.Function):
                     ops.colsum(src[:, k * H:(k + 1) * H], v.grad.view(-1), beta=v.grad_beta())
                     v.grad_done()
         dx = None
-        if ctx.needs_input_grad[0] and frames is None:
-            dx = ops.hoisted_dx(dz2, W.data[:Din], bf16=ctx.bf16).view(F, B, Din)
+        if ctx.needs_input_grad[0]:
+            dx = frames.dx(dz2, W.data[:Din])
         return dx, None, None, None, None, None, None, None, None
 
 
@@ -1480,30 +1475,55 @@ def attention_logits_u8(q, rs, mean_x, W, b, parts=None):
 U8_ALPHA = 4.0 / 255.0
 
 
-def u8_cnn_supported(q):
-    """The einsum CNN of W/all_frame_models/cnn_deep_combine_chain_model.py:60-82 straight from the reader's bytes (u8_cnn): the frame
-    image kernels want D % 16 == 0, the shifted weight-gradient products whole K blocks per shift (B % 16 == 0)."""
+def _u8_frames_supported(q):
+    """What every product on U8FrameImages needs: the reader's bytes [B,F,D] on the device, D in whole K blocks of 16 that the byte
+    projection covers."""
     if q.dtype != torch.uint8 or q.dim() != 3 or not q.is_cuda:
         return False
     B, F, D = q.shape
-    return bool(D % 16 == 0 and 16 <= D <= 2048 and B % 16 == 0 and F >= 1 and _lib.lib().yt8m_u8_proj_supported(D))
+    return bool(D % 16 == 0 and 16 <= D <= 2048 and F >= 1 and _lib.lib().yt8m_u8_proj_supported(D))
+
+
+def u8_cnn_supported(q):
+    """The einsum CNN of W/all_frame_models/cnn_deep_combine_chain_model.py:60-82 straight from the reader's bytes (u8_cnn): the shifted
+    weight-gradient products want whole K blocks per shift (B % 16 == 0)."""
+    return _u8_frames_supported(q) and q.shape[0] % 16 == 0
+
+
+def u8_hoisted_supported(q):
+    """A recurrent layer's hoisted input projection straight from the reader's bytes (GRU and LayerNorm-LSTM layers outside the native
+    stack): whole K blocks of frame rows for the weight gradient (F B % 16 == 0)."""
+    return _u8_frames_supported(q) and (q.shape[1] * q.shape[0]) % 16 == 0
+
+
+def _colsum_row(x):
+    return ops.colsum(x, torch.empty((x.shape[1],), dtype=torch.float32, device=x.device))
+
+
+def _colsum_row_torch(x):
+    return x.sum(0).contiguous()
 
 
 class U8FrameImages(object):
     """Operand images of one batch of raw frames q [B,F,D] uint8, made ONCE per step and shared by every product that reads the frames:
     `img` = (q - 128) as a one-plane half image in TIME-major row order t B + b (exact; yt8m_u8_frames_image_f16), `r` [F B] = 1 / ||a0 q + c0||
-    per frame (0 on the padding frames), `trans()` = the transposed image (K = frame rows) for weight gradients, made on first use."""
+    per frame (0 on the padding frames), `trans()` = the transposed image (K = frame rows) for weight gradients, made on first use.
+    project / weight_grad are the two products on them, x = the dequantised, l2-normalised, padding-masked frames (W/utils.py:23-38,
+    readers.py:178-187, default_transformer.py:4-8); a recurrent layer takes them as its hoisted input (as _FloatFrames for floats), the
+    einsum CNN once per shift: in time-major row order a shift by i frames is a row offset of i B."""
 
     def __init__(self, q, num_frames, eps=1e-12):
         q = q.contiguous()
         _dev(q)
         self.q, self.nf = q, _nf(num_frames)
         self.B, self.F, self.D = q.shape
+        self.device = q.device
         M = self.F * self.B
         self.img = torch.empty(((M + 31) // 32) * (self.D // 16) * 1024, dtype=torch.uint8, device=q.device)
         self.r = torch.empty((M,), dtype=torch.float32, device=q.device)
         _lib.check(_lib.lib().yt8m_u8_frames_image_f16(_p(q), _p(self.nf), self.B, self.F, self.D, float(eps), _p(self.img), None, _p(self.r),
                                                        _stream()))
+        self.saved = self.r                                           # what a layer saves for backward
         self._t = None
 
     def trans(self):
@@ -1513,123 +1533,85 @@ class U8FrameImages(object):
             _lib.check(_lib.lib().yt8m_u8_frames_image_t_f16(_p(self.q), _p(self.nf), self.B, self.F, self.D, _p(self._t), _stream()))
         return self._t
 
+    def project(self, Wrows, bias, out2d, *, row_shift=0, image=None, beta=0.0):
+        """out2d[row_shift B ..] = x[.. M - row_shift B] . Wrows (+ bias) (+ itself if beta == 1), out2d [F B rows (t B + b), N] (a column
+        window of a wider matrix will do): two f16 products of the frames' half image against (alpha Wrows)^T under a device-measured
+        scale, the affine remainder in the epilogue (yt8m_gemm_h1x2_nt_ex) -- the form the native LSTM stack's layer 0 takes.
+        image = (H2Image of a taller W^T, first of Wrows' rows in it): Wrows is that K window of an operand image made by the caller."""
+        out = out2d[row_shift * self.B:]
+        rows, D = out.shape[0], self.D
+        if rows <= 0:
+            return
+        w2, k0 = image or (ops.h2_split(Wrows, plain=False, trans=True, scale=U8_ALPHA, dynamic=True)[1], 0)
+        bptr = ctypes.c_void_p(w2.buf.data_ptr() + k0 // 16 * 2048)     # K blocks of 16: two 1 KiB half planes each
+        N = Wrows.shape[1]
+        cs = _colsum_row(Wrows)
+        ws = ops._workspace(self.device)
+        _lib.check(_lib.lib().yt8m_gemm_h1x2_nt_ex(rows, N, D, _p(self.img), 0, bptr, w2.K // 16 if w2.K > D else 0, _p(out), out.stride(0),
+                                                   _p(bias), 1.0, _p(w2.dinv), _p(self.r), _p(cs), U8_BETA, float(beta), _p(ws),
+                                                   ws.numel() * 4, _stream()))
+
+    def weight_grad(self, dy2d, gWrows, beta, *, row_shift=0, colsum=_colsum_row):
+        """gWrows [D, N] (beta = 0 / 1: overwrite / accumulate) (+)= x[.. M - row_shift B]^T . dy2d[row_shift B ..]: the transposed byte
+        image at K offset 0 against (r (.) dy)^T written by one pass over dy (yt8m_h2_split_ex), the affine remainder as a rank-1 term of
+        the epilogue.  colsum: how that pass' per-tile partial sums are reduced (the CNN keeps torch's sum, see DESIGN_LOG.md 16).  The
+        frames are data: no dx."""
+        M, D = self.F * self.B, self.D
+        part = dy2d[row_shift * self.B:].contiguous()                 # dy of the frames that saw this shift
+        rows, N = part.shape
+        if rows <= 0:
+            if beta == 0.0:
+                gWrows.zero_()
+            return
+        dev = part.device
+        lib = _lib.lib()
+        nb = max(lib.yt8m_x3_image_bytes(N, rows) // 3 * 2, 16)
+        word = ops.h2_absmax(part)
+        dzT = torch.empty(nb, dtype=torch.uint8, device=dev)
+        dzTs = torch.empty(nb, dtype=torch.uint8, device=dev)
+        ntile = (rows + 63) // 64
+        cp = torch.empty((ntile, N), dtype=torch.float32, device=dev)
+        cps = torch.empty((ntile, N), dtype=torch.float32, device=dev)
+        _lib.check(lib.yt8m_h2_split_ex(_p(part), rows, N, N, 1.0, _p(word), _p(self.r), None, _p(dzT), _p(dzTs), _p(cp), _p(cps), _stream()))
+        csr = colsum(cps)
+        ws = ops._workspace(dev)
+        _lib.check(lib.yt8m_gemm_h1x2_nt_ex(D, N, rows, _p(self.trans()), (M + 15) // 16, _p(dzTs), 0, _p(gWrows), N, None, U8_ALPHA, _p(word),
+                                            None, _p(csr), U8_BETA / U8_ALPHA, float(beta), _p(ws), ws.numel() * 4, _stream()))
+
+    def dx(self, dy2d, Wrows, into=None):
+        return None                                                   # the frames are data
+
 
 def _u8_cnn_dense(frames, filters):
     """y [F B rows (t B + b), sum N_k]: for every filter k and shift i < fs_k
         y_k[rows i B ..] += x[rows .. M - i B] . W_k[i D : (i + 1) D]
-    as ONE yt8m_gemm_h1x2_nt_ex launch on the frames' half image (two f16 products against the K range [i D, (i + 1) D) of the filter's
-    half-plane image (alpha W_k)^T -- one image and one device-measured scale per filter --, dequantise / l2-normalise affine in the
-    epilogue), accumulated in place: in time-major row order a shift by i frames is a row offset of i B."""
-    B, F, D = frames.B, frames.F, frames.D
-    M = F * B
-    dev = frames.q.device
-    lib = _lib.lib()
+    as ONE frames.project launch against the K range [i D, (i + 1) D) of the filter's half-plane image (alpha W_k)^T -- one image and
+    one device-measured scale per filter --, accumulated in place."""
+    D = frames.D
     Ntot = sum(W.data.shape[1] for W in filters)
-    y = torch.empty((M, Ntot), dtype=torch.float32, device=dev)
-    ws = ops._workspace(dev)
+    y = torch.empty((frames.F * frames.B, Ntot), dtype=torch.float32, device=frames.device)
     c0 = 0
     for W in filters:
         assert W.data.shape[0] % D == 0 and W.data.is_contiguous(), "cnn filter must be [fs * D, N]"
         fs, N = W.data.shape[0] // D, W.data.shape[1]
         _, w2 = ops.h2_split(W.data, plain=False, trans=True, scale=U8_ALPHA, dynamic=True)     # [N rows, K = fs D]
-        cs = torch.empty((fs, N), dtype=torch.float32, device=dev)                                  # column sums per shift slice
         for i in range(fs):
-            ops.colsum(W.data[i * D:(i + 1) * D], cs[i])
-        for i in range(fs):
-            rows = M - i * B
-            if rows <= 0:
-                continue
-            bptr = ctypes.c_void_p(w2.buf.data_ptr() + i * (D // 16) * 2048)                    # K blocks of 16: two 1 KiB half planes each
-            cptr = ctypes.c_void_p(y.data_ptr() + (i * B * Ntot + c0) * 4)
-            _lib.check(lib.yt8m_gemm_h1x2_nt_ex(rows, N, D, _p(frames.img), 0, bptr, fs * D // 16 if fs > 1 else 0, cptr, Ntot, None, 1.0,
-                                                _p(w2.dinv), _p(frames.r), _p(cs[i]), U8_BETA, 1.0 if i else 0.0, _p(ws), ws.numel() * 4,
-                                                _stream()))
+            frames.project(W.data[i * D:(i + 1) * D], None, y[:, c0:c0 + N], row_shift=i, image=(w2, i * D), beta=1.0 if i else 0.0)
         c0 += N
     return y
 
 
-def u8_hoisted_supported(q):
-    """A recurrent layer's hoisted input projection straight from the reader's bytes (u8_hoisted_fwd / _dw: GRU and LayerNorm-LSTM layers
-    outside the native stack): D % 16 == 0, whole K blocks of frame rows for the weight gradient (F B % 16 == 0)."""
-    if q.dtype != torch.uint8 or q.dim() != 3 or not q.is_cuda:
-        return False
-    B, F, D = q.shape
-    return bool(D % 16 == 0 and 16 <= D <= 2048 and (F * B) % 16 == 0 and F >= 1 and _lib.lib().yt8m_u8_proj_supported(D))
-
-
-def u8_hoisted_fwd(frames, Wrows, bias, out2d):
-    """out2d [F B rows (t B + b), N] = x . Wrows (+ bias), x = the dequantised, l2-normalised, padding-masked frames (W/utils.py:23-38,
-    readers.py:178-187, default_transformer.py:4-8): two f16 products of the frames' half image against (alpha Wrows)^T under a
-    device-measured scale, the affine remainder in the epilogue (yt8m_gemm_h1x2_nt_ex) -- the form the native LSTM stack's layer 0 takes."""
-    M, D = frames.F * frames.B, frames.D
-    N = Wrows.shape[1]
-    dev = frames.q.device
-    _, w2 = ops.h2_split(Wrows, plain=False, trans=True, scale=U8_ALPHA, dynamic=True)
-    cs = torch.empty((N,), dtype=torch.float32, device=dev)
-    ops.colsum(Wrows, cs)
-    ws = ops._workspace(dev)
-    _lib.check(_lib.lib().yt8m_gemm_h1x2_nt_ex(M, N, D, _p(frames.img), 0, _p(w2.buf), 0, _p(out2d), N, _p(bias), 1.0, _p(w2.dinv),
-                                               _p(frames.r), _p(cs), U8_BETA, 0.0, _p(ws), ws.numel() * 4, _stream()))
-
-
-def u8_hoisted_dw(frames, dz2d, gWrows, beta):
-    """gWrows [D, N] (beta = 0 / 1: overwrite / accumulate) (+)= x^T . dz2d: the transposed byte image against (r (.) dz)^T written by one
-    pass over dz (yt8m_h2_split_ex), the affine remainder as a rank-1 term of the epilogue."""
-    M, D = frames.F * frames.B, frames.D
-    N = dz2d.shape[1]
-    dev = dz2d.device
-    lib = _lib.lib()
-    nb = max(lib.yt8m_x3_image_bytes(N, M) // 3 * 2, 16)
-    word = ops.h2_absmax(dz2d)
-    dzT = torch.empty(nb, dtype=torch.uint8, device=dev)
-    dzTs = torch.empty(nb, dtype=torch.uint8, device=dev)
-    ntile = (M + 63) // 64
-    cp = torch.empty((ntile, N), dtype=torch.float32, device=dev)
-    cps = torch.empty((ntile, N), dtype=torch.float32, device=dev)
-    _lib.check(lib.yt8m_h2_split_ex(_p(dz2d), M, N, N, 1.0, _p(word), _p(frames.r), None, _p(dzT), _p(dzTs), _p(cp), _p(cps), _stream()))
-    csr = torch.empty((N,), dtype=torch.float32, device=dev)
-    ops.colsum(cps, csr)
-    ws = ops._workspace(dev)
-    _lib.check(lib.yt8m_gemm_h1x2_nt_ex(D, N, M, _p(frames.trans()), (M + 15) // 16, _p(dzTs), 0, _p(gWrows), N, None, U8_ALPHA, _p(word), None,
-                                        _p(csr), U8_BETA / U8_ALPHA, float(beta), _p(ws), ws.numel() * 4, _stream()))
-
-
 def _u8_cnn_dw(frames, filters, dyt):
-    """Weight gradients of _u8_cnn_dense from dyt [F B rows (t B + b), sum N_k]: per filter slice x[.. M - i B]^T . dy_k[i B ..] from the
-    transposed byte image at K offset 0 (the recurrent stack's layer-0 form).  The frames are data: no dx."""
-    B, F, D = frames.B, frames.F, frames.D
-    M = F * B
-    dev = dyt.device
-    lib = _lib.lib()
-    ws = ops._workspace(dev)
-    nb = lambda rows_, K: max(lib.yt8m_x3_image_bytes(rows_, K) // 3 * 2, 16)
-    qT = None
+    """Weight gradients of _u8_cnn_dense from dyt [F B rows (t B + b), sum N_k]: per filter slice x[.. M - i B]^T . dy_k[i B ..]
+    (frames.weight_grad)."""
+    D = frames.D
     c0 = 0
     for W in filters:
         fs, N = W.data.shape[0] // D, W.data.shape[1]
         if W.trainable and W.grad is not None:
             wbeta = float(W.grad_beta())
-            if qT is None:
-                qT = frames.trans()
             for i in range(fs):
-                rows = M - i * B
-                gW = W.grad[i * D:(i + 1) * D]
-                if rows <= 0:
-                    if wbeta == 0.0:
-                        gW.zero_()
-                    continue
-                part = dyt[i * B:, c0:c0 + N].contiguous()          # dy of the frames that saw this shift
-                word = ops.h2_absmax(part)
-                dzT = torch.empty(nb(N, rows), dtype=torch.uint8, device=dev)
-                dzTs = torch.empty(nb(N, rows), dtype=torch.uint8, device=dev)
-                ntile = (rows + 63) // 64
-                cp = torch.empty((ntile, N), dtype=torch.float32, device=dev)
-                cps = torch.empty((ntile, N), dtype=torch.float32, device=dev)
-                _lib.check(lib.yt8m_h2_split_ex(_p(part), rows, N, N, 1.0, _p(word), _p(frames.r), None, _p(dzT), _p(dzTs), _p(cp),
-                                                _p(cps), _stream()))
-                csr = cps.sum(0).contiguous()
-                _lib.check(lib.yt8m_gemm_h1x2_nt_ex(D, N, rows, _p(qT), (M + 15) // 16, _p(dzTs), 0, _p(gW), N, None, U8_ALPHA, _p(word),
-                                                    None, _p(csr), U8_BETA / U8_ALPHA, wbeta, _p(ws), ws.numel() * 4, _stream()))
+                frames.weight_grad(dyt[:, c0:c0 + N], W.grad[i * D:(i + 1) * D], wbeta, row_shift=i, colsum=_colsum_row_torch)
             W.grad_done()
         c0 += N
 
