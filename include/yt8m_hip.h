@@ -181,6 +181,23 @@ int yt8m_timepool_shiftmax_f32(const float* z, int64_t F, int64_t B, int64_t ldz
                                int32_t* idx, int64_t ldo, yt8m_stream_t stream);
 int yt8m_u8_cnn_pool_dw(const uint8_t* q, const float* r_tm, const int32_t* idx, const float* g, int64_t ldg, int64_t B, int64_t F, int64_t D,
                         int64_t N, int64_t fs, float* dW, float beta, yt8m_stream_t stream);
+/* The backward of a max-pooled einsum CNN whose input is NOT data (csrc/cnn_pool_f32.hip; W/all_frame_models/lstm_cnn_deep_combine_chain_model.py:
+ * the CNNs read the LSTM outputs).  x [F B rows (t B + b), D] fp32 time-major (row stride ldx); g, idx [B, .] (row stride ldg) are the
+ * gradient at the pooled output and the argmax the pooling kept; an idx outside [0, F) contributes nothing.  fp32, fixed summation order:
+ * two calls on the same inputs give the same bits.
+ *   yt8m_f32_cnn_pool_dw : the fp32 twin of yt8m_u8_cnn_pool_dw for ONE filter W [fs D, N] (g, idx point at its first column):
+ *                          dW[i D + d, n] = beta dW + sum_b g[b, n] x[(idx[b, n] - i) B + b, d]   (terms with idx - i < 0 dropped; beta 0 / 1;
+ *                          dW row stride lddw).  D, ldx multiples of 4, D <= 4096, x 16-byte aligned.
+ *   yt8m_f32_cnn_pool_dx : EVERY filter of EVERY CNN that read x in one call (nfilt <= 32 filters in the column order of g / idx; host arrays
+ *                          fs, ncol, wt): dx[(idx[b, n] - i) B + b, :] += g[b, n] W_k[i D : (i + 1) D, n] over all filters k, shifts i < fs[k]
+ *                          and columns n.  wt[k] = W_k TRANSPOSED, [ncol[k], fs[k] D] contiguous (device pointers, 8-byte aligned).  Writes
+ *                          every row of dx [F B, D] (row stride lddx): rows nothing points at become zeros.  No atomics on floats: each row
+ *                          has one owner that adds its terms in an order fixed by the inputs.  D, lddx even, D <= 2048;
+ *                          8 F max(fs) + 12 sum(ncol) bytes of LDS <= 160 KiB. */
+int yt8m_f32_cnn_pool_dw(const float* x, int64_t ldx, const int32_t* idx, const float* g, int64_t ldg, int64_t B, int64_t F, int64_t D,
+                         int64_t N, int64_t fs, float* dW, int64_t lddw, float beta, yt8m_stream_t stream);
+int yt8m_f32_cnn_pool_dx(const int32_t* idx, const float* g, int64_t ldg, int64_t B, int64_t F, int64_t D, int nfilt, const float* const* wt,
+                         const int32_t* fs, const int32_t* ncol, float* dx, int64_t lddx, yt8m_stream_t stream);
 int yt8m_u8_frames_image_f16(const uint8_t* q, const int32_t* num_frames, int64_t B, int64_t F, int64_t D, float eps, void* image,
                              float* x_tm, float* r_out, yt8m_stream_t stream);
 int yt8m_u8_frames_image_t_f16(const uint8_t* q, const int32_t* num_frames, int64_t B, int64_t F, int64_t D, void* image_t,

@@ -297,6 +297,9 @@ SIGNATURES = {
     "yt8m_timepool_shiftmax_f32": (c_int, [P, c_int64, c_int64, c_int64, c_int, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), P, P,
                                            c_int64, P]),
     "yt8m_u8_cnn_pool_dw": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, P, c_float, P]),
+    "yt8m_f32_cnn_pool_dw": (c_int, [P, c_int64, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, P, c_int64, c_float, P]),
+    "yt8m_f32_cnn_pool_dx": (c_int, [P, P, c_int64, c_int64, c_int64, c_int64, c_int, PP, ctypes.POINTER(ctypes.c_int32),
+                                     ctypes.POINTER(ctypes.c_int32), P, c_int64, P]),
     "yt8m_u8_frames_image_f16": (c_int, [P, P, c_int64, c_int64, c_int64, c_float, P, P, P, P]),
     "yt8m_u8_frames_image_t_f16": (c_int, [P, P, c_int64, c_int64, c_int64, P, P]),
     "yt8m_gemm_h2_nt_grouped": (c_int, [c_int, ctypes.POINTER(GemmProblem), ctypes.POINTER(c_float), PP, PP, P, c_int64, P]),

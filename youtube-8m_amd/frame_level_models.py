@@ -106,7 +106,7 @@ def _lstm_cells(d_in, lstm_size, number_of_layers, multi=True):
     return wb
 
 
-def _lstm_stack(model_input, num_frames, lstm_size, number_of_layers, scope="RNN", input_keep_prob=None):
+def _lstm_stack(model_input, num_frames, lstm_size, number_of_layers, scope="RNN", input_keep_prob=None, **kwargs):
     """MultiRNNCell([BasicLSTMCell(H, forget_bias=1.0)] * L) under tf.nn.dynamic_rnn inside variable_scope("RNN")
     (W/all_frame_models/lstm_model.py:34-47).  TF-1.0 variable names:
     RNN/multi_rnn_cell/cell_<l>/basic_lstm_cell/{weights,biases}.  Returns time-major outputs of the top layer
@@ -117,7 +117,7 @@ def _lstm_stack(model_input, num_frames, lstm_size, number_of_layers, scope="RNN
     with g.variable_scope(scope):
         wb = _lstm_cells(model_input.shape[2], lstm_size, number_of_layers)
     # all layers in one op: layer l+1 works on time chunk c while layer l is already in chunk c+1 (seq_ops._LstmStack)
-    return _native_stack(x_tm, num_frames, wb, input_keep_prob=input_keep_prob)
+    return _native_stack(x_tm, num_frames, wb, input_keep_prob=input_keep_prob, **kwargs)
 
 
 class FrameLevelLogisticModel(models.BaseModel):
@@ -372,6 +372,24 @@ class LstmAttentionMaxPoolingModel(models.BaseModel):
                                             "gates-" + sub_scope, "experts-" + sub_scope)
 
 
+def _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, number_of_layers, own_slots=False):
+    """One LSTM stack per input feature under scope RNN<i> (W/all_frame_models/lstm_parallel_finaloutput_model.py:34-64,
+    lstm_cnn_deep_combine_chain_model.py:139-174): the input is split by feature_sizes and each part re-normalised; a part that arrives
+    as bytes goes to _stack_input as bytes (see LstmParallelFinaloutputModel).  own_slots: stack i takes slot=i -- for a caller that keeps
+    the stacks' outputs alive together.  Returns [(top outputs time-major [F,B,H_i], finals)] per part."""
+    assert len(lstm_sizes) == len(feature_sizes), \
+        "length of lstm_sizes (={}) != length of feature_sizes (={})".format(len(lstm_sizes), len(feature_sizes))
+    assert sum(feature_sizes) == model_input.shape[2], "feature_sizes do not add up to the input width"
+    res, off = [], 0
+    for i, (fs, hs) in enumerate(zip(feature_sizes, lstm_sizes)):
+        sub_input = model_input[:, :, off:off + fs].contiguous()
+        if sub_input.dtype != torch.uint8:                        # (bytes: _stack_input reads them or dequantises + normalises the slice)
+            sub_input = ops.l2_normalize(sub_input)
+        off += fs
+        res.append(_lstm_stack(sub_input, num_frames, hs, number_of_layers, scope="RNN%d" % i, **(dict(slot=i) if own_slots else {})))
+    return res
+
+
 class LstmParallelFinaloutputModel(models.BaseModel):
     """W/all_frame_models/lstm_parallel_finaloutput_model.py:13-73: one LSTM stack per input feature (rgb / audio: the
     input is split by --feature_sizes, each part re-normalised), head input = concat of every layer's final h.
@@ -384,17 +402,7 @@ class LstmParallelFinaloutputModel(models.BaseModel):
         number_of_layers = FLAGS.lstm_layers
         lstm_sizes = [int(v) for v in str(FLAGS.lstm_cells).split(",")]
         feature_sizes = [int(v) for v in str(FLAGS.feature_sizes).split(",")]
-        assert len(lstm_sizes) == len(feature_sizes), \
-            "length of lstm_sizes (={}) != length of feature_sizes (={})".format(len(lstm_sizes), len(feature_sizes))
-        assert sum(feature_sizes) == model_input.shape[2], "feature_sizes do not add up to the input width"
-        states, off = [], 0
-        for i, (fs, hs) in enumerate(zip(feature_sizes, lstm_sizes)):
-            sub_input = model_input[:, :, off:off + fs].contiguous()
-            if sub_input.dtype != torch.uint8:                        # (bytes: _stack_input reads them or dequantises + normalises the slice)
-                sub_input = ops.l2_normalize(sub_input)
-            off += fs
-            _, finals = _lstm_stack(sub_input, num_frames, hs, number_of_layers, scope="RNN%d" % i)
-            states.extend(h for _, h in finals)
+        states = [h for _, finals in _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, number_of_layers) for _, h in finals]
         final_state = torch.cat(states, dim=1)
         return _head()().create_model(model_input=final_state, original_input=model_input, vocab_size=vocab_size,
                                       **unused_params)
@@ -494,6 +502,78 @@ class CnnDeepCombineChainModel(models.BaseModel):
         num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
         return video_level_models.moe_block(model_input, vocab_size, num_mixtures, l2_penalty,
                                             "gates-" + sub_scope, "experts-" + sub_scope, frozen_cols=frozen_cols)
+
+
+def _pooled_cnn_chain(lstm_output_tm, cnns):
+    """[reduce_max over ALL max_frames rows of cnn_c(lstm_output) [B, sum N]] for every CNN c of the chain, lstm_output_tm [F,B,D]
+    time-major (padding rows zeros, as dynamic_rnn leaves them).  The ONE place the chain plugins' pooled CNNs go through: one op for the
+    whole chain whose backward gathers (seq_ops.cnn_tm_maxpool).  Composed from the other plugins' ops it would be
+    [seq_ops.cnn_tm(x, B, cnn).view(F, B, -1).amax(0) for cnn in cnns] -- what tests and tools/lstmcnn_step.py put here to compare."""
+    F, B, D = lstm_output_tm.shape
+    return seq_ops.cnn_tm_maxpool(lstm_output_tm.reshape(F * B, D), B, cnns)
+
+
+class LstmCnnDeepCombineChainModel(models.BaseModel):
+    """W/all_frame_models/lstm_cnn_deep_combine_chain_model.py:10-174: one LSTM stack per input feature (RNN<i>, as
+    LstmParallelFinaloutputModel), their OUTPUTS concatenated [B,F,sum H_i] (zeros at frames >= num_frames); deep_chain_layers + 1 einsum CNNs
+    (filter lengths 1, 2, 3; c, 2c, c filters for cnn0 and c, c, 2c for the others, c = --deep_chain_relu_cells) over that, each max-pooled
+    over all max_frames rows and l2-normalised; a chain of MoE sub-predictions: stage 0 reads cnn0 alone, stage l + 1 reads
+    [cnn_{l+1} | mean-relu | relu-0 .. relu-l] (no mean_input columns, unlike CnnDeepCombineChainModel).  None of the CNNs depends on a
+    prediction: they run as one op (_pooled_cnn_chain) on the stacks' time-major outputs, no transpose to batch-major.
+    Variables: RNN<i>/multi_rnn_cell/cell_<l>/basic_lstm_cell/{weights,biases}, cnn<k>cnn-filter-len{1,2,3}, mean-relu, relu-<l>,
+    gates-/experts-prediction-<l>, gates-/experts--main (the reference's constant mask_emb lookup table is num_frames arithmetic here).
+    accepts_quantized_input: the stacks read their slices of the reader's bytes, the mean frame comes from the bytes too."""
+    accepts_quantized_input = True
+
+    def _first_relu_layers(self, l2_penalty, **unused_params):
+        """What stands in relu_layers before mean-relu, and whether stage 0 already reads relu_layers."""
+        return [], False
+
+    def create_model(self, model_input, vocab_size, num_frames, num_mixtures=None, l2_penalty=1e-8, sub_scope="",
+                     original_input=None, **unused_params):
+        num_layers = FLAGS.deep_chain_layers
+        relu_cells = FLAGS.deep_chain_relu_cells
+        lstm_sizes = [int(v) for v in str(FLAGS.lstm_cells).split(",")]
+        feature_sizes = [int(v) for v in str(FLAGS.feature_sizes).split(",")]
+        relu_layers, early = self._first_relu_layers(l2_penalty, **unused_params)
+        model_input, _ = _bytes_or_floats(model_input, num_frames, lambda q: seq_ops.u8_attention_supported(q, 1))
+        mean_input = _mean_frame(model_input, num_frames)
+        stacks = _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, FLAGS.lstm_layers, own_slots=True)
+        lstm_output = torch.cat([out_tm for out_tm, _ in stacks], dim=2)                   # [F,B,sum H_i] time-major
+        mean_relu = video_level_models.fully_connected(mean_input, relu_cells, sub_scope + "mean-relu", activation="relu",
+                                                       l2_penalty=l2_penalty)
+        relu_layers.append(ops.l2_normalize(mean_relu))
+        D = lstm_output.shape[2]
+        cnns = [_cnn_filters(D, sub_scope + "cnn%d" % k, [relu_cells, 2 * relu_cells, relu_cells] if k == 0 else
+                             [relu_cells, relu_cells, 2 * relu_cells], [1, 2, 3], l2_penalty) for k in range(num_layers + 1)]
+        pooled = [ops.l2_normalize(p) for p in _pooled_cnn_chain(lstm_output, cnns)]
+        next_input = torch.cat([pooled[0]] + relu_layers, dim=1) if early else pooled[0]
+        support_predictions = []
+        for layer in range(num_layers):
+            sub_prediction = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "prediction-%d" % layer)
+            support_predictions.append(sub_prediction)
+            sub_relu = video_level_models.fully_connected(sub_prediction, relu_cells, sub_scope + "relu-%d" % layer,
+                                                          activation="relu", l2_penalty=l2_penalty)
+            relu_layers.append(ops.l2_normalize(sub_relu))
+            next_input = torch.cat([pooled[layer + 1]] + relu_layers, dim=1)
+        main_predictions = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "-main")
+        return {"predictions": main_predictions, "support_predictions": torch.cat(support_predictions, dim=1)}
+
+    def sub_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", **unused_params):
+        num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
+        return video_level_models.moe_block(model_input, vocab_size, num_mixtures, l2_penalty, "gates-" + sub_scope, "experts-" + sub_scope)
+
+
+class DistillchainLstmCnnDeepCombineChainModel(LstmCnnDeepCombineChainModel):
+    """W/all_frame_models/distillchain_lstm_cnn_deep_combine_chain_model.py:10-105: LstmCnnDeepCombineChainModel whose relu_layers start
+    with "distillrelu" (relu FC, --distillchain_relu_cells wide, over another model's predictions, l2-normalised) in front of mean-relu,
+    and whose stage 0 already reads [cnn0 | relu_layers]."""
+
+    def _first_relu_layers(self, l2_penalty, distillation_predictions=None, **unused_params):
+        assert distillation_predictions is not None, "distillation feature must be used"
+        distill_relu = video_level_models.fully_connected(distillation_predictions.to(torch.float32), FLAGS.distillchain_relu_cells,
+                                                          "distillrelu", activation="relu", l2_penalty=l2_penalty)
+        return [ops.l2_normalize(distill_relu)], True
 
 
 def _bn_vars(scope, n):

@@ -1906,6 +1906,31 @@ def _cnn_role(M, N, K):
     return "h2" if (ops.LINEAR_FWD_H2 and ops._linear_h2_size(M, N, K) and N % 4 == 0 and K >= 512) else None
 
 
+def _cnn_tm_dense(x, B, filters):
+    """y [M rows (t B + b), sum N_k] of _CnnTM from x [M, D] fp32: one grouped launch per shift (the products of one shift write disjoint
+    column windows), accumulated in place."""
+    M, D = x.shape
+    Ntot = sum(W.data.shape[1] for W in filters)
+    y = torch.empty((M, Ntot), dtype=torch.float32, device=x.device)
+    fsmax = max(W.data.shape[0] // D for W in filters)
+    for i in range(fsmax):                                         # products of one shift write disjoint column windows: one group
+        rows = M - i * B
+        items, role, c0 = [], "h2", 0
+        for W in filters:
+            fs, N = W.data.shape[0] // D, W.data.shape[1]
+            assert W.data.shape[0] == fs * D, "cnn filter must be [fs * D, N]"
+            if i < fs:
+                if rows > 0:
+                    items.append(dict(A=x[:rows], B=W.data[i * D:(i + 1) * D], out=y[i * B:, c0:c0 + N], beta=1.0 if i else 0.0))
+                    role = role if _cnn_role(rows, N, D) else None
+                elif i == 0:
+                    y[:, c0:c0 + N].zero_()
+            c0 += N
+        if items:
+            ops.gemm_grouped(items, role=role)
+    return y
+
+
 class _CnnTM(torch.autograd.Function):
     """The einsum CNN of W/all_frame_models/multiscale_cnn_lstm_model.py:12-38 on float frames in time-major order, x [F B rows (t B + b), D]:
     a shift by i frames is a row offset of i B, so filter k's output is
@@ -1917,25 +1942,7 @@ class _CnnTM(torch.autograd.Function):
     def forward(ctx, x, token, B, *filters):
         x = _f32c(x)
         _dev(x)
-        M, D = x.shape
-        Ntot = sum(W.data.shape[1] for W in filters)
-        y = torch.empty((M, Ntot), dtype=torch.float32, device=x.device)
-        fsmax = max(W.data.shape[0] // D for W in filters)
-        for i in range(fsmax):                                     # products of one shift write disjoint column windows: one group
-            rows = M - i * B
-            items, role, c0 = [], "h2", 0
-            for W in filters:
-                fs, N = W.data.shape[0] // D, W.data.shape[1]
-                assert W.data.shape[0] == fs * D, "cnn filter must be [fs * D, N]"
-                if i < fs:
-                    if rows > 0:
-                        items.append(dict(A=x[:rows], B=W.data[i * D:(i + 1) * D], out=y[i * B:, c0:c0 + N], beta=1.0 if i else 0.0))
-                        role = role if _cnn_role(rows, N, D) else None
-                    elif i == 0:
-                        y[:, c0:c0 + N].zero_()
-                c0 += N
-            if items:
-                ops.gemm_grouped(items, role=role)
+        y = _cnn_tm_dense(x, B, filters)
         ctx.save_for_backward(x)
         ctx.filters, ctx.B = filters, B
         return y
@@ -1980,6 +1987,95 @@ class _CnnTM(torch.autograd.Function):
 def cnn_tm(x_tm2d, B, filters):
     """x_tm2d [F B, D] float time-major (B videos per frame); filters as u8_cnn_tm -> cnn_output [F B, sum N_k] time-major."""
     return _CnnTM.apply(x_tm2d, _token(filters[0]._graph), int(B), *filters)
+
+
+def cnn_tm_maxpool_supported(D, cnns):
+    """The pooled chain (csrc/cnn_pool.hip, cnn_pool_f32.hip): 16-byte column windows per filter and per CNN, rows of D floats the
+    gather kernels cover, at most 32 filters in all."""
+    filters = [W for cnn in cnns for W in cnn]
+    return bool(D % 4 == 0 and 4 <= D <= 2048 and len(filters) <= 32 and all(W.data.shape[1] % 4 == 0 and W.data.shape[1] >= 4 and
+                                                                              W.data.shape[0] // D <= 16 for W in filters))
+
+
+# The CNNs of a chain read the same x.  False: one set of products and one pooling pass per CNN (y [F B, sum N_k of the CNN], 79 MB at
+# the script's shape, is pooled while the last-level cache still holds it); True: one set for the whole chain (y 314 MB).  Measured by
+# tools/lstmcnn_step.py, see DESIGN_LOG.md 17.
+CNN_POOL_WHOLE_CHAIN = False
+
+
+class _PooledCnnChainTM(torch.autograd.Function):
+    """tf.reduce_max(cnn(x), axis=1) of W/all_frame_models/lstm_cnn_deep_combine_chain_model.py:13-41,66-68,86-88 for EVERY CNN of the chain
+    at once, x [F B rows (t B + b), D] fp32 time-major with a gradient (the LSTM outputs): the products of _CnnTM, the pooling over all F
+    rows in time-major order with the argmax kept (yt8m_timepool_max_f32), and a backward that uses what the pooling did to the gradient
+    -- non-zero at ONE frame per (video, column): B gathered rows of x per (column, shift) for a filter (yt8m_f32_cnn_pool_dw) and, for x,
+    one gathered sum per row over the whole chain (yt8m_f32_cnn_pool_dx), instead of the dense [D, F B] x [F B, N] and
+    [F B, N] x [N, D] products of a gradient that is all zeros but B sum N entries."""
+
+    @staticmethod
+    def forward(ctx, x, token, B, sizes, *filters):
+        x = _f32c(x)
+        _dev(x)
+        M, D = x.shape
+        F = M // B
+        assert F * B == M and F >= 1
+        lib = _lib.lib()
+        Ntot = sum(W.data.shape[1] for W in filters)
+        out = torch.empty((B, Ntot), dtype=torch.float32, device=x.device)
+        idx = torch.empty((B, Ntot), dtype=torch.int32, device=x.device)
+        k0 = c0 = 0
+        for n in ([len(filters)] if CNN_POOL_WHOLE_CHAIN else sizes):
+            y = _cnn_tm_dense(x, B, filters[k0:k0 + n])
+            N = y.shape[1]
+            _lib.check(lib.yt8m_timepool_max_f32(_p(y), F, B, N, N, ctypes.c_void_p(out.data_ptr() + c0 * 4),
+                                                 ctypes.c_void_p(idx.data_ptr() + c0 * 4), Ntot, _stream()))
+            k0 += n
+            c0 += N
+        ctx.save_for_backward(x, idx)
+        ctx.filters, ctx.B = filters, B
+        ctx.mark_non_differentiable(idx)
+        return out, idx
+
+    @staticmethod
+    def backward(ctx, g, _):
+        x, idx = ctx.saved_tensors
+        filters, B = ctx.filters, ctx.B
+        M, D = x.shape
+        F = M // B
+        g = _f32c(g)
+        Ntot = g.shape[1]
+        lib = _lib.lib()
+        c0 = 0
+        for W in filters:
+            fs, N = W.data.shape[0] // D, W.data.shape[1]
+            if W.trainable and W.grad is not None:
+                wbeta = float(W.grad_beta())
+                _lib.check(lib.yt8m_f32_cnn_pool_dw(_p(x), D, ctypes.c_void_p(idx.data_ptr() + c0 * 4), ctypes.c_void_p(g.data_ptr() + c0 * 4),
+                                                    Ntot, B, F, D, N, fs, _p(W.grad), N, wbeta, _stream()))
+            c0 += N
+        dx = None
+        if ctx.needs_input_grad[0]:
+            n = len(filters)
+            wts = [W.data.t().contiguous() for W in filters]          # [N_k, fs_k D]: a term's walk over d is contiguous (layout glue)
+            wt = (ctypes.c_void_p * n)(*[t.data_ptr() for t in wts])
+            fs = (ctypes.c_int32 * n)(*[W.data.shape[0] // D for W in filters])
+            nc = (ctypes.c_int32 * n)(*[W.data.shape[1] for W in filters])
+            dx = torch.empty_like(x)
+            _lib.check(lib.yt8m_f32_cnn_pool_dx(_p(idx), _p(g), Ntot, B, F, D, n, wt, fs, nc, _p(dx), D, _stream()))
+        for W in filters:                                              # (after dx has read the filters: a finished gradient may be consumed)
+            if W.trainable and W.grad is not None:
+                W.grad_done()
+        return (dx, None, None, None) + (None,) * len(filters)
+
+
+def cnn_tm_maxpool(x_tm2d, B, cnns, want_idx=False):
+    """x_tm2d [F B, D] float time-major (B videos per frame, padding rows zeros: no num_frames here); cnns: one list of cnn-filter
+    Variables [fs_k D, N_k] per CNN of a chain, all reading x -> [reduce_max over the F frames of that CNN's output [B, sum N_k]] per CNN
+    (and, want_idx, the frames [B, sum over the chain] int32 the maxima were taken from)."""
+    filters = [W for cnn in cnns for W in cnn]
+    assert cnn_tm_maxpool_supported(x_tm2d.shape[1], cnns), "cnn_tm_maxpool: filter columns in multiples of 4, D % 4 == 0, D <= 2048"
+    out, idx = _PooledCnnChainTM.apply(x_tm2d, _token(filters[0]._graph), int(B), tuple(len(c) for c in cnns), *filters)
+    pooled = list(torch.split(out, [sum(W.data.shape[1] for W in cnn) for cnn in cnns], dim=1))
+    return (pooled, idx) if want_idx else pooled
 
 
 _MS_WS = {}
