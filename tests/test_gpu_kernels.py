@@ -1,6 +1,10 @@
 """-m gpu: parity of every C-ABI kernel (called through the ctypes boundary) against the oracle on seeded
 inputs, including the edge cases the domain has: ragged / empty num_frames, non-multiple-of-tile shapes,
-unaligned leading dimensions, saturated probabilities, ties."""
+unaligned leading dimensions, saturated probabilities, ties.
+
+These are the quick small-shape checks.  The dispatch branches of the streaming kernels (shape thresholds, pointer alignment, grid caps,
+workspace fall-backs, the models' own shapes) are covered arm by arm in tests/test_gpu_streaming_branches.py, whose BRANCH_TABLE lists
+them."""
 import numpy as np
 import pytest
 import torch

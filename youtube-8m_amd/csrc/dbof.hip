@@ -127,6 +127,48 @@ __global__ __launch_bounds__(256) void frame_pool_bwd_kernel(const float* __rest
 }
 
 // ---- batch norm -----------------------------------------------------------------------------------------------------------
+// One row lane's share of a column sum: rows rl, rl + 4, ... of f.  Sixty-four of them at a time go through eight independent partial
+// sums (eight loads in flight) that are combined as a tree and added to the running total; the remainder is added serially.  A fixed
+// order (bitwise reproducible) whose rounding grows with the N / 256 blocks, not with the N / 4 terms a single accumulator chains: at
+// N = 30 720 the single chain left the variance 8 x further from fp64 than torch's fp32 reduction (tests/test_gpu_streaming_branches.py).
+template <typename F>
+__device__ __forceinline__ float row_lane_sum(int rl, int N, F f) {
+  float total = 0.f;
+  int r = rl;
+  for (; r + 4 * 63 < N; r += 4 * 64) {
+    float p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) p[u] += f(r + 4 * (8 * j + u));
+    }
+    total += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+  }
+  float tail = 0.f;
+  for (; r < N; r += 4) tail += f(r);
+  return total + tail;
+}
+
+// the same order for two sums fed by one pass over the rows (f returns the pair of terms of row r)
+template <typename F>
+__device__ __forceinline__ float2 row_lane_sum2(int rl, int N, F f) {
+  float ta = 0.f, tb = 0.f;
+  int r = rl;
+  for (; r + 4 * 63 < N; r += 4 * 64) {
+    float p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, q[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) { const float2 t = f(r + 4 * (8 * j + u)); p[u] += t.x; q[u] += t.y; }
+    }
+    ta += ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
+    tb += ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
+  }
+  float la = 0.f, lb = 0.f;
+  for (; r < N; r += 4) { const float2 t = f(r); la += t.x; lb += t.y; }
+  return float2{ta + la, tb + lb};
+}
+
 // column statistics over N rows: workgroup = 64 columns x 4 row lanes; two passes (mean, then centred second moment)
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, int N, int C, float eps, float decay,
                                                        float* __restrict__ mean, float* __restrict__ rstd,
@@ -136,13 +178,13 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
   const int c = blockIdx.x * 64 + cl;
   const bool ok = c < C;
   float acc = 0.f;
-  if (ok) for (int r = rl; r < N; r += 4) acc += x[(long long)r * C + c];
+  if (ok) acc = row_lane_sum(rl, N, [&](int r) { return x[(long long)r * C + c]; });
   red[rl][cl] = acc;
   __syncthreads();
   const float mu = ((red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl])) / (float)N;
   __syncthreads();
   acc = 0.f;
-  if (ok) for (int r = rl; r < N; r += 4) { const float d = x[(long long)r * C + c] - mu; acc += d * d; }
+  if (ok) acc = row_lane_sum(rl, N, [&](int r) { const float d = x[(long long)r * C + c] - mu; return d * d; });
   red[rl][cl] = acc;
   __syncthreads();
   if (rl == 0 && ok) {
@@ -182,11 +224,12 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
   float a = 0.f, b = 0.f;
   if (ok) {
     const float mu = mean[c], rs = rstd[c];
-    for (int r = rl; r < N; r += 4) {
+    const float2 ab = row_lane_sum2(rl, N, [&](int r) {
       const float g = dy[(long long)r * C + c];
-      a += g;
-      b += g * ((x[(long long)r * C + c] - mu) * rs);
-    }
+      return float2{g, g * ((x[(long long)r * C + c] - mu) * rs)};
+    });
+    a = ab.x;
+    b = ab.y;
   }
   red[0][rl][cl] = a;
   red[1][rl][cl] = b;
