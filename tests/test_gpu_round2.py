@@ -230,6 +230,118 @@ def test_persistent_lstm_vs_fp64_oracle_full_width(dev, lstm_partition):
     assert float((grads[1].double() - gW).abs().max()) <= 1e-4 * float(gW.abs().max())
 
 
+# ---- every form of the Python orchestration (seq_ops._StackLayer) against fp64, one case per reachable combination --------------
+_PS = dict(PERSIST=False, PERSIST_BWD=False)      # per-step recurrence kernels in both passes
+_ORCH_CASES = {
+    # id: (input, B, F, D, H, seq_ops switches, bf16, dropout, (layer-0 proj, hoisted, rec_fwd, rec_bwd))
+    "x3-persist": ("f32", 32, 40, 64, 256, {}, False, False, ("x3", "x3", "persist", "persist")),
+    "x3-steps": ("f32", 32, 40, 64, 256, _PS, False, False, ("x3", "x3", "steps", "steps")),
+    "x3-persist_fwd-steps_bwd": ("f32", 32, 40, 64, 256, dict(PERSIST_BWD=False), False, False, ("x3", "x3", "persist", "steps")),
+    "fp32-persist": ("f32", 32, 40, 64, 256, dict(X3=False), False, False, ("fp32", "fp32", "persist", "persist")),
+    "fp32-steps": ("f32", 32, 40, 64, 64, {}, False, False, ("fp32", "fp32", "steps", "steps")),       # H = 64: no persistent kernel
+    "u8image-persist": ("u8", 32, 40, 64, 256, {}, False, False, ("u8image", "x3", "persist", "persist")),
+    "u8image-steps": ("u8", 32, 40, 64, 128, _PS, False, False, ("u8image", "x3", "steps", "steps")),
+    "u8copies-persist": ("u8", 32, 40, 40, 256, {}, False, False, ("u8copies", "x3", "persist", "persist")),
+    "u8copies-steps": ("u8", 24, 48, 40, 128, _PS, False, False, ("u8copies", "x3", "steps", "steps")),
+    "u8copies-fp32-persist": ("u8", 32, 40, 64, 256, dict(X3=False), False, False, ("u8copies", "fp32", "persist", "persist")),
+    "bf16-bf16_steps": ("f32", 32, 40, 64, 256, {}, True, False, ("bf16", "bf16", "bf16", "bf16")),
+    "bf16-persist": ("f32", 32, 40, 64, 256, dict(REC_BF16=False), True, False, ("bf16", "bf16", "persist", "persist")),
+    "bf16-steps": ("f32", 32, 40, 64, 256, dict(REC_BF16=False, **_PS), True, False, ("bf16", "bf16", "steps", "steps")),
+    "u8-bf16-bf16_steps": ("u8", 32, 40, 64, 256, {}, True, False, ("bf16", "bf16", "bf16", "bf16")),
+    "x3-persist-dropout": ("f32", 32, 40, 64, 256, {}, False, True, ("x3", "x3", "persist", "persist")),
+    "u8-x3-persist-dropout": ("u8", 32, 40, 64, 256, {}, False, True, ("x3", "x3", "persist", "persist")),
+    "bf16-bf16_steps-dropout": ("f32", 32, 40, 64, 256, {}, True, True, ("bf16", "bf16", "bf16", "bf16")),
+}
+_ORCH_REF = {}     # the fp64 references, shared by the cases that differ in switches only
+
+
+def _orch_reference(dev, key, x64, nf, P, drop, emulate):
+    """fp64 autograd of oracle.torch_ref.lstm_stack: (outputs + final states, dx [F,B,D], flat weight / bias gradients, and -- for the
+    bf16 forms -- the forward results of the value emulation `emulate`)."""
+    from oracle import torch_ref
+    if key not in _ORCH_REF:
+        xs = x64.clone().requires_grad_(True)                      # [B,F,D]
+        layers = [(w.clone().requires_grad_(True), b.clone().requires_grad_(True)) for w, b in P]
+        out, c, h = torch_ref.lstm_stack(xs, nf.cpu(), layers, dropout_spec=drop)
+        ref = [out.transpose(0, 1)] + [t for pair in zip(c, h) for t in pair]
+        gen2 = torch.Generator(device=dev).manual_seed(7)
+        sum((r * torch.rand(r.shape, device=dev, generator=gen2).cpu().double()).sum() for r in ref).backward()
+        emu = None
+        if emulate:
+            with torch.no_grad():
+                o, c, h = torch_ref.lstm_stack(x64, nf.cpu(), P, dropout_spec=drop, bf16_operands=emulate)
+            emu = [o.transpose(0, 1)] + [t for pair in zip(c, h) for t in pair]
+        _ORCH_REF[key] = ([r.detach() for r in ref], xs.grad.transpose(0, 1), torch.cat([t.grad.reshape(-1) for pair in layers for t in pair]), emu)
+    return _ORCH_REF[key]
+
+
+@pytest.mark.parametrize("case", sorted(_ORCH_CASES))
+def test_orchestration_forms_vs_fp64_oracle(dev, case, monkeypatch, honour_lstm_chunks):
+    """The Python orchestration (NATIVE_STACK off) in every reachable combination of projection form x recurrence form, dropout and the
+    byte input as modifiers: two layers, chunks = 2 (t0 > 0, the backward `phase` carry over an even chunk length), ragged num_frames
+    incl. 0 and F; outputs, final states, dx and every weight / bias gradient against fp64 autograd of torch_ref.lstm_stack.  The
+    forms each layer chose are asserted, so a case cannot silently land on another path.  Shapes: the smallest that still reach the
+    form -- F B >= X3_MIN_ROWS and H >= 128 for x3; D % 16 == 0 and chunk starts on 32-row groups for the byte image, D = 40 (or X3
+    off) for the bf16 copies; T B = 640 >= ops.BF16_MIN_ROWS rows per chunk, B even and H % 256 == 0 (yt8m_lstm_packed16_elems > 0) for
+    bf16; H = 256, B = 32 for the persistent kernels, H = 64 or PERSIST off for the per-step ones.
+    Tolerances: the fp32-grade forms (fp32, x3, byte projections: exact products, fp32 accumulation) take those of
+    test_persistent_lstm_vs_fp64_oracle_full_width above (2e-5 absolute on results, 1e-4 of the largest gradient); the bf16 forms those of
+    test_gpu_models.py::test_lstm_model_bf16_projections (2e-3 against the value emulation on bf16-rounded operands, 3e-2 against fp64,
+    gradients within 6e-2 of their scale)."""
+    import yt8m_amd.seq_ops as seq_ops
+    from yt8m_amd.variables import xavier_uniform, zeros
+    from oracle import np_ref
+    kind, B, F, D, H, switches, bf16, drop, want = _ORCH_CASES[case]
+    monkeypatch.setattr(seq_ops, "NATIVE_STACK", False)
+    monkeypatch.setattr(seq_ops, "PERSIST_CHECK", True)
+    for k, v in switches.items():
+        monkeypatch.setattr(seq_ops, k, v)
+    forms, prepare_bwd = [], seq_ops._StackLayer.prepare_bwd
+
+    def spy(st, dh, dc):
+        prepare_bwd(st, dh, dc)
+        forms.append((st.proj, st.hoisted, st.rec_fwd, st.rec_bwd))
+    monkeypatch.setattr(seq_ops._StackLayer, "prepare_bwd", spy)
+    g = reset_default_graph(device=dev, seed=0)
+    g.begin_step()
+    gen = torch.Generator(device=dev).manual_seed(0)
+    nf = torch.randint(0, F + 1, (B,), device=dev, generator=torch.Generator(device=dev).manual_seed(3), dtype=torch.int32)
+    nf[0], nf[1] = F, 0
+    if kind == "u8":
+        x = torch.randint(0, 256, (B, F, D), device=dev, generator=gen, dtype=torch.uint8)
+        x64 = torch.from_numpy(np_ref.dequant_l2norm_folded(x.cpu().numpy(), nf.cpu().numpy()))
+    else:
+        x = (torch.rand((F, B, D), device=dev, generator=gen) - 0.5).requires_grad_(True)
+        x64 = x.detach().cpu().double().transpose(0, 1).contiguous()
+    wb, d_in = [], D
+    for l in range(2):
+        wb.append((g.get_variable("l%d/w" % l, (d_in + H, 4 * H), xavier_uniform), g.get_variable("l%d/b" % l, (4 * H,), zeros)))
+        d_in = H
+    g.finalize()
+    seeds = [11, 12] if drop else None
+    out, finals = seq_ops.lstm_stack(x, nf, wb, chunks=2, bf16=bf16, input_keep_prob=0.8 if drop else None, seeds=seeds)
+    res = [out] + [t for p in finals for t in p]
+    gen2 = torch.Generator(device=dev).manual_seed(7)
+    sum((r * torch.rand(r.shape, device=dev, generator=gen2)).sum() for r in res).backward()
+    torch.cuda.synchronize()
+    seq_ops.check_persist_errors()
+    assert forms == [want, (want[1],) + want[1:]], "the layers chose other forms than this case is about: %r" % (forms,)
+    P = [(w.data.detach().cpu().double(), b.data.detach().cpu().double()) for w, b in wb]
+    emulate = (True if want[2] == "bf16" else "input") if bf16 else False
+    ref, dx_ref, gW, emu = _orch_reference(dev, (kind, B, F, D, H, drop, emulate), x64, nf, P, (0.8, seeds) if drop else None, emulate)
+    res = [r.detach().cpu().double() for r in res]
+    e_res = max(float((u - v).abs().max()) for u, v in zip(res, ref))
+    e_emu = max(float((u - v).abs().max()) for u, v in zip(res, emu)) if bf16 else 0.0
+    floor = 1e-3 if bf16 else 1e-300                                # (the bf16 neighbour's floor on the gradient scale)
+    e_w = float((g.grads.detach().cpu().double() - gW).abs().max()) / max(float(gW.abs().max()), floor)
+    e_x = 0.0 if kind == "u8" else float((x.grad.detach().cpu().double() - dx_ref).abs().max()) / max(float(dx_ref.abs().max()), floor)
+    print("%s: results %.3g, vs emulation %.3g, dW/db %.3g, dx %.3g (relative to the largest gradient)" % (case, e_res, e_emu, e_w, e_x))
+    if bf16:
+        assert e_emu < 2e-3 and e_res < 3e-2 and e_w <= 6e-2 and e_x <= 6e-2
+    else:
+        assert e_res < 2e-5 and e_w <= 1e-4 and e_x <= 1e-4
+
+
 # ---- BASELINE configs[4] in its own dtype: the bf16 composite end to end (VERDICT r1 N2) -------------------------------------
 def test_config5_composite_bf16_engaged(dev, flags, monkeypatch):
     """GatedNetVLADAttentionChainModel with --compute_dtype=bfloat16 at B*A = 512 chain rows: the bf16 MFMA GEMMs, the fused

@@ -1,11 +1,68 @@
 """Frame-axis autograd ops over the C ABI: BasicLSTM layer (whole recurrence in one call), attention weights,
 NetVLAD assignment / aggregation, batched pooling GEMMs.  See include/yt8m_hip.h for the kernel contracts."""
 import ctypes
+import os
+import warnings
+import weakref
 
 import torch
 
 from . import _lib, ops
 from .ops import _p, _stream, _dev, _f32c, _token
+
+# ---- switches (environment defaults), each read at call time as an attribute of this module: tests assign to them ----
+PERSIST = os.environ.get("YT8M_LSTM_PERSIST", "1") != "0"        # persistent recurrence kernels (csrc/lstm_persist.hip)
+PERSIST_BWD = os.environ.get("YT8M_LSTM_PERSIST_BWD", "1") != "0"
+# Partition of the time axis when the recurrence runs on the persistent kernels (0: the caller's `chunks`).  A whole-chip forward
+# launch leaves no CU for the other layer's projection, so cutting the forward pass only adds launches: ONE chunk.  The backward
+# launches take half the chip and run beside the weight-gradient GEMMs: three parts (shorter lone first / last phases and a
+# shorter GEMM tail than two; BASELINE configs[3], B = 128: 24.3 ms/step against 24.8 with 2 + 2, 24.4 with 1 + 4).
+PERSIST_FWD_CHUNKS = int(os.environ.get("YT8M_LSTM_PERSIST_FWD_CHUNKS", "1"))
+PERSIST_BWD_CHUNKS = int(os.environ.get("YT8M_LSTM_PERSIST_BWD_CHUNKS", "3"))
+REC_STREAM_PRIORITY = int(os.environ.get("YT8M_REC_STREAM_PRIORITY", "-1"))
+PERSIST_STEP_IMAGES = os.environ.get("YT8M_PERSIST_STEP_IMAGES", "1") != "0"
+PERSIST_STEP_IMAGES_MAX_BYTES = 8 << 30                 # per layer; larger launches keep the two-image exchange
+PERSIST_CHECK = os.environ.get("YT8M_PERSIST_CHECK", "0") == "1"  # debug: synchronise + check the timeout word after each launch
+# GRUCell forward on the persistent protocol (csrc/gru_persist.inl); the library switch YT8M_GRU_PERSIST=0 turns it off too.
+# Measured at B = 128, H = 1024, F = 300 (profiles/r6_gru_persist.txt): 13.9 us/step in one launch against 17.6 in 600.  A persistent
+# backward ran at 29.0 us/step against 20.3 for the per-step launches (two exchange rounds per step on a K = 3H reduction: every
+# item's fragment fetch is exposed with four tiles per workgroup) and was removed.
+GRU_PERSIST_FWD = os.environ.get("YT8M_GRU_PERSIST_FWD", "1") != "0"
+X3 = os.environ.get("YT8M_GEMM_X3", "1") != "0"      # hoisted fp32 products on the bf16 pipe (three-plane split, csrc/gemm_x3.hip)
+X3_MIN_ROWS = 1024                                      # F * B below which the fp32-MFMA kernel's smaller tiles win
+REC_BF16 = os.environ.get("YT8M_REC_BF16", "1") != "0"       # compute_dtype=bfloat16: bf16 operands for the recurrent product too (csrc/lstm_bf16.hip); False = hoisted
+                      # products only
+NATIVE_STACK = os.environ.get("YT8M_LSTM_STACK_NATIVE", "1") != "0"   # whole stack behind yt8m_lstm_stack_fwd / _bwd (csrc/lstm_stack.hip)
+NATIVE_DROPOUT = os.environ.get("YT8M_NATIVE_DROPOUT", "1") != "0"   # DropoutWrapper inside yt8m_lstm_stack_fwd / _bwd (round 6)
+# --compute_dtype=bfloat16 on the native stack (round 4): hoisted products on one-plane bf16 operand images (b1 kernel), the
+# recurrence itself on the fp32-grade persistent kernels -- i.e. "bf16 operands" applies to the input projections, dx and the
+# weight gradients only (torch_ref.lstm_stack(bf16_operands="input") is its value emulation).  YT8M_LSTM_STACK_BF16=0 keeps the
+# Python orchestration with the per-step bf16 recurrence kernels (csrc/lstm_bf16.hip).
+NATIVE_BF16 = os.environ.get("YT8M_LSTM_STACK_BF16", "1") != "0"
+# Per-layer reports of the native stack's gradients under a reducer (each layer's collective starts when THAT layer's last
+# weight-gradient product is done: yt8m_lstm_stack_layer_done_wait).  Opt-in: on one GPU with a 1-rank RCCL group the extra stream
+# costs 1.5-1.7 ms of the 23.6 ms step (profiles/r3_force_reducer.md; more hardware queues -- GPU_MAX_HW_QUEUES=8 -- do not help),
+# more than the ~0.3 ms of layer-1 all-reduce it can hide on eight.
+DP_LAYER_BUCKETS = os.environ.get("YT8M_DP_LAYER_BUCKETS", "0") != "0"
+# Clip + Adam of the already-final gradients inside the recurrent stack's backward pass:
+# train.TrainGraph.step (single device) leaves its optimiser arguments in graph.early_optimizer before backward(); when the native
+# stack's backward pass starts, every trainable variable that has reported its gradient final (Variable.grad_done: for LstmModel the
+# MoE head, 97 of 114 M parameters) gets its per-tensor clip + Adam update on the library's weight-gradient stream, behind the
+# operand-image preparation and while the top layer's first recurrence runs alone on half the chip
+# (yt8m_lstm_stack_set_early_optimizer: the library enqueues it).  The same kernels on the same numbers as the end-of-step pass -- which then only covers what
+# is left (graph.early_done).  A side stream that started at once took CUs from that recurrence (25.2 -> 26.7 ms/step in round 2);
+# here the recurrence is enqueued first.  YT8M_EARLY_ADAM=0 turns it off.
+EARLY_ADAM = os.environ.get("YT8M_EARLY_ADAM", "1") != "0"
+# Overlapped directions (opt-in; measured in DESIGN_LOG.md "BiLstmModel"): the bw stack is issued from a side stream on the library's
+# second stream set, both directions' forward recurrences capped at half the chip.  The library's residency gate (csrc/lstm_persist.hip,
+# PersistGate) admits a persistent launch beside the running ones only while all of them fit the chip together, so two capped
+# recurrences run side by side and nothing whole-chip ever overlaps another persistent launch.
+BI_OVERLAP = os.environ.get("YT8M_BI_OVERLAP", "0") != "0"
+MULTISCALE_FUSED = os.environ.get("YT8M_MULTISCALE_FUSED", "1") != "0"   # 0: the plugin composes the scale from ops.linear / ops.batch_norm / torch
+_STACK_SCRATCH_MAX = int(os.environ.get("YT8M_STACK_SCRATCH_MAX", "8"))   # resident scratch buffers of the native stack (a few GB each)
+
+_PERSIST_WS_MAX = 16                                    # resident workspaces of the persistent recurrence launches
+U8_BETA = 128.0 * 4.0 / 255.0 + (4.0 / 512.0 - 2.0)     # dequantise(q) = (4/255) (q - 128) + U8_BETA
 
 
 def _nf(num_frames):
@@ -276,8 +333,8 @@ def lnlstm_layer(x_tm, W, gammas, betas, num_frames, forget_bias=1.0, keep_prob=
     return _LnLstmLayer.apply(x_tm, _token(W._graph), W, tuple(gammas), tuple(betas), num_frames, forget_bias, keep_prob, seed)
 
 
-# ---- MultiRNNCell stack, pipelined over time chunks ----------------------------------------------------------------
-_SIDE = {}
+# ---- MultiRNNCell stack, pipelined over time chunks: streams, resident buffers, native descriptor ----------
+_SIDE = {}            # (device, persistent) -> the stack's layer / weight-gradient streams; (device, name) -> a one-off side stream
 
 
 def _side_streams(device, L, persistent=False):
@@ -305,74 +362,54 @@ def _side_streams(device, L, persistent=False):
     return pool["r"][:L], pool["r"][:L], pool["w"]
 
 
+def _side_stream(dev, name, priority=0):                           # the one side stream `name` of a device, made on first use
+    if (dev, name) not in _SIDE:
+        _SIDE[(dev, name)] = torch.cuda.Stream(device=dev, priority=priority)
+    return _SIDE[(dev, name)]
+
+
 def _chunks(F, n):
     n = max(1, min(int(n), F))
     step = (F + n - 1) // n
     return [(t0, min(step, F - t0)) for t0 in range(0, F, step)]
 
 
-import os as _os
-PERSIST = _os.environ.get("YT8M_LSTM_PERSIST", "1") != "0"        # persistent recurrence kernels (csrc/lstm_persist.hip)
-U8_BETA = 128.0 * 4.0 / 255.0 + (4.0 / 512.0 - 2.0)     # dequantise(q) = (4/255) (q - 128) + U8_BETA
-
-
 def _bwd_parts(F, fwd_parts, persistent=False):
     if persistent and PERSIST_BWD_CHUNKS > 0:
         return _chunks(F, PERSIST_BWD_CHUNKS)
     return fwd_parts
-# Partition of the time axis when the recurrence runs on the persistent kernels (0: the caller's `chunks`).  A whole-chip forward
-# launch leaves no CU for the other layer's projection, so cutting the forward pass only adds launches: ONE chunk.  The backward
-# launches take half the chip and run beside the weight-gradient GEMMs: three parts (shorter lone first / last phases and a
-# shorter GEMM tail than two; BASELINE configs[3], B = 128: 24.3 ms/step against 24.8 with 2 + 2, 24.4 with 1 + 4).
-PERSIST_FWD_CHUNKS = int(_os.environ.get("YT8M_LSTM_PERSIST_FWD_CHUNKS", "1"))
-PERSIST_BWD_CHUNKS = int(_os.environ.get("YT8M_LSTM_PERSIST_BWD_CHUNKS", "3"))
-REC_STREAM_PRIORITY = int(_os.environ.get("YT8M_REC_STREAM_PRIORITY", "-1"))
-PERSIST_STEP_IMAGES = _os.environ.get("YT8M_PERSIST_STEP_IMAGES", "1") != "0"
-PERSIST_STEP_IMAGES_MAX_BYTES = 8 << 30                 # per layer; larger launches keep the two-image exchange
-_PERSIST_WS = {}      # (device, caller's stream, layer, bytes) -> scratch workspace of that layer's persistent launches
-_PERSIST_WS_MAX = 16
 
 
-def _persist_ws(dev, main, l, nbytes):
-    """Scratch of the persistent recurrence launches of layer `l` (control words + exchange images; nothing in it outlives a
-    launch): ONE resident buffer per (device, calling stream, layer, size), reused by every step.  Every launch that touches it is
-    ordered through the calling stream -- a stack's forward and backward both start from an event of that stream and join it
-    before they return -- so two users of one key never overlap on the GPU.  Allocating it per step pinned ~0.6 GB per layer and
-    step (32 steps' worth before the old table was cleared) and put two hipMalloc calls into every backward pass; on some boxes
-    each of those waits ~17 ms on a DMA fence inside the driver, which made the step host-bound (25 -> 38-42 ms).
-    The buffer's first line is the sticky error word of include/yt8m_hip.h: zeroed here, once; a buffer is only dropped from the
-    table after its status has been read (a time-out is never lost with the eviction)."""
-    key = (dev.index, main.cuda_stream, l, int(nbytes))
-    ent = _PERSIST_WS.get(key)
-    if ent is not None:
-        _PERSIST_WS[key] = _PERSIST_WS.pop(key)                    # LRU order (dicts keep insertion order)
-    else:
-        if len(_PERSIST_WS) >= _PERSIST_WS_MAX:                    # other shapes: drop the least recently used entry
-            _retire(_PERSIST_WS.pop(next(iter(_PERSIST_WS))), _check_ws)
-            global _PERSIST_EVICTIONS
-            _PERSIST_EVICTIONS += 1
-            if _PERSIST_EVICTIONS in (64, 1024):                     # a model cycling through > 16 shapes re-zeroes ~0.6 GB per miss
-                import warnings
-                warnings.warn("yt8m_amd: %d persistent-recurrence workspaces evicted; raise seq_ops._PERSIST_WS_MAX" % _PERSIST_EVICTIONS)
-        ws = torch.zeros(int(nbytes), dtype=torch.uint8, device=dev)   # zeroed once: the sticky error word starts clear
-        ent = (ws, main)
-        _PERSIST_WS[key] = ent
-    return ent[0]
-
-
-_PERSIST_EVICTIONS = 0
-_STACK_SCRATCH_MAX = int(_os.environ.get("YT8M_STACK_SCRATCH_MAX", "8"))
-# Evicted workspaces that something may still launch on (an autograd ctx between its forward and its backward keeps the tensor
+# Evicted buffers that something may still launch on (an autograd ctx between its forward and its backward keeps the tensor
 # alive): weak references, checked -- and dropped -- by the next check_persist_errors(), so a time-out in such a backward pass is
 # still reported (ADVICE r3).  A tensor nobody holds any more cannot be launched on and needs no check beyond the one at eviction.
 _RETIRED = []
 
 
 def _retire(ent, checker):
-    import weakref
     checker(*ent)                                                    # what ran so far (synchronises that stream)
     _RETIRED.append((weakref.ref(ent[0]), ent[1:], checker))
-    del ent
+
+
+class _ResidentBuffers(dict):
+    """key -> (buffer, calling stream, ...): zero-initialised resident device buffers, least recently USED first (dicts keep insertion
+    order).  A buffer's first line is the sticky error word of include/yt8m_hip.h: zeroed once, here; an entry is only dropped after
+    `checker(*entry)` has read its status (a time-out is never lost with the eviction)."""
+
+    def __init__(self, checker, warning=None):
+        self.checker, self.warning, self.evictions = checker, warning, 0
+
+    def buffer(self, key, nbytes, dev, rest, capacity):
+        ent = self.pop(key, None)
+        if ent is None:
+            if len(self) >= capacity:                                # other shapes: drop the least recently used entry
+                _retire(self.pop(next(iter(self))), self.checker)
+                self.evictions += 1
+                if self.warning and self.evictions in (64, 1024):    # a model cycling through more shapes re-zeroes a buffer per miss
+                    warnings.warn(self.warning % self.evictions)
+            ent = (torch.zeros(int(nbytes), dtype=torch.uint8, device=dev),) + rest
+        self[key] = ent                                              # (back) at the recently-used end
+        return ent[0]
 
 
 def _check_ws(ws, stream):
@@ -381,71 +418,25 @@ def _check_ws(ws, stream):
         _lib.check(_lib.lib().yt8m_lstm_persist_status(_p(ws), ctypes.c_void_p(stream.cuda_stream)))
 
 
-def check_persist_errors():
-    """Synchronises and raises if ANY persistent-recurrence launch since the previous check gave up waiting for a tile (bounded
-    spins set a sticky error word instead of hanging the GPU; no later launch clears it).  The training loop calls this at its
-    checkpoints; tests run with PERSIST_CHECK per launch."""
-    err = None
-    for ws, stream in list(_PERSIST_WS.values()):
-        try:
-            _check_ws(ws, stream)
-        except _lib.Yt8mHipError as e:                               # read (= clear) every word before raising
-            err = e
-    for ent in list(_STACK_SCRATCH.values()):
-        try:
-            _check_stack(*ent)
-        except _lib.Yt8mHipError as e:
-            err = e
-    retired, _RETIRED[:] = list(_RETIRED), []
-    for ref, rest, checker in retired:
-        ws = ref()
-        if ws is None:
-            continue
-        try:
-            checker(ws, *rest)
-        except _lib.Yt8mHipError as e:
-            err = e
-        _RETIRED.append((ref, rest, checker))                        # still alive: stays on the list
-    if err is not None:
-        raise err
-PERSIST_BWD = _os.environ.get("YT8M_LSTM_PERSIST_BWD", "1") != "0"
-# GRUCell forward on the persistent protocol (csrc/gru_persist.inl); the library switch YT8M_GRU_PERSIST=0 turns it off too.
-# Measured at B = 128, H = 1024, F = 300 (profiles/r6_gru_persist.txt): 13.9 us/step in one launch against 17.6 in 600.  A persistent
-# backward ran at 29.0 us/step against 20.3 for the per-step launches (two exchange rounds per step on a K = 3H reduction: every
-# item's fragment fetch is exposed with four tiles per workgroup) and was removed.
-GRU_PERSIST_FWD = _os.environ.get("YT8M_GRU_PERSIST_FWD", "1") != "0"
-PERSIST_CHECK = _os.environ.get("YT8M_PERSIST_CHECK", "0") == "1"  # debug: synchronise + check the timeout word after each launch
-X3 = _os.environ.get("YT8M_GEMM_X3", "1") != "0"      # hoisted fp32 products on the bf16 pipe (three-plane split, csrc/gemm_x3.hip)
-X3_MIN_ROWS = 1024                                      # F * B below which the fp32-MFMA kernel's smaller tiles win
-REC_BF16 = _os.environ.get("YT8M_REC_BF16", "1") != "0"       # compute_dtype=bfloat16: bf16 operands for the recurrent product too (csrc/lstm_bf16.hip); False = hoisted
-                      # products only
+def _check_stack(scratch, stream, desc):
+    with torch.cuda.device(scratch.device):
+        _lib.check(_lib.lib().yt8m_lstm_stack_status(ctypes.byref(desc), _p(scratch), ctypes.c_void_p(stream.cuda_stream)))
 
 
-NATIVE_STACK = _os.environ.get("YT8M_LSTM_STACK_NATIVE", "1") != "0"   # whole stack behind yt8m_lstm_stack_fwd / _bwd (csrc/lstm_stack.hip)
-NATIVE_DROPOUT = _os.environ.get("YT8M_NATIVE_DROPOUT", "1") != "0"   # DropoutWrapper inside yt8m_lstm_stack_fwd / _bwd (round 6)
-_STACK_SCRATCH = {}   # (device, calling stream, description) -> zero-initialised scratch of the native stack (resident, like _PERSIST_WS)
-NATIVE_CALLS = {"fwd": 0, "bwd": 0}     # how often the native path ran (tests assert that it engaged)
+# (device, caller's stream, layer, bytes) -> scratch workspace of that layer's persistent launches (~0.6 GB each)
+_PERSIST_WS = _ResidentBuffers(_check_ws, "yt8m_amd: %d persistent-recurrence workspaces evicted; raise seq_ops._PERSIST_WS_MAX")
+# (device, calling stream, description) -> zero-initialised scratch of the native stack (a few GB each: keep the table small)
+_STACK_SCRATCH = _ResidentBuffers(_check_stack)
 
 
-# --compute_dtype=bfloat16 on the native stack (round 4): hoisted products on one-plane bf16 operand images (b1 kernel), the
-# recurrence itself on the fp32-grade persistent kernels -- i.e. "bf16 operands" applies to the input projections, dx and the
-# weight gradients only (torch_ref.lstm_stack(bf16_operands="input") is its value emulation).  YT8M_LSTM_STACK_BF16=0 keeps the
-# Python orchestration with the per-step bf16 recurrence kernels (csrc/lstm_bf16.hip).
-NATIVE_BF16 = _os.environ.get("YT8M_LSTM_STACK_BF16", "1") != "0"
-
-
-def _stack_desc(B, F, D, H, L, u8, forget_bias, need_dx, bf16=False, keep_prob=None, seeds=None):
-    # 0 = the library's own partition (csrc/lstm_stack.hip: one forward launch per layer, three unequal backward parts) unless the
-    # environment / a test names a number of parts
-    fwd = PERSIST_FWD_CHUNKS if (PERSIST_FWD_CHUNKS != 1 or "YT8M_LSTM_PERSIST_FWD_CHUNKS" in _os.environ) else 0
-    bwd = PERSIST_BWD_CHUNKS if (PERSIST_BWD_CHUNKS != 3 or "YT8M_LSTM_PERSIST_BWD_CHUNKS" in _os.environ) else 0
-    d = _lib.LstmStackDesc(int(B), int(F), int(D), int(H), int(L), int(bool(u8)) | (2 if bf16 else 0), float(forget_bias), int(fwd),
-                           int(bwd), int(bool(need_dx)))                       # input_u8: bit 0 uint8 frames, bit 1 bf16 operand images
-    if keep_prob is not None and float(keep_prob) < 1.0:                       # DropoutWrapper(input_keep_prob) inside the stack (ABI 4)
-        d.input_keep_prob = float(keep_prob)
-        for l, sd in enumerate(list(seeds)[:8]):
-            d.dropout_seed[l] = int(sd) & 0xFFFFFFFFFFFFFFFF
-    return d
+def _persist_ws(dev, main, l, nbytes):
+    """Scratch of the persistent recurrence launches of layer `l` (control words + exchange images; nothing in it outlives a
+    launch): ONE resident buffer per (device, calling stream, layer, size), reused by every step.  Every launch that touches it is
+    ordered through the calling stream -- a stack's forward and backward both start from an event of that stream and join it
+    before they return -- so two users of one key never overlap on the GPU.  Allocating it per step pinned ~0.6 GB per layer and
+    step (32 steps' worth before the old table was cleared) and put two hipMalloc calls into every backward pass; on some boxes
+    each of those waits ~17 ms on a DMA fence inside the driver, which made the step host-bound (25 -> 38-42 ms)."""
+    return _PERSIST_WS.buffer((dev.index, main.cuda_stream, l, int(nbytes)), nbytes, dev, (main,), _PERSIST_WS_MAX)
 
 
 def _stack_scratch(dev, main, desc, slot=0):
@@ -458,20 +449,31 @@ def _stack_scratch(dev, main, desc, slot=0):
                                                       if f not in ("forget_bias", "input_keep_prob", "reserved0", "dropout_seed"))
     if slot:
         key += (("slot", int(slot)),)
-    ent = _STACK_SCRATCH.get(key)
-    if ent is not None:
-        _STACK_SCRATCH[key] = _STACK_SCRATCH.pop(key)                # least recently USED goes first (dicts keep insertion order)
-    else:
-        if len(_STACK_SCRATCH) >= _STACK_SCRATCH_MAX:                # a few GB each: keep the table small
-            _retire(_STACK_SCRATCH.pop(next(iter(_STACK_SCRATCH))), _check_stack)
-        ent = (torch.zeros(need, dtype=torch.uint8, device=dev), main, desc)      # zeroed ONCE: the sticky time-out words start clear
-        _STACK_SCRATCH[key] = ent
-    return ent[0]
+    return _STACK_SCRATCH.buffer(key, need, dev, (main, desc), _STACK_SCRATCH_MAX)
 
 
-def _check_stack(scratch, stream, desc):
-    with torch.cuda.device(scratch.device):
-        _lib.check(_lib.lib().yt8m_lstm_stack_status(ctypes.byref(desc), _p(scratch), ctypes.c_void_p(stream.cuda_stream)))
+def check_persist_errors():
+    """Synchronises and raises if ANY persistent-recurrence launch since the previous check gave up waiting for a tile (bounded
+    spins set a sticky error word instead of hanging the GPU; no later launch clears it).  The training loop calls this at its
+    checkpoints; tests run with PERSIST_CHECK per launch."""
+    errs = []
+
+    def check(checker, *ent):
+        try:
+            checker(*ent)
+        except _lib.Yt8mHipError as e:                               # read (= clear) every word before raising
+            errs.append(e)
+    for cache in (_PERSIST_WS, _STACK_SCRATCH):
+        for ent in list(cache.values()):
+            check(cache.checker, *ent)
+    retired, _RETIRED[:] = list(_RETIRED), []
+    for ref, rest, checker in retired:
+        ws = ref()
+        if ws is not None:
+            check(checker, ws, *rest)
+            _RETIRED.append((ref, rest, checker))                    # still alive: stays on the list
+    if errs:
+        raise errs[-1]
 
 
 def _tape_view(lib, desc, tape, layer, which, shape):
@@ -484,35 +486,26 @@ def _tape_view(lib, desc, tape, layer, which, shape):
     return tape[off:off + n].view(torch.float32).view(*shape)
 
 
-# Per-layer reports of the native stack's gradients under a reducer (each layer's collective starts when THAT layer's last
-# weight-gradient product is done: yt8m_lstm_stack_layer_done_wait).  Opt-in: on one GPU with a 1-rank RCCL group the extra stream
-# costs 1.5-1.7 ms of the 23.6 ms step (profiles/r3_force_reducer.md; more hardware queues -- GPU_MAX_HW_QUEUES=8 -- do not help),
-# more than the ~0.3 ms of layer-1 all-reduce it can hide on eight.
-DP_LAYER_BUCKETS = _os.environ.get("YT8M_DP_LAYER_BUCKETS", "0") != "0"
+NATIVE_CALLS = {"fwd": 0, "bwd": 0}     # how often the native path ran (tests assert that it engaged)
 DP_LAYER_BUCKETS_USED = [0]
-_DP_SIDE = {}
-
-
-def _dp_side_stream(dev):
-    st = _DP_SIDE.get(dev)
-    if st is None:
-        st = torch.cuda.Stream(device=dev)
-        _DP_SIDE[dev] = st
-    return st
-
-
-# ---- clip + Adam of the already-final gradients inside the recurrent stack's backward pass ---------------------------------------
-# train.TrainGraph.step (single device) leaves its optimiser arguments in graph.early_optimizer before backward(); when the native
-# stack's backward pass starts, every trainable variable that has reported its gradient final (Variable.grad_done: for LstmModel the
-# MoE head, 97 of 114 M parameters) gets its per-tensor clip + Adam update on the library's weight-gradient stream, behind the
-# operand-image preparation and while the top layer's first recurrence runs alone on half the chip
-# (yt8m_lstm_stack_set_early_optimizer: the library enqueues it).  The same kernels on the same numbers as the end-of-step pass -- which then only covers what
-# is left (graph.early_done).  A side stream that started at once took CUs from that recurrence (25.2 -> 26.7 ms/step in round 2);
-# here the recurrence is enqueued first.  YT8M_EARLY_ADAM=0 turns it off.
-EARLY_ADAM = _os.environ.get("YT8M_EARLY_ADAM", "1") != "0"
 EARLY_ADAM_RUNS = [0]      # how often the early pass ran (tests assert that it engaged)
 
 
+def _stack_desc(B, F, D, H, L, u8, forget_bias, need_dx, bf16=False, keep_prob=None, seeds=None):
+    # 0 = the library's own partition (csrc/lstm_stack.hip: one forward launch per layer, three unequal backward parts) unless the
+    # environment / a test names a number of parts
+    fwd = PERSIST_FWD_CHUNKS if (PERSIST_FWD_CHUNKS != 1 or "YT8M_LSTM_PERSIST_FWD_CHUNKS" in os.environ) else 0
+    bwd = PERSIST_BWD_CHUNKS if (PERSIST_BWD_CHUNKS != 3 or "YT8M_LSTM_PERSIST_BWD_CHUNKS" in os.environ) else 0
+    d = _lib.LstmStackDesc(int(B), int(F), int(D), int(H), int(L), int(bool(u8)) | (2 if bf16 else 0), float(forget_bias), int(fwd),
+                           int(bwd), int(bool(need_dx)))                       # input_u8: bit 0 uint8 frames, bit 1 bf16 operand images
+    if keep_prob is not None and float(keep_prob) < 1.0:                       # DropoutWrapper(input_keep_prob) inside the stack (ABI 4)
+        d.input_keep_prob = float(keep_prob)
+        for l, sd in enumerate(list(seeds)[:8]):
+            d.dropout_seed[l] = int(sd) & 0xFFFFFFFFFFFFFFFF
+    return d
+
+
+# ---- clip + Adam of the already-final gradients inside the recurrent stack's backward pass (see EARLY_ADAM) ------------------------------
 class _EarlyOpt(object):
     """The early pass as a descriptor the library consumes (yt8m_lstm_stack_set_early_optimizer, round 5): yt8m_lstm_stack_bwd
     enqueues sqnorm / Adam (/ the image tile pass) of `ranges` itself -- no Python runs inside the native call any more (the ctypes
@@ -603,6 +596,256 @@ class _StreamSet(object):
         return False
 
 
+class _ByteFrames(object):
+    """The reader's bytes [B,F,D] under the orchestrated stack's layer-0 projection (csrc/u8proj.hip): one pass writes (q - 128) as bf16 in
+    time-major order, the row norms `rrow`, and the fp32 frames `x_tm` that only the weight-gradient product still reads.  `image`: one-plane
+    operand image for the x3 kernel when every time chunk starts on a 32-row group of it; else `copies`: three bf16 copies side by side."""
+
+    def __init__(self, lib, q, nf, parts):
+        _dev(q)
+        q = q.contiguous()
+        B, F, D = q.shape
+        self.rrow = torch.empty((F * B,), dtype=torch.float32, device=q.device)
+        self.x_tm = torch.empty((F, B, D), dtype=torch.float32, device=q.device)
+        self.image = self.copies = None
+        if X3 and D % 16 == 0 and all((t0 * B) % 32 == 0 for t0, _ in parts):
+            self.image = torch.empty(((F * B + 31) // 32) * (D // 16) * 1024, dtype=torch.uint8, device=q.device)
+            _lib.check(lib.yt8m_u8_frames_image(_p(q), _p(nf), B, F, D, 1e-12, _p(self.image), _p(self.x_tm), _p(self.rrow), _stream()))
+        else:
+            self.copies = ops._bf16_empty(F * B, 3 * D, q.device)
+            _lib.check(lib.yt8m_u8_frames_to_bf16_tm(_p(q), _p(nf), B, F, D, 1e-12, 3, _p(self.copies), self.copies.stride(0), _p(self.x_tm), _p(self.rrow), _stream()))
+
+
+class _StackLayer(object):
+    """One layer of the orchestrated stack: its buffers and its two forms, each chosen once; every method enqueues on the current stream.
+    `hoisted` (dx, weight gradients): "bf16" copies of both operands on the bf16 MFMA kernel | "x3" three-plane split of both on the bf16
+    pipe (csrc/gemm_x3.hip) | "fp32" MFMA kernel; `proj` (input projection): the same, or "u8image" / "u8copies" of layer 0's _ByteFrames.
+    `rec_fwd`, `rec_bwd`: "bf16" per-step kernels on bf16 operands (csrc/lstm_bf16.hip) | "persist" one launch per chunk, W_h resident in
+    registers (csrc/lstm_persist.hip) | "steps" per-step fp32 kernels."""
+    FWD_ONLY = ("WxT", "WxT3", "W3T", "Wcs", "Wp16", "hs16")        # operand images the backward pass drops when it starts
+    WxT = WxT3 = W3T = Wcs = Wp16 = hs16 = Wxb = Wx3 = None
+
+    def __init__(self, lib, x, W, b, nf, forget_bias, bf16, drop, pws, undropped=None, bytes_=None):
+        # drop: (keep_prob, seed) | None.  Layer 0 only: undropped = the frames under dropout (x: the buffer of their dropped copy), bytes_
+        self.lib, self.x, self.W, self.b, self.nf, self.forget_bias = lib, x, W, b, nf, float(forget_bias)
+        self.undropped, self.bytes, self.drop = undropped, bytes_, drop
+        F, B, Din = x.shape
+        H = W.data.shape[1] // 4
+        assert W.data.shape[0] == Din + H, "cell weights must be [in + H, 4H]"
+        self.F, self.B, self.Din, self.H, dev = F, B, Din, H, x.device
+        self.z = torch.empty((F, B, 4 * H), dtype=torch.float32, device=dev)
+        self.cs = torch.empty((F + 1, B, H), dtype=torch.float32, device=dev)
+        self.hs = torch.empty((F + 1, B, H), dtype=torch.float32, device=dev)
+        self.out = torch.empty((F, B, H), dtype=torch.float32, device=dev)
+        npk = lib.yt8m_lstm_packed_floats(B, H)
+        self.Wp = torch.empty(npk, dtype=torch.float32, device=dev) if npk else None
+        # decided on the whole sequence, not the chunk: every partition of the time axis runs the same arithmetic
+        self.hoisted = "bf16" if bf16 and Din % 2 == 0 else "x3" if X3 and F * B >= X3_MIN_ROWS and H >= 128 else "fp32"
+        self.proj = self.hoisted
+        if bytes_ is not None and drop is None and self.hoisted != "bf16":
+            self.proj = "u8image" if bytes_.image is not None else "u8copies"
+        self.rec16 = self.hoisted == "bf16" and REC_BF16 and lib.yt8m_lstm_packed16_elems(B, H) > 0
+        self.pws = None if self.rec16 else pws
+        self.rec_fwd = self._recurrence(False)
+
+    def _recurrence(self, backward):
+        if self.rec16:
+            return "bf16"
+        if self.pws is not None and (not backward or (PERSIST_BWD and self.lib.yt8m_lstm_persist_bwd_supported(self.B, self.H))):
+            return "persist"
+        return "steps"
+
+    def _rows(self, buf, t0, T):
+        return buf[t0:t0 + T].view(T * self.B, buf.shape[2])
+
+    def prepare_fwd(self):
+        lib, Din, H, W, dev = self.lib, self.Din, self.H, self.W.data, self.x.device
+        self.cs[0].zero_()
+        self.hs[0].zero_()
+        if self.Wp is not None:
+            _lib.check(lib.yt8m_lstm_pack(_p(W[Din:]), 4 * H, H, _p(self.Wp), None, _stream()))
+        if self.proj in ("u8image", "u8copies"):
+            # 3-way bf16 split of (4/255) W_x, transposed ([4H, 3 D], K-contiguous) + the column sums of W_x
+            if self.proj == "u8image":
+                self.W3T = ops.x3_split(W[:Din], plain=False, trans=True, scale=4.0 / 255.0)[1]
+            else:
+                self.W3T = ops._bf16_empty(4 * H, 3 * Din, dev)
+                _lib.check(lib.yt8m_split3_bf16_t(_p(W[:Din]), 4 * H, Din, 4 * H, 4.0 / 255.0, _p(self.W3T), self.W3T.stride(0), _stream()))
+            self.Wcs = torch.empty((4 * H,), dtype=torch.float32, device=dev)
+            ops.colsum(W[:Din], self.Wcs)
+        elif self.proj == "x3":                                     # W_x^T as the K-contiguous operand of the projection
+            self.WxT3 = ops.x3_split(W[:Din], plain=False, trans=True)[1]
+        elif self.proj == "bf16":                                   # W_x^T once per step, K-contiguous for the NT product
+            self.WxT = ops.cast_bf16(W[:Din], transpose=True)
+        if self.rec16:                                              # bf16 operands for the recurrent product too
+            self.hs16 = torch.empty((self.F + 1, self.B, H), dtype=torch.bfloat16, device=dev)
+            self.hs16[0].zero_()
+            self.Wp16 = torch.empty(H * 4 * H, dtype=torch.bfloat16, device=dev)
+            _lib.check(lib.yt8m_lstm_pack_bf16(_p(W[Din:]), 4 * H, H, _p(self.Wp16), None, _stream()))
+
+    def project(self, t0, T):
+        """z[t0:t0+T] = dropout(x[t0:t0+T]) . W_x + b"""
+        lib, B, Din, H, bias = self.lib, self.B, self.Din, self.H, self.b.data
+        xc, zc = self._rows(self.x, t0, T), self._rows(self.z, t0, T)
+        if self.drop is not None:
+            src = xc if self.undropped is None else self._rows(self.undropped, t0, T)
+            _lib.check(lib.yt8m_dropout_f32(_p(src), _p(xc), xc.numel(), self.drop[0], self.drop[1], t0 * B * Din, _stream()))
+        if self.proj == "u8image":
+            q, ws = self.bytes, ops._workspace(self.x.device)
+            _lib.check(lib.yt8m_gemm_x1x3_nt(T * B, 4 * H, Din, _p(q.image[(t0 * B // 32) * (Din // 16) * 1024:]), _p(self.W3T.buf),
+                                             _p(zc), 4 * H, _p(bias), _p(q.rrow[t0 * B:]), _p(self.Wcs), U8_BETA, _p(ws), ws.numel() * 4, _stream()))
+        elif self.proj == "u8copies":
+            q = self.bytes
+            ops.gemm_bf16_nt_grouped([dict(A=q.copies[t0 * B:(t0 + T) * B], B=self.W3T, out=zc)])
+            _lib.check(lib.yt8m_rowscale_bias_f32(_p(zc), T * B, 4 * H, 4 * H, _p(q.rrow[t0 * B:]), _p(self.Wcs), U8_BETA, _p(bias), _stream()))
+        elif self.proj == "bf16":
+            ops.gemm_bf16_nt_grouped([dict(A=ops.cast_bf16(xc), B=self.WxT, out=zc, bias=bias)])
+        elif self.proj == "x3":
+            ops.gemm_x3_grouped([dict(A=ops.x3_split(xc)[0], B=self.WxT3, out=zc, bias=bias)])
+        else:
+            ops.gemm(xc, self.W.data[:Din], out=zc, bias=bias)
+
+    def recur_fwd(self, t0, T):
+        lib, B, Din, H, fb = self.lib, self.B, self.Din, self.H, self.forget_bias
+        z, cs, hs, out, nf, Wh = _p(self.z), _p(self.cs), _p(self.hs), _p(self.out), _p(self.nf), self.W.data[Din:]
+        ws = ops._workspace(self.x.device)
+        if self.rec_fwd == "bf16":
+            _lib.check(lib.yt8m_lstm_steps_fwd_bf16(z, _p(self.Wp16), cs, hs, _p(self.hs16), out, nf, t0, T, B, H, fb, _stream()))
+        elif self.rec_fwd == "persist":
+            _lib.check(lib.yt8m_lstm_persist_fwd(z, _p(Wh), 4 * H, cs, hs, out, nf, t0, T, B, H, fb, _p(self.pws), self.pws.numel(), _stream()))
+            if PERSIST_CHECK:
+                _lib.check(lib.yt8m_lstm_persist_status(_p(self.pws), _stream()))
+        else:
+            _lib.check(lib.yt8m_lstm_steps_fwd(z, _p(Wh), 4 * H, _p(self.Wp), cs, hs, out, nf, t0, T, B, H, fb, _p(ws), ws.numel() * 4, _stream()))
+
+    def release(self, names):
+        for name in names:
+            setattr(self, name, None)
+
+    def alloc_bwd(self, dout_top, top, wants_dx):                   # (dout: the caller's on top, else written from above)
+        F, B, H, dev, self.wants_dx = self.F, self.B, self.H, self.x.device, wants_dx
+        self.dz = torch.empty((F, B, 4 * H), dtype=torch.float32, device=dev)
+        self.work = torch.empty((4, B, H), dtype=torch.float32, device=dev)
+        self.dout = (None if dout_top is None else _f32c(dout_top)) if top else torch.empty((F, B, H), dtype=torch.float32, device=dev)
+        npk = self.lib.yt8m_lstm_packed_floats(B, H)
+        self.Wq = torch.empty(npk, dtype=torch.float32, device=dev) if npk else None
+
+    def prepare_bwd(self, dh, dc):
+        lib, Din, H, W = self.lib, self.Din, self.H, self.W.data
+        for row, d in ((self.work[0], dh), (self.work[1], dc)):
+            if d is None:
+                row.zero_()
+            else:
+                row.copy_(d)
+        self.phase = 0
+        self.rec_bwd = self._recurrence(True)
+        if self.rec16:
+            self.dz16 = torch.empty((self.F, self.B, 4 * H), dtype=torch.bfloat16, device=self.x.device)
+            self.Wq16 = torch.empty(H * 4 * H, dtype=torch.bfloat16, device=self.x.device)
+            _lib.check(lib.yt8m_lstm_pack_bf16(_p(W[Din:]), 4 * H, H, None, _p(self.Wq16), _stream()))
+        elif self.Wq is not None:
+            _lib.check(lib.yt8m_lstm_pack(_p(W[Din:]), 4 * H, H, None, _p(self.Wq), _stream()))
+
+    def recur_bwd(self, t0, T):
+        lib, B, Din, H = self.lib, self.B, self.Din, self.H
+        z, cs, dout, dz, work, nf, Wh = _p(self.z), _p(self.cs), _p(self.dout), _p(self.dz), _p(self.work), _p(self.nf), self.W.data[Din:]
+        ws = ops._workspace(self.x.device)
+        if self.rec_bwd == "bf16":
+            _lib.check(lib.yt8m_lstm_steps_bwd_bf16(z, _p(self.Wq16), cs, dout, dz, _p(self.dz16), work, self.phase, nf, t0, T, B, H, _stream()))
+        elif self.rec_bwd == "persist":
+            # (no dbias_rows: the bias gradient as per-row sums in the epilogue measured SLOWER, 37.1 -> 40.3 ms/step --
+            # four more scattered read-modify-writes per lane and item in front of the exchange loads)
+            _lib.check(lib.yt8m_lstm_persist_bwd(z, _p(Wh), 4 * H, cs, dout, dz, work, self.phase, None, nf, t0, T, B, H, _p(self.pws), self.pws.numel(), _stream()))
+            if PERSIST_CHECK:
+                _lib.check(lib.yt8m_lstm_persist_status(_p(self.pws), _stream()))
+        else:
+            _lib.check(lib.yt8m_lstm_steps_bwd(z, _p(Wh), 4 * H, _p(self.Wq), cs, dout, dz, work, self.phase, nf, t0, T, B, H, _p(ws), ws.numel() * 4, _stream()))
+        self.phase = (self.phase + T) % 2
+
+    def dx_operands(self, t0, T):
+        """(dz as the dx product reads it, bf16: its transposed copy for the dW products, the event that says so); first chunk: W_x too."""
+        dzc, Wx = self._rows(self.dz, t0, T), self.W.data[:self.Din]
+        if self.hoisted == "bf16":                                  # dz feeds dx (plain) and both dW products (transposed)
+            if self.rec16:                                          # the step kernels already wrote the plain bf16 copy
+                dzb, dzT = self._rows(self.dz16, t0, T), ops.cast_bf16(dzc, transpose=True)
+            else:
+                dzb, dzT = ops.cast_bf16_both(dzc)
+            if self.Wxb is None:
+                self.Wxb = ops.cast_bf16(Wx)
+            return dzb, dzT, torch.cuda.current_stream(dzc.device).record_event()
+        if self.hoisted == "x3" and self.wants_dx:                  # dz as stored feeds dx: on the layer stream (critical path);
+            dz3 = ops.x3_split(dzc)[0]                              # its transposed image (both dW products) is made by weight_grad
+            if self.Wx3 is None:
+                self.Wx3 = ops.x3_split(Wx)[0]
+            return dz3, None, None
+        return None, None, None
+
+    def dx(self, t0, T, dst, dz):
+        """dst[t0:t0+T] = dz . W_x^T, through the dropout mask the forward pass applied to this layer's input."""
+        out = self._rows(dst, t0, T)
+        if self.hoisted == "x3":
+            ops.gemm_x3_grouped([dict(A=dz[0], B=self.Wx3, out=out)])
+        elif self.hoisted == "bf16":
+            ops.gemm_bf16_nt_grouped([dict(A=dz[0], B=self.Wxb, out=out)])
+        else:
+            ops.gemm(self._rows(self.dz, t0, T), self.W.data[:self.Din], out=out, transB=True)
+        if self.drop is not None:
+            ops.dropout_(dst[t0:t0 + T], self.drop[0], self.drop[1], t0 * self.B * self.Din)
+
+    def weight_grad(self, t0, T, beta, dz):
+        """W.grad = beta W.grad + [x ; h]^T dz over the chunk."""
+        Din, gW = self.Din, self.W.grad
+        xc, hc, dzc = self._rows(self.x, t0, T), self._rows(self.hs, t0, T), self._rows(self.dz, t0, T)
+        if self.hoisted == "bf16":
+            ops.gemm_bf16_nt_grouped([dict(A=ops.cast_bf16(xc, transpose=True), B=dz[1], out=gW[:Din], beta=beta),
+                                      dict(A=ops.cast_bf16(hc, transpose=True), B=dz[1], out=gW[Din:], beta=beta)])
+        elif self.hoisted == "x3":
+            dzT3 = ops.x3_split(dzc, plain=False, trans=True)[1]
+            xT3 = ops.x3_split(xc, plain=False, trans=True)[1]
+            hT3 = ops.x3_split(hc, plain=False, trans=True)[1]
+            ops.gemm_x3_grouped([dict(A=xT3, B=dzT3, out=gW[:Din], beta=beta), dict(A=hT3, B=dzT3, out=gW[Din:], beta=beta)])
+        else:
+            ops.gemm(xc, dzc, out=gW[:Din], transA=True, beta=beta, role="dw")
+            ops.gemm(hc, dzc, out=gW[Din:], transA=True, beta=beta, role="dw")
+
+    def bias_grad(self, t0, T, beta):
+        ops.colsum(self._rows(self.dz, t0, T), self.b.grad.view(-1), beta=beta)
+
+
+def _stack_dispatch(lib, x_tm, wb, forget_bias, input_keep_prob, seeds, bf16, need_dx):
+    """Native stack or orchestration, decided once: (desc, u8, drop, pers, own, B, F), desc = the native call's descriptor or None.
+    u8: raw reader bytes [B,F,D] (batch-major); drop: DropoutWrapper is active; pers: the persistent recurrence covers every layer;
+    own: the fp32 stack on it cuts time its own way (PERSIST_FWD_CHUNKS) -- `chunks` is the caller's hint for the per-step pipeline."""
+    L = len(wb) // 2
+    Hs = [w.data.shape[1] // 4 for w in wb[0::2]]
+    u8 = x_tm.dtype == torch.uint8
+    B, F = (x_tm.shape[0], x_tm.shape[1]) if u8 else (x_tm.shape[1], x_tm.shape[0])
+    drop = input_keep_prob is not None and float(input_keep_prob) < 1.0
+    pers = PERSIST and all(lib.yt8m_lstm_persist_supported(B, h) for h in Hs)
+    free = pers and os.environ.get("YT8M_PERSIST_CUS") is None                  # no caller-supplied CU budget
+    own = free and not bf16
+    # The product's own configuration runs entirely inside the library (csrc/lstm_stack.hip: partition, streams, operand images,
+    # product forms -- the path bench.py measures); everything else (caller's chunks, dropout, bf16 operands, per-step kernels,
+    # tuning knobs) keeps the orchestration, built from the same per-call entry points.
+    # (round 6: DropoutWrapper(input_keep_prob) stays on the native stack -- the mask is applied where the operand images are built,
+    # csrc/lstm_stack.hip -- for a float input on the f16 product forms; yt8m_lstm_stack_supported refuses the rest and the
+    # orchestration takes over.  YT8M_NATIVE_DROPOUT=0 keeps dropout on the orchestration.)
+    drop_native = drop and NATIVE_DROPOUT and not u8 and not bf16 and L <= 8
+    desc = None
+    if (NATIVE_STACK and free and (not bf16 or NATIVE_BF16) and X3 and PERSIST_BWD and PERSIST_STEP_IMAGES and
+            (not drop or drop_native) and PERSIST_FWD_CHUNKS > 0 and PERSIST_BWD_CHUNKS > 0 and len(set(Hs)) == 1):
+        D0 = x_tm.shape[2]
+        desc = _stack_desc(B, F, D0, Hs[0], L, u8, forget_bias, (not u8) and bool(need_dx), bf16=bool(bf16),
+                           keep_prob=input_keep_prob if drop else None, seeds=seeds if drop else None)
+        if not ((u8 or x_tm.dtype == torch.float32) and wb[0].data.shape[0] == D0 + Hs[0] and lib.yt8m_lstm_stack_supported(ctypes.byref(desc))):
+            desc = None
+    return desc, u8, drop, pers, own, B, F
+
+
+def _stack_grads(dx, L):                                            # nothing for apply()'s nine other arguments and 2 L Variables
+    return (dx,) + (None,) * (9 + 2 * L)
+
+
 class _LstmStack(torch.autograd.Function):
     """MultiRNNCell([BasicLSTMCell] * L) under tf.nn.dynamic_rnn (W/all_frame_models/lstm_model.py:34-47), time-major, as ONE
     op so that the layers can be pipelined: the sequence is cut into time chunks; layer l's hoisted input projection of
@@ -611,6 +854,7 @@ class _LstmStack(torch.autograd.Function):
     overlap the latency-bound recurrence steps.  Backward runs the same wavefront in reverse time order (top layer first;
     the dx GEMM of a chunk releases the layer below) and every weight-gradient GEMM goes to a further stream, accumulating
     chunk by chunk.  Same kernels and the same per-step arithmetic as the unpipelined op; chunks = 1 is the sequential form.
+    forward() / backward() are that wavefront over _StackLayer's operations; the product's own configuration runs in the library instead.
 
     input_keep_prob < 1 is tf.contrib.rnn.DropoutWrapper(cell, input_keep_prob) around every layer
     (W/all_frame_models/lstm_memory_model.py:36-45): the INPUT of each layer (frames for layer 0, the outputs of the layer
@@ -630,193 +874,60 @@ class _LstmStack(torch.autograd.Function):
     def forward(ctx, x_tm, token, num_frames, forget_bias, chunks, input_keep_prob, seeds, bf16, slot, stream_set, *wb):
         lib = _lib.lib()
         nf = _nf(num_frames)
-        q_raw = None
         L = len(wb) // 2
-        Hs = [w.data.shape[1] // 4 for w in wb[0::2]]
-        if x_tm.dtype == torch.uint8:
-            B, F = x_tm.shape[0], x_tm.shape[1]                    # raw reader output is batch-major
-        else:
-            F, B = x_tm.shape[0], x_tm.shape[1]
-        pers = PERSIST and all(lib.yt8m_lstm_persist_supported(B, h) for h in Hs)
-        parts = _chunks(F, chunks)
-        # fp32 stack on the persistent kernels: the partition is the stack's own (see PERSIST_FWD_CHUNKS), `chunks` is the caller's
-        # hint for the per-step kernels' layer pipeline
-        own = pers and not bf16 and _os.environ.get("YT8M_PERSIST_CUS") is None
-        # The product's own configuration runs entirely inside the library (csrc/lstm_stack.hip: partition, streams, operand images,
-        # product forms -- the path bench.py measures); everything else (caller's chunks, dropout, bf16 operands, per-step kernels,
-        # tuning knobs) keeps the orchestration below, built from the same per-call entry points.
-        drop_ = input_keep_prob is not None and float(input_keep_prob) < 1.0
-        nat_ok = pers and _os.environ.get("YT8M_PERSIST_CUS") is None and (not bf16 or NATIVE_BF16)
-        # (round 6: DropoutWrapper(input_keep_prob) stays on the native stack -- the mask is applied where the operand images are built,
-        # csrc/lstm_stack.hip -- for a float input on the f16 product forms; yt8m_lstm_stack_supported refuses the rest and the
-        # orchestration below takes over.  YT8M_NATIVE_DROPOUT=0 keeps dropout on the orchestration.)
-        u8_in = x_tm.dtype == torch.uint8
-        drop_native = drop_ and NATIVE_DROPOUT and not u8_in and not bf16 and L <= 8
-        if (NATIVE_STACK and nat_ok and X3 and PERSIST_BWD and PERSIST_STEP_IMAGES and (not drop_ or drop_native) and
-                PERSIST_FWD_CHUNKS > 0 and PERSIST_BWD_CHUNKS > 0 and len(set(Hs)) == 1):
-            u8 = x_tm.dtype == torch.uint8
-            D0 = x_tm.shape[2]
-            desc = _stack_desc(B, F, D0, Hs[0], L, u8, forget_bias, (not u8) and bool(ctx.needs_input_grad[0]), bf16=bool(bf16),
-                               keep_prob=input_keep_prob if drop_ else None, seeds=seeds if drop_ else None)
-            if (u8 or x_tm.dtype == torch.float32) and wb[0].data.shape[0] == D0 + Hs[0] and lib.yt8m_lstm_stack_supported(ctypes.byref(desc)):
-                return _LstmStack._native_forward(ctx, lib, desc, x_tm, nf, wb, slot, stream_set)
-        if own and PERSIST_FWD_CHUNKS > 0:
-            parts = _chunks(F, PERSIST_FWD_CHUNKS)
+        desc, u8, drop, pers, own, B, F = _stack_dispatch(lib, x_tm, wb, forget_bias, input_keep_prob, seeds, bf16, ctx.needs_input_grad[0])
+        if desc is not None:
+            return _LstmStack._native_forward(ctx, lib, desc, x_tm, nf, wb, slot, stream_set)
+        parts = _chunks(F, PERSIST_FWD_CHUNKS if own and PERSIST_FWD_CHUNKS > 0 else chunks)
+        # the backward pass may cut time differently (all buffers are whole-layer): its first recurrence chunk runs with nothing
+        # beside it, so shorter chunks shorten that pipeline fill; the forward recurrence owns the chip and wants few launches
         bwd_parts = _bwd_parts(F, _chunks(F, chunks), own)
-        if x_tm.dtype == torch.uint8:
-            # raw reader output [B,F,D] (batch-major): the layer-0 projection takes the bytes themselves (csrc/u8proj.hip) --
-            # one conversion pass writes (q - 128) as bf16 in time-major order (three copies side by side: the three bf16
-            # terms of alpha W share one concatenated reduction), the row norms, and the fp32 time-major frames that only
-            # the weight-gradient product still reads
-            _dev(x_tm)
-            q_raw = x_tm.contiguous()
-            Bq, Fq, Dq = q_raw.shape
-            rrow = torch.empty((Fq * Bq,), dtype=torch.float32, device=q_raw.device)
-            x_tm = torch.empty((Fq, Bq, Dq), dtype=torch.float32, device=q_raw.device)
-            Qb = Qimg = None
-            # one-plane operand image for the x3 kernel (three exact products per element pair) when every time chunk starts on
-            # a 32-row group of the image; otherwise three bf16 copies side by side for the plain bf16 kernel
-            if X3 and Dq % 16 == 0 and all((t0 * Bq) % 32 == 0 for t0, _ in parts):
-                Qimg = torch.empty(((Fq * Bq + 31) // 32) * (Dq // 16) * 1024, dtype=torch.uint8, device=q_raw.device)
-                _lib.check(lib.yt8m_u8_frames_image(_p(q_raw), _p(nf), Bq, Fq, Dq, 1e-12, _p(Qimg), _p(x_tm), _p(rrow), _stream()))
-            else:
-                Qb = ops._bf16_empty(Fq * Bq, 3 * Dq, q_raw.device)
-                _lib.check(lib.yt8m_u8_frames_to_bf16_tm(_p(q_raw), _p(nf), Bq, Fq, Dq, 1e-12, 3, _p(Qb), Qb.stride(0), _p(x_tm), _p(rrow),
-                                                         _stream()))
-        x_tm = _f32c(x_tm)
+        q = _ByteFrames(lib, x_tm, nf, parts) if u8 else None
+        x_tm = _f32c(q.x_tm if u8 else x_tm)
         _dev(x_tm)
-        Ws, bs = wb[0::2], wb[1::2]
         assert (F, B) == tuple(x_tm.shape[:2])
         dev = x_tm.device
         main = torch.cuda.current_stream(dev)
         rs, gs, _ = _side_streams(dev, L, pers)
-        ctx.pers = pers
         bf16 = bool(bf16) and B % 2 == 0 and min(T for _, T in parts) * B >= ops.BF16_MIN_ROWS
-        drop = input_keep_prob is not None and float(input_keep_prob) < 1.0
         layers, inp = [], x_tm
         for l in range(L):                                          # every buffer comes from the main stream's pool
             if drop and l == 0:
                 inp = torch.empty_like(x_tm)                        # dropped copy of the frames (the input itself is data)
-            Din = inp.shape[2]
-            H = Ws[l].data.shape[1] // 4
-            assert Ws[l].data.shape[0] == Din + H, "cell weights must be [in + H, 4H]"
-            st = dict(x=inp, Din=Din, H=H, W=Ws[l], b=bs[l],
-                      z=torch.empty((F, B, 4 * H), dtype=torch.float32, device=dev),
-                      cs=torch.empty((F + 1, B, H), dtype=torch.float32, device=dev),
-                      hs=torch.empty((F + 1, B, H), dtype=torch.float32, device=dev),
-                      out=torch.empty((F, B, H), dtype=torch.float32, device=dev))
-            npk = lib.yt8m_lstm_packed_floats(B, H)
-            st["Wp"] = torch.empty(npk, dtype=torch.float32, device=dev) if npk else None
-            # persistent recurrence (csrc/lstm_persist.hip): one launch per (layer, chunk), W_h resident in registers
+            H = wb[2 * l].data.shape[1] // 4
             pws = lib.yt8m_lstm_persist_workspace_bytes(B, H) if PERSIST else 0
-            if pws and PERSIST_STEP_IMAGES:
-                # one exchange image per step of the longest launch (forward or backward partition): XCD-L2-shared state fetch
-                tmax = max([T for _, T in parts] + [T for _, T in bwd_parts])
-                big = lib.yt8m_lstm_persist_workspace_bytes_steps(B, H, tmax)
-                if big <= PERSIST_STEP_IMAGES_MAX_BYTES:
-                    pws = big
-            st["pws"] = _persist_ws(dev, main, (slot, l) if slot else l, pws) if pws else None
-            layers.append(st)
-            inp = st["out"]
-        start = torch.cuda.Event()
-        start.record(main)
+            # one exchange image per step of the longest launch (forward or backward partition): XCD-L2-shared state fetch
+            big = lib.yt8m_lstm_persist_workspace_bytes_steps(B, H, max(T for _, T in parts + bwd_parts)) if pws and PERSIST_STEP_IMAGES else 0
+            if 0 < big <= PERSIST_STEP_IMAGES_MAX_BYTES:
+                pws = big
+            layers.append(_StackLayer(lib, inp, wb[2 * l], wb[2 * l + 1], nf, forget_bias, bf16, (float(input_keep_prob), int(seeds[l])) if drop else None,
+                                      _persist_ws(dev, main, (slot, l) if slot else l, pws) if pws else None,
+                                      x_tm if drop and l == 0 else None, q if l == 0 else None))
+            inp = layers[-1].out
+        start = main.record_event()
         for l, st in enumerate(layers):
             gs[l].wait_event(start)
             with torch.cuda.stream(rs[l]):
                 rs[l].wait_event(start)
-                st["cs"][0].zero_()
-                st["hs"][0].zero_()
-                if st["Wp"] is not None:
-                    _lib.check(lib.yt8m_lstm_pack(_p(st["W"].data[st["Din"]:]), 4 * st["H"], st["H"], _p(st["Wp"]), None, _stream()))
-                st["bf16"] = bf16 and st["Din"] % 2 == 0
-                # decided on the whole sequence, not the chunk: every partition of the time axis runs the same arithmetic
-                st["x3"] = X3 and not st["bf16"] and F * B >= X3_MIN_ROWS and st["H"] >= 128
-                if l == 0 and q_raw is not None and not drop and not st["bf16"]:
-                    # 3-way bf16 split of (4/255) W_x, transposed ([4H, 3 D], K-contiguous) + the column sums of W_x
-                    Din_, H_ = st["Din"], st["H"]
-                    if Qimg is not None:
-                        st["W3T"] = ops.x3_split(st["W"].data[:Din_], plain=False, trans=True, scale=4.0 / 255.0)[1]
-                    else:
-                        st["W3T"] = ops._bf16_empty(4 * H_, 3 * Din_, dev)
-                        _lib.check(lib.yt8m_split3_bf16_t(_p(st["W"].data[:Din_]), 4 * H_, Din_, 4 * H_, 4.0 / 255.0, _p(st["W3T"]),
-                                                          st["W3T"].stride(0), _stream()))
-                    st["Wcs"] = torch.empty((4 * H_,), dtype=torch.float32, device=dev)
-                    ops.colsum(st["W"].data[:Din_], st["Wcs"])
-                if st["x3"] and "W3T" not in st:                    # W_x^T as the K-contiguous operand of the projection
-                    st["WxT3"] = ops.x3_split(st["W"].data[:st["Din"]], plain=False, trans=True)[1]
-                st["rec16"] = st["bf16"] and REC_BF16 and lib.yt8m_lstm_packed16_elems(B, st["H"]) > 0
-                if st["rec16"]:
-                    st["pws"] = None
-                if st["bf16"]:                                      # W_x^T once per step, K-contiguous for the NT product
-                    st["WxT"] = ops.cast_bf16(st["W"].data[:st["Din"]], transpose=True)
-                if st["rec16"]:                                     # bf16 operands for the recurrent product too
-                    H_ = st["H"]
-                    st["hs16"] = torch.empty((F + 1, B, H_), dtype=torch.bfloat16, device=dev)
-                    st["hs16"][0].zero_()
-                    st["Wp16"] = torch.empty(H_ * 4 * H_, dtype=torch.bfloat16, device=dev)
-                    _lib.check(lib.yt8m_lstm_pack_bf16(_p(st["W"].data[st["Din"]:]), 4 * H_, H_, _p(st["Wp16"]), None, _stream()))
+                st.prepare_fwd()
         r_done = [[torch.cuda.Event() for _ in parts] for _ in range(L)]
         for c, (t0, T) in enumerate(parts):
             for l, st in enumerate(layers):
-                Din, H = st["Din"], st["H"]
                 with torch.cuda.stream(gs[l]):                      # hoisted input projection of the chunk
                     if l > 0:
                         gs[l].wait_event(r_done[l - 1][c])
-                    if drop:
-                        xc = st["x"][t0:t0 + T]
-                        src = x_tm[t0:t0 + T] if l == 0 else xc
-                        _lib.check(lib.yt8m_dropout_f32(_p(src), _p(xc), xc.numel(), float(input_keep_prob), int(seeds[l]),
-                                                        t0 * B * Din, _stream()))
-                    if "W3T" in st and Qimg is not None:
-                        zc = st["z"][t0:t0 + T].view(T * B, 4 * H)
-                        ws = ops._workspace(dev)
-                        _lib.check(lib.yt8m_gemm_x1x3_nt(T * B, 4 * H, Din, _p(Qimg[(t0 * B // 32) * (Din // 16) * 1024:]), _p(st["W3T"].buf),
-                                                         _p(zc), 4 * H, _p(st["b"].data), _p(rrow[t0 * B:]), _p(st["Wcs"]), U8_BETA,
-                                                         _p(ws), ws.numel() * 4, _stream()))
-                    elif "W3T" in st:
-                        zc = st["z"][t0:t0 + T].view(T * B, 4 * H)
-                        ops.gemm_bf16_nt_grouped([dict(A=Qb[t0 * B:(t0 + T) * B], B=st["W3T"], out=zc)])
-                        _lib.check(lib.yt8m_rowscale_bias_f32(_p(zc), T * B, 4 * H, 4 * H, _p(rrow[t0 * B:]), _p(st["Wcs"]),
-                                                              U8_BETA, _p(st["b"].data), _stream()))
-                    elif st["bf16"]:
-                        ops.gemm_bf16_nt_grouped([dict(A=ops.cast_bf16(st["x"][t0:t0 + T].view(T * B, Din)), B=st["WxT"],
-                                                       out=st["z"][t0:t0 + T].view(T * B, 4 * H), bias=st["b"].data)])
-                    elif st["x3"]:
-                        xi = ops.x3_split(st["x"][t0:t0 + T].view(T * B, Din))[0]
-                        ops.gemm_x3_grouped([dict(A=xi, B=st["WxT3"], out=st["z"][t0:t0 + T].view(T * B, 4 * H), bias=st["b"].data)])
-                    else:
-                        ops.gemm(st["x"][t0:t0 + T].view(T * B, Din), st["W"].data[:Din], out=st["z"][t0:t0 + T].view(T * B, 4 * H),
-                                 bias=st["b"].data)
-                    g_ev = torch.cuda.Event()
-                    g_ev.record(gs[l])
+                    st.project(t0, T)
+                    g_ev = gs[l].record_event()
                 with torch.cuda.stream(rs[l]):                      # recurrence steps of the chunk
                     rs[l].wait_event(g_ev)
-                    ws = ops._workspace(dev)
-                    if st["rec16"]:
-                        _lib.check(lib.yt8m_lstm_steps_fwd_bf16(_p(st["z"]), _p(st["Wp16"]), _p(st["cs"]), _p(st["hs"]), _p(st["hs16"]),
-                                                                _p(st["out"]), _p(nf), t0, T, B, H, float(forget_bias), _stream()))
-                    elif st["pws"] is not None:
-                        _lib.check(lib.yt8m_lstm_persist_fwd(_p(st["z"]), _p(st["W"].data[Din:]), 4 * H, _p(st["cs"]), _p(st["hs"]),
-                                                             _p(st["out"]), _p(nf), t0, T, B, H, float(forget_bias), _p(st["pws"]),
-                                                             st["pws"].numel(), _stream()))
-                        if PERSIST_CHECK:
-                            _lib.check(lib.yt8m_lstm_persist_status(_p(st["pws"]), _stream()))
-                    else:
-                        _lib.check(lib.yt8m_lstm_steps_fwd(_p(st["z"]), _p(st["W"].data[Din:]), 4 * H, _p(st["Wp"]), _p(st["cs"]),
-                                                           _p(st["hs"]), _p(st["out"]), _p(nf), t0, T, B, H, float(forget_bias),
-                                                           _p(ws), ws.numel() * 4, _stream()))
+                    st.recur_fwd(t0, T)
                     r_done[l][c].record(rs[l])
-        for l in range(L):
+        for l, st in enumerate(layers):
             main.wait_event(r_done[l][-1])
-        # the backward pass may cut time differently (all buffers are whole-layer): its first recurrence chunk runs with nothing
-        # beside it, so shorter chunks shorten that pipeline fill; the forward recurrence owns the chip and wants few launches
-        ctx.layers, ctx.nf, ctx.parts = layers, nf, bwd_parts
-        ctx.drop = (float(input_keep_prob), tuple(int(v) for v in seeds)) if drop else None
+            st.release(("undropped", "bytes"))                      # what only forward() needed
+        ctx.layers, ctx.parts, ctx.pers = layers, bwd_parts, pers
         ctx.set_materialize_grads(False)
-        outs = [layers[-1]["out"]]
-        for st in layers:
-            outs += [st["cs"][F], st["hs"][F]]
-        return tuple(outs)
+        return (layers[-1].out,) + tuple(t for st in layers for t in (st.cs[F], st.hs[F]))
 
     @staticmethod
     def _native_forward(ctx, lib, desc, x, nf, wb, slot=0, stream_set=0):
@@ -908,7 +1019,7 @@ class _LstmStack(torch.autograd.Function):
             # data parallel: report each layer's gradients from a side stream that waits for THAT layer only (the library records
             # the point on its weight-gradient stream: layer L-1's gradients are final a whole last part before layer 0's), so
             # the reducer's collective for layer L-1 is on the wire while layer 0's last weight-gradient products still run
-            side = _dp_side_stream(dev)
+            side = _side_stream(dev, "dp")
             for l in reversed(range(L)):
                 _lib.check(lib.yt8m_lstm_stack_layer_done_wait(l, ctypes.c_void_p(side.cuda_stream)))
                 with torch.cuda.stream(side):
@@ -920,168 +1031,75 @@ class _LstmStack(torch.autograd.Function):
             for v in list(Ws) + list(bs):
                 if v.grad is not None:
                     v.grad_done()
-        return (dx, None, None, None, None, None, None, None, None, None) + (None,) * (2 * L)
+        return _stack_grads(dx, L)
 
     @staticmethod
     def backward(ctx, dout_top, *dfinal):
         if getattr(ctx, "native", None) is not None:
             return _LstmStack._native_backward(ctx, dout_top, dfinal)
-        layers, nf, parts = ctx.layers, ctx.nf, ctx.parts
+        layers, parts = ctx.layers, ctx.parts
         ctx.layers = None
         L = len(layers)
-        F, B, _ = layers[0]["x"].shape
-        dev = layers[0]["x"].device
-        lib = _lib.lib()
+        dev = layers[0].x.device
         main = torch.cuda.current_stream(dev)
         rs, gs, sw = _side_streams(dev, L, ctx.pers)
         need_dx = ctx.needs_input_grad[0]
-        dx = torch.empty_like(layers[0]["x"]) if need_dx else None
-        for st in layers:
-            st.pop("WxT", None)
-            st.pop("WxT3", None)
-            st.pop("W3T", None)
-            st.pop("Wcs", None)
-            st.pop("Wp16", None)
-            st.pop("hs16", None)
+        dx = torch.empty_like(layers[0].x) if need_dx else None
+        for st in layers:                                           # forward-only images go before anything is allocated
+            st.release(st.FWD_ONLY)
         for l, st in enumerate(layers):                            # buffers come from the main stream's pool
-            H = st["H"]
-            st["dz"] = torch.empty((F, B, 4 * H), dtype=torch.float32, device=dev)
-            st["work"] = torch.empty((4, B, H), dtype=torch.float32, device=dev)
-            st["dout"] = (None if dout_top is None else _f32c(dout_top)) if l == L - 1 else \
-                torch.empty((F, B, H), dtype=torch.float32, device=dev)
-            npk = lib.yt8m_lstm_packed_floats(B, H)
-            st["Wq"] = torch.empty(npk, dtype=torch.float32, device=dev) if npk else None
-        start = torch.cuda.Event()
-        start.record(main)
+            st.alloc_bwd(dout_top, l == L - 1, l > 0 or need_dx)
+        start = main.record_event()
         sw.wait_event(start)
         for l, st in enumerate(layers):
-            H = st["H"]
             gs[l].wait_event(start)
             with torch.cuda.stream(rs[l]):
                 rs[l].wait_event(start)
-                dc, dh = dfinal[2 * l], dfinal[2 * l + 1]
-                if dh is None:
-                    st["work"][0].zero_()
-                else:
-                    st["work"][0].copy_(dh)
-                if dc is None:
-                    st["work"][1].zero_()
-                else:
-                    st["work"][1].copy_(dc)
-                st["phase"] = 0
-                if st["rec16"]:
-                    st["dz16"] = torch.empty((F, B, 4 * H), dtype=torch.bfloat16, device=dev)
-                    st["Wq16"] = torch.empty(H * 4 * H, dtype=torch.bfloat16, device=dev)
-                    _lib.check(lib.yt8m_lstm_pack_bf16(_p(st["W"].data[st["Din"]:]), 4 * H, H, None, _p(st["Wq16"]), _stream()))
-                elif st["Wq"] is not None:
-                    _lib.check(lib.yt8m_lstm_pack(_p(st["W"].data[st["Din"]:]), 4 * H, H, None, _p(st["Wq"]), _stream()))
-        wbeta = {}
+                st.prepare_bwd(dfinal[2 * l + 1], dfinal[2 * l])
+        seen = set()
+
+        def beta(v):                                                # a Variable's first chunk: grad_beta(), later ones add
+            first = id(v) not in seen
+            seen.add(id(v))
+            return v.grad_beta() if first else 1.0
+
         last = []
         for c in range(len(parts) - 1, -1, -1):
             t0, T = parts[c]
             dx_ev = None                                            # dx GEMM of the layer above for this chunk
             for l in range(L - 1, -1, -1):
                 st = layers[l]
-                Din, H, W, b = st["Din"], st["H"], st["W"], st["b"]
-                dzc = st["dz"][t0:t0 + T].view(T * B, 4 * H)
                 with torch.cuda.stream(rs[l]):
                     if dx_ev is not None:
                         rs[l].wait_event(dx_ev)
-                    ws = ops._workspace(dev)
-                    if st["rec16"]:
-                        _lib.check(lib.yt8m_lstm_steps_bwd_bf16(_p(st["z"]), _p(st["Wq16"]), _p(st["cs"]), _p(st["dout"]), _p(st["dz"]),
-                                                                _p(st["dz16"]), _p(st["work"]), st["phase"], _p(nf), t0, T, B, H,
-                                                                _stream()))
-                    elif st.get("pws") is not None and PERSIST_BWD and lib.yt8m_lstm_persist_bwd_supported(B, H):
-                        # (no dbias_rows: the bias gradient as per-row sums in the epilogue measured SLOWER, 37.1 -> 40.3 ms/step --
-                        # four more scattered read-modify-writes per lane and item in front of the exchange loads)
-                        _lib.check(lib.yt8m_lstm_persist_bwd(_p(st["z"]), _p(W.data[Din:]), 4 * H, _p(st["cs"]), _p(st["dout"]),
-                                                             _p(st["dz"]), _p(st["work"]), st["phase"], None, _p(nf),
-                                                             t0, T, B, H, _p(st["pws"]), st["pws"].numel(), _stream()))
-                        if PERSIST_CHECK:
-                            _lib.check(lib.yt8m_lstm_persist_status(_p(st["pws"]), _stream()))
-                    else:
-                        _lib.check(lib.yt8m_lstm_steps_bwd(_p(st["z"]), _p(W.data[Din:]), 4 * H, _p(st["Wq"]), _p(st["cs"]), _p(st["dout"]),
-                                                           _p(st["dz"]), _p(st["work"]), st["phase"], _p(nf), t0, T, B, H, _p(ws),
-                                                           ws.numel() * 4, _stream()))
-                    st["phase"] = (st["phase"] + T) % 2
-                    rb = torch.cuda.Event()
-                    rb.record(rs[l])
+                    st.recur_bwd(t0, T)
+                    rb = rs[l].record_event()
                 dx_ev = None
-                dzb = dzT = None
-                if st["bf16"]:                                      # dz feeds dx (plain) and both dW products (transposed)
-                    with torch.cuda.stream(gs[l]):
-                        gs[l].wait_event(rb)
-                        if st["rec16"]:                         # the step kernels already wrote the plain bf16 copy
-                            dzb, dzT = st["dz16"][t0:t0 + T].view(T * B, 4 * H), ops.cast_bf16(dzc, transpose=True)
-                        else:
-                            dzb, dzT = ops.cast_bf16_both(dzc)
-                        if "Wxb" not in st:
-                            st["Wxb"] = ops.cast_bf16(W.data[:Din])
-                        cast_ev = torch.cuda.Event()
-                        cast_ev.record(gs[l])
-                dz3 = None
-                if st["x3"] and (l > 0 or need_dx):                 # dz as stored feeds dx: on the layer stream (critical path);
-                    with torch.cuda.stream(gs[l]):                  # its transposed image (both dW products) is made on `sw`
-                        gs[l].wait_event(rb)
-                        dz3 = ops.x3_split(dzc)[0]
-                        if "Wx3" not in st:
-                            st["Wx3"] = ops.x3_split(W.data[:Din])[0]
-                if l > 0 or need_dx:
-                    with torch.cuda.stream(gs[l]):
-                        gs[l].wait_event(rb)
-                        dst = layers[l - 1]["dout"] if l > 0 else dx
-                        if st["x3"]:
-                            ops.gemm_x3_grouped([dict(A=dz3, B=st["Wx3"], out=dst[t0:t0 + T].view(T * B, Din))])
-                        elif st["bf16"]:
-                            ops.gemm_bf16_nt_grouped([dict(A=dzb, B=st["Wxb"], out=dst[t0:t0 + T].view(T * B, Din))])
-                        else:
-                            ops.gemm(dzc, W.data[:Din], out=dst[t0:t0 + T].view(T * B, Din), transB=True)
-                        if ctx.drop is not None:
-                            ops.dropout_(dst[t0:t0 + T], ctx.drop[0], ctx.drop[1][l], t0 * B * Din)
-                        dx_ev = torch.cuda.Event()
-                        dx_ev.record(gs[l])
+                with torch.cuda.stream(gs[l]):
+                    gs[l].wait_event(rb)
+                    dz = st.dx_operands(t0, T)
+                    if st.wants_dx:
+                        st.dx(t0, T, layers[l - 1].dout if l > 0 else dx, dz)
+                        dx_ev = gs[l].record_event()
                         if c == 0:
                             last.append(dx_ev)
                 with torch.cuda.stream(sw):
                     sw.wait_event(rb)
-                    if W.grad is not None:
-                        beta = wbeta.get(id(W))
-                        if beta is None:
-                            beta = W.grad_beta()
-                            wbeta[id(W)] = 1.0
-                        if st["bf16"]:
-                            sw.wait_event(cast_ev)
-                            dzT.record_stream(sw)
-                            ops.gemm_bf16_nt_grouped([
-                                dict(A=ops.cast_bf16(st["x"][t0:t0 + T].view(T * B, Din), transpose=True), B=dzT, out=W.grad[:Din], beta=beta),
-                                dict(A=ops.cast_bf16(st["hs"][t0:t0 + T].view(T * B, H), transpose=True), B=dzT, out=W.grad[Din:], beta=beta)])
-                        elif st["x3"]:
-                            dzT3 = ops.x3_split(dzc, plain=False, trans=True)[1]
-                            xT3 = ops.x3_split(st["x"][t0:t0 + T].view(T * B, Din), plain=False, trans=True)[1]
-                            hT3 = ops.x3_split(st["hs"][t0:t0 + T].view(T * B, H), plain=False, trans=True)[1]
-                            ops.gemm_x3_grouped([dict(A=xT3, B=dzT3, out=W.grad[:Din], beta=beta),
-                                                 dict(A=hT3, B=dzT3, out=W.grad[Din:], beta=beta)])
-                        else:
-                            ops.gemm(st["x"][t0:t0 + T].view(T * B, Din), dzc, out=W.grad[:Din], transA=True, beta=beta, role="dw")
-                            ops.gemm(st["hs"][t0:t0 + T].view(T * B, H), dzc, out=W.grad[Din:], transA=True, beta=beta, role="dw")
-                    if b.grad is not None:
-                        beta = wbeta.get(id(b))
-                        if beta is None:
-                            beta = b.grad_beta()
-                            wbeta[id(b)] = 1.0
-                        ops.colsum(dzc, b.grad.view(-1), beta=beta)
-        fin = torch.cuda.Event()
-        fin.record(sw)                                              # sw waited for every recurrence chunk
-        main.wait_event(fin)
+                    if st.W.grad is not None:
+                        if dz[2] is not None:                       # bf16: dz^T made on the dx stream
+                            sw.wait_event(dz[2])
+                            dz[1].record_stream(sw)
+                        st.weight_grad(t0, T, beta(st.W), dz)
+                    if st.b.grad is not None:
+                        st.bias_grad(t0, T, beta(st.b))
+        main.wait_event(sw.record_event())                          # sw waited for every recurrence chunk
         for e in last:
             main.wait_event(e)
         for st in layers:
-            if st["W"].grad is not None:
-                st["W"].grad_done()
-            if st["b"].grad is not None:
-                st["b"].grad_done()
-        return (dx, None, None, None, None, None, None, None, None, None) + (None,) * (2 * L)
+            for v in (st.W, st.b):
+                if v.grad is not None:
+                    v.grad_done()
+        return _stack_grads(dx, L)
 
 
 def lstm_stack(x_tm, num_frames, weights_biases, forget_bias=1.0, chunks=4, input_keep_prob=None, seeds=None, bf16=False, slot=0,
@@ -1169,21 +1187,7 @@ def bi_concat(out_fw, out_bw, num_frames):
     return _BiConcat.apply(out_fw, out_bw, num_frames)
 
 
-# Overlapped directions (opt-in; measured in DESIGN_LOG.md "BiLstmModel"): the bw stack is issued from a side stream on the library's
-# second stream set, both directions' forward recurrences capped at half the chip.  The library's residency gate (csrc/lstm_persist.hip,
-# PersistGate) admits a persistent launch beside the running ones only while all of them fit the chip together, so two capped
-# recurrences run side by side and nothing whole-chip ever overlaps another persistent launch.
-BI_OVERLAP = _os.environ.get("YT8M_BI_OVERLAP", "0") != "0"
 BI_OVERLAP_RUNS = [0]          # how often the overlapped form ran (tests assert that it engaged)
-_BI_SIDE = {}
-
-
-def _bi_side_stream(dev):
-    st = _BI_SIDE.get(dev)
-    if st is None:
-        st = torch.cuda.Stream(device=dev, priority=REC_STREAM_PRIORITY)
-        _BI_SIDE[dev] = st
-    return st
 
 
 def bidirectional_lstm_stacks(x_fw, x_bw, num_frames, wb_fw, wb_bw, forget_bias=1.0, chunks=4, bf16=False, overlap=None):
@@ -1199,7 +1203,7 @@ def bidirectional_lstm_stacks(x_fw, x_bw, num_frames, wb_fw, wb_bw, forget_bias=
     lib = _lib.lib()
     dev = x_fw.device
     main = torch.cuda.current_stream(dev)
-    side = _bi_side_stream(dev)
+    side = _side_stream(dev, "bi", REC_STREAM_PRIORITY)
     side.wait_stream(main)
     half = torch.cuda.get_device_properties(dev).multi_processor_count // 2
     prev_f, prev_b = ctypes.c_int(-1), ctypes.c_int(-1)
@@ -1871,11 +1875,6 @@ def netvlad_pool_u8(q, num_frames, Wc, bc, centres, nsplit=2, eps=1e-12, want_q=
 
 
 # ---- MultiscaleCnnLstmModel: CNN -> batch norm -> ReLU -> (LSTM input, pair-max for the next scale), everything time-major ------------
-import os as _os_ms
-
-MULTISCALE_FUSED = _os_ms.environ.get("YT8M_MULTISCALE_FUSED", "1") != "0"   # 0: the plugin composes the scale from ops.linear / ops.batch_norm / torch
-
-
 def bn_relu_pool2_supported(x, C):
     """The fused scale (csrc/multiscale.hip): a device tensor and C % 4 == 0 (16-byte column accesses)."""
     return bool(x.is_cuda and C % 4 == 0 and C >= 4)
