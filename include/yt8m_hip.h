@@ -326,6 +326,24 @@ int yt8m_dequant_l2norm_u8(const uint8_t* q, const int32_t* num_frames, float* x
  * dequantized values") then L2-normalise: q[B,F,D] -> x[B,D] */
 int yt8m_dequant_mean_l2norm_u8(const uint8_t* q, const int32_t* num_frames, float* x,
                                 int64_t B, int64_t F, int64_t D, float eps, yt8m_stream_t stream);
+/* yt8m_resolution_mean_*: the ResolutionTransformer (W/all_feature_transform/resolution_transformer.py:7-29; csrc/transform.hip) in one
+ * pass over the frames: x [B,F,D] -> y [B,F2,D] fp32 (batch-major, dense) with r = resolution, F2 = F / r (integer division); frames
+ * from F2 r on are dropped.  Per video b, n = num_frames[b] clamped to [0, F] (num_frames == NULL: n = F).
+ *   _u8:  y[b,g,:] = (1/r) * the sum over j < r with g r + j < n of Dequantize(q[b, g r + j, :]), Dequantize(v) = v (4/255) + (4/512 - 2).
+ *         The divisor is r also where fewer than r frames of the group are real (the reference's reduce_mean over zero-padded frames);
+ *         a group with no real frame is a zero row.  The bytes are summed as integers: (sc sum + k bias) / r for k real frames.
+ *         The mean and its normalisation are formed in fp64 from the exact integer (512 sum - 65025 k) over 32640 r and rounded to
+ *         fp32 once (rows of more than 2048 columns: their tail twice).
+ *   _f32: the plain mean of the r rows as they are, padding rows included (the reference averages whatever floats it is given).
+ *   l2norm != 0: every output row times rsqrt(max(sum of squares, eps)); a zero row stays zero.
+ *   num_frames_out [B] (may be NULL) = n / r (integer division), written on the device: a video with n < r gets 0.
+ * Out of place: every operand disjoint.  resolution outside [1, F] is YT8M_E_BADARG.  Any D: a wave keeps a row of up to 2048 columns in
+ * registers (the 16-byte forms) and scales wider rows in place; 16-byte loads when D % 16 == 0 (_u8) or D % 4 == 0 (_f32), 4-byte
+ * loads when D % 4 == 0 (_u8), single elements otherwise. */
+int yt8m_resolution_mean_u8(const uint8_t* q, const int32_t* num_frames, float* y, int32_t* num_frames_out, int64_t B, int64_t F,
+                            int64_t D, int64_t resolution, int l2norm, float eps, yt8m_stream_t stream);
+int yt8m_resolution_mean_f32(const float* x, const int32_t* num_frames, float* y, int32_t* num_frames_out, int64_t B, int64_t F,
+                             int64_t D, int64_t resolution, int l2norm, float eps, yt8m_stream_t stream);
 
 /* ---- MoE head (W/all_video_models/moe_model.py:54-64) ------------------------------------------
  * Zg [B, V*(M+1)] gate logits (label-major, mixture-minor; gate M = dummy expert), Ze [B, V*M] expert

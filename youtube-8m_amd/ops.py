@@ -621,6 +621,29 @@ def dequantize_frames(q, num_frames):
     return dequant_noise(q, num_frames, 0.0, 0)
 
 
+# ---- input transformers beyond the default (csrc/transform.hip; feature_transform.py) -----------------------------------------------
+def resolution_mean(x, num_frames, resolution, l2norm=True, eps=1e-12):
+    """ResolutionTransformer (W/all_feature_transform/resolution_transformer.py:7-29) in one pass: uint8 or float32 frames [B,F,D] ->
+    (float32 [B, F // r, D], num_frames // r [B] int32 on the device).  Row g of a video is the mean of its frames [g r, (g + 1) r),
+    l2-normalised when l2norm; frames from (F // r) r on are dropped.  uint8: dequantised with the padding frames 0, the divisor
+    always r.  float32: the plain mean of the rows as they are.  num_frames may be on the host.  Frames are data: no gradient."""
+    x, nf = _frames_nf(x, num_frames)
+    B, F, D = x.shape
+    r = int(resolution)
+    if r < 1 or r > F:
+        raise ValueError("resolution must be in [1, F = %d], got %d" % (F, r))
+    if x.dtype == torch.uint8:
+        fn = _lib.lib().yt8m_resolution_mean_u8
+    elif x.dtype == torch.float32:
+        fn = _lib.lib().yt8m_resolution_mean_f32
+    else:
+        raise TypeError("expected uint8 or float32 frames, got %s" % x.dtype)
+    y = torch.empty((B, F // r, D), dtype=torch.float32, device=x.device)
+    nf_out = torch.empty((B,), dtype=torch.int32, device=x.device)
+    _lib.check(fn(_p(x), _p(nf), _p(y), _p(nf_out), B, F, D, r, 1 if l2norm else 0, eps, _stream()))
+    return y, nf_out
+
+
 def moe_mix_fwd(Zg, Ze, V, M):
     _dev(Zg, Ze)
     B = Zg.shape[0]

@@ -296,6 +296,8 @@ def build_graph(model, label_loss_fn=None, batch_size=None, **kw):
     """Name-compatible entry: returns the TrainGraph configured from FLAGS like W/train.py:679-728 does."""
     if "augmenter_class" not in kw:                               # W/train.py:708
         kw["augmenter_class"] = find_class_by_name(FLAGS.data_augmenter, [data_augmentation])
+    if "transformer_class" not in kw:                             # W/train.py:707 (and W/eval.py, W/inference.py the same way)
+        kw["transformer_class"] = find_class_by_name(FLAGS.feature_transformer, [feature_transform])
     return TrainGraph(model, label_loss_fn=label_loss_fn,
                       batch_size=batch_size or FLAGS.batch_size,
                       base_learning_rate=kw.pop("base_learning_rate", FLAGS.base_learning_rate),
