@@ -4,7 +4,9 @@ unaligned leading dimensions, saturated probabilities, ties.
 
 These are the quick small-shape checks.  The dispatch branches of the streaming kernels (shape thresholds, pointer alignment, grid caps,
 workspace fall-backs, the models' own shapes) are covered arm by arm in tests/test_gpu_streaming_branches.py, whose BRANCH_TABLE lists
-them."""
+them.  The arms of the GEMM family (layouts, the LDS-DMA and guarded paths, K tails, the float4 epilogue, rounds and split-K, groups,
+the bf16 tile floor, the image-form chooser, every refusal) are covered the same way, on integer data bit for bit, in
+tests/test_gpu_gemm_branches.py."""
 import numpy as np
 import pytest
 import torch

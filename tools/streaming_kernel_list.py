@@ -36,18 +36,19 @@ def instantiation(name):
     return s.strip()
 
 
-def main(path):
+def main(path, stem="streaming"):
+    """stem: which branch module the run was of (tools/gemm_kernel_list.py passes "gemm")."""
     ours = project_kernels()
     calls = {}
     for row in csv.DictReader(open(path)):
         inst = instantiation(row["Name"])
         if re.match(r"\w+", inst).group(0) in ours and "::" not in inst.split("<")[0]:
             calls[inst] = calls.get(inst, 0) + int(row["Calls"])
-    with open(os.path.join(ROOT, "profiles", "streaming_branches_kernel_stats.csv"), "w") as f:
+    with open(os.path.join(ROOT, "profiles", "%s_branches_kernel_stats.csv" % stem), "w") as f:
         f.write('"Name","Calls"\n')
         for k in sorted(calls):
             f.write('"%s",%d\n' % (k, calls[k]))
-    with open(os.path.join(ROOT, "tests", "golden", "streaming_kernels_seen.txt"), "w") as f:
+    with open(os.path.join(ROOT, "tests", "golden", "%s_kernels_seen.txt" % stem), "w") as f:
         for k in sorted({re.match(r"\w+", k).group(0) for k in calls}):
             f.write(k + "\n")
     print("%d instantiations of %d kernels" % (len(calls), len({k.split("<")[0] for k in calls})))

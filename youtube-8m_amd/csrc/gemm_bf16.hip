@@ -571,7 +571,7 @@ int gemm_bf16_big_launch(int nprob, const yt8m_gemm_problem* probs, void* worksp
   hipLaunchKernelGGL(gemm_bf16_big_kernel, dim3((unsigned)grid), dim3(512), NST * STAGE_F * sizeof(float), s, G);
   }
   if (G.S > 1) hipLaunchKernelGGL(bf16_fixup_kernel, dim3((unsigned)G.rem * 16), dim3(256), 0, s, G);
-  return launch_status("gemm_bf16_big_kernel");
+  return launch_status(k64 ? "gemm_bf16_k64_kernel" : "gemm_bf16_big_kernel");
 }
 
 }  // namespace yt8m

@@ -13,7 +13,9 @@
 //   whole K-step ahead, two LDS buffers, ONE barrier per K-step).  The LDS image is lane-linear as the DMA requires;
 //   K-contiguous operands are XOR-swizzled through the SOURCE address so their ds_read_b128 fragment fetch is
 //   conflict-free, N-contiguous operands are read with conflict-free ds_read_b32 (32 consecutive floats / half-wave).
-//   Edge tiles, unaligned leading dimensions and K % 16 != 0 take a guarded register-staged path with the same image.
+//   Edge tiles stay on the LDS-DMA path (rows / column chunks beyond the matrix are redirected: fill_dma) and so does K % 16 != 0
+//   (only its last, partial K-step is a guarded zero-padded store: fill_step); operands that are not 16-byte aligned or whose
+//   leading dimension is not a multiple of 4 take a guarded register-staged path with the same image.
 //   XCD-aware rasterisation: consecutive workgroup ids land on different XCDs (id % 8), so the grid is remapped such
 //   that each XCD walks a contiguous strip of tiles and re-uses its B panel from its own 4 MiB L2 across M-tiles.
 #include "common.h"
@@ -227,7 +229,7 @@ __device__ __forceinline__ void mma_step_bf16(const Frag& fa, const Frag& fb, f3
 //                COUNTED vmcnt(4) -- each lane has exactly 4 DMA instructions per K-step in flight order -- so only
 //                K-step kt+1 is waited for, kt+2 stays on the wire across the barrier (raw s_barrier: __syncthreads()
 //                would drain vmcnt(0)).  A stage is re-filled two barriers after its last ds_read.
-//  guarded path: register staging, 2 stages; used for unaligned operands / K % 16 != 0.
+//  guarded path: register staging, 2 stages; used when either operand is not 16-byte aligned with ld % 4 == 0 (process_tile).
 // In both, every fragment of the K-step is fetched from LDS before the first MFMA (sched_barrier pins the order) so
 // the LDS latency is paid once per K-step and the MFMAs stream.
 template <bool A_KC, bool B_KC, bool DMA, bool BF16>
@@ -576,9 +578,9 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmArgs g) {
 // Up to 4 problems with the same layout flags share one tile space of T tiles; P = 768 resident slots (3 per CU).
 //   whole-tile rounds  : the first floor(T / P) * P tiles, one per workgroup, whole K, K-synchronised across the chip so
 //                        operand panels are re-used out of L2;
-//   remainder (T % P)  : each tile is split along K into S = P / remainder parts; part s of remainder tile r parks its
-//                        raw accumulators in ws[(r*S + s)][128][128]; splitk_fixup_kernel then sums the S parts in a
-//                        fixed order (deterministic).
+//   remainder (T % P)  : each tile is split along K into S parts (S chosen by grouped_launch's cost model: at most min_nk / 8,
+//                        96 and what the workspace holds); part s of remainder tile r parks its raw accumulators in
+//                        ws[(r*S + s)][128][128]; splitk_fixup_kernel then sums the S parts in a fixed order (deterministic).
 // This removes the wave-quantisation tail (e.g. 888 tiles on 768 slots = 58 % -> 98 % slot utilisation).
 constexpr int MAX_GROUP = 4;
 struct GroupArgs {

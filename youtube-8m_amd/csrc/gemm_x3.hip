@@ -1668,7 +1668,9 @@ int x3_launch(int nprob, const yt8m_gemm_problem* probs, const float* rscale, co
   // YT8M_B1_PIPE=0: the round-3 kernel (two 64 KiB stages, one barrier per four blocks) instead of gemm_b1q_kernel
   static const bool piped_env = getenv("YT8M_B1_PIPE") == nullptr || atoi(getenv("YT8M_B1_PIPE")) != 0;
   const bool piped = g_schedule_mode == 1 || (g_schedule_mode == 0 && piped_env);
+  const char* launched = "gemm_x3_kernel";                         // what launch_status names on failure
   if constexpr (PA == 0) {
+    launched = piped ? "gemm_b1q_kernel" : "gemm_b1_kernel";
     if (piped) {
       static DeviceOnce lds_once_q;
       YT8M_HIP_CHECK(lds_once_q.lds(reinterpret_cast<const void*>(gemm_b1q_kernel), BQ_SLOTS * BQ_SLOT_F * (int)sizeof(float)));
@@ -1678,15 +1680,18 @@ int x3_launch(int nprob, const yt8m_gemm_problem* probs, const float* rscale, co
     }
   }
   else if constexpr (PA == 2) {
+    launched = "gemm_h2q_kernel";
     hipLaunchKernelGGL(gemm_h2q_kernel<2>, dim3((unsigned)grid), dim3(512), LDS_BYTES, as_stream(stream), G);
   }
   else if constexpr (PA == 4) {
+    launched = "gemm_h2q_kernel";
     hipLaunchKernelGGL(gemm_h2q_kernel<1>, dim3((unsigned)grid), dim3(512), LDS_BYTES, as_stream(stream), G);
   }
   else {
     // YT8M_X3_PIPE=0: the round-3 kernel (reads and requests issued in groups between the products)
     static const bool xpiped_env = getenv("YT8M_X3_PIPE") == nullptr || atoi(getenv("YT8M_X3_PIPE")) != 0;
     const bool xpiped = g_schedule_mode == 1 || (g_schedule_mode == 0 && xpiped_env);
+    launched = xpiped ? "gemm_x3q_kernel" : "gemm_x3_kernel";
     if (xpiped) {
       static DeviceOnce lds_once_xq;
       YT8M_HIP_CHECK(lds_once_xq.lds(reinterpret_cast<const void*>(gemm_x3q_kernel<(PA == 1) ? 1 : 3>), LDS_BYTES));
@@ -1696,7 +1701,7 @@ int x3_launch(int nprob, const yt8m_gemm_problem* probs, const float* rscale, co
     }
   }
   if (fix > 0 && !G.cnt) hipLaunchKernelGGL(x3_fixup_kernel, dim3((unsigned)fix * 16), dim3(256), 0, as_stream(stream), G);
-  return launch_status("gemm_x3_kernel");
+  return launch_status(launched);
 }
 }  // namespace
 
