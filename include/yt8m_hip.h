@@ -541,6 +541,46 @@ int yt8m_xent_bwd(const float* p, const void* labels, int label_dtype, const flo
                   const float* upstream_dev, float* dp, int64_t B, int64_t V, float eps, float upstream,
                   yt8m_stream_t stream);
 
+/* ---- losses: the batch-agreement losses (W/losses.py:281-356) and the pointwise ones (:76-108, :132-148); csrc/losses.hip -------
+ * p [B, V] float32 probabilities, labels uint8 {0,1} or float32, B <= 65535.  ce = -(y log(p+eps) + (1-y) log(1-p+eps)); every loss is
+ * mean_b sum_v (...), loss_out: device float[1].  A call enqueues its passes on `stream` and never synchronises: the batch statistics
+ * pass from kernel to kernel through `stats` (device floats, written by the forward call, read by the backward call), the
+ * per-workgroup partial sums through `workspace` (>= yt8m_batch_agreement_workspace_bytes(B, V), free again when the call's kernels
+ * have run).  The partial sums are added in a fixed order (fp64): a call on the same inputs gives the same bits.
+ * backward: dp = dL/dp * upstream * (upstream_dev ? *upstream_dev : 1)  (upstream_dev: device float[1]).
+ *
+ * BatchAgreementCrossEntropyLoss: min_pp = min(p y + 1 - y), max_np = max(p (1 - y)) over the batch; fn = [p < max_np] y,
+ * fp = [p > min_pp] (1 - y); n = sum of a mask, c = sum(p mask) / n; r = max(eps, max_np - min_pp);
+ * w = 1 + agreement (sigmoid(3 (c_fp - p) / r) (n_fp / batch_size) fn + sigmoid(3 (p - c_fn) / r) (n_fn / batch_size) fp); loss = mean_b
+ * sum_v w ce.  batch_size is --batch_size as a float, not B.  w is differentiated: through p, through both centres and through r
+ * (into the positions of the two extrema, ties sharing equally); masks and counts are constants.  No false negative or no false
+ * positive in the batch: c = 0 / 0, loss and dp are NaN, as in the reference.  stats: float[YT8M_BA_STATS_FLOATS]; [0] min_pp,
+ * [1] max_np, [2] c_fn, [3] c_fp, [14] n_fn, [15] n_fp, [16] / [17] the number of elements at max_np / min_pp (the rest: csrc/losses.hip).
+ *
+ * TopKBatchAgreementCrossEntropyLoss: tau_b = 20th largest value of row b, equal values counted as often as they occur (V >= 20 else
+ * YT8M_E_SHAPE), m = [p >= tau_b], min_pp = min(p y m + 1 - y m), fn = [p < tau_b] y, fp = [p > min_pp] (1 - y) m,
+ * w = 1 + agreement (fn + fp), a constant of the differentiation.  stats: float[1 + B] (min_pp, tau). */
+#define YT8M_BA_STATS_FLOATS 20
+int64_t yt8m_batch_agreement_workspace_bytes(int64_t B, int64_t V);
+int yt8m_batch_agreement_fwd(const float* p, const void* labels, int label_dtype, float* loss_out, float* stats, int64_t B, int64_t V,
+                             float eps, float agreement, float batch_size, void* workspace, yt8m_stream_t stream);
+int yt8m_batch_agreement_bwd(const float* p, const void* labels, int label_dtype, const float* stats, const float* upstream_dev,
+                             float* dp, int64_t B, int64_t V, float eps, float upstream, yt8m_stream_t stream);
+int yt8m_topk_batch_agreement_fwd(const float* p, const void* labels, int label_dtype, float* loss_out, float* stats, int64_t B,
+                                  int64_t V, float eps, float agreement, void* workspace, yt8m_stream_t stream);
+int yt8m_topk_batch_agreement_bwd(const float* p, const void* labels, int label_dtype, const float* stats, const float* upstream_dev,
+                                  float* dp, int64_t B, int64_t V, float eps, float agreement, float upstream, yt8m_stream_t stream);
+/* Pointwise losses, value and / or gradient in one pass (dp may be NULL in fwd_bwd; workspace >= yt8m_pointwise_loss_workspace_bytes):
+ *   WEIGHTED_XENT  -(c0 y log(p+eps) + c1 (1-y) log(1-p+eps))   c0 / c1: --false_negative_punishment / --false_positive_punishment
+ *   MSE            (y - p)^2                                     (c0, c1, eps unused)
+ *   HINGE          max(0, c0 - (2y - 1) p), c0 = b; the subgradient at the kink is 0 as tf.maximum's  (c1, eps unused) */
+enum yt8m_pointwise_loss { YT8M_LOSS_WEIGHTED_XENT = 0, YT8M_LOSS_MSE = 1, YT8M_LOSS_HINGE = 2 };
+int64_t yt8m_pointwise_loss_workspace_bytes(int64_t B, int64_t V);
+int yt8m_pointwise_loss_fwd_bwd(int kind, const float* p, const void* labels, int label_dtype, float* loss_out, float* dp, int64_t B,
+                                int64_t V, float c0, float c1, float eps, float upstream, void* workspace, yt8m_stream_t stream);
+int yt8m_pointwise_loss_bwd(int kind, const float* p, const void* labels, int label_dtype, const float* upstream_dev, float* dp,
+                            int64_t B, int64_t V, float c0, float c1, float eps, float upstream, yt8m_stream_t stream);
+
 /* ---- optimiser slice of build_graph (W/train.py:435-466, W/utils.py:164-174, tf.train.AdamOptimizer)
  * The parameters live in one flat fp32 arena; `chunks` (device, int32[nchunks*4]) describes it as
  * {offset, count, tensor_id, unused} with no chunk spanning two tensors; count <= 4096.

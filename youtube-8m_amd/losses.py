@@ -1,10 +1,25 @@
-"""Label losses; names, flags and semantics mirror W/losses.py (W = /root/reference/youtube-8m-wangheda)."""
+"""Label losses; names, flags and semantics mirror W/losses.py (W = /root/reference/youtube-8m-wangheda).
+
+Here: CrossEntropyLoss, WeightedCrossEntropyLoss, MeanSquareErrorLoss, HingeLoss, MultiTaskCrossEntropyLoss,
+BatchAgreementCrossEntropyLoss and TopKBatchAgreementCrossEntropyLoss.  Every one runs as HIP kernels (csrc/elementwise.hip for the
+plain cross entropy, csrc/losses.hip for the others), forward and backward.
+
+Left out of W/losses.py:
+  PairwiseHingeLoss, MixedLoss                                  they unstack the batch by --batch_size and draw TF random integers
+                                                                (tf.random_uniform, dtype int32), for which this repository has no
+                                                                parity definition.
+  SoftmaxLoss, MultiTaskCrossEntropyAndSoftmaxLoss              a row-softmax loss is a kernel of its own: the next step.
+  MultiTaskDivergenceCrossEntropyLoss,                          they take [batch, models, classes] support predictions from plugins
+  MultiTaskDivergenceCrossEntropyAndMSELoss                     this repository does not have.
+--label_loss with one of these names ends in StopIteration at train.find_class_by_name, as any unknown name does."""
 import torch
 
 from . import ops
 from .flags import FLAGS, DEFINE_float, DEFINE_string, DEFINE_integer, DEFINE_bool
 
 # W/losses.py:22-44
+DEFINE_float("false_negative_punishment", 1.0, "punishment constant to 1 classified to 0")
+DEFINE_float("false_positive_punishment", 1.0, "punishment constant to 0 classified to 1")
 DEFINE_integer("num_classes", 4716, "number of classes")
 DEFINE_float("support_loss_percent", 0.1, "the part that support loss (in multi-task scenario) take in the whole loss function.")
 DEFINE_string("support_type", "vertical", "type of support label, vertical or frequent or vertical,frequent.")
@@ -12,6 +27,7 @@ DEFINE_integer("num_supports", 25, "Number of total support categories.")
 DEFINE_integer("num_verticals", 25, "Number of total vertical categories.")
 DEFINE_integer("num_frequents", 200, "Number of total frequent categories.")
 DEFINE_string("vertical_file", "resources/vertical.tsv", "Location of label-vertical mapping file.")
+DEFINE_float("batch_agreement", 0.1, "the batch_agreement parameter")
 DEFINE_bool("label_smoothing", False, "whether do label smoothing")
 DEFINE_float("label_smoothing_epsilon", 0.1, "whether do label smoothing")
 
@@ -64,6 +80,59 @@ class CrossEntropyLoss(BaseLoss):
     def calculate_loss(self, predictions, labels, weights=None, scale=1.0, **unused_params):
         y = smoothing(labels) if FLAGS.label_smoothing else labels
         return ops.cross_entropy(predictions, y, weights, scale)
+
+
+class WeightedCrossEntropyLoss(BaseLoss):
+    """W/losses.py:76-93: cross entropy whose two terms carry --false_negative_punishment and --false_positive_punishment."""
+
+    def calculate_loss(self, predictions, labels, **unused_params):
+        y = smoothing(labels) if FLAGS.label_smoothing else labels
+        return ops.pointwise_loss(predictions, y, "weighted_xent", FLAGS.false_negative_punishment, FLAGS.false_positive_punishment)
+
+
+class MeanSquareErrorLoss(BaseLoss):
+    """W/losses.py:96-108: mean_b sum_v (y - p)^2."""
+
+    def calculate_loss(self, predictions, labels, **unused_params):
+        y = smoothing(labels) if FLAGS.label_smoothing else labels
+        return ops.pointwise_loss(predictions, y, "mse")
+
+
+class HingeLoss(BaseLoss):
+    """W/losses.py:132-148: mean_b sum_v max(0, b - (2y - 1) p); the subgradient at the kink is 0 (tf.maximum hands a tie's
+    gradient to its first argument, the zeros).  No label smoothing, as in the reference."""
+
+    def calculate_loss(self, predictions, labels, b=1.0, **unused_params):
+        return ops.pointwise_loss(predictions, labels, "hinge", b)
+
+
+class BatchAgreementCrossEntropyLoss(BaseLoss):
+    """W/losses.py:281-320: cross entropy that weighs up the elements which break the batch-wide order.  With min_pp the smallest
+    prediction of a positive and max_np the largest of a negative in the whole batch, a positive below max_np is a false negative,
+    a negative above min_pp a false positive; n and c are the number and the mean prediction of either set, r = max(eps, max_np -
+    min_pp), and
+
+        w = 1 + a (sigmoid(3 (c_fp - p) / r) (n_fp / N) fn + sigmoid(3 (p - c_fn) / r) (n_fn / N) fp),   loss = mean_b sum_v w ce
+
+    with a = --batch_agreement and N = float(--batch_size): the flag, not the number of rows (under data parallelism the statistics
+    are those of the local batch, as with batch normalisation, and N is still the flag).  The reference puts no stop_gradient on w:
+    the gradient also runs through w's own p, through both centres and through r into the positions of the two extrema (ties share
+    it equally); the comparisons and counts carry none.  A batch without a false negative or without a false positive has c = 0/0:
+    the loss is NaN there as it is in the reference (a perfectly separated batch ends the run; nothing is substituted).  Label
+    smoothing and `weights` do not apply (the latter are swallowed like every unused parameter)."""
+
+    def calculate_loss(self, predictions, labels, **unused_params):
+        return ops.batch_agreement_cross_entropy(predictions, labels, FLAGS.batch_agreement, float(FLAGS.batch_size))
+
+
+class TopKBatchAgreementCrossEntropyLoss(BaseLoss):
+    """W/losses.py:322-356: with tau_b the 20th largest prediction of row b (k is 20 whatever `topk` says, as in the reference),
+    m = [p >= tau_b] and min_pp the smallest prediction of a positive inside its row's top 20 (1 if there is none), a positive below
+    tau_b is a false negative and a negative inside the top 20 and above min_pp a false positive: w = 1 + a (fn + fp) under
+    stop_gradient, loss = mean_b sum_v w ce.  Fewer than 20 classes: ValueError (tf.nn.top_k refuses them)."""
+
+    def calculate_loss(self, predictions, labels, topk=20, **unused_params):
+        return ops.topk_batch_agreement_cross_entropy(predictions, labels, FLAGS.batch_agreement)
 
 
 class MultiTaskLoss(BaseLoss):

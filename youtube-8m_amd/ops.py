@@ -1646,3 +1646,155 @@ class _Xent(torch.autograd.Function):
 
 def cross_entropy(p, labels, weights=None, scale=1.0):
     return _Xent.apply(p, labels, weights, float(scale))
+
+
+BA_STATS_FLOATS = 20                  # YT8M_BA_STATS_FLOATS
+BA_STATS = {"min_pp": 0, "max_np": 1, "c_fn": 2, "c_fp": 3, "n_fn": 14, "n_fp": 15, "ties_max_np": 16, "ties_min_pp": 17}
+BA_TOPK = 20                          # W/losses.py:331
+POINTWISE_LOSSES = {"weighted_xent": 0, "mse": 1, "hinge": 2}      # enum yt8m_pointwise_loss
+
+
+def _loss_args(p, labels, min_classes=1):
+    """(p, labels, label dtype code, B, V) of a [B, V] loss; shape errors come before the device check (they need no device)."""
+    if p.dim() != 2:
+        raise ValueError("expected [batch, classes] predictions, got %s" % (tuple(p.shape),))
+    B, V = p.shape
+    if tuple(labels.shape) != (B, V):
+        raise ValueError("labels shape %s != predictions shape %s" % (tuple(labels.shape), (B, V)))
+    if V < min_classes:
+        raise ValueError("%d classes: top_k(k = %d) needs at least %d" % (V, min_classes, min_classes))
+    _dev(p, labels)
+    lab, ldt = _labels_arg(labels)
+    return _f32c(p), lab, ldt, B, V
+
+
+def _loss_workspace(nbytes, device):
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
+
+
+def batch_agreement_fwd(p, labels, agreement, batch_size, eps=XENT_EPS):
+    """BatchAgreementCrossEntropyLoss (W/losses.py:281-320): (loss, stats).  stats: the batch statistics, BA_STATS_FLOATS device
+    floats (BA_STATS names the readable ones) that batch_agreement_bwd takes."""
+    p, lab, ldt, B, V = _loss_args(p, labels)
+    L = _lib.lib()
+    ws = _loss_workspace(L.yt8m_batch_agreement_workspace_bytes(B, V), p.device)
+    loss = torch.empty((), dtype=torch.float32, device=p.device)
+    stats = torch.empty(BA_STATS_FLOATS, dtype=torch.float32, device=p.device)
+    _lib.check(L.yt8m_batch_agreement_fwd(_p(p), _p(lab), ldt, _p(loss), _p(stats), B, V, eps, agreement, batch_size, _p(ws), _stream()))
+    return loss, stats
+
+
+def batch_agreement_bwd(p, labels, stats, upstream_dev, eps=XENT_EPS, upstream=1.0):
+    p, lab, ldt, B, V = _loss_args(p, labels)
+    _dev(stats, upstream_dev)
+    dp = torch.empty_like(p)
+    up = None if upstream_dev is None else _f32c(upstream_dev)
+    _lib.check(_lib.lib().yt8m_batch_agreement_bwd(_p(p), _p(lab), ldt, _p(_f32c(stats)), _p(up), _p(dp), B, V, eps, upstream, _stream()))
+    return dp
+
+
+def topk_batch_agreement_fwd(p, labels, agreement, eps=XENT_EPS):
+    """TopKBatchAgreementCrossEntropyLoss (W/losses.py:322-356): (loss, stats); stats = min_pp, then the rows' thresholds (1 + B)."""
+    p, lab, ldt, B, V = _loss_args(p, labels, min_classes=BA_TOPK)
+    L = _lib.lib()
+    ws = _loss_workspace(L.yt8m_batch_agreement_workspace_bytes(B, V), p.device)
+    loss = torch.empty((), dtype=torch.float32, device=p.device)
+    stats = torch.empty(1 + B, dtype=torch.float32, device=p.device)
+    _lib.check(L.yt8m_topk_batch_agreement_fwd(_p(p), _p(lab), ldt, _p(loss), _p(stats), B, V, eps, agreement, _p(ws), _stream()))
+    return loss, stats
+
+
+def topk_batch_agreement_bwd(p, labels, stats, upstream_dev, agreement, eps=XENT_EPS, upstream=1.0):
+    p, lab, ldt, B, V = _loss_args(p, labels, min_classes=BA_TOPK)
+    _dev(stats, upstream_dev)
+    dp = torch.empty_like(p)
+    up = None if upstream_dev is None else _f32c(upstream_dev)
+    _lib.check(_lib.lib().yt8m_topk_batch_agreement_bwd(_p(p), _p(lab), ldt, _p(_f32c(stats)), _p(up), _p(dp), B, V, eps, agreement,
+                                                        upstream, _stream()))
+    return dp
+
+
+def pointwise_loss_fwd(p, labels, kind, c0=1.0, c1=1.0, want_dp=False, eps=XENT_EPS, upstream=1.0):
+    p, lab, ldt, B, V = _loss_args(p, labels)
+    L = _lib.lib()
+    ws = _loss_workspace(L.yt8m_pointwise_loss_workspace_bytes(B, V), p.device)
+    loss = torch.empty((), dtype=torch.float32, device=p.device)
+    dp = torch.empty_like(p) if want_dp else None
+    _lib.check(L.yt8m_pointwise_loss_fwd_bwd(POINTWISE_LOSSES[kind], _p(p), _p(lab), ldt, _p(loss), _p(dp), B, V, c0, c1, eps, upstream,
+                                             _p(ws), _stream()))
+    return loss, dp
+
+
+def pointwise_loss_bwd(p, labels, kind, upstream_dev, c0=1.0, c1=1.0, eps=XENT_EPS, upstream=1.0):
+    p, lab, ldt, B, V = _loss_args(p, labels)
+    _dev(upstream_dev)
+    dp = torch.empty_like(p)
+    up = None if upstream_dev is None else _f32c(upstream_dev)
+    _lib.check(_lib.lib().yt8m_pointwise_loss_bwd(POINTWISE_LOSSES[kind], _p(p), _p(lab), ldt, _p(up), _p(dp), B, V, c0, c1, eps, upstream,
+                                                  _stream()))
+    return dp
+
+
+class _BatchAgreementXent(torch.autograd.Function):
+    """Saves p and the 20 floats of batch statistics; the backward pass recomputes dL/dp from (p, y) and them, with the upstream
+    scalar read on the device: no host sync, nothing of size [B, V] kept beyond p."""
+
+    @staticmethod
+    def forward(ctx, p, labels, agreement, batch_size):
+        loss, stats = batch_agreement_fwd(p, labels, agreement, batch_size)
+        ctx.save_for_backward(p, stats)
+        ctx.labels = labels
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        p, stats = ctx.saved_tensors
+        return batch_agreement_bwd(p, ctx.labels, stats, dloss.reshape(1)), None, None, None
+
+
+class _TopKBatchAgreementXent(torch.autograd.Function):
+    """Saves p, min_pp and the rows' thresholds (1 + B floats)."""
+
+    @staticmethod
+    def forward(ctx, p, labels, agreement):
+        loss, stats = topk_batch_agreement_fwd(p, labels, agreement)
+        ctx.save_for_backward(p, stats)
+        ctx.labels, ctx.agreement = labels, agreement
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        p, stats = ctx.saved_tensors
+        return topk_batch_agreement_bwd(p, ctx.labels, stats, dloss.reshape(1), ctx.agreement), None, None
+
+
+class _PointwiseLoss(torch.autograd.Function):
+    """WeightedCrossEntropyLoss / MeanSquareErrorLoss / HingeLoss (W/losses.py:76-108, 132-148): mean_b sum_v f(p, y); the backward
+    pass recomputes f' from (p, y)."""
+
+    @staticmethod
+    def forward(ctx, p, labels, kind, c0, c1):
+        loss, _ = pointwise_loss_fwd(p, labels, kind, c0, c1)
+        ctx.save_for_backward(p)
+        ctx.args = labels, kind, c0, c1
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (p,) = ctx.saved_tensors
+        labels, kind, c0, c1 = ctx.args
+        return pointwise_loss_bwd(p, labels, kind, dloss.reshape(1), c0, c1), None, None, None, None
+
+
+def batch_agreement_cross_entropy(p, labels, agreement, batch_size):
+    """batch_size: --batch_size as the reference takes it (float(FLAGS.batch_size)), whatever the number of rows of p."""
+    return _BatchAgreementXent.apply(p, labels, float(agreement), float(batch_size))
+
+
+def topk_batch_agreement_cross_entropy(p, labels, agreement):
+    return _TopKBatchAgreementXent.apply(p, labels, float(agreement))
+
+
+def pointwise_loss(p, labels, kind, c0=1.0, c1=1.0):
+    """kind: "weighted_xent" (c0 / c1 = false negative / false positive punishment), "mse" or "hinge" (c0 = b)."""
+    return _PointwiseLoss.apply(p, labels, kind, float(c0), float(c1))

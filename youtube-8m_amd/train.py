@@ -298,6 +298,8 @@ def build_graph(model, label_loss_fn=None, batch_size=None, **kw):
         kw["augmenter_class"] = find_class_by_name(FLAGS.data_augmenter, [data_augmentation])
     if "transformer_class" not in kw:                             # W/train.py:707 (and W/eval.py, W/inference.py the same way)
         kw["transformer_class"] = find_class_by_name(FLAGS.feature_transformer, [feature_transform])
+    if label_loss_fn is None:                                     # W/train.py:705
+        label_loss_fn = find_class_by_name(FLAGS.label_loss, [losses])()
     return TrainGraph(model, label_loss_fn=label_loss_fn,
                       batch_size=batch_size or FLAGS.batch_size,
                       base_learning_rate=kw.pop("base_learning_rate", FLAGS.base_learning_rate),
