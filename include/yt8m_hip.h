@@ -513,6 +513,22 @@ enum yt8m_act { YT8M_ACT_SIGMOID = 0, YT8M_ACT_RELU = 1, YT8M_ACT_RELU6 = 2, YT8
 int yt8m_act_fwd_f32(int act, const float* x, float* y, int64_t n, yt8m_stream_t stream);
 /* dx = dy * act'(.) expressed from the OUTPUT y (sigmoid/tanh/relu/relu6/elu all admit it) */
 int yt8m_act_bwd_f32(int act, const float* y, const float* dy, float* dx, int64_t n, yt8m_stream_t stream);
+/* One "link" of the chain / distillchain plugins (csrc/chain_link.hip): relu or elu of a fully-connected pre-activation z [rows, cols],
+ * optional Gaussian noise, tf.nn.l2_normalize along the row -- yt8m_act_fwd_f32, yt8m_add_noise_f32 and yt8m_l2norm_fwd_f32 in one pass
+ * (W/all_video_models/distillchain_deep_combine_chain_model.py:27-56).  act: YT8M_ACT_RELU or YT8M_ACT_ELU only.
+ *   fwd, per row: a = act(z); stddev > 0: a += stddev * n with n the normal yt8m_add_noise_f32 adds at (seed, offset + row * cols + col);
+ *     ss = sum a^2, r = rsqrt(max(ss, eps)) (1 / sqrt(eps), rounded once on the host, when ss <= eps), y = a * r;
+ *     rinv[row] = r when ss > eps, else -r: the sign carries the eps branch to the backward pass.
+ *   bwd, per row: R = |rinv|, k = sum(y * dy); da = R * (dy - y * k) when rinv > 0, else R * dy (SURVEY.md Appendix G from the output);
+ *     dz = da * act'(z), act' from the INPUT: relu z > 0 (a tie at 0 gets 0), elu z > 0 ? 1 : exp(z).  The noise has no gradient.
+ *     Saved for it: z, y and rinv [rows]; eps is part of the signature for symmetry and is only validated.
+ * One wave per row; rows of up to 1024 columns are read once (16-byte accesses when cols % 4 == 0 and the operands are 16-byte
+ * aligned), wider rows twice.  Fixed summation order, no atomics.  Out of place.  An unsupported act, a null pointer, rows or cols <= 0,
+ * eps <= 0, stddev < 0 or offset < 0 is YT8M_E_BADARG and nothing is launched. */
+int yt8m_chain_link_fwd(int act, const float* z, float* y, float* rinv, int64_t rows, int64_t cols, float eps, float stddev,
+                        uint64_t seed, int64_t offset, yt8m_stream_t stream);
+int yt8m_chain_link_bwd(int act, const float* z, const float* y, const float* rinv, const float* dy, float* dz, int64_t rows,
+                        int64_t cols, float eps, yt8m_stream_t stream);
 /* out[n] (beta=0) or out[n] += (beta=1): sum over rows of X[rows, cols]; deterministic (fixed summation order).
  * workspace (optional, may be NULL): >= yt8m_colsum_workspace_bytes() device bytes let tall-and-narrow inputs
  * ([B*F, 8..64] attention / cluster logits) be split over rows so that the whole chip is used. */

@@ -357,7 +357,7 @@ class LstmAttentionMaxPoolingModel(models.BaseModel):
                 [model_input] + parts + [outputs], num_attentions, "attention-" + sub_scope, l2_penalty=l2_penalty)
         attention_weights = seq_ops.attention_weights(attention_activations, num_frames)   # [B,F,A]
         attention_outputs = seq_ops.pool_tn(attention_weights, outputs)                    # [B,A,H]
-        moe_predictions = self.sub_moe(attention_outputs, vocab_size, sub_scope="sub-moe")
+        moe_predictions = self.sub_moe(self._moe_input(attention_outputs), vocab_size, sub_scope="sub-moe")
         predictions = moe_predictions.view(-1, num_attentions, vocab_size)
         max_predictions = ops.frame_pool(predictions, "max")          # tf.reduce_max over the attentions
         return {"predictions": max_predictions}
@@ -365,6 +365,10 @@ class LstmAttentionMaxPoolingModel(models.BaseModel):
     def attention_parts(self, model_input, num_frames, l2_penalty):
         """(what the attention FC sees between the frames and the LSTM outputs, the bytes' frame scales if they were needed): nothing."""
         return [], None
+
+    def _moe_input(self, attention_outputs):
+        """What sub_moe reads, from the attention outputs [B,A,H]: the attention outputs."""
+        return attention_outputs
 
     def sub_moe(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", **unused_params):
         num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
@@ -471,17 +475,9 @@ class CnnDeepCombineChainModel(models.BaseModel):
         mean_relu = video_level_models.fully_connected(mean_input, relu_cells, sub_scope + "mean-relu", activation="relu",
                                                        l2_penalty=l2_penalty)
         relu_layers = [ops.l2_normalize(mean_relu)]
-        filters = dict(num_filters=[relu_cells, relu_cells, relu_cells * 2], filter_sizes=[1, 2, 3])
 
         def pooled_cnn(scope):
-            if frames is not None:
-                fvars = _cnn_filters(D, scope, l2_penalty=l2_penalty, **filters)
-                if sum(filters["num_filters"]) % 4 == 0:                          # pooled in time-major order, sparse weight gradient
-                    return ops.l2_normalize(seq_ops.u8_cnn_maxpool(frames, fvars))
-                cnn_output = seq_ops.u8_cnn(frames, fvars)
-            else:
-                cnn_output = self.cnn(model_input, sub_scope=scope, l2_penalty=l2_penalty, **filters)
-            return ops.l2_normalize(ops.frame_pool(cnn_output, "max"))      # reduce_max over ALL max_frames rows, as the reference
+            return self._pooled_cnn(model_input, frames, scope, relu_cells, l2_penalty)
 
         next_input = pooled_cnn(sub_scope + "cnn0")
         frozen = 0
@@ -497,6 +493,19 @@ class CnnDeepCombineChainModel(models.BaseModel):
             frozen = 0 if mean_input.requires_grad else D           # the mean frame in front of the stage's input is data
         main_predictions = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "-main", frozen_cols=frozen)
         return {"predictions": main_predictions, "support_predictions": torch.cat(support_predictions, dim=1)}
+
+    def _pooled_cnn(self, model_input, frames, scope, relu_cells, l2_penalty):
+        """l2_normalize(reduce_max over the frames of the chain's CNN under `scope`) [B, 4 relu_cells]; frames: the byte image of the
+        reader's bytes (seq_ops.U8FrameImages) or None for float frames."""
+        filters = dict(num_filters=[relu_cells, relu_cells, relu_cells * 2], filter_sizes=[1, 2, 3])
+        if frames is not None:
+            fvars = _cnn_filters(model_input.shape[2], scope, l2_penalty=l2_penalty, **filters)
+            if sum(filters["num_filters"]) % 4 == 0:                          # pooled in time-major order, sparse weight gradient
+                return ops.l2_normalize(seq_ops.u8_cnn_maxpool(frames, fvars))
+            cnn_output = seq_ops.u8_cnn(frames, fvars)
+        else:
+            cnn_output = self.cnn(model_input, sub_scope=scope, l2_penalty=l2_penalty, **filters)
+        return ops.l2_normalize(ops.frame_pool(cnn_output, "max"))      # reduce_max over ALL max_frames rows, as the reference
 
     def sub_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", frozen_cols=0, **unused_params):
         num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
@@ -574,6 +583,83 @@ class DistillchainLstmCnnDeepCombineChainModel(LstmCnnDeepCombineChainModel):
         distill_relu = video_level_models.fully_connected(distillation_predictions.to(torch.float32), FLAGS.distillchain_relu_cells,
                                                           "distillrelu", activation="relu", l2_penalty=l2_penalty)
         return [ops.l2_normalize(distill_relu)], True
+
+
+def _distill_link(distillation_predictions, relu_cells, l2_penalty, scope="distillrelu"):
+    """l2_normalize(relu(FC(distillation_predictions))) [B, relu_cells] under `scope`, as one link (ops.chain_link): what the
+    Distillchain plugins below concatenate into their classifiers' inputs."""
+    assert distillation_predictions is not None, "distillation feature must be used"
+    distill_activation = video_level_models.fully_connected(distillation_predictions.to(torch.float32), relu_cells, scope,
+                                                            l2_penalty=l2_penalty)
+    return ops.chain_link(distill_activation, "relu")
+
+
+class DistillchainLstmParallelFinaloutputModel(LstmParallelFinaloutputModel):
+    """W/all_frame_models/distillchain_lstm_parallel_finaloutput_model.py:13-88: LstmParallelFinaloutputModel whose head input is
+    [final h of every layer of every stack | distill_norm] ("distillrelu", --distillchain_relu_cells wide, over another model's
+    predictions).  Reads bytes on its parent's terms (_parallel_stacks)."""
+
+    def create_model(self, model_input, vocab_size, num_frames, distillation_predictions=None, l2_penalty=1e-8, **unused_params):
+        distill_norm = _distill_link(distillation_predictions, FLAGS.distillchain_relu_cells, l2_penalty)
+        number_of_layers = FLAGS.lstm_layers
+        lstm_sizes = [int(v) for v in str(FLAGS.lstm_cells).split(",")]
+        feature_sizes = [int(v) for v in str(FLAGS.feature_sizes).split(",")]
+        states = [h for _, finals in _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, number_of_layers) for _, h in finals]
+        final_state = torch.cat(states + [distill_norm], dim=1)
+        return _head()().create_model(model_input=final_state, original_input=model_input, vocab_size=vocab_size,
+                                      **unused_params)
+
+
+class DistillchainCnnDeepCombineChainModel(CnnDeepCombineChainModel):
+    """W/all_frame_models/distillchain_cnn_deep_combine_chain_model.py:10-148: relu_layers starts [distill_norm, mean_relu_norm] and every
+    stage -- stage 0 included -- reads [normalized_cnn_output] + relu_layers: no mean_input columns in front, unlike this build's
+    CnnDeepCombineChainModel.  distillrelu is --distillchain_relu_cells wide; mean-relu and relu-<l> go through ops.chain_link too.  The
+    byte path (seq_ops.U8FrameImages, u8_cnn_maxpool) under the parent's conditions."""
+
+    def create_model(self, model_input, vocab_size, num_frames, num_mixtures=None, l2_penalty=1e-8, sub_scope="",
+                     original_input=None, distillation_predictions=None, **unused_params):
+        num_layers = FLAGS.deep_chain_layers
+        relu_cells = FLAGS.deep_chain_relu_cells
+        relu_layers = [_distill_link(distillation_predictions, FLAGS.distillchain_relu_cells, l2_penalty)]
+        model_input, u8 = _bytes_or_floats(model_input, num_frames, lambda q: seq_ops.u8_cnn_supported(q) and
+                                           seq_ops.u8_attention_supported(q, 1))
+        frames = seq_ops.U8FrameImages(model_input, num_frames) if u8 else None   # one byte image for every CNN of the chain
+        mean_input = _mean_frame(model_input, num_frames)
+        mean_activation = video_level_models.fully_connected(mean_input, relu_cells, sub_scope + "mean-relu", l2_penalty=l2_penalty)
+        relu_layers.append(ops.chain_link(mean_activation, "relu"))
+        normalized_cnn_output = self._pooled_cnn(model_input, frames, sub_scope + "cnn0", relu_cells, l2_penalty)
+        next_input = torch.cat([normalized_cnn_output] + relu_layers, dim=1)
+        support_predictions = []
+        for layer in range(num_layers):
+            sub_prediction = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "prediction-%d" % layer)
+            support_predictions.append(sub_prediction)
+            sub_activation = video_level_models.fully_connected(sub_prediction, relu_cells, sub_scope + "relu-%d" % layer,
+                                                                l2_penalty=l2_penalty)
+            relu_layers.append(ops.chain_link(sub_activation, "relu"))
+            normalized_cnn_output = self._pooled_cnn(model_input, frames, sub_scope + "cnn%d" % (layer + 1), relu_cells, l2_penalty)
+            next_input = torch.cat([normalized_cnn_output] + relu_layers, dim=1)
+        main_predictions = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "-main")
+        return {"predictions": main_predictions, "support_predictions": torch.cat(support_predictions, dim=1)}
+
+
+class DistillchainLstmAttentionMaxPoolingModel(LstmAttentionMaxPoolingModel):
+    """W/all_frame_models/distillchain_lstm_attention_max_pooling_model.py:10-116: LstmAttentionMaxPoolingModel whose sub_moe reads
+    [attention_outputs | distill_norm tiled over the --lstm_attentions rows of a video] ("distillrelu", --distillchain_relu_cells wide).
+    The rest is the parent's path, bytes included."""
+
+    def create_model(self, model_input, vocab_size, num_frames, num_mixtures=None, l2_penalty=1e-8, sub_scope="",
+                     distillation_predictions=None, original_input=None, **unused_params):
+        self._distill_norm = _distill_link(distillation_predictions, FLAGS.distillchain_relu_cells, l2_penalty)
+        try:
+            return super().create_model(model_input, vocab_size, num_frames, num_mixtures=num_mixtures, l2_penalty=l2_penalty,
+                                        sub_scope=sub_scope, original_input=original_input, **unused_params)
+        finally:
+            self._distill_norm = None
+
+    def _moe_input(self, attention_outputs):
+        B, A, _ = attention_outputs.shape
+        tiled_distill_norm = self._distill_norm[:, None, :].expand(B, A, self._distill_norm.shape[1])
+        return torch.cat([attention_outputs, tiled_distill_norm], dim=2)
 
 
 def _bn_vars(scope, n):

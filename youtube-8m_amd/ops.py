@@ -1238,6 +1238,55 @@ def l2_normalize(x, eps=1e-12):
     return _L2Norm.apply(x, eps)
 
 
+CHAIN_LINK_FUSED = os.environ.get("YT8M_CHAIN_LINK_FUSED", "1") != "0"   # 0: chain_link composes the three existing ops (A/B runs, tests)
+
+
+class _ChainLink(torch.autograd.Function):
+    """csrc/chain_link.hip: relu / elu, optional noise and l2_normalize of a pre-activation in one pass each way.  Saved for backward:
+    z (the linear's output), y (the next stage's input) and rinv [rows]."""
+
+    @staticmethod
+    def forward(ctx, z, kind, stddev, seed, offset, eps):
+        z = _f32c(z)
+        _dev(z)
+        cols = z.shape[-1]
+        rows = z.numel() // max(cols, 1)
+        y = torch.empty_like(z)
+        rinv = torch.empty(rows, dtype=torch.float32, device=z.device)
+        _lib.check(_lib.lib().yt8m_chain_link_fwd(ACT[kind], _p(z), _p(y), _p(rinv), rows, cols, float(eps), float(stddev), int(seed),
+                                                  int(offset), _stream()))
+        ctx.kind, ctx.eps = kind, float(eps)
+        ctx.save_for_backward(z, y, rinv)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, y, rinv = ctx.saved_tensors
+        dy = _f32c(dy)
+        dz = torch.empty_like(z)
+        _lib.check(_lib.lib().yt8m_chain_link_bwd(ACT[ctx.kind], _p(z), _p(y), _p(rinv), _p(dy), _p(dz), rinv.numel(), z.shape[-1],
+                                                  ctx.eps, _stream()))
+        return dz, None, None, None, None, None
+
+
+def chain_link(z, kind="relu", noise_level=None, seed=None, offset=0, eps=1e-12, graph=None):
+    """l2_normalize(add_noise(activation(z, kind), noise_level)) on the last axis: one "link" of the chain / distillchain plugins
+    (W/all_video_models/distillchain_deep_combine_chain_model.py:27-56).  kind: "relu" or "elu".  noise_level None or 0: no noise and
+    no seed is taken; otherwise seed None takes the next key of the graph's random stream, as add_noise does.
+    YT8M_CHAIN_LINK_FUSED=0 (read at import): the three existing ops instead of the fused kernel."""
+    if kind not in ("relu", "elu"):
+        raise ValueError("chain_link: kind must be relu or elu, got %r" % (kind,))
+    noisy = noise_level is not None and float(noise_level) != 0.0
+    if noisy and seed is None:
+        seed = (graph or get_default_graph()).next_random_seed()
+    if not CHAIN_LINK_FUSED:
+        a = activation(z, kind)
+        if noisy:
+            a = add_noise(a, noise_level, seed, offset)
+        return l2_normalize(a, eps)
+    return _ChainLink.apply(z, kind, float(noise_level) if noisy else 0.0, seed if noisy else 0, offset, eps)
+
+
 class _MoeHead(torch.autograd.Function):
     """MoE block of W/all_video_models/moe_model.py:40-64: two GEMMs + mixing kernel; backward per Appendix G."""
 

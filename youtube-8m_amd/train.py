@@ -30,7 +30,10 @@ DEFINE_string("feature_names", "mean_rgb", "Name of the feature to use for train
 DEFINE_string("feature_sizes", "1024", "Length of the feature vectors.")
 # new: raw uint8 frame blocks reach models that fold the input transform into their first GEMM (NetVLAD)
 DEFINE_bool("fold_dequant", True, "Hand raw uint8 frames to models that declare accepts_quantized_input.")
-# W/train.py:53-64 distillation inputs: a second model's predictions arrive with the batch
+# W/train.py:53-64 distillation inputs: a second model's predictions arrive with the batch.
+# --distillation_as_input hands them to create_model as distillation_predictions; the plugins that read them (the others ignore the
+# keyword): DistillchainDeepCombineChainModel (video level), DistillchainLstmParallelFinaloutputModel, DistillchainCnnDeepCombineChainModel,
+# DistillchainLstmAttentionMaxPoolingModel, DistillchainLstmCnnDeepCombineChainModel, DistillchainMultiscaleCnnLstmModel.
 DEFINE_bool("distillation_features", False, "If set, *DistillationFeatureReader will be used, the feature must contains the "
             "added distillation_predictions features.")
 DEFINE_integer("distillation_type", 0, "Type of distillation, options are 1 and 2.")

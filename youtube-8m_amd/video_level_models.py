@@ -123,3 +123,33 @@ class DeepCombineChainModel(models.BaseModel):
             model_input = ops.dropout(model_input, 1.0 if keep_prob is None else keep_prob)
         return moe_block(model_input, vocab_size, num_mixtures, l2_penalty, "gates-" + sub_scope, "experts-" + sub_scope,
                          frozen_cols=frozen_cols)
+
+
+class DistillchainDeepCombineChainModel(DeepCombineChainModel):
+    """W/all_video_models/distillchain_deep_combine_chain_model.py:9-96: DeepCombineChainModel whose chain starts from
+    [model_input | distill_norm], distill_norm = the l2-normalised relu projection (scope sub_scope + "distillrelu",
+    --deep_chain_relu_cells wide here) of another model's predictions.  Every relu -> (noise) -> l2norm is one ops.chain_link."""
+
+    def create_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="",
+                     original_input=None, dropout=False, keep_prob=None, noise_level=None, distillation_predictions=None,
+                     num_frames=None, **unused_params):
+        assert distillation_predictions is not None, "distillation feature must be used"
+        num_layers = FLAGS.deep_chain_layers
+        relu_cells = FLAGS.deep_chain_relu_cells
+        relu_type = FLAGS.deep_chain_relu_type
+        distill_activation = fully_connected(distillation_predictions.to(torch.float32), relu_cells, sub_scope + "distillrelu",
+                                             l2_penalty=l2_penalty)
+        distill_norm = ops.chain_link(distill_activation, "relu")
+        next_input = torch.cat([model_input, distill_norm], dim=1)
+        # the model input stays in front of every stage's input: when it is data, no head computes a gradient for it
+        frozen = 0 if model_input.requires_grad else int(model_input.shape[1])
+        support_predictions = []
+        for layer in range(num_layers):
+            sub_prediction = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "prediction-%d" % layer,
+                                            dropout=dropout, keep_prob=keep_prob, noise_level=noise_level, frozen_cols=frozen)
+            sub_activation = fully_connected(sub_prediction, relu_cells, sub_scope + "relu-%d" % layer, l2_penalty=l2_penalty)
+            relu_norm = ops.chain_link(sub_activation, "elu" if relu_type == "elu" else "relu", noise_level)
+            next_input = torch.cat([next_input, relu_norm], dim=1)
+            support_predictions.append(sub_prediction)
+        main_predictions = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "-main", frozen_cols=frozen)
+        return {"predictions": main_predictions, "support_predictions": torch.cat(support_predictions, dim=1)}
