@@ -78,6 +78,38 @@ def _workspace(device):
     return ws
 
 
+_F32, _F32_BF16 = (torch.float32,), (torch.float32, torch.bfloat16)
+
+
+def _marshal(pre, M, N, K, a, lda, b, ldb, out, bias, beta, out_dtypes=_F32, new_dtype=torch.float32):
+    """One product of a grouped launch -> (yt8m_gemm_problem, its output, the temporaries the launch reads).  a / b: the tensors the
+    operand pointers come from (lda = ldb = 0 for operand images); a missing `out` is allocated as [M, N] of new_dtype.  The caller
+    keeps the temporaries (contiguous copies, the converted bias) referenced until its launch has returned.  pre: the family's name in
+    its error messages."""
+    if out is None:
+        if beta != 0.0:
+            raise ValueError("beta != 0 needs an output tensor")
+        out = torch.empty((M, N), dtype=new_dtype, device=a.device)
+    if out.dtype not in out_dtypes or tuple(out.shape) != (M, N) or (out.stride(1) != 1 and N != 1):
+        raise ValueError(pre + ": bad output tensor")
+    ldc = out.stride(0) if M > 1 else max(N, 1)
+    if bias is not None:
+        bias = _f32c(bias)
+        if bias.numel() != N:
+            raise ValueError("bias size mismatch")
+    pr = _lib.GemmProblem(M, N, K, a.data_ptr(), lda, b.data_ptr(), ldb, out.data_ptr(), ldc,
+                          bias.data_ptr() if bias is not None else None, float(beta))
+    return pr, out, (a, b, bias)
+
+
+def _chunks(per, probs, *side):
+    """Cuts a group into launches of at most `per` problems: yields (n, yt8m_gemm_problem[n], the same slice of every per-problem
+    side list)."""
+    for lo in range(0, len(probs), per):
+        part = probs[lo:lo + per]
+        yield (len(part), (_lib.GemmProblem * len(part))(*part)) + tuple(s[lo:lo + per] for s in side)
+
+
 def _problem(A, B, out, transA, transB, bias, beta):
     A, lda = _rowmajor2d(A)
     B, ldb = _rowmajor2d(B)
@@ -85,20 +117,7 @@ def _problem(A, B, out, transA, transB, bias, beta):
     K2, N = (B.shape[1], B.shape[0]) if transB else (B.shape[0], B.shape[1])
     if K != K2:
         raise ValueError("gemm: inner dimensions differ (%d vs %d)" % (K, K2))
-    if out is None:
-        if beta != 0.0:
-            raise ValueError("beta != 0 needs an output tensor")
-        out = torch.empty((M, N), dtype=torch.float32, device=A.device)
-    if out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (M, N) or (out.stride(1) != 1 and N != 1):
-        raise ValueError("gemm: bad output tensor")
-    ldc = out.stride(0) if M > 1 else max(N, 1)
-    if bias is not None:
-        bias = _f32c(bias)
-        if bias.numel() != N:
-            raise ValueError("bias size mismatch")
-    pr = _lib.GemmProblem(M, N, K, A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), ldc,
-                          bias.data_ptr() if bias is not None else None, float(beta))
-    return pr, out, (A, B, bias)
+    return _marshal("gemm", M, N, K, A, lda, B, ldb, out, bias, beta)
 
 
 X3 = os.environ.get("YT8M_GEMM_X3", "1") != "0"        # large fp32 products on the bf16 pipe (three-plane split, csrc/gemm_x3.hip)
@@ -135,25 +154,21 @@ def gemm_grouped(items, transA=False, transB=False, role=None):
     ta = int(bool(transA)) | (GEMM_ROLE_DW if (role == "dw" and transA and not transB) else 0) | (GEMM_ROLE_H2 if role == "h2" else 0)
     ws = _workspace(outs[0].device)
     lib = _lib.lib()
-    for lo in range(0, len(probs), 64):
-        part = probs[lo:lo + 64]
-        arr = (_lib.GemmProblem * len(part))(*part)
-        if not X3:
-            for i in range(0, len(part), 4):
-                sub = (_lib.GemmProblem * len(part[i:i + 4]))(*part[i:i + 4])
-                _lib.check(lib.yt8m_gemm_f32_grouped(int(transA), int(transB), len(part[i:i + 4]), sub, _p(ws), ws.numel() * 4, _stream()))
-            continue
-        nb = lib.yt8m_gemm_auto_scratch_bytes(ta, int(transB), len(part), arr)
+    if not X3:
+        for n, arr in _chunks(4, probs):
+            _lib.check(lib.yt8m_gemm_f32_grouped(int(transA), int(transB), n, arr, _p(ws), ws.numel() * 4, _stream()))
+        return outs
+    # absmaxA / absmaxB: operands whose maximum the caller already has on the device (a [1] float tensor holding it as float bits:
+    # yt8m_h2_absmax's form) skip their absmax pass when they take the h2 form
+    for n, arr, wa, wb in _chunks(64, probs, [it.get("absmaxA") for it in items], [it.get("absmaxB") for it in items]):
+        nb = lib.yt8m_gemm_auto_scratch_bytes(ta, int(transB), n, arr)
         img = torch.empty(nb, dtype=torch.uint8, device=outs[0].device) if nb else None
-        words = [(it.get("absmaxA"), it.get("absmaxB")) for it in items[lo:lo + 64]]
-        if any(a is not None or b is not None for a, b in words):
-            # operands whose maximum the caller already has on the device (a [1] float tensor holding it as float bits: yt8m_h2_absmax's
-            # form) skip their absmax pass when they take the h2 form
-            pa = (ctypes.c_void_p * len(part))(*[a.data_ptr() if a is not None else None for a, _ in words])
-            pb = (ctypes.c_void_p * len(part))(*[b.data_ptr() if b is not None else None for _, b in words])
-            _lib.check(lib.yt8m_gemm_auto_grouped_ex(ta, int(transB), len(part), arr, pa, pb, _p(ws), ws.numel() * 4, _p(img), nb, None, _stream()))
+        if any(w is not None for w in wa) or any(w is not None for w in wb):
+            pa = (ctypes.c_void_p * n)(*[w.data_ptr() if w is not None else None for w in wa])
+            pb = (ctypes.c_void_p * n)(*[w.data_ptr() if w is not None else None for w in wb])
+            _lib.check(lib.yt8m_gemm_auto_grouped_ex(ta, int(transB), n, arr, pa, pb, _p(ws), ws.numel() * 4, _p(img), nb, None, _stream()))
         else:
-            _lib.check(lib.yt8m_gemm_auto_grouped(ta, int(transB), len(part), arr, _p(ws), ws.numel() * 4, _p(img), nb, None, _stream()))
+            _lib.check(lib.yt8m_gemm_auto_grouped(ta, int(transB), n, arr, _p(ws), ws.numel() * 4, _p(img), nb, None, _stream()))
     return outs
 
 
@@ -227,102 +242,94 @@ def gemm_bf16_nt_grouped(items):
         N, K2 = B.shape
         if K != K2:
             raise ValueError("gemm_bf16_nt: inner dimensions differ (%d vs %d)" % (K, K2))
-        out = it.get("out")
-        beta = it.get("beta", 0.0)
-        if out is None:
-            if beta != 0.0:
-                raise ValueError("beta != 0 needs an output tensor")
-            out = torch.empty((M, N), dtype=torch.float32, device=A.device)
-        if out.dtype != torch.float32 or tuple(out.shape) != (M, N) or (out.stride(1) != 1 and N != 1):
-            raise ValueError("gemm_bf16_nt: bad output tensor")
-        bias = it.get("bias")
-        if bias is not None:
-            bias = _f32c(bias)
-        lda = A.stride(0) if M > 1 else max(K, 1)
-        ldb = B.stride(0) if N > 1 else max(K, 1)
-        ldc = out.stride(0) if M > 1 else max(N, 1)
-        probs.append(_lib.GemmProblem(M, N, K, A.data_ptr(), lda, B.data_ptr(), ldb, out.data_ptr(), ldc,
-                                      bias.data_ptr() if bias is not None else None, float(beta)))
+        pr, out, k = _marshal("gemm_bf16_nt", M, N, K, A, A.stride(0) if M > 1 else max(K, 1), B, B.stride(0) if N > 1 else max(K, 1),
+                              it.get("out"), it.get("bias"), it.get("beta", 0.0))
+        probs.append(pr)
         outs.append(out)
-        keep.append((A, B, bias))
-    arr = (_lib.GemmProblem * len(probs))(*probs)
+        keep.append(k)
     ws = _workspace(outs[0].device)
-    _lib.check(_lib.lib().yt8m_gemm_bf16_nt_grouped(len(probs), arr, _p(ws), ws.numel() * 4, _stream()))
+    for n, arr in _chunks(4, probs):                                # the library takes 1..4 problems per launch
+        _lib.check(_lib.lib().yt8m_gemm_bf16_nt_grouped(n, arr, _p(ws), ws.numel() * 4, _stream()))
     return outs
 
 
+# ---- operand images (csrc/gemm_x3.hip, csrc/x3_image.h): [32-row group][16-column K block][plane] of 2-byte elements -----------------
+def image_bytes(rows, K, planes):
+    """Bytes of a `planes`-plane operand image of a `rows` x `K` operand (a third of the library's three-plane size per plane)."""
+    return _lib.lib().yt8m_x3_image_bytes(rows, K) // 3 * planes
+
+
+def image_buffer(rows, K, planes, device, header=0, alloc=torch.empty):
+    """uint8 buffer for that image (at least 16 bytes: an empty operand still hands the kernels a pointer), `header` bytes in front."""
+    return alloc(header + max(image_bytes(rows, K, planes), 16), dtype=torch.uint8, device=device)
+
+
 class X3Image:
-    """Three-plane bf16 split of an fp32 matrix (csrc/gemm_x3.hip): `rows` x `K` logical shape, [row][ceil(K/16)][3][16] bf16."""
-    __slots__ = ("buf", "rows", "K")
+    """Operand image of an fp32 matrix: `rows` x `K` logical shape, `planes` planes per K block -- 3: the three-plane bf16 split
+    [row][ceil(K/16)][3][16] (x3_split), 1: its first plane alone (bf16_image); 2: see H2Image.  Each image family's product takes
+    its own plane count only."""
+    __slots__ = ("buf", "rows", "K", "planes")
 
-    def __init__(self, buf, rows, K):
-        self.buf, self.rows, self.K = buf, rows, K
+    def __init__(self, buf, rows, K, planes=3):
+        self.buf, self.rows, self.K, self.planes = buf, rows, K, planes
 
 
-def _x3_empty(rows, K, device):
-    n = _lib.lib().yt8m_x3_image_bytes(rows, K)
-    return X3Image(torch.empty(max(n, 16), dtype=torch.uint8, device=device), rows, K)
+def _image_empty(rows, K, planes, device):
+    return X3Image(image_buffer(rows, K, planes, device), rows, K, planes)
+
+
+def _weight_or_fresh_images(x, want_p, want_t, planes, scale, split):
+    """(image of x as an [R rows, K = C] operand, image of x^T as a [C rows, K = R] operand), None where not wanted: the resident image
+    of a weight matrix where the optimiser pass keeps one current (wimg.py), else a fresh buffer; `split` (yt8m_x3_split /
+    yt8m_bf16_image) fills the fresh ones in one pass over x."""
+    _dev(x)
+    x, ld = _rowmajor2d(x)
+    R, C = x.shape
+    imgs, fresh = [None, None], [None, None]
+    for trans, want, rows, K in ((0, want_p, R, C), (1, want_t, C, R)):
+        if want:
+            r = _wimg.resident_image(x, R, C, ld, trans, planes, scale)
+            imgs[trans] = X3Image(r[0], rows, K, planes) if r else _image_empty(rows, K, planes, x.device)
+            fresh[trans] = None if r else imgs[trans].buf
+    if fresh[0] is not None or fresh[1] is not None:
+        _lib.check(split(_p(x), R, C, ld, float(scale), _p(fresh[0]), _p(fresh[1]), _stream()))
+    return tuple(imgs)
 
 
 def x3_split(x, plain=True, trans=False, scale=1.0):
     """fp32 [R, C] -> (X3Image of x as an [R rows, K = C] operand or None, X3Image of x^T as a [C rows, K = R] operand or None),
     both from one pass over x (yt8m_x3_split)."""
-    _dev(x)
-    x, ld = _rowmajor2d(x)
-    R, C = x.shape
-    ip = it = None
-    if plain:                                                # a weight matrix whose image the optimiser pass keeps current (wimg.py)
-        r = _wimg.resident_image(x, R, C, ld, 0, 3, scale)
-        ip = X3Image(r[0], R, C) if r else None
-    if trans:
-        r = _wimg.resident_image(x, R, C, ld, 1, 3, scale)
-        it = X3Image(r[0], C, R) if r else None
-    mk_p, mk_t = plain and ip is None, trans and it is None
-    if mk_p:
-        ip = _x3_empty(R, C, x.device)
-    if mk_t:
-        it = _x3_empty(C, R, x.device)
-    if mk_p or mk_t:
-        _lib.check(_lib.lib().yt8m_x3_split(_p(x), R, C, ld, float(scale), _p(ip.buf) if mk_p else None, _p(it.buf) if mk_t else None,
-                                            _stream()))
-    return ip, it
+    return _weight_or_fresh_images(x, plain, trans, 3, scale, _lib.lib().yt8m_x3_split)
+
+
+def _image_problems(pre, what, planes, items, bf16_out=False):
+    """The items of an image family's group -> (problems, outputs, temporaries).  Operands are images of `planes` planes ([M rows, K]
+    and [N rows, K]); bf16_out: the family also writes bf16 outputs (an item's out_dtype picks what a missing `out` is made as)."""
+    probs, outs, keep = [], [], []
+    out_dtypes = _F32_BF16 if bf16_out else _F32
+    for it in items:
+        A, B = it["A"], it["B"]
+        if getattr(A, "planes", None) != planes or getattr(B, "planes", None) != planes:
+            raise TypeError("%s: operands must be %s" % (pre, what))
+        if A.K != B.K:
+            raise ValueError("%s: inner dimensions differ (%d vs %d)" % (pre, A.K, B.K))
+        out, bias = it.get("out"), it.get("bias")
+        _dev(A.buf, B.buf, out, bias)
+        pr, out, k = _marshal(pre, A.rows, B.rows, A.K, A.buf, 0, B.buf, 0, out, bias, it.get("beta", 0.0), out_dtypes,
+                              it.get("out_dtype", torch.float32) if bf16_out else torch.float32)
+        probs.append(pr)
+        outs.append(out)
+        keep.append(k)
+    return probs, outs, keep
 
 
 def gemm_x3_grouped(items):
     """items: dicts(A=X3Image [M rows, K], B=X3Image [N rows, K], out=None fp32 [M,N], bias=None, beta=0.0) -> fp32 outputs
     C = A . B^T from six bf16 MFMA products of the split operands (yt8m_gemm_x3_nt_grouped): fp32-grade accuracy."""
-    probs, outs, keep = [], [], []
-    for it in items:
-        A, B = it["A"], it["B"]
-        if not isinstance(A, X3Image) or not isinstance(B, X3Image):
-            raise TypeError("gemm_x3: operands must be X3Image")
-        if A.K != B.K:
-            raise ValueError("gemm_x3: inner dimensions differ (%d vs %d)" % (A.K, B.K))
-        M, N, K = A.rows, B.rows, A.K
-        out = it.get("out")
-        beta = it.get("beta", 0.0)
-        _dev(A.buf, B.buf, out, it.get("bias"))
-        if out is None:
-            if beta != 0.0:
-                raise ValueError("beta != 0 needs an output tensor")
-            out = torch.empty((M, N), dtype=torch.float32, device=A.buf.device)
-        if out.dtype != torch.float32 or tuple(out.shape) != (M, N) or (out.stride(1) != 1 and N != 1):
-            raise ValueError("gemm_x3: bad output tensor")
-        bias = it.get("bias")
-        if bias is not None:
-            bias = _f32c(bias)
-            if bias.numel() != N:
-                raise ValueError("bias size mismatch")
-        ldc = out.stride(0) if M > 1 else max(N, 1)
-        probs.append(_lib.GemmProblem(M, N, K, A.buf.data_ptr(), 0, B.buf.data_ptr(), 0, out.data_ptr(), ldc,
-                                      bias.data_ptr() if bias is not None else None, float(beta)))
-        outs.append(out)
-        keep.append((A, B, bias))
+    probs, outs, keep = _image_problems("gemm_x3", "X3Image", 3, items)
     ws = _workspace(outs[0].device)
-    for i in range(0, len(probs), 4):                               # the library takes 1..4 problems per launch
-        part = probs[i:i + 4]
-        arr = (_lib.GemmProblem * len(part))(*part)
-        _lib.check(_lib.lib().yt8m_gemm_x3_nt_grouped(len(part), arr, _p(ws), ws.numel() * 4, _stream()))
+    for n, arr in _chunks(4, probs):                                # the library takes 1..4 problems per launch
+        _lib.check(_lib.lib().yt8m_gemm_x3_nt_grouped(n, arr, _p(ws), ws.numel() * 4, _stream()))
     return outs
 
 
@@ -333,7 +340,7 @@ class H2Image(X3Image):
     __slots__ = ("scale", "dinv")
 
     def __init__(self, buf, rows, K, scale=1.0, dinv=None):
-        X3Image.__init__(self, buf, rows, K)
+        X3Image.__init__(self, buf, rows, K, 2)
         self.scale, self.dinv = float(scale), dinv
 
 
@@ -352,12 +359,10 @@ def h2_split(x, plain=True, trans=False, scale=1.0, dynamic=False):
     _dev(x)
     x, ld = _rowmajor2d(x)
     R, C = x.shape
-    lib = _lib.lib()
     ds = h2_absmax(x) if dynamic else None
-    mk = lambda rows, K: torch.empty(max(lib.yt8m_x3_image_bytes(rows, K) // 3 * 2, 16), dtype=torch.uint8, device=x.device)
-    bp = mk(R, C) if plain else None
-    bt = mk(C, R) if trans else None
-    _lib.check(lib.yt8m_h2_split(_p(x), R, C, ld, float(scale), _p(ds), _p(bp), _p(bt), None, _stream()))
+    bp = image_buffer(R, C, 2, x.device) if plain else None
+    bt = image_buffer(C, R, 2, x.device) if trans else None
+    _lib.check(_lib.lib().yt8m_h2_split(_p(x), R, C, ld, float(scale), _p(ds), _p(bp), _p(bt), None, _stream()))
     return (H2Image(bp, R, C, scale, ds) if plain else None, H2Image(bt, C, R, scale, ds) if trans else None)
 
 
@@ -365,40 +370,14 @@ def gemm_h2_grouped(items):
     """items: dicts(A=H2Image [M rows, K], B=H2Image [N rows, K], out=None fp32 [M,N], bias=None, beta=0.0) -> fp32 outputs
     C = A . B^T from three f16 MFMA products of the two-plane operands (yt8m_gemm_h2_nt_grouped); the images' scales are undone in
     the epilogue (host part as alpha, device part through pointers)."""
-    probs, outs, keep, alphas, dsa, dsb = [], [], [], [], [], []
-    for it in items:
-        A, B = it["A"], it["B"]
-        if not isinstance(A, H2Image) or not isinstance(B, H2Image):
-            raise TypeError("gemm_h2: operands must be H2Image")
-        if A.K != B.K:
-            raise ValueError("gemm_h2: inner dimensions differ (%d vs %d)" % (A.K, B.K))
-        M, N, K = A.rows, B.rows, A.K
-        out, beta, bias = it.get("out"), it.get("beta", 0.0), it.get("bias")
-        _dev(A.buf, B.buf, out, bias)
-        if out is None:
-            if beta != 0.0:
-                raise ValueError("beta != 0 needs an output tensor")
-            out = torch.empty((M, N), dtype=torch.float32, device=A.buf.device)
-        if out.dtype != torch.float32 or tuple(out.shape) != (M, N) or (out.stride(1) != 1 and N != 1):
-            raise ValueError("gemm_h2: bad output tensor")
-        if bias is not None:
-            bias = _f32c(bias)
-        ldc = out.stride(0) if M > 1 else max(N, 1)
-        probs.append(_lib.GemmProblem(M, N, K, A.buf.data_ptr(), 0, B.buf.data_ptr(), 0, out.data_ptr(), ldc,
-                                      bias.data_ptr() if bias is not None else None, float(beta)))
-        alphas.append(1.0 / (A.scale * B.scale))
-        dsa.append(A.dinv.data_ptr() if A.dinv is not None else None)
-        dsb.append(B.dinv.data_ptr() if B.dinv is not None else None)
-        outs.append(out)
-        keep.append((A, B, bias))
+    probs, outs, keep = _image_problems("gemm_h2", "H2Image", 2, items)
+    alphas = [1.0 / (it["A"].scale * it["B"].scale) for it in items]
+    dsa = [it["A"].dinv.data_ptr() if it["A"].dinv is not None else None for it in items]
+    dsb = [it["B"].dinv.data_ptr() if it["B"].dinv is not None else None for it in items]
     ws = _workspace(outs[0].device)
-    for i in range(0, len(probs), 4):
-        n = len(probs[i:i + 4])
-        arr = (_lib.GemmProblem * n)(*probs[i:i + 4])
-        al = (ctypes.c_float * n)(*alphas[i:i + 4])
-        pa = (ctypes.c_void_p * n)(*dsa[i:i + 4])
-        pb = (ctypes.c_void_p * n)(*dsb[i:i + 4])
-        _lib.check(_lib.lib().yt8m_gemm_h2_nt_grouped(n, arr, al, pa, pb, _p(ws), ws.numel() * 4, _stream()))
+    for n, arr, al, pa, pb in _chunks(4, probs, alphas, dsa, dsb):
+        _lib.check(_lib.lib().yt8m_gemm_h2_nt_grouped(n, arr, (ctypes.c_float * n)(*al), (ctypes.c_void_p * n)(*pa), (ctypes.c_void_p * n)(*pb),
+                                                      _p(ws), ws.numel() * 4, _stream()))
     return outs
 
 
@@ -413,64 +392,24 @@ def _b1_ok(M, N, K):
 def bf16_image(x, transpose=False, both=False):
     """fp32 [R, C] -> one-plane bf16 operand image(s) of csrc/gemm_x3.hip (yt8m_bf16_image): the matrix as an [R rows, K = C]
     operand, its transpose as a [C rows, K = R] operand (transpose=True), or both from one pass (both=True -> (plain, trans))."""
-    _dev(x)
-    x, ld = _rowmajor2d(x)
-    R, C = x.shape
-    lib = _lib.lib()
-    mk = lambda rows, K: X3Image(torch.empty(max(lib.yt8m_x3_image_bytes(rows, K) // 3, 16), dtype=torch.uint8, device=x.device), rows, K)
-    want_p, want_t = both or not transpose, both or transpose
-    ip = it = None
-    if want_p:                                               # resident one-plane image of a weight matrix (wimg.py)
-        r = _wimg.resident_image(x, R, C, ld, 0, 1)
-        ip = X3Image(r[0], R, C) if r else None
-    if want_t:
-        r = _wimg.resident_image(x, R, C, ld, 1, 1)
-        it = X3Image(r[0], C, R) if r else None
-    mk_p, mk_t = want_p and ip is None, want_t and it is None
-    if mk_p:
-        ip = mk(R, C)
-    if mk_t:
-        it = mk(C, R)
-    if mk_p or mk_t:
-        _lib.check(lib.yt8m_bf16_image(_p(x), R, C, ld, 1.0, _p(ip.buf) if mk_p else None, _p(it.buf) if mk_t else None, _stream()))
+    ip, it = _weight_or_fresh_images(x, both or not transpose, both or transpose, 1, 1.0, _lib.lib().yt8m_bf16_image)
     return (ip, it) if both else (it if transpose else ip)
 
 
 def gemm_b1_grouped(items):
     """items: dicts(A=image [M rows, K], B=image [N rows, K], out=None fp32 [M,N], bias=None, beta=0.0) -> fp32 outputs;
     C = A . B^T on v_mfma_f32_32x32x16_bf16 from ONE-plane bf16 operand images (yt8m_gemm_b1_nt_grouped)."""
-    probs, outs, keep = [], [], []
-    for it in items:
-        A, B = it["A"], it["B"]
-        if A.K != B.K:
-            raise ValueError("gemm_b1: inner dimensions differ (%d vs %d)" % (A.K, B.K))
-        M, N, K = A.rows, B.rows, A.K
-        out, beta, bias = it.get("out"), it.get("beta", 0.0), it.get("bias")
-        _dev(A.buf, B.buf, out, bias)
-        if out is None:
-            if beta != 0.0:
-                raise ValueError("beta != 0 needs an output tensor")
-            out = torch.empty((M, N), dtype=it.get("out_dtype", torch.float32), device=A.buf.device)
-        if out.dtype not in (torch.float32, torch.bfloat16) or tuple(out.shape) != (M, N) or (out.stride(1) != 1 and N != 1):
-            raise ValueError("gemm_b1: bad output tensor")
-        if out.dtype == torch.bfloat16 and (beta != 0.0 or out.stride(0) % 4 != 0):
+    probs, outs, keep = _image_problems("gemm_b1", "one-plane images", 1, items, bf16_out=True)
+    for pr, out in zip(probs, outs):
+        if out.dtype == torch.bfloat16 and (pr.beta != 0.0 or out.stride(0) % 4 != 0):
             raise ValueError("gemm_b1: a bf16 output takes beta = 0 and a row pitch that is a multiple of 4")
-        if bias is not None:
-            bias = _f32c(bias)
-        ldc = out.stride(0) if M > 1 else max(N, 1)
-        probs.append(_lib.GemmProblem(M, N, K, A.buf.data_ptr(), 0, B.buf.data_ptr(), 0, out.data_ptr(), ldc,
-                                      bias.data_ptr() if bias is not None else None, float(beta)))
-        outs.append(out)
-        keep.append((A, B, bias))
     ws = _workspace(outs[0].device)
-    for i in range(0, len(probs), 4):
-        part = probs[i:i + 4]
-        arr = (_lib.GemmProblem * len(part))(*part)
-        mask = sum(1 << j for j, o in enumerate(outs[i:i + 4]) if o.dtype == torch.bfloat16)
+    for n, arr, part in _chunks(4, probs, outs):
+        mask = sum(1 << j for j, o in enumerate(part) if o.dtype == torch.bfloat16)
         if mask:                                  # bf16 outputs (round 6: the MoE logits of the bf16 configuration)
-            _lib.check(_lib.lib().yt8m_gemm_b1_nt_grouped_bf16c(len(part), arr, mask, _p(ws), ws.numel() * 4, _stream()))
+            _lib.check(_lib.lib().yt8m_gemm_b1_nt_grouped_bf16c(n, arr, mask, _p(ws), ws.numel() * 4, _stream()))
         else:
-            _lib.check(_lib.lib().yt8m_gemm_b1_nt_grouped(len(part), arr, _p(ws), ws.numel() * 4, _stream()))
+            _lib.check(_lib.lib().yt8m_gemm_b1_nt_grouped(n, arr, _p(ws), ws.numel() * 4, _stream()))
     return outs
 
 
@@ -1013,11 +952,10 @@ def _linear_dx_h2_rows(dy, W, out=None, beta=0.0, row0=0):
     K = W.data.shape[0]
     assert row0 % 32 == 0 and 0 <= row0 < K
     dev = dy.device
-    nb = lambda rows, kk: max(L.yt8m_x3_image_bytes(rows, kk) // 3 * 2, 16)
     S = torch.empty(M, dtype=torch.float32, device=dev)
     inv = torch.empty(M, dtype=torch.float32, device=dev)
     _lib.check(L.yt8m_h2_rowscales(_p(dy), M, N, N, _p(S), _p(inv), _stream()))
-    dyi = torch.empty(nb(M, N), dtype=torch.uint8, device=dev)
+    dyi = image_buffer(M, N, 2, dev)
     _lib.check(L.yt8m_h2_split_rows(_p(dy), M, N, N, _p(S), _p(dyi), _stream()))
     wp = ctypes.c_void_p(W.data.data_ptr())
     ptr = L.yt8m_wimg_lookup(wp, K, N, N, 0, 2, 0.0)
@@ -1027,7 +965,7 @@ def _linear_dx_h2_rows(dy, W, out=None, beta=0.0, row0=0):
     else:
         L.yt8m_wimg_note_demand(wp, K, N, N, 0, 2, 0.0)                            # its owner may keep it resident from the next step on
         word = h2_absmax(W.data)
-        wi = torch.empty(nb(K, N), dtype=torch.uint8, device=dev)
+        wi = image_buffer(K, N, 2, dev)
         _lib.check(L.yt8m_h2_split(wp, K, N, N, 1.0, _p(word), _p(wi), None, None, _stream()))
         keep = (word, wi)
         wimg_p, word_p = _p(wi), _p(word)
@@ -1292,19 +1230,9 @@ class _MoeHead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, token, Wg, We, be, V, M, bf16, dx_from=0):
-        x2 = _f32c(x)
-        ctx.images = {} if (bf16 and FUSED_MIX_BF16 and M == 2 and ctx.needs_input_grad[1]) else None
-        ctx.words = {}                                  # max |x| measured once: the weight gradient's split of x^T takes the same word
-        Zg, Ze = _moe_logits(x2, Wg, We, be, bf16, keep=ctx.images, z16=_z16_ok(x2, Wg, We, V, M, bf16, ctx.images is not None),
-                             words=ctx.words)
-        ctx.bf16 = bf16
+        x2, Zg, Ze = _moe_head_fwd(ctx, x, Wg, We, be, V, M, bf16, z16=True)
         ctx.dx_from = dx_from
-        p = moe_mix_fwd(Zg, Ze, V, M)
-        ctx.save_for_backward(x2)
-        ctx.Z = (Zg, Ze)
-        ctx.vars = (Wg, We, be)
-        ctx.VM = (V, M)
-        return p
+        return moe_mix_fwd(Zg, Ze, V, M)
 
     @staticmethod
     def backward(ctx, dp):
@@ -1327,6 +1255,41 @@ class _MoeHead(torch.autograd.Function):
 FUSED_MIX_BF16 = True     # compute_dtype=bfloat16, M == 2: mixing backward writes the bf16 GEMM operands itself (csrc/moe_bf16.hip)
 
 
+def _moe_head_fwd(ctx, x, Wg, We, be, V, M, bf16, z16=False):
+    """What the two head ops' forward passes share: the logits (x2, Zg, Ze) and everything the backward forms read from ctx.
+    z16: the logits may leave the product as bf16 (_z16_ok)."""
+    x2 = _f32c(x)
+    ctx.images = {} if (bf16 and FUSED_MIX_BF16 and M == 2 and ctx.needs_input_grad[1]) else None
+    ctx.words = {}                                  # max |x| measured once: the weight gradient's split of x^T takes the same word
+    Zg, Ze = _moe_logits(x2, Wg, We, be, bf16, keep=ctx.images, z16=z16 and _z16_ok(x2, Wg, We, V, M, bf16, ctx.images is not None),
+                         words=ctx.words)
+    ctx.bf16 = bf16
+    ctx.save_for_backward(x2)
+    ctx.Z = (Zg, Ze)
+    ctx.vars = (Wg, We, be)
+    ctx.VM = (V, M)
+    return x2, Zg, Ze
+
+
+def _moe_head_dw(product, pg, pe, Wg, We, be, bsrc, **kw):
+    """The tail of every backward form of the head: the weight-gradient products pg -> Wg.grad, pe -> We.grad through `product` (None,
+    None: a gradient slot is missing, no product) and the experts' bias gradient, the column sums of bsrc."""
+    if pg is not None:
+        if Wg._graph is not None and Wg._graph.grad_ready_hook is not None:
+            # data-parallel: finish the big gate gradient first so its all-reduce rides under the expert GEMM
+            product([pg], **kw)
+            Wg.grad_done()
+            product([pe], **kw)
+            We.grad_done()
+        else:
+            product([pg, pe], **kw)
+            Wg.grad_done()
+            We.grad_done()
+    if be.grad is not None:
+        colsum(bsrc, be.grad.view(-1), beta=be.grad_beta())
+        be.grad_done()
+
+
 def _moe_head_bwd_bf16_fused(ctx, x, Zg, Ze, Wg, We, be, V, M, dp=None, labels=None, ldt=0, dscale=1.0, up=None):
     """bf16 configuration: ONE pass over the fp32 logits produces dL/dZ as bf16 in both layouts + the bias partial sums, then
     the same three bf16 products as _moe_head_param_grads_bf16 (no fp32 dZ, no cast passes, no colsum over dZ_e)."""
@@ -1347,23 +1310,12 @@ def _moe_head_bwd_bf16_fused(ctx, x, Zg, Ze, Wg, We, be, V, M, dp=None, labels=N
         dx, = gemm_bf16_nt_grouped([dict(A=Zgb, B=cast_bf16(Wg.data))])
         gemm_bf16_nt_grouped([dict(A=Zeb, B=cast_bf16(We.data), out=dx, beta=1.0)])
     del Zgb, Zeb
+    pg = pe = None
     if Wg.grad is not None and We.grad is not None:
         xT = cast_bf16(x, transpose=True)
-        overlap = Wg._graph is not None and Wg._graph.grad_ready_hook is not None
         pg = dict(A=xT, B=ZgT, out=Wg.grad, beta=Wg.grad_beta())
         pe = dict(A=xT, B=ZeT, out=We.grad, beta=We.grad_beta())
-        if overlap:
-            gemm_bf16_nt_grouped([pg])
-            Wg.grad_done()
-            gemm_bf16_nt_grouped([pe])
-            We.grad_done()
-        else:
-            gemm_bf16_nt_grouped([pg, pe])
-            Wg.grad_done()
-            We.grad_done()
-    if be.grad is not None:
-        colsum(part, be.grad.view(-1), beta=be.grad_beta())
-        be.grad_done()
+    _moe_head_dw(gemm_bf16_nt_grouped, pg, pe, Wg, We, be, part)
     return dx
 
 
@@ -1373,8 +1325,7 @@ def _moe_head_bwd_bf16_images(ctx, x, Zg, Ze, Wg, We, be, V, M, dp, labels, ldt,
     L = _lib.lib()
     B, Ng, Ne = Zg.shape[0], Zg.shape[1], Ze.shape[1]
     dev = Zg.device
-    mk = lambda rows, K: X3Image(torch.empty(max(L.yt8m_x3_image_bytes(rows, K) // 3, 16), dtype=torch.uint8, device=dev), rows, K)
-    Zgi, ZgTi, Zei, ZeTi = mk(B, Ng), mk(Ng, B), mk(B, Ne), mk(Ne, B)
+    Zgi, ZgTi, Zei, ZeTi = _image_empty(B, Ng, 1, dev), _image_empty(Ng, B, 1, dev), _image_empty(B, Ne, 1, dev), _image_empty(Ne, B, 1, dev)
     part = torch.empty((L.yt8m_moe_mix_bwd_bf16_partial_rows(B), Ne), dtype=torch.float32, device=dev) if be.grad is not None else None
     kb = lambda K: (K + 15) // 16
     mix = L.yt8m_moe_mix_bwd_bf16_images_z16 if Zg.dtype == torch.bfloat16 else L.yt8m_moe_mix_bwd_bf16_images
@@ -1387,23 +1338,12 @@ def _moe_head_bwd_bf16_images(ctx, x, Zg, Ze, Wg, We, be, V, M, dp, labels, ldt,
         dx, = gemm_b1_grouped([dict(A=Zgi, B=kept.get("Wg") or bf16_image(Wg.data))])           # W [D, N] as [D rows, K = N]
         gemm_b1_grouped([dict(A=Zei, B=kept.get("We") or bf16_image(We.data), out=dx, beta=1.0)])
     del Zgi, Zei
+    pg = pe = None
     if Wg.grad is not None and We.grad is not None:
         xT = kept.get("xT") or bf16_image(x, transpose=True)                    # [D rows, K = B]
-        overlap = Wg._graph is not None and Wg._graph.grad_ready_hook is not None
         pg = dict(A=xT, B=ZgTi, out=Wg.grad, beta=Wg.grad_beta())
         pe = dict(A=xT, B=ZeTi, out=We.grad, beta=We.grad_beta())
-        if overlap:
-            gemm_b1_grouped([pg])
-            Wg.grad_done()
-            gemm_b1_grouped([pe])
-            We.grad_done()
-        else:
-            gemm_b1_grouped([pg, pe])
-            Wg.grad_done()
-            We.grad_done()
-    if be.grad is not None:
-        colsum(part, be.grad.view(-1), beta=be.grad_beta())
-        be.grad_done()
+    _moe_head_dw(gemm_b1_grouped, pg, pe, Wg, We, be, part)
     return dx
 
 
@@ -1488,11 +1428,7 @@ class _MoeHeadXent(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, token, Wg, We, be, labels, V, M, bf16):
-        x2 = _f32c(x)
-        ctx.images = {} if (bf16 and FUSED_MIX_BF16 and M == 2 and ctx.needs_input_grad[1]) else None
-        ctx.words = {}
-        Zg, Ze = _moe_logits(x2, Wg, We, be, bf16, keep=ctx.images, words=ctx.words)
-        ctx.bf16 = bf16
+        x2, Zg, Ze = _moe_head_fwd(ctx, x, Wg, We, be, V, M, bf16)
         B = x2.shape[0]
         lab, ldt = _labels_arg(labels)
         if tuple(lab.shape) != (B, V):
@@ -1502,11 +1438,7 @@ class _MoeHeadXent(torch.autograd.Function):
         p = torch.empty((B, V), dtype=torch.float32, device=x2.device)
         loss = torch.empty((), dtype=torch.float32, device=x2.device)
         _lib.check(L.yt8m_moe_mix_xent_fwd(_p(Zg), _p(Ze), _p(lab), ldt, _p(p), _p(loss), B, V, M, XENT_EPS, _p(ws), _stream()))
-        ctx.save_for_backward(x2)
-        ctx.Z = (Zg, Ze)
-        ctx.vars = (Wg, We, be)
         ctx.lab = (lab, ldt)
-        ctx.VM = (V, M)
         ctx.mark_non_differentiable(p)          # predictions leave through the loss only on this path
         ctx.set_materialize_grads(False)        # no [B,V] zero-fill for the unused dL/dp slot
         return p, loss
@@ -1555,23 +1487,12 @@ def _moe_head_param_grads_bf16(ctx, x, Zg, Ze, Wg, We, be):
         else:                                      # odd V*(M+1): the reduction length cannot be packed in bf16 pairs
             dx = gemm(Zg, Wg.data, transB=True)
             gemm(Ze, We.data, out=dx, transB=True, beta=1.0)
+    pg = pe = None
     if need_dw:
         xT = cast_bf16(x, transpose=True)
-        overlap = Wg._graph is not None and Wg._graph.grad_ready_hook is not None
         pg = dict(A=xT, B=ZgT if ZgT is not None else cast_bf16(Zg, transpose=True), out=Wg.grad, beta=Wg.grad_beta())
         pe = dict(A=xT, B=ZeT if ZeT is not None else cast_bf16(Ze, transpose=True), out=We.grad, beta=We.grad_beta())
-        if overlap:
-            gemm_bf16_nt_grouped([pg])
-            Wg.grad_done()
-            gemm_bf16_nt_grouped([pe])
-            We.grad_done()
-        else:
-            gemm_bf16_nt_grouped([pg, pe])
-            Wg.grad_done()
-            We.grad_done()
-    if be.grad is not None:
-        colsum(Ze, be.grad.view(-1), beta=be.grad_beta())
-        be.grad_done()
+    _moe_head_dw(gemm_bf16_nt_grouped, pg, pe, Wg, We, be, Ze)
     return dx
 
 
@@ -1628,7 +1549,6 @@ def _moe_head_param_grads(ctx, x, Zg, Ze, Wg, We, be, zmax=None, xmax=None):
         else:
             dx = gemm(Zg, Wg.data, transB=True)
             gemm(Ze, We.data, out=dx, transB=True, beta=1.0)
-    overlap = Wg._graph is not None and Wg._graph.grad_ready_hook is not None
     side = side_stream(Wg._graph) if (dx is not None and Wg.grad is not None and We.grad is not None and be.grad is not None) else None
     if side is not None:
         # dx is on its way to the recurrent stack; the parameter gradients are read by the optimiser only: off the critical chain
@@ -1648,20 +1568,11 @@ def _moe_head_param_grads(ctx, x, Zg, Ze, Wg, We, be, zmax=None, xmax=None):
         We.grad_done()
         be.grad_done()
         return dx
-    if Wg.grad is not None and We.grad is not None and not overlap:
-        gemm_grouped([dict(A=x, B=Zg, out=Wg.grad, beta=Wg.grad_beta(), absmaxA=xmax, absmaxB=mg),
-                      dict(A=x, B=Ze, out=We.grad, beta=We.grad_beta(), absmaxA=xmax, absmaxB=me)], transA=True, role="dw")
-        Wg.grad_done()
-        We.grad_done()
-    elif Wg.grad is not None and We.grad is not None:
-        # data-parallel: finish the big gate gradient first so its all-reduce rides under the expert GEMM
-        gemm_grouped([dict(A=x, B=Zg, out=Wg.grad, beta=Wg.grad_beta(), absmaxA=xmax, absmaxB=mg)], transA=True, role="dw")
-        Wg.grad_done()
-        gemm_grouped([dict(A=x, B=Ze, out=We.grad, beta=We.grad_beta(), absmaxA=xmax, absmaxB=me)], transA=True, role="dw")
-        We.grad_done()
-    if be.grad is not None:
-        colsum(Ze, be.grad.view(-1), beta=be.grad_beta())
-        be.grad_done()
+    pg = pe = None
+    if Wg.grad is not None and We.grad is not None:
+        pg = dict(A=x, B=Zg, out=Wg.grad, beta=Wg.grad_beta(), absmaxA=xmax, absmaxB=mg)
+        pe = dict(A=x, B=Ze, out=We.grad, beta=We.grad_beta(), absmaxA=xmax, absmaxB=me)
+    _moe_head_dw(gemm_grouped, pg, pe, Wg, We, be, Ze, transA=True, role="dw")
     return dx
 
 

@@ -1569,10 +1569,9 @@ class U8FrameImages(object):
             return
         dev = part.device
         lib = _lib.lib()
-        nb = max(lib.yt8m_x3_image_bytes(N, rows) // 3 * 2, 16)
         word = ops.h2_absmax(part)
-        dzT = torch.empty(nb, dtype=torch.uint8, device=dev)
-        dzTs = torch.empty(nb, dtype=torch.uint8, device=dev)
+        dzT = ops.image_buffer(N, rows, 2, dev)
+        dzTs = ops.image_buffer(N, rows, 2, dev)
         ntile = (rows + 63) // 64
         cp = torch.empty((ntile, N), dtype=torch.float32, device=dev)
         cps = torch.empty((ntile, N), dtype=torch.float32, device=dev)
@@ -1655,7 +1654,7 @@ def _u8_cnn_partials(frames, filters):
     word = torch.zeros(1, dtype=torch.int32, device=dev)
     for W in filters:                                                                            # max |W| over all filters (atomicMax)
         _lib.check(lib.yt8m_h2_absmax(_p(W.data), W.data.shape[0], W.data.shape[1], W.data.shape[1], _p(word), _stream()))
-    nbytes = lambda rows, K: lib.yt8m_x3_image_bytes(rows, K) // 3 * 2
+    nbytes = lambda rows, K: ops.image_bytes(rows, K, 2)
     img = torch.empty(sum(W.data.shape[0] // D * nbytes(W.data.shape[1], D) for W in filters), dtype=torch.uint8, device=dev)
     cs = torch.empty((Ntz,), dtype=torch.float32, device=dev)
     off, c = 0, 0

@@ -135,6 +135,7 @@ class WeightImages(object):
     def add(self, keys):
         """Allocates, builds and registers the images `keys` ((tensor, row0, rows, trans, planes, scale) each; at most four distinct
         (row window, planes, scale) per tensor -- the rest is left to the per-step split)."""
+        from .ops import image_buffer
         g = self.g
         L = _lib.lib()
         tv = g.trainable_variables()
@@ -158,13 +159,12 @@ class WeightImages(object):
             t, row0, rows, trans, planes, scale = k
             C = tv[t].data.shape[1]
             img_rows, K = (C, rows) if trans else (rows, C)
-            nbytes = L.yt8m_x3_image_bytes(img_rows, K) // 3 * planes
             if planes == 2:                                                # [256-byte header: scale word, next maximum | image]
-                whole = torch.zeros(H2_HEADER + max(nbytes, 16), dtype=torch.uint8, device=g.params.device)
+                whole = image_buffer(img_rows, K, planes, g.params.device, header=H2_HEADER, alloc=torch.zeros)
                 buf = whole[H2_HEADER:]
                 self.h2_whole[k] = whole
             else:
-                buf = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=g.params.device)
+                buf = image_buffer(img_rows, K, planes, g.params.device)
             self.keys[k] = buf
             BUFFERS[buf.data_ptr()] = (buf, img_rows, K, planes)
         self._layout()
