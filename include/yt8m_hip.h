@@ -529,6 +529,25 @@ int yt8m_chain_link_fwd(int act, const float* z, float* y, float* rinv, int64_t 
                         uint64_t seed, int64_t offset, yt8m_stream_t stream);
 int yt8m_chain_link_bwd(int act, const float* z, const float* y, const float* rinv, const float* dy, float* dz, int64_t rows,
                         int64_t cols, float eps, yt8m_stream_t stream);
+/* The step from the final memories of the multi-LSTM chain plugins' stacks to a stage's classifier input (csrc/memory_link.hip):
+ * torch.cat and, with normalize, tf.nn.l2_normalize along the row, in one pass each way
+ * (W/all_frame_models/lstm_memory_deep_chain_model.py:72, distillchain_lstm_memory_deep_combine_chain_model.py:57,74,97).
+ * src[s] / dsrc[s]: [rows, widths[s]] contiguous fp32, 1 <= nseg <= 16; src, dsrc and widths are HOST arrays, copied into the kernel
+ * arguments.  C = sum of the widths (< 2^31).
+ *   fwd: y [rows, C] = [src_0 | src_1 | ...].  normalize = 0: an exact copy, rinv may be NULL.  normalize != 0, per row:
+ *     ss = sum concat^2, r = rsqrt(max(ss, eps)) (1 / sqrt(eps), rounded once on the host, when ss <= eps), y = concat * r;
+ *     rinv[row] = r when ss > eps, else -r: the sign carries the eps branch to the backward pass (as yt8m_chain_link_fwd).
+ *   bwd: normalize = 0: dsrc[s] = the columns of segment s of dy, an exact copy (y and rinv may be NULL).  normalize != 0, per row:
+ *     R = |rinv|, k = sum(y * dy); d = R * (dy - y * k) when rinv > 0, else R * dy; dsrc[s] = the columns of segment s of d.
+ *     A NULL dsrc[s] is skipped: nothing is written for that segment.  The dsrc[s] are what yt8m_lstm_stack_bwd takes as dc_final.
+ *     eps is part of the signature for symmetry and is only validated.
+ * One wave per row; rows of up to 1024 columns are read once, wider rows twice; 16-byte accesses when every width % 4 == 0 and every
+ * operand is 16-byte aligned.  Fixed summation order, no atomics.  nseg out of range, a width or rows <= 0, a null operand (rinv only
+ * with normalize), eps <= 0 is YT8M_E_BADARG and nothing is launched. */
+int yt8m_memory_link_fwd(int nseg, const float* const* src, const int64_t* widths, int normalize, float* y, float* rinv, int64_t rows,
+                         float eps, yt8m_stream_t stream);
+int yt8m_memory_link_bwd(int nseg, const int64_t* widths, int normalize, const float* y, const float* rinv, const float* dy,
+                         float* const* dsrc, int64_t rows, float eps, yt8m_stream_t stream);
 /* out[n] (beta=0) or out[n] += (beta=1): sum over rows of X[rows, cols]; deterministic (fixed summation order).
  * workspace (optional, may be NULL): >= yt8m_colsum_workspace_bytes() device bytes let tall-and-narrow inputs
  * ([B*F, 8..64] attention / cluster logits) be split over rows so that the whole chip is used. */

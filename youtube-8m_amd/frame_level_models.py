@@ -662,6 +662,99 @@ class DistillchainLstmAttentionMaxPoolingModel(LstmAttentionMaxPoolingModel):
         return torch.cat([attention_outputs, tiled_distill_norm], dim=2)
 
 
+def _memory_stacks(x_tm, d_in, num_frames, lstm_size, number_of_layers):
+    """k -> [final c of every layer] of stack k of a multi-LSTM chain plugin: MultiRNNCell([BasicLSTMCell(H, forget_bias=1.0)] * L) under
+    dynamic_rnn in variable_scope("lstm-<k>-RNN") (W/all_frame_models/lstm_memory_deep_chain_model.py:57-73; variables
+    lstm-<k>-RNN/multi_rnn_cell/cell_<l>/basic_lstm_cell/{weights,biases}).  Every stack reads the SAME prepared input x_tm (_stack_input,
+    made once by the caller) and owns slot k: the stacks' scratch and tapes are alive together until the backward pass."""
+    g = get_default_graph()
+
+    def memories(k):
+        with g.variable_scope("lstm-%d-RNN" % k):
+            wb = _lstm_cells(d_in, lstm_size, number_of_layers)
+        _, finals = _native_stack(x_tm, num_frames, wb, slot=k)
+        return [c for c, _ in finals]
+    return memories
+
+
+class LstmMemoryDeepChainModel(models.BaseModel):
+    """W/all_frame_models/lstm_memory_deep_chain_model.py:13-104: deep_chain_layers + 1 LSTM stacks over the same frames (_memory_stacks),
+    a chain of MoE sub-predictions: stage 0 reads the concatenated final memories of stack 0, stage l + 1 reads [memories of stack l + 1 |
+    l2norm(relu-<l>(prediction-<l>))] -- only the latest relu, unlike the Combine form.  The concatenation is ops.memory_link, the relu ->
+    l2norm ops.chain_link.  Variables: lstm-<k>-RNN/..., relu-<l>, gates-/experts-prediction-<l>, gates-/experts--main.
+    accepts_quantized_input: every stack reads the reader's bytes (see _stack_input), prepared once."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, sub_scope="", original_input=None, **unused_params):
+        num_layers = FLAGS.deep_chain_layers
+        relu_cells = FLAGS.deep_chain_relu_cells
+        memories = _memory_stacks(_stack_input(model_input, num_frames), model_input.shape[2], num_frames, int(FLAGS.lstm_cells),
+                                  FLAGS.lstm_layers)
+        next_input = ops.memory_link(memories(0), normalize=False)
+        support_predictions = []
+        for layer in range(num_layers):
+            sub_prediction = self.sub_moe(next_input, vocab_size, sub_scope=sub_scope + "prediction-%d" % layer)
+            support_predictions.append(sub_prediction)
+            sub_activation = video_level_models.fully_connected(sub_prediction, relu_cells, sub_scope + "relu-%d" % layer,
+                                                                l2_penalty=l2_penalty)
+            relu_norm = ops.chain_link(sub_activation, "relu")
+            next_input = torch.cat([ops.memory_link(memories(layer + 1), normalize=False), relu_norm], dim=1)
+        main_predictions = self.sub_moe(next_input, vocab_size, sub_scope=sub_scope + "-main")
+        return {"predictions": main_predictions, "support_predictions": torch.cat(support_predictions, dim=1)}
+
+    def sub_moe(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", **unused_params):
+        num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
+        return video_level_models.moe_block(model_input, vocab_size, num_mixtures, l2_penalty, "gates-" + sub_scope, "experts-" + sub_scope)
+
+
+class DistillchainLstmMemoryDeepCombineChainModel(LstmMemoryDeepChainModel):
+    """W/all_frame_models/distillchain_lstm_memory_deep_combine_chain_model.py:13-129: deep_chain_layers + 1 LSTM stacks over the same
+    frames; relu_layers starts [distill_norm, mean_relu_norm] ("distill-relu" -- with a hyphen, unlike the other cascade plugins'
+    distillrelu -- --distillchain_relu_cells wide over another model's predictions; "mean-relu" over the num_frames mean of the frames) and
+    gains relu-<l> after stage l; every stage, stage 0 included, reads [l2norm(memories of stack k) | relu_layers...].  The normalised
+    concatenation is ops.memory_link(normalize=True), every relu -> l2norm ops.chain_link.
+    accepts_quantized_input: where the stack's byte projection and the byte pooling both cover the shape the stacks and the mean frame
+    read the reader's bytes; else the frames are dequantised once for all of them."""
+
+    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, sub_scope="", original_input=None,
+                     distillation_predictions=None, **unused_params):
+        num_layers = FLAGS.deep_chain_layers
+        relu_cells = FLAGS.deep_chain_relu_cells
+        relu_layers = [_distill_link(distillation_predictions, FLAGS.distillchain_relu_cells, l2_penalty, scope="distill-relu")]
+        model_input, _ = _bytes_or_floats(model_input, num_frames, lambda q: _lib_u8_ok(q.shape[2]) and seq_ops.u8_attention_supported(q, 1))
+        mean_input = _mean_frame(model_input, num_frames)
+        mean_activation = video_level_models.fully_connected(mean_input, relu_cells, sub_scope + "mean-relu", l2_penalty=l2_penalty)
+        relu_layers.append(ops.chain_link(mean_activation, "relu"))
+        memories = _memory_stacks(_stack_input(model_input, num_frames), model_input.shape[2], num_frames, int(FLAGS.lstm_cells),
+                                  FLAGS.lstm_layers)
+        next_input = torch.cat([ops.memory_link(memories(0), normalize=True)] + relu_layers, dim=1)
+        support_predictions = []
+        for layer in range(num_layers):
+            sub_prediction = self.sub_moe(next_input, vocab_size, sub_scope=sub_scope + "prediction-%d" % layer)
+            support_predictions.append(sub_prediction)
+            sub_activation = video_level_models.fully_connected(sub_prediction, relu_cells, sub_scope + "relu-%d" % layer,
+                                                                l2_penalty=l2_penalty)
+            relu_layers.append(ops.chain_link(sub_activation, "relu"))
+            next_input = torch.cat([ops.memory_link(memories(layer + 1), normalize=True)] + relu_layers, dim=1)
+        main_predictions = self.sub_moe(next_input, vocab_size, sub_scope=sub_scope + "-main")
+        return {"predictions": main_predictions, "support_predictions": torch.cat(support_predictions, dim=1)}
+
+
+class LstmParallelMemoryModel(models.BaseModel):
+    """W/all_frame_models/lstm_parallel_memory_model.py:13-73: LstmParallelFinaloutputModel's stacks (one per input feature, RNN<i>), head
+    input = every layer's final MEMORY c of every stack side by side (ops.memory_link over widths such as 1024, 1024, 128, 128).  Reads
+    bytes on _parallel_stacks' terms."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, **unused_params):
+        lstm_sizes = [int(v) for v in str(FLAGS.lstm_cells).split(",")]
+        feature_sizes = [int(v) for v in str(FLAGS.feature_sizes).split(",")]
+        stacks = _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, FLAGS.lstm_layers, own_slots=True)
+        final_state = ops.memory_link([c for _, finals in stacks for c, _ in finals], normalize=False)
+        return _head()().create_model(model_input=final_state, original_input=model_input, vocab_size=vocab_size,
+                                      **unused_params)
+
+
 def _bn_vars(scope, n):
     g = get_default_graph()
     return (g.get_variable(scope + "/gamma", (n,), ones), g.get_variable(scope + "/beta", (n,), zeros),

@@ -1225,6 +1225,63 @@ def chain_link(z, kind="relu", noise_level=None, seed=None, offset=0, eps=1e-12,
     return _ChainLink.apply(z, kind, float(noise_level) if noisy else 0.0, seed if noisy else 0, offset, eps)
 
 
+# 0 (the default): memory_link composes torch.cat and l2_normalize; anything else: the fused kernel.  Composed is the default because
+# tools/multilstm_step.py measured it faster on the host without normalize (a cat and slice views against two launches through a Python
+# autograd Function), and whole steps do not move either way (DESIGN_LOG.md section 23).
+MEMORY_LINK_FUSED = os.environ.get("YT8M_MEMORY_LINK_FUSED", "0") != "0"
+
+
+class _MemoryLink(torch.autograd.Function):
+    """csrc/memory_link.hip: the concatenation of [B, w_s] tensors along the columns and, with normalize, l2_normalize of the result, in
+    one pass each way.  Saved for backward with normalize: y (the next stage's input) and rinv [rows]; without: nothing."""
+
+    @staticmethod
+    def forward(ctx, normalize, eps, *tensors):
+        srcs = [_f32c(t) for t in tensors]
+        _dev(*srcs)
+        rows = srcs[0].shape[0]
+        for t in srcs:
+            if t.dim() != 2 or t.shape[0] != rows:
+                raise ValueError("memory_link: every tensor must be [%d, width], got %s" % (rows, tuple(t.shape)))
+        n = len(srcs)
+        widths = (ctypes.c_int64 * n)(*[t.shape[1] for t in srcs])
+        y = torch.empty((rows, sum(t.shape[1] for t in srcs)), dtype=torch.float32, device=srcs[0].device)
+        rinv = torch.empty(rows, dtype=torch.float32, device=y.device) if normalize else None
+        _lib.check(_lib.lib().yt8m_memory_link_fwd(n, (ctypes.c_void_p * n)(*[t.data_ptr() for t in srcs]), widths, int(normalize), _p(y),
+                                                   _p(rinv), rows, float(eps), _stream()))
+        ctx.normalize, ctx.eps, ctx.widths = bool(normalize), float(eps), widths
+        if normalize:
+            ctx.save_for_backward(y, rinv)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, rinv = ctx.saved_tensors if ctx.normalize else (None, None)
+        dy = _f32c(dy)
+        n = len(ctx.widths)
+        grads = [torch.empty((dy.shape[0], ctx.widths[s]), dtype=torch.float32, device=dy.device) if ctx.needs_input_grad[2 + s] else None
+                 for s in range(n)]
+        _lib.check(_lib.lib().yt8m_memory_link_bwd(n, ctx.widths, int(ctx.normalize), _p(y), _p(rinv), _p(dy),
+                                                   (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in grads]),
+                                                   dy.shape[0], ctx.eps, _stream()))
+        return (None, None) + tuple(grads)
+
+
+def memory_link(tensors, normalize, eps=1e-12):
+    """[B, sum w_s]: the [B, w_s] tensors side by side and, with normalize, l2-normalised along the row -- what turns the final memories of
+    the multi-LSTM chain plugins' stacks into a stage's classifier input (W/all_frame_models/lstm_memory_deep_chain_model.py:72,
+    distillchain_lstm_memory_deep_combine_chain_model.py:57,74).  1 to 16 tensors.  The backward pass hands every input one contiguous
+    gradient of its own (the stack's dc_final operands).
+    YT8M_MEMORY_LINK_FUSED (read at import): 0, the default, is torch.cat and ops.l2_normalize; 1 is the fused kernel."""
+    tensors = list(tensors)
+    if not 1 <= len(tensors) <= 16:
+        raise ValueError("memory_link: 1 to 16 tensors, got %d" % len(tensors))
+    if not MEMORY_LINK_FUSED:
+        cat = torch.cat(tensors, dim=1)
+        return l2_normalize(cat, eps) if normalize else cat
+    return _MemoryLink.apply(bool(normalize), eps, *tensors)
+
+
 class _MoeHead(torch.autograd.Function):
     """MoE block of W/all_video_models/moe_model.py:40-64: two GEMMs + mixing kernel; backward per Appendix G."""
 
