@@ -344,6 +344,25 @@ int yt8m_resolution_mean_u8(const uint8_t* q, const int32_t* num_frames, float* 
                             int64_t D, int64_t resolution, int l2norm, float eps, yt8m_stream_t stream);
 int yt8m_resolution_mean_f32(const float* x, const int32_t* num_frames, float* y, int32_t* num_frames_out, int64_t B, int64_t F,
                              int64_t D, int64_t resolution, int l2norm, float eps, yt8m_stream_t stream);
+/* The frame pyramid of the multi-resolution LSTM plugin (csrc/frame_pyramid.hip;
+ * W/all_frame_models/multires_lstm_memory_deep_combine_chain_model.py:149-165 and :21): every level r = 2, 4, .., 2^levels of
+ * yt8m_resolution_mean_u8's means, split by feature and l2-normalised PER PART, written time-major, in ONE pass over the bytes.
+ *   widths [nseg] (HOST array, 1 <= nseg <= 8, positive, adding up to D): the column parts.
+ *   y [levels * nseg] (HOST array of device pointers, level-major): y[l * nseg + s] is [F / r, B, widths[s]] fp32 contiguous, r = 2^(l+1).
+ *     Group g of video b holds k = clamp(n - g r, 0, r) real frames with byte sums S_c; m_c = (512 S_c - 65025 k) / (32640 r);
+ *     y = m_c / sqrt(max(sum over the part of m^2, eps)), formed in fp64 from the exact integer and rounded to fp32 once.  A group with
+ *     no real frame is a zero row.  Groups past F / r are not written (the coarser levels drop frames the finer ones still use).
+ *   num_frames_out [levels] (HOST array, or NULL, or NULL entries): num_frames_out[l][b] = n / r with n = num_frames[b] clamped to [0, F]
+ *     (num_frames == NULL: n = F).
+ * Level l + 1's integer sums are the sums of two neighbouring groups of level l: every byte is read once.  Fixed summation order, no
+ * atomics.  16-byte accesses where every width % 16 == 0 and every operand is 16-byte aligned, 4-byte ones where every width % 4 == 0,
+ * single bytes otherwise.  levels < 1 or 2^levels > F, nseg or a width out of range, widths not adding up to D, a null operand,
+ * eps <= 0, an output overlapping another operand: YT8M_E_BADARG; a shape yt8m_frame_pyramid_supported refuses (levels > 5, a row wider
+ * than a lane's registers hold: 2048 columns in the 16- and 4-byte forms, 512 in single bytes; the tree of sums past 64 KB of LDS):
+ * YT8M_E_SHAPE.  Nothing is launched then; B == 0 is YT8M_OK with nothing launched. */
+int yt8m_frame_pyramid_u8(const uint8_t* q, const int32_t* num_frames, int64_t B, int64_t F, int64_t D, int levels, int nseg,
+                          const int64_t* widths, float* const* y, int32_t* const* num_frames_out, float eps, yt8m_stream_t stream);
+int yt8m_frame_pyramid_supported(int64_t D, int nseg, const int64_t* widths, int levels);
 
 /* ---- MoE head (W/all_video_models/moe_model.py:54-64) ------------------------------------------
  * Zg [B, V*(M+1)] gate logits (label-major, mixture-minor; gate M = dummy expert), Ze [B, V*M] expert

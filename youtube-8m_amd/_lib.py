@@ -176,6 +176,8 @@ SIGNATURES = {
     "yt8m_chain_link_bwd": (c_int, [c_int, P, P, P, P, P, c_int64, c_int64, c_float, P]),
     "yt8m_memory_link_fwd": (c_int, [c_int, P, P, c_int, P, P, c_int64, c_float, P]),
     "yt8m_memory_link_bwd": (c_int, [c_int, P, c_int, P, P, P, P, c_int64, c_float, P]),
+    "yt8m_frame_pyramid_u8": (c_int, [P, P, c_int64, c_int64, c_int64, c_int, c_int, P, P, P, c_float, P]),
+    "yt8m_frame_pyramid_supported": (c_int, [c_int64, c_int, P, c_int]),
     "yt8m_colsum_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "yt8m_colsum_f32": (c_int, [P, c_int64, c_int64, c_int64, P, c_float, P, c_int64, P]),
     "yt8m_rank1_add_rows_f32": (c_int, [P, c_int64, c_int64, c_int64, P, c_float, P]),

@@ -376,11 +376,11 @@ class LstmAttentionMaxPoolingModel(models.BaseModel):
                                             "gates-" + sub_scope, "experts-" + sub_scope)
 
 
-def _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, number_of_layers, own_slots=False):
-    """One LSTM stack per input feature under scope RNN<i> (W/all_frame_models/lstm_parallel_finaloutput_model.py:34-64,
+def _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, number_of_layers, own_slots=False, scope_prefix="", slot_base=0):
+    """One LSTM stack per input feature under scope <scope_prefix>RNN<i> (W/all_frame_models/lstm_parallel_finaloutput_model.py:34-64,
     lstm_cnn_deep_combine_chain_model.py:139-174): the input is split by feature_sizes and each part re-normalised; a part that arrives
-    as bytes goes to _stack_input as bytes (see LstmParallelFinaloutputModel).  own_slots: stack i takes slot=i -- for a caller that keeps
-    the stacks' outputs alive together.  Returns [(top outputs time-major [F,B,H_i], finals)] per part."""
+    as bytes goes to _stack_input as bytes (see LstmParallelFinaloutputModel).  own_slots: stack i takes slot = slot_base + i -- for a
+    caller that keeps the stacks' outputs alive together.  Returns [(top outputs time-major [F,B,H_i], finals)] per part."""
     assert len(lstm_sizes) == len(feature_sizes), \
         "length of lstm_sizes (={}) != length of feature_sizes (={})".format(len(lstm_sizes), len(feature_sizes))
     assert sum(feature_sizes) == model_input.shape[2], "feature_sizes do not add up to the input width"
@@ -390,7 +390,8 @@ def _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, number_
         if sub_input.dtype != torch.uint8:                        # (bytes: _stack_input reads them or dequantises + normalises the slice)
             sub_input = ops.l2_normalize(sub_input)
         off += fs
-        res.append(_lstm_stack(sub_input, num_frames, hs, number_of_layers, scope="RNN%d" % i, **(dict(slot=i) if own_slots else {})))
+        res.append(_lstm_stack(sub_input, num_frames, hs, number_of_layers, scope="%sRNN%d" % (scope_prefix, i),
+                               **(dict(slot=slot_base + i) if own_slots else {})))
     return res
 
 
@@ -752,6 +753,130 @@ class LstmParallelMemoryModel(models.BaseModel):
         stacks = _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, FLAGS.lstm_layers, own_slots=True)
         final_state = ops.memory_link([c for _, finals in stacks for c, _ in finals], normalize=False)
         return _head()().create_model(model_input=final_state, original_input=model_input, vocab_size=vocab_size,
+                                      **unused_params)
+
+
+def _time_major_stacks(parts_tm, num_frames, lstm_sizes, number_of_layers, scope_prefix, slot_base):
+    """_parallel_stacks for parts that are prepared already: parts_tm[i] float32 [T, B, w_i] time-major and l2-normalised (a level of
+    ops.frame_pyramid, or the hopped outputs of the level below).  Stack i runs under scope <scope_prefix>RNN<i> in slot slot_base + i;
+    a part that requires a gradient gets one (the native stack's dx).  Returns [(top outputs [T,B,H_i], finals)]."""
+    assert len(lstm_sizes) == len(parts_tm), \
+        "length of lstm_sizes (={}) != length of feature_sizes (={})".format(len(lstm_sizes), len(parts_tm))
+    g = get_default_graph()
+    res = []
+    for i, (x_tm, hs) in enumerate(zip(parts_tm, lstm_sizes)):
+        with g.variable_scope("%sRNN%d" % (scope_prefix, i)):
+            wb = _lstm_cells(x_tm.shape[2], hs, number_of_layers)
+        res.append(_native_stack(x_tm, num_frames, wb, slot=slot_base + i))
+    return res
+
+
+def _length_code(num_frames):
+    """get_length_code of the temporal-pooling plugins: [B,5] one-hot float32 over num_frames <= 60, <= 120, <= 180, <= 240, > 240."""
+    n = num_frames.view(-1, 1)
+    edges = torch.tensor([60, 120, 180, 240], device=n.device, dtype=n.dtype)
+    bucket = (n > edges).sum(dim=1)
+    return torch.nn.functional.one_hot(bucket, 5).to(torch.float32)
+
+
+class MultiresLstmMemoryDeepCombineChainModel(models.BaseModel):
+    """W/all_frame_models/multires_lstm_memory_deep_combine_chain_model.py:13-165: DeepCombineChainModel's chain whose stage i reads the
+    final memories of a fresh tower of per-feature LSTM stacks (lstm<i>RNN<j>, no hyphen) over the frames at resolution
+    r_i = 2^(deep_chain_layers - i): the mean over every r frames, split by --feature_sizes, every part l2-normalised, num_frames // r
+    steps.  next_input = [memories (stack-major, then layer) | length code with --deep_chain_use_length | l2norm(relu-<l>(prediction-<l>))
+    of every earlier stage]; dropout on the support stages' inputs only.  Every level r >= 2 comes from ONE ops.frame_pyramid call, r = 1
+    goes through _parallel_stacks; the memories of a stage are an ops.memory_link, every relu -> (noise) -> l2norm an ops.chain_link.
+    accepts_quantized_input is False on purpose: elsewhere here uint8 frames at create_model stand for the DefaultTransformer's output
+    (dequantised AND l2-normalised), and for this model the mean of normalised frames is not the mean of raw frames -- so the trainer folds
+    nothing.  Under --feature_transformer=IdenticalTransformer (the training script's) the reader's bytes arrive as they are and mean
+    what the reference's reader delivers: dequantised, padding zero, not normalised -- the pyramid kernel's path.  Under
+    DefaultTransformer the model receives the normalised floats and averages those, as the reference would."""
+    accepts_quantized_input = False
+
+    def create_model(self, model_input, vocab_size, num_frames, num_mixtures=None, l2_penalty=1e-8, sub_scope="", original_input=None,
+                     dropout=False, keep_prob=None, noise_level=None, **unused_params):
+        num_layers = FLAGS.deep_chain_layers
+        relu_cells = FLAGS.deep_chain_relu_cells
+        relu_type = "elu" if FLAGS.deep_chain_relu_type == "elu" else "relu"
+        number_of_layers = FLAGS.lstm_layers
+        lstm_sizes = [int(v) for v in str(FLAGS.lstm_cells).split(",")]
+        feature_sizes = [int(v) for v in str(FLAGS.feature_sizes).split(",")]
+        assert len(lstm_sizes) == len(feature_sizes), \
+            "length of lstm_sizes (={}) != length of feature_sizes (={})".format(len(lstm_sizes), len(feature_sizes))
+        B, F, D = model_input.shape
+        if F < (1 << num_layers):
+            raise ValueError("MultiresLstmMemoryDeepCombineChainModel: %d frames are fewer than the coarsest resolution 2^%d: its LSTMs "
+                             "would run over zero frames" % (F, num_layers))
+        n = len(feature_sizes)
+        seq_ops.reserve_resident((num_layers + 1) * n, number_of_layers)
+        additional_features = [_length_code(num_frames)] if FLAGS.deep_chain_use_length else []
+        parts, frames = ops.frame_pyramid(model_input, num_frames, num_layers, feature_sizes) if num_layers else ([], [])
+
+        def memories(stage):
+            level = num_layers - stage - 1                                  # resolution 2^(level + 1); -1: the frames themselves
+            if level < 0:
+                stacks = _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, number_of_layers, own_slots=True,
+                                          scope_prefix="lstm%d" % stage, slot_base=stage * n)
+            else:
+                stacks = _time_major_stacks(parts[level], frames[level], lstm_sizes, number_of_layers, "lstm%d" % stage, stage * n)
+            return ops.memory_link([c for _, finals in stacks for c, _ in finals], normalize=False)
+
+        next_input = torch.cat([memories(0)] + additional_features, dim=1)
+        support_predictions = []
+        for layer in range(num_layers):
+            sub_prediction = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "prediction-%d" % layer, dropout=dropout,
+                                            keep_prob=keep_prob)
+            support_predictions.append(sub_prediction)
+            sub_activation = video_level_models.fully_connected(sub_prediction, relu_cells, sub_scope + "relu-%d" % layer,
+                                                                l2_penalty=l2_penalty)
+            additional_features.append(ops.chain_link(sub_activation, relu_type, noise_level))
+            next_input = torch.cat([memories(layer + 1)] + additional_features, dim=1)
+        main_predictions = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "-main")
+        res = {"predictions": main_predictions}
+        if support_predictions:
+            res["support_predictions"] = torch.cat(support_predictions, dim=1)
+        return res
+
+    def sub_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", dropout=False, keep_prob=None,
+                  **unused_params):
+        num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
+        if dropout:                                                         # :108-110 tf.nn.dropout on the stage's whole input
+            model_input = ops.dropout(model_input, 1.0 if keep_prob is None else keep_prob)
+        return video_level_models.moe_block(model_input, vocab_size, num_mixtures, l2_penalty, "gates-" + sub_scope, "experts-" + sub_scope)
+
+
+class FramehopLstmMemoryModel(models.BaseModel):
+    """W/all_frame_models/framehop_lstm_memory_model.py:13-126: a tower of per-feature LSTM stacks (lstm<k>RNN<i>), level 0 over the
+    l2-normalised frames, level k >= 1 over l2norm(rows 1, 3, 5, .. of the top outputs of stack i of level k - 1): T_k = T_{k-1} // 2
+    rows, input width and cells both H_i.  Every level k >= 1 is handed the ORIGINAL num_frames // 2 (:81), and dynamic_rnn runs no
+    further than its input: min(num_frames // 2, T_k) steps, formed on the device.  Outputs past a video's length are zero rows and are
+    hopped as they are.  Head input = every level's final memories, level-major, then stack, then layer (torch.cat: 20 tensors at the
+    script's settings, more than ops.memory_link takes).  Gradients flow from every level through the hop into the level below.
+    accepts_quantized_input: level 0 normalises per feature, so the bytes' two meanings agree, as in LstmParallelMemoryModel."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, **unused_params):
+        if FLAGS.deep_chain_use_length:
+            raise ValueError("FramehopLstmMemoryModel: --deep_chain_use_length reaches an undefined name (additional_features) in the "
+                             "reference (framehop_lstm_memory_model.py:73); there is nothing to reproduce")
+        num_layers = FLAGS.deep_chain_layers
+        number_of_layers = FLAGS.lstm_layers
+        lstm_sizes = [int(v) for v in str(FLAGS.lstm_cells).split(",")]
+        feature_sizes = [int(v) for v in str(FLAGS.feature_sizes).split(",")]
+        n = len(feature_sizes)
+        seq_ops.reserve_resident((num_layers + 1) * n, number_of_layers)
+        stacks = _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, number_of_layers, own_slots=True, scope_prefix="lstm0")
+        states = [c for _, finals in stacks for c, _ in finals]
+        half = torch.div(num_frames, 2, rounding_mode="floor")
+        for k in range(1, num_layers + 1):
+            T = stacks[0][0].shape[0] // 2
+            if T < 1:
+                raise ValueError("FramehopLstmMemoryModel: level %d of the tower has no frames left (%d at level 0)" % (k, model_input.shape[1]))
+            hopped = [ops.l2_normalize(out[1:2 * T:2].contiguous()) for out, _ in stacks]
+            stacks = _time_major_stacks(hopped, half.clamp(max=T), lstm_sizes, number_of_layers, "lstm%d" % k, k * n)
+            states.extend(c for _, finals in stacks for c, _ in finals)
+        final_states = torch.cat(states, dim=1)
+        return _head()().create_model(model_input=final_states, original_input=model_input, vocab_size=vocab_size, num_frames=num_frames,
                                       **unused_params)
 
 

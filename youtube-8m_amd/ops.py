@@ -583,6 +583,55 @@ def resolution_mean(x, num_frames, resolution, l2norm=True, eps=1e-12):
     return y, nf_out
 
 
+# anything but 0 (the default): frame_pyramid runs csrc/frame_pyramid.hip on the reader's bytes where it covers the shape; 0: every level
+# is composed from resolution_mean, slices, l2_normalize and a transpose copy (A/B runs, tests).  The rule for the default and the
+# measurements behind it: DESIGN_LOG.md section 24.
+FRAME_PYRAMID_FUSED = os.environ.get("YT8M_FRAME_PYRAMID_FUSED", "1") != "0"
+
+
+def frame_pyramid_supported(D, widths, levels):
+    widths = [int(w) for w in widths]
+    return bool(_lib.lib().yt8m_frame_pyramid_supported(int(D), len(widths), (ctypes.c_int64 * len(widths))(*widths), int(levels)))
+
+
+def frame_pyramid(x, num_frames, levels, widths, eps=1e-12):
+    """The coarse inputs of the multi-resolution LSTM plugin (W/all_frame_models/multires_lstm_memory_deep_combine_chain_model.py:149-165,
+    :21): uint8 or float32 frames [B,F,D] -> (parts, num_frames_out) with parts[l][s] float32 [F // r, B, widths[s]] TIME-major for
+    r = 2^(l+1), l < levels -- the mean over every r frames (resolution_mean's: dequantised bytes with the padding frames 0, floats as
+    they are; the divisor always r), split by widths and every part l2-normalised -- and num_frames_out[l] = num_frames // r [B] int32 on
+    the device.  uint8: one pass over the bytes writes every level (csrc/frame_pyramid.hip) where yt8m_frame_pyramid_supported holds and
+    FRAME_PYRAMID_FUSED is on; everything else composes resolution_mean(l2norm=False) -> slice -> l2_normalize -> transpose copy per
+    level.  Frames are data: no gradient."""
+    x, nf = _frames_nf(x, num_frames)
+    B, F, D = x.shape
+    levels, widths = int(levels), [int(w) for w in widths]
+    if levels < 1 or (1 << levels) > F:
+        raise ValueError("frame_pyramid: levels must be >= 1 with 2^levels <= F = %d, got %d" % (F, levels))
+    if not widths or min(widths) <= 0 or sum(widths) != D:
+        raise ValueError("frame_pyramid: widths %s do not partition the %d columns" % (widths, D))
+    if x.dtype not in (torch.uint8, torch.float32):
+        raise TypeError("expected uint8 or float32 frames, got %s" % x.dtype)
+    if x.dtype == torch.uint8 and FRAME_PYRAMID_FUSED and x.data_ptr() % 16 == 0 and frame_pyramid_supported(D, widths, levels):
+        n = len(widths)
+        parts = [[torch.empty((F >> (l + 1), B, w), dtype=torch.float32, device=x.device) for w in widths] for l in range(levels)]
+        nf_out = [torch.empty((B,), dtype=torch.int32, device=x.device) for _ in range(levels)]
+        _lib.check(_lib.lib().yt8m_frame_pyramid_u8(_p(x), _p(nf), B, F, D, levels, n, (ctypes.c_int64 * n)(*widths),
+                                                    (ctypes.c_void_p * (levels * n))(*[t.data_ptr() for row in parts for t in row]),
+                                                    (ctypes.c_void_p * levels)(*[t.data_ptr() for t in nf_out]), eps, _stream()))
+        return parts, nf_out
+    parts, nf_out = [], []
+    with torch.no_grad():
+        for l in range(levels):
+            y, n_l = resolution_mean(x, nf, 2 << l, l2norm=False, eps=eps)
+            row, off = [], 0
+            for w in widths:
+                row.append(l2_normalize(y[:, :, off:off + w].contiguous(), eps).transpose(0, 1).contiguous())
+                off += w
+            parts.append(row)
+            nf_out.append(n_l)
+    return parts, nf_out
+
+
 def moe_mix_fwd(Zg, Ze, V, M):
     _dev(Zg, Ze)
     B = Zg.shape[0]

@@ -452,6 +452,16 @@ def _stack_scratch(dev, main, desc, slot=0):
     return _STACK_SCRATCH.buffer(key, need, dev, (main, desc), _STACK_SCRATCH_MAX)
 
 
+def reserve_resident(stacks, layers):
+    """Room in the two resident tables for a plugin that keeps `stacks` LSTM stacks of `layers` layers alive between its forward and its
+    backward pass, each under a key of its own (slot, shape): _STACK_SCRATCH_MAX becomes at least `stacks` and _PERSIST_WS_MAX at least
+    stacks * layers.  Never lowers either (YT8M_STACK_SCRATCH_MAX and an earlier, larger reservation stay).  With smaller tables every
+    step of such a plugin would evict -- synchronise on, free and re-zero -- buffers that the very next step needs again."""
+    global _STACK_SCRATCH_MAX, _PERSIST_WS_MAX
+    _STACK_SCRATCH_MAX = max(_STACK_SCRATCH_MAX, int(stacks))
+    _PERSIST_WS_MAX = max(_PERSIST_WS_MAX, int(stacks) * int(layers))
+
+
 def check_persist_errors():
     """Synchronises and raises if ANY persistent-recurrence launch since the previous check gave up waiting for a tile (bounded
     spins set a sticky error word instead of hanging the GPU; no later launch clears it).  The training loop calls this at its
