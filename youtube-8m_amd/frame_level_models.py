@@ -7,6 +7,8 @@ import math
 import torch
 
 from . import models, model_utils, ops, seq_ops, video_level_models
+from .video_level_models import (composed_link, distill_link as _distill_link, fused_link, moe_stage, prediction_chain, relu_kind,
+                                 relu_link)
 from .flags import FLAGS, DEFINE_integer, DEFINE_bool, DEFINE_string
 from .variables import get_default_graph, xavier_uniform, zeros, ones, random_normal
 
@@ -42,6 +44,19 @@ DEFINE_bool("netvlad_add_batch_norm", False, "Kept False so examples stay indepe
 
 def _head(name=None):
     return getattr(video_level_models, name or FLAGS.video_level_classifier_model)
+
+
+def _classify(head_input, model_input, vocab_size, **params):
+    """The video-level classifier (--video_level_classifier_model) on head_input; params: what the calling plugin forwards to it."""
+    return _head()().create_model(model_input=head_input, original_input=model_input, vocab_size=vocab_size, **params)
+
+
+def _sizes_per_feature():
+    """(--lstm_cells, --feature_sizes) as lists of ints: one LSTM size per input feature."""
+    lstm_sizes, feature_sizes = ([int(v) for v in str(flag).split(",")] for flag in (FLAGS.lstm_cells, FLAGS.feature_sizes))
+    assert len(lstm_sizes) == len(feature_sizes), \
+        "length of lstm_sizes (={}) != length of feature_sizes (={})".format(len(lstm_sizes), len(feature_sizes))
+    return lstm_sizes, feature_sizes
 
 
 def _lib_u8_ok(D):
@@ -147,8 +162,7 @@ class LstmModel(models.BaseModel):
         number_of_layers = FLAGS.lstm_layers
         _, finals = _lstm_stack(model_input, num_frames, lstm_size, number_of_layers)
         state = torch.cat([t for pair in finals for t in pair], dim=1)
-        return _head()().create_model(model_input=state, original_input=model_input, vocab_size=vocab_size,
-                                      **unused_params)
+        return _classify(state, model_input, vocab_size, **unused_params)
 
 
 def _bidirectional_stacks(model_input, num_frames, lstm_size, number_of_layers, multi):
@@ -184,7 +198,7 @@ class BiLstmModel(models.BaseModel):
         lstm_size = int(FLAGS.lstm_cells)
         (_, fin_fw), (_, fin_bw) = _bidirectional_stacks(model_input, num_frames, lstm_size, FLAGS.lstm_layers, multi=True)
         state = torch.cat([t for pair in fin_fw + fin_bw for t in pair], dim=1)
-        return _head()().create_model(model_input=state, original_input=model_input, vocab_size=vocab_size, **unused_params)
+        return _classify(state, model_input, vocab_size, **unused_params)
 
 
 class BiUniLstmModel(models.BaseModel):
@@ -204,7 +218,7 @@ class BiUniLstmModel(models.BaseModel):
             wb2 = _lstm_cells(2 * lstm_size, lstm_size, 1, multi=False)
         _, fin2 = _native_stack(l1, num_frames, wb2, slot=2)
         state = torch.cat([t for pair in fin_fw + fin_bw + fin2 for t in pair], dim=1)
-        return _head()().create_model(model_input=state, original_input=model_input, vocab_size=vocab_size, **unused_params)
+        return _classify(state, model_input, vocab_size, **unused_params)
 
 
 class LstmMemoryModel(models.BaseModel):
@@ -221,8 +235,7 @@ class LstmMemoryModel(models.BaseModel):
         final_state = torch.cat([c for c, _ in finals], dim=1)
         if noise_level is not None:
             final_state = ops.add_noise(final_state, noise_level)
-        return _head()().create_model(model_input=final_state, original_input=model_input, vocab_size=vocab_size,
-                                      num_frames=num_frames, **unused_params)
+        return _classify(final_state, model_input, vocab_size, num_frames=num_frames, **unused_params)
 
 
 def _hoisted_input(model_input, num_frames):
@@ -271,8 +284,7 @@ class GruPoolingModel(models.BaseModel):
     def create_model(self, model_input, vocab_size, num_frames, **unused_params):
         out_tm, _ = _gru_stack(model_input, num_frames, FLAGS.gru_cells, FLAGS.gru_layers)
         pooling_output = _mean_over_frames(out_tm, num_frames)
-        return _head()().create_model(model_input=pooling_output, original_input=model_input, vocab_size=vocab_size,
-                                      **unused_params)
+        return _classify(pooling_output, model_input, vocab_size, **unused_params)
 
 
 class GruWithPoolingModel(models.BaseModel):
@@ -283,8 +295,7 @@ class GruWithPoolingModel(models.BaseModel):
     def create_model(self, model_input, vocab_size, num_frames, **unused_params):
         out_tm, finals = _gru_stack(model_input, num_frames, FLAGS.gru_cells, FLAGS.gru_layers)
         final_output = torch.cat([_mean_over_frames(out_tm, num_frames)] + finals, dim=1)
-        return _head()().create_model(model_input=final_output, original_input=model_input, vocab_size=vocab_size,
-                                      **unused_params)
+        return _classify(final_output, model_input, vocab_size, **unused_params)
 
 
 LN_GATES = ("input", "transform", "forget", "output", "state")
@@ -316,8 +327,7 @@ class LayerNormLstmMemoryModel(models.BaseModel):
         final_state = torch.cat(cs, dim=1)
         if noise_level is not None:
             final_state = ops.add_noise(final_state, noise_level)
-        return _head()().create_model(model_input=final_state, original_input=model_input, vocab_size=vocab_size,
-                                      **unused_params)
+        return _classify(final_state, model_input, vocab_size, **unused_params)
 
 
 def _attention_fc_u8(q, num_frames, parts, num_outputs, scope, l2_penalty, rs=None):
@@ -370,10 +380,8 @@ class LstmAttentionMaxPoolingModel(models.BaseModel):
         """What sub_moe reads, from the attention outputs [B,A,H]: the attention outputs."""
         return attention_outputs
 
-    def sub_moe(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", **unused_params):
-        num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
-        return video_level_models.moe_block(model_input, vocab_size, num_mixtures, l2_penalty,
-                                            "gates-" + sub_scope, "experts-" + sub_scope)
+    def sub_moe(self, model_input, vocab_size, **params):
+        return moe_stage(model_input, vocab_size, **params)
 
 
 def _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, number_of_layers, own_slots=False, scope_prefix="", slot_base=0):
@@ -381,8 +389,6 @@ def _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, number_
     lstm_cnn_deep_combine_chain_model.py:139-174): the input is split by feature_sizes and each part re-normalised; a part that arrives
     as bytes goes to _stack_input as bytes (see LstmParallelFinaloutputModel).  own_slots: stack i takes slot = slot_base + i -- for a
     caller that keeps the stacks' outputs alive together.  Returns [(top outputs time-major [F,B,H_i], finals)] per part."""
-    assert len(lstm_sizes) == len(feature_sizes), \
-        "length of lstm_sizes (={}) != length of feature_sizes (={})".format(len(lstm_sizes), len(feature_sizes))
     assert sum(feature_sizes) == model_input.shape[2], "feature_sizes do not add up to the input width"
     res, off = [], 0
     for i, (fs, hs) in enumerate(zip(feature_sizes, lstm_sizes)):
@@ -403,14 +409,16 @@ class LstmParallelFinaloutputModel(models.BaseModel):
     other slices are dequantised and normalised as floats."""
     accepts_quantized_input = True
 
+    def _head_extras(self, **unused_params):
+        """(what stands behind the stacks' final h in the head input, the parameters left for the head)."""
+        return [], unused_params
+
     def create_model(self, model_input, vocab_size, num_frames, **unused_params):
-        number_of_layers = FLAGS.lstm_layers
-        lstm_sizes = [int(v) for v in str(FLAGS.lstm_cells).split(",")]
-        feature_sizes = [int(v) for v in str(FLAGS.feature_sizes).split(",")]
-        states = [h for _, finals in _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, number_of_layers) for _, h in finals]
-        final_state = torch.cat(states, dim=1)
-        return _head()().create_model(model_input=final_state, original_input=model_input, vocab_size=vocab_size,
-                                      **unused_params)
+        extras, unused_params = self._head_extras(**unused_params)
+        lstm_sizes, feature_sizes = _sizes_per_feature()
+        states = [h for _, finals in _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, FLAGS.lstm_layers) for _, h in finals]
+        final_state = torch.cat(states + extras, dim=1)
+        return _classify(final_state, model_input, vocab_size, **unused_params)
 
 
 class LstmPositionalAttentionMaxPoolingModel(LstmAttentionMaxPoolingModel):
@@ -454,7 +462,8 @@ def _einsum_cnn(model_input, fvars):
 class CnnDeepCombineChainModel(models.BaseModel):
     """W/all_frame_models/cnn_deep_combine_chain_model.py:10-140: chain of MoE sub-predictions whose inputs are max-pooled
     "einsum CNNs" over the frames (filter lengths 1,2,3 = GEMMs on the input concatenated with its 1- and 2-frame shifts),
-    the masked mean input and the l2-normalised relu projections of the previous predictions.
+    the masked mean input and the l2-normalised relu projections of the previous predictions (the loop: video_level_models.prediction_chain
+    with composed links; stage 0 reads cnn0 alone, a later stage [mean_input | cnn_k | mean-relu | relu-0 ..]).
     accepts_quantized_input: on the reader's bytes every CNN of the chain reads ONE half image of the frames (seq_ops.u8_cnn: a shift by
     i frames is a row offset in time-major order -- no concatenated [B,F,2D] / [B,F,3D] tensors, no fp32 copy of the frames), the mean
     frame comes from the bytes too."""
@@ -466,34 +475,25 @@ class CnnDeepCombineChainModel(models.BaseModel):
 
     def create_model(self, model_input, vocab_size, num_frames, num_mixtures=None, l2_penalty=1e-8, sub_scope="",
                      original_input=None, **unused_params):
-        num_layers = FLAGS.deep_chain_layers
         relu_cells = FLAGS.deep_chain_relu_cells
-        B, F, D = model_input.shape
+        model_input, frames, mean_input = self._frames_and_mean(model_input, num_frames)
+        links = [relu_link(mean_input, relu_cells, sub_scope + "mean-relu", l2_penalty, composed_link("relu"))]
+        frozen = 0 if mean_input.requires_grad else model_input.shape[2]      # the mean frame in front of a later stage's input is data
+
+        def stage_input(k, links):                                  # cnn<k>'s variables are made here: after relu-<k - 1>
+            cnn_output = self._pooled_cnn(model_input, frames, sub_scope + "cnn%d" % k, relu_cells, l2_penalty)
+            return torch.cat([mean_input, cnn_output] + links, dim=1) if k else cnn_output
+
+        return prediction_chain(self.sub_model, stage_input, composed_link("relu"), links, vocab_size, l2_penalty, sub_scope,
+                                frozen_cols=lambda k: frozen if k else 0)
+
+    def _frames_and_mean(self, model_input, num_frames):
+        """(the frames as the chain's CNNs read them, their byte image -- ONE for every CNN of the chain, None for float frames --, the mean
+        frame [B,D])."""
         model_input, u8 = _bytes_or_floats(model_input, num_frames, lambda q: seq_ops.u8_cnn_supported(q) and
                                            seq_ops.u8_attention_supported(q, 1))
-        frames = seq_ops.U8FrameImages(model_input, num_frames) if u8 else None   # one byte image for every CNN of the chain
-        mean_input = _mean_frame(model_input, num_frames)
-        mean_relu = video_level_models.fully_connected(mean_input, relu_cells, sub_scope + "mean-relu", activation="relu",
-                                                       l2_penalty=l2_penalty)
-        relu_layers = [ops.l2_normalize(mean_relu)]
-
-        def pooled_cnn(scope):
-            return self._pooled_cnn(model_input, frames, scope, relu_cells, l2_penalty)
-
-        next_input = pooled_cnn(sub_scope + "cnn0")
-        frozen = 0
-        support_predictions = []
-        for layer in range(num_layers):
-            sub_prediction = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "prediction-%d" % layer, frozen_cols=frozen)
-            support_predictions.append(sub_prediction)
-            sub_relu = video_level_models.fully_connected(sub_prediction, relu_cells, sub_scope + "relu-%d" % layer,
-                                                          activation="relu", l2_penalty=l2_penalty)
-            relu_layers.append(ops.l2_normalize(sub_relu))
-            normalized_cnn_output = pooled_cnn(sub_scope + "cnn%d" % (layer + 1))
-            next_input = torch.cat([mean_input, normalized_cnn_output] + relu_layers, dim=1)
-            frozen = 0 if mean_input.requires_grad else D           # the mean frame in front of the stage's input is data
-        main_predictions = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "-main", frozen_cols=frozen)
-        return {"predictions": main_predictions, "support_predictions": torch.cat(support_predictions, dim=1)}
+        frames = seq_ops.U8FrameImages(model_input, num_frames) if u8 else None
+        return model_input, frames, _mean_frame(model_input, num_frames)
 
     def _pooled_cnn(self, model_input, frames, scope, relu_cells, l2_penalty):
         """l2_normalize(reduce_max over the frames of the chain's CNN under `scope`) [B, 4 relu_cells]; frames: the byte image of the
@@ -508,10 +508,8 @@ class CnnDeepCombineChainModel(models.BaseModel):
             cnn_output = self.cnn(model_input, sub_scope=scope, l2_penalty=l2_penalty, **filters)
         return ops.l2_normalize(ops.frame_pool(cnn_output, "max"))      # reduce_max over ALL max_frames rows, as the reference
 
-    def sub_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", frozen_cols=0, **unused_params):
-        num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
-        return video_level_models.moe_block(model_input, vocab_size, num_mixtures, l2_penalty,
-                                            "gates-" + sub_scope, "experts-" + sub_scope, frozen_cols=frozen_cols)
+    def sub_model(self, model_input, vocab_size, **params):
+        return moe_stage(model_input, vocab_size, **params)
 
 
 def _pooled_cnn_chain(lstm_output_tm, cnns):
@@ -527,7 +525,7 @@ class LstmCnnDeepCombineChainModel(models.BaseModel):
     """W/all_frame_models/lstm_cnn_deep_combine_chain_model.py:10-174: one LSTM stack per input feature (RNN<i>, as
     LstmParallelFinaloutputModel), their OUTPUTS concatenated [B,F,sum H_i] (zeros at frames >= num_frames); deep_chain_layers + 1 einsum CNNs
     (filter lengths 1, 2, 3; c, 2c, c filters for cnn0 and c, c, 2c for the others, c = --deep_chain_relu_cells) over that, each max-pooled
-    over all max_frames rows and l2-normalised; a chain of MoE sub-predictions: stage 0 reads cnn0 alone, stage l + 1 reads
+    over all max_frames rows and l2-normalised; a chain of MoE sub-predictions (prediction_chain): stage 0 reads cnn0 alone, stage l + 1 reads
     [cnn_{l+1} | mean-relu | relu-0 .. relu-l] (no mean_input columns, unlike CnnDeepCombineChainModel).  None of the CNNs depends on a
     prediction: they run as one op (_pooled_cnn_chain) on the stacks' time-major outputs, no transpose to batch-major.
     Variables: RNN<i>/multi_rnn_cell/cell_<l>/basic_lstm_cell/{weights,biases}, cnn<k>cnn-filter-len{1,2,3}, mean-relu, relu-<l>,
@@ -543,35 +541,22 @@ class LstmCnnDeepCombineChainModel(models.BaseModel):
                      original_input=None, **unused_params):
         num_layers = FLAGS.deep_chain_layers
         relu_cells = FLAGS.deep_chain_relu_cells
-        lstm_sizes = [int(v) for v in str(FLAGS.lstm_cells).split(",")]
-        feature_sizes = [int(v) for v in str(FLAGS.feature_sizes).split(",")]
-        relu_layers, early = self._first_relu_layers(l2_penalty, **unused_params)
+        lstm_sizes, feature_sizes = _sizes_per_feature()
+        links, early = self._first_relu_layers(l2_penalty, **unused_params)
         model_input, _ = _bytes_or_floats(model_input, num_frames, lambda q: seq_ops.u8_attention_supported(q, 1))
         mean_input = _mean_frame(model_input, num_frames)
         stacks = _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, FLAGS.lstm_layers, own_slots=True)
         lstm_output = torch.cat([out_tm for out_tm, _ in stacks], dim=2)                   # [F,B,sum H_i] time-major
-        mean_relu = video_level_models.fully_connected(mean_input, relu_cells, sub_scope + "mean-relu", activation="relu",
-                                                       l2_penalty=l2_penalty)
-        relu_layers.append(ops.l2_normalize(mean_relu))
+        links.append(relu_link(mean_input, relu_cells, sub_scope + "mean-relu", l2_penalty, composed_link("relu")))
         D = lstm_output.shape[2]
         cnns = [_cnn_filters(D, sub_scope + "cnn%d" % k, [relu_cells, 2 * relu_cells, relu_cells] if k == 0 else
                              [relu_cells, relu_cells, 2 * relu_cells], [1, 2, 3], l2_penalty) for k in range(num_layers + 1)]
         pooled = [ops.l2_normalize(p) for p in _pooled_cnn_chain(lstm_output, cnns)]
-        next_input = torch.cat([pooled[0]] + relu_layers, dim=1) if early else pooled[0]
-        support_predictions = []
-        for layer in range(num_layers):
-            sub_prediction = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "prediction-%d" % layer)
-            support_predictions.append(sub_prediction)
-            sub_relu = video_level_models.fully_connected(sub_prediction, relu_cells, sub_scope + "relu-%d" % layer,
-                                                          activation="relu", l2_penalty=l2_penalty)
-            relu_layers.append(ops.l2_normalize(sub_relu))
-            next_input = torch.cat([pooled[layer + 1]] + relu_layers, dim=1)
-        main_predictions = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "-main")
-        return {"predictions": main_predictions, "support_predictions": torch.cat(support_predictions, dim=1)}
+        return prediction_chain(self.sub_model, lambda k, links: torch.cat([pooled[k]] + links, dim=1) if k or early else pooled[0],
+                                composed_link("relu"), links, vocab_size, l2_penalty, sub_scope)
 
-    def sub_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", **unused_params):
-        num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
-        return video_level_models.moe_block(model_input, vocab_size, num_mixtures, l2_penalty, "gates-" + sub_scope, "experts-" + sub_scope)
+    def sub_model(self, model_input, vocab_size, **params):
+        return moe_stage(model_input, vocab_size, **params)
 
 
 class DistillchainLstmCnnDeepCombineChainModel(LstmCnnDeepCombineChainModel):
@@ -580,19 +565,7 @@ class DistillchainLstmCnnDeepCombineChainModel(LstmCnnDeepCombineChainModel):
     and whose stage 0 already reads [cnn0 | relu_layers]."""
 
     def _first_relu_layers(self, l2_penalty, distillation_predictions=None, **unused_params):
-        assert distillation_predictions is not None, "distillation feature must be used"
-        distill_relu = video_level_models.fully_connected(distillation_predictions.to(torch.float32), FLAGS.distillchain_relu_cells,
-                                                          "distillrelu", activation="relu", l2_penalty=l2_penalty)
-        return [ops.l2_normalize(distill_relu)], True
-
-
-def _distill_link(distillation_predictions, relu_cells, l2_penalty, scope="distillrelu"):
-    """l2_normalize(relu(FC(distillation_predictions))) [B, relu_cells] under `scope`, as one link (ops.chain_link): what the
-    Distillchain plugins below concatenate into their classifiers' inputs."""
-    assert distillation_predictions is not None, "distillation feature must be used"
-    distill_activation = video_level_models.fully_connected(distillation_predictions.to(torch.float32), relu_cells, scope,
-                                                            l2_penalty=l2_penalty)
-    return ops.chain_link(distill_activation, "relu")
+        return [_distill_link(distillation_predictions, FLAGS.distillchain_relu_cells, l2_penalty, link=composed_link("relu"))], True
 
 
 class DistillchainLstmParallelFinaloutputModel(LstmParallelFinaloutputModel):
@@ -600,15 +573,8 @@ class DistillchainLstmParallelFinaloutputModel(LstmParallelFinaloutputModel):
     [final h of every layer of every stack | distill_norm] ("distillrelu", --distillchain_relu_cells wide, over another model's
     predictions).  Reads bytes on its parent's terms (_parallel_stacks)."""
 
-    def create_model(self, model_input, vocab_size, num_frames, distillation_predictions=None, l2_penalty=1e-8, **unused_params):
-        distill_norm = _distill_link(distillation_predictions, FLAGS.distillchain_relu_cells, l2_penalty)
-        number_of_layers = FLAGS.lstm_layers
-        lstm_sizes = [int(v) for v in str(FLAGS.lstm_cells).split(",")]
-        feature_sizes = [int(v) for v in str(FLAGS.feature_sizes).split(",")]
-        states = [h for _, finals in _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, number_of_layers) for _, h in finals]
-        final_state = torch.cat(states + [distill_norm], dim=1)
-        return _head()().create_model(model_input=final_state, original_input=model_input, vocab_size=vocab_size,
-                                      **unused_params)
+    def _head_extras(self, distillation_predictions=None, l2_penalty=1e-8, **unused_params):
+        return [_distill_link(distillation_predictions, FLAGS.distillchain_relu_cells, l2_penalty)], unused_params
 
 
 class DistillchainCnnDeepCombineChainModel(CnnDeepCombineChainModel):
@@ -619,28 +585,15 @@ class DistillchainCnnDeepCombineChainModel(CnnDeepCombineChainModel):
 
     def create_model(self, model_input, vocab_size, num_frames, num_mixtures=None, l2_penalty=1e-8, sub_scope="",
                      original_input=None, distillation_predictions=None, **unused_params):
-        num_layers = FLAGS.deep_chain_layers
         relu_cells = FLAGS.deep_chain_relu_cells
-        relu_layers = [_distill_link(distillation_predictions, FLAGS.distillchain_relu_cells, l2_penalty)]
-        model_input, u8 = _bytes_or_floats(model_input, num_frames, lambda q: seq_ops.u8_cnn_supported(q) and
-                                           seq_ops.u8_attention_supported(q, 1))
-        frames = seq_ops.U8FrameImages(model_input, num_frames) if u8 else None   # one byte image for every CNN of the chain
-        mean_input = _mean_frame(model_input, num_frames)
-        mean_activation = video_level_models.fully_connected(mean_input, relu_cells, sub_scope + "mean-relu", l2_penalty=l2_penalty)
-        relu_layers.append(ops.chain_link(mean_activation, "relu"))
-        normalized_cnn_output = self._pooled_cnn(model_input, frames, sub_scope + "cnn0", relu_cells, l2_penalty)
-        next_input = torch.cat([normalized_cnn_output] + relu_layers, dim=1)
-        support_predictions = []
-        for layer in range(num_layers):
-            sub_prediction = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "prediction-%d" % layer)
-            support_predictions.append(sub_prediction)
-            sub_activation = video_level_models.fully_connected(sub_prediction, relu_cells, sub_scope + "relu-%d" % layer,
-                                                                l2_penalty=l2_penalty)
-            relu_layers.append(ops.chain_link(sub_activation, "relu"))
-            normalized_cnn_output = self._pooled_cnn(model_input, frames, sub_scope + "cnn%d" % (layer + 1), relu_cells, l2_penalty)
-            next_input = torch.cat([normalized_cnn_output] + relu_layers, dim=1)
-        main_predictions = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "-main")
-        return {"predictions": main_predictions, "support_predictions": torch.cat(support_predictions, dim=1)}
+        links = [_distill_link(distillation_predictions, FLAGS.distillchain_relu_cells, l2_penalty)]
+        model_input, frames, mean_input = self._frames_and_mean(model_input, num_frames)
+        links.append(relu_link(mean_input, relu_cells, sub_scope + "mean-relu", l2_penalty, fused_link("relu")))
+
+        def stage_input(k, links):
+            return torch.cat([self._pooled_cnn(model_input, frames, sub_scope + "cnn%d" % k, relu_cells, l2_penalty)] + links, dim=1)
+
+        return prediction_chain(self.sub_model, stage_input, fused_link("relu"), links, vocab_size, l2_penalty, sub_scope)
 
 
 class DistillchainLstmAttentionMaxPoolingModel(LstmAttentionMaxPoolingModel):
@@ -680,32 +633,24 @@ def _memory_stacks(x_tm, d_in, num_frames, lstm_size, number_of_layers):
 
 class LstmMemoryDeepChainModel(models.BaseModel):
     """W/all_frame_models/lstm_memory_deep_chain_model.py:13-104: deep_chain_layers + 1 LSTM stacks over the same frames (_memory_stacks),
-    a chain of MoE sub-predictions: stage 0 reads the concatenated final memories of stack 0, stage l + 1 reads [memories of stack l + 1 |
-    l2norm(relu-<l>(prediction-<l>))] -- only the latest relu, unlike the Combine form.  The concatenation is ops.memory_link, the relu ->
-    l2norm ops.chain_link.  Variables: lstm-<k>-RNN/..., relu-<l>, gates-/experts-prediction-<l>, gates-/experts--main.
+    a prediction_chain of MoE sub-predictions: stage 0 reads the concatenated final memories of stack 0, stage l + 1 reads [memories of
+    stack l + 1 | l2norm(relu-<l>(prediction-<l>))] -- only the latest relu, unlike the Combine form.  The concatenation is ops.memory_link,
+    the relu -> l2norm ops.chain_link.  Variables: lstm-<k>-RNN/..., relu-<l>, gates-/experts-prediction-<l>, gates-/experts--main.
     accepts_quantized_input: every stack reads the reader's bytes (see _stack_input), prepared once."""
     accepts_quantized_input = True
 
     def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, sub_scope="", original_input=None, **unused_params):
-        num_layers = FLAGS.deep_chain_layers
-        relu_cells = FLAGS.deep_chain_relu_cells
         memories = _memory_stacks(_stack_input(model_input, num_frames), model_input.shape[2], num_frames, int(FLAGS.lstm_cells),
                                   FLAGS.lstm_layers)
-        next_input = ops.memory_link(memories(0), normalize=False)
-        support_predictions = []
-        for layer in range(num_layers):
-            sub_prediction = self.sub_moe(next_input, vocab_size, sub_scope=sub_scope + "prediction-%d" % layer)
-            support_predictions.append(sub_prediction)
-            sub_activation = video_level_models.fully_connected(sub_prediction, relu_cells, sub_scope + "relu-%d" % layer,
-                                                                l2_penalty=l2_penalty)
-            relu_norm = ops.chain_link(sub_activation, "relu")
-            next_input = torch.cat([ops.memory_link(memories(layer + 1), normalize=False), relu_norm], dim=1)
-        main_predictions = self.sub_moe(next_input, vocab_size, sub_scope=sub_scope + "-main")
-        return {"predictions": main_predictions, "support_predictions": torch.cat(support_predictions, dim=1)}
 
-    def sub_moe(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", **unused_params):
-        num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
-        return video_level_models.moe_block(model_input, vocab_size, num_mixtures, l2_penalty, "gates-" + sub_scope, "experts-" + sub_scope)
+        def stage_input(k, links):                                  # stack k is built here: after relu-<k - 1>; only the latest link
+            memory = ops.memory_link(memories(k), normalize=False)
+            return torch.cat([memory, links[-1]], dim=1) if k else memory
+
+        return prediction_chain(self.sub_moe, stage_input, fused_link("relu"), [], vocab_size, l2_penalty, sub_scope)
+
+    def sub_moe(self, model_input, vocab_size, **params):
+        return moe_stage(model_input, vocab_size, **params)
 
 
 class DistillchainLstmMemoryDeepCombineChainModel(LstmMemoryDeepChainModel):
@@ -719,26 +664,14 @@ class DistillchainLstmMemoryDeepCombineChainModel(LstmMemoryDeepChainModel):
 
     def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, sub_scope="", original_input=None,
                      distillation_predictions=None, **unused_params):
-        num_layers = FLAGS.deep_chain_layers
-        relu_cells = FLAGS.deep_chain_relu_cells
-        relu_layers = [_distill_link(distillation_predictions, FLAGS.distillchain_relu_cells, l2_penalty, scope="distill-relu")]
+        links = [_distill_link(distillation_predictions, FLAGS.distillchain_relu_cells, l2_penalty, scope="distill-relu")]
         model_input, _ = _bytes_or_floats(model_input, num_frames, lambda q: _lib_u8_ok(q.shape[2]) and seq_ops.u8_attention_supported(q, 1))
         mean_input = _mean_frame(model_input, num_frames)
-        mean_activation = video_level_models.fully_connected(mean_input, relu_cells, sub_scope + "mean-relu", l2_penalty=l2_penalty)
-        relu_layers.append(ops.chain_link(mean_activation, "relu"))
+        links.append(relu_link(mean_input, FLAGS.deep_chain_relu_cells, sub_scope + "mean-relu", l2_penalty, fused_link("relu")))
         memories = _memory_stacks(_stack_input(model_input, num_frames), model_input.shape[2], num_frames, int(FLAGS.lstm_cells),
                                   FLAGS.lstm_layers)
-        next_input = torch.cat([ops.memory_link(memories(0), normalize=True)] + relu_layers, dim=1)
-        support_predictions = []
-        for layer in range(num_layers):
-            sub_prediction = self.sub_moe(next_input, vocab_size, sub_scope=sub_scope + "prediction-%d" % layer)
-            support_predictions.append(sub_prediction)
-            sub_activation = video_level_models.fully_connected(sub_prediction, relu_cells, sub_scope + "relu-%d" % layer,
-                                                                l2_penalty=l2_penalty)
-            relu_layers.append(ops.chain_link(sub_activation, "relu"))
-            next_input = torch.cat([ops.memory_link(memories(layer + 1), normalize=True)] + relu_layers, dim=1)
-        main_predictions = self.sub_moe(next_input, vocab_size, sub_scope=sub_scope + "-main")
-        return {"predictions": main_predictions, "support_predictions": torch.cat(support_predictions, dim=1)}
+        return prediction_chain(self.sub_moe, lambda k, links: torch.cat([ops.memory_link(memories(k), normalize=True)] + links, dim=1),
+                                fused_link("relu"), links, vocab_size, l2_penalty, sub_scope)
 
 
 class LstmParallelMemoryModel(models.BaseModel):
@@ -748,20 +681,16 @@ class LstmParallelMemoryModel(models.BaseModel):
     accepts_quantized_input = True
 
     def create_model(self, model_input, vocab_size, num_frames, **unused_params):
-        lstm_sizes = [int(v) for v in str(FLAGS.lstm_cells).split(",")]
-        feature_sizes = [int(v) for v in str(FLAGS.feature_sizes).split(",")]
+        lstm_sizes, feature_sizes = _sizes_per_feature()
         stacks = _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, FLAGS.lstm_layers, own_slots=True)
         final_state = ops.memory_link([c for _, finals in stacks for c, _ in finals], normalize=False)
-        return _head()().create_model(model_input=final_state, original_input=model_input, vocab_size=vocab_size,
-                                      **unused_params)
+        return _classify(final_state, model_input, vocab_size, **unused_params)
 
 
 def _time_major_stacks(parts_tm, num_frames, lstm_sizes, number_of_layers, scope_prefix, slot_base):
     """_parallel_stacks for parts that are prepared already: parts_tm[i] float32 [T, B, w_i] time-major and l2-normalised (a level of
     ops.frame_pyramid, or the hopped outputs of the level below).  Stack i runs under scope <scope_prefix>RNN<i> in slot slot_base + i;
     a part that requires a gradient gets one (the native stack's dx).  Returns [(top outputs [T,B,H_i], finals)]."""
-    assert len(lstm_sizes) == len(parts_tm), \
-        "length of lstm_sizes (={}) != length of feature_sizes (={})".format(len(lstm_sizes), len(parts_tm))
     g = get_default_graph()
     res = []
     for i, (x_tm, hs) in enumerate(zip(parts_tm, lstm_sizes)):
@@ -780,8 +709,8 @@ def _length_code(num_frames):
 
 
 class MultiresLstmMemoryDeepCombineChainModel(models.BaseModel):
-    """W/all_frame_models/multires_lstm_memory_deep_combine_chain_model.py:13-165: DeepCombineChainModel's chain whose stage i reads the
-    final memories of a fresh tower of per-feature LSTM stacks (lstm<i>RNN<j>, no hyphen) over the frames at resolution
+    """W/all_frame_models/multires_lstm_memory_deep_combine_chain_model.py:13-165: DeepCombineChainModel's prediction_chain whose stage i reads
+    the final memories of a fresh tower of per-feature LSTM stacks (lstm<i>RNN<j>, no hyphen) over the frames at resolution
     r_i = 2^(deep_chain_layers - i): the mean over every r frames, split by --feature_sizes, every part l2-normalised, num_frames // r
     steps.  next_input = [memories (stack-major, then layer) | length code with --deep_chain_use_length | l2norm(relu-<l>(prediction-<l>))
     of every earlier stage]; dropout on the support stages' inputs only.  Every level r >= 2 comes from ONE ops.frame_pyramid call, r = 1
@@ -796,13 +725,8 @@ class MultiresLstmMemoryDeepCombineChainModel(models.BaseModel):
     def create_model(self, model_input, vocab_size, num_frames, num_mixtures=None, l2_penalty=1e-8, sub_scope="", original_input=None,
                      dropout=False, keep_prob=None, noise_level=None, **unused_params):
         num_layers = FLAGS.deep_chain_layers
-        relu_cells = FLAGS.deep_chain_relu_cells
-        relu_type = "elu" if FLAGS.deep_chain_relu_type == "elu" else "relu"
         number_of_layers = FLAGS.lstm_layers
-        lstm_sizes = [int(v) for v in str(FLAGS.lstm_cells).split(",")]
-        feature_sizes = [int(v) for v in str(FLAGS.feature_sizes).split(",")]
-        assert len(lstm_sizes) == len(feature_sizes), \
-            "length of lstm_sizes (={}) != length of feature_sizes (={})".format(len(lstm_sizes), len(feature_sizes))
+        lstm_sizes, feature_sizes = _sizes_per_feature()
         B, F, D = model_input.shape
         if F < (1 << num_layers):
             raise ValueError("MultiresLstmMemoryDeepCombineChainModel: %d frames are fewer than the coarsest resolution 2^%d: its LSTMs "
@@ -821,28 +745,12 @@ class MultiresLstmMemoryDeepCombineChainModel(models.BaseModel):
                 stacks = _time_major_stacks(parts[level], frames[level], lstm_sizes, number_of_layers, "lstm%d" % stage, stage * n)
             return ops.memory_link([c for _, finals in stacks for c, _ in finals], normalize=False)
 
-        next_input = torch.cat([memories(0)] + additional_features, dim=1)
-        support_predictions = []
-        for layer in range(num_layers):
-            sub_prediction = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "prediction-%d" % layer, dropout=dropout,
-                                            keep_prob=keep_prob)
-            support_predictions.append(sub_prediction)
-            sub_activation = video_level_models.fully_connected(sub_prediction, relu_cells, sub_scope + "relu-%d" % layer,
-                                                                l2_penalty=l2_penalty)
-            additional_features.append(ops.chain_link(sub_activation, relu_type, noise_level))
-            next_input = torch.cat([memories(layer + 1)] + additional_features, dim=1)
-        main_predictions = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "-main")
-        res = {"predictions": main_predictions}
-        if support_predictions:
-            res["support_predictions"] = torch.cat(support_predictions, dim=1)
-        return res
+        return prediction_chain(self.sub_model, lambda k, links: torch.cat([memories(k)] + links, dim=1),
+                                fused_link(relu_kind(), noise_level), additional_features, vocab_size, l2_penalty, sub_scope,
+                                support_kwargs=dict(dropout=dropout, keep_prob=keep_prob))
 
-    def sub_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", dropout=False, keep_prob=None,
-                  **unused_params):
-        num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
-        if dropout:                                                         # :108-110 tf.nn.dropout on the stage's whole input
-            model_input = ops.dropout(model_input, 1.0 if keep_prob is None else keep_prob)
-        return video_level_models.moe_block(model_input, vocab_size, num_mixtures, l2_penalty, "gates-" + sub_scope, "experts-" + sub_scope)
+    def sub_model(self, model_input, vocab_size, **params):
+        return moe_stage(model_input, vocab_size, **params)
 
 
 class FramehopLstmMemoryModel(models.BaseModel):
@@ -861,8 +769,7 @@ class FramehopLstmMemoryModel(models.BaseModel):
                              "reference (framehop_lstm_memory_model.py:73); there is nothing to reproduce")
         num_layers = FLAGS.deep_chain_layers
         number_of_layers = FLAGS.lstm_layers
-        lstm_sizes = [int(v) for v in str(FLAGS.lstm_cells).split(",")]
-        feature_sizes = [int(v) for v in str(FLAGS.feature_sizes).split(",")]
+        lstm_sizes, feature_sizes = _sizes_per_feature()
         n = len(feature_sizes)
         seq_ops.reserve_resident((num_layers + 1) * n, number_of_layers)
         stacks = _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, number_of_layers, own_slots=True, scope_prefix="lstm0")
@@ -876,8 +783,7 @@ class FramehopLstmMemoryModel(models.BaseModel):
             stacks = _time_major_stacks(hopped, half.clamp(max=T), lstm_sizes, number_of_layers, "lstm%d" % k, k * n)
             states.extend(c for _, finals in stacks for c, _ in finals)
         final_states = torch.cat(states, dim=1)
-        return _head()().create_model(model_input=final_states, original_input=model_input, vocab_size=vocab_size, num_frames=num_frames,
-                                      **unused_params)
+        return _classify(final_states, model_input, vocab_size, num_frames=num_frames, **unused_params)
 
 
 def _bn_vars(scope, n):
@@ -920,9 +826,8 @@ class MultiscaleCnnLstmModel(models.BaseModel):
         _, finals = _native_stack(x_tm, num_frames, wb, slot=layer)                              # the L stacks are alive in one step
         return finals[0][0]                                                                      # state.c
 
-    def moe(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, scopename="", **unused_params):
-        num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
-        return video_level_models.moe_block(model_input, vocab_size, num_mixtures, l2_penalty, "gates" + scopename, "experts" + scopename)
+    def moe(self, model_input, vocab_size, scopename="", **params):
+        return moe_stage(model_input, vocab_size, sub_scope=scopename, hyphen=False, **params)
 
     def _head_input(self, lstm_memory):
         return lstm_memory
@@ -978,10 +883,7 @@ class DistillchainMultiscaleCnnLstmModel(MultiscaleCnnLstmModel):
     the LSTM memory."""
 
     def create_model(self, model_input, vocab_size, num_frames, distillation_predictions=None, l2_penalty=1e-8, **unused_params):
-        assert distillation_predictions is not None, "distillation feature must be used"
-        distill_relu = video_level_models.fully_connected(distillation_predictions.to(torch.float32), FLAGS.distillchain_relu_cells,
-                                                          "distillrelu", activation="relu", l2_penalty=l2_penalty)
-        self._distill_norm = ops.l2_normalize(distill_relu)
+        self._distill_norm = _distill_link(distillation_predictions, FLAGS.distillchain_relu_cells, l2_penalty, link=composed_link("relu"))
         try:
             return super().create_model(model_input, vocab_size, num_frames, l2_penalty=l2_penalty, **unused_params)
         finally:
@@ -1037,8 +939,7 @@ class DbofModel(models.BaseModel):
             hidden1_biases = g.anonymous_variable((hidden1_size,), random_normal(0.01))
             activation = ops.linear(activation, hidden1_weights, hidden1_biases)
         activation = ops.activation(activation, "relu6")
-        return _head()().create_model(model_input=activation, original_input=model_input, vocab_size=vocab_size,
-                                      **unused_params)
+        return _classify(activation, model_input, vocab_size, **unused_params)
 
 
 class NetVLADModel(models.BaseModel):
@@ -1091,8 +992,7 @@ class NetVLADModel(models.BaseModel):
     def create_model(self, model_input, vocab_size, num_frames, cluster_size=None, hidden_size=None, gating=None,
                      **unused_params):
         h = self.descriptor(model_input, num_frames, cluster_size, hidden_size, gating)
-        return _head()().create_model(model_input=h, original_input=model_input, vocab_size=vocab_size,
-                                      **unused_params)
+        return _classify(h, model_input, vocab_size, **unused_params)
 
 
 class GatedNetVLADModel(NetVLADModel):

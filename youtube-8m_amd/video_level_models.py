@@ -51,9 +51,83 @@ def moe_block(model_input, vocab_size, num_mixtures, l2_penalty, gate_scope, exp
     Wg = g.get_variable(gate_scope + "/weights", (d_in, vocab_size * (M + 1)), xavier_uniform, l2=l2_penalty)
     We = g.get_variable(expert_scope + "/weights", (d_in, vocab_size * M), xavier_uniform, l2=l2_penalty)
     be = g.get_variable(expert_scope + "/biases", (vocab_size * M,), zeros)
-    lead = model_input.shape[:-1]
     p = ops.moe_head(model_input.reshape(-1, d_in), Wg, We, be, vocab_size, M, bf16=FLAGS.compute_dtype == "bfloat16", dx_from=frozen_cols)
-    return p.view(-1, vocab_size) if len(lead) <= 1 else p.view(-1, vocab_size)
+    return p.view(-1, vocab_size)
+
+
+def moe_scopes(sub_scope, hyphen=True):
+    """(gate scope, expert scope): gates-<s> / experts-<s> for the stages of the chain and attention plugins, gates<s> / experts<s> for
+    MoeModel and MultiscaleCnnLstmModel."""
+    return ("gates-" + sub_scope, "experts-" + sub_scope) if hyphen else ("gates" + sub_scope, "experts" + sub_scope)
+
+
+def moe_stage(model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", dropout=False, keep_prob=None, frozen_cols=0,
+              hyphen=True, **unused_params):
+    """One MoE stage of a chain, attention or multiscale plugin: what the reference's sub_model / sub_moe / moe methods all are.  With
+    `dropout`, tf.nn.dropout on the stage's whole input first (deep_combine_chain_model.py:57-58)."""
+    if dropout:
+        model_input = ops.dropout(model_input, 1.0 if keep_prob is None else keep_prob)
+    return moe_block(model_input, vocab_size, num_mixtures or FLAGS.moe_num_mixtures, l2_penalty, *moe_scopes(sub_scope, hyphen),
+                     frozen_cols=frozen_cols)
+
+
+def composed_link(kind="relu", noise_level=None):
+    """The link form activation -> [add_noise] -> l2_normalize as separate ops: a noise_level that is not None, 0.0 included, runs
+    ops.add_noise and takes a seed."""
+    def link(z):
+        y = ops.activation(z, kind)
+        if noise_level is not None:
+            y = ops.add_noise(y, noise_level)
+        return ops.l2_normalize(y)
+    return link
+
+
+def fused_link(kind="relu", noise_level=None):
+    """The same link as one ops.chain_link: no noise and no seed for a noise_level of None or 0."""
+    return lambda z: ops.chain_link(z, kind, noise_level)
+
+
+def relu_kind():
+    """--deep_chain_relu_type as the chain plugins read it: "elu", anything else is relu."""
+    return "elu" if FLAGS.deep_chain_relu_type == "elu" else "relu"
+
+
+def relu_link(x, relu_cells, scope, l2_penalty, link):
+    """link(FC(x)) [B, relu_cells] under `scope`: mean-relu, distillrelu."""
+    return link(fully_connected(x, relu_cells, scope, l2_penalty=l2_penalty))
+
+
+def distill_link(distillation_predictions, relu_cells, l2_penalty, scope="distillrelu", link=None):
+    """The link (fused_link("relu") unless given) over another model's predictions, [B, relu_cells] under `scope`: what the Distillchain
+    plugins concatenate into their classifiers' inputs."""
+    assert distillation_predictions is not None, "distillation feature must be used"
+    return relu_link(distillation_predictions.to(torch.float32), relu_cells, scope, l2_penalty, link or fused_link("relu"))
+
+
+def prediction_chain(sub_model, stage_input, link, links, vocab_size, l2_penalty=1e-8, sub_scope="", support_kwargs=None,
+                     frozen_cols=lambda k: 0, support_pool=None):
+    """The prediction chain of every chain plugin (W/all_video_models/deep_combine_chain_model.py:38-55 and its frame-level kin;
+    DESIGN_LOG.md section 25).  Stage l: sub_model on the stage's input under "prediction-<l>" (gates-, experts- variables; support_kwargs,
+    such as dropout, go to these stages only, never to "-main"), FC to --deep_chain_relu_cells under "relu-<l>", link(...) appended to
+    `links`, THEN stage_input(l + 1, links) -- which may create the next stage's cnn / lstm variables -- and last the stage's entry of
+    "support_predictions" (support_pool applied first where given).  The order of these calls is the order of the variables in the arena
+    and of the graph's random keys: tests/test_chain_order_host.py pins it per plugin.
+    stage_input(k, links) -> [B, width_k], called once per k in rising order; frozen_cols(k): the leading data columns of stage k's
+    input; no "support_predictions" key without support stages."""
+    num_layers, relu_cells = FLAGS.deep_chain_layers, FLAGS.deep_chain_relu_cells
+    support_predictions = []
+    next_input = stage_input(0, links)
+    for layer in range(num_layers):
+        sub_prediction = sub_model(next_input, vocab_size, sub_scope=sub_scope + "prediction-%d" % layer, frozen_cols=frozen_cols(layer),
+                                   **(support_kwargs or {}))
+        sub_activation = fully_connected(sub_prediction, relu_cells, sub_scope + "relu-%d" % layer, l2_penalty=l2_penalty)
+        links.append(link(sub_activation))
+        next_input = stage_input(layer + 1, links)
+        support_predictions.append(sub_prediction if support_pool is None else support_pool(sub_prediction))
+    res = {"predictions": sub_model(next_input, vocab_size, sub_scope=sub_scope + "-main", frozen_cols=frozen_cols(num_layers))}
+    if support_predictions:
+        res["support_predictions"] = torch.cat(support_predictions, dim=1)
+    return res
 
 
 class LogisticModel(models.BaseModel):
@@ -73,21 +147,28 @@ class MoeModel(models.BaseModel):
         fused = (labels is not None and fuse_loss and FLAGS.fused_head_loss and FLAGS.label_loss == "CrossEntropyLoss"
                  and not FLAGS.label_smoothing and not FLAGS.multitask and torch.is_grad_enabled()
                  and model_input.dim() == 2 and tuple(labels.shape) == (model_input.shape[0], vocab_size))
+        gate_scope, expert_scope = moe_scopes(sub_scope, hyphen=False)
         if fused:
             g = get_default_graph()
             d_in, M = model_input.shape[-1], num_mixtures
-            Wg = g.get_variable("gates" + sub_scope + "/weights", (d_in, vocab_size * (M + 1)), xavier_uniform, l2=l2_penalty)
-            We = g.get_variable("experts" + sub_scope + "/weights", (d_in, vocab_size * M), xavier_uniform, l2=l2_penalty)
-            be = g.get_variable("experts" + sub_scope + "/biases", (vocab_size * M,), zeros)
+            Wg = g.get_variable(gate_scope + "/weights", (d_in, vocab_size * (M + 1)), xavier_uniform, l2=l2_penalty)
+            We = g.get_variable(expert_scope + "/weights", (d_in, vocab_size * M), xavier_uniform, l2=l2_penalty)
+            be = g.get_variable(expert_scope + "/biases", (vocab_size * M,), zeros)
             p, loss = ops.moe_head_xent(model_input, Wg, We, be, labels, vocab_size, M, bf16=FLAGS.compute_dtype == "bfloat16")
             return {"predictions": p, "loss": loss}
-        p = moe_block(model_input, vocab_size, num_mixtures, l2_penalty, "gates" + sub_scope, "experts" + sub_scope)
-        return {"predictions": p}
+        return {"predictions": moe_block(model_input, vocab_size, num_mixtures, l2_penalty, gate_scope, expert_scope)}
 
 
 class DeepCombineChainModel(models.BaseModel):
     """W/all_video_models/deep_combine_chain_model.py:9-85: chain of MoE sub-predictions, each projected to
-    relu cells, L2-normalised and concatenated to the input of the next stage."""
+    relu cells, L2-normalised and concatenated to the input of the next stage (prediction_chain; composed links)."""
+
+    def _first_input(self, model_input, l2_penalty, sub_scope, **unused_params):
+        """What stage 0 reads: the model input."""
+        return model_input
+
+    def _link(self, noise_level):
+        return composed_link(relu_kind(), noise_level)
 
     def create_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="",
                      original_input=None, dropout=False, keep_prob=None, noise_level=None, num_frames=None,
@@ -96,33 +177,21 @@ class DeepCombineChainModel(models.BaseModel):
         sub-prediction BEFORE the concatenation into "support_predictions" -- a caller that reduces the rows anyway (the attention
         composite takes the max over its A attention rows per video) then concatenates [B, V] pieces instead of [B * A, V] ones: the
         [B * A, L * V] copy (464 MB at B * A = 8192, L = 3) and the strided gradient slices it leaves behind disappear."""
-        num_layers = FLAGS.deep_chain_layers
-        relu_cells = FLAGS.deep_chain_relu_cells
-        relu_type = FLAGS.deep_chain_relu_type
-        next_input = model_input
         # the model input stays in front of every later stage's input (:66-70): when it is data, no head computes a gradient for it
         frozen = 0 if model_input.requires_grad else int(model_input.shape[1])
-        support_predictions = []
-        for layer in range(num_layers):
-            sub_prediction = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "prediction-%d" % layer,
-                                            dropout=dropout, keep_prob=keep_prob, noise_level=noise_level, frozen_cols=frozen)
-            sub_activation = fully_connected(sub_prediction, relu_cells, sub_scope + "relu-%d" % layer, l2_penalty=l2_penalty)
-            sub_relu = ops.activation(sub_activation, "elu" if relu_type == "elu" else "relu")
-            if noise_level is not None:
-                sub_relu = ops.add_noise(sub_relu, noise_level)
-            relu_norm = ops.l2_normalize(sub_relu)
-            next_input = torch.cat([next_input, relu_norm], dim=1)
-            support_predictions.append(sub_prediction if support_pool is None else support_pool(sub_prediction))
-        main_predictions = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "-main", frozen_cols=frozen)
-        return {"predictions": main_predictions, "support_predictions": torch.cat(support_predictions, dim=1)}
+        grown = [self._first_input(model_input, l2_penalty, sub_scope, **unused_params)]
 
-    def sub_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", dropout=False,
-                  keep_prob=None, noise_level=None, frozen_cols=0, **unused_params):
-        num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
-        if dropout:                                                 # :57-58 tf.nn.dropout on the (grown) chain input
-            model_input = ops.dropout(model_input, 1.0 if keep_prob is None else keep_prob)
-        return moe_block(model_input, vocab_size, num_mixtures, l2_penalty, "gates-" + sub_scope, "experts-" + sub_scope,
-                         frozen_cols=frozen_cols)
+        def stage_input(k, links):                                  # the previous stage's input with the newest link behind it
+            if k:
+                grown[0] = torch.cat([grown[0], links[-1]], dim=1)
+            return grown[0]
+
+        return prediction_chain(self.sub_model, stage_input, self._link(noise_level), [], vocab_size, l2_penalty, sub_scope,
+                                support_kwargs=dict(dropout=dropout, keep_prob=keep_prob, noise_level=noise_level),
+                                frozen_cols=lambda k: frozen, support_pool=support_pool)
+
+    def sub_model(self, model_input, vocab_size, **params):
+        return moe_stage(model_input, vocab_size, **params)
 
 
 class DistillchainDeepCombineChainModel(DeepCombineChainModel):
@@ -130,26 +199,9 @@ class DistillchainDeepCombineChainModel(DeepCombineChainModel):
     [model_input | distill_norm], distill_norm = the l2-normalised relu projection (scope sub_scope + "distillrelu",
     --deep_chain_relu_cells wide here) of another model's predictions.  Every relu -> (noise) -> l2norm is one ops.chain_link."""
 
-    def create_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="",
-                     original_input=None, dropout=False, keep_prob=None, noise_level=None, distillation_predictions=None,
-                     num_frames=None, **unused_params):
-        assert distillation_predictions is not None, "distillation feature must be used"
-        num_layers = FLAGS.deep_chain_layers
-        relu_cells = FLAGS.deep_chain_relu_cells
-        relu_type = FLAGS.deep_chain_relu_type
-        distill_activation = fully_connected(distillation_predictions.to(torch.float32), relu_cells, sub_scope + "distillrelu",
-                                             l2_penalty=l2_penalty)
-        distill_norm = ops.chain_link(distill_activation, "relu")
-        next_input = torch.cat([model_input, distill_norm], dim=1)
-        # the model input stays in front of every stage's input: when it is data, no head computes a gradient for it
-        frozen = 0 if model_input.requires_grad else int(model_input.shape[1])
-        support_predictions = []
-        for layer in range(num_layers):
-            sub_prediction = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "prediction-%d" % layer,
-                                            dropout=dropout, keep_prob=keep_prob, noise_level=noise_level, frozen_cols=frozen)
-            sub_activation = fully_connected(sub_prediction, relu_cells, sub_scope + "relu-%d" % layer, l2_penalty=l2_penalty)
-            relu_norm = ops.chain_link(sub_activation, "elu" if relu_type == "elu" else "relu", noise_level)
-            next_input = torch.cat([next_input, relu_norm], dim=1)
-            support_predictions.append(sub_prediction)
-        main_predictions = self.sub_model(next_input, vocab_size, sub_scope=sub_scope + "-main", frozen_cols=frozen)
-        return {"predictions": main_predictions, "support_predictions": torch.cat(support_predictions, dim=1)}
+    def _first_input(self, model_input, l2_penalty, sub_scope, distillation_predictions=None, **unused_params):
+        distill_norm = distill_link(distillation_predictions, FLAGS.deep_chain_relu_cells, l2_penalty, sub_scope + "distillrelu")
+        return torch.cat([model_input, distill_norm], dim=1)
+
+    def _link(self, noise_level):
+        return fused_link(relu_kind(), noise_level)
