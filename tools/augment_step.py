@@ -5,14 +5,11 @@ difference is what the augmentation itself costs), and DeepCombineChainModel wit
 profiler's view) and reports the achieved bandwidth on the bytes the shapes imply.  Every leg runs in a child process of its own under
 its own time limit; the driver stops at the first leg that fails.
 usage: python tools/augment_step.py [--steps K] [--warmup W] [--out FILE] [leg ...]      legs: see LEGS, and `kernels`"""
-import argparse
 import json
-import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import steplib
+
 LEGS = {                                     # leg -> (model, augmenter, videos per step)
     "lstm_half": ("LstmModel", "HalfAugmenter", 128),
     "lstm_tiled": ("LstmModel", "DefaultAugmenter", 128),
@@ -23,25 +20,14 @@ LEGS = {                                     # leg -> (model, augmenter, videos 
     "chain_halfvideo": ("DeepCombineChainModel", "HalfVideoAugmenter", 200),
     "chain_tiled": ("DeepCombineChainModel", "DefaultAugmenter", 200),
 }
-F, D, V = 300, 1152, 4716
-
-
-def _setup():
-    import torch
-    sys.path.insert(0, ROOT)
-    import __graft_entry__
-    __graft_entry__.load_package()
-    dev = torch.device("cuda:0")
-    torch.cuda.set_device(dev)
-    return dev
+F, D = 300, 1152
 
 
 def kernels(iters):
     import torch
-    dev = _setup()
+    dev = steplib.setup()
     import yt8m_amd.ops as ops
     gen = torch.Generator(device=dev).manual_seed(1)
-    rows = []
     for name, B in (("half_segments_u8", 128), ("half_segment_means_u8", 200), ("dequant_noise_u8", 128)):
         q = torch.randint(0, 256, (B, F, D), device=dev, generator=gen, dtype=torch.uint8)
         nf = torch.randint(F // 2, F + 1, (B,), device=dev, generator=gen, dtype=torch.int32)
@@ -53,14 +39,7 @@ def kernels(iters):
             fn, nbytes = (lambda: ops.dequant_noise(q, nf, 0.2, 7)), 5 * B * F * D                 # 1 byte in, 4 bytes out
         for _ in range(3):
             fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        us = e0.elapsed_time(e1) / iters * 1e3
+        us = steplib.events_us(fn, iters)
         row = dict(leg="kernel", kernel=name, B=B, F=F, D=D, us_per_call=round(us, 2), bytes=nbytes,
                    tb_per_s=round(nbytes / (us * 1e-6) / 1e12, 3), timing="hip events over %d back-to-back calls (torch allocations included)" % iters)
         print(json.dumps(row), flush=True)
@@ -70,7 +49,7 @@ def kernels(iters):
 def child(leg, steps, warmup):
     import numpy as np
     import torch
-    dev = _setup()
+    dev = steplib.setup()
     import yt8m_amd.data_augmentation as da
     import yt8m_amd.frame_level_models as flm
     import yt8m_amd.ops as ops
@@ -85,10 +64,7 @@ def child(leg, steps, warmup):
     g = reset_default_graph(device=dev, seed=0)
     model = getattr(flm, model_name, None) or getattr(vlm, model_name)
     tg = train.TrainGraph(model(), batch_size=B, graph=g, augmenter_class=getattr(da, aug))
-    gen = torch.Generator(device=dev).manual_seed(1)
-    x = torch.randint(0, 256, (B, F, D), device=dev, generator=gen, dtype=torch.uint8)
-    nf = torch.randint(F // 2, F + 1, (B,), device=dev, generator=gen, dtype=torch.int32)
-    y = torch.rand((B, V), device=dev, generator=gen) < 3.4 / V
+    x, y, nf, _ = steplib.random_batch(dev, B, F)
     nf_host = nf.cpu()                                                     # the reader's host copy: the augmenter's no-sync path
     if aug == "DefaultAugmenter":                                          # the batch the augmenter would make, made up front
         if model_name == "DeepCombineChainModel":
@@ -97,64 +73,37 @@ def child(leg, steps, warmup):
             x, nf = ops.half_segments(x, nf)
             nf_host = nf
         y = torch.cat([y, y, y])
-    loss_first = None
-    for _ in range(warmup):
-        o = tg.step(x, y, nf_host)
-        seq_ops.check_persist_errors()
-        if loss_first is None:
-            loss_first = float(o["loss"])
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        out = tg.step(x, y, nf_host)
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) / steps * 1e3
+    loss_first = steplib.warm_up(lambda: tg.step(x, y, nf_host), warmup, seq_ops.check_persist_errors)
+    out, elapsed, _ = steplib.timed_steps(lambda: tg.step(x, y, nf_host), steps)
     seq_ops.check_persist_errors()
-    finite = all(bool(torch.isfinite(v.data).all()) for v in g.trainable_variables())
+    finite = steplib.params_finite(g)
     print(json.dumps(dict(leg=leg, model=model_name, augmenter=aug, videos=B, rows=int(out["predictions"].shape[0]),
-                          input=str(x.dtype).replace("torch.", ""), ms_per_step=round(ms, 3), steps=steps, warmup=warmup,
+                          input=str(x.dtype).replace("torch.", ""), ms_per_step=round(elapsed / steps * 1e3, 3), steps=steps, warmup=warmup,
                           loss_first=loss_first, loss=float(out["loss"]), params_finite=finite)), flush=True)
     return 0 if finite and np.isfinite(loss_first) else 1
 
 
+def summarise(rows):
+    by = {r["leg"]: r["ms_per_step"] for r in rows if "ms_per_step" in r}
+    costs = []
+    for base in ("lstm", "cnn", "attn", "chain"):
+        aug = base + ("_halfvideo" if base == "chain" else "_half")
+        if aug in by and base + "_tiled" in by:
+            costs.append(dict(leg=base + "_augment_cost", ms_per_step=round(by[aug] - by[base + "_tiled"], 3)))
+    return rows + costs
+
+
+def parser():
+    return steplib.arg_parser(steps=20, warmup=3, timeout=300)
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--timeout", type=int, default=300, help="seconds per leg")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("legs", nargs="*")
-    a = ap.parse_args()
+    a = steplib.parse_args(parser(), list(LEGS) + ["kernels"])
     if a.child == "kernels":
         return kernels(a.steps)
     if a.child:
         return child(a.child, a.steps, a.warmup)
-    rows = []
-    for leg in a.legs or list(LEGS) + ["kernels"]:
-        cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", leg, "--steps", str(a.steps),
-               "--warmup", str(a.warmup)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
-        if r.returncode != 0 or not lines:
-            sys.stderr.write(r.stdout[-4000:] + r.stderr[-4000:])
-            print("leg %s failed with exit status %d: stopping" % (leg, r.returncode), flush=True)
-            return r.returncode or 1
-        for ln in lines:
-            rows.append(json.loads(ln))
-            print(ln, flush=True)
-    by = {r["leg"]: r["ms_per_step"] for r in rows if "ms_per_step" in r}
-    for base in ("lstm", "cnn", "attn", "chain"):
-        aug = base + ("_halfvideo" if base == "chain" else "_half")
-        if aug in by and base + "_tiled" in by:
-            row = dict(leg=base + "_augment_cost", ms_per_step=round(by[aug] - by[base + "_tiled"], 3))
-            rows.append(row)
-            print(json.dumps(row), flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            for r in rows:
-                f.write(json.dumps(r) + "\n")
-    return 0
+    return steplib.drive(__file__, a.legs or list(LEGS) + ["kernels"], steplib.child_args(a), a.timeout, a.out, summarise=summarise)
 
 
 if __name__ == "__main__":

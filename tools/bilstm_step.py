@@ -7,14 +7,11 @@ put a synchronisation into the timing); after the last step every parameter must
 step; `loss` the last one's -- on these uniform-noise frames with fixed labels the MoE head saturates within the warm-up, and the last
 loss comes out the same for every model (the positives' -log(eps) average), so it is no evidence about the model.
 usage: python tools/bilstm_step.py [--steps K] [--warmup W] [--out FILE] [leg ...]    legs: lstm bilstm_seq bilstm_overlap biuni"""
-import argparse
 import json
-import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import steplib
+
 LEGS = {
     "lstm": ("LstmModel", "0"),
     "bilstm_seq": ("BiLstmModel", "0"),
@@ -24,84 +21,49 @@ LEGS = {
 
 
 def child(leg, steps, warmup):
-    import torch
-    sys.path.insert(0, ROOT)
-    import __graft_entry__
-    __graft_entry__.load_package()
+    dev = steplib.setup()
     import yt8m_amd.frame_level_models as flm
     import yt8m_amd.seq_ops as seq_ops
     import yt8m_amd.train as train
     from yt8m_amd.flags import FLAGS
     from yt8m_amd.variables import reset_default_graph
-    dev = torch.device("cuda:0")
-    torch.cuda.set_device(dev)
-    B, F, D, V = 128, 300, 1152, 4716
+    B, F = 128, 300
     FLAGS.reset()
     FLAGS.lstm_cells, FLAGS.lstm_layers = "1024", 2
     g = reset_default_graph(device=dev, seed=0)
     tg = train.TrainGraph(getattr(flm, LEGS[leg][0])(), batch_size=B, graph=g)
-    gen = torch.Generator(device=dev).manual_seed(1)
-    x = torch.randint(0, 256, (B, F, D), device=dev, generator=gen, dtype=torch.uint8)
-    nf = torch.randint(F // 2, F + 1, (B,), device=dev, generator=gen, dtype=torch.int32)
-    y = torch.rand((B, V), device=dev, generator=gen) < 3.4 / V
+    x, y, nf, _ = steplib.random_batch(dev, B, F)
     calls = dict(seq_ops.NATIVE_CALLS)
-    loss_first = None
-    for _ in range(warmup):
-        o = tg.step(x, y, nf)
-        seq_ops.check_persist_errors()
-        if loss_first is None:
-            loss_first = float(o["loss"])
+    loss_first = steplib.warm_up(lambda: tg.step(x, y, nf), warmup, seq_ops.check_persist_errors)
     native = seq_ops.NATIVE_CALLS["fwd"] - calls["fwd"]
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        out = tg.step(x, y, nf)
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) / steps * 1e3
+    out, elapsed, _ = steplib.timed_steps(lambda: tg.step(x, y, nf), steps)
     seq_ops.check_persist_errors()
-    finite = all(bool(torch.isfinite(v.data).all()) for v in g.trainable_variables())
-    print(json.dumps(dict(leg=leg, model=LEGS[leg][0], overlap=LEGS[leg][1] == "1", ms_per_step=round(ms, 3), steps=steps, warmup=warmup,
-                          loss_first=loss_first, loss=float(out["loss"]), params_finite=finite, native_stacks_per_step=native / max(warmup, 1),
-                          overlap_runs=seq_ops.BI_OVERLAP_RUNS[0])), flush=True)
+    finite = steplib.params_finite(g)
+    print(json.dumps(dict(leg=leg, model=LEGS[leg][0], overlap=LEGS[leg][1] == "1", ms_per_step=round(elapsed / steps * 1e3, 3), steps=steps,
+                          warmup=warmup, loss_first=loss_first, loss=float(out["loss"]), params_finite=finite,
+                          native_stacks_per_step=native / max(warmup, 1), overlap_runs=seq_ops.BI_OVERLAP_RUNS[0])), flush=True)
     return 0 if finite else 1
 
 
+def summarise(rows):
+    by = {r["leg"]: r["ms_per_step"] for r in rows}
+    if not ("lstm" in by and "bilstm_seq" in by and "bilstm_overlap" in by):
+        return rows
+    return rows + [dict(bilstm_seq_over_lstm=round(by["bilstm_seq"] / by["lstm"], 3),
+                        bilstm_overlap_over_lstm=round(by["bilstm_overlap"] / by["lstm"], 3),
+                        overlap_default=by["bilstm_overlap"] < by["bilstm_seq"])]
+
+
+def parser():
+    return steplib.arg_parser(steps=20, warmup=3, timeout=300)
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--timeout", type=int, default=300, help="seconds per leg")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("legs", nargs="*")
-    a = ap.parse_args()
+    a = steplib.parse_args(parser(), list(LEGS))
     if a.child:
         return child(a.child, a.steps, a.warmup)
-    rows = []
-    for leg in a.legs or list(LEGS):
-        env = dict(os.environ, YT8M_BI_OVERLAP=LEGS[leg][1])
-        cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", leg, "--steps", str(a.steps),
-               "--warmup", str(a.warmup)]
-        r = subprocess.run(cmd, env=env, capture_output=True, text=True)
-        line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
-        if r.returncode != 0 or not line:
-            sys.stderr.write(r.stdout[-4000:] + r.stderr[-4000:])
-            print("leg %s failed with exit status %d: stopping" % (leg, r.returncode), flush=True)
-            return r.returncode or 1
-        rows.append(json.loads(line[-1]))
-        print(line[-1], flush=True)
-    by = {r["leg"]: r["ms_per_step"] for r in rows}
-    if "lstm" in by and "bilstm_seq" in by and "bilstm_overlap" in by:
-        summary = dict(bilstm_seq_over_lstm=round(by["bilstm_seq"] / by["lstm"], 3),
-                       bilstm_overlap_over_lstm=round(by["bilstm_overlap"] / by["lstm"], 3),
-                       overlap_default=by["bilstm_overlap"] < by["bilstm_seq"])
-        print(json.dumps(summary), flush=True)
-        rows.append(summary)
-    if a.out:
-        with open(a.out, "w") as f:
-            for r in rows:
-                f.write(json.dumps(r) + "\n")
-    return 0
+    return steplib.drive(__file__, a.legs or list(LEGS), steplib.child_args(a), a.timeout, a.out,
+                         env_of=lambda leg: {"YT8M_BI_OVERLAP": LEGS[leg][1]}, summarise=summarise)
 
 
 if __name__ == "__main__":

@@ -9,15 +9,12 @@ of its non-distill parent, in ONE process and in turn inside every repeat, at th
 of a leg states on - off against the spread the leg saw between its own repeats.
 Every leg runs in a child process of its own under its own time limit; the driver stops at the first leg that fails.
 usage: python tools/distillchain_step.py [--steps K] [--warmup W] [--repeats N] [--out FILE] [leg ...]      legs: see LEGS, and `kernels`"""
-import argparse
 import json
-import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-V = 4716
+import steplib
+
+V = steplib.V
 # leg: (module, plugin, parent, batch, frame level?, flags of the script)
 LEGS = {
     "video": ("video_level_models", "DistillchainDeepCombineChainModel", "DeepCombineChainModel", 512, False,
@@ -35,35 +32,9 @@ KERNEL_SHAPES = ((128, 128), (128, 256), (1024, 256), (8192, 256))
 KERNEL_KINDS = (("relu", None), ("elu", 0.1))
 
 
-def _setup():
-    import torch
-    sys.path.insert(0, ROOT)
-    import __graft_entry__
-    __graft_entry__.load_package()
-    dev = torch.device("cuda:0")
-    torch.cuda.set_device(dev)
-    return dev
-
-
-def _events_us(fn, iters):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e3
-
-
-def _median(v):
-    return sorted(v)[len(v) // 2]
-
-
 def kernels(iters, repeats):
     import torch
-    dev = _setup()
+    dev = steplib.setup()
     import yt8m_amd.ops as ops
     for rows, cols in KERNEL_SHAPES:
         gen = torch.Generator(device=dev).manual_seed(rows + cols)
@@ -78,21 +49,15 @@ def kernels(iters, repeats):
                 return y.detach(), q.grad
 
             forms = {"fused": lambda: run(True), "composed": lambda: run(False)}
-            us = {k: [] for k in forms}
-            for f in forms.values():                                         # warm-up: every form for as long as it is timed
-                _events_us(f, iters)
-            for _ in range(repeats):                                         # alternating: both forms see the same machine
-                for k, f in forms.items():
-                    us[k].append(_events_us(f, iters))
+            us = steplib.alternate(forms, iters, repeats)
             (yf, df), (yc, dc) = forms["fused"](), forms["composed"]()
             ops.CHAIN_LINK_FUSED = True
-            f_, c_ = us["fused"], us["composed"]
+            f_, c_ = steplib.median(us["fused"]), steplib.median(us["composed"])
             print(json.dumps(dict(
                 leg="kernel", rows=rows, cols=cols, kind=kind, noise_level=noise, what="forward + backward through autograd",
                 launches_fused=2, launches_composed=(3 if noise else 2) + 2,
-                fused_us=round(_median(f_), 2), fused_us_min=round(min(f_), 2), fused_us_max=round(max(f_), 2),
-                composed_us=round(_median(c_), 2), composed_us_min=round(min(c_), 2), composed_us_max=round(max(c_), 2),
-                composed_over_fused=round(_median(c_) / _median(f_), 2), fused_not_slower=bool(_median(f_) <= _median(c_)),
+                **steplib.spread_fields("fused", us["fused"], "us"), **steplib.spread_fields("composed", us["composed"], "us"),
+                composed_over_fused=round(c_ / f_, 2), fused_not_slower=bool(f_ <= c_),
                 y_diff_fused_composed=float((yf - yc).abs().max()), grad_diff_fused_composed_rel_to_max=float((df - dc).abs().max() / dc.abs().max()),
                 repeats=repeats, timing="hip events over %d back-to-back calls (torch allocations and autograd included), median of the repeats"
                                         % iters)), flush=True)
@@ -103,7 +68,7 @@ def kernels(iters, repeats):
 def child(leg, steps, warmup, repeats):
     import numpy as np
     import torch
-    dev = _setup()
+    dev = steplib.setup()
     import importlib
     import yt8m_amd.ops as ops
     import yt8m_amd.train as train
@@ -116,16 +81,7 @@ def child(leg, steps, warmup, repeats):
     FLAGS.distillation_features = FLAGS.distillation_as_input = True
     for k, v in fl.items():
         setattr(FLAGS, k, v)
-    gen = torch.Generator(device=dev).manual_seed(1)
-    if frames:
-        F, D = 300, 1152
-        x = torch.randint(0, 256, (B, F, D), device=dev, generator=gen, dtype=torch.uint8)
-        nf = torch.randint(1, F + 1, (B,), device=dev, generator=gen, dtype=torch.int32)
-        nf[0], nf[1] = F, 1
-    else:
-        x = torch.randn((B, 1152), device=dev, generator=gen)
-    y = torch.rand((B, V), device=dev, generator=gen) < 3.4 / V
-    y[:, 0] = True
+    x, y, nf, gen = steplib.random_batch(dev, B, 300 if frames else None, "ends", first_label=True)
     batch = (x, y, nf) if frames else (x, y)
     distill = torch.rand((B, V), device=dev, generator=gen) * 0.05
     # learning rate 0 (the step does the same work): the steps repeat one random batch
@@ -145,61 +101,33 @@ def child(leg, steps, warmup, repeats):
         return float(out["loss"])
 
     losses = {k: run(k, warmup) for k in forms}
-    ms = {k: [] for k in forms}
-    for _ in range(repeats):                                             # in turn: every form sees the same machine
-        for k in forms:
-            t0 = time.perf_counter()
-            run(k, steps)
-            ms[k].append((time.perf_counter() - t0) / steps * 1e3)
+    ms = steplib.steps_in_turn(run, forms, steps, repeats)
     ops.CHAIN_LINK_FUSED = True
     finite = all(np.isfinite(v) for v in losses.values())
     row = dict(leg=leg, plugin=plugin, parent=parent, B=B, V=V, input="uint8 [B,300,1152]" if frames else "float32 [B,1152]",
                flags=fl, steps=steps, warmup=warmup, repeats=repeats, losses_after_warmup=losses,
                timing="host clock around the steps of one form, ending in a device synchronise; forms in turn inside every repeat")
     for k, v in ms.items():
-        row["%s_ms_per_step" % k] = round(_median(v), 3)
-        row["%s_ms_min" % k], row["%s_ms_max" % k] = round(min(v), 3), round(max(v), 3)
-    spread = max(max(ms["fused"]) - min(ms["fused"]), max(ms["composed"]) - min(ms["composed"]))
-    row["fused_minus_composed_ms"] = round(_median(ms["fused"]) - _median(ms["composed"]), 3)
-    row["spread_between_repeats_ms"] = round(spread, 3)
-    row["fused_within_spread_of_composed"] = bool(_median(ms["fused"]) - _median(ms["composed"]) <= spread)
+        row.update(steplib.spread_fields(k, v, "ms"))
+    row.update(steplib.fused_against_composed(ms))
     print(json.dumps(row), flush=True)
     return 0 if finite else 1
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+def parser():
+    ap = steplib.arg_parser(steps=20, warmup=3, timeout=420)
     ap.add_argument("--repeats", type=int, default=5, help="timing repeats inside every leg")
     ap.add_argument("--kernel_iters", type=int, default=200)
-    ap.add_argument("--timeout", type=int, default=420, help="seconds per leg")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("legs", nargs="*")
-    a = ap.parse_args()
+    return ap
+
+
+def main():
+    a = steplib.parse_args(parser(), ["kernels"] + list(LEGS))
     if a.child == "kernels":
         return kernels(a.kernel_iters, a.repeats)
     if a.child:
         return child(a.child, a.steps, a.warmup, a.repeats)
-    rows = []
-    for leg in a.legs or ["kernels"] + list(LEGS):
-        cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", leg, "--steps", str(a.steps),
-               "--warmup", str(a.warmup), "--repeats", str(a.repeats), "--kernel_iters", str(a.kernel_iters)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
-        if r.returncode != 0 or not lines:
-            sys.stderr.write(r.stdout[-4000:] + r.stderr[-4000:])
-            print("leg %s failed with exit status %d: stopping" % (leg, r.returncode), flush=True)
-            return r.returncode or 1
-        for ln in lines:
-            rows.append(json.loads(ln))
-            print(ln, flush=True)
-        if a.out:                                                        # after every leg: a later leg's failure keeps the earlier rows
-            with open(a.out, "w") as f:
-                for row in rows:
-                    f.write(json.dumps(row) + "\n")
-    return 0
+    return steplib.drive(__file__, a.legs or ["kernels"] + list(LEGS), steplib.child_args(a, "repeats", "kernel_iters"), a.timeout, a.out)
 
 
 if __name__ == "__main__":

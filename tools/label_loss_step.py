@@ -11,30 +11,18 @@ Step legs: a MoeModel training step (fp32, clip + Adam, learning rate 0) at B = 
 with the fused head + loss off (--nofused_head_loss: the step the two losses add their cost to).  Every leg runs in a child process
 of its own under its own time limit, the step legs `--repeats` times in turn; the driver stops at the first leg that fails.
 usage: python tools/label_loss_step.py [--steps K] [--warmup W] [--repeats N] [--out FILE] [leg ...]      legs: see LEGS, and `kernels`"""
-import argparse
 import json
 import os
 import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import steplib
+
 LEGS = ("moe_batch_agreement", "moe_topk_batch_agreement", "moe_cross_entropy_unfused")
 LOSS_OF_LEG = {"moe_batch_agreement": "BatchAgreementCrossEntropyLoss", "moe_topk_batch_agreement": "TopKBatchAgreementCrossEntropyLoss",
                "moe_cross_entropy_unfused": "CrossEntropyLoss"}
-D, V = 1152, 4716
+D, V = 1152, steplib.V
 AGREEMENT = 0.1
-
-
-def _setup():
-    import torch
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import __graft_entry__
-    __graft_entry__.load_package()
-    dev = torch.device("cuda:0")
-    torch.cuda.set_device(dev)
-    return dev
 
 
 def _shader_clock():
@@ -45,18 +33,6 @@ def _shader_clock():
         return next((v for k, v in card.items() if "sclk" in k.lower()), None)
     except Exception:
         return None
-
-
-def _events_us(fn, iters):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e3
 
 
 def _inputs(kind, B, dev):
@@ -73,13 +49,10 @@ def _inputs(kind, B, dev):
     return p.contiguous(), y
 
 
-def _median(v):
-    return sorted(v)[len(v) // 2]
-
-
 def kernels(iters, repeats):
     import torch
-    dev = _setup()
+    dev = steplib.setup()
+    sys.path.insert(0, os.path.join(steplib.ROOT, "tests"))
     import yt8m_amd.ops as ops
     import test_losses_host as H
     clock_before = _shader_clock()
@@ -102,24 +75,18 @@ def kernels(iters, repeats):
                 ("topk_batch_agreement", "composed"): lambda: fwd_bwd(H.topk_batch_agreement_ref, yf, AGREEMENT),
                 ("cross_entropy", "fused"): lambda: fwd_bwd(ops.cross_entropy, y),
             }
-            us = {k: [] for k in forms}
-            for f in forms.values():                                         # warm-up: every form for as long as it is timed
-                _events_us(f, iters)
-            for _ in range(repeats):                                         # alternating: every form sees the same machine
-                for k, f in forms.items():
-                    us[k].append(_events_us(f, iters))
+            us = steplib.alternate(forms, iters, repeats)
             for loss_name in ("batch_agreement", "topk_batch_agreement", "cross_entropy"):
                 lf, df = forms[(loss_name, "fused")]()
                 row = dict(leg="kernel", loss=loss_name, predictions=kind, B=B, V=V, what="forward + backward through autograd",
-                           fused_us=round(_median(us[(loss_name, "fused")]), 2), fused_us_min=round(min(us[(loss_name, "fused")]), 2),
-                           fused_us_max=round(max(us[(loss_name, "fused")]), 2), repeats=repeats, loss_value=float(lf),
+                           **steplib.spread_fields("fused", us[(loss_name, "fused")], "us"), repeats=repeats, loss_value=float(lf),
                            timing="hip events over %d back-to-back calls (torch allocations and autograd included), median of the repeats"
                                   % iters)
                 if (loss_name, "composed") in forms:
                     lc, dc = forms[(loss_name, "composed")]()
                     c = us[(loss_name, "composed")]
-                    row.update(composed_us=round(_median(c), 2), composed_us_min=round(min(c), 2), composed_us_max=round(max(c), 2),
-                               composed_over_fused=round(_median(c) / _median(us[(loss_name, "fused")]), 2),
+                    row.update(**steplib.spread_fields("composed", c, "us"),
+                               composed_over_fused=round(steplib.median(c) / steplib.median(us[(loss_name, "fused")]), 2),
                                loss_rel_diff_fused_composed=abs(float(lf) - float(lc)) / abs(float(lc)),
                                grad_diff_fused_composed_rel_to_max=float((df - dc).abs().max() / dc.abs().max()))
                 print(json.dumps(row), flush=True)
@@ -138,14 +105,9 @@ def kernels(iters, repeats):
                 "topk_rows_k20": (lambda: ops.topk_rows(p, 20), 4 * B * V, "for comparison, the eval path's top-k (values and indices): 1 read of p"),
                 "xent_bwd": (lambda: ops.xent_bwd(p, y, None, up), read + 4 * B * V, "1 read of (p, y), 1 write of dL/dp"),
             }
-            cus = {k: [] for k in calls}
-            for f, _, _ in calls.values():
-                _events_us(f, iters)
-            for _ in range(repeats):
-                for k, (f, _, _) in calls.items():
-                    cus[k].append(_events_us(f, iters))
+            cus = steplib.alternate({k: c[0] for k, c in calls.items()}, iters, repeats)
             for k, (_, nbytes, what) in calls.items():
-                med = _median(cus[k])
+                med = steplib.median(cus[k])
                 print(json.dumps(dict(leg="call", call=k, predictions=kind, B=B, V=V, us_per_call=round(med, 2), us_min=round(min(cus[k]), 2),
                                       us_max=round(max(cus[k]), 2), algorithmic_bytes=nbytes, passes=what,
                                       tb_per_s_on_algorithmic_bytes=round(nbytes / (med * 1e-6) / 1e12, 3))), flush=True)
@@ -156,8 +118,7 @@ def kernels(iters, repeats):
 
 def child(leg, steps, warmup):
     import numpy as np
-    import torch
-    dev = _setup()
+    dev = steplib.setup()
     import yt8m_amd.losses as losses
     import yt8m_amd.train as train
     import yt8m_amd.video_level_models as vlm
@@ -173,73 +134,32 @@ def child(leg, steps, warmup):
     # heart within some tens of steps -- a perfectly separated batch, where BatchAgreementCrossEntropyLoss is NaN by definition
     tg = train.build_graph(vlm.MoeModel(), batch_size=B, graph=g, base_learning_rate=0.0)
     assert type(tg.label_loss_fn) is getattr(losses, LOSS_OF_LEG[leg])
-    gen = torch.Generator(device=dev).manual_seed(1)
-    x = torch.randn((B, D), device=dev, generator=gen)
-    y = torch.rand((B, V), device=dev, generator=gen) < 3.4 / V
-    loss_first = None
-    for _ in range(warmup):
-        o = tg.step(x, y)
-        if loss_first is None:
-            loss_first = float(o["loss"])
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        out = tg.step(x, y)
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) / steps * 1e3
-    finite = all(bool(torch.isfinite(v.data).all()) for v in g.trainable_variables())
+    x, y, _, _ = steplib.random_batch(dev, B, D=D)
+    loss_first = steplib.warm_up(lambda: tg.step(x, y), warmup)
+    out, elapsed, _ = steplib.timed_steps(lambda: tg.step(x, y), steps)
+    finite = steplib.params_finite(g)
     print(json.dumps(dict(leg=leg, model="MoeModel", label_loss=LOSS_OF_LEG[leg], fused_head_loss=bool(FLAGS.fused_head_loss), B=B, D=D,
-                          V=V, ms_per_step=round(ms, 3), steps=steps, warmup=warmup, loss_first=loss_first, loss=float(out["loss"]),
-                          params_finite=finite, timing="host clock around the steps, ending in a device synchronise")), flush=True)
+                          V=V, ms_per_step=round(elapsed / steps * 1e3, 3), steps=steps, warmup=warmup, loss_first=loss_first,
+                          loss=float(out["loss"]), params_finite=finite,
+                          timing="host clock around the steps, ending in a device synchronise")), flush=True)
     return 0 if finite and np.isfinite(loss_first) else 1
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
+def parser():
+    ap = steplib.arg_parser(steps=50, warmup=5, timeout=300)
     ap.add_argument("--repeats", type=int, default=5, help="times every step leg runs (in turn), and timing repeats of the kernel leg")
     ap.add_argument("--kernel_iters", type=int, default=100)
-    ap.add_argument("--timeout", type=int, default=300, help="seconds per leg")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("legs", nargs="*")
-    a = ap.parse_args()
+    return ap
+
+
+def main():
+    a = steplib.parse_args(parser(), ("kernels",) + LEGS)
     if a.child == "kernels":
         return kernels(a.kernel_iters, a.repeats)
     if a.child:
         return child(a.child, a.steps, a.warmup)
-    legs = a.legs or ["kernels"] + list(LEGS)
-    plan = [(leg, 0) for leg in legs if leg == "kernels"] + [(leg, rep) for rep in range(a.repeats) for leg in legs if leg != "kernels"]
-    rows = []
-    for leg, rep in plan:
-        cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", leg, "--steps", str(a.steps),
-               "--warmup", str(a.warmup), "--repeats", str(a.repeats), "--kernel_iters", str(a.kernel_iters)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
-        if r.returncode != 0 or not lines:
-            sys.stderr.write(r.stdout[-4000:] + r.stderr[-4000:])
-            print("leg %s failed with exit status %d: stopping" % (leg, r.returncode), flush=True)
-            return r.returncode or 1
-        for ln in lines:
-            row = json.loads(ln)
-            if leg != "kernels":
-                row["rep"] = rep
-            rows.append(row)
-            print(json.dumps(row), flush=True)
-    by = {}
-    for r in rows:
-        if "ms_per_step" in r:
-            by.setdefault(r["leg"], []).append(r["ms_per_step"])
-    for leg, v in by.items():
-        row = dict(leg=leg + "_summary", ms_per_step_median=sorted(v)[len(v) // 2], ms_per_step_min=min(v), ms_per_step_max=max(v), runs=len(v))
-        rows.append(row)
-        print(json.dumps(row), flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            for r in rows:
-                f.write(json.dumps(r) + "\n")
-    return 0
+    return steplib.drive(__file__, steplib.repeated_plan(a.legs or ["kernels"] + list(LEGS), "kernels", a.repeats),
+                         steplib.child_args(a, "repeats", "kernel_iters"), a.timeout, a.out, summarise=steplib.per_leg_medians)
 
 
 if __name__ == "__main__":

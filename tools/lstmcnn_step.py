@@ -9,14 +9,11 @@ limit; the driver stops at the first leg that fails; without a GPU a leg fails, 
 and composed twice: the difference between the two runs of one leg is the repeat-to-repeat spread the comparison has to be read against.
 The timed window of a leg is device-synchronised at both ends and at least --min_seconds long.
 usage: python tools/lstmcnn_step.py [--steps K] [--warmup W] [--out FILE] [leg ...]    legs: pooled pooled_chain composed parallel kernels"""
-import argparse
 import json
-import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import steplib
+
 LEGS = {
     "pooled": "LstmCnnDeepCombineChainModel",
     "pooled_chain": "LstmCnnDeepCombineChainModel",
@@ -25,7 +22,7 @@ LEGS = {
     "kernels": None,
 }
 DEFAULT_ORDER = ["pooled", "composed", "pooled", "composed", "pooled_chain", "parallel", "kernels"]
-B, F, D, V = 128, 300, 1152, 4716
+B, F, D = 128, 300, 1152
 CHAIN = [[(1, 128), (2, 256), (3, 128)]] + [[(1, 128), (2, 128), (3, 256)]] * 3          # (filter length, columns) per CNN, c = 128
 
 
@@ -38,18 +35,8 @@ def gather_bytes(B_, F_, D_, chain):
     return dict(dw=rows + 4.0 * terms * D_ + 8.0 * B_ * terms, dx=rows + 4.0 * F_ * B_ * D_ + 8.0 * B_ * cols)
 
 
-def _setup():
-    import torch
-    sys.path.insert(0, ROOT)
-    import __graft_entry__
-    __graft_entry__.load_package()
-    dev = torch.device("cuda:0")                                       # (no device: this raises, nothing falls back)
-    torch.cuda.set_device(dev)
-    return torch, dev
-
-
 def child_step(leg, steps, warmup, min_seconds):
-    torch, dev = _setup()
+    dev = steplib.setup()
     import yt8m_amd.frame_level_models as flm
     import yt8m_amd.losses as losses
     import yt8m_amd.seq_ops as seq_ops
@@ -71,29 +58,13 @@ def child_step(leg, steps, warmup, min_seconds):
     g = reset_default_graph(device=dev, seed=0)
     kw = dict(label_loss_fn=losses.MultiTaskCrossEntropyLoss(), multitask=True) if chain else {}
     tg = train.TrainGraph(getattr(flm, LEGS[leg])(), batch_size=B, graph=g, **kw)
-    gen = torch.Generator(device=dev).manual_seed(1)
-    x = torch.randint(0, 256, (B, F, D), device=dev, generator=gen, dtype=torch.uint8)
-    nf = torch.full((B,), F, device=dev, dtype=torch.int32)            # all 300 frames
-    y = torch.rand((B, V), device=dev, generator=gen) < 3.4 / V
+    x, y, nf, _ = steplib.random_batch(dev, B, F, "all")                  # all 300 frames
     calls = dict(seq_ops.NATIVE_CALLS)
-    loss_first = None
-    for _ in range(warmup):
-        o = tg.step(x, y, nf)
-        seq_ops.check_persist_errors()
-        if loss_first is None:
-            loss_first = float(o["loss"])
+    loss_first = steplib.warm_up(lambda: tg.step(x, y, nf), warmup, seq_ops.check_persist_errors)
     native = seq_ops.NATIVE_CALLS["fwd"] - calls["fwd"]
-    done, elapsed = 0, 0.0
-    while elapsed < min_seconds:                                       # whole windows of `steps` steps until the window is long enough
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            out = tg.step(x, y, nf)
-        torch.cuda.synchronize()
-        elapsed += time.perf_counter() - t0
-        done += steps
+    out, elapsed, done = steplib.timed_steps(lambda: tg.step(x, y, nf), steps, min_seconds)
     seq_ops.check_persist_errors()
-    finite = all(bool(torch.isfinite(v.data).all()) for v in g.trainable_variables())
+    finite = steplib.params_finite(g)
     print(json.dumps(dict(leg=leg, model=LEGS[leg], ms_per_step=round(elapsed / done * 1e3, 3), steps=done, warmup=warmup,
                           window_s=round(elapsed, 3), loss_first=loss_first, loss=float(out["loss"]), params_finite=finite,
                           native_stacks_per_step=native / max(warmup, 1))), flush=True)
@@ -104,7 +75,8 @@ def child_kernels(reps):
     """yt8m_f32_cnn_pool_dw (the 12 calls of one backward pass, timed together) and yt8m_f32_cnn_pool_dx (one call) at the script's
     shape on random argmax frames.  Both are gathers from L2 / Infinity Cache, not streams: the [F B, 1152] fp32 operand of dw is 177 MB
     (it does not fit the cache whole), the transposed filters of dx 21 MB (they do)."""
-    torch, dev = _setup()
+    import torch
+    dev = steplib.setup()
     import ctypes
     import yt8m_amd._lib as L
     lib = L.lib()
@@ -138,64 +110,35 @@ def child_kernels(reps):
     for name, (nb, fn) in cases.items():
         for _ in range(3):
             L.check(fn())
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(reps):
-            L.check(fn())
-        e1.record()
-        torch.cuda.synchronize()
-        us = e0.elapsed_time(e1) / reps * 1e3
+        us = steplib.events_us(lambda: L.check(fn()), reps)
         rows.append(dict(kernel=name, us=round(us, 1), mbytes=round(nb / 1e6, 1), tb_per_s=round(nb / us / 1e6, 2)))
     print(json.dumps(dict(leg="kernels", shape=[F, B, D], columns=Ntot, reps=reps, kernels=rows)), flush=True)
     return 0
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
+def summarise(rows):
+    by = steplib.ms_by_leg(rows)
+    if not ("pooled" in by and "composed" in by):
+        return rows
+    spread = lambda v: round(max(v) - min(v), 3) if len(v) > 1 else None
+    sp, sc = spread(by["pooled"]), spread(by["composed"])
+    gain = min(by["composed"]) - max(by["pooled"])                     # the smallest difference any pairing of the runs shows
+    return rows + [dict(pooled_ms=by["pooled"], composed_ms=by["composed"], pooled_spread_ms=sp, composed_spread_ms=sc,
+                        pooled_over_composed=round(min(by["pooled"]) / min(by["composed"]), 3), pooled_chain_ms=by.get("pooled_chain"),
+                        parallel_ms=by.get("parallel"), pooled_faster_beyond_spread=bool(gain > max(sp or 0.0, sc or 0.0)))]
+
+
+def parser():
+    ap = steplib.arg_parser(steps=10, warmup=3, timeout=300)
     ap.add_argument("--min_seconds", type=float, default=1.0, help="shortest timed window of a leg")
-    ap.add_argument("--timeout", type=int, default=300, help="seconds per leg")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("legs", nargs="*")
-    a = ap.parse_args()
-    for leg in a.legs + ([a.child] if a.child else []):
-        if leg not in LEGS:
-            ap.error("unknown leg %r (legs: %s)" % (leg, " ".join(LEGS)))
+    return ap
+
+
+def main():
+    a = steplib.parse_args(parser(), list(LEGS))
     if a.child:
         return child_kernels(20) if a.child == "kernels" else child_step(a.child, a.steps, a.warmup, a.min_seconds)
-    rows = []
-    for leg in a.legs or DEFAULT_ORDER:
-        cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", leg, "--steps", str(a.steps),
-               "--warmup", str(a.warmup), "--min_seconds", str(a.min_seconds)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
-        if r.returncode != 0 or not line:
-            sys.stderr.write(r.stdout[-4000:] + r.stderr[-4000:])
-            print("leg %s failed with exit status %d: stopping" % (leg, r.returncode), flush=True)
-            return r.returncode or 1
-        rows.append(json.loads(line[-1]))
-        print(line[-1], flush=True)
-    by = {}
-    for r in rows:
-        if "ms_per_step" in r:
-            by.setdefault(r["leg"], []).append(r["ms_per_step"])
-    if "pooled" in by and "composed" in by:
-        spread = lambda v: round(max(v) - min(v), 3) if len(v) > 1 else None
-        sp, sc = spread(by["pooled"]), spread(by["composed"])
-        gain = min(by["composed"]) - max(by["pooled"])                 # the smallest difference any pairing of the runs shows
-        summary = dict(pooled_ms=by["pooled"], composed_ms=by["composed"], pooled_spread_ms=sp, composed_spread_ms=sc,
-                       pooled_over_composed=round(min(by["pooled"]) / min(by["composed"]), 3), pooled_chain_ms=by.get("pooled_chain"),
-                       parallel_ms=by.get("parallel"), pooled_faster_beyond_spread=bool(gain > max(sp or 0.0, sc or 0.0)))
-        print(json.dumps(summary), flush=True)
-        rows.append(summary)
-    if a.out:
-        with open(a.out, "w") as f:
-            for r in rows:
-                f.write(json.dumps(r) + "\n")
-    return 0
+    return steplib.drive(__file__, a.legs or DEFAULT_ORDER, steplib.child_args(a, "min_seconds"), a.timeout, a.out, summarise=summarise)
 
 
 if __name__ == "__main__":

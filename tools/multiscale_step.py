@@ -6,14 +6,11 @@ its own under its own time limit; the driver stops at the first leg that fails; 
 default order alternates fused and generic twice: the difference between the two runs of one leg is the repeat-to-repeat spread the
 comparison has to be read against.  The timed window of a leg is device-synchronised at both ends and at least --min_seconds long.
 usage: python tools/multiscale_step.py [--steps K] [--warmup W] [--out FILE] [leg ...]    legs: fused generic lstm kernels"""
-import argparse
 import json
-import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import steplib
+
 LEGS = {
     "fused": ("MultiscaleCnnLstmModel", "1"),
     "generic": ("MultiscaleCnnLstmModel", "0"),
@@ -24,25 +21,15 @@ DEFAULT_ORDER = ["fused", "generic", "fused", "generic", "lstm", "kernels"]
 HBM_PEAK_TBS, HBM_MEASURED_TBS, INFINITY_CACHE_MIB = 8.0, 6.3, 256     # MI355X: spec, float4 copy, last-level cache
 
 
-def _setup():
-    import torch
-    sys.path.insert(0, ROOT)
-    import __graft_entry__
-    __graft_entry__.load_package()
-    dev = torch.device("cuda:0")
-    torch.cuda.set_device(dev)
-    return torch, dev
-
-
 def child_step(leg, steps, warmup, min_seconds):
-    torch, dev = _setup()
+    dev = steplib.setup()
     import yt8m_amd.frame_level_models as flm
     import yt8m_amd.losses as losses
     import yt8m_amd.seq_ops as seq_ops
     import yt8m_amd.train as train
     from yt8m_amd.flags import FLAGS
     from yt8m_amd.variables import reset_default_graph
-    B, F, D, V = 128, 300, 1152, 4716
+    B, F = 128, 300
     FLAGS.reset()
     FLAGS.lstm_cells, FLAGS.lstm_layers = "1024", 2
     FLAGS.multiscale_cnn_lstm_layers, FLAGS.moe_num_mixtures, FLAGS.is_training = 4, 4, True
@@ -51,29 +38,13 @@ def child_step(leg, steps, warmup, min_seconds):
     g = reset_default_graph(device=dev, seed=0)
     kw = dict(label_loss_fn=losses.MultiTaskCrossEntropyLoss(), multitask=True) if multiscale else {}
     tg = train.TrainGraph(getattr(flm, LEGS[leg][0])(), batch_size=B, graph=g, **kw)
-    gen = torch.Generator(device=dev).manual_seed(1)
-    x = torch.randint(0, 256, (B, F, D), device=dev, generator=gen, dtype=torch.uint8)
-    nf = torch.randint(F // 2, F + 1, (B,), device=dev, generator=gen, dtype=torch.int32)
-    y = torch.rand((B, V), device=dev, generator=gen) < 3.4 / V
+    x, y, nf, _ = steplib.random_batch(dev, B, F)
     calls = dict(seq_ops.NATIVE_CALLS)
-    loss_first = None
-    for _ in range(warmup):
-        o = tg.step(x, y, nf)
-        seq_ops.check_persist_errors()
-        if loss_first is None:
-            loss_first = float(o["loss"])
+    loss_first = steplib.warm_up(lambda: tg.step(x, y, nf), warmup, seq_ops.check_persist_errors)
     native = seq_ops.NATIVE_CALLS["fwd"] - calls["fwd"]
-    done, elapsed = 0, 0.0
-    while elapsed < min_seconds:                                       # whole windows of `steps` steps until the window is long enough
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            out = tg.step(x, y, nf)
-        torch.cuda.synchronize()
-        elapsed += time.perf_counter() - t0
-        done += steps
+    out, elapsed, done = steplib.timed_steps(lambda: tg.step(x, y, nf), steps, min_seconds)
     seq_ops.check_persist_errors()
-    finite = all(bool(torch.isfinite(v.data).all()) for v in g.trainable_variables())
+    finite = steplib.params_finite(g)
     print(json.dumps(dict(leg=leg, model=LEGS[leg][0], fused=bool(seq_ops.MULTISCALE_FUSED) if multiscale else None,
                           ms_per_step=round(elapsed / done * 1e3, 3), steps=done, warmup=warmup, window_s=round(elapsed, 3),
                           loss_first=loss_first, loss=float(out["loss"]), params_finite=finite,
@@ -87,7 +58,8 @@ def child_kernels(reps):
     writes dy.  The 157 MB tensors partly fit the 256 MiB Infinity Cache (a kernel's second read of y, or the reads of a tensor the
     previous kernel just wrote, may come from it): figures up to the measured HBM rate (6.3 TB/s; 8 TB/s spec) can be read against HBM,
     anything above only against the cache."""
-    torch, dev = _setup()
+    import torch
+    dev = steplib.setup()
     import ctypes
     import yt8m_amd._lib as L
     lib = L.lib()
@@ -117,62 +89,36 @@ def child_kernels(reps):
     for name, (nbytes, fn) in cases.items():
         for _ in range(3):
             L.check(fn())
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(reps):
-            L.check(fn())
-        e1.record()
-        torch.cuda.synchronize()
-        us = e0.elapsed_time(e1) / reps * 1e3
+        us = steplib.events_us(lambda: L.check(fn()), reps)
         rows.append(dict(kernel=name, us=round(us, 1), mbytes=round(nbytes / 1e6, 1), tb_per_s=round(nbytes / us / 1e6, 2)))
     print(json.dumps(dict(leg="kernels", shape=[F, B, C], reps=reps, hbm_peak_tb_per_s=HBM_PEAK_TBS, hbm_measured_tb_per_s=HBM_MEASURED_TBS,
                           infinity_cache_mib=INFINITY_CACHE_MIB, tensor_mbytes=round(full / 1e6, 1), kernels=rows)), flush=True)
     return 0
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
+def summarise(rows):
+    by = steplib.ms_by_leg(rows)
+    if not ("fused" in by and "generic" in by):
+        return rows
+    spread = lambda v: round(max(v) - min(v), 3) if len(v) > 1 else None
+    fused, generic = min(by["fused"]), min(by["generic"])
+    return rows + [dict(fused_ms=by["fused"], generic_ms=by["generic"], fused_spread_ms=spread(by["fused"]),
+                        generic_spread_ms=spread(by["generic"]), fused_over_generic=round(fused / generic, 3),
+                        lstm_ms=by.get("lstm"), fused_default=max(by["fused"]) <= max(by["generic"]))]
+
+
+def parser():
+    ap = steplib.arg_parser(steps=10, warmup=3, timeout=300)
     ap.add_argument("--min_seconds", type=float, default=1.0, help="shortest timed window of a leg")
-    ap.add_argument("--timeout", type=int, default=300, help="seconds per leg")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("legs", nargs="*")
-    a = ap.parse_args()
+    return ap
+
+
+def main():
+    a = steplib.parse_args(parser(), list(LEGS))
     if a.child:
         return child_kernels(50) if a.child == "kernels" else child_step(a.child, a.steps, a.warmup, a.min_seconds)
-    rows = []
-    for leg in a.legs or DEFAULT_ORDER:
-        env = dict(os.environ, YT8M_MULTISCALE_FUSED=LEGS[leg][1])
-        cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", leg, "--steps", str(a.steps),
-               "--warmup", str(a.warmup), "--min_seconds", str(a.min_seconds)]
-        r = subprocess.run(cmd, env=env, capture_output=True, text=True)
-        line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
-        if r.returncode != 0 or not line:
-            sys.stderr.write(r.stdout[-4000:] + r.stderr[-4000:])
-            print("leg %s failed with exit status %d: stopping" % (leg, r.returncode), flush=True)
-            return r.returncode or 1
-        rows.append(json.loads(line[-1]))
-        print(line[-1], flush=True)
-    by = {}
-    for r in rows:
-        if "ms_per_step" in r:
-            by.setdefault(r["leg"], []).append(r["ms_per_step"])
-    if "fused" in by and "generic" in by:
-        spread = lambda v: round(max(v) - min(v), 3) if len(v) > 1 else None
-        fused, generic = min(by["fused"]), min(by["generic"])
-        summary = dict(fused_ms=by["fused"], generic_ms=by["generic"], fused_spread_ms=spread(by["fused"]),
-                       generic_spread_ms=spread(by["generic"]), fused_over_generic=round(fused / generic, 3),
-                       lstm_ms=by.get("lstm"), fused_default=max(by["fused"]) <= max(by["generic"]))
-        print(json.dumps(summary), flush=True)
-        rows.append(summary)
-    if a.out:
-        with open(a.out, "w") as f:
-            for r in rows:
-                f.write(json.dumps(r) + "\n")
-    return 0
+    return steplib.drive(__file__, a.legs or DEFAULT_ORDER, steplib.child_args(a, "min_seconds"), a.timeout, a.out,
+                         env_of=lambda leg: {"YT8M_MULTISCALE_FUSED": LEGS[leg][1]}, summarise=summarise)
 
 
 if __name__ == "__main__":

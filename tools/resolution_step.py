@@ -7,27 +7,14 @@ Step legs: LstmMemoryModel ms / step (fp32 step with clip + Adam) with --feature
 fused and composed, and under DefaultTransformer (all 300 frames) for scale.  Every leg runs in a child process of its own under its own
 time limit, the step legs `--repeats` times in turn; the driver stops at the first leg that fails.
 usage: python tools/resolution_step.py [--steps K] [--warmup W] [--repeats N] [--out FILE] [leg ...]      legs: see LEGS, and `kernels`"""
-import argparse
 import json
-import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import steplib
+
 LEGS = ("lstmmem_resolution_fused", "lstmmem_resolution_composed", "lstmmem_default")
-B, F, D, V = 128, 300, 1152, 4716
+B, F, D = 128, 300, 1152
 RESOLUTION = 8
-
-
-def _setup():
-    import torch
-    sys.path.insert(0, ROOT)
-    import __graft_entry__
-    __graft_entry__.load_package()
-    dev = torch.device("cuda:0")
-    torch.cuda.set_device(dev)
-    return dev
 
 
 def composed_resolution_mean(q, num_frames, r):
@@ -42,25 +29,11 @@ def composed_resolution_mean(q, num_frames, r):
     return ops.l2norm_fwd(m), torch.div(nf, r, rounding_mode="floor").to(torch.int32)
 
 
-def _events_us(fn, iters):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e3
-
-
 def kernels(iters, repeats):
     import torch
-    dev = _setup()
+    dev = steplib.setup()
     import yt8m_amd.ops as ops
-    gen = torch.Generator(device=dev).manual_seed(1)
-    q = torch.randint(0, 256, (B, F, D), device=dev, generator=gen, dtype=torch.uint8)
-    nf = torch.randint(F // 2, F + 1, (B,), device=dev, generator=gen, dtype=torch.int32)
+    q, _, nf, _ = steplib.random_batch(dev, B, F)
     live = torch.arange(F, device=dev).view(1, F) < nf.view(B, 1)
     q = q * live.unsqueeze(2).to(torch.uint8)                                # the reader's zero padding
     for r in (2, 8, 30):
@@ -75,27 +48,25 @@ def kernels(iters, repeats):
             composed()
         us = {"fused": [], "composed": []}
         for _ in range(repeats):                                             # alternating: both forms see the same machine
-            us["fused"].append(_events_us(fused, iters))
-            us["composed"].append(_events_us(composed, iters))
+            us["fused"].append(steplib.events_us(fused, iters))
+            us["composed"].append(steplib.events_us(composed, iters))
         nbytes = int(torch.minimum(nf, torch.tensor(F2 * r, device=dev)).sum()) * D + 4 * B * F2 * D
         for form in ("fused", "composed"):
-            v = sorted(us[form])
-            med = v[len(v) // 2]
-            print(json.dumps(dict(leg="kernel", form=form, resolution=r, B=B, F=F, D=D, us_per_call=round(med, 2), us_min=round(v[0], 2),
-                                  us_max=round(v[-1], 2), repeats=repeats, algorithmic_bytes=nbytes,
+            med = steplib.median(us[form])
+            print(json.dumps(dict(leg="kernel", form=form, resolution=r, B=B, F=F, D=D, us_per_call=round(med, 2),
+                                  us_min=round(min(us[form]), 2), us_max=round(max(us[form]), 2), repeats=repeats, algorithmic_bytes=nbytes,
                                   tb_per_s_on_algorithmic_bytes=round(nbytes / (med * 1e-6) / 1e12, 3), max_abs_diff_fused_composed=diff,
                                   timing="hip events over %d back-to-back calls (torch allocations included), median of the repeats"
                                          % iters)), flush=True)
-        print(json.dumps(dict(leg="kernel_ratio", resolution=r, composed_over_fused=round(sorted(us["composed"])[repeats // 2]
-                                                                                          / sorted(us["fused"])[repeats // 2], 2),
+        print(json.dumps(dict(leg="kernel_ratio", resolution=r,
+                              composed_over_fused=round(steplib.median(us["composed"]) / steplib.median(us["fused"]), 2),
                               slowest_fused_us=round(max(us["fused"]), 2), fastest_composed_us=round(min(us["composed"]), 2))), flush=True)
     return 0
 
 
 def child(leg, steps, warmup):
     import numpy as np
-    import torch
-    dev = _setup()
+    dev = steplib.setup()
     import yt8m_amd.feature_transform as ft
     import yt8m_amd.frame_level_models as flm
     import yt8m_amd.seq_ops as seq_ops
@@ -113,77 +84,33 @@ def child(leg, steps, warmup):
     FLAGS.lstm_cells, FLAGS.lstm_layers, FLAGS.time_resolution = "1024", 2, RESOLUTION
     g = reset_default_graph(device=dev, seed=0)
     tg = train.TrainGraph(flm.LstmMemoryModel(), batch_size=B, graph=g, transformer_class=transformer)
-    gen = torch.Generator(device=dev).manual_seed(1)
-    x = torch.randint(0, 256, (B, F, D), device=dev, generator=gen, dtype=torch.uint8)
-    nf = torch.randint(F // 2, F + 1, (B,), device=dev, generator=gen, dtype=torch.int32)
-    y = torch.rand((B, V), device=dev, generator=gen) < 3.4 / V
-    loss_first = None
-    for _ in range(warmup):
-        o = tg.step(x, y, nf)
-        seq_ops.check_persist_errors()
-        if loss_first is None:
-            loss_first = float(o["loss"])
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        out = tg.step(x, y, nf)
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) / steps * 1e3
+    x, y, nf, _ = steplib.random_batch(dev, B, F)
+    loss_first = steplib.warm_up(lambda: tg.step(x, y, nf), warmup, seq_ops.check_persist_errors)
+    out, elapsed, _ = steplib.timed_steps(lambda: tg.step(x, y, nf), steps)
     seq_ops.check_persist_errors()
-    finite = all(bool(torch.isfinite(v.data).all()) for v in g.trainable_variables())
+    finite = steplib.params_finite(g)
     print(json.dumps(dict(leg=leg, model="LstmMemoryModel", transformer=transformer.__name__, videos=B, frames=F,
-                          time_resolution=RESOLUTION if "resolution" in leg else None, ms_per_step=round(ms, 3), steps=steps,
+                          time_resolution=RESOLUTION if "resolution" in leg else None, ms_per_step=round(elapsed / steps * 1e3, 3), steps=steps,
                           warmup=warmup, loss_first=loss_first, loss=float(out["loss"]), params_finite=finite,
                           timing="host clock around the steps, ending in a device synchronise")), flush=True)
     return 0 if finite and np.isfinite(loss_first) else 1
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+def parser():
+    ap = steplib.arg_parser(steps=20, warmup=3, timeout=300)
     ap.add_argument("--repeats", type=int, default=3, help="times every step leg runs (in turn), and timing repeats of the kernel leg")
     ap.add_argument("--kernel_iters", type=int, default=50)
-    ap.add_argument("--timeout", type=int, default=300, help="seconds per leg")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("legs", nargs="*")
-    a = ap.parse_args()
+    return ap
+
+
+def main():
+    a = steplib.parse_args(parser(), ("kernels",) + LEGS)
     if a.child == "kernels":
         return kernels(a.kernel_iters, a.repeats)
     if a.child:
         return child(a.child, a.steps, a.warmup)
-    legs = a.legs or ["kernels"] + list(LEGS)
-    plan = [(leg, 0) for leg in legs if leg == "kernels"] + [(leg, rep) for rep in range(a.repeats) for leg in legs if leg != "kernels"]
-    rows = []
-    for leg, rep in plan:
-        cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", leg, "--steps", str(a.steps),
-               "--warmup", str(a.warmup), "--repeats", str(a.repeats), "--kernel_iters", str(a.kernel_iters)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
-        if r.returncode != 0 or not lines:
-            sys.stderr.write(r.stdout[-4000:] + r.stderr[-4000:])
-            print("leg %s failed with exit status %d: stopping" % (leg, r.returncode), flush=True)
-            return r.returncode or 1
-        for ln in lines:
-            row = json.loads(ln)
-            if leg != "kernels":
-                row["rep"] = rep
-            rows.append(row)
-            print(json.dumps(row), flush=True)
-    by = {}
-    for r in rows:
-        if "ms_per_step" in r:
-            by.setdefault(r["leg"], []).append(r["ms_per_step"])
-    for leg, v in by.items():
-        row = dict(leg=leg + "_summary", ms_per_step_median=sorted(v)[len(v) // 2], ms_per_step_min=min(v), ms_per_step_max=max(v), runs=len(v))
-        rows.append(row)
-        print(json.dumps(row), flush=True)
-    if a.out:
-        with open(a.out, "w") as f:
-            for r in rows:
-                f.write(json.dumps(r) + "\n")
-    return 0
+    return steplib.drive(__file__, steplib.repeated_plan(a.legs or ["kernels"] + list(LEGS), "kernels", a.repeats),
+                         steplib.child_args(a, "repeats", "kernel_iters"), a.timeout, a.out, summarise=steplib.per_leg_medians)
 
 
 if __name__ == "__main__":
