@@ -14,7 +14,7 @@
 // with two forms of the recurrent product: the packed-weight MFMA step kernels of lstm_fused.hip with the cell's pointwise
 // block as their epilogue (H % 256 == 0: GRU 2 launches per forward step / 3 per backward step, LN-LSTM 2 / 2), else one
 // grouped-GEMM launch per product.
-#include "common.h"
+#include "step_kernels.h"
 
 namespace {
 
@@ -358,18 +358,6 @@ __global__ __launch_bounds__(256) void lnlstm_bwd_kernel(const float* __restrict
 
 using namespace yt8m;
 
-namespace yt8m {  // lstm_fused.hip: packed-weight step products (one launch per product, epilogue fused)
-bool cell_packed_supported(int64_t B, int64_t H);
-int cell_pack(const float* Wh, int64_t ldw, float* Wp, float* Wq, int64_t H, int G, hipStream_t s);
-int cell_step_add4(float* z, const float* Wp, const float* h_prev, int64_t B, int64_t H, hipStream_t s);
-int gru_step_gates(float* zg, const float* Wp_g, const float* h_prev, float* rh, int64_t B, int64_t H, hipStream_t s);
-int gru_step_cand(float* zc, const float* Wp_c, const float* rh, const float* zg, const float* h_prev, float* h_new, float* out,
-                  const int32_t* nf, int t, int64_t B, int64_t H, hipStream_t s);
-int cell_step_bwd(const float* dz, const float* Wq, float* dh_prev, int64_t B, int64_t H, int G, hipStream_t s);
-int gru_step_bwd_cand(const float* dzc, const float* Wq_c, float* dh_prev, const float* zg, const float* h_prev, float* dzg,
-                      const int32_t* nf, int t, int64_t B, int64_t H, hipStream_t s);
-}  // namespace yt8m
-
 static bool packed_ok(int64_t B, int64_t H, int G, void* ws, int64_t ws_bytes) {
   static const bool off = getenv("YT8M_NO_PACKED_CELLS") != nullptr;      // A/B switch for tools/ and tests
   return !off && ws && cell_packed_supported(B, H) && ws_bytes >= (int64_t)sizeof(float) * H * G * H;
@@ -400,25 +388,23 @@ extern "C" int yt8m_gru_layer_fwd(float* zg, float* zc, const float* Wg_h, int64
     }
     return rc;
   }
+  const StepProduct gate = {Wg_h, ldg, nullptr, nullptr, 2, B, H, gemm_workspace, gemm_workspace_bytes, stream};
+  const StepProduct cand = {Wc_h, ldc, nullptr, nullptr, 1, B, H, gemm_workspace, gemm_workspace_bytes, stream};
   for (int64_t t = 0; t < F; ++t) {
     float* zgt = zg + t * B * 2 * H;
     float* zct = zc + t * BH;
     float* rht = rh + t * BH;
-    yt8m_gemm_problem pg = {B, 2 * H, H, hs + t * BH, H, Wg_h, ldg, zgt, 2 * H, nullptr, 1.0f};      // zg_t += h . Wg_h
-    int rc = yt8m_gemm_f32_grouped(0, 0, 1, &pg, gemm_workspace, gemm_workspace_bytes, stream);
+    int rc = gate.add_hW(hs + t * BH, zgt);                                                           // zg_t += h . Wg_h
     if (rc != YT8M_OK) return rc;
     {
       ProfScope prof(F_LSTM, s);
       hipLaunchKernelGGL(gru_gates_kernel, grid, dim3(256), 0, s, zgt, hs + t * BH, rht, B, H);
     }
-    yt8m_gemm_problem pc = {B, H, H, rht, H, Wc_h, ldc, zct, H, nullptr, 1.0f};                       // zc_t += (r*h) . Wc_h
-    rc = yt8m_gemm_f32_grouped(0, 0, 1, &pc, gemm_workspace, gemm_workspace_bytes, stream);
+    rc = cand.add_hW(rht, zct);                                                                       // zc_t += (r*h) . Wc_h
     if (rc != YT8M_OK) return rc;
-    {
-      ProfScope prof(F_LSTM, s);
-      hipLaunchKernelGGL(gru_out_kernel, grid, dim3(256), 0, s, zct, zgt, hs + t * BH, hs + (t + 1) * BH,
-                         out ? out + t * BH : nullptr, num_frames, (int)t, B, H);
-    }
+    ProfScope prof(F_LSTM, s);
+    hipLaunchKernelGGL(gru_out_kernel, grid, dim3(256), 0, s, zct, zgt, hs + t * BH, hs + (t + 1) * BH,
+                       out ? out + t * BH : nullptr, num_frames, (int)t, B, H);
   }
   return launch_status("gru step kernels");
 }
@@ -436,8 +422,7 @@ extern "C" int yt8m_gru_layer_bwd(const float* zg, const float* zc, const float*
   float* dh_cur = work;
   float* dh_prev = work + BH;
   float* drh = work + 2 * BH;
-  if (dh_final) YT8M_HIP_CHECK(hipMemcpyAsync(dh_cur, dh_final, BH * sizeof(float), hipMemcpyDeviceToDevice, s));
-  else YT8M_HIP_CHECK(hipMemsetAsync(dh_cur, 0, BH * sizeof(float), s));
+  YT8M_HIP_CHECK(seed_state(dh_cur, dh_final, BH, s));
   const dim3 grid((unsigned)((BH + 255) / 256));
   const bool packed = packed_ok(B, H, 3, gemm_workspace, gemm_workspace_bytes);
   float* Wq_g = static_cast<float*>(gemm_workspace);
@@ -448,36 +433,32 @@ extern "C" int yt8m_gru_layer_bwd(const float* zg, const float* zc, const float*
     if (rc == YT8M_OK) rc = cell_pack(Wc_h, ldc, nullptr, Wq_c, H, 1, s);
     if (rc != YT8M_OK) return rc;
   }
-  for (int64_t t = F - 1; t >= 0; --t) {
+  const StepProduct gate = {Wg_h, ldg, nullptr, packed ? Wq_g : nullptr, 2, B, H, gemm_workspace, gemm_workspace_bytes, stream};
+  for (int64_t t = F - 1; t >= 0; --t, std::swap(dh_cur, dh_prev)) {
     const float* zgt = zg + t * B * 2 * H;
     float* dzgt = dzg + t * B * 2 * H;
     float* dzct = dzc + t * BH;
-    if (packed) {                                  // 3 launches per step
+    int rc = YT8M_OK;
+    {
       ProfScope prof(F_LSTM, s);
       hipLaunchKernelGGL(gru_bwd1_kernel, grid, dim3(256), 0, s, zgt, zc + t * BH, hs + t * BH, dh_cur,
                          dout ? dout + t * BH : nullptr, dzgt, dzct, dh_prev, num_frames, (int)t, B, H);
-      int rc = gru_step_bwd_cand(dzct, Wq_c, dh_prev, zgt, hs + t * BH, dzgt, num_frames, (int)t, B, H, s);
-      if (rc == YT8M_OK) rc = cell_step_bwd(dzgt, Wq_g, dh_prev, B, H, 2, s);
+      if (packed) {                                // 3 launches per step, one scope: d(r*h) is folded into dzg_r and dh_prev
+        rc = gru_step_bwd_cand(dzct, Wq_c, dh_prev, zgt, hs + t * BH, dzgt, num_frames, (int)t, B, H, s);
+        if (rc == YT8M_OK) rc = gate.add_dzWt(dzgt, dh_prev, true);
+      }
+    }
+    if (!packed) {
+      yt8m_gemm_problem pc = {B, H, H, dzct, H, Wc_h, ldc, drh, H, nullptr, 0.0f};                     // drh = dzc . Wc_h^T
+      rc = yt8m_gemm_f32_grouped(0, 1, 1, &pc, gemm_workspace, gemm_workspace_bytes, stream);
       if (rc != YT8M_OK) return rc;
-      float* tmp = dh_cur; dh_cur = dh_prev; dh_prev = tmp;
-      continue;
+      {
+        ProfScope prof(F_LSTM, s);
+        hipLaunchKernelGGL(gru_bwd2_kernel, grid, dim3(256), 0, s, zgt, hs + t * BH, drh, dzgt, dh_prev, num_frames, (int)t, B, H);
+      }
+      rc = gate.add_dzWt(dzgt, dh_prev);
     }
-    {
-      ProfScope prof(F_LSTM, s);
-      hipLaunchKernelGGL(gru_bwd1_kernel, grid, dim3(256), 0, s, zgt, zc + t * BH, hs + t * BH, dh_cur,
-                         dout ? dout + t * BH : nullptr, dzgt, dzct, dh_prev, num_frames, (int)t, B, H);
-    }
-    yt8m_gemm_problem pc = {B, H, H, dzct, H, Wc_h, ldc, drh, H, nullptr, 0.0f};                       // drh = dzc . Wc_h^T
-    int rc = yt8m_gemm_f32_grouped(0, 1, 1, &pc, gemm_workspace, gemm_workspace_bytes, stream);
     if (rc != YT8M_OK) return rc;
-    {
-      ProfScope prof(F_LSTM, s);
-      hipLaunchKernelGGL(gru_bwd2_kernel, grid, dim3(256), 0, s, zgt, hs + t * BH, drh, dzgt, dh_prev, num_frames, (int)t, B, H);
-    }
-    yt8m_gemm_problem pg = {B, H, 2 * H, dzgt, 2 * H, Wg_h, ldg, dh_prev, H, nullptr, 1.0f};           // dh_prev += dzg . Wg_h^T
-    rc = yt8m_gemm_f32_grouped(0, 1, 1, &pg, gemm_workspace, gemm_workspace_bytes, stream);
-    if (rc != YT8M_OK) return rc;
-    float* tmp = dh_cur; dh_cur = dh_prev; dh_prev = tmp;
   }
   return launch_status("gru backward step kernels");
 }
@@ -495,22 +476,16 @@ extern "C" int yt8m_lnlstm_layer_fwd(float* z, const float* Wh, int64_t ldw, con
   hipStream_t s = as_stream(stream);
   const int64_t BH = B * H;
   const bool packed = packed_ok(B, H, 4, gemm_workspace, gemm_workspace_bytes);
-  float* Wp = static_cast<float*>(gemm_workspace);
+  float* Wp = packed ? static_cast<float*>(gemm_workspace) : nullptr;
   if (packed) {
     ProfScope prof(F_LSTM, s);
     int rc = cell_pack(Wh, ldw, Wp, nullptr, H, 4, s);
     if (rc != YT8M_OK) return rc;
   }
+  const StepProduct rec = {Wh, ldw, Wp, nullptr, 4, B, H, gemm_workspace, gemm_workspace_bytes, stream};
   for (int64_t t = 0; t < F; ++t) {
     float* zt = z + t * B * 4 * H;
-    int rc;
-    if (packed) {
-      ProfScope prof(F_LSTM, s);
-      rc = cell_step_add4(zt, Wp, hs + t * BH, B, H, s);
-    } else {
-      yt8m_gemm_problem pr = {B, 4 * H, H, hs + t * BH, H, Wh, ldw, zt, 4 * H, nullptr, 1.0f};
-      rc = yt8m_gemm_f32_grouped(0, 0, 1, &pr, gemm_workspace, gemm_workspace_bytes, stream);
-    }
+    int rc = rec.add_hW(hs + t * BH, zt);
     if (rc != YT8M_OK) return rc;
     ProfScope prof(F_LSTM, s);
     auto kfn = H <= 512 ? lnlstm_fwd_kernel<2> : H <= 1024 ? lnlstm_fwd_kernel<4> : lnlstm_fwd_kernel<LN_PT>;
@@ -535,42 +510,29 @@ extern "C" int yt8m_lnlstm_layer_bwd(const float* z, const float* Wh, int64_t ld
   YT8M_REQUIRE(ldw >= 4 * H, YT8M_E_SHAPE, "ldw < 4H");
   hipStream_t s = as_stream(stream);
   const int64_t BH = B * H;
-  float* dh_cur = work;
-  float* dc_cur = work + BH;
-  float* dh_prev = work + 2 * BH;
-  float* dc_prev = work + 3 * BH;
-  if (dh_final) YT8M_HIP_CHECK(hipMemcpyAsync(dh_cur, dh_final, BH * sizeof(float), hipMemcpyDeviceToDevice, s));
-  else YT8M_HIP_CHECK(hipMemsetAsync(dh_cur, 0, BH * sizeof(float), s));
-  if (dc_final) YT8M_HIP_CHECK(hipMemcpyAsync(dc_cur, dc_final, BH * sizeof(float), hipMemcpyDeviceToDevice, s));
-  else YT8M_HIP_CHECK(hipMemsetAsync(dc_cur, 0, BH * sizeof(float), s));
+  StateGrads g(work, 0, BH);
+  YT8M_HIP_CHECK(seed_state(g.dh_cur, dh_final, BH, s));
+  YT8M_HIP_CHECK(seed_state(g.dc_cur, dc_final, BH, s));
   const bool packed = packed_ok(B, H, 4, gemm_workspace, gemm_workspace_bytes);
-  float* Wq = static_cast<float*>(gemm_workspace);
+  float* Wq = packed ? static_cast<float*>(gemm_workspace) : nullptr;
   if (packed) {
     ProfScope prof(F_LSTM, s);
     int rc = cell_pack(Wh, ldw, nullptr, Wq, H, 4, s);
     if (rc != YT8M_OK) return rc;
   }
-  for (int64_t t = F - 1; t >= 0; --t) {
+  const StepProduct rec = {Wh, ldw, nullptr, Wq, 4, B, H, gemm_workspace, gemm_workspace_bytes, stream};
+  for (int64_t t = F - 1; t >= 0; --t, g.swap()) {
     float* dzt = dz + t * B * 4 * H;
     {
       ProfScope prof(F_LSTM, s);
       auto kfn = H <= 512 ? lnlstm_bwd_kernel<2> : H <= 1024 ? lnlstm_bwd_kernel<4> : lnlstm_bwd_kernel<LN_PT>;
       hipLaunchKernelGGL(kfn, dim3((unsigned)B), dim3(256), 0, s, z + t * B * 4 * H, gamma, beta,
-                         stats + t * B * 10, cs + t * BH, cs + (t + 1) * BH, dh_cur, dc_cur, dout ? dout + t * BH : nullptr, dzt,
-                         dyb + t * B * 5 * H, dyg + t * B * 5 * H, dc_prev, dh_prev, num_frames, (int)t, B, H, forget_bias,
+                         stats + t * B * 10, cs + t * BH, cs + (t + 1) * BH, g.dh_cur, g.dc_cur, dout ? dout + t * BH : nullptr, dzt,
+                         dyb + t * B * 5 * H, dyg + t * B * 5 * H, g.dc_prev, g.dh_prev, num_frames, (int)t, B, H, forget_bias,
                          keep_prob, seed);
     }
-    int rc;
-    if (packed) {
-      ProfScope prof(F_LSTM, s);
-      rc = cell_step_bwd(dzt, Wq, dh_prev, B, H, 4, s);
-    } else {
-      yt8m_gemm_problem pr = {B, H, 4 * H, dzt, 4 * H, Wh, ldw, dh_prev, H, nullptr, 1.0f};
-      rc = yt8m_gemm_f32_grouped(0, 1, 1, &pr, gemm_workspace, gemm_workspace_bytes, stream);
-    }
+    int rc = rec.add_dzWt(dzt, g.dh_prev);
     if (rc != YT8M_OK) return rc;
-    float* tmp = dh_cur; dh_cur = dh_prev; dh_prev = tmp;
-    tmp = dc_cur; dc_cur = dc_prev; dc_prev = tmp;
   }
   return launch_status("lnlstm_bwd_kernel");
 }

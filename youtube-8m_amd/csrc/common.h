@@ -72,6 +72,10 @@ int run_chain(const GraphKey& key, hipStream_t s, const std::function<int()>& la
 
 inline hipStream_t as_stream(yt8m_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// gemm_bf16.hip, called from gemm_f32.hip: 256 x 256 tiles for problems large enough to fill the chip with them
+bool gemm_bf16_big_ok(int nprob, const yt8m_gemm_problem* probs);
+int gemm_bf16_big_launch(int nprob, const yt8m_gemm_problem* probs, void* workspace, int64_t workspace_bytes, hipStream_t s);
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute and launch functions run on several host threads (one per
 // stream of the layer pipeline): one flag per (call site, device).  Usage: static DeviceOnce once; once.lds(kernel, bytes);
 struct DeviceOnce {

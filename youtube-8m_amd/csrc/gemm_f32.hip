@@ -811,11 +811,6 @@ extern "C" int yt8m_gemm_f32_grouped(int transA, int transB, int nprob, const yt
   return grouped_launch(transA, transB, 0, nprob, probs, workspace, workspace_bytes, stream);
 }
 
-namespace yt8m {  // gemm_bf16.hip: 256 x 256 tiles for problems large enough to fill the chip with them
-bool gemm_bf16_big_ok(int nprob, const yt8m_gemm_problem* probs);
-int gemm_bf16_big_launch(int nprob, const yt8m_gemm_problem* probs, void* workspace, int64_t workspace_bytes, hipStream_t s);
-}  // namespace yt8m
-
 extern "C" int yt8m_gemm_bf16_nt_grouped(int nprob, const yt8m_gemm_problem* probs, void* workspace, int64_t workspace_bytes,
                                          yt8m_stream_t stream) {
   using namespace yt8m;

@@ -5,7 +5,7 @@
 // h / W_h they pull through the L2s per step, bf16 operands halve that traffic and cut the matrix time 8x.  The cell state,
 // the gates, the hidden state handed to the next layer and every gradient stay fp32; each step additionally emits the bf16 copy
 // of h_t (forward) / dz_{t-1} (backward) that the next step's product reads.
-#include "common.h"
+#include "step_kernels.h"
 
 namespace {
 
@@ -241,12 +241,7 @@ extern "C" int yt8m_lstm_steps_fwd_bf16(float* z, const void* Wp16, float* cs, f
   ProfScope prof(F_LSTM, s);
   const int64_t BH = B * H;
   unsigned short* h16 = static_cast<unsigned short*>(hs16);
-  GraphKey key;
-  memset(&key, 0, sizeof(key));
-  key.kind = 3;
-  key.p[0] = z; key.p[1] = Wp16; key.p[2] = cs; key.p[3] = hs; key.p[4] = out; key.p[5] = num_frames; key.p[6] = hs16;
-  key.v[0] = t0; key.v[1] = T; key.v[2] = B; key.v[3] = H;
-  memcpy(&key.v[4], &forget_bias, sizeof(float));
+  const GraphKey key = graph_key(3, {z, Wp16, cs, hs, out, num_frames, hs16}, {t0, T, B, H}, forget_bias);
   const unsigned grid = (unsigned)(((B + 31) / 32) * (H / 8));
   return run_chain(key, s, [&]() {
     for (int64_t t = t0; t < t0 + T; ++t)
@@ -270,36 +265,28 @@ extern "C" int yt8m_lstm_steps_bwd_bf16(const float* gates, const void* Wq16, co
   const int64_t BH = B * H, Z = B * 4 * H;
   unsigned short* d16 = static_cast<unsigned short*>(dz16);
   const unsigned short* Wq = static_cast<const unsigned short*>(Wq16);
-  GraphKey key;
-  memset(&key, 0, sizeof(key));
-  key.kind = 4;
-  key.p[0] = gates; key.p[1] = Wq16; key.p[2] = cs; key.p[3] = dout; key.p[4] = dz; key.p[5] = work; key.p[6] = num_frames; key.p[7] = dz16;
-  key.v[0] = t0; key.v[1] = T; key.v[2] = B; key.v[3] = H; key.v[4] = phase;
+  const GraphKey key = graph_key(4, {gates, Wq16, cs, dout, dz, work, num_frames, dz16}, {t0, T, B, H, phase});
   const unsigned grid = (unsigned)(((B + 15) / 16) * (H / 16));
   return run_chain(key, s, [&]() {
-    float* dh_cur = work + (phase ? 2 : 0) * BH;
-    float* dc_cur = dh_cur + BH;
-    float* dh_prev = work + (phase ? 0 : 2) * BH;
-    float* dc_prev = dh_prev + BH;
+    StateGrads g(work, phase, BH);
     const int64_t t_hi = t0 + T - 1;
-    int rc = yt8m_lstm_gates_bwd(gates + t_hi * Z, cs + t_hi * BH, cs + (t_hi + 1) * BH, dh_cur, dc_cur, dout ? dout + t_hi * BH : nullptr,
-                                 dz + t_hi * Z, dc_prev, dh_prev, num_frames, (int32_t)t_hi, B, H, stream);
+    int rc = yt8m_lstm_gates_bwd(gates + t_hi * Z, cs + t_hi * BH, cs + (t_hi + 1) * BH, g.dh_cur, g.dc_cur,
+                                 dout ? dout + t_hi * BH : nullptr, dz + t_hi * Z, g.dc_prev, g.dh_prev, num_frames, (int32_t)t_hi, B, H,
+                                 stream);
     if (rc != YT8M_OK) return rc;
     ProfScope prof(F_LSTM, s);
     hipLaunchKernelGGL(cast_rows16_kernel, dim3((unsigned)((Z / 4 + 255) / 256)), dim3(256), 0, s, dz + t_hi * Z, d16 + t_hi * Z, Z);
-    for (int64_t t = t_hi; t >= t0; --t) {
+    for (int64_t t = t_hi; t >= t0; --t, g.swap()) {
       if (t > t0) {
         const int64_t t1 = t - 1;
-        GateBwd16 gb = {gates + t1 * Z, cs + t1 * BH, cs + (t1 + 1) * BH, dc_prev, dout ? dout + t1 * BH : nullptr,
-                        dz + t1 * Z, d16 + t1 * Z, dc_cur, dh_cur};
-        hipLaunchKernelGGL((lstm_step_bwd16_kernel<true>), dim3(grid), dim3(256), 0, s, d16 + t * Z, Wq, dh_prev, (int)B, (int)H,
+        GateBwd16 gb = {gates + t1 * Z, cs + t1 * BH, cs + (t1 + 1) * BH, g.dc_prev, dout ? dout + t1 * BH : nullptr,
+                        dz + t1 * Z, d16 + t1 * Z, g.dc_cur, g.dh_cur};
+        hipLaunchKernelGGL((lstm_step_bwd16_kernel<true>), dim3(grid), dim3(256), 0, s, d16 + t * Z, Wq, g.dh_prev, (int)B, (int)H,
                            num_frames, (int)t, gb);
       } else {
-        hipLaunchKernelGGL((lstm_step_bwd16_kernel<false>), dim3(grid), dim3(256), 0, s, d16 + t * Z, Wq, dh_prev, (int)B, (int)H,
+        hipLaunchKernelGGL((lstm_step_bwd16_kernel<false>), dim3(grid), dim3(256), 0, s, d16 + t * Z, Wq, g.dh_prev, (int)B, (int)H,
                            num_frames, (int)t, GateBwd16{});
       }
-      float* tmp = dh_cur; dh_cur = dh_prev; dh_prev = tmp;
-      tmp = dc_cur; dc_cur = dc_prev; dc_prev = tmp;
     }
     return launch_status("lstm_step_bwd16_kernel");
   });

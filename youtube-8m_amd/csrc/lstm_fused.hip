@@ -13,7 +13,7 @@
 //     loads for h, as in gemm_f32.hip), partial 32x32 tiles meet in LDS, and thread t finishes (row t/8, unit t%8).
 // Backward: dz_t comes from the pointwise kernel (sequence.hip); dh_{t-1} += dz_t . W_h^T runs on 16x16x4 MFMAs with
 // 16 rows x 16 units per workgroup (512 workgroups) over Wq[unit-group][k][16], K = 4H split over the four waves.
-#include "common.h"
+#include "step_kernels.h"
 
 #ifndef STEP_KDIV
 #define STEP_KDIV 1     // timing experiments only (tools/build_variant.sh -DSTEP_KDIV=n): run 1/n of every K loop
@@ -417,24 +417,12 @@ bool lstm_fused_supported(int64_t B, int64_t H, int64_t workspace_bytes) {
   return H >= 128 && (H % 128) == 0 && B >= 1 && workspace_bytes >= (int64_t)sizeof(float) * H * 4 * H;
 }
 
-int lstm_pack(const float* Wh, int64_t ldw, float* Wp, float* Wq, int64_t H, hipStream_t s) {
-  hipLaunchKernelGGL(lstm_pack_kernel, dim3(2048), dim3(256), 0, s, Wh, ldw, Wp, Wq, (int)H, 4);
-  return launch_status("lstm_pack_kernel");
-}
-
 int lstm_step_fwd(float* z, const float* Wp, const float* c_prev, const float* h_prev, float* c_new, float* h_new, float* out,
                   const int32_t* nf, int t, int64_t B, int64_t H, float fb, hipStream_t s) {
   const unsigned grid = (unsigned)(((B + 31) / 32) * (H / 8));
   FWD_LAUNCH(4, EP_LSTM, 0, dim3(grid), dim3(256), 0, s, z, Wp, h_prev, c_prev, h_prev, c_new,
                      h_new, out, nf, t, (int)B, (int)H, fb, (const float*)nullptr, (float*)nullptr);
   return launch_status("lstm_step_fwd_kernel");
-}
-
-int lstm_step_bwd(const float* dz, const float* Wq, float* dh_prev, int64_t B, int64_t H, hipStream_t s) {
-  const unsigned grid = (unsigned)(((B + 15) / 16) * (H / 16));
-  BWD_LAUNCH(0, 2, dim3(grid), dim3(256), 0, s, dz, Wq, dh_prev, (int)B, (int)H, (int)(4 * H),
-                     (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (const int32_t*)nullptr, 0, GateBwd{});
-  return launch_status("lstm_step_bwd_kernel");
 }
 
 // product of step t (dz_t . Wh^T added to dh_prev) + gate backward of step t1 = t - 1 in one launch
@@ -448,8 +436,8 @@ int lstm_step_bwd_fused(const float* dz_t, const float* Wq, const float* dh_prev
   return launch_status("lstm_step_bwd_kernel<fused gates>");
 }
 
-// ---- the same packed-weight step products for the other cells (cells.hip) ----------------------------------------------
-// G gates: packed sizes are H * G*H floats for both Wp and Wq.  Needs H % 256 == 0 (the K = H backward split).
+// ---- the same packed-weight step products for any cell: G gates, packed sizes are H * G*H floats for both Wp and Wq -----------
+// (BasicLSTM is G = 4 at H % 128 == 0.)  The other cells (cells.hip) need H % 256 == 0 (the K = H backward split).
 bool cell_packed_supported(int64_t B, int64_t H) { return B >= 1 && H >= 256 && (H % 256) == 0; }
 
 int cell_pack(const float* Wh, int64_t ldw, float* Wp, float* Wq, int64_t H, int G, hipStream_t s) {

@@ -1,7 +1,7 @@
 // sequence.hip -- frame-axis kernels: BasicLSTM gate block, attention / assignment softmaxes, per-row top-k.
 // (gfx950, wave64; all HBM/latency-bound pointwise or short-reduction work, wave-shuffle reductions.)
 #include <algorithm>
-#include "common.h"
+#include "step_kernels.h"
 
 namespace {
 
@@ -242,43 +242,6 @@ __global__ __launch_bounds__(256) void perr_rows_kernel(const float* __restrict_
 
 using namespace yt8m;
 
-namespace yt8m {  // lstm_fused.hip
-bool lstm_fused_supported(int64_t B, int64_t H, int64_t workspace_bytes);
-int lstm_pack(const float* Wh, int64_t ldw, float* Wp, float* Wq, int64_t H, hipStream_t s);
-int lstm_step_fwd(float* z, const float* Wp, const float* c_prev, const float* h_prev, float* c_new, float* h_new, float* out,
-                  const int32_t* nf, int t, int64_t B, int64_t H, float fb, hipStream_t s);
-int lstm_step_bwd(const float* dz, const float* Wq, float* dh_prev, int64_t B, int64_t H, hipStream_t s);
-int lstm_step_bwd_fused(const float* dz_t, const float* Wq, const float* dh_prev, const float* gates1, const float* c_prev1,
-                        const float* c_new1, const float* dc_in, const float* dout1, float* dz1, float* dc_out, float* dh_out,
-                        const int32_t* nf, int t, int64_t B, int64_t H, hipStream_t s);
-}  // namespace yt8m
-
-// Packed-weight backward over steps t_hi .. t_lo: ONE launch per step -- the pointwise gate backward runs once for t_hi,
-// afterwards the product kernel of step t carries the gate backward of step t-1 as its epilogue; a plain product closes
-// the range.  (dh, dc) ping-pong between the two halves of `work` exactly as in the two-launch form.
-static int lstm_bwd_range_packed(const float* gates, const float* Wq, const float* cs, const float* dout, float* dz,
-                                 float*& dh_cur, float*& dc_cur, float*& dh_prev, float*& dc_prev, const int32_t* num_frames,
-                                 int64_t t_lo, int64_t t_hi, int64_t B, int64_t H, yt8m_stream_t stream) {
-  hipStream_t s = as_stream(stream);
-  const int64_t BH = B * H, Z = B * 4 * H;
-  int rc = yt8m_lstm_gates_bwd(gates + t_hi * Z, cs + t_hi * BH, cs + (t_hi + 1) * BH, dh_cur, dc_cur,
-                               dout ? dout + t_hi * BH : nullptr, dz + t_hi * Z, dc_prev, dh_prev, num_frames, (int32_t)t_hi, B, H,
-                               stream);
-  ProfScope prof(F_LSTM, s);
-  for (int64_t t = t_hi; t >= t_lo && rc == YT8M_OK; --t) {
-    if (t > t_lo) {
-      const int64_t t1 = t - 1;
-      rc = lstm_step_bwd_fused(dz + t * Z, Wq, dh_prev, gates + t1 * Z, cs + t1 * BH, cs + (t1 + 1) * BH, dc_prev,
-                               dout ? dout + t1 * BH : nullptr, dz + t1 * Z, dc_cur, dh_cur, num_frames, (int)t, B, H, s);
-    } else {
-      rc = lstm_step_bwd(dz + t * Z, Wq, dh_prev, B, H, s);
-    }
-    float* tmp = dh_cur; dh_cur = dh_prev; dh_prev = tmp;
-    tmp = dc_cur; dc_cur = dc_prev; dc_prev = tmp;
-  }
-  return rc;
-}
-
 extern "C" int yt8m_lstm_gates_fwd(float* z, const float* c_prev, const float* h_prev, float* c_new, float* h_new,
                                    float* out, const int32_t* num_frames, int32_t t, int64_t B, int64_t H,
                                    float forget_bias, yt8m_stream_t stream) {
@@ -305,6 +268,63 @@ extern "C" int yt8m_lstm_gates_bwd(const float* gates, const float* c_prev, cons
   return launch_status("lstm_gates_bwd_kernel");
 }
 
+// ---- BasicLSTM time loops: one per direction, over steps [t_lo, t_hi], for the whole-layer and the time-range entry points ----
+static int lstm_fwd_range(float* z, const StepProduct& rec, float* cs, float* hs, float* out, const int32_t* num_frames,
+                          int64_t t_lo, int64_t t_hi, float forget_bias) {
+  const int64_t B = rec.B, H = rec.H, BH = B * H, Z = B * 4 * H;
+  int rc = YT8M_OK;
+  for (int64_t t = t_lo; t <= t_hi && rc == YT8M_OK; ++t) {
+    float* o = out ? out + t * BH : nullptr;
+    if (rec.Wp) {     // one launch per step: recurrent product + gates + copy-through (inside the caller's F_LSTM scope)
+      rc = lstm_step_fwd(z + t * Z, rec.Wp, cs + t * BH, hs + t * BH, cs + (t + 1) * BH, hs + (t + 1) * BH, o, num_frames, (int)t,
+                         B, H, forget_bias, as_stream(rec.stream));
+    } else {
+      rc = rec.add_hW(hs + t * BH, z + t * Z);
+      if (rc == YT8M_OK)
+        rc = yt8m_lstm_gates_fwd(z + t * Z, cs + t * BH, hs + t * BH, cs + (t + 1) * BH, hs + (t + 1) * BH, o, num_frames,
+                                 (int32_t)t, B, H, forget_bias, rec.stream);
+    }
+  }
+  return rc;
+}
+
+// Packed-weight backward over steps t_hi .. t_lo: ONE launch per step -- the pointwise gate backward runs once for t_hi,
+// afterwards the product kernel of step t carries the gate backward of step t-1 as its epilogue; a plain product closes
+// the range.  (dh, dc) ping-pong between the two halves of `work` exactly as in the two-launch form.
+static int lstm_bwd_range_packed(const float* gates, const StepProduct& rec, const float* cs, const float* dout, float* dz,
+                                 StateGrads g, const int32_t* num_frames, int64_t t_lo, int64_t t_hi) {
+  hipStream_t s = as_stream(rec.stream);
+  const int64_t B = rec.B, H = rec.H, BH = B * H, Z = B * 4 * H;
+  int rc = yt8m_lstm_gates_bwd(gates + t_hi * Z, cs + t_hi * BH, cs + (t_hi + 1) * BH, g.dh_cur, g.dc_cur,
+                               dout ? dout + t_hi * BH : nullptr, dz + t_hi * Z, g.dc_prev, g.dh_prev, num_frames, (int32_t)t_hi,
+                               B, H, rec.stream);
+  ProfScope prof(F_LSTM, s);
+  for (int64_t t = t_hi; t >= t_lo && rc == YT8M_OK; --t, g.swap()) {
+    if (t > t_lo) {
+      const int64_t t1 = t - 1;
+      rc = lstm_step_bwd_fused(dz + t * Z, rec.Wq, g.dh_prev, gates + t1 * Z, cs + t1 * BH, cs + (t1 + 1) * BH, g.dc_prev,
+                               dout ? dout + t1 * BH : nullptr, dz + t1 * Z, g.dc_cur, g.dh_cur, num_frames, (int)t, B, H, s);
+    } else {
+      rc = rec.add_dzWt(dz + t * Z, g.dh_prev, true);
+    }
+  }
+  return rc;
+}
+
+// `g`: the running gradients on entry (step t_hi); after the call they sit in the other half of `work` when the range is odd
+static int lstm_bwd_range(const float* gates, const StepProduct& rec, const float* cs, const float* dout, float* dz, StateGrads g,
+                          const int32_t* num_frames, int64_t t_lo, int64_t t_hi) {
+  if (rec.Wq) return lstm_bwd_range_packed(gates, rec, cs, dout, dz, g, num_frames, t_lo, t_hi);
+  const int64_t B = rec.B, H = rec.H, BH = B * H, Z = B * 4 * H;
+  int rc = YT8M_OK;
+  for (int64_t t = t_hi; t >= t_lo && rc == YT8M_OK; --t, g.swap()) {
+    rc = yt8m_lstm_gates_bwd(gates + t * Z, cs + t * BH, cs + (t + 1) * BH, g.dh_cur, g.dc_cur, dout ? dout + t * BH : nullptr,
+                             dz + t * Z, g.dc_prev, g.dh_prev, num_frames, (int32_t)t, B, H, rec.stream);
+    if (rc == YT8M_OK) rc = rec.add_dzWt(dz + t * Z, g.dh_prev);
+  }
+  return rc;
+}
+
 // ---- whole-layer drivers: the time loop lives here (host side of the library), not in Python -------------
 extern "C" int yt8m_lstm_layer_fwd(float* z, const float* Wh, int64_t ldw, float* cs, float* hs, float* out,
                                    const int32_t* num_frames, int64_t F, int64_t B, int64_t H, float forget_bias,
@@ -313,28 +333,15 @@ extern "C" int yt8m_lstm_layer_fwd(float* z, const float* Wh, int64_t ldw, float
   if (F * B * H == 0) return YT8M_OK;
   YT8M_REQUIRE(z && Wh && cs && hs, YT8M_E_BADARG, "null operand");
   YT8M_REQUIRE(ldw >= 4 * H, YT8M_E_SHAPE, "ldw < 4H");
-  const int64_t BH = B * H;
-  if (gemm_workspace && lstm_fused_supported(B, H, gemm_workspace_bytes)) {
-    // fused path: one launch per step (recurrent product + gates + copy-through), W_h re-packed once per call
-    ProfScope prof(F_LSTM, as_stream(stream));
-    float* Wp = static_cast<float*>(gemm_workspace);
-    int rc = lstm_pack(Wh, ldw, Wp, nullptr, H, as_stream(stream));
-    for (int64_t t = 0; t < F && rc == YT8M_OK; ++t)
-      rc = lstm_step_fwd(z + t * B * 4 * H, Wp, cs + t * BH, hs + t * BH, cs + (t + 1) * BH, hs + (t + 1) * BH,
-                         out ? out + t * BH : nullptr, num_frames, (int)t, B, H, forget_bias, as_stream(stream));
-    return rc;
-  }
-  for (int64_t t = 0; t < F; ++t) {
-    float* zt = z + t * B * 4 * H;
-    // z_t += h_{t-1} . Wh        [B,H] x [H,4H]
-    yt8m_gemm_problem pr = {B, 4 * H, H, hs + t * BH, H, Wh, ldw, zt, 4 * H, nullptr, 1.0f};
-    int rc = yt8m_gemm_f32_grouped(0, 0, 1, &pr, gemm_workspace, gemm_workspace_bytes, stream);
-    if (rc != YT8M_OK) return rc;
-    rc = yt8m_lstm_gates_fwd(zt, cs + t * BH, hs + t * BH, cs + (t + 1) * BH, hs + (t + 1) * BH,
-                             out ? out + t * BH : nullptr, num_frames, (int32_t)t, B, H, forget_bias, stream);
-    if (rc != YT8M_OK) return rc;
-  }
-  return YT8M_OK;
+  StepProduct rec = {Wh, ldw, nullptr, nullptr, 4, B, H, gemm_workspace, gemm_workspace_bytes, stream};
+  if (!(gemm_workspace && lstm_fused_supported(B, H, gemm_workspace_bytes)))
+    return lstm_fwd_range(z, rec, cs, hs, out, num_frames, 0, F - 1, forget_bias);
+  // fused path: W_h re-packed once per call into the caller's workspace
+  ProfScope prof(F_LSTM, as_stream(stream));
+  float* Wp = static_cast<float*>(gemm_workspace);
+  rec.Wp = Wp;
+  const int rc = cell_pack(Wh, ldw, Wp, nullptr, H, 4, as_stream(stream));
+  return rc != YT8M_OK ? rc : lstm_fwd_range(z, rec, cs, hs, out, num_frames, 0, F - 1, forget_bias);
 }
 
 extern "C" int yt8m_lstm_layer_bwd(const float* gates, const float* Wh, int64_t ldw, const float* cs, const float* dout,
@@ -346,44 +353,23 @@ extern "C" int yt8m_lstm_layer_bwd(const float* gates, const float* Wh, int64_t 
   YT8M_REQUIRE(gates && Wh && cs && dz && work, YT8M_E_BADARG, "null operand");
   YT8M_REQUIRE(ldw >= 4 * H, YT8M_E_SHAPE, "ldw < 4H");
   hipStream_t s = as_stream(stream);
-  const int64_t BH = B * H;
-  float* dh_cur = work;
-  float* dc_cur = work + BH;
-  float* dh_prev = work + 2 * BH;
-  float* dc_prev = work + 3 * BH;
-  if (dh_final) YT8M_HIP_CHECK(hipMemcpyAsync(dh_cur, dh_final, BH * sizeof(float), hipMemcpyDeviceToDevice, s));
-  else YT8M_HIP_CHECK(hipMemsetAsync(dh_cur, 0, BH * sizeof(float), s));
-  if (dc_final) YT8M_HIP_CHECK(hipMemcpyAsync(dc_cur, dc_final, BH * sizeof(float), hipMemcpyDeviceToDevice, s));
-  else YT8M_HIP_CHECK(hipMemsetAsync(dc_cur, 0, BH * sizeof(float), s));
-  const bool fused = gemm_workspace && lstm_fused_supported(B, H, gemm_workspace_bytes);
-  float* Wq = static_cast<float*>(gemm_workspace);
-  if (fused) {
-    int rc = lstm_pack(Wh, ldw, nullptr, Wq, H, s);
+  const StateGrads g(work, 0, B * H);
+  YT8M_HIP_CHECK(seed_state(g.dh_cur, dh_final, B * H, s));
+  YT8M_HIP_CHECK(seed_state(g.dc_cur, dc_final, B * H, s));
+  StepProduct rec = {Wh, ldw, nullptr, nullptr, 4, B, H, gemm_workspace, gemm_workspace_bytes, stream};
+  if (gemm_workspace && lstm_fused_supported(B, H, gemm_workspace_bytes)) {
+    float* Wq = static_cast<float*>(gemm_workspace);
+    rec.Wq = Wq;
+    const int rc = cell_pack(Wh, ldw, nullptr, Wq, H, 4, s);
     if (rc != YT8M_OK) return rc;
-    return lstm_bwd_range_packed(gates, Wq, cs, dout, dz, dh_cur, dc_cur, dh_prev, dc_prev, num_frames, 0, F - 1, B, H, stream);
   }
-  for (int64_t t = F - 1; t >= 0; --t) {
-    float* dzt = dz + t * B * 4 * H;
-    int rc = yt8m_lstm_gates_bwd(gates + t * B * 4 * H, cs + t * BH, cs + (t + 1) * BH, dh_cur, dc_cur,
-                                 dout ? dout + t * BH : nullptr, dzt, dc_prev, dh_prev, num_frames, (int32_t)t, B, H, stream);
-    if (rc != YT8M_OK) return rc;
-    // dh_{t-1} += dz_t . Wh^T    [B,4H] x [4H,H]   (Wh stored [H,4H] => transB)
-    if (fused) {
-      rc = lstm_step_bwd(dzt, Wq, dh_prev, B, H, s);
-    } else {
-      yt8m_gemm_problem pr = {B, H, 4 * H, dzt, 4 * H, Wh, ldw, dh_prev, H, nullptr, 1.0f};
-      rc = yt8m_gemm_f32_grouped(0, 1, 1, &pr, gemm_workspace, gemm_workspace_bytes, stream);
-    }
-    if (rc != YT8M_OK) return rc;
-    float* tmp = dh_cur; dh_cur = dh_prev; dh_prev = tmp;
-    tmp = dc_cur; dc_cur = dc_prev; dc_prev = tmp;
-  }
-  return YT8M_OK;
+  return lstm_bwd_range(gates, rec, cs, dout, dz, g, num_frames, 0, F - 1);
 }
 
 // ---- time-range forms: the same step kernels over steps [t0, t0 + T) of a layer, with the packed recurrent weights owned
 // by the caller.  They let the host pipeline the layers of a stack over time chunks on separate streams (layer l+1's
 // input projection and recurrence for chunk c run while layer l is in chunk c+1), seq_ops._LstmStack.
+// Only the packed forms are launch-bound chains worth a hipGraph; the generic ones take host-side split-K decisions.
 extern "C" int64_t yt8m_lstm_packed_floats(int64_t B, int64_t H) {
   return lstm_fused_supported(B, H, (int64_t)sizeof(float) * H * 4 * H) ? H * 4 * H : 0;
 }
@@ -392,7 +378,7 @@ extern "C" int yt8m_lstm_pack(const float* Wh, int64_t ldw, int64_t H, float* Wp
   YT8M_REQUIRE(Wh && H > 0 && ldw >= 4 * H && (Wp || Wq), YT8M_E_BADARG, "bad operand");
   YT8M_REQUIRE(lstm_fused_supported(1, H, (int64_t)sizeof(float) * H * 4 * H), YT8M_E_SHAPE, "H must be a multiple of 128");
   ProfScope prof(F_LSTM, as_stream(stream));
-  return lstm_pack(Wh, ldw, Wp, Wq, H, as_stream(stream));
+  return cell_pack(Wh, ldw, Wp, Wq, H, 4, as_stream(stream));
 }
 
 extern "C" int yt8m_lstm_steps_fwd(float* z, const float* Wh, int64_t ldw, const float* Wp, float* cs, float* hs, float* out,
@@ -402,36 +388,13 @@ extern "C" int yt8m_lstm_steps_fwd(float* z, const float* Wh, int64_t ldw, const
   if (T * B * H == 0) return YT8M_OK;
   YT8M_REQUIRE(z && Wh && cs && hs, YT8M_E_BADARG, "null operand");
   YT8M_REQUIRE(ldw >= 4 * H, YT8M_E_SHAPE, "ldw < 4H");
-  const int64_t BH = B * H;
-  if (Wp) {
-    YT8M_REQUIRE(lstm_fused_supported(B, H, (int64_t)sizeof(float) * H * 4 * H), YT8M_E_SHAPE, "packed path needs H % 128 == 0");
-    ProfScope prof(F_LSTM, as_stream(stream));
-    hipStream_t s = as_stream(stream);
-    // T tiny kernels back to back: launch-bound -> captured once per argument tuple, replayed as one hipGraph afterwards
-    GraphKey key;
-    memset(&key, 0, sizeof(key));
-    key.kind = 1;
-    key.p[0] = z; key.p[1] = Wp; key.p[2] = cs; key.p[3] = hs; key.p[4] = out; key.p[5] = num_frames;
-    key.v[0] = t0; key.v[1] = T; key.v[2] = B; key.v[3] = H;
-    memcpy(&key.v[4], &forget_bias, sizeof(float));
-    return run_chain(key, s, [&]() {
-      int rc = YT8M_OK;
-      for (int64_t t = t0; t < t0 + T && rc == YT8M_OK; ++t)
-        rc = lstm_step_fwd(z + t * B * 4 * H, Wp, cs + t * BH, hs + t * BH, cs + (t + 1) * BH, hs + (t + 1) * BH,
-                           out ? out + t * BH : nullptr, num_frames, (int)t, B, H, forget_bias, s);
-      return rc;
-    });
-  }
-  for (int64_t t = t0; t < t0 + T; ++t) {
-    float* zt = z + t * B * 4 * H;
-    yt8m_gemm_problem pr = {B, 4 * H, H, hs + t * BH, H, Wh, ldw, zt, 4 * H, nullptr, 1.0f};
-    int rc = yt8m_gemm_f32_grouped(0, 0, 1, &pr, gemm_workspace, gemm_workspace_bytes, stream);
-    if (rc != YT8M_OK) return rc;
-    rc = yt8m_lstm_gates_fwd(zt, cs + t * BH, hs + t * BH, cs + (t + 1) * BH, hs + (t + 1) * BH,
-                             out ? out + t * BH : nullptr, num_frames, (int32_t)t, B, H, forget_bias, stream);
-    if (rc != YT8M_OK) return rc;
-  }
-  return YT8M_OK;
+  const StepProduct rec = {Wh, ldw, Wp, nullptr, 4, B, H, gemm_workspace, gemm_workspace_bytes, stream};
+  auto chain = [&]() { return lstm_fwd_range(z, rec, cs, hs, out, num_frames, t0, t0 + T - 1, forget_bias); };
+  if (!Wp) return chain();
+  YT8M_REQUIRE(lstm_fused_supported(B, H, (int64_t)sizeof(float) * H * 4 * H), YT8M_E_SHAPE, "packed path needs H % 128 == 0");
+  ProfScope prof(F_LSTM, as_stream(stream));
+  // T tiny kernels back to back: launch-bound -> captured once per argument tuple, replayed as one hipGraph afterwards
+  return run_chain(graph_key(1, {z, Wp, cs, hs, out, num_frames}, {t0, T, B, H}, forget_bias), as_stream(stream), chain);
 }
 
 // steps t0 + T - 1 down to t0.  work [4,B,H]: the running (dh, dc) live in work[0], work[1] when `phase` is 0 and in
@@ -446,38 +409,10 @@ extern "C" int yt8m_lstm_steps_bwd(const float* gates, const float* Wh, int64_t 
   YT8M_REQUIRE(gates && Wh && cs && dz && work, YT8M_E_BADARG, "null operand");
   YT8M_REQUIRE(ldw >= 4 * H, YT8M_E_SHAPE, "ldw < 4H");
   if (Wq) YT8M_REQUIRE(lstm_fused_supported(B, H, (int64_t)sizeof(float) * H * 4 * H), YT8M_E_SHAPE, "packed path needs H % 128 == 0");
-  hipStream_t s = as_stream(stream);
-  const int64_t BH = B * H;
-  auto chain = [&]() {
-    float* dh_cur = work + (phase ? 2 : 0) * BH;
-    float* dc_cur = dh_cur + BH;
-    float* dh_prev = work + (phase ? 0 : 2) * BH;
-    float* dc_prev = dh_prev + BH;
-    if (Wq) return lstm_bwd_range_packed(gates, Wq, cs, dout, dz, dh_cur, dc_cur, dh_prev, dc_prev, num_frames, t0, t0 + T - 1, B, H, stream);
-    for (int64_t t = t0 + T - 1; t >= t0; --t) {
-      float* dzt = dz + t * B * 4 * H;
-      int rc = yt8m_lstm_gates_bwd(gates + t * B * 4 * H, cs + t * BH, cs + (t + 1) * BH, dh_cur, dc_cur,
-                                   dout ? dout + t * BH : nullptr, dzt, dc_prev, dh_prev, num_frames, (int32_t)t, B, H, stream);
-      if (rc != YT8M_OK) return rc;
-      if (Wq) {
-        rc = lstm_step_bwd(dzt, Wq, dh_prev, B, H, s);
-      } else {
-        yt8m_gemm_problem pr = {B, H, 4 * H, dzt, 4 * H, Wh, ldw, dh_prev, H, nullptr, 1.0f};
-        rc = yt8m_gemm_f32_grouped(0, 1, 1, &pr, gemm_workspace, gemm_workspace_bytes, stream);
-      }
-      if (rc != YT8M_OK) return rc;
-      float* tmp = dh_cur; dh_cur = dh_prev; dh_prev = tmp;
-      tmp = dc_cur; dc_cur = dc_prev; dc_prev = tmp;
-    }
-    return (int)YT8M_OK;
-  };
-  if (!Wq) return chain();                        // generic path: host-side split-K decisions, not captured
-  GraphKey key;
-  memset(&key, 0, sizeof(key));
-  key.kind = 2;
-  key.p[0] = gates; key.p[1] = Wq; key.p[2] = cs; key.p[3] = dout; key.p[4] = dz; key.p[5] = work; key.p[6] = num_frames;
-  key.v[0] = t0; key.v[1] = T; key.v[2] = B; key.v[3] = H; key.v[4] = phase;
-  return run_chain(key, s, chain);
+  const StepProduct rec = {Wh, ldw, nullptr, Wq, 4, B, H, gemm_workspace, gemm_workspace_bytes, stream};
+  auto chain = [&]() { return lstm_bwd_range(gates, rec, cs, dout, dz, StateGrads(work, phase, B * H), num_frames, t0, t0 + T - 1); };
+  if (!Wq) return chain();
+  return run_chain(graph_key(2, {gates, Wq, cs, dout, dz, work, num_frames}, {t0, T, B, H, phase}), as_stream(stream), chain);
 }
 
 extern "C" int yt8m_attn_softmax_fwd(const float* act, const int32_t* num_frames, float* w, int64_t B, int64_t F,

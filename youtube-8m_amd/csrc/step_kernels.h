@@ -1,0 +1,90 @@
+// step_kernels.h -- the per-step recurrence launchers of lstm_fused.hip, declared once for the drivers that sequence them
+// (sequence.hip, cells.hip, lstm_bf16.hip), and the small host pieces every time loop shares.  No launcher opens a ProfScope.
+#pragma once
+#include <algorithm>
+#include <initializer_list>
+#include "common.h"
+
+namespace yt8m {
+
+// ---- lstm_fused.hip: packed-weight step products, one launch per product with the epilogue fused --------------------------
+// G gates of H units (LSTM 4, GRU gate block 2, GRU candidate 1); Wp / Wq hold H * G*H floats each.
+bool lstm_fused_supported(int64_t B, int64_t H, int64_t workspace_bytes);   // BasicLSTM: H % 128 == 0
+bool cell_packed_supported(int64_t B, int64_t H);                           // the other cells: H % 256 == 0
+int cell_pack(const float* Wh, int64_t ldw, float* Wp, float* Wq, int64_t H, int G, hipStream_t s);
+int lstm_step_fwd(float* z, const float* Wp, const float* c_prev, const float* h_prev, float* c_new, float* h_new, float* out,
+                  const int32_t* nf, int t, int64_t B, int64_t H, float fb, hipStream_t s);
+int lstm_step_bwd_fused(const float* dz_t, const float* Wq, const float* dh_prev, const float* gates1, const float* c_prev1,
+                        const float* c_new1, const float* dc_in, const float* dout1, float* dz1, float* dc_out, float* dh_out,
+                        const int32_t* nf, int t, int64_t B, int64_t H, hipStream_t s);
+int cell_step_add4(float* z, const float* Wp, const float* h_prev, int64_t B, int64_t H, hipStream_t s);
+int cell_step_bwd(const float* dz, const float* Wq, float* dh_prev, int64_t B, int64_t H, int G, hipStream_t s);
+int gru_step_gates(float* zg, const float* Wp_g, const float* h_prev, float* rh, int64_t B, int64_t H, hipStream_t s);
+int gru_step_cand(float* zc, const float* Wp_c, const float* rh, const float* zg, const float* h_prev, float* h_new, float* out,
+                  const int32_t* nf, int t, int64_t B, int64_t H, hipStream_t s);
+int gru_step_bwd_cand(const float* dzc, const float* Wq_c, float* dh_prev, const float* zg, const float* h_prev, float* dzg,
+                      const int32_t* nf, int t, int64_t B, int64_t H, hipStream_t s);
+
+// ---- the recurrent product of one step: the packed launcher when packed weights are present, else one grouped fp32 GEMM ----
+// (the GEMM takes host-side split-K decisions and opens its own ProfScope; a packed launch is counted under F_LSTM)
+struct StepProduct {
+  const float* Wh;          // [H, G*H], leading dimension ld
+  int64_t ld;
+  const float* Wp;          // packed forward weights (G = 4 only: cell_step_add4) or null
+  const float* Wq;          // packed backward weights or null
+  int G;
+  int64_t B, H;
+  void* ws;                 // GEMM workspace
+  int64_t ws_bytes;
+  yt8m_stream_t stream;
+
+  // z[B, G*H] += h[B, H] . Wh
+  int add_hW(const float* h, float* z) const {
+    if (Wp) {
+      ProfScope prof(F_LSTM, as_stream(stream));
+      return cell_step_add4(z, Wp, h, B, H, as_stream(stream));
+    }
+    yt8m_gemm_problem pr = {B, G * H, H, h, H, Wh, ld, z, G * H, nullptr, 1.0f};
+    return yt8m_gemm_f32_grouped(0, 0, 1, &pr, ws, ws_bytes, stream);
+  }
+  // dh_prev[B, H] += dz[B, G*H] . Wh^T   (Wh stored [H, G*H] => transB).  in_scope: the caller's F_LSTM scope covers a packed launch
+  int add_dzWt(const float* dz, float* dh_prev, bool in_scope = false) const {
+    if (Wq && in_scope) return cell_step_bwd(dz, Wq, dh_prev, B, H, G, as_stream(stream));
+    if (Wq) {
+      ProfScope prof(F_LSTM, as_stream(stream));
+      return cell_step_bwd(dz, Wq, dh_prev, B, H, G, as_stream(stream));
+    }
+    yt8m_gemm_problem pr = {B, H, G * H, dz, G * H, Wh, ld, dh_prev, H, nullptr, 1.0f};
+    return yt8m_gemm_f32_grouped(0, 1, 1, &pr, ws, ws_bytes, stream);
+  }
+};
+
+// dst[n] = src[n], or zeros when there is no src (the gradients of the final state)
+inline hipError_t seed_state(float* dst, const float* src, int64_t n, hipStream_t s) {
+  return src ? hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s) : hipMemsetAsync(dst, 0, n * sizeof(float), s);
+}
+
+// the running gradients of a backward recurrence in work [4, B, H]: (dh, dc) of the step being processed and of the one before
+// it.  They live in work[0], work[1] / work[2], work[3] when `phase` is 0 and the other way round when it is 1; every step swaps.
+struct StateGrads {
+  float *dh_cur, *dc_cur, *dh_prev, *dc_prev;
+  StateGrads(float* work, int phase, int64_t BH)
+      : dh_cur(work + (phase ? 2 : 0) * BH), dc_cur(dh_cur + BH), dh_prev(work + (phase ? 0 : 2) * BH), dc_prev(dh_prev + BH) {}
+  void swap() {
+    std::swap(dh_cur, dh_prev);
+    std::swap(dc_cur, dc_prev);
+  }
+};
+
+// key of a captured step chain: every pointer and integer the chain depends on (+ the bits of the forward's forget bias)
+inline GraphKey graph_key(int kind, std::initializer_list<const void*> p, std::initializer_list<int64_t> v, float forget_bias = 0.f) {
+  GraphKey key;
+  memset(&key, 0, sizeof(key));
+  key.kind = kind;
+  std::copy(p.begin(), p.end(), key.p);
+  std::copy(v.begin(), v.end(), key.v);
+  memcpy(&key.v[7], &forget_bias, sizeof(float));
+  return key;
+}
+
+}  // namespace yt8m
