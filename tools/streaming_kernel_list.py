@@ -22,8 +22,26 @@ def project_kernels():
     return names
 
 
-def instantiation(name):
+def unmangled(name, ours):
+    """The profiler leaves a name mangled when its demangler does not know a parameter type (_Float16: vlad_pack_kernel).  Such a name
+    still spells the kernel as <length><name> and its literal template arguments as I L<type><value>E ... E: 'k<true>' from
+    '_ZN12_GLOBAL__N_116vlad_pack_kernelILb1EEEv...' (bool and integer arguments, which is all these kernels take)."""
+    for k in sorted(ours, key=len, reverse=True):
+        head, sep, rest = name.partition("%d%s" % (len(k), k))
+        if sep:
+            m = re.match(r"I((?:L[a-z]n?\d+E)+)E", rest)
+            if not m:
+                return k
+            args = [("true" if v != "0" else "false") if t == "b" else v.replace("n", "-")
+                    for t, v in re.findall(r"L([a-z])(n?\d+)E", m.group(1))]
+            return "%s<%s>" % (k, ", ".join(args))
+    return name
+
+
+def instantiation(name, ours=()):
     """'void (anonymous namespace)::k<1, float>(float const*, ...)' -> 'k<1, float>' (the first '(' outside angle brackets ends it)."""
+    if name.startswith("_Z"):
+        return unmangled(name, ours)
     s = re.sub(r"^void\s+", "", name.strip()).replace("(anonymous namespace)::", "")
     depth = 0
     for i, ch in enumerate(s):
@@ -41,7 +59,7 @@ def main(path, stem="streaming"):
     ours = project_kernels()
     calls = {}
     for row in csv.DictReader(open(path)):
-        inst = instantiation(row["Name"])
+        inst = instantiation(row["Name"], ours)
         if re.match(r"\w+", inst).group(0) in ours and "::" not in inst.split("<")[0]:
             calls[inst] = calls.get(inst, 0) + int(row["Calls"])
     with open(os.path.join(ROOT, "profiles", "%s_branches_kernel_stats.csv" % stem), "w") as f:
