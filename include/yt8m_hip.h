@@ -1213,6 +1213,23 @@ int yt8m_bn_relu_pool2_tm_bwd(const float* y, int64_t ldy, int64_t F, int64_t B,
                               int64_t lddp, float* dy, int64_t lddy, float* dgamma, float dgamma_beta, float* dbeta,
                               float dbeta_beta, void* workspace, int64_t workspace_bytes, yt8m_stream_t stream);
 
+/* ---- DeepCnnDeepCombineChainModel: max over all frames + max over frame pairs on TIME-major rows in one pass (csrc/deep_cnn.hip;
+ * W/all_frame_models/deep_cnn_deep_combine_chain_model.py:42-63,93,115) ----------------------------------------------
+ * y [F B rows (t B + b), C] fp32 is a CNN level's output.  Both want F >= 1, 1 <= B < 65536, F B < 2^31, C % 4 == 0, C >= 4, leading
+ * dimensions (in floats) >= C that are multiples of 4, 16-byte aligned operands and non-NULL y, out, idx, dy; anything else returns
+ * YT8M_E_SHAPE / YT8M_E_BADARG with nothing launched.
+ * yt8m_timepool_max_pool2_f32_fwd: ONE pass over y: out [B, C] = max over the frames, idx [B, C] = the FIRST frame that attains it
+ *   (yt8m_timepool_max_f32's contract; out and idx share the row stride ldo) and, unless pooled is NULL, pooled [F / 2, B, C] with
+ *   pooled[j] = max(y[2j], y[2j + 1]) (an odd last frame is not pooled).
+ * yt8m_timepool_max_pool2_f32_bwd: g [B, C] (gradient at out; may be NULL = zeros; g and idx share the row stride ldg) and dp
+ *   [F / 2, B, C] (gradient at pooled; may be NULL = zeros): dy[t] = (t == idx ? g : 0) + (t wins its pair ? dp[t / 2] : 0), the winner
+ *   recomputed from y (frame 2j wins iff y[2j] >= y[2j + 1]: the first frame takes a tie).  ONE pass that writes every element of dy:
+ *   no zero-fill, no atomics. */
+int yt8m_timepool_max_pool2_f32_fwd(const float* y, int64_t ldy, int64_t F, int64_t B, int64_t C, float* out, int32_t* idx, int64_t ldo,
+                                    float* pooled, int64_t ldp, yt8m_stream_t stream);
+int yt8m_timepool_max_pool2_f32_bwd(const float* y, int64_t ldy, int64_t F, int64_t B, int64_t C, const float* g, const int32_t* idx,
+                                    int64_t ldg, const float* dp, int64_t lddp, float* dy, int64_t lddy, yt8m_stream_t stream);
+
 /* ---- per-row top-k for the GAP@20 eval path (W/eval_util.py:123-165 top_k_triplets) -------------
  * p [B,V] -> vals [B,k] (descending), idx [B,k] int32; ties broken towards the LOWER class index. k<=64 */
 int yt8m_topk_rows(const float* p, int64_t B, int64_t V, int k, float* vals, int32_t* idx,

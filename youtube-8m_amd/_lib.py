@@ -333,6 +333,8 @@ SIGNATURES = {
     "yt8m_bn_relu_pool2_tm_fwd": (c_int, [P, c_int64, c_int64, c_int64, c_int64, P, P, P, P, P, c_int64, P, c_int64, P]),
     "yt8m_bn_relu_pool2_tm_bwd": (c_int, [P, c_int64, c_int64, c_int64, c_int64, P, P, P, P, c_int, P, c_int64, P, c_int64, P, c_int64, P,
                                           c_float, P, c_float, P, c_int64, P]),
+    "yt8m_timepool_max_pool2_f32_fwd": (c_int, [P, c_int64, c_int64, c_int64, c_int64, P, P, c_int64, P, c_int64, P]),
+    "yt8m_timepool_max_pool2_f32_bwd": (c_int, [P, c_int64, c_int64, c_int64, c_int64, P, P, c_int64, P, c_int64, P, c_int64, P]),
 }
 
 # The ABI this host binds (include/yt8m_hip.h, yt8m_abi_version): workspace layouts and argument meanings, not just symbols.

@@ -35,6 +35,7 @@ DEFINE_integer("lstm_attentions", 8, "Attention size in lstm_attention_max_pooli
 DEFINE_bool("is_training", False, "used in batch normalization.")
 DEFINE_integer("multiscale_cnn_lstm_layers", 1, "number of layers in multiscale cnn_lstm.")          # W/frame_level_models.py:77
 DEFINE_integer("distillchain_relu_cells", 256, "number of relu cells in distillchain model.")        # W/frame_level_models.py:81
+DEFINE_integer("deep_cnn_base_size", 128, "Base number of cnn filters in deep cnn models.")          # W/frame_level_models.py:65
 # new (Appendix B)
 DEFINE_integer("netvlad_cluster_size", 64, "Number of NetVLAD clusters.")
 DEFINE_integer("netvlad_hidden_size", 1024, "Width of the FC after the VLAD descriptor.")
@@ -438,9 +439,9 @@ class LstmPositionalAttentionMaxPoolingModel(LstmAttentionMaxPoolingModel):
         return [positional_embedding, _mean_frame(model_input, num_frames)[:, None, :].expand(B, F, D)], None
 
 
-def _cnn_filters(D, sub_scope, num_filters, filter_sizes, l2_penalty):
+def _cnn_filters(D, sub_scope, num_filters, filter_sizes, l2_penalty, name="cnn-filter-len%d"):
     g = get_default_graph()
-    return [g.get_variable(sub_scope + "cnn-filter-len%d" % fs, (D * fs, nf), random_normal(0.1), l2=l2_penalty)
+    return [g.get_variable(sub_scope + name % fs, (D * fs, nf), random_normal(0.1), l2=l2_penalty)
             for nf, fs in zip(num_filters, filter_sizes)]
 
 
@@ -510,6 +511,109 @@ class CnnDeepCombineChainModel(models.BaseModel):
 
     def sub_model(self, model_input, vocab_size, **params):
         return moe_stage(model_input, vocab_size, **params)
+
+
+class DeepCnnDeepCombineChainModel(CnnDeepCombineChainModel):
+    """W/all_frame_models/deep_cnn_deep_combine_chain_model.py:10-172: CnnDeepCombineChainModel whose stage k reads a three-level "deep CNN"
+    deepcnn<k> instead of one CNN (c = --deep_cnn_base_size): level 0 the einsum CNN on the frames (filter lengths 1, 2, 3; c, c, 2c
+    filters), levels 1 and 2 (lengths 2, 3; c filters each) on the max over frame pairs (tf.nn.pool MAX, window 2, stride 2, VALID) of
+    the level before, F -> F // 2 -> F // 4 frames; the stage reads l2_normalize([max_t y0 | max_t y1 | max_t y2]) [B, 8c].  Padding
+    frames are masked nowhere, as in the reference.  Unlike its sibling, tf.nn.dropout (--dropout) stands in front of EVERY stage,
+    "-main" included (:119-120, 129-131); noise_level is accepted without effect.
+    Variables in creation order: mean-relu, deepcnn0cnn<i>filter-len<fs>, gates-/experts-prediction-0, relu-0, deepcnn1.., gates-/experts--main.
+    On the device everything is time-major (row t B + b): level 0 as seq_ops.u8_cnn_tm on ONE byte image of the frames shared by every
+    deep CNN of the chain (seq_ops.cnn_tm on float frames), a level's two maxima from ONE pass over its output (seq_ops.max_pool2_tm,
+    csrc/deep_cnn.hip), the last level as seq_ops.cnn_tm_maxpool, whose backward gathers.  CPU tensors take the batch-major composed form."""
+    accepts_quantized_input = True
+
+    LEVEL_FILTERS = ((1, 1, 2), (1, 1), (1, 1))                           # in units of --deep_cnn_base_size
+    LEVEL_FILTER_SIZES = ((1, 2, 3), (2, 3), (2, 3))
+
+    def create_model(self, model_input, vocab_size, num_frames, num_mixtures=None, dropout=False, keep_prob=None, noise_level=None,
+                     l2_penalty=1e-8, sub_scope="", original_input=None, **unused_params):
+        relu_cells, cnn_size = FLAGS.deep_chain_relu_cells, FLAGS.deep_cnn_base_size
+        if model_input.shape[1] >> (len(self.LEVEL_FILTERS) - 1) == 0:
+            raise ValueError("DeepCnnDeepCombineChainModel halves the frames twice: %d frames would leave a level without frames"
+                             % model_input.shape[1])
+        model_input, frames, mean_input = self._frames_and_mean(model_input, num_frames)
+        links = [relu_link(mean_input, relu_cells, sub_scope + "mean-relu", l2_penalty, composed_link("relu"))]
+        frozen = 0 if mean_input.requires_grad else model_input.shape[2]      # the mean frame in front of a later stage's input is data
+
+        def stage_input(k, links):                                  # deepcnn<k>'s variables are made here: after relu-<k - 1>
+            cnn_output = self._deep_cnn(model_input, frames, sub_scope + "deepcnn%d" % k, cnn_size, l2_penalty)
+            return torch.cat([mean_input, cnn_output] + links, dim=1) if k else cnn_output
+
+        def stage(x, vocab_size, **params):                         # the dropout reaches "-main" too: not prediction_chain's support_kwargs
+            return self.sub_model(x, vocab_size, dropout=dropout, keep_prob=keep_prob, noise_level=noise_level, **params)
+
+        return prediction_chain(stage, stage_input, composed_link("relu"), links, vocab_size, l2_penalty, sub_scope,
+                                frozen_cols=lambda k: frozen if k else 0)
+
+    def _deep_cnn(self, model_input, frames, scope, cnn_size, l2_penalty):
+        """l2_normalize([reduce_max over the frames of every level's output]) [B, 8 cnn_size] of the deep CNN under `scope`; frames: the
+        byte image of the reader's bytes (seq_ops.U8FrameImages) or None for float frames."""
+        B, F, D = model_input.shape
+        levels, d = [], D
+        for i, (mult, sizes) in enumerate(zip(self.LEVEL_FILTERS, self.LEVEL_FILTER_SIZES)):
+            levels.append(_cnn_filters(d, scope + "cnn%d" % i, [m * cnn_size for m in mult], sizes, l2_penalty, name="filter-len%d"))
+            d = sum(mult) * cnn_size
+        maxima = []
+        if frames is not None or model_input.is_cuda:               # time-major rows t B + b throughout
+            y = seq_ops.u8_cnn_tm(frames, levels[0]) if frames is not None else \
+                seq_ops.cnn_tm(model_input.transpose(0, 1).reshape(F * B, D), B, levels[0])            # (layout glue)
+            for fvars in levels[1:-1]:
+                m, p = seq_ops.max_pool2_tm(y, F, B)
+                maxima.append(m)
+                F = F // 2
+                y = seq_ops.cnn_tm(p.view(F * B, p.shape[2]), B, fvars)
+            m, p = seq_ops.max_pool2_tm(y, F, B)
+            maxima.append(m)
+            F, x = F // 2, p.view((F // 2) * B, p.shape[2])
+            if seq_ops.cnn_tm_maxpool_supported(x.shape[1], [levels[-1]]):                            # one frame per (video, column): gathers
+                maxima.extend(seq_ops.cnn_tm_maxpool(x, B, [levels[-1]]))
+            else:
+                maxima.append(seq_ops.max_pool2_tm(seq_ops.cnn_tm(x, B, levels[-1]), F, B, want_pool=False)[0])
+        else:                                                       # batch-major, composed, as the reference
+            x = model_input
+            for i, fvars in enumerate(levels):
+                y = _einsum_cnn(x, fvars)
+                maxima.append(y.amax(dim=1))
+                if i + 1 < len(levels):
+                    x = y[:, :(F // 2) * 2].reshape(B, F // 2, 2, y.shape[2]).amax(dim=2)
+                    F = F // 2
+        return ops.l2_normalize(torch.cat(maxima, dim=1))
+
+
+class CnnLstmMemoryModel(models.BaseModel):
+    """W/all_frame_models/cnn_lstm_memory_model.py:13-86: the einsum CNN (filter lengths 1, 2, 3 with 1024 filters each, fixed) on the
+    frames, every frame's 3072 outputs l2-normalised, MultiRNNCell of --lstm_layers BasicLSTMCell(--lstm_cells) under dynamic_rnn; the
+    head reads the concatenated c states.  Variables: cnn-filter-len{1,2,3}, RNN/multi_rnn_cell/cell_<l>/basic_lstm_cell/{weights,biases}.
+    The CNN output rows num_frames and num_frames + 1 are non-zero (their windows reach live frames); dynamic_rnn never reads them and
+    their gradient is zero.  On the device the CNN's output stays time-major (seq_ops.u8_cnn_tm on the reader's bytes, seq_ops.cnn_tm on
+    floats) and IS, normalised, the native stack's float input [F,B,3072], which hands back the gradient to it."""
+    accepts_quantized_input = True
+
+    NUM_FILTERS = (1024, 1024, 1024)
+    FILTER_SIZES = (1, 2, 3)
+
+    def create_model(self, model_input, vocab_size, num_frames, **unused_params):
+        lstm_size = int(FLAGS.lstm_cells)
+        number_of_layers = FLAGS.lstm_layers
+        B, F, D = model_input.shape
+        width = sum(self.NUM_FILTERS)
+        x, u8 = _bytes_or_floats(model_input, num_frames, seq_ops.u8_cnn_supported)
+        fvars = _cnn_filters(D, "", self.NUM_FILTERS, self.FILTER_SIZES, 1e-8)
+        if u8 or x.is_cuda:
+            y = seq_ops.u8_cnn_tm(seq_ops.U8FrameImages(x, num_frames), fvars) if u8 else \
+                seq_ops.cnn_tm(x.transpose(0, 1).reshape(F * B, D), B, fvars)                          # (layout glue)
+            x_tm = ops.l2_normalize(y).view(F, B, width)
+        else:
+            x_tm = ops.l2_normalize(_einsum_cnn(x, fvars).reshape(B * F, width)).view(B, F, width).transpose(0, 1).contiguous()
+        with get_default_graph().variable_scope("RNN"):
+            wb = _lstm_cells(width, lstm_size, number_of_layers)
+        _, finals = _native_stack(x_tm, num_frames.to(torch.int32), wb)
+        final_state = torch.cat([c for c, _ in finals], dim=1)
+        return _classify(final_state, model_input, vocab_size, **unused_params)
 
 
 def _pooled_cnn_chain(lstm_output_tm, cnns):

@@ -2158,3 +2158,112 @@ def bn_relu_pool2_tm(y, gamma, beta, moving_mean, moving_variance, is_training, 
     a, p = _BnReluPool2TM.apply(y, _token(gamma._graph), gamma, beta, moving_mean, moving_variance, bool(is_training), float(eps),
                                 float(decay), int(F), int(B), bool(want_pool))
     return a, (p if want_pool else None)
+
+
+# ---- DeepCnnDeepCombineChainModel: max over all frames (classifier) + max over frame pairs (next level) of a CNN level's output --------
+# Which form max_pool2_tm takes on the device, read at call time: the one-pass kernels of csrc/deep_cnn.hip, or the composed form
+# (yt8m_timepool_max_f32 + a pair maximum from torch ops).  The default follows DESIGN_LOG.md section 23's rule on tools/deepcnn_step.py's
+# op leg (section 28 has the rows).
+DEEP_CNN_FUSED_DEFAULT = "1"
+
+
+def deep_cnn_fused():
+    return os.environ.get("YT8M_DEEP_CNN_FUSED", DEEP_CNN_FUSED_DEFAULT) != "0"
+
+
+def max_pool2_tm_supported(y, C):
+    """The one-pass kernels (csrc/deep_cnn.hip): a device tensor and C % 4 == 0 (16-byte column accesses)."""
+    return bool(y.is_cuda and C % 4 == 0 and C >= 4)
+
+
+def _max_pool2_kernel_ok(y, F, B, C):
+    return max_pool2_tm_supported(y, C) and y.dtype == torch.float32 and 1 <= B < 65536 and F >= 1 and F * B < (1 << 31) - 64
+
+
+class _MaxPool2TM(torch.autograd.Function):
+    """tf.reduce_max over all frames and tf.nn.pool(MAX, window 2, stride 2, VALID) of
+    W/all_frame_models/deep_cnn_deep_combine_chain_model.py:59-61,93 in ONE pass over a CNN level's output y [F B, C] (time-major), and
+    ONE backward pass that writes dy (csrc/deep_cnn.hip).  Keeps y (the CNN's output, alive anyway) and the frames of the maxima."""
+
+    @staticmethod
+    def forward(ctx, y, F, B, want_pool):
+        y = _f32c(y)
+        _dev(y)
+        M, C = y.shape
+        assert M == F * B
+        dev = y.device
+        m = torch.empty((B, C), dtype=torch.float32, device=dev)
+        idx = torch.empty((B, C), dtype=torch.int32, device=dev)
+        p = torch.empty((F // 2, B, C), dtype=torch.float32, device=dev) if want_pool else None
+        _lib.check(_lib.lib().yt8m_timepool_max_pool2_f32_fwd(_p(y), C, F, B, C, _p(m), _p(idx), C,
+                                                              _p(p) if (p is not None and p.numel()) else None, C, _stream()))
+        ctx.save_for_backward(y, idx)
+        ctx.dims = (F, B)
+        if p is None:
+            p = y.new_empty((0,))
+            ctx.mark_non_differentiable(p)
+        ctx.mark_non_differentiable(idx)
+        return m, p, idx
+
+    @staticmethod
+    def backward(ctx, g, dp, _):
+        y, idx = ctx.saved_tensors
+        F, B = ctx.dims
+        C = y.shape[1]
+        g = _f32c(g) if g is not None else None
+        dp = _f32c(dp) if (dp is not None and dp.numel()) else None
+        dy = torch.empty_like(y)
+        _lib.check(_lib.lib().yt8m_timepool_max_pool2_f32_bwd(_p(y), C, F, B, C, _p(g), _p(idx), C, _p(dp), C, _p(dy), C, _stream()))
+        return dy, None, None, None
+
+
+class _TimepoolMaxTM(torch.autograd.Function):
+    """The composed form's maximum over all frames on the device: yt8m_timepool_max_f32 with the frames kept; backward a zero-fill and a
+    scatter of g to them."""
+
+    @staticmethod
+    def forward(ctx, y, F, B):
+        y = _f32c(y)
+        _dev(y)
+        C = y.shape[1]
+        m = torch.empty((B, C), dtype=torch.float32, device=y.device)
+        idx = torch.empty((B, C), dtype=torch.int32, device=y.device)
+        _lib.check(_lib.lib().yt8m_timepool_max_f32(_p(y), F, B, C, C, _p(m), _p(idx), C, _stream()))
+        ctx.save_for_backward(idx)
+        ctx.dims = (F, B, C)
+        ctx.mark_non_differentiable(idx)
+        return m, idx
+
+    @staticmethod
+    def backward(ctx, g, _):
+        (idx,) = ctx.saved_tensors
+        F, B, C = ctx.dims
+        dy = torch.zeros((F, B, C), dtype=torch.float32, device=g.device)
+        dy.scatter_(0, idx.to(torch.int64)[None], _f32c(g)[None])
+        return dy.view(F * B, C), None, None
+
+
+def _pair_max(y3):
+    """max(y[2j], y[2j + 1]) [F // 2, B, C] from torch ops, the first frame taking a tie in the gradient (the kernel's rule; amax would
+    split it)."""
+    F = y3.shape[0]
+    pairs = y3[:2 * (F // 2)].reshape(F // 2, 2, y3.shape[1], y3.shape[2])
+    y0, y1 = pairs[:, 0], pairs[:, 1]
+    return torch.where(y0 >= y1, y0, y1)
+
+
+def max_pool2_tm(y, F, B, want_pool=True):
+    """y [F B, C] time-major (row t B + b) -> (m [B, C] = max over the F frames, p [F // 2, B, C] = max over the frame pairs (2j, 2j + 1),
+    an odd last frame dropped; None unless want_pool).  On the device the one-pass kernels of csrc/deep_cnn.hip unless
+    YT8M_DEEP_CNN_FUSED=0 or they refuse the shape; then, and for every CPU tensor, the composed form: yt8m_timepool_max_f32 (amax off the
+    device) plus a pair maximum from torch ops."""
+    M, C = y.shape
+    assert M == F * B and F >= 1, "max_pool2_tm: y must be [F B, C]"
+    if deep_cnn_fused() and _max_pool2_kernel_ok(y, F, B, C):
+        m, p, _ = _MaxPool2TM.apply(y, int(F), int(B), bool(want_pool))
+        return m, (p if want_pool else None)
+    if max_pool2_tm_supported(y, C) and y.dtype == torch.float32:       # (yt8m_timepool_max_f32 wants C % 4 == 0 too)
+        m, _ = _TimepoolMaxTM.apply(y, int(F), int(B))
+    else:
+        m = y.view(F, B, C).amax(dim=0)
+    return m, (_pair_max(y.view(F, B, C)) if want_pool else None)
