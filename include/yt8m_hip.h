@@ -788,6 +788,15 @@ int yt8m_lstm_persist_fwd_on_bf16_pipe(int64_t B, int64_t H);
 int yt8m_lstm_persist_set_cus(int fwd_cus, int bwd_cus);
 /* The current choice of yt8m_lstm_persist_set_cus (-1: environment / default), so that a caller that caps for a while can restore it. */
 int yt8m_lstm_persist_get_cus(int* fwd_cus, int* bwd_cus);
+/* Tape prefetch of the f16 form of the backward recurrence (yt8m_lstm_persist_bwd_h2 / _ex with an absmax word) for the following launches
+ * OF THE CALLING THREAD: 0 = process default (on; YT8M_PERSIST_TAPE_PREFETCH=0 turns it off), 1 = on, 2 = off.  On, the epilogue touches
+ * the saved activations of the next step with throw-away scalar loads so that its vector reads find them in L2.  Bit-identical results
+ * either way (tests/test_gpu_tape_prefetch.py).  Per thread means the thread that LAUNCHES: a backward pass that PyTorch's autograd
+ * drives launches from autograd's device worker thread, which a setter called around loss.backward() does not reach (set it inside the
+ * backward, run under torch.autograd.set_multithreading_enabled(False), or use the environment variable).
+ * yt8m_lstm_persist_tape_prefetch_launches: how many f16-form backward launches of the process ran with / without it so far. */
+int yt8m_lstm_persist_set_tape_prefetch(int mode);
+int yt8m_lstm_persist_tape_prefetch_launches(int64_t* with_prefetch, int64_t* without_prefetch);
 /* CUs the library leaves out of its "do these persistent launches fit the chip together" arithmetic: a data-parallel host reserves
  * room for the RCCL kernels of the gradient all-reduce that run beside the backward pass (launches that no longer fit side by side
  * are chained instead of spinning on a partly resident grid).  Env default: YT8M_PERSIST_RESERVED_CUS, else 0. */

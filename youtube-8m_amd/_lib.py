@@ -208,6 +208,8 @@ SIGNATURES = {
     "yt8m_lstm_persist_fwd_on_bf16_pipe": (c_int, [c_int64, c_int64]),
     "yt8m_lstm_persist_set_cus": (c_int, [c_int, c_int]),
     "yt8m_lstm_persist_get_cus": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "yt8m_lstm_persist_set_tape_prefetch": (c_int, [c_int]),
+    "yt8m_lstm_persist_tape_prefetch_launches": (c_int, [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     "yt8m_lstm_persist_status": (c_int, [P, P]),
     "yt8m_lstm_persist_reserve_cus": (c_int, [c_int, ctypes.POINTER(c_int)]),
     "yt8m_lstm_persist_debug_fault": (c_int, [P, P]),

@@ -916,6 +916,25 @@ struct PersistBwdArgs {
 
 constexpr int NSLOT_B = 3;
 
+// Tape prefetch (TPF form of the H2 backward recurrence): one throw-away dword read per saved-activation segment through the SCALAR data
+// cache, PF_DIST steps before the epilogue's vector loads of it.  A scalar read does not pass through the CU's vector L1 and its ~64
+// request window: the HBM round trip is paid by a request that holds no window slot, and the later vector read is served from the XCD's
+// L2.  Loads only; the values are discarded (kept alive up to the end of their batch with an empty asm, which is also where the compiler
+// puts the batch's lgkmcnt wait).  Measured stand-alone at B = 128, H = 1024: 12.5-12.8 against 14.4-14.7 us per step; two steps ahead
+// 12.8-12.9 (DESIGN_LOG 29).  The forward recurrence has no such form: it is one serial chain, every LDS read of its epilogue shares
+// lgkmcnt with the scalar loads, and both placements tried there ran 19-35 % slower.
+constexpr int PF_DIST = 1;       // steps ahead of the vector loads
+constexpr int PF_ROWS = 4;       // tile rows per batch of scalar loads (6 loads per row: 4 gate blocks, cs, dout)
+typedef const __attribute__((address_space(4))) unsigned* tape_kptr;
+// (base: a wave-uniform pointer; off: a byte offset -- a compile-time constant below 2^20 at every call site, so that it lands in the
+// instruction's immediate and a whole tile's touches share three base register pairs)
+__device__ __forceinline__ unsigned tape_touch(const float* base, unsigned off) {
+  const unsigned long long u = reinterpret_cast<unsigned long long>(base);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+  return *reinterpret_cast<tape_kptr>((((unsigned long long)hi << 32) | lo) + off);
+}
+__device__ __forceinline__ void tape_discard(unsigned v) { asm volatile("" ::"s"(v)); }
+
 // round-to-nearest-even bf16 bits / exact three-term split: the arithmetic of csrc/gemm_x3.hip's split pass, bit for bit
 __device__ __forceinline__ unsigned p_bf16_rn_bits(float x) {
   const unsigned u = __float_as_uint(x);
@@ -959,8 +978,10 @@ __device__ __forceinline__ void p_split3(float x, unsigned& h1, unsigned& h2, un
 //   K slot (block 2 p + uh, k-group kg, j) of the exchange = producer p's value (unit 8 uh + 2 kg + j / 4, gate j % 4): a lane of the
 //   epilogue (one unit x four gates per row) and its neighbour fill one 16-byte A fragment piece -- one DPP move per dword instead of the
 //   one-plane form's three-step gather.
-template <int NQB, bool PF, bool SH, bool ROT, bool IMG = false, bool BF = false, bool H2 = false>
+// TPF (H2 form): the rotated epilogue warms the saved-activation lines of step t - PF_DIST in L2 through the scalar cache (tape_touch).
+template <int NQB, bool PF, bool SH, bool ROT, bool IMG = false, bool BF = false, bool H2 = false, bool TPF = false>
 __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a) {
+  static_assert(!TPF || H2, "the tape prefetch belongs to the two-half-plane form");
   static_assert(!IMG || ROT, "the operand images are written by the rotated epilogue");
   static_assert(!BF || (PF && SH && ROT && !IMG && (NQB % 4) == 0), "the bf16-operand form: prefetching, one image per step, rotated epilogue");
   static_assert(!H2 || (PF && SH && ROT && !IMG && !BF && (NQB % 8) == 0), "the two-half-plane form: prefetching, one image per step, rotated epilogue");
@@ -1619,6 +1640,42 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
         }
       }
     };
+    // TPF: what gate_load(tp, rows of tile T) will read, one scalar dword per 64-byte segment of this workgroup's 16 units: 16 rows x (4
+    // gate blocks, cs, dout when there is one) = 96 loads per item in batches of PF_ROWS rows.  (Every workgroup touches its OWN half of
+    // the 128-byte line: with the rows divided between the two neighbours that share the lines the gain was gone.)  Only steps of this
+    // launch (time runs downwards: tp >= t0; the caller guarantees tp < t0 + T) and rows < B: pad rows of the last tile get none.
+    auto tape_prefetch = [&](int tp, int T) {
+      if constexpr (TPF) {
+        if (tp < a.t0) return;
+        const int row0 = T * 16;
+        const int nrows = B - row0 < 16 ? B - row0 : 16;
+        const float* gp = a.gates + ((long long)tp * B + row0) * 4 * H + ub * 16;
+        const float* cp = a.cs + (long long)tp * BH + (long long)row0 * H + ub * 16;
+        const float* dp = a.dout ? a.dout + (long long)tp * BH + (long long)row0 * H + ub * 16 : nullptr;
+        constexpr unsigned HBY = NQB * 32 * 4;            // bytes of H floats: H == 32 NQB (persist_geometry_bwd), so every offset is an immediate
+#pragma unroll
+        for (int rb = 0; rb < 16; rb += PF_ROWS) {
+          if (rb >= nrows) break;
+          unsigned v[PF_ROWS][6];
+#pragma unroll
+          for (int rr = 0; rr < PF_ROWS; ++rr) {
+#pragma unroll
+            for (int j = 0; j < 6; ++j) v[rr][j] = 0;
+            if (rb + rr < nrows) {
+#pragma unroll
+              for (int g4 = 0; g4 < 4; ++g4) v[rr][g4] = tape_touch(gp, (unsigned)(4 * (rb + rr) + g4) * HBY);
+              v[rr][4] = tape_touch(cp, (unsigned)(rb + rr) * HBY);
+              if (dp) v[rr][5] = tape_touch(dp, (unsigned)(rb + rr) * HBY);
+            }
+          }
+#pragma unroll
+          for (int rr = 0; rr < PF_ROWS; ++rr) {
+#pragma unroll
+            for (int j = 0; j < 6; ++j) tape_discard(v[rr][j]);
+          }
+        }
+      }
+    };
     // ---- prologue: gate backward of step t_hi from the caller's running (dh, dc) in half `phase`; publish #1 of this wave's tiles
     for (int it = ew; it < n_it; it += 4) {
       const int T = g + it * RB;
@@ -1670,6 +1727,7 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
           }
           if (!last) q[r] = gate_load(t1, br, it * 16 + 4 * rq + r, carry, car_cn[r]);
         }
+        tape_prefetch(t1 - PF_DIST, T);                   // behind this item's own requests, in the wait for its partial tiles
         lds_wait_ge(&lds_cnt[slot], 8u * (unsigned)(gen + 1), a.ctl);
         STAMP(1);
         float p[4];
@@ -1954,6 +2012,17 @@ int device_cus(int* dev_out) {
   return cus[dev];
 }
 
+// Tape prefetch of the H2 backward recurrence (TPF): YT8M_PERSIST_TAPE_PREFETCH=0 turns it off process-wide;
+// yt8m_lstm_persist_set_tape_prefetch overrides the default for the CALLING THREAD's following launches (0 = default, 1 = on, 2 = off) --
+// launches that autograd drives come from its own worker thread, not from the thread that called backward().
+// g_tpf_launches: H2 backward launches of the process without / with the prefetch (yt8m_lstm_persist_tape_prefetch_launches).
+std::atomic<long long> g_tpf_launches[2] = {{0}, {0}};
+thread_local int g_tape_prefetch_mode = 0;
+bool tape_prefetch_on() {
+  static const bool env_off = getenv("YT8M_PERSIST_TAPE_PREFETCH") != nullptr && atoi(getenv("YT8M_PERSIST_TAPE_PREFETCH")) == 0;
+  return g_tape_prefetch_mode == 1 || (g_tape_prefetch_mode == 0 && !env_off);
+}
+
 struct Geometry { int NQ, NU, RB, NT16, per, pf; };
 
 bool persist_geometry(int64_t B, int64_t H, Geometry* geo) {
@@ -2032,6 +2101,19 @@ extern "C" int yt8m_lstm_persist_reserve_cus(int cus, int* previous) {
   std::lock_guard<std::mutex> lk(g_gate.mu);
   if (previous) *previous = g_reserved_cus;
   g_reserved_cus = cus;
+  return YT8M_OK;
+}
+
+extern "C" int yt8m_lstm_persist_set_tape_prefetch(int mode) {
+  YT8M_REQUIRE(mode >= 0 && mode <= 2, YT8M_E_BADARG, "mode must be 0 (default), 1 (on) or 2 (off)");
+  g_tape_prefetch_mode = mode;
+  return YT8M_OK;
+}
+
+// f16-form backward launches of this process so far, with and without the tape prefetch (either pointer may be null)
+extern "C" int yt8m_lstm_persist_tape_prefetch_launches(int64_t* with_prefetch, int64_t* without_prefetch) {
+  if (with_prefetch) *with_prefetch = g_tpf_launches[1].load();
+  if (without_prefetch) *without_prefetch = g_tpf_launches[0].load();
   return YT8M_OK;
 }
 
@@ -2282,7 +2364,10 @@ int launch_bwd_sh(const PersistBwdArgs& a, unsigned grid, hipStream_t s) {
   }
   if constexpr (SH && (NQB == 16 || NQB == 32)) {
     if (a.h2 && rot) {
-      hipLaunchKernelGGL((lstm_persist_bwd_kernel<NQB, true, true, true, false, false, true>), dim3(grid), dim3(768), 0, s, a);
+      const bool tpf = tape_prefetch_on();
+      ++g_tpf_launches[tpf ? 1 : 0];
+      if (tpf) hipLaunchKernelGGL((lstm_persist_bwd_kernel<NQB, true, true, true, false, false, true, true>), dim3(grid), dim3(768), 0, s, a);
+      else hipLaunchKernelGGL((lstm_persist_bwd_kernel<NQB, true, true, true, false, false, true>), dim3(grid), dim3(768), 0, s, a);
       return yt8m::launch_status("lstm_persist_bwd_kernel");
     }
   }
