@@ -1287,6 +1287,30 @@ int yt8m_tfrecord_write_predictions(const char* path, int64_t n, const char* vid
                                     const uint8_t* labels, const float* predictions, int64_t num_classes,
                                     const char* feature_name);
 
+/* The ensemble stage's combine over stacked predictions (csrc/ensemble.hip; E/all_ensemble_models/ of the reference's
+ * youtube-8m-ensemble).  x is METHOD-MAJOR [M, B, V] -- a [B, V, M] view of strides (V, 1, B V) -- and is data; Wt [J, M, V] are the J
+ * logit tables, v innermost; gate [B, J], or null with J == 1 (gate = 1).
+ *   logit[b,v,k] = sum_j gate[b,j] Wt[j,k,v];  out[b,v] = sum_k softmax_k(logit)[k] t(x[k,b,v]);
+ *   stat [2, B, V]: stat[0,b,v] = max_k logit, stat[1,b,v] = 1 / sum_k exp(logit - max) (apart, so that logits of +-80 lose nothing)
+ *   t: xform 0 the identity, 1 log((1e-5 + x) / (1 + 1e-5 - x)) (nonunit_matrix_regression_model.py:27)
+ * fwd: one pass over x; stat may be null (no backward pass will follow).
+ * bwd: one pass over x with the forward's out and stat: dWt[j,k,v] = sum_b gate[b,j] dl, dgate[b,j] = sum_{v,k} dl Wt[j,k,v],
+ *   dl = dout exp(logit - stat[0]) stat[1] (t - out).  dgate is given exactly when gate is.  Rows are split into at most 8 chunks whose partial
+ *   tables are summed in chunk order; dgate's per-(column tile, method range) partials likewise: no atomics, a second run gives the same
+ *   bits.  workspace: yt8m_ens_combine_bwd_workspace_bytes (-1 for sizes the calls refuse).
+ * moments: mean[b,v] over the M methods and, where var is not null, the unbiased variance (/(M - 1); M < 2 with var: YT8M_E_BADARG).
+ * 16-byte accesses where V % 4 == 0 and every operand is 16-byte aligned, single elements otherwise.  A null operand, a non-positive
+ * size, J outside [1, yt8m_ens_max_gates() = 4], a null gate with J > 1, an xform other than 0 and 1: YT8M_E_BADARG; B > 262140 (moments:
+ * 65535), V > 2^24, M > 2^16: YT8M_E_SHAPE.  Nothing is launched then. */
+int yt8m_ens_max_gates(void);
+int yt8m_ens_combine_fwd(const float* x, const float* Wt, const float* gate, int xform, float* out, float* stat, int64_t B, int64_t V,
+                         int64_t M, int J, yt8m_stream_t stream);
+int64_t yt8m_ens_combine_bwd_workspace_bytes(int64_t B, int64_t V, int64_t M, int J);
+int yt8m_ens_combine_bwd(const float* x, const float* Wt, const float* gate, int xform, const float* out, const float* stat,
+                         const float* dout, float* dWt, float* dgate, void* workspace, int64_t workspace_bytes, int64_t B, int64_t V,
+                         int64_t M, int J, yt8m_stream_t stream);
+int yt8m_ens_moments(const float* x, float* mean, float* var, int64_t B, int64_t V, int64_t M, yt8m_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -337,6 +337,11 @@ SIGNATURES = {
                                           c_float, P, c_float, P, c_int64, P]),
     "yt8m_timepool_max_pool2_f32_fwd": (c_int, [P, c_int64, c_int64, c_int64, c_int64, P, P, c_int64, P, c_int64, P]),
     "yt8m_timepool_max_pool2_f32_bwd": (c_int, [P, c_int64, c_int64, c_int64, c_int64, P, P, c_int64, P, c_int64, P, c_int64, P]),
+    "yt8m_ens_max_gates": (c_int, []),
+    "yt8m_ens_combine_fwd": (c_int, [P, P, P, c_int, P, P, c_int64, c_int64, c_int64, c_int, P]),
+    "yt8m_ens_combine_bwd_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int]),
+    "yt8m_ens_combine_bwd": (c_int, [P, P, P, c_int, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int, P]),
+    "yt8m_ens_moments": (c_int, [P, P, P, c_int64, c_int64, c_int64, P]),
 }
 
 # The ABI this host binds (include/yt8m_hip.h, yt8m_abi_version): workspace layouts and argument meanings, not just symbols.

@@ -1,7 +1,8 @@
 """Thin Python wrappers + autograd plumbing over the C ABI (include/yt8m_hip.h).
 
 torch is used for device memory, streams and the autograd tape only; every FLOP of the hot path is a
-HIP kernel in libyt8m_hip.so.  No op has a CPU / eager fallback: host tensors raise.
+HIP kernel in libyt8m_hip.so.  No op has a CPU / eager fallback: host tensors raise.  (One documented exception: ens_combine /
+ens_moments of the ensemble stage have a composed torch form that inputs outside the kernels' layout take by rule, not by failure.)
 
 Gradient routing: parameters are NOT autograd leaves.  Each op's backward writes dW directly into the
 variable's slice of the gradient arena (GEMM beta = 0 on first write, 1 afterwards) and returns None for
@@ -1329,6 +1330,111 @@ def memory_link(tensors, normalize, eps=1e-12):
         cat = torch.cat(tensors, dim=1)
         return l2_normalize(cat, eps) if normalize else cat
     return _MemoryLink.apply(bool(normalize), eps, *tensors)
+
+
+# 0: ens_combine / ens_moments compose torch ops; anything else (the default): the fused kernels of csrc/ensemble.hip where the input is a
+# method-major device tensor.  Fused is the default because tools/ensemble_step.py's op leg measured its median below the composed form's
+# at every shape in both runs of the leg, 3.6 - 13 x (DESIGN_LOG.md section 30).
+ENSEMBLE_FUSED = os.environ.get("YT8M_ENSEMBLE_FUSED", "1") != "0"
+ENS_XFORM = {None: 0, "logit": 1}
+ENS_LOGIT_EPS = 1e-5                  # E/all_ensemble_models/nonunit_matrix_regression_model.py:27
+
+
+def ens_method_major(x):
+    """x [B, V, M] is a view of a contiguous [M, B, V] buffer (strides (V, 1, B V)): ensemble.EnsembleInput's layout."""
+    return x.dim() == 3 and x.permute(2, 0, 1).is_contiguous()
+
+
+def _ens_fused(x, J=1):
+    return (ENSEMBLE_FUSED and x.is_cuda and x.dtype == torch.float32 and not x.requires_grad and ens_method_major(x)
+            and J <= _lib.lib().yt8m_ens_max_gates())
+
+
+def ens_xform(x, xform=None):
+    if xform not in ENS_XFORM:
+        raise ValueError("ens_combine: xform must be None or 'logit', got %r" % (xform,))
+    return x if xform is None else torch.log((ENS_LOGIT_EPS + x) / (1.0 + ENS_LOGIT_EPS - x))
+
+
+def ens_combine_composed(x, W, gate=None, xform=None):
+    """The reference's formulation in torch ops: logits, their softmax over the methods and the weighted sum."""
+    t = ens_xform(x, xform)
+    if gate is None:
+        return torch.einsum("bvk,vk->bv", t, torch.softmax(W[0], dim=-1))
+    return (torch.softmax(torch.einsum("bj,jvk->bvk", gate, W), dim=-1) * t).sum(dim=-1)
+
+
+class _EnsCombine(torch.autograd.Function):
+    """csrc/ensemble.hip: one pass over the method-major predictions each way.  Saved for backward: x (data), the [J, M, V] re-layout of
+    the tables, gate, out [B, V] and the softmax statistics [2, B, V] -- nothing of size [B, V, M]."""
+
+    @staticmethod
+    def forward(ctx, x, W, gate, xform):
+        B, V, M = x.shape
+        J = W.shape[0]
+        Wt = W.detach().permute(0, 2, 1).contiguous()                    # v innermost: 5.6 MB at J = 4, V = 4716, M = 74
+        g = None if gate is None else _f32c(gate.detach())
+        need = ctx.needs_input_grad[1] or (gate is not None and ctx.needs_input_grad[2])
+        out = torch.empty((B, V), dtype=torch.float32, device=x.device)
+        stat = torch.empty((2, B, V), dtype=torch.float32, device=x.device) if need else None
+        _lib.check(_lib.lib().yt8m_ens_combine_fwd(_p(x), _p(Wt), _p(g), ENS_XFORM[xform], _p(out), _p(stat), B, V, M, J, _stream()))
+        ctx.xform = xform
+        if need:
+            ctx.has_gate = g is not None
+            ctx.save_for_backward(*([x, Wt, out, stat] + ([g] if g is not None else [])))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, Wt, out, stat = ctx.saved_tensors[:4]
+        g = ctx.saved_tensors[4] if ctx.has_gate else None
+        B, V, M = x.shape
+        J = Wt.shape[0]
+        dout = _f32c(dout)
+        dWt = torch.empty_like(Wt)
+        dgate = torch.empty_like(g) if g is not None else None
+        nbytes = _lib.lib().yt8m_ens_combine_bwd_workspace_bytes(B, V, M, J)
+        ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=x.device)
+        _lib.check(_lib.lib().yt8m_ens_combine_bwd(_p(x), _p(Wt), _p(g), ENS_XFORM[ctx.xform], _p(out), _p(stat), _p(dout), _p(dWt), _p(dgate),
+                                                   _p(ws), nbytes, B, V, M, J, _stream()))
+        return None, dWt.permute(0, 2, 1), dgate, None
+
+
+def ens_combine(x, W, gate=None, xform=None):
+    """out [B, V] = sum_k softmax_k(sum_j gate[b, j] W[j, v, k]) t(x[b, v, k]): the combine every plugin of ensemble_level_models.py
+    ends in.  x [B, V, M]: stacked predictions, data.  W [J, V, M]: logit tables; gate [B, J], or None with J = 1 (gate = 1).  xform:
+    None (t = identity) or "logit" (t = log((1e-5 + x) / (1 + 1e-5 - x))).  Gradients reach W and gate.
+    The fused kernels take device tensors in ensemble.EnsembleInput's method-major layout with up to 4 tables unless YT8M_ENSEMBLE_FUSED
+    (read at import) is 0; CPU tensors, contiguous [B, V, M] inputs, an x that requires a gradient and more tables take the composed
+    torch form, which computes the same thing."""
+    if xform not in ENS_XFORM:
+        raise ValueError("ens_combine: xform must be None or 'logit', got %r" % (xform,))
+    if x.dim() != 3 or W.dim() != 3 or tuple(W.shape[1:]) != tuple(x.shape[1:]):
+        raise ValueError("ens_combine: x [B, V, M] and W [J, V, M], got %s and %s" % (tuple(x.shape), tuple(W.shape)))
+    if gate is None and W.shape[0] != 1:
+        raise ValueError("ens_combine: no gate means one table, got %d" % W.shape[0])
+    if gate is not None and tuple(gate.shape) != (x.shape[0], W.shape[0]):
+        raise ValueError("ens_combine: gate must be [%d, %d], got %s" % (x.shape[0], W.shape[0], tuple(gate.shape)))
+    if not _ens_fused(x, W.shape[0]):
+        return ens_combine_composed(x, W, gate, xform)
+    return _EnsCombine.apply(x, W, gate, xform)
+
+
+def ens_moments(x, variance=False):
+    """(mean over the methods [B, V], unbiased variance [B, V] or None) of stacked predictions x [B, V, M]; x is data, no gradient.
+    One kernel pass under the conditions of ens_combine, torch ops otherwise."""
+    M = x.shape[2]
+    if variance and M < 2:
+        raise ValueError("ens_moments: the unbiased variance needs at least 2 methods")
+    with torch.no_grad():
+        if not _ens_fused(x):
+            mean = x.mean(dim=2)
+            return mean, ((x - mean.unsqueeze(2)) ** 2).sum(dim=2) / (M - 1) if variance else None
+        B, V, _ = x.shape
+        mean = torch.empty((B, V), dtype=torch.float32, device=x.device)
+        var = torch.empty_like(mean) if variance else None
+        _lib.check(_lib.lib().yt8m_ens_moments(_p(x), _p(mean), _p(var), B, V, M, _stream()))
+        return mean, var
 
 
 class _MoeHead(torch.autograd.Function):

@@ -74,6 +74,19 @@ def xavier_uniform(shape, gen, device):
     return torch.empty(shape, dtype=torch.float32, device=device).uniform_(-lim, lim, generator=gen)
 
 
+def glorot_uniform(shape, gen, device):
+    """What tf.get_variable without an initializer draws for a float variable under TF 1.0 (glorot_uniform_initializer; fans as
+    init_ops._compute_fans): 1-D fan_in = fan_out = shape[0]; 2-D shape[0], shape[1]; N-D the last two dimensions times the product of
+    the leading ones.  xavier_uniform above agrees for 1-D and 2-D shapes."""
+    if len(shape) <= 2:
+        return xavier_uniform(shape, gen, device)
+    field = 1
+    for d in shape[:-2]:
+        field *= d
+    lim = math.sqrt(6.0 / (shape[-2] * field + shape[-1] * field))
+    return torch.empty(shape, dtype=torch.float32, device=device).uniform_(-lim, lim, generator=gen)
+
+
 def zeros(shape, gen, device):
     return torch.zeros(shape, dtype=torch.float32, device=device)
 
