@@ -499,6 +499,30 @@ int yt8m_lnlstm_layer_bwd(const float* z, const float* Wh, int64_t ldw, const fl
                           float keep_prob, uint64_t seed, void* gemm_workspace, int64_t gemm_workspace_bytes,
                           yt8m_stream_t stream);
 
+/* ---- scalar-gate LSTM layer (csrc/gate_lstm.hip), time-major, generic per-step form ---------------------------------
+ * The recurrent unit of Z/frame_level_models.py:1583-1640 (LstmGateModel; LstmGateMultilayerModel :1733-1790) under a plain
+ * tf.while_loop over all F steps -- no copy-through, no masking; h_0 = c_0 = 0:
+ *   i = sigmoid(x.Wi + h.Ui + bi) [B,1],  f = sigmoid(x.Wf + h.Uf + bf) [B,1],  o = sigmoid(x.Wog + h.Uog + bog) [B,H],
+ *   g = tanh(x.Wc + h.Uc + bc) [B,H];  c' = f c + i g;  h' = o tanh(c').
+ *   zv [F,B,2H]: in = x.[Wog|Wc] + [bog|bc] (hoisted by the caller), out = the activations o | g, in place;
+ *   zs [F,B] rows of stride lds >= 2: in = x.[Wi|Wf] + [bi|bf] in columns 0 and 1, out = i | f (other columns untouched);
+ *   Uv = [Uog|Uc] [H,2H] with leading dimension ldu, Us [2,H] = the rows Ui, Uf;
+ *   hs, cs [F+1,B,H] with row 0 = initial state (zeroed by the caller);
+ *   c_last [B,H] (optional) receives cs[num_frames[b]][b], written by the step with t + 1 == num_frames[b]; zeros for rows
+ *   with num_frames[b] < 1 or > F.  num_frames may be NULL only together with c_last and dc_last.
+ * Backward: dout [F,B,H] (optional, w.r.t. hs[1:]), dc_last [B,H] (optional) -> dzv [F,B,2H], dzs (stride lds, columns 0, 1;
+ * the other columns are not touched); work >= 4*B*H floats.  Weight / input gradients are hoisted GEMMs over dzv / dzs (caller).
+ * yt8m_gate_lstm_supported: what the step kernels take (H % 256 == 0, H <= 2048); both entry points refuse other shapes with
+ * YT8M_E_SHAPE. */
+int yt8m_gate_lstm_supported(int64_t B, int64_t H);
+int yt8m_gate_lstm_layer_fwd(float* zv, float* zs, int64_t lds, const float* Uv, int64_t ldu, const float* Us, float* hs, float* cs,
+                             float* c_last, const int32_t* num_frames, int64_t F, int64_t B, int64_t H, void* gemm_workspace,
+                             int64_t gemm_workspace_bytes, yt8m_stream_t stream);
+int yt8m_gate_lstm_layer_bwd(const float* zv, const float* zs, int64_t lds, const float* Uv, int64_t ldu, const float* Us,
+                             const float* hs, const float* cs, const float* dout, const float* dc_last, float* dzv, float* dzs,
+                             float* work, const int32_t* num_frames, int64_t F, int64_t B, int64_t H, void* gemm_workspace,
+                             int64_t gemm_workspace_bytes, yt8m_stream_t stream);
+
 /* ---- counter-based random elementwise ops (csrc/random.hip) -------------------------------------
  * Philox4x32-10: element e of the logical tensor uses word (e & 3) of the block with counter (e >> 2), key = seed;
  * `offset` = logical index of x[0], so a chunk of a tensor draws the same numbers as a call over the whole tensor and the

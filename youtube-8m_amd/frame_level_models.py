@@ -10,7 +10,7 @@ from . import models, model_utils, ops, seq_ops, video_level_models
 from .video_level_models import (composed_link, distill_link as _distill_link, fused_link, moe_stage, prediction_chain, relu_kind,
                                  relu_link)
 from .flags import FLAGS, DEFINE_integer, DEFINE_bool, DEFINE_string
-from .variables import get_default_graph, xavier_uniform, zeros, ones, random_normal
+from .variables import constant, get_default_graph, ones, random_normal, truncated_normal, xavier_uniform, zeros
 
 # W/frame_level_models.py:20-84 (hot-path subset)
 DEFINE_integer("iterations", 30, "Number of frames per batch for DBoF.")
@@ -1143,3 +1143,68 @@ class GatedNetVLADAttentionChainModel(GatedNetVLADModel):
         res = video_level_models.DeepCombineChainModel().create_model(chain_in, vocab_size, l2_penalty=l2_penalty,
                                                                       original_input=model_input, support_pool=pool, **unused_params)
         return {"predictions": pool(res["predictions"]), "support_predictions": res["support_predictions"]}
+
+
+# ---- Z = youtube-8m-zhangteng: the scalar-gate LSTM models ------------------------------------------------------------------------
+# Not built from Z/frame_level_models.py (one line each):
+#   MoeDistillChain* heads: Z's video-level chain heads, a separate family from --video_level_classifier_model's;
+#   LstmGlu* / LstmBiglu*: carry a second recurrent state over the input and need another cell;
+#   LstmMultiscale*: the gate cell over several pooled time scales, a different loop structure;
+#   the *Extend* models: extra per-video feature inputs the readers here do not provide.
+GATE_LSTM_VARS = ("Wi", "Ui", "bi", "Wf", "Uf", "bf", "Wog", "Uog", "bog", "Wc", "Uc", "bc")      # create_recurrent_unit's order
+
+
+def _gate_lstm_unit(d_in, hidden, l2_penalty):
+    """create_recurrent_unit (Z/frame_level_models.py:1583-1611, :1733-1761) in the current scope: the twelve Variables with the
+    reference's names, shapes and initial values -- weights truncated_normal(stddev=0.1), bi = bog = bc = 0.1, bf = 1.0 -- every one
+    of them, biases included, under l2_penalty * l2_loss."""
+    g = get_default_graph()
+    shapes = {"Wi": (d_in, 1), "Ui": (hidden, 1), "bi": (1,), "Wf": (d_in, 1), "Uf": (hidden, 1), "bf": (1,),
+              "Wog": (d_in, hidden), "Uog": (hidden, hidden), "bog": (hidden,), "Wc": (d_in, hidden), "Uc": (hidden, hidden), "bc": (hidden,)}
+    inits = {"bi": constant(0.1), "bf": constant(1.0), "bog": constant(0.1), "bc": constant(0.1)}
+    return {n: g.get_variable(n, shapes[n], inits.get(n, truncated_normal(0.1)), l2=l2_penalty) for n in GATE_LSTM_VARS}
+
+
+def _gate_lstm_layer(x_tm, num_frames, hidden, scope, l2_penalty):
+    """One layer under variable_scope(scope): the unit's Variables as views into the operands of seq_ops.gate_lstm_layer (concatenated
+    per call: [Wog|Wc], [Wi|Wf], [Uog|Uc], [Ui|Uf]^T; the gradients come back through the same glue into each Variable's slot).
+    Returns (out_tm [F,B,H], the memory gathered at frame num_frames - 1 [B,H])."""
+    d_in = x_tm.D if isinstance(x_tm, seq_ops.U8FrameImages) else x_tm.shape[2]
+    with get_default_graph().variable_scope(scope):
+        v = {n: ops.as_tensor(var) for n, var in _gate_lstm_unit(d_in, hidden, l2_penalty).items()}
+    Wv, bv = torch.cat([v["Wog"], v["Wc"]], dim=1), torch.cat([v["bog"], v["bc"]])
+    Ws, bs = torch.cat([v["Wi"], v["Wf"]], dim=1), torch.cat([v["bi"], v["bf"]])
+    Uv, Us = torch.cat([v["Uog"], v["Uc"]], dim=1), torch.cat([v["Ui"], v["Uf"]], dim=1).t()
+    return seq_ops.gate_lstm_layer(x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames)
+
+
+class LstmGateModel(models.BaseModel):
+    """Z/frame_level_models.py:1521-1640: one layer of the scalar-gate LSTM cell (input and forget gate one scalar per video, output
+    gate and candidate vectors) run over all max_frames steps by a tf.while_loop -- no dynamic_rnn copy-through; the head
+    (--video_level_classifier_model) reads the memory c gathered at frame num_frames - 1 (:1570-1574).  H = --lstm_cells.  Variables
+    lstm_forward/{Wi,Ui,bi,Wf,Uf,bf,Wog,Uog,bog,Wc,Uc,bc}.  A row with num_frames < 1 (the reference gathers the previous video's last
+    frame there, out of range for the first video) hands zeros to the head and receives no gradient.
+    accepts_quantized_input: _hoisted_input -- the layer reads the reader's bytes where the byte products cover the shape."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
+        x_tm = _hoisted_input(model_input, num_frames)
+        _, state = _gate_lstm_layer(x_tm, num_frames, int(FLAGS.lstm_cells), "lstm_forward", l2_penalty)
+        return _classify(state, model_input, vocab_size, **unused_params)
+
+
+class LstmGateMultilayerModel(models.BaseModel):
+    """Z/frame_level_models.py:1642-1790: --lstm_layers layers of the scalar-gate cell (rnn_gate, :1674-1731); layer l + 1 reads all
+    max_frames hidden outputs h of layer l, the head reads the layers' gathered memories concatenated (:1666).  Layer i's Variables
+    live under "lstm_lsyer<i>lstm_forward/" -- the reference's spelling, which checkpoints carry.  Rows with num_frames < 1: as
+    LstmGateModel.  accepts_quantized_input: _hoisted_input -- layer 0 reads the reader's bytes."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
+        hidden_outputs = _hoisted_input(model_input, num_frames)
+        state_outputs = []
+        for i in range(FLAGS.lstm_layers):
+            # rnn_gate takes its own l2_penalty=1e-8 (:1674); create_model's is not forwarded to it
+            hidden_outputs, state = _gate_lstm_layer(hidden_outputs, num_frames, int(FLAGS.lstm_cells), "lstm_lsyer%dlstm_forward" % i, 1e-8)
+            state_outputs.append(state)
+        return _classify(torch.cat(state_outputs, dim=1), model_input, vocab_size, **unused_params)

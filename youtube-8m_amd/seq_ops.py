@@ -333,6 +333,155 @@ def lnlstm_layer(x_tm, W, gammas, betas, num_frames, forget_bias=1.0, keep_prob=
     return _LnLstmLayer.apply(x_tm, _token(W._graph), W, tuple(gammas), tuple(betas), num_frames, forget_bias, keep_prob, seed)
 
 
+# ---- scalar-gate LSTM layer (Z/frame_level_models.py:1521-1790; csrc/gate_lstm.hip) ------------------------------------
+GATE_LSTM_FUSED = os.environ.get("YT8M_GATE_LSTM_FUSED", "1") != "0"   # 0: the composed torch form everywhere (A/B runs, tests)
+GATE_LSTM_CALLS = {"kernels": 0, "composed": 0}     # which form ran (tests assert that the kernels engaged)
+_GATE_U8_LDS = 4                                    # the byte products' scaled epilogue stores float4: N % 4 == 0
+
+
+def _gate_last_memory(cs, num_frames):
+    """cs [F,B,H] (the memory after every step) -> cs[num_frames[b] - 1][b]; zeros for rows whose num_frames is not in 1..F."""
+    F, B = cs.shape[0], cs.shape[1]
+    nf = num_frames.to(torch.int64)
+    valid = ((nf >= 1) & (nf <= F)).to(cs.dtype).unsqueeze(1)
+    return cs[(nf - 1).clamp(0, F - 1), torch.arange(B, device=cs.device)] * valid
+
+
+def gate_lstm_layer_composed(x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames):
+    """gate_lstm_layer in plain torch under autograd: a Python time loop over all F steps, in the dtype of its operands."""
+    GATE_LSTM_CALLS["composed"] += 1
+    if isinstance(x_tm, U8FrameImages):                       # the bytes' meaning: dequantised, padding zeroed, l2-normalised
+        x_tm = ops.dequant_l2norm(x_tm.q, x_tm.nf).transpose(0, 1)
+    F, B, D = x_tm.shape
+    H = Uv.shape[0]
+    x2 = x_tm.reshape(F * B, D)
+    zv = (x2 @ Wv + bv).view(F, B, 2 * H)
+    zs = (x2 @ Ws + bs).view(F, B, 2)
+    h = c = torch.zeros((B, H), dtype=zv.dtype, device=zv.device)
+    hs, cs = [], []
+    for t in range(F):
+        s = torch.sigmoid(zs[t] + h @ Us.t())
+        v = zv[t] + h @ Uv
+        i, f = s[:, 0:1], s[:, 1:2]
+        o, g = torch.sigmoid(v[:, :H]), torch.tanh(v[:, H:])
+        c = f * c + i * g
+        h = o * torch.tanh(c)
+        hs.append(h)
+        cs.append(c)
+    return torch.stack(hs), _gate_last_memory(torch.stack(cs), num_frames)
+
+
+class _GateLstmLayer(torch.autograd.Function):
+    """One layer of the scalar-gate cell on the step kernels (yt8m_gate_lstm_layer_fwd / _bwd hold the time loop); the parameters are
+    tensors under autograd.  The four input projections are two hoisted products over all steps: the vector block [Wog|Wc] and the
+    scalar block [Wi|Wf], the latter zero-padded to _GATE_U8_LDS columns in scratch on the byte path."""
+
+    @staticmethod
+    def forward(ctx, x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames):
+        bf = ops.FLAGS.compute_dtype == "bfloat16"
+        frames = _hoisted_input(x_tm, bf)
+        F, B, Din, dev = frames.F, frames.B, frames.D, frames.device
+        H = Uv.shape[0]
+        assert tuple(Wv.shape) == (Din, 2 * H) and tuple(Ws.shape) == (Din, 2) and tuple(Uv.shape) == (H, 2 * H) \
+            and tuple(Us.shape) == (2, H) and bv.numel() == 2 * H and bs.numel() == 2, "gate LSTM operands: Wv [in,2H], Ws [in,2], Uv [H,2H], Us [2,H]"
+        lds = _GATE_U8_LDS if isinstance(frames, U8FrameImages) else 2
+        Wv, bv, Uv, Us = (_f32c(t.detach()) for t in (Wv, bv, Uv, Us))
+        Wsp = torch.zeros((Din, lds), dtype=torch.float32, device=dev)
+        bsp = torch.zeros((lds,), dtype=torch.float32, device=dev)
+        Wsp[:, :2].copy_(Ws.detach())
+        bsp[:2].copy_(bs.detach().view(-1))
+        zv = torch.empty((F, B, 2 * H), dtype=torch.float32, device=dev)
+        zs = torch.empty((F * B, lds), dtype=torch.float32, device=dev)
+        frames.project(Wv, bv.view(-1), zv.view(F * B, 2 * H))
+        frames.project(Wsp, bsp, zs)
+        hs = torch.empty((F + 1, B, H), dtype=torch.float32, device=dev)
+        cs = torch.empty((F + 1, B, H), dtype=torch.float32, device=dev)
+        hs[0].zero_()
+        cs[0].zero_()
+        c_last = torch.empty((B, H), dtype=torch.float32, device=dev)
+        nf = _nf(num_frames)
+        ws = ops._workspace(dev)
+        _lib.check(_lib.lib().yt8m_gate_lstm_layer_fwd(_p(zv), _p(zs), lds, _p(Uv), 2 * H, _p(Us), _p(hs), _p(cs), _p(c_last), _p(nf),
+                                                       F, B, H, _p(ws), ws.numel() * 4, _stream()))
+        GATE_LSTM_CALLS["kernels"] += 1
+        ctx.save_for_backward(frames.saved)
+        ctx.frames = frames
+        ctx.state = (zv, zs, hs, cs, nf, Wv, Wsp, Uv, Us, lds)
+        ctx.bf16 = bf
+        ctx.set_materialize_grads(False)
+        return hs[1:], c_last
+
+    @staticmethod
+    def backward(ctx, dout, dc_last):
+        ctx.saved_tensors                                            # (the frames' tensor: checked against in-place changes)
+        frames = ctx.frames
+        zv, zs, hs, cs, nf, Wv, Wsp, Uv, Us, lds = ctx.state
+        ctx.state = ctx.frames = None
+        F, B, Din, dev = frames.F, frames.B, frames.D, frames.device
+        H = Uv.shape[0]
+        dzv = torch.empty((F, B, 2 * H), dtype=torch.float32, device=dev)
+        # the padding columns are zeroed once: the kernel writes columns 0 and 1 only, the hoisted products read every column
+        dzs = (torch.zeros if lds > 2 else torch.empty)((F * B, lds), dtype=torch.float32, device=dev)
+        work = torch.empty((4, B, H), dtype=torch.float32, device=dev)
+        dout = None if dout is None else _f32c(dout)
+        dc_last = None if dc_last is None else _f32c(dc_last)
+        ws = ops._workspace(dev)
+        _lib.check(_lib.lib().yt8m_gate_lstm_layer_bwd(_p(zv), _p(zs), lds, _p(Uv), 2 * H, _p(Us), _p(hs), _p(cs), _p(dout), _p(dc_last),
+                                                       _p(dzv), _p(dzs), _p(work), _p(nf), F, B, H, _p(ws), ws.numel() * 4, _stream()))
+        v2 = dzv.view(F * B, 2 * H)
+        h2 = hs[:F].view(F * B, H)
+        need = ctx.needs_input_grad
+        gWv = gbv = gWs = gbs = gUv = gUs = dx = None
+        if need[1]:
+            gWv = torch.empty((Din, 2 * H), dtype=torch.float32, device=dev)
+            frames.weight_grad(v2, gWv, 0.0)
+        if need[2]:
+            gbv = ops.colsum(v2, torch.empty((2 * H,), dtype=torch.float32, device=dev))
+        if need[3]:
+            gWsp = torch.empty((Din, lds), dtype=torch.float32, device=dev)
+            frames.weight_grad(dzs, gWsp, 0.0)
+            gWs = gWsp[:, :2]
+        if need[4]:
+            gbs = ops.colsum(dzs, torch.empty((lds,), dtype=torch.float32, device=dev))[:2]
+        if need[5]:
+            gUv = ops.gemm_any(h2, v2, transA=True, role="dw", bf16=ctx.bf16)
+        if need[6]:
+            gUs = ops.gemm_any(dzs, h2, transA=True, role="dw", bf16=ctx.bf16)[:2]
+        if need[0]:
+            dx = frames.dx(dzs, Wsp, into=frames.dx(v2, Wv))
+        return dx, gWv, gbv, gWs, gbs, gUv, gUs, None
+
+
+def gate_lstm_supported(x_tm, H):
+    """Whether gate_lstm_layer runs x_tm (U8FrameImages, or float frames [F,B,in]) at H cells on the step kernels."""
+    if not GATE_LSTM_FUSED:
+        return False
+    if isinstance(x_tm, U8FrameImages):
+        B = x_tm.B
+    elif x_tm.is_cuda and x_tm.dtype == torch.float32:
+        B = x_tm.shape[1]
+    else:
+        return False
+    return bool(_lib.lib().yt8m_gate_lstm_supported(int(B), int(H)))
+
+
+def gate_lstm_layer(x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames):
+    """One layer of the scalar-gate LSTM cell of Z/frame_level_models.py:1583-1640 (LstmGateModel.create_recurrent_unit; :1733-1790 in
+    LstmGateMultilayerModel) under its tf.while_loop (:1554-1565 / :1708-1720), time-major:
+        i = sigmoid(x.Wi + h.Ui + bi) [B,1]     f = sigmoid(x.Wf + h.Uf + bf) [B,1]
+        o = sigmoid(x.Wog + h.Uog + bog) [B,H]  g = tanh(x.Wc + h.Uc + bc) [B,H]       c' = f c + i g,  h' = o tanh(c'),  h_0 = c_0 = 0.
+    x_tm: float frames [F,B,in] or U8FrameImages; Wv = [Wog|Wc] [in,2H], bv = [bog|bc] [2H], Ws = [Wi|Wf] [in,2], bs = [bi|bf] [2],
+    Uv = [Uog|Uc] [H,2H], Us = [Ui^T; Uf^T] [2,H]: tensors under autograd.  Every row runs all F steps (no copy-through, no masking; the
+    padding frames are zero rows of x).  Returns (out_tm [F,B,H] = every step's h, c_last [B,H] = the memory after step
+    num_frames - 1, the reference's gather at :1570-1574 / :1728-1729).  Rows with num_frames < 1: the reference's flat gather index is then
+    the previous video's last frame (out of range for the first video); here such a row's c_last is zeros and it receives no gradient.
+    Device tensors at shapes yt8m_gate_lstm_supported takes run on the step kernels (csrc/gate_lstm.hip); CPU tensors, other shapes and
+    YT8M_GATE_LSTM_FUSED=0 take gate_lstm_layer_composed, which computes the same function."""
+    if gate_lstm_supported(x_tm, Uv.shape[0]):
+        return _GateLstmLayer.apply(x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames)
+    return gate_lstm_layer_composed(x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames)
+
+
 # ---- MultiRNNCell stack, pipelined over time chunks: streams, resident buffers, native descriptor ----------
 _SIDE = {}            # (device, persistent) -> the stack's layer / weight-gradient streams; (device, name) -> a one-off side stream
 

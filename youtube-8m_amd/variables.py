@@ -101,6 +101,25 @@ def random_normal(stddev):
     return init
 
 
+def truncated_normal(stddev):
+    """tf.truncated_normal(shape, stddev=stddev): normal draws, those beyond two standard deviations drawn again."""
+    def init(shape, gen, device):
+        t = torch.empty(shape, dtype=torch.float32, device=device).normal_(0.0, 1.0, generator=gen)
+        while True:
+            far = t.abs() > 2.0
+            n = int(far.sum())
+            if n == 0:
+                return t.mul_(stddev)
+            t[far] = torch.empty((n,), dtype=torch.float32, device=device).normal_(0.0, 1.0, generator=gen)
+    return init
+
+
+def constant(value):
+    def init(shape, gen, device):
+        return torch.full(shape, float(value), dtype=torch.float32, device=device)
+    return init
+
+
 def random_seed(graph_seed, rank, step, call):
     """Key of random op number `call` of forward pass `step` on `rank`: splitmix64 finaliser over the packed tuple, so that
     tests (and a restarted job) can reproduce every mask from four integers."""
