@@ -523,6 +523,45 @@ int yt8m_gate_lstm_layer_bwd(const float* zv, const float* zs, int64_t lds, cons
                              float* work, const int32_t* num_frames, int64_t F, int64_t B, int64_t H, void* gemm_workspace,
                              int64_t gemm_workspace_bytes, yt8m_stream_t stream);
 
+/* ---- input-memory LSTM layer (csrc/glu_lstm.hip), time-major, generic per-step form ------------------------------------
+ * The recurrent unit of Z/frame_level_models.py:695-792 (LstmGlu2Model; LstmGlu2MultilayerModel :794-885) under a plain tf.while_loop
+ * over all F steps -- no copy-through, no masking; every state starts at 0.  Beside h and c the cell carries xm [B,D], a memory of
+ * its input, and reads it l2-normalised: hx = xm * r, r = rsqrt(max(n2, 1e-12)), n2 = sum xm^2:
+ *   s = sigmoid(x.Ws + hx.Vs + h.Us + bs) [B,4] = i | f | ix | fx,  o = sigmoid(x.Wog + hx.Vog + h.Uog + bog) [B,H],
+ *   g = tanh(x.Wc + hx.Vc + h.Uc + bc) [B,H];  c' = f c + i g;  h' = o tanh(c');  xm' = fx xm + ix x.
+ * The projections of xm are carried as states, qv = xm.[Vog|Vc] [B,2H] and qs = xm.Vs [B,4]: qv' = fx qv + ix pv_t, qs' = fx qs + ix ps_t
+ * with pv_t = x_t.[Vog|Vc], ps_t = x_t.Vs hoisted by the caller, and hx.V = r q.
+ *   zv, pv [F,B] rows of 2H floats, both with row stride ldv >= 2H (two windows of one [F B, 4H] product, or two matrices):
+ *     zv in = x.[Wog|Wc] + [bog|bc], out = the activations o | g, in place; pv = x.[Vog|Vc], read only;
+ *   zs [F,B] rows of stride lds >= 8: columns 0..3 in = x.[Wi|Wf|Wix|Wfx] + [bi|bf|bix|bfx], out = i | f | ix | fx; columns 4..7 =
+ *     x.[Vi|Vf|Vix|Vfx], read only; other columns untouched;
+ *   Uv = [Uog|Uc] [H,2H] with leading dimension ldu, Us [4,H] = the rows Ui, Uf, Uix, Ufx;
+ *   the frames: x [F,B,D] floats, or xq [B,F,D] bytes with xr [F,B] = 1 / ||a0 q + c0|| per frame (0 on padding frames;
+ *     U8FrameImages.q / .r): x_t[b] = xr[t B + b] (a0 xq[b,t,:] + c0).  Exactly one of x, xq; 16- / 4-byte aligned;
+ *   tapes with row 0 = the initial state (zeroed by the caller): hs, cs [F+1,B,H], qv [F+1,B,2H], qs [F+1,B,4], xm [F+1,B,D] (16-byte
+ *     aligned), n2 [F+1,B];
+ *   c_last [B,H] (optional) receives cs[num_frames[b]][b]; zeros for rows with num_frames[b] < 1 or > F.  num_frames may be NULL only
+ *     together with c_last and dc_last.
+ * Backward: dout [F,B,H] (optional, w.r.t. hs[1:]), dc_last [B,H] (optional) -> dzv, dpv [F,B] rows of 2H floats with row stride lddv
+ * (gradients w.r.t. zv's and pv's inputs), dzs rows of stride lds (columns 0..3 w.r.t. zs, 4..7 w.r.t. ps; other columns untouched),
+ * dx_direct [F,B,D] (optional; float frames: the part of dx that does not pass through a hoisted product, ix dxm).  With byte
+ * frames the rows of dpv and dps that belong to a padding frame (xr = 0: x_t = 0, and every gradient that reads them multiplies
+ * them by x_t) are written as zeros: their true values grow like r, up to 1e6 once xm has decayed below the epsilon;
+ * work >= B * (8 H + D + 8) floats, 16-byte aligned.  Weight / input gradients are hoisted GEMMs over dzv | dpv and dzs (caller).
+ * yt8m_glu_lstm_supported: what the step kernels take (H % 256 == 0, H <= 2048; D % 4 == 0, D <= 2048); both entry points refuse
+ * other shapes with YT8M_E_SHAPE. */
+int yt8m_glu_lstm_supported(int64_t B, int64_t H, int64_t D);
+int yt8m_glu_lstm_layer_fwd(float* zv, float* pv, int64_t ldv, float* zs, int64_t lds, const float* Uv, int64_t ldu, const float* Us,
+                            const float* x, const uint8_t* xq, const float* xr, float* hs, float* cs, float* qv, float* qs, float* xm,
+                            float* n2, float* c_last, const int32_t* num_frames, int64_t F, int64_t B, int64_t H, int64_t D,
+                            void* gemm_workspace, int64_t gemm_workspace_bytes, yt8m_stream_t stream);
+int yt8m_glu_lstm_layer_bwd(const float* zv, const float* pv, int64_t ldv, const float* zs, int64_t lds, const float* Uv, int64_t ldu,
+                            const float* Us, const float* x, const uint8_t* xq, const float* xr, const float* hs, const float* cs,
+                            const float* qv, const float* qs, const float* xm, const float* n2, const float* dout,
+                            const float* dc_last, float* dzv, float* dpv, int64_t lddv, float* dzs, float* dx_direct, float* work,
+                            const int32_t* num_frames, int64_t F, int64_t B, int64_t H, int64_t D, void* gemm_workspace,
+                            int64_t gemm_workspace_bytes, yt8m_stream_t stream);
+
 /* ---- counter-based random elementwise ops (csrc/random.hip) -------------------------------------
  * Philox4x32-10: element e of the logical tensor uses word (e & 3) of the block with counter (e >> 2), key = seed;
  * `offset` = logical index of x[0], so a chunk of a tensor draws the same numbers as a call over the whole tensor and the

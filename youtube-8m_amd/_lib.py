@@ -164,6 +164,10 @@ SIGNATURES = {
     "yt8m_gate_lstm_layer_fwd": (c_int, [P, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int64, c_int64, P, c_int64, P]),
     "yt8m_gate_lstm_layer_bwd": (c_int, [P, P, c_int64, P, c_int64, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, P, c_int64,
                                          P]),
+    "yt8m_glu_lstm_supported": (c_int, [c_int64, c_int64, c_int64]),
+    "yt8m_glu_lstm_layer_fwd": (c_int, [P, P, c_int64, P, c_int64, P, c_int64] + [P] * 12 + [c_int64] * 4 + [P, c_int64, P]),
+    "yt8m_glu_lstm_layer_bwd": (c_int, [P, P, c_int64, P, c_int64, P, c_int64] + [P] * 14 + [c_int64] + [P] * 4 + [c_int64] * 4 +
+                                        [P, c_int64, P]),
     "yt8m_dropout_f32": (c_int, [P, P, c_int64, c_float, ctypes.c_uint64, c_int64, P]),
     "yt8m_add_noise_f32": (c_int, [P, P, c_int64, c_float, ctypes.c_uint64, c_int64, P]),
     "yt8m_moe_mix_bwd_bf16_partial_rows": (c_int64, [c_int64]),

@@ -1148,7 +1148,7 @@ class GatedNetVLADAttentionChainModel(GatedNetVLADModel):
 # ---- Z = youtube-8m-zhangteng: the scalar-gate LSTM models ------------------------------------------------------------------------
 # Not built from Z/frame_level_models.py (one line each):
 #   MoeDistillChain* heads: Z's video-level chain heads, a separate family from --video_level_classifier_model's;
-#   LstmGlu* / LstmBiglu*: carry a second recurrent state over the input and need another cell;
+#   LstmBiglu*: a gate layer on reversed frames feeding a layer with a second hoisted input;
 #   LstmMultiscale*: the gate cell over several pooled time scales, a different loop structure;
 #   the *Extend* models: extra per-video feature inputs the readers here do not provide.
 GATE_LSTM_VARS = ("Wi", "Ui", "bi", "Wf", "Uf", "bf", "Wog", "Uog", "bog", "Wc", "Uc", "bc")      # create_recurrent_unit's order
@@ -1206,5 +1206,73 @@ class LstmGateMultilayerModel(models.BaseModel):
         for i in range(FLAGS.lstm_layers):
             # rnn_gate takes its own l2_penalty=1e-8 (:1674); create_model's is not forwarded to it
             hidden_outputs, state = _gate_lstm_layer(hidden_outputs, num_frames, int(FLAGS.lstm_cells), "lstm_lsyer%dlstm_forward" % i, 1e-8)
+            state_outputs.append(state)
+        return _classify(torch.cat(state_outputs, dim=1), model_input, vocab_size, **unused_params)
+
+
+# ---- Z: the input-memory LSTM models (LstmGlu2Model, LstmGlu2MultilayerModel) -----------------------------------------------------
+GLU_LSTM_VARS = ("Wi", "Ui", "Vi", "bi", "Wf", "Vf", "Uf", "bf", "Wog", "Vog", "Uog", "bog", "Wc", "Vc", "Uc", "bc",
+                 "Wix", "Vix", "Uix", "bix", "Wfx", "Vfx", "Ufx", "bfx")                       # create_recurrent_unit's order
+
+
+def _glu_lstm_unit(d_in, hidden, l2_penalty):
+    """create_recurrent_unit (Z/frame_level_models.py:695-749) in the current scope: the 24 Variables with the reference's names, shapes
+    and initial values -- weights truncated_normal(stddev=0.1), bi = bog = bc = bix = 0.1, bf = bfx = 1.0 -- every one of them, biases
+    included, under l2_penalty * l2_loss.  W* act on the frame, V* on the l2-normalised input memory, U* on h."""
+    g = get_default_graph()
+
+    def shape(n):
+        if n[0] == "b":
+            return (hidden,) if n in ("bog", "bc") else (1,)
+        return (hidden if n[0] == "U" else d_in, hidden if n[1:] in ("og", "c") else 1)
+
+    inits = {"bi": constant(0.1), "bf": constant(1.0), "bog": constant(0.1), "bc": constant(0.1), "bix": constant(0.1), "bfx": constant(1.0)}
+    return {n: g.get_variable(n, shape(n), inits.get(n, truncated_normal(0.1)), l2=l2_penalty) for n in GLU_LSTM_VARS}
+
+
+def _glu_lstm_layer(x_tm, num_frames, hidden, scope, l2_penalty):
+    """One layer under variable_scope(scope): the unit's Variables as views into the operands of seq_ops.glu_lstm_layer (concatenated
+    per call, as _gate_lstm_layer: [Wog|Wc], [Vog|Vc], [Uog|Uc] and the four scalar gates' columns in the order i, f, ix, fx; the
+    gradients come back through the same glue into each Variable's slot).  Returns (out_tm [F,B,H], the memory gathered at frame
+    num_frames - 1 [B,H])."""
+    d_in = x_tm.D if isinstance(x_tm, seq_ops.U8FrameImages) else x_tm.shape[2]
+    with get_default_graph().variable_scope(scope):
+        v = {n: ops.as_tensor(var) for n, var in _glu_lstm_unit(d_in, hidden, l2_penalty).items()}
+    sc = ("i", "f", "ix", "fx")
+    Wv, Vv, Uv = (torch.cat([v[k + "og"], v[k + "c"]], dim=1) for k in "WVU")
+    Ws, Vs, Us = (torch.cat([v[k + n] for n in sc], dim=1) for k in "WVU")
+    bv, bs = torch.cat([v["bog"], v["bc"]]), torch.cat([v["b" + n] for n in sc])
+    return seq_ops.glu_lstm_layer(x_tm, Wv, bv, Ws, bs, Vv, Vs, Uv, Us.t(), num_frames)
+
+
+class LstmGlu2Model(models.BaseModel):
+    """Z/frame_level_models.py:631-792: one layer of the input-memory LSTM cell -- the scalar-gate cell (LstmGateModel) with a second
+    recurrent state over the INPUT, x_prev' = fx x_prev + ix x under two more scalar gates, whose l2-normalised value enters all six
+    gates through V* -- run over all max_frames steps by a tf.while_loop; the head (--video_level_classifier_model) reads the memory
+    c gathered at frame num_frames - 1 (:682-686).  H = --lstm_cells.  Variables lstm_forward/{Wi,Ui,Vi,bi,Wf,Vf,Uf,bf,Wog,Vog,Uog,bog,
+    Wc,Vc,Uc,bc,Wix,Vix,Uix,bix,Wfx,Vfx,Ufx,bfx}.  A row with num_frames < 1 hands zeros to the head and receives no gradient (as
+    LstmGateModel).  accepts_quantized_input: _hoisted_input -- the layer reads the reader's bytes where the byte products cover the
+    shape."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
+        x_tm = _hoisted_input(model_input, num_frames)
+        _, state = _glu_lstm_layer(x_tm, num_frames, int(FLAGS.lstm_cells), "lstm_forward", l2_penalty)
+        return _classify(state, model_input, vocab_size, **unused_params)
+
+
+class LstmGlu2MultilayerModel(models.BaseModel):
+    """Z/frame_level_models.py:794-885: --lstm_layers layers of the input-memory cell (rnn_gate, :826-885); layer l + 1 reads all
+    max_frames hidden outputs h of layer l, the head reads the layers' gathered memories concatenated (:818).  Layer i's Variables
+    live under "lstm_lsyer<i>lstm_forward/" -- the reference's spelling, which checkpoints carry.  Rows with num_frames < 1: as
+    LstmGlu2Model.  accepts_quantized_input: _hoisted_input -- layer 0 reads the reader's bytes."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
+        hidden_outputs = _hoisted_input(model_input, num_frames)
+        state_outputs = []
+        for i in range(FLAGS.lstm_layers):
+            # rnn_gate takes its own l2_penalty=1e-8 (:826); create_model's is not forwarded to it
+            hidden_outputs, state = _glu_lstm_layer(hidden_outputs, num_frames, int(FLAGS.lstm_cells), "lstm_lsyer%dlstm_forward" % i, 1e-8)
             state_outputs.append(state)
         return _classify(torch.cat(state_outputs, dim=1), model_input, vocab_size, **unused_params)

@@ -482,6 +482,179 @@ def gate_lstm_layer(x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames):
     return gate_lstm_layer_composed(x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames)
 
 
+# ---- input-memory LSTM layer (Z/frame_level_models.py:631-885; csrc/glu_lstm.hip) -------------------------------------------
+# The default form follows the project's rule: the kernels only if their median is the lower one at every shape of tools/glu_lstm_step.py
+# in both runs (DESIGN_LOG.md 32).  1: the step kernels where the shape is supported; 0: the composed torch form everywhere.
+GLU_LSTM_FUSED = os.environ.get("YT8M_GLU_LSTM_FUSED", "1") != "0"
+GLU_LSTM_CALLS = {"kernels": 0, "composed": 0}      # which form ran (tests assert that the kernels engaged)
+_GLU_LDS = 8                                        # zs | ps: the eight scalar projections of a frame, one row
+
+
+def glu_lstm_layer_composed(x_tm, Wv, bv, Ws, bs, Vv, Vs, Uv, Us, num_frames):
+    """glu_lstm_layer in plain torch under autograd, in the reference's form: a Python time loop over all F steps that carries xm and
+    multiplies hx = l2_normalize(xm) by [Vog|Vc] and Vs at every step; in the dtype of its operands."""
+    GLU_LSTM_CALLS["composed"] += 1
+    if isinstance(x_tm, U8FrameImages):                       # the bytes' meaning: dequantised, padding zeroed, l2-normalised
+        x_tm = ops.dequant_l2norm(x_tm.q, x_tm.nf).transpose(0, 1)
+    F, B, D = x_tm.shape
+    H = Uv.shape[0]
+    x2 = x_tm.reshape(F * B, D)
+    zv = (x2 @ Wv + bv).view(F, B, 2 * H)
+    zs = (x2 @ Ws + bs).view(F, B, 4)
+    h = c = torch.zeros((B, H), dtype=zv.dtype, device=zv.device)
+    xm = torch.zeros((B, D), dtype=zv.dtype, device=zv.device)
+    hs, cs = [], []
+    for t in range(F):
+        hx = xm * torch.rsqrt((xm * xm).sum(1, keepdim=True).clamp(min=1e-12))
+        s = torch.sigmoid(zs[t] + hx @ Vs + h @ Us.t())
+        v = zv[t] + hx @ Vv + h @ Uv
+        i, f, ix, fx = s[:, 0:1], s[:, 1:2], s[:, 2:3], s[:, 3:4]
+        o, g = torch.sigmoid(v[:, :H]), torch.tanh(v[:, H:])
+        c = f * c + i * g
+        h = o * torch.tanh(c)
+        xm = fx * xm + ix * x_tm[t]
+        hs.append(h)
+        cs.append(c)
+    return torch.stack(hs), _gate_last_memory(torch.stack(cs), num_frames)
+
+
+class _GluLstmLayer(torch.autograd.Function):
+    """One layer of the input-memory cell on the step kernels (yt8m_glu_lstm_layer_fwd / _bwd hold the time loop); the parameters are
+    tensors under autograd.  The twelve input projections are two hoisted products over all steps: x.[Wog|Wc|Vog|Vc] -> zv | pv and
+    x.[Wi|Wf|Wix|Wfx|Vi|Vf|Vix|Vfx] -> zs | ps; the kernels carry xm's projections as states and read the frames themselves (floats,
+    or U8FrameImages.q / .r: no fp32 copy of the bytes is made)."""
+
+    @staticmethod
+    def forward(ctx, x_tm, Wv, bv, Ws, bs, Vv, Vs, Uv, Us, num_frames):
+        bf = ops.FLAGS.compute_dtype == "bfloat16"
+        frames = _hoisted_input(x_tm, bf)
+        F, B, Din, dev = frames.F, frames.B, frames.D, frames.device
+        H = Uv.shape[0]
+        assert tuple(Wv.shape) == (Din, 2 * H) and tuple(Vv.shape) == (Din, 2 * H) and tuple(Ws.shape) == (Din, 4) \
+            and tuple(Vs.shape) == (Din, 4) and tuple(Uv.shape) == (H, 2 * H) and tuple(Us.shape) == (4, H) and bv.numel() == 2 * H \
+            and bs.numel() == 4, "glu LSTM operands: Wv, Vv [in,2H], Ws, Vs [in,4], Uv [H,2H], Us [4,H]"
+        u8 = isinstance(frames, U8FrameImages)
+        lds = _GLU_LDS
+        Uv, Us = _f32c(Uv.detach()), _f32c(Us.detach())
+        W4 = torch.cat([Wv.detach(), Vv.detach()], dim=1).float().contiguous()
+        b4 = torch.zeros((4 * H,), dtype=torch.float32, device=dev)
+        b4[:2 * H].copy_(bv.detach().view(-1))
+        W8 = torch.cat([Ws.detach(), Vs.detach()], dim=1).float().contiguous()
+        b8 = torch.zeros((lds,), dtype=torch.float32, device=dev)
+        b8[:4].copy_(bs.detach().view(-1))
+        zvp = torch.empty((F * B, 4 * H), dtype=torch.float32, device=dev)
+        zs = torch.empty((F * B, lds), dtype=torch.float32, device=dev)
+        frames.project(W4, b4, zvp)
+        frames.project(W8, b8, zs)
+        tape = lambda *shape: torch.empty((F + 1,) + shape, dtype=torch.float32, device=dev)
+        hs, cs, qv, qs, xm, n2 = tape(B, H), tape(B, H), tape(B, 2 * H), tape(B, 4), tape(B, Din), tape(B)
+        for s in (hs, cs, qv, qs, xm, n2):
+            s[0].zero_()
+        c_last = torch.empty((B, H), dtype=torch.float32, device=dev)
+        nf = _nf(num_frames)
+        ws = ops._workspace(dev)
+        xin = (None, frames.q, frames.r) if u8 else (frames.x2, None, None)
+        _lib.check(_lib.lib().yt8m_glu_lstm_layer_fwd(_p(zvp), _p(zvp[:, 2 * H:]), 4 * H, _p(zs), lds, _p(Uv), 2 * H, _p(Us), _p(xin[0]),
+                                                      _p(xin[1]), _p(xin[2]), _p(hs), _p(cs), _p(qv), _p(qs), _p(xm), _p(n2), _p(c_last),
+                                                      _p(nf), F, B, H, Din, _p(ws), ws.numel() * 4, _stream()))
+        GLU_LSTM_CALLS["kernels"] += 1
+        ctx.save_for_backward(frames.saved)
+        ctx.frames = frames
+        ctx.state = (zvp, zs, hs, cs, qv, qs, xm, n2, nf, W4, W8, Uv, Us, xin)
+        ctx.bf16 = bf
+        ctx.set_materialize_grads(False)
+        return hs[1:], c_last
+
+    @staticmethod
+    def backward(ctx, dout, dc_last):
+        ctx.saved_tensors                                            # (the frames' tensor: checked against in-place changes)
+        frames = ctx.frames
+        zvp, zs, hs, cs, qv, qs, xm, n2, nf, W4, W8, Uv, Us, xin = ctx.state
+        ctx.state = ctx.frames = None
+        F, B, Din, dev = frames.F, frames.B, frames.D, frames.device
+        H = Uv.shape[0]
+        lds = _GLU_LDS
+        need = ctx.needs_input_grad
+        dv4 = torch.empty((F * B, 4 * H), dtype=torch.float32, device=dev)          # dzv | dpv
+        ds8 = torch.empty((F * B, lds), dtype=torch.float32, device=dev)            # dzs | dps: the kernel writes all eight columns
+        dxd = torch.empty((F, B, Din), dtype=torch.float32, device=dev) if (need[0] and xin[0] is not None) else None
+        work = torch.empty((B * (8 * H + Din + 8),), dtype=torch.float32, device=dev)
+        dout = None if dout is None else _f32c(dout)
+        dc_last = None if dc_last is None else _f32c(dc_last)
+        ws = ops._workspace(dev)
+        _lib.check(_lib.lib().yt8m_glu_lstm_layer_bwd(_p(zvp), _p(zvp[:, 2 * H:]), 4 * H, _p(zs), lds, _p(Uv), 2 * H, _p(Us), _p(xin[0]),
+                                                      _p(xin[1]), _p(xin[2]), _p(hs), _p(cs), _p(qv), _p(qs), _p(xm), _p(n2), _p(dout),
+                                                      _p(dc_last), _p(dv4), _p(dv4[:, 2 * H:]), 4 * H, _p(ds8), _p(dxd), _p(work), _p(nf),
+                                                      F, B, H, Din, _p(ws), ws.numel() * 4, _stream()))
+        h2 = hs[:F].view(F * B, H)
+        gWv = gbv = gWs = gbs = gVv = gVs = gUv = gUs = dx = None
+        # dpv_t and dps_t grow like r = 1 / ||xm||: up to 1e6 on the frames behind a video's end, where xm decays below the normalisation's
+        # epsilon and x_t = 0.  On bytes the kernel writes those rows as zeros; on float frames they are kept (dx reads them), so the
+        # products over dpv / dps keep the fp32-grade form instead of the weight-gradient role's one scale per matrix.
+        u8 = xin[0] is None
+        if need[1] or need[5]:
+            gW4 = torch.empty((Din, 4 * H), dtype=torch.float32, device=dev)
+            if u8:
+                frames.weight_grad(dv4, gW4, 0.0)
+            else:
+                frames.weight_grad(dv4[:, :2 * H], gW4[:, :2 * H], 0.0)
+                ops.gemm_any(frames.x2, dv4[:, 2 * H:], out=gW4[:, 2 * H:], transA=True, bf16=ctx.bf16)
+            gWv, gVv = gW4[:, :2 * H], gW4[:, 2 * H:]
+        if need[2]:
+            gbv = ops.colsum(dv4[:, :2 * H], torch.empty((2 * H,), dtype=torch.float32, device=dev))
+        if need[3] or need[6]:
+            gW8 = torch.empty((Din, lds), dtype=torch.float32, device=dev)
+            if u8:
+                frames.weight_grad(ds8, gW8, 0.0)
+            else:
+                ops.gemm_any(frames.x2, ds8, out=gW8, transA=True, bf16=ctx.bf16)
+            gWs, gVs = gW8[:, :4], gW8[:, 4:8]
+        if need[4]:
+            gbs = ops.colsum(ds8, torch.empty((lds,), dtype=torch.float32, device=dev))[:4]
+        if need[7]:
+            gUv = ops.gemm_any(h2, dv4[:, :2 * H], transA=True, role="dw", bf16=ctx.bf16)
+        if need[8]:
+            gUs = ops.gemm_any(ds8[:, :4], h2, transA=True, role="dw", bf16=ctx.bf16)
+        if need[0]:
+            dx = frames.dx(ds8, W8, into=frames.dx(dv4, W4))
+            if dx is not None:
+                dx.add_(dxd)
+        return dx, gWv, gbv, gWs, gbs, gVv, gVs, gUv, gUs, None
+
+
+def glu_lstm_supported(x_tm, H):
+    """Whether glu_lstm_layer runs x_tm (U8FrameImages, or float frames [F,B,in]) at H cells on the step kernels."""
+    if not GLU_LSTM_FUSED:
+        return False
+    if isinstance(x_tm, U8FrameImages):
+        B, D = x_tm.B, x_tm.D
+    elif x_tm.is_cuda and x_tm.dtype == torch.float32:
+        B, D = x_tm.shape[1], x_tm.shape[2]
+    else:
+        return False
+    return bool(_lib.lib().yt8m_glu_lstm_supported(int(B), int(H), int(D)))
+
+
+def glu_lstm_layer(x_tm, Wv, bv, Ws, bs, Vv, Vs, Uv, Us, num_frames):
+    """One layer of the input-memory LSTM cell of Z/frame_level_models.py:695-792 (LstmGlu2Model.create_recurrent_unit; :848 in
+    LstmGlu2MultilayerModel) under its tf.while_loop (:666-677 / :862-873), time-major.  With xm the memory of the input (x_prev in the
+    reference) and hx = xm * rsqrt(max(sum xm^2, 1e-12)) (tf.nn.l2_normalize), all states starting at 0:
+        s = sigmoid(x.Ws + hx.Vs + h.Us + bs) [B,4] = i | f | ix | fx
+        o = sigmoid(x.Wog + hx.Vog + h.Uog + bog) [B,H]     g = tanh(x.Wc + hx.Vc + h.Uc + bc) [B,H]
+        c' = f c + i g,  h' = o tanh(c'),  xm' = fx xm + ix x.
+    x_tm: float frames [F,B,in] or U8FrameImages; Wv = [Wog|Wc], Vv = [Vog|Vc] [in,2H], bv = [bog|bc] [2H]; Ws = [Wi|Wf|Wix|Wfx],
+    Vs = [Vi|Vf|Vix|Vfx] [in,4], bs = [bi|bf|bix|bfx] [4]; Uv = [Uog|Uc] [H,2H], Us = [Ui|Uf|Uix|Ufx]^T [4,H]: tensors under autograd.
+    Every row runs all F steps (no copy-through, no masking; the padding frames are zero rows of x).  Returns (out_tm [F,B,H] = every
+    step's h, c_last [B,H] = the memory after step num_frames - 1, the reference's gather at :682-686 / :882-883).  Rows with
+    num_frames < 1: c_last is zeros and the row receives no gradient through it (as gate_lstm_layer).
+    Device tensors at shapes yt8m_glu_lstm_supported takes run on the step kernels (csrc/glu_lstm.hip), which carry xm.V as a state instead
+    of multiplying at every step; CPU tensors, other shapes and YT8M_GLU_LSTM_FUSED=0 take glu_lstm_layer_composed, which computes the
+    same function in the reference's form."""
+    if glu_lstm_supported(x_tm, Uv.shape[0]):
+        return _GluLstmLayer.apply(x_tm, Wv, bv, Ws, bs, Vv, Vs, Uv, Us, num_frames)
+    return glu_lstm_layer_composed(x_tm, Wv, bv, Ws, bs, Vv, Vs, Uv, Us, num_frames)
+
+
 # ---- MultiRNNCell stack, pipelined over time chunks: streams, resident buffers, native descriptor ----------
 _SIDE = {}            # (device, persistent) -> the stack's layer / weight-gradient streams; (device, name) -> a one-off side stream
 
