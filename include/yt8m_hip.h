@@ -1374,6 +1374,35 @@ int yt8m_ens_combine_bwd(const float* x, const float* Wt, const float* gate, int
                          int64_t M, int J, yt8m_stream_t stream);
 int yt8m_ens_moments(const float* x, float* mean, float* var, int64_t B, int64_t V, int64_t M, yt8m_stream_t stream);
 
+/* ---- sigmoid attention pooling over TIME-major rows (csrc/sigmoid_attention.hip; W/all_frame_models/lstm_attention_model.py:61-73,
+ * lstm_attention_lstm_model.py:78-92, lstm_multi_attention_model.py:63-78) ----------------------------------------------------------
+ * m[t,b] = 1 for t < clamp(num_frames[b], 0, F), else 0.  Row (t, b) of src / vals / dsrc / dvals starts at (t B + b) ld floats.
+ *   z[t,b,a] = src[t,b,:] . Wa[:,a] + ba[a]     src [F,B,Hs], Wa [Hs,A], ba [A]
+ *   s = sigmoid(z) m;   den[b,a] = sum_t s + 1e-8;   att[b,t,a] = s / den            att [B,F,A] (what yt8m_attn_pool_* read), den [B,A]
+ *   pooled[b,a,:] = sum_t att[b,t,a] vals[t,b,:]                                     vals [F,B,Hv], pooled [B,A,Hv]; both NULL with Hv = 0
+ * A video with num_frames <= 0 gets att = 0, pooled = 0 and no gradient.  src and vals rows past num_frames are not read.
+ * fwd: one pass over src and vals; writes att, den and (Hv > 0) pooled.
+ * bwd: G = dpooled [B,A,Hv] (needs vals and pooled) and E = datt [B,F,A]; either may be NULL.  With dt = E + vals . G,
+ *   inner = sum_t att dt and dz = (dt - inner) / den sig (1 - sig) m, sig = att den:  dsrc[t,b,:] = sum_a dz Wa[:,a] (always written),
+ *   dvals[t,b,:] = sum_a att G[b,a,:] (optional; zeros without G), dWa [Hs,A] = sum_{t,b} src dz and dba [A] = sum_{t,b} dz (each
+ *   optional).  One pass over src and vals; EVERY row of dsrc and dvals is written, those past num_frames as exact zeros.
+ * The frames are split into chunks of 32 per workgroup; partial sums go through the workspace and are added in a fixed order: no
+ * atomics, a second run gives the same bits.  workspace: yt8m_sigattn_workspace_bytes (one size for both directions; -1 for refused
+ * shapes), owned by the caller for the duration of the call.  16-byte accesses where every pointer is 16-byte aligned and every leading
+ * dimension is a multiple of 4, single elements otherwise.
+ * yt8m_sigattn_supported: Hs % 4 == 0, 4 <= Hs <= 2048; Hv % 4 == 0, 0 <= Hv <= 2048; 1 <= A <= 8; B, F in [1, 65536] and
+ * B ceil(F / 32) <= 2^21.  Other shapes: YT8M_E_SHAPE; a null operand, a leading dimension below its width, a short workspace:
+ * YT8M_E_BADARG.  Nothing is launched then. */
+int yt8m_sigattn_supported(int64_t B, int64_t F, int64_t Hs, int64_t Hv, int64_t A);
+int64_t yt8m_sigattn_workspace_bytes(int64_t B, int64_t F, int64_t Hs, int64_t Hv, int64_t A);
+int yt8m_sigattn_fwd(const float* src, int64_t ld_src, const float* vals, int64_t ld_vals, const float* Wa, const float* ba,
+                     const int32_t* num_frames, float* att, float* den, float* pooled, void* workspace, int64_t workspace_bytes,
+                     int64_t B, int64_t F, int64_t Hs, int64_t Hv, int64_t A, yt8m_stream_t stream);
+int yt8m_sigattn_bwd(const float* src, int64_t ld_src, const float* vals, int64_t ld_vals, const float* Wa, const int32_t* num_frames,
+                     const float* att, const float* den, const float* pooled, const float* G, const float* E, float* dsrc,
+                     int64_t ld_dsrc, float* dvals, int64_t ld_dvals, float* dWa, float* dba, void* workspace, int64_t workspace_bytes,
+                     int64_t B, int64_t F, int64_t Hs, int64_t Hv, int64_t A, yt8m_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

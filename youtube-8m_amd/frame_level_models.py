@@ -32,6 +32,7 @@ DEFINE_integer("lstm_pipeline_chunks", 2, "Time chunks over which the layers of 
 DEFINE_string("feature_sizes", "1024", "Length of the feature vectors.")     # W/train.py:58 (read by the parallel LSTM model)
 DEFINE_integer("positional_embedding_size", 32, "Positional embedding dimension use in lstm_positional_attention_max_pooling_model.")
 DEFINE_integer("lstm_attentions", 8, "Attention size in lstm_attention_max_pooling_model.")
+DEFINE_integer("attention_size", 1, "Number of attention layers.")                                   # W/frame_level_models.py:49
 DEFINE_bool("is_training", False, "used in batch normalization.")
 DEFINE_integer("multiscale_cnn_lstm_layers", 1, "number of layers in multiscale cnn_lstm.")          # W/frame_level_models.py:77
 DEFINE_integer("distillchain_relu_cells", 256, "number of relu cells in distillchain model.")        # W/frame_level_models.py:81
@@ -383,6 +384,93 @@ class LstmAttentionMaxPoolingModel(models.BaseModel):
 
     def sub_moe(self, model_input, vocab_size, **params):
         return moe_stage(model_input, vocab_size, **params)
+
+
+def _sigmoid_attention_fc(src_tm, num_frames, attention_size, scope, l2_penalty, values_tm=None):
+    """slim.fully_connected(outputs, attention_size, activation_fn=tf.nn.sigmoid, weights_regularizer=l2) under `scope`, masked by
+    num_frames and divided by its sum over the frames plus 1e-8 (W/all_frame_models/lstm_attention_model.py:61-71), on the time-major
+    outputs src_tm [F,B,H] of a stack.  Returns (attention [B,F,A], sum_t attention * values_tm [B,A,Hv] or None): seq_ops.sigmoid_attention."""
+    g = get_default_graph()
+    W = g.get_variable(scope + "/weights", (src_tm.shape[2], attention_size), xavier_uniform, l2=l2_penalty)
+    b = g.get_variable(scope + "/biases", (attention_size,), zeros)
+    return seq_ops.sigmoid_attention(src_tm, W, b, num_frames, values_tm)
+
+
+def _attend_frames(attention, model_input, num_frames):
+    """sum_t attention[b,t,a] * model_input[b,t,:] [B,A,D]: on the reader's bytes one weighted pooling pass over them (no fp32 copy of
+    the frames), on float frames pool_tn.  The frames are data: the gradient goes to the attention only."""
+    if model_input.dtype == torch.uint8:
+        return seq_ops.pool_tn_u8(attention, model_input, seq_ops.u8_frame_scales(model_input, num_frames))
+    return seq_ops.pool_tn(attention, model_input)
+
+
+class LstmAttentionModel(models.BaseModel):
+    """W/all_frame_models/lstm_attention_model.py:13-83: an LSTM stack under RNN; one sigmoid per frame from a fully connected layer on
+    its top outputs, masked and normalised over the video's frames, weighs the INPUT frames; the head reads [mean_input | state], state
+    in LstmModel's state_is_tuple=False order [c0|h0|c1|h1...].  Variables (TF 1.0, from memory): RNN/multi_rnn_cell/cell_<l>/
+    basic_lstm_cell/{weights,biases} and RNN/fully_connected/{weights,biases} (the FC sits inside the RNN scope; its weights carry
+    l2_penalty).  The reference's mask_emb, a non-trainable [F+1,F] lookup table of frame masks, is left out: the mask is computed
+    from num_frames.  accepts_quantized_input: the stack (see _lstm_stack) and the pooling read the reader's bytes."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, **unused_params):
+        lstm_size = int(FLAGS.lstm_cells)
+        l2_penalty = unused_params.get("l2_penalty", 1e-8)
+        model_input, _ = _bytes_or_floats(model_input, num_frames, lambda q: _lib_u8_ok(q.shape[2]) and seq_ops.u8_attention_supported(q, 1))
+        out_tm, finals = _lstm_stack(model_input, num_frames, lstm_size, FLAGS.lstm_layers)
+        attention, _ = _sigmoid_attention_fc(out_tm, num_frames, 1, "RNN/fully_connected", l2_penalty)
+        mean_input = _attend_frames(attention, model_input, num_frames).view(model_input.shape[0], model_input.shape[2])
+        state = torch.cat([t for pair in finals for t in pair], dim=1)
+        return _classify(torch.cat([mean_input, state], dim=1), model_input, vocab_size, **unused_params)
+
+
+class LstmAttentionLstmModel(models.BaseModel):
+    """W/all_frame_models/lstm_attention_lstm_model.py:13-102: two LSTM stacks over the same input, ATT and RNN; the sigmoid attention
+    comes from the ATT stack's top outputs and weighs the RNN stack's top outputs; the head reads [attended_output | ATT final memories
+    c | RNN final memories c].  Variables (TF 1.0, from memory): {ATT,RNN}/multi_rnn_cell/cell_<l>/basic_lstm_cell/{weights,biases} and
+    RNN/fully_connected/{weights,biases} (l2_penalty on the weights).  mask_emb is left out as in LstmAttentionModel.
+    accepts_quantized_input: both stacks read the reader's bytes (see _lstm_stack); logit, gate, mask, sums and the pooling of the RNN
+    outputs are one pass over the two time-major output tensors (seq_ops.sigmoid_attention)."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, **unused_params):
+        lstm_size = int(FLAGS.lstm_cells)
+        number_of_layers = FLAGS.lstm_layers
+        l2_penalty = unused_params.get("l2_penalty", 1e-8)
+        g = get_default_graph()
+        x_tm = _stack_input(model_input, num_frames)                 # prepared once, read by both stacks
+        seq_ops.reserve_resident(2, number_of_layers)
+        stacks = []
+        for slot, scope in enumerate(("ATT", "RNN")):                # both stacks' outputs are alive together: slots of their own
+            with g.variable_scope(scope):
+                wb = _lstm_cells(model_input.shape[2], lstm_size, number_of_layers)
+            stacks.append(_native_stack(x_tm, num_frames, wb, slot=slot))
+        (att_outputs, att_finals), (outputs, finals) = stacks
+        _, attended = _sigmoid_attention_fc(att_outputs, num_frames, 1, "RNN/fully_connected", l2_penalty, values_tm=outputs)
+        final_state = torch.cat([attended.view(attended.shape[0], lstm_size)] + [c for c, _ in att_finals] + [c for c, _ in finals], dim=1)
+        return _classify(final_state, model_input, vocab_size, **unused_params)
+
+
+class LstmMultiAttentionModel(models.BaseModel):
+    """W/all_frame_models/lstm_multi_attention_model.py:13-91: as LstmAttentionModel with --attention_size sigmoid attentions; each
+    weighs the input frames (attention_input [B,A,D], the reference's einsum), the head runs on the B A rows and the prediction is the
+    maximum over a video's A rows, as LstmAttentionMaxPoolingModel finishes.  Variables: RNN/multi_rnn_cell/cell_<l>/basic_lstm_cell/
+    {weights,biases} and fully_connected/{weights,biases} (this FC sits outside the RNN scope; l2_penalty on the weights).  mask_emb is
+    left out as in LstmAttentionModel.  accepts_quantized_input: the stack and the pooling read the reader's bytes."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, **unused_params):
+        lstm_size = int(FLAGS.lstm_cells)
+        attention_size = FLAGS.attention_size
+        l2_penalty = unused_params.get("l2_penalty", 1e-8)
+        model_input, _ = _bytes_or_floats(model_input, num_frames,
+                                          lambda q: _lib_u8_ok(q.shape[2]) and seq_ops.u8_attention_supported(q, attention_size))
+        out_tm, _ = _lstm_stack(model_input, num_frames, lstm_size, FLAGS.lstm_layers)
+        attention, _ = _sigmoid_attention_fc(out_tm, num_frames, attention_size, "fully_connected", l2_penalty)
+        attention_input = _attend_frames(attention, model_input, num_frames)                                  # [B,A,D]
+        attention_output = _classify(attention_input.reshape(-1, model_input.shape[2]), model_input, vocab_size, **unused_params)["predictions"]
+        final_output = ops.frame_pool(attention_output.view(-1, attention_size, vocab_size), "max")           # tf.reduce_max over the attentions
+        return {"predictions": final_output}
 
 
 def _parallel_stacks(model_input, num_frames, lstm_sizes, feature_sizes, number_of_layers, own_slots=False, scope_prefix="", slot_base=0):

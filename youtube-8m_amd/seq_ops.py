@@ -2589,3 +2589,136 @@ def max_pool2_tm(y, F, B, want_pool=True):
     else:
         m = y.view(F, B, C).amax(dim=0)
     return m, (_pair_max(y.view(F, B, C)) if want_pool else None)
+
+
+# ---- sigmoid attention pooling over time-major rows (W/all_frame_models/lstm_attention_model.py:61-73; csrc/sigmoid_attention.hip) ---
+# The default form follows the project's rule: the kernels only if their median is the lower one at every shape of
+# tools/sigmoid_attention_step.py in both runs (DESIGN_LOG.md 33).  1: the kernels where the shape is supported; 0: the composed form.
+SIGMOID_ATTENTION_FUSED = os.environ.get("YT8M_SIGMOID_ATTENTION_FUSED", "1") != "0"
+SIGMOID_ATTENTION_CALLS = {"kernels": 0, "composed": 0}      # which form ran (tests assert that the kernels engaged)
+_SIGATTN_EPS = 1e-8
+
+
+def _is_variable(v):
+    return hasattr(v, "_graph") and not torch.is_tensor(v)
+
+
+def sigmoid_attention_composed(src_tm, Wa, ba, num_frames, values_tm=None):
+    """sigmoid_attention from existing ops, as the reference writes it, in the dtype of its operands: the FC on the [F B, Hs] view
+    (ops.linear on the device when Wa, ba are Variables, else a plain product), torch sigmoid / mask / sum / divide, and pool_tn on a
+    batch-major copy of the values (an einsum off the device)."""
+    SIGMOID_ATTENTION_CALLS["composed"] += 1
+    F, B, Hs = src_tm.shape
+    if _is_variable(Wa) and src_tm.is_cuda:
+        z = ops.linear(src_tm.reshape(F * B, Hs), Wa, ba)
+    else:
+        Wt, bt = (ops.as_tensor(v) if _is_variable(v) else v for v in (Wa, ba))
+        z = src_tm.reshape(F * B, Hs) @ Wt + bt
+    A = z.shape[1]
+    n = num_frames.to(src_tm.device).to(torch.int64).clamp(0, F)
+    mask = (torch.arange(F, device=src_tm.device)[:, None] < n[None, :]).to(z.dtype)              # [F,B]
+    s = torch.sigmoid(z).view(F, B, A) * mask[:, :, None]
+    att = (s / (s.sum(dim=0, keepdim=True) + _SIGATTN_EPS)).permute(1, 0, 2).contiguous()         # [B,F,A]
+    if values_tm is None:
+        return att, None
+    if values_tm.is_cuda and values_tm.dtype == torch.float32:
+        return att, pool_tn(att, values_tm.transpose(0, 1).contiguous())
+    return att, torch.einsum("bfa,fbh->bah", att, values_tm)
+
+
+def _rows_tm(t):
+    """A [F,B,H] float32 tensor as the kernels read it: (tensor, row stride in floats); rows (t, b) at (t B + b) ld."""
+    if t.dtype != torch.float32:
+        raise TypeError("expected float32, got %s" % t.dtype)
+    B = t.shape[1]
+    if t.shape[2] > 0 and not (t.stride(2) == 1 and t.stride(0) == B * t.stride(1) and t.stride(1) >= t.shape[2]):
+        t = t.contiguous()
+    return t, t.stride(1)
+
+
+class _SigmoidAttention(torch.autograd.Function):
+    """yt8m_sigattn_fwd / _bwd under autograd: gradients to src_tm, Wa, ba and values_tm, from the gradient of att and / or of pooled."""
+
+    @staticmethod
+    def forward(ctx, src_tm, Wa, ba, num_frames, values_tm):
+        src, ld_src = _rows_tm(src_tm)
+        _dev(src, Wa, ba, values_tm)
+        F, B, Hs = src.shape
+        A = Wa.shape[1]
+        assert tuple(Wa.shape) == (Hs, A) and ba.numel() == A, "sigmoid attention operands: Wa [Hs,A], ba [A]"
+        Wa, ba = _f32c(Wa.detach()), _f32c(ba.detach().view(-1))
+        vals, ld_vals, Hv = None, 0, 0
+        if values_tm is not None:
+            assert tuple(values_tm.shape[:2]) == (F, B), "values_tm must be [F,B,Hv] like src_tm"
+            vals, ld_vals = _rows_tm(values_tm)
+            Hv = vals.shape[2]
+        dev = src.device
+        lib = _lib.lib()
+        nf = _nf(num_frames)
+        att = torch.empty((B, F, A), dtype=torch.float32, device=dev)
+        den = torch.empty((B, A), dtype=torch.float32, device=dev)
+        pooled = torch.empty((B, A, Hv), dtype=torch.float32, device=dev) if Hv else None
+        nbytes = int(lib.yt8m_sigattn_workspace_bytes(B, F, Hs, Hv, A))
+        ws = torch.empty((max(nbytes, 16) // 4,), dtype=torch.float32, device=dev)
+        _lib.check(lib.yt8m_sigattn_fwd(_p(src), ld_src, _p(vals), ld_vals, _p(Wa), _p(ba), _p(nf), _p(att), _p(den), _p(pooled), _p(ws),
+                                        nbytes, B, F, Hs, Hv, A, _stream()))
+        SIGMOID_ATTENTION_CALLS["kernels"] += 1
+        ctx.save_for_backward(src, vals, Wa, att, den, pooled)
+        ctx.nf, ctx.nbytes = nf, nbytes
+        ctx.set_materialize_grads(False)
+        return att, pooled
+
+    @staticmethod
+    def backward(ctx, datt, dpooled):
+        src, vals, Wa, att, den, pooled = ctx.saved_tensors
+        if datt is None and dpooled is None:
+            return None, None, None, None, None
+        F, B, Hs = src.shape
+        A = Wa.shape[1]
+        Hv = vals.shape[2] if vals is not None else 0
+        dev = src.device
+        E = None if datt is None else _f32c(datt)
+        G = None if dpooled is None else _f32c(dpooled)
+        need = ctx.needs_input_grad
+        dsrc = torch.empty((F, B, Hs), dtype=torch.float32, device=dev)
+        dvals = torch.empty((F, B, Hv), dtype=torch.float32, device=dev) if (vals is not None and need[4]) else None
+        dWa = torch.empty((Hs, A), dtype=torch.float32, device=dev) if need[1] else None
+        dba = torch.empty((A,), dtype=torch.float32, device=dev) if need[2] else None
+        ld_src, ld_vals = src.stride(1), (vals.stride(1) if vals is not None else 0)
+        ws = torch.empty((max(ctx.nbytes, 16) // 4,), dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().yt8m_sigattn_bwd(_p(src), ld_src, _p(vals), ld_vals, _p(Wa), _p(ctx.nf), _p(att), _p(den), _p(pooled), _p(G),
+                                               _p(E), _p(dsrc), Hs, _p(dvals), Hv, _p(dWa), _p(dba), _p(ws), ctx.nbytes, B, F, Hs, Hv, A,
+                                               _stream()))
+        return (dsrc if need[0] else None), dWa, dba, None, dvals
+
+
+def sigmoid_attention_supported(src_tm, A, values_tm=None):
+    """Whether sigmoid_attention runs these operands on the kernels of csrc/sigmoid_attention.hip."""
+    if not SIGMOID_ATTENTION_FUSED or not (torch.is_tensor(src_tm) and src_tm.is_cuda and src_tm.dtype == torch.float32 and src_tm.dim() == 3):
+        return False
+    Hv = 0
+    if values_tm is not None:
+        if not (values_tm.is_cuda and values_tm.dtype == torch.float32 and tuple(values_tm.shape[:2]) == tuple(src_tm.shape[:2])):
+            return False
+        Hv = values_tm.shape[2]
+        if Hv == 0:
+            return False
+    F, B, Hs = src_tm.shape
+    return bool(_lib.lib().yt8m_sigattn_supported(int(B), int(F), int(Hs), int(Hv), int(A)))
+
+
+def sigmoid_attention(src_tm, Wa, ba, num_frames, values_tm=None):
+    """The sigmoid attention pooling of W/all_frame_models/lstm_attention_model.py:61-73, lstm_attention_lstm_model.py:78-92 and
+    lstm_multi_attention_model.py:63-78 on TIME-major operands, m[t,b] = 1 for t < clamp(num_frames[b], 0, F):
+        s = sigmoid(src_tm . Wa + ba) m;   att[b,t,a] = s[t,b,a] / (sum_t s + 1e-8);   pooled[b,a,:] = sum_t att[b,t,a] values_tm[t,b,:]
+    src_tm [F,B,Hs] (an LSTM stack's outputs), Wa [Hs,A] and ba [A] (Variables, or tensors under autograd), values_tm [F,B,Hv] or None.
+    Returns (att [B,F,A] -- the layout pool_tn / pool_tn_u8 read -- and pooled [B,A,Hv], None without values).  A video with
+    num_frames = 0 gets att = 0 and pooled = 0 and receives no gradient.  The reference's mask_emb lookup table is this mask.
+    Device tensors at shapes yt8m_sigattn_supported takes run on the kernels (one pass over src_tm and values_tm each way, no batch-major
+    copy); CPU tensors, other shapes and YT8M_SIGMOID_ATTENTION_FUSED=0 take sigmoid_attention_composed, which computes the same
+    function."""
+    A = (Wa.data if _is_variable(Wa) else Wa).shape[1]
+    if sigmoid_attention_supported(src_tm, A, values_tm):
+        Wt, bt = (ops.as_tensor(v) if _is_variable(v) else v for v in (Wa, ba))
+        return _SigmoidAttention.apply(src_tm, Wt, bt, num_frames, values_tm)
+    return sigmoid_attention_composed(src_tm, Wa, ba, num_frames, values_tm)
