@@ -1403,6 +1403,42 @@ int yt8m_sigattn_bwd(const float* src, int64_t ld_src, const float* vals, int64_
                      int64_t ld_dsrc, float* dvals, int64_t ld_dvals, float* dWa, float* dba, void* workspace, int64_t workspace_bytes,
                      int64_t B, int64_t F, int64_t Hs, int64_t Hv, int64_t A, yt8m_stream_t stream);
 
+/* ---- windowed softmax attention pooling over TIME-major rows (csrc/softmax_attention.hip; Z/frame_level_models.py:5218-5223
+ * LstmExtendModel, :6059-6064 InputExtendModel) --------------------------------------------------------------------------------------
+ * Row (t, b) of src / vals / dsrc / dvals starts at (t B + b) ld floats.  Per head e of E:
+ *   z[t,b,e]   = src[t,b,:] . W1[:,e] + b1[e] + extra[b,t,e]     src [F,B,Hs], W1 [Hs,E], b1 [E], extra [B,F,E] or NULL
+ *   m[t,b,e]   = valid[b,t] (lo[b,e] <= t <= hi[b,e])            valid uint8 [B,F] (NULL: ones), lo / hi int32 [B,E], inclusive, clamped to
+ *                                                                [0, F-1] (NULL: 0 / F-1); lo > hi is an empty window
+ *   att[b,t,e] = m exp(z - M[b,e]) / sum_t' m exp(z[t'] - M[b,e]),  M[b,e] = max of z over the frames with m = 1       att [B,F,E]
+ *   pooled[b,e,:] = sum_t att[b,t,e] vals[t,b,:]                 vals [F,B,Hv], pooled [B,E,Hv]
+ * The reference's softmax over all frames, times the mask, divided by its sum is this function; a (b, e) without an unmasked frame (NaN
+ * there) gets att = 0, pooled = 0 and neither receives nor sends a gradient.  Rows of src and vals that no head unmasks are not read.
+ * Shared mode: vals == src (then Hv == Hs, ld_vals == ld_src): the logits and the pooling walk ONE tensor (a workgroup reads its 64 rows
+ * twice in a row).
+ * fwd: writes att and pooled.
+ * bwd, from G = dpooled [B,E,Hv] alone (att carries no gradient): dz = att ((vals - pooled) . G), the difference taken per element;
+ *   dsrc[t,b,:] = sum_e dz W1[:,e] (always written), dvals[t,b,:] = sum_e att G[b,e,:], dW1 [Hs,E] = sum_{t,b} src dz, dextra [B,F,E] =
+ *   dz, db1 [E] = sum_{t,b} dz, which is 0 whatever the operands (a softmax does not see a shift of all its logits) and is written as
+ *   exact zeros (each optional).  In the shared mode dvals must be NULL and dsrc takes the sum of both row
+ *   gradients.  EVERY row of dsrc, dvals and dextra is written, those no head unmasks as exact zeros.
+ * A workgroup owns 64 frames of one video; partial results go through the workspace and are added in a fixed order: no
+ * atomics, a second run gives the same bits.  workspace: yt8m_smattn_workspace_bytes (one size for both directions; -1 for refused
+ * shapes), owned by the caller for the duration of the call.  16-byte accesses where every pointer is 16-byte aligned and every leading
+ * dimension is a multiple of 4, single elements otherwise.
+ * yt8m_smattn_supported: Hs % 4 == 0, 4 <= Hs <= 2048; Hv % 4 == 0, 4 <= Hv <= 2048; 1 <= E <= 8; B, F in [1, 65536] and
+ * B ceil(F / 32) <= 2^21.  Other shapes: YT8M_E_SHAPE; a null required operand, a leading dimension below its width, a short workspace,
+ * a shared mode with different widths or with dvals: YT8M_E_BADARG.  Nothing is launched then. */
+int yt8m_smattn_supported(int64_t B, int64_t F, int64_t Hs, int64_t Hv, int64_t E);
+int64_t yt8m_smattn_workspace_bytes(int64_t B, int64_t F, int64_t Hs, int64_t Hv, int64_t E);
+int yt8m_smattn_fwd(const float* src, int64_t ld_src, const float* vals, int64_t ld_vals, const float* W1, const float* b1,
+                    const float* extra, const uint8_t* valid, const int32_t* lo, const int32_t* hi, float* att, float* pooled,
+                    void* workspace, int64_t workspace_bytes, int64_t B, int64_t F, int64_t Hs, int64_t Hv, int64_t E,
+                    yt8m_stream_t stream);
+int yt8m_smattn_bwd(const float* src, int64_t ld_src, const float* vals, int64_t ld_vals, const float* W1, const uint8_t* valid,
+                    const int32_t* lo, const int32_t* hi, const float* att, const float* pooled, const float* G, float* dsrc,
+                    int64_t ld_dsrc, float* dvals, int64_t ld_dvals, float* dW1, float* db1, float* dextra, void* workspace,
+                    int64_t workspace_bytes, int64_t B, int64_t F, int64_t Hs, int64_t Hv, int64_t E, yt8m_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

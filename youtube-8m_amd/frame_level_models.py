@@ -1238,7 +1238,13 @@ class GatedNetVLADAttentionChainModel(GatedNetVLADModel):
 #   MoeDistillChain* heads: Z's video-level chain heads, a separate family from --video_level_classifier_model's;
 #   LstmBiglu*: a gate layer on reversed frames feeding a layer with a second hoisted input;
 #   LstmMultiscale*: the gate cell over several pooled time scales, a different loop structure;
-#   the *Extend* models: extra per-video feature inputs the readers here do not provide.
+#   the other *Extend* models, each LstmExtendModel's attention (built at the end of this file, with InputExtendModel) with one change:
+#   LstmExtendStateModel, LstmExtendCNNModel: the attention pools the outputs of a shifted-frames einsum CNN over the input (:5236, :5403);
+#   LstmExtendInputModel: the attention pools the input frames themselves (:5336);
+#   LstmExtendOrthoModel: calculate_ortho(W1) is added to the regularisation losses (:5503);
+#   LstmGateExtendModel, LstmGluExtendModel: the outputs come from a scalar-gate / glu cell's while_loop, not dynamic_rnn (:5574, :5675);
+#   LstmExtendParallelModel: an LSTM over the rgb part only, whose attention also pools the raw audio part (:5778);
+#   LstmExtendCombineModel: ends in MoeMix4Model, a head that is not built here, and its predictions_class (:5852).
 GATE_LSTM_VARS = ("Wi", "Ui", "bi", "Wf", "Uf", "bf", "Wog", "Uog", "bog", "Wc", "Uc", "bc")      # create_recurrent_unit's order
 
 
@@ -1364,3 +1370,103 @@ class LstmGlu2MultilayerModel(models.BaseModel):
             hidden_outputs, state = _glu_lstm_layer(hidden_outputs, num_frames, int(FLAGS.lstm_cells), "lstm_lsyer%dlstm_forward" % i, 1e-8)
             state_outputs.append(state)
         return _classify(torch.cat(state_outputs, dim=1), model_input, vocab_size, **unused_params)
+
+
+# ---- Z: the Extend attention models (LstmExtendModel, InputExtendModel) ------------------------------------------------------------
+def _extend_variables(lstm_size, d_in, num_extend, l2_penalty):
+    """W1 [H,E], b1 [E], W2 [D,E], b2 [E] at the top level, in the reference's order (Z/frame_level_models.py:5210-5217): weights
+    truncated_normal(stddev=0.1), biases 0.1, every one of the four, biases included, under l2_penalty * l2_loss."""
+    g = get_default_graph()
+    return (g.get_variable("W1", (lstm_size, num_extend), truncated_normal(0.1), l2=l2_penalty),
+            g.get_variable("b1", (num_extend,), constant(0.1), l2=l2_penalty),
+            g.get_variable("W2", (d_in, num_extend), truncated_normal(0.1), l2=l2_penalty),
+            g.get_variable("b2", (num_extend,), constant(0.1), l2=l2_penalty))
+
+
+def _extend_input_logits(model_input, num_frames, W2, b2):
+    """xw_plus_b(rnn_input, W2, b2) as [B,F,E], the `extra` operand of seq_ops.softmax_attention_tm: on the reader's bytes one skinny
+    product over them (b2 on the padding frames, whose dequantised rows are zero), on float frames ops.linear.  The frames are data:
+    the gradient goes to W2 and b2 only."""
+    B, F, D = model_input.shape
+    if model_input.dtype == torch.uint8:
+        return seq_ops.attention_logits_u8(model_input, seq_ops.u8_frame_scales(model_input, num_frames), None, W2, b2, parts=[])
+    if model_input.is_cuda:
+        return ops.linear(model_input.reshape(B * F, D), W2, b2).view(B, F, -1)
+    return (model_input.reshape(B * F, D) @ ops.as_tensor(W2) + ops.as_tensor(b2)).view(B, F, -1)
+
+
+class LstmExtendModel(models.BaseModel):
+    """Z/frame_level_models.py:5169-5234: an LSTM stack under RNN; --moe_num_extend attention heads, each a softmax OVER THE FRAMES of
+    outputs . W1 + b1 + input . W2 + b2, times the mask of the video's frames and divided by its sum, pool the stack's top outputs
+    into [B, E, H]; the head (--video_level_classifier_model, MoeExtendModel in the scripts) runs on the B E rows.  The result also
+    carries "attention_weight" [B, E F] in the reference's head-major order, detached.  Variables: RNN/multi_rnn_cell/cell_<l>/
+    basic_lstm_cell/{weights,biases}, then W1, b1, W2, b2 at the top level (see _extend_variables).  create_model's own l2_penalty
+    reaches those four and, as in the reference, is not forwarded to the head.
+    The mask: the reference takes frames_bool = (sum |x| > 0) per frame; float frames get exactly that.  On the reader's bytes a
+    dequantised real frame is never all zero (127 * 4 / 255 - 2 + 4 / 512 != 0), so frames_bool is t < num_frames and the window
+    hi = num_frames - 1 states it.  A video without a frame is NaN in the reference; here its attention and pooled rows are zero and it
+    neither receives nor sends a gradient (seq_ops.softmax_attention_tm).
+    accepts_quantized_input: the stack (see _lstm_stack) and the input logits read the reader's bytes; logits, softmax, mask and the
+    pooling are one pass over the stack's time-major outputs in the shared mode of seq_ops.softmax_attention_tm."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
+        lstm_size = int(FLAGS.lstm_cells)
+        num_extend = FLAGS.moe_num_extend
+        model_input, u8 = _bytes_or_floats(model_input, num_frames,
+                                           lambda q: _lib_u8_ok(q.shape[2]) and seq_ops.u8_attention_supported(q, num_extend))
+        B, F, D = model_input.shape
+        out_tm, _ = _lstm_stack(model_input, num_frames, lstm_size, FLAGS.lstm_layers)
+        W1, b1, W2, b2 = _extend_variables(lstm_size, D, num_extend, l2_penalty)
+        extra = _extend_input_logits(model_input, num_frames, W2, b2)
+        if u8:
+            mask = dict(hi=(num_frames.to(torch.int32) - 1).view(B, 1).expand(B, num_extend).contiguous())
+        else:
+            mask = dict(valid=(model_input.abs().sum(dim=2) > 0).to(torch.uint8))
+        attention, pooled = seq_ops.softmax_attention_tm(out_tm, W1, b1, out_tm, extra=extra, **mask)
+        result = _classify(pooled.reshape(B * num_extend, lstm_size), model_input, vocab_size, **unused_params)
+        result["attention_weight"] = attention.detach().transpose(1, 2).reshape(B, num_extend * F)
+        return result
+
+
+def input_extend_windows(num_frames, num_extend):
+    """(lo, hi) int32 [B,E], both ends included: lo = (num_frames // E) i, hi = lo + 2 (num_frames // E) (Z/frame_level_models.py:
+    6022-6030).  num_frames = 0 gives [0, 0] for every head."""
+    step = (num_frames.to(torch.int32) // num_extend).view(-1, 1)
+    lo = step * torch.arange(num_extend, dtype=torch.int32, device=num_frames.device).view(1, -1)
+    return lo.contiguous(), (lo + 2 * step).contiguous()
+
+
+class InputExtendModel(models.BaseModel):
+    """Z/frame_level_models.py:5995-6073: two LSTM stacks over the same input, RNN_Attention and RNN; --moe_num_extend attention heads,
+    each a softmax over the frames of outputs(RNN_Attention) . W1 + b1 + input . W2 + b2 restricted to the head's window of frames
+    [(num_frames // E) i, (num_frames // E) (i + 2)], pool the RNN stack's top outputs into [B, E, H]; the head runs on the B E rows.
+    Variables: {RNN_Attention,RNN}/multi_rnn_cell/cell_<l>/basic_lstm_cell/{weights,biases}, then W1, b1, W2, b2 (_extend_variables).
+    The mask is the window alone: the reference computes frames_bool_all, the mask of the empty frames, and never uses it, so the last
+    windows run past num_frames ((E + 1) (num_frames // E) can exceed it).  There the stacks' rows are zero, the logit is b1 + b2, and
+    those frames take their share of the softmax while adding zeros to the pooled rows.  That is reproduced.  num_frames = 0 gives the
+    window [0, 0]: frame 0 takes all the weight and the pooled rows are zero.
+    accepts_quantized_input: both stacks (slots of their own, as LstmAttentionLstmModel) and the input logits read the reader's bytes."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
+        lstm_size = int(FLAGS.lstm_cells)
+        number_of_layers = FLAGS.lstm_layers
+        num_extend = FLAGS.moe_num_extend
+        g = get_default_graph()
+        model_input, _ = _bytes_or_floats(model_input, num_frames,
+                                          lambda q: _lib_u8_ok(q.shape[2]) and seq_ops.u8_attention_supported(q, num_extend))
+        B, F, D = model_input.shape
+        x_tm = _stack_input(model_input, num_frames)                 # prepared once, read by both stacks
+        seq_ops.reserve_resident(2, number_of_layers)
+        stacks = []
+        for slot, scope in enumerate(("RNN_Attention", "RNN")):      # both stacks' outputs are alive together: slots of their own
+            with g.variable_scope(scope):
+                wb = _lstm_cells(D, lstm_size, number_of_layers)
+            stacks.append(_native_stack(x_tm, num_frames, wb, slot=slot))
+        (outputs, _), (outputs_features, _) = stacks
+        W1, b1, W2, b2 = _extend_variables(lstm_size, D, num_extend, l2_penalty)
+        extra = _extend_input_logits(model_input, num_frames, W2, b2)
+        lo, hi = input_extend_windows(num_frames, num_extend)
+        _, pooled = seq_ops.softmax_attention_tm(outputs, W1, b1, outputs_features, extra=extra, lo=lo, hi=hi)
+        return _classify(pooled.reshape(B * num_extend, lstm_size), model_input, vocab_size, **unused_params)

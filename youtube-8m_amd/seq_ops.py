@@ -2722,3 +2722,154 @@ def sigmoid_attention(src_tm, Wa, ba, num_frames, values_tm=None):
         Wt, bt = (ops.as_tensor(v) if _is_variable(v) else v for v in (Wa, ba))
         return _SigmoidAttention.apply(src_tm, Wt, bt, num_frames, values_tm)
     return sigmoid_attention_composed(src_tm, Wa, ba, num_frames, values_tm)
+
+
+# ---- windowed softmax attention pooling over time-major rows (Z/frame_level_models.py:5218-5223, :6059-6064; csrc/softmax_attention.hip)
+# The default form follows the project's rule: the kernels only if their median is the lower one at every shape of
+# tools/extend_attention_step.py in both runs (DESIGN_LOG.md 34).  1: the kernels where the shape is supported; 0: the composed form.
+SOFTMAX_ATTENTION_FUSED = os.environ.get("YT8M_SOFTMAX_ATTENTION_FUSED", "1") != "0"
+SOFTMAX_ATTENTION_CALLS = {"kernels": 0, "composed": 0}      # which form ran (tests assert that the kernels engaged)
+
+
+def softmax_attention_mask(F, B, E, valid=None, lo=None, hi=None, device=None):
+    """m [B,F,E] bool: valid[b,t] != 0 and lo[b,e] <= t <= hi[b,e] (inclusive; an absent operand does not restrict)."""
+    m = torch.ones((B, F, E), dtype=torch.bool, device=device)
+    t = torch.arange(F, device=device).view(1, F, 1)
+    if lo is not None:
+        m = m & (t >= lo.to(device).to(torch.int64).view(B, 1, E))
+    if hi is not None:
+        m = m & (t <= hi.to(device).to(torch.int64).view(B, 1, E))
+    if valid is not None:
+        m = m & (valid.to(device).view(B, F, 1) != 0)
+    return m
+
+
+def softmax_attention_tm_composed(src_tm, W1, b1, values_tm, extra=None, valid=None, lo=None, hi=None):
+    """softmax_attention_tm from existing ops, in the dtype of its operands: the FC on the [F B, Hs] view (ops.linear on the device when
+    W1, b1 are Variables, else a plain product), a masked softmax over the frames in torch (max over the unmasked frames, so finite
+    where the reference's softmax-times-mask underflows), and pool_tn on a batch-major copy of the values (an einsum off the device).
+    A (b, e) without an unmasked frame gets att = 0 and pooled = 0 and neither receives nor sends a gradient; att is detached."""
+    SOFTMAX_ATTENTION_CALLS["composed"] += 1
+    F, B, Hs = src_tm.shape
+    if _is_variable(W1) and src_tm.is_cuda:
+        z = ops.linear(src_tm.reshape(F * B, Hs), W1, b1)
+    else:
+        Wt, bt = (ops.as_tensor(v) if _is_variable(v) else v for v in (W1, b1))
+        z = src_tm.reshape(F * B, Hs) @ Wt + bt
+    E = z.shape[1]
+    z = z.view(F, B, E).permute(1, 0, 2)                                                          # [B,F,E]
+    if extra is not None:
+        z = z + extra
+    m = softmax_attention_mask(F, B, E, valid, lo, hi, src_tm.device)
+    zm = z.masked_fill(~m, float("-inf"))
+    M = zm.detach().amax(dim=1, keepdim=True)
+    p = torch.exp(zm - torch.where(torch.isfinite(M), M, torch.zeros_like(M)))                    # 0 on the masked frames
+    L = p.sum(dim=1, keepdim=True)
+    att = (p / torch.where(L > 0, L, torch.ones_like(L))).contiguous()                            # [B,F,E]
+    if values_tm.is_cuda and values_tm.dtype == torch.float32:
+        pooled = pool_tn(att, values_tm.transpose(0, 1).contiguous())
+    else:
+        pooled = torch.einsum("bfe,fbh->beh", att, values_tm)
+    return att.detach(), pooled
+
+
+class _SoftmaxAttentionTM(torch.autograd.Function):
+    """yt8m_smattn_fwd / _bwd under autograd: gradients to src_tm, W1, b1, values_tm and extra from the gradient of pooled; att is not
+    differentiable.  values_tm None is the shared mode (the values ARE src_tm): src_tm then receives the one sum of both gradients."""
+
+    @staticmethod
+    def forward(ctx, src_tm, W1, b1, values_tm, extra, valid, lo, hi):
+        src, ld_src = _rows_tm(src_tm)
+        _dev(src, W1, b1, values_tm, extra)
+        F, B, Hs = src.shape
+        E = W1.shape[1]
+        assert tuple(W1.shape) == (Hs, E) and b1.numel() == E, "softmax attention operands: W1 [Hs,E], b1 [E]"
+        W1, b1 = _f32c(W1.detach()), _f32c(b1.detach().view(-1))
+        shared = values_tm is None
+        if shared:
+            vals, ld_vals = src, ld_src
+        else:
+            assert tuple(values_tm.shape[:2]) == (F, B), "values_tm must be [F,B,Hv] like src_tm"
+            vals, ld_vals = _rows_tm(values_tm)
+        Hv = vals.shape[2]
+        dev = src.device
+        if extra is not None:
+            assert tuple(extra.shape) == (B, F, E), "extra must be [B,F,E]"
+            extra = _f32c(extra.detach())
+        valid = None if valid is None else valid.to(device=dev, dtype=torch.uint8).contiguous().view(B, F)
+        lo, hi = (None if w is None else w.to(device=dev, dtype=torch.int32).contiguous().view(B, E) for w in (lo, hi))
+        lib = _lib.lib()
+        att = torch.empty((B, F, E), dtype=torch.float32, device=dev)
+        pooled = torch.empty((B, E, Hv), dtype=torch.float32, device=dev)
+        nbytes = int(lib.yt8m_smattn_workspace_bytes(B, F, Hs, Hv, E))
+        ws = torch.empty((max(nbytes, 16) // 4,), dtype=torch.float32, device=dev)
+        _lib.check(lib.yt8m_smattn_fwd(_p(src), ld_src, _p(vals), ld_vals, _p(W1), _p(b1), _p(extra), _p(valid), _p(lo), _p(hi), _p(att),
+                                       _p(pooled), _p(ws), nbytes, B, F, Hs, Hv, E, _stream()))
+        SOFTMAX_ATTENTION_CALLS["kernels"] += 1
+        ctx.save_for_backward(src, None if shared else vals, W1, att, pooled)
+        ctx.masks, ctx.nbytes, ctx.has_extra = (valid, lo, hi), nbytes, extra is not None
+        ctx.mark_non_differentiable(att)
+        ctx.set_materialize_grads(False)
+        return att, pooled
+
+    @staticmethod
+    def backward(ctx, _datt, dpooled):
+        src, vals, W1, att, pooled = ctx.saved_tensors
+        if dpooled is None:
+            return (None,) * 8
+        shared = vals is None
+        F, B, Hs = src.shape
+        E = W1.shape[1]
+        Hv = Hs if shared else vals.shape[2]
+        dev = src.device
+        G = _f32c(dpooled)
+        need = ctx.needs_input_grad
+        valid, lo, hi = ctx.masks
+        dsrc = torch.empty((F, B, Hs), dtype=torch.float32, device=dev)
+        dvals = torch.empty((F, B, Hv), dtype=torch.float32, device=dev) if (not shared and need[3]) else None
+        dW1 = torch.empty((Hs, E), dtype=torch.float32, device=dev) if need[1] else None
+        db1 = torch.empty((E,), dtype=torch.float32, device=dev) if need[2] else None
+        dextra = torch.empty((B, F, E), dtype=torch.float32, device=dev) if (ctx.has_extra and need[4]) else None
+        ld_src = src.stride(1)
+        v, ld_vals = (src, ld_src) if shared else (vals, vals.stride(1))
+        ws = torch.empty((max(ctx.nbytes, 16) // 4,), dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().yt8m_smattn_bwd(_p(src), ld_src, _p(v), ld_vals, _p(W1), _p(valid), _p(lo), _p(hi), _p(att), _p(pooled), _p(G),
+                                              _p(dsrc), Hs, _p(dvals), Hv, _p(dW1), _p(db1), _p(dextra), _p(ws), ctx.nbytes, B, F, Hs, Hv, E,
+                                              _stream()))
+        return (dsrc if need[0] else None), dW1, db1, dvals, dextra, None, None, None
+
+
+def softmax_attention_tm_supported(src_tm, E, values_tm, extra=None):
+    """Whether softmax_attention_tm runs these operands on the kernels of csrc/softmax_attention.hip."""
+    ok = lambda t: torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32
+    if not SOFTMAX_ATTENTION_FUSED or not (ok(src_tm) and src_tm.dim() == 3 and ok(values_tm) and values_tm.dim() == 3):
+        return False
+    if tuple(values_tm.shape[:2]) != tuple(src_tm.shape[:2]):
+        return False
+    F, B, Hs = src_tm.shape
+    if extra is not None and not (ok(extra) and tuple(extra.shape) == (B, F, E)):
+        return False
+    return bool(_lib.lib().yt8m_smattn_supported(int(B), int(F), int(Hs), int(values_tm.shape[2]), int(E)))
+
+
+def softmax_attention_tm(src_tm, W1, b1, values_tm, extra=None, valid=None, lo=None, hi=None):
+    """The windowed softmax attention pooling of Z/frame_level_models.py:5218-5223 (LstmExtendModel) and :6059-6064 (InputExtendModel)
+    on TIME-major operands, per head e of E:
+        z[t,b,e] = src_tm[t,b,:] . W1[:,e] + b1[e] + extra[b,t,e];   m[t,b,e] = valid[b,t] (lo[b,e] <= t <= hi[b,e])
+        att[b,t,e] = m exp(z - M) / sum_t' m exp(z[t'] - M),  M[b,e] = max of z over the frames with m = 1
+        pooled[b,e,:] = sum_t att[b,t,e] values_tm[t,b,:]
+    src_tm [F,B,Hs] and values_tm [F,B,Hv] (LSTM stacks' outputs), W1 [Hs,E] and b1 [E] (Variables, or tensors under autograd), extra
+    [B,F,E] (batch-major, what attention_logits_u8 writes) or None, valid [B,F] (any non-zero is 1) or None = all ones, lo / hi [B,E]
+    integers, inclusive, or None = 0 / F - 1.  Returns (att [B,F,E], detached: it is for "attention_weight" and carries no gradient, and
+    pooled [B,E,Hv]).  The reference writes softmax over all F frames, times the mask, divided by its sum: the same function.  A (b, e)
+    without an unmasked frame is NaN there; here it gets att = 0 and pooled = 0 and neither receives nor sends a gradient (the
+    convention of sigmoid_attention).
+    values_tm IS src_tm (the same tensor object) is the shared mode: the rows are read once for the logits and the pooling, and src_tm
+    receives ONE gradient tensor holding the sum of both.  Device tensors at shapes yt8m_smattn_supported takes run on the kernels (no
+    batch-major copy); CPU tensors, other shapes and YT8M_SOFTMAX_ATTENTION_FUSED=0 take softmax_attention_tm_composed, which computes
+    the same function."""
+    E = (W1.data if _is_variable(W1) else W1).shape[1]
+    if softmax_attention_tm_supported(src_tm, E, values_tm, extra):
+        Wt, bt = (ops.as_tensor(v) if _is_variable(v) else v for v in (W1, b1))
+        return _SoftmaxAttentionTM.apply(src_tm, Wt, bt, None if values_tm is src_tm else values_tm, extra, valid, lo, hi)
+    return softmax_attention_tm_composed(src_tm, W1, b1, values_tm, extra, valid, lo, hi)

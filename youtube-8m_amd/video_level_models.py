@@ -16,6 +16,7 @@ DEFINE_integer("deep_chain_layers", 3, "The number of layers used for DeepChainM
 DEFINE_integer("deep_chain_relu_cells", 200, "The number of relu cells used for DeepChainModel")
 DEFINE_string("deep_chain_relu_type", "relu", "The type of relu cells used for DeepChainModel (options are elu and relu)")
 DEFINE_bool("deep_chain_use_length", False, "unused by DeepCombineChainModel (kept for flag compatibility)")
+DEFINE_integer("moe_num_extend", 8, "The number of attention outputs, used for MoeExtendModel.")      # Z/video_level_models.py:31
 # new: MoeModel may return its own "loss" (W/train.py:384-385 honours it) computed by the fused mixing+cross-entropy pass
 DEFINE_bool("fused_head_loss", True, "MoeModel returns {'loss': CrossEntropyLoss(predictions, labels)} from a fused kernel "
             "when labels are given, --label_loss=CrossEntropyLoss, no label smoothing and no --multitask.")
@@ -205,3 +206,38 @@ class DistillchainDeepCombineChainModel(DeepCombineChainModel):
 
     def _link(self, noise_level):
         return fused_link(relu_kind(), noise_level)
+
+
+# ---- Z = youtube-8m-zhangteng: the heads of the Extend attention plugins (frame_level_models.LstmExtendModel, InputExtendModel) ----
+class MoeExtendModel(models.BaseModel):
+    """Z/video_level_models.py:2272-2330: MoeModel's gates and experts (scopes "gates" and "experts") on the B E rows an Extend plugin
+    hands over, E = --moe_num_extend consecutive rows per video, then the maximum over a video's E rows: predictions [B, V]."""
+
+    def _rows(self, model_input, l2_penalty, **unused_params):
+        """What the gates and experts read: the rows as they come."""
+        return model_input
+
+    def create_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, original_input=None, **unused_params):
+        num_mixtures = num_mixtures or FLAGS.moe_num_mixtures
+        num_extends = FLAGS.moe_num_extend
+        assert model_input.shape[0] % num_extends == 0, "MoeExtendModel wants --moe_num_extend rows per video"
+        rows = self._rows(model_input, l2_penalty, **unused_params)
+        p = moe_block(rows, vocab_size, num_mixtures, l2_penalty, "gates", "experts")
+        return {"predictions": ops.frame_pool(p.view(-1, num_extends, vocab_size), "max")}       # tf.reduce_max over a video's rows
+
+
+class MoeExtendDistillChainModel(MoeExtendModel):
+    """Z/video_level_models.py:2332-2400: MoeExtendModel whose rows carry, behind the input, class_input = relu(FC(another model's
+    predictions)) under scope "class_inputs", of fixed width 256 and NOT l2-normalised (unlike distill_link), tiled over a video's E
+    rows.  Without distillation predictions (the reference's distill_labels is None) it is MoeExtendModel."""
+    CLASS_SIZE = 256
+
+    def _rows(self, model_input, l2_penalty, distillation_predictions=None, **unused_params):
+        if distillation_predictions is None:
+            return model_input
+        num_extends = FLAGS.moe_num_extend
+        class_input = fully_connected(distillation_predictions.to(torch.float32), self.CLASS_SIZE, "class_inputs", activation="relu",
+                                      l2_penalty=l2_penalty)
+        B = class_input.shape[0]
+        tiled = class_input.unsqueeze(1).expand(B, num_extends, self.CLASS_SIZE).reshape(B * num_extends, self.CLASS_SIZE)
+        return torch.cat([model_input, tiled], dim=1)
