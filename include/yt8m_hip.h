@@ -1438,6 +1438,21 @@ int yt8m_smattn_bwd(const float* src, int64_t ld_src, const float* vals, int64_t
                     const int32_t* lo, const int32_t* hi, const float* att, const float* pooled, const float* G, float* dsrc,
                     int64_t ld_dsrc, float* dvals, int64_t ld_dvals, float* dW1, float* db1, float* dextra, void* workspace,
                     int64_t workspace_bytes, int64_t B, int64_t F, int64_t Hs, int64_t Hv, int64_t E, yt8m_stream_t stream);
+/* How the LstmMultiscale plugins combine their scales (csrc/scale_mix.hip; Z/frame_level_models.py:2977-2985, :3149-3157): tf.stack,
+ * tf.nn.softmax(dim=1), multiply and reduce_sum in one pass each way.  p[l], z[l] (and dp[l], dz[l]): [rows, cols] contiguous fp32,
+ * 1 <= L <= 8; p, z, dp and dz are HOST arrays of L device pointers, copied into the kernel arguments.
+ *   fwd: w_l = softmax over l of z_l (the maximum subtracted, e_l / sum e); out = sum_l w_l p_l.  Nothing of size [L, rows, cols] is
+ *     written.  L = 1: out is bitwise p_0.
+ *   bwd: from p, z, the saved out and g = dout: w recomputed; dp_l = w_l g, dz_l = w_l (p_l - out) g, the difference taken per element
+ *     (L = 1: dz_0 is zeros).  Every element of every non-NULL dp[l] and dz[l] is written exactly once; a NULL dp[l] or dz[l] is skipped.
+ * Elementwise: no reductions across threads, no atomics, a second run gives the same bits.  16-byte accesses when every operand is
+ * 16-byte aligned (the last rows * cols % 4 elements singly), single elements otherwise.  Out of place.
+ * yt8m_scale_mix_supported: 1 <= L <= 8, 1 <= rows, cols < 2^31, rows * cols <= 2^40; no device is touched.  Other shapes:
+ * YT8M_E_SHAPE; a null required operand or plane: YT8M_E_BADARG.  Nothing is launched then. */
+int yt8m_scale_mix_supported(int L, int64_t rows, int64_t cols);
+int yt8m_scale_mix_fwd(int L, const float* const* p, const float* const* z, float* out, int64_t rows, int64_t cols, yt8m_stream_t stream);
+int yt8m_scale_mix_bwd(int L, const float* const* p, const float* const* z, const float* out, const float* g, float* const* dp,
+                       float* const* dz, int64_t rows, int64_t cols, yt8m_stream_t stream);
 
 #ifdef __cplusplus
 }

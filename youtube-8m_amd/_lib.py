@@ -358,6 +358,9 @@ SIGNATURES = {
     "yt8m_smattn_workspace_bytes": (c_int64, [c_int64] * 5),
     "yt8m_smattn_fwd": (c_int, [P, c_int64, P, c_int64] + [P] * 9 + [c_int64] + [c_int64] * 5 + [P]),
     "yt8m_smattn_bwd": (c_int, [P, c_int64, P, c_int64] + [P] * 8 + [c_int64, P, c_int64, P, P, P, P, c_int64] + [c_int64] * 5 + [P]),
+    "yt8m_scale_mix_supported": (c_int, [c_int, c_int64, c_int64]),
+    "yt8m_scale_mix_fwd": (c_int, [c_int, PP, PP, P, c_int64, c_int64, P]),
+    "yt8m_scale_mix_bwd": (c_int, [c_int, PP, PP, P, P, PP, PP, c_int64, c_int64, P]),
 }
 
 # The ABI this host binds (include/yt8m_hip.h, yt8m_abi_version): workspace layouts and argument meanings, not just symbols.

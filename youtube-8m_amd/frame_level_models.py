@@ -10,7 +10,7 @@ from . import models, model_utils, ops, seq_ops, video_level_models
 from .video_level_models import (composed_link, distill_link as _distill_link, fused_link, moe_stage, prediction_chain, relu_kind,
                                  relu_link)
 from .flags import FLAGS, DEFINE_integer, DEFINE_bool, DEFINE_string
-from .variables import constant, get_default_graph, ones, random_normal, truncated_normal, xavier_uniform, zeros
+from .variables import constant, get_default_graph, glorot_uniform, ones, random_normal, truncated_normal, xavier_uniform, zeros
 
 # W/frame_level_models.py:20-84 (hot-path subset)
 DEFINE_integer("iterations", 30, "Number of frames per batch for DBoF.")
@@ -527,9 +527,9 @@ class LstmPositionalAttentionMaxPoolingModel(LstmAttentionMaxPoolingModel):
         return [positional_embedding, _mean_frame(model_input, num_frames)[:, None, :].expand(B, F, D)], None
 
 
-def _cnn_filters(D, sub_scope, num_filters, filter_sizes, l2_penalty, name="cnn-filter-len%d"):
+def _cnn_filters(D, sub_scope, num_filters, filter_sizes, l2_penalty, name="cnn-filter-len%d", init=None):
     g = get_default_graph()
-    return [g.get_variable(sub_scope + name % fs, (D * fs, nf), random_normal(0.1), l2=l2_penalty)
+    return [g.get_variable(sub_scope + name % fs, (D * fs, nf), init or random_normal(0.1), l2=l2_penalty)
             for nf, fs in zip(num_filters, filter_sizes)]
 
 
@@ -1010,6 +1010,8 @@ class MultiscaleCnnLstmModel(models.BaseModel):
 
     NUM_FILTERS = (256, 256, 512)
     FILTER_SIZES = (1, 2, 3)
+    FILTER_INIT = None                       # _cnn_filters' default: tf.random_normal_initializer(stddev=0.1)
+    SCALES_FLAG = "multiscale_cnn_lstm_layers"
 
     def _rnn(self, x_tm, num_frames, d_in, lstm_size, layer):
         g = get_default_graph()
@@ -1025,7 +1027,16 @@ class MultiscaleCnnLstmModel(models.BaseModel):
         return lstm_memory
 
     def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, is_training=True, **unused_params):
-        num_layers = FLAGS.multiscale_cnn_lstm_layers
+        sub_predictions, _ = self._scales(model_input, vocab_size, num_frames, FLAGS.multiscale_cnn_lstm_layers, l2_penalty, is_training)
+        support_predictions = torch.cat(sub_predictions, dim=1)
+        predictions = sub_predictions[0]
+        for p in sub_predictions[1:]:
+            predictions = predictions + p
+        return {"predictions": predictions / float(len(sub_predictions)), "support_predictions": support_predictions}
+
+    def _scales(self, model_input, vocab_size, num_frames, num_layers, l2_penalty, is_training):
+        """The scale loop, shared with the LstmMultiscale plugins: ([sub-prediction [B,V] per scale], [lstm memory [B,H] per scale]).  Per
+        scale the subclass's _rnn, _head_input (self._scale = the scale's index while it runs) and moe."""
         lstm_size = int(FLAGS.lstm_cells)
         is_training = bool(FLAGS.is_training and is_training)
         features_size = sum(self.NUM_FILTERS)
@@ -1036,10 +1047,11 @@ class MultiscaleCnnLstmModel(models.BaseModel):
         nf = num_frames.to(torch.int32)
         # fused: cnn_input is time-major [F_k B, D_k]; generic: batch-major [B, F_k, D_k]
         cnn_input = None if frames is not None else (model_input.transpose(0, 1).reshape(F * B, D) if fused else model_input)
-        sub_predictions = []
+        sub_predictions, memories = [], []
         for layer in range(num_layers):
             scope = "cnn%d" % (layer + 1)
-            fvars = _cnn_filters(D, scope, self.NUM_FILTERS, self.FILTER_SIZES, l2_penalty)
+            self._scale = layer
+            fvars = _cnn_filters(D, scope, self.NUM_FILTERS, self.FILTER_SIZES, l2_penalty, init=self.FILTER_INIT)
             gamma, beta, mm, mv = _bn_vars(scope + "cluster_bn", features_size)
             last = layer + 1 == num_layers
             if fused:
@@ -1056,17 +1068,14 @@ class MultiscaleCnnLstmModel(models.BaseModel):
                 relu_tm = relu.transpose(0, 1).contiguous()
                 next_input = None if last else relu[:, :(F // 2) * 2].reshape(B, F // 2, 2, features_size).amax(dim=2)
             lstm_memory = self._rnn(relu_tm, nf, features_size, lstm_size, layer)
+            memories.append(lstm_memory)
             sub_predictions.append(self.moe(self._head_input(lstm_memory), vocab_size, l2_penalty=l2_penalty,
                                             scopename="moe%d" % (layer + 1)))
             cnn_input, F, D = next_input, F // 2, features_size
             nf = torch.clamp(nf // 2, min=1)                        # tf.maximum(num_frames / pool_size, 1), integer division
             if F == 0 and not last:
-                raise ValueError("multiscale_cnn_lstm_layers = %d needs more than %d frames" % (num_layers, model_input.shape[1]))
-        support_predictions = torch.cat(sub_predictions, dim=1)
-        predictions = sub_predictions[0]
-        for p in sub_predictions[1:]:
-            predictions = predictions + p
-        return {"predictions": predictions / float(len(sub_predictions)), "support_predictions": support_predictions}
+                raise ValueError("%s = %d needs more than %d frames" % (self.SCALES_FLAG, num_layers, model_input.shape[1]))
+        return sub_predictions, memories
 
 
 class DistillchainMultiscaleCnnLstmModel(MultiscaleCnnLstmModel):
@@ -1237,7 +1246,10 @@ class GatedNetVLADAttentionChainModel(GatedNetVLADModel):
 # Not built from Z/frame_level_models.py (one line each):
 #   MoeDistillChain* heads: Z's video-level chain heads, a separate family from --video_level_classifier_model's;
 #   LstmBiglu*: a gate layer on reversed frames feeding a layer with a second hoisted input;
-#   LstmMultiscale*: the gate cell over several pooled time scales, a different loop structure;
+#   LstmMultiscale3Model: LstmMultiscale2Model on LstmGlu2Model's input-memory cell with the HIDDEN state gathered at frame num_frames - 1,
+#   not the memory (:3375, :3507): seq_ops.glu_lstm_layer hands back the gathered memory only, so it needs a second gather and its gradient;
+#   LstmMultiscaleRebuildModel: a second training stage that fits ensemble_weight2d alone behind stop_gradient on restored scales; it has
+#   no prediction_frames and needs the checkpoint hand-over between two models, which train.py does not have (:3592);
 #   the other *Extend* models, each LstmExtendModel's attention (built at the end of this file, with InputExtendModel) with one change:
 #   LstmExtendStateModel, LstmExtendCNNModel: the attention pools the outputs of a shifted-frames einsum CNN over the input (:5236, :5403);
 #   LstmExtendInputModel: the attention pools the input frames themselves (:5336);
@@ -1470,3 +1482,121 @@ class InputExtendModel(models.BaseModel):
         lo, hi = input_extend_windows(num_frames, num_extend)
         _, pooled = seq_ops.softmax_attention_tm(outputs, W1, b1, outputs_features, extra=extra, lo=lo, hi=hi)
         return _classify(pooled.reshape(B * num_extend, lstm_size), model_input, vocab_size, **unused_params)
+
+
+# ---- Z: the LstmMultiscale models -- the scale loop of MultiscaleCnnLstmModel with a learned per-label mix of the scales --------------------
+DEFINE_integer("cnn_cells", 256, "Number of CNN cells.")                                             # Z/frame_level_models.py:58
+
+
+class LstmMultiscaleModel(MultiscaleCnnLstmModel):
+    """Z/frame_level_models.py:2827-2986: L = --moe_num_extend scales of MultiscaleCnnLstmModel's loop (_scales) -- einsum CNN with
+    256, 256, 512 filters (truncated_normal(stddev=0.1) here), slim.batch_norm over all B F_k rows, ReLU, one BasicLSTMCell inside a
+    one-cell MultiRNNCell whose final memory feeds sub_moe, the pair maximum as the next scale's input -- combined per label:
+        weight = softmax over the scales of memory_l . ensemble_weight2d[l],   predictions = sum_l weight_l sub_prediction_l
+    (ops.scale_mix; the L logit products are one grouped launch each way, ops.linear_group), and
+        prediction_frames [B L, V], row b L + l = scale l's sub-prediction for video b,
+    which is what Z trains on: train.TrainGraph takes its label loss from prediction_frames and none from predictions (Z/train.py:
+    359-379).  predictions_no_grad (TrainGraph.step passes it): predictions is then built without an autograd graph, so no zeros run
+    back through the mix and its products; ensemble_weight2d stays a registered Variable under its l2 term.
+    Variables: cnn<k>cnn-filter-len{1,2,3}, cnn<k>cluster_bn/{gamma,beta,moving_mean,moving_variance},
+    RNN-rnn<k>/multi_rnn_cell/cell_0/basic_lstm_cell/{weights,biases}, gatesmoe<k>/weights, expertsmoe<k>/{weights,biases},
+    ensemble_weight2d [L, sum(filters), V] (glorot uniform, l2 1e-8).  The reference multiplies memories --lstm_cells wide by a weight2d
+    sum(filters) = 1024 deep: any other --lstm_cells is a shape error there and a ValueError here.
+    accepts_quantized_input: as MultiscaleCnnLstmModel."""
+    accepts_quantized_input = True
+    trains_on_prediction_frames = True       # train.TrainGraph.step: asks for predictions without a graph
+
+    FILTER_INIT = staticmethod(truncated_normal(0.1))
+    SCALES_FLAG = "moe_num_extend"
+    WEIGHT2D_L2 = 1.0e-8
+
+    def _rnn(self, x_tm, num_frames, d_in, lstm_size, layer):
+        g = get_default_graph()
+        with g.variable_scope("RNN-rnn%d" % (layer + 1)):
+            wb = _lstm_cells(d_in, lstm_size, 1, multi=True)
+        _, finals = _native_stack(x_tm, num_frames, wb, slot=layer)
+        return finals[0][0]
+
+    def _weight2d_depth(self, features_size, lstm_size):
+        if lstm_size != features_size:
+            raise ValueError("%s multiplies memories --lstm_cells = %d wide by ensemble_weight2d [L, %d, V], as the reference: "
+                             "--lstm_cells must be %d" % (type(self).__name__, lstm_size, features_size, features_size))
+        return features_size
+
+    def _weight2d(self, num_extend, vocab_size):
+        depth = self._weight2d_depth(sum(self.NUM_FILTERS), int(FLAGS.lstm_cells))
+        return get_default_graph().get_variable("ensemble_weight2d", (num_extend, depth, vocab_size), glorot_uniform, l2=self.WEIGHT2D_L2)
+
+    def _combine(self, sub_predictions, memories, weight2d):
+        """predictions from the sub-predictions [B,V], the memories [B,H] and ensemble_weight2d."""
+        logits = ops.linear_group(memories, [(weight2d, l, None) for l in range(len(memories))])
+        return ops.scale_mix(sub_predictions, logits)
+
+    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, is_training=True, predictions_no_grad=False,
+                     **unused_params):
+        num_extend = FLAGS.moe_num_extend
+        self._weight2d_depth(sum(self.NUM_FILTERS), int(FLAGS.lstm_cells))                        # refuses before anything is created
+        seq_ops.reserve_resident(num_extend, 1)                           # the L stacks are alive in one step
+        sub_predictions, memories = self._scales(model_input, vocab_size, num_frames, num_extend, l2_penalty, is_training)
+        weight2d = self._weight2d(num_extend, vocab_size)
+        if predictions_no_grad:
+            with torch.no_grad():
+                predictions = self._combine(sub_predictions, memories, weight2d)
+        else:
+            predictions = self._combine(sub_predictions, memories, weight2d)
+        return {"predictions": predictions,
+                "prediction_frames": torch.stack(sub_predictions, dim=1).reshape(-1, vocab_size)}
+
+
+class LstmMultiscale2Model(LstmMultiscaleModel):
+    """Z/frame_level_models.py:3160-3373: LstmMultiscaleModel with the scalar-gate cell per scale (_gate_lstm_layer under
+    rnn<k>lstm_forward, l2 1e-8, the memory gathered at frame num_frames - 1 of the scale; rows without frames as LstmGateModel) and
+    predictions = the plain mean of the sub-predictions (:3372).  ensemble_weight2d and its softmax are built but unused there (:3366-
+    3369): the Variable is created (checkpoints carry it; the optimiser moves it by its l2 term alone) and nothing is computed from it.
+    Variables: cnn<k>..., rnn<k>lstm_forward/{Wi,Ui,bi,Wf,Uf,bf,Wog,Uog,bog,Wc,Uc,bc}, gatesmoe<k>, expertsmoe<k>, ensemble_weight2d."""
+
+    def _rnn(self, x_tm, num_frames, d_in, lstm_size, layer):
+        _, state = _gate_lstm_layer(x_tm, num_frames, lstm_size, "rnn%dlstm_forward" % (layer + 1), 1e-8)     # rnn_gate's own l2_penalty
+        return state
+
+    def _combine(self, sub_predictions, memories, weight2d):
+        predictions = sub_predictions[0]
+        for p in sub_predictions[1:]:
+            predictions = predictions + p
+        return predictions / float(len(sub_predictions))
+
+
+class LstmMultiscaleDitillChainModel(LstmMultiscaleModel):
+    """Z/frame_level_models.py:2988-3158 (the reference's spelling): LstmMultiscaleModel with filters (c, c, 2 c), c = --cnn_cells, an
+    ensemble_weight2d --lstm_cells deep, and a cascade input: each sub_moe reads [memory | relu(FC_256(distillation_predictions))], the FC
+    under class_inputsmoe<k> (one per scale, width fixed at 256, l2, NOT l2-normalised; :3051-3059).  The L FCs read one input: they are
+    created together before the scale loop and run as one grouped launch each way.  The cascade input arrives as
+    distillation_predictions (--distillation_as_input); without it the model is LstmMultiscaleModel with the other widths, as in the
+    reference."""
+    CLASS_SIZE = 256
+
+    def _weight2d_depth(self, features_size, lstm_size):
+        return lstm_size
+
+    def _head_input(self, lstm_memory):
+        if self._class_inputs is None:
+            return lstm_memory
+        return torch.cat([lstm_memory, self._class_inputs[self._scale]], dim=1)
+
+    def create_model(self, model_input, vocab_size, num_frames, distillation_predictions=None, l2_penalty=1e-8, **unused_params):
+        c = FLAGS.cnn_cells
+        self.NUM_FILTERS = (c, c, 2 * c)
+        self._class_inputs = None
+        if distillation_predictions is not None:
+            g = get_default_graph()
+            x = distillation_predictions.to(torch.float32)
+            spec = []
+            for k in range(FLAGS.moe_num_extend):
+                scope = "class_inputsmoe%d" % (k + 1)
+                spec.append((g.get_variable(scope + "/weights", (x.shape[1], self.CLASS_SIZE), xavier_uniform, l2=l2_penalty), None,
+                             g.get_variable(scope + "/biases", (self.CLASS_SIZE,), zeros)))
+            self._class_inputs = [ops.activation(y, "relu") for y in ops.linear_group([x] * len(spec), spec)]
+        try:
+            return super().create_model(model_input, vocab_size, num_frames, l2_penalty=l2_penalty, **unused_params)
+        finally:
+            self._class_inputs = None

@@ -1,8 +1,9 @@
 """Thin Python wrappers + autograd plumbing over the C ABI (include/yt8m_hip.h).
 
 torch is used for device memory, streams and the autograd tape only; every FLOP of the hot path is a
-HIP kernel in libyt8m_hip.so.  No op has a CPU / eager fallback: host tensors raise.  (One documented exception: ens_combine /
-ens_moments of the ensemble stage have a composed torch form that inputs outside the kernels' layout take by rule, not by failure.)
+HIP kernel in libyt8m_hip.so.  No op has a CPU / eager fallback: host tensors raise.  (Documented exceptions: ens_combine /
+ens_moments of the ensemble stage and scale_mix have a composed torch form that inputs outside the kernels' layout take by rule, not by
+failure; linear_group multiplies CPU tensors with torch, for the host tests.)
 
 Gradient routing: parameters are NOT autograd leaves.  Each op's backward writes dW directly into the
 variable's slice of the gradient arena (GEMM beta = 0 on first write, 1 afterwards) and returns None for
@@ -1330,6 +1331,131 @@ def memory_link(tensors, normalize, eps=1e-12):
         cat = torch.cat(tensors, dim=1)
         return l2_normalize(cat, eps) if normalize else cat
     return _MemoryLink.apply(bool(normalize), eps, *tensors)
+
+
+# 0 (the default): scale_mix composes torch.stack, softmax, multiply and sum; anything else: the fused kernels of csrc/scale_mix.hip.
+# Composed is the default until tools/scale_mix_step.py's op leg has shown the kernels' median below the composed form's at every shape in
+# both runs: nobody has measured it on an MI355X yet (DESIGN_LOG.md section 35).
+SCALE_MIX_FUSED = os.environ.get("YT8M_SCALE_MIX_FUSED", "0") != "0"
+SCALE_MIX_MAX = 8                                    # csrc/scale_mix.hip MAX_L
+SCALE_MIX_CALLS = {"kernels": 0, "composed": 0}      # which form ran (tests)
+
+
+def scale_mix_composed(ps, zs):
+    """sum_l softmax_l(z_l) p_l in torch ops, in the dtype of the inputs."""
+    return (torch.softmax(torch.stack(list(zs), dim=0), dim=0) * torch.stack(list(ps), dim=0)).sum(dim=0)
+
+
+def _ptr_table(tensors):
+    """A host array of device pointers (NULL for None), as the C ABI's `float* const*` arguments take it."""
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+class _ScaleMix(torch.autograd.Function):
+    """csrc/scale_mix.hip: the per-label softmax over the scales and the weighted sum of the sub-predictions in one pass each way.  Saved
+    for backward: the 2 L planes and out."""
+
+    @staticmethod
+    def forward(ctx, L, *planes):
+        planes = [_f32c(t) for t in planes]
+        _dev(*planes)
+        rows, cols = planes[0].shape
+        out = torch.empty((rows, cols), dtype=torch.float32, device=planes[0].device)
+        ctx.L = L
+        ctx.save_for_backward(out, *planes)
+        _lib.check(_lib.lib().yt8m_scale_mix_fwd(L, _ptr_table(planes[:L]), _ptr_table(planes[L:]), _p(out), rows, cols, _stream()))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        out, *planes = ctx.saved_tensors
+        L = ctx.L
+        g = _f32c(g)
+        want = [k for k in range(2 * L) if ctx.needs_input_grad[1 + k]]
+        slab = torch.empty((len(want),) + tuple(out.shape), dtype=torch.float32, device=out.device)       # one allocation for every gradient
+        grads = [None] * (2 * L)
+        for i, k in enumerate(want):
+            grads[k] = slab[i]
+        _lib.check(_lib.lib().yt8m_scale_mix_bwd(L, _ptr_table(planes[:L]), _ptr_table(planes[L:]), _p(out), _p(g), _ptr_table(grads[:L]),
+                                                 _ptr_table(grads[L:]), out.shape[0], out.shape[1], _stream()))
+        return (None,) + tuple(grads)
+
+
+def scale_mix(ps, zs):
+    """out [B,V] = sum_l softmax over l of z_l [B,V] times p_l [B,V]: the LstmMultiscale plugins' per-label mix of their scales' sub-
+    predictions (Z/frame_level_models.py:2982-2985: tf.stack, tf.nn.softmax(dim=1), multiply, reduce_sum).  ps: L tensors [B,V]; zs: L
+    tensors [B,V] or one [L,B,V] tensor (taken apart into its L planes, no copy).  Differentiable in every plane.
+    YT8M_SCALE_MIX_FUSED (read at import): 0, the default, is the composed torch form; 1 is the fused kernel pair, which CPU tensors,
+    non-float32 tensors, L > 8 and shapes yt8m_scale_mix_supported refuses never take."""
+    ps = list(ps)
+    zs = list(zs.unbind(0)) if torch.is_tensor(zs) else list(zs)
+    L = len(ps)
+    if L < 1 or len(zs) != L:
+        raise ValueError("scale_mix: L >= 1 sub-predictions and as many mix logits, got %d and %d" % (L, len(zs)))
+    shape = tuple(ps[0].shape)
+    if len(shape) != 2 or any(tuple(t.shape) != shape for t in ps + zs):
+        raise ValueError("scale_mix: every plane must be [B, V] = %s" % (shape,))
+    fused = (SCALE_MIX_FUSED and L <= SCALE_MIX_MAX and all(t.is_cuda and t.dtype == torch.float32 for t in ps + zs)
+             and bool(_lib.lib().yt8m_scale_mix_supported(L, shape[0], shape[1])))
+    SCALE_MIX_CALLS["kernels" if fused else "composed"] += 1
+    if not fused:
+        return scale_mix_composed(ps, zs)
+    return _ScaleMix.apply(L, *ps, *zs)
+
+
+class _LinearGroup(torch.autograd.Function):
+    """y_k = x_k . W_k (+ b_k) for n products of one shape family, each direction one grouped launch (gemm_grouped): the forward
+    products, the weight gradients x_k^T . dy_k (role "dw") into the Variables' arena slots, and dx_k = dy_k . W_k^T for the inputs that
+    want one.  spec[k] = (W, index, b): W_k is W.data (index None) or the plane W.data[index] of a stacked Variable."""
+
+    @staticmethod
+    def forward(ctx, token, spec, *xs):
+        xs = [_f32c(x) for x in xs]
+        planes = [W.data if i is None else W.data[i] for W, i, _ in spec]
+        ys = gemm_grouped([dict(A=x, B=Wk, bias=None if b is None else b.data) for x, Wk, (_, _, b) in zip(xs, planes, spec)])
+        ctx.spec = spec
+        ctx.save_for_backward(*xs)
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        xs, spec = ctx.saved_tensors, ctx.spec
+        dys = [_f32c(dy) for dy in dys]
+        betas, items = {}, []
+        for x, dy, (W, i, b) in zip(xs, dys, spec):
+            if W.trainable and W.grad is not None:
+                if id(W) not in betas:                                   # the planes of one stacked Variable: one first write each
+                    betas[id(W)] = (W, W.grad_beta())
+                items.append(dict(A=x, B=dy, out=W.grad if i is None else W.grad[i], beta=betas[id(W)][1]))
+            if b is not None and b.trainable and b.grad is not None:
+                colsum(dy, b.grad.view(-1), beta=b.grad_beta())
+                b.grad_done()
+        if items:
+            gemm_grouped(items, transA=True, role="dw")
+        for W, _ in betas.values():
+            W.grad_done()
+        dxs = [None] * len(xs)
+        want = [k for k in range(len(xs)) if ctx.needs_input_grad[2 + k]]
+        if want:
+            outs = gemm_grouped([dict(A=dys[k], B=spec[k][0].data if spec[k][1] is None else spec[k][0].data[spec[k][1]]) for k in want],
+                                transB=True)
+            for k, dx in zip(want, outs):
+                dxs[k] = dx
+        return (None, None) + tuple(dxs)
+
+
+def linear_group(xs, spec):
+    """[x_k . W_k (+ b_k)] for spec[k] = (W, index, b) (see _LinearGroup): n fully-connected products as one grouped launch per
+    direction.  CPU tensors take torch.matmul on the Variables as tensors (host tests; the device never does)."""
+    xs = list(xs)
+    if not xs[0].is_cuda:
+        ys = []
+        for x, (W, i, b) in zip(xs, spec):
+            Wt = as_tensor(W)
+            y = x @ (Wt if i is None else Wt[i])
+            ys.append(y if b is None else y + as_tensor(b))
+        return ys
+    return list(_LinearGroup.apply(_token(spec[0][0]._graph), tuple(spec), *xs))
 
 
 # 0: ens_combine / ens_moments compose torch ops; anything else (the default): the fused kernels of csrc/ensemble.hip where the input is a

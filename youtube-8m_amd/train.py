@@ -33,7 +33,8 @@ DEFINE_bool("fold_dequant", True, "Hand raw uint8 frames to models that declare 
 # W/train.py:53-64 distillation inputs: a second model's predictions arrive with the batch.
 # --distillation_as_input hands them to create_model as distillation_predictions; the plugins that read them (the others ignore the
 # keyword): DistillchainDeepCombineChainModel (video level), DistillchainLstmParallelFinaloutputModel, DistillchainCnnDeepCombineChainModel,
-# DistillchainLstmAttentionMaxPoolingModel, DistillchainLstmCnnDeepCombineChainModel, DistillchainMultiscaleCnnLstmModel.
+# DistillchainLstmAttentionMaxPoolingModel, DistillchainLstmCnnDeepCombineChainModel, DistillchainMultiscaleCnnLstmModel,
+# LstmMultiscaleDitillChainModel.
 DEFINE_bool("distillation_features", False, "If set, *DistillationFeatureReader will be used, the feature must contains the "
             "added distillation_predictions features.")
 DEFINE_integer("distillation_type", 0, "Type of distillation, options are 1 and 2.")
@@ -125,9 +126,11 @@ class TrainGraph(object):
 
     # ---- forward -----------------------------------------------------------------------------------
     def forward(self, model_input_raw, labels_batch=None, num_frames=None, is_training=True, fuse_loss=True,
-                distillation_predictions=None, transformed=False):
+                distillation_predictions=None, transformed=False, train_step=False):
         """transformed: model_input_raw already went through the feature transformer (step() after an augmenter that folds it).
-        The data augmenter never runs here: forward(is_training=False), eval and inference see the batch as it is."""
+        The data augmenter never runs here: forward(is_training=False), eval and inference see the batch as it is.
+        train_step: the result feeds step()'s backward pass; a model that trains on "prediction_frames" (below) then builds its
+        "predictions", which receive no gradient, without an autograd graph."""
         g = set_default_graph(self.graph)
         g.begin_step()
         model_input, num_frames = (model_input_raw, num_frames) if transformed else self._transform(model_input_raw, num_frames)
@@ -137,6 +140,8 @@ class TrainGraph(object):
         if FLAGS.dropout:                                         # W/train.py:359-369; the keep_prob placeholder defaults to
             kw["dropout"] = True                                  # 1.0 and is fed FLAGS.keep_prob by the training loop (:569)
             kw["keep_prob"] = float(FLAGS.keep_prob) if is_training else 1.0
+        if train_step and getattr(self.model, "trains_on_prediction_frames", False):
+            kw["predictions_no_grad"] = True
         noise_level = float(FLAGS.noise_level) if (FLAGS.noise_level > 0 and is_training) else None      # :349-352, :571
         result = self.model.create_model(model_input, num_frames=num_frames, vocab_size=FLAGS.num_classes
                                          if labels_batch is None else labels_batch.shape[1],
@@ -145,9 +150,29 @@ class TrainGraph(object):
         return result
 
     def _label_loss(self, result, labels, weights):
+        if "prediction_frames" in result:
+            return self._frames_loss(result["prediction_frames"], labels, weights)
         if self.multitask:                                        # W/train.py:394-413
             return self.label_loss_fn.calculate_loss(result["predictions"], result["support_predictions"], labels, weights=weights)
         return self.label_loss_fn.calculate_loss(result["predictions"], labels, weights=weights)
+
+    def _frames_loss(self, prediction_frames, labels, weights):
+        """The Z training rule (Z/train.py:359-379, :418): a result that holds "prediction_frames" [B L, V] (row b L + l: the l-th
+        sub-prediction for video b) is trained on them alone -- label_loss on "predictions" times 0.0, plus
+        calculate_loss(prediction_frames, labels tiled L times per video).  The labels (and per-video weights) are tiled as the
+        reference tiles them, row b L + l = video b: one loss launch over the B L rows for every --label_loss, the batch-agreement pair
+        (whose statistics span the rows, and whose N stays --batch_size) included."""
+        if self.multitask:
+            raise ValueError("--multitask takes its loss from predictions and support_predictions; a model that returns "
+                             "prediction_frames is trained on those alone (Z/train.py:359-379) and has no such combination")
+        rows, B = prediction_frames.shape[0], labels.shape[0]
+        if B == 0 or rows % B != 0:
+            raise ValueError("prediction_frames has %d rows for %d videos: not a whole number of rows per video" % (rows, B))
+        L = rows // B
+        labels_frames = labels if L == 1 else labels.repeat_interleave(L, dim=0)
+        if weights is not None and L != 1:
+            weights = weights.repeat_interleave(L, dim=0)
+        return self.label_loss_fn.calculate_loss(prediction_frames, labels_frames, weights=weights)
 
     def loss(self, result, labels_batch, weights=None, distill_labels_batch=None):
         """W/train.py:384-430: a model-provided "loss" wins; otherwise the label loss, optionally blended with / replaced by
@@ -200,8 +225,11 @@ class TrainGraph(object):
         # and it computes exactly CrossEntropyLoss: any other configured loss (TrainGraph(label_loss_fn=...), multitask) wins
         fuse = (weights is None and distill is None and not self.multitask
                 and type(self.label_loss_fn) is losses.CrossEntropyLoss)
+        # a model trained on its prediction_frames (Z/train.py:359-379) is told that this forward pass feeds a training step (only such a
+        # model: subclasses' forward() keep their signature)
+        frames_kw = {"train_step": True} if getattr(self.model, "trains_on_prediction_frames", False) else {}
         result = self.forward(model_input_raw, labels_batch, num_frames, fuse_loss=fuse,
-                              distillation_predictions=distill if FLAGS.distillation_as_input else None, transformed=transformed)
+                              distillation_predictions=distill if FLAGS.distillation_as_input else None, transformed=transformed, **frames_kw)
         label_loss = self.loss(result, labels_batch, weights, distill)
         # W/train.py:435-456: a model may hand back its own "regularization_loss" (added to the final loss with the
         # --regularization_penalty weight; the slim l2 regularisers are applied as l2*w inside the optimiser pass) and
@@ -219,7 +247,7 @@ class TrainGraph(object):
             # weights on every rank (once per run; with identical seeds the values do not change).
             g._rng_step -= 1                                      # the same forward pass again: the same random-op seeds
             result = self.forward(model_input_raw, labels_batch, num_frames, fuse_loss=fuse,
-                                  distillation_predictions=distill if FLAGS.distillation_as_input else None, transformed=transformed)
+                                  distillation_predictions=distill if FLAGS.distillation_as_input else None, transformed=transformed, **frames_kw)
             final_loss = label_loss = self.loss(result, labels_batch, weights, distill)
             if "regularization_loss" in result and torch.is_tensor(result["regularization_loss"]) \
                     and result["regularization_loss"].requires_grad and self.reg_penalty != 0:
