@@ -52,15 +52,16 @@ def _lengths(B, F, shift):
 
 
 # ---- through the C ABI on given hoisted inputs: the two step kernels apart from the hoisted GEMMs ------------------------------------
-ABI_CASES = [(3, 256, 5, 2, 0, 0), (5, 2048, 4, 16, 0, 0), (128, 1024, 6, 2, 64, 2)]
+ABI_CASES = [(3, 256, 5, 2, 0, 0), (5, 2048, 4, 16, 0, 0), (128, 1024, 6, 2, 64, 2), (4, 512, 3, 2, 0, 1)]
 PAD = 7.25          # what the caller leaves in the padding columns of zs / dzs
 
 
 @pytest.mark.parametrize("B,H,F,lds,ldu_extra,shift", ABI_CASES)
 def test_step_kernels_match_fp64_through_the_c_abi(dev, monkeypatch, B, H, F, lds, ldu_extra, shift):
     """yt8m_gate_lstm_layer_fwd / _bwd at (B, H, F) = (3, 256, 5): one unit per thread, odd B; (5, 2048, 4): the widest supported, lds = 16;
-    (128, 1024, 6): the plugins' shape, ldu = 2H + 64.  o, g, i, f, every hs[t] and cs[t], c_last, dzv and dzs against fp64; with dout
-    null, dzv and dzs are exactly zero at and past each row's num_frames; the padding columns of zs and dzs keep the caller's bits.
+    (128, 1024, 6): the plugins' shape, ldu = 2H + 64; (4, 512, 3): two units per thread.  o, g, i, f, every hs[t] and cs[t], c_last,
+    dzv and dzs against fp64; with dout null, dzv and dzs are exactly zero at and past each row's num_frames; the padding columns of
+    zs and dzs keep the caller's bits.
     Measured on an MI355X: see DESIGN_LOG.md "Scalar-gate LSTM"."""
     lib = L.lib()
     assert lib.yt8m_gate_lstm_supported(B, H)

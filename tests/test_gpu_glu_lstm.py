@@ -181,14 +181,16 @@ def _run_abi_case(dev, monkeypatch, B, H, F, D, lds, ldu_extra, shift, u8, windo
     return nf, fwd, grads, ref[torch.float64]
 
 
-ABI_CASES = [(3, 256, 5, 64, 8, 0, 0, False, False), (5, 2048, 4, 1152, 16, 0, 0, True, True), (128, 1024, 6, 1024, 8, 64, 2, False, True)]
+ABI_CASES = [(3, 256, 5, 64, 8, 0, 0, False, False), (5, 2048, 4, 1152, 16, 0, 0, True, True), (128, 1024, 6, 1024, 8, 64, 2, False, True),
+             (4, 512, 3, 64, 8, 0, 1, False, False)]
 
 
 @pytest.mark.parametrize("B,H,F,D,lds,ldu_extra,shift,u8,windows", ABI_CASES)
 def test_step_kernels_match_fp64_through_the_c_abi(dev, monkeypatch, B, H, F, D, lds, ldu_extra, shift, u8, windows):
     """yt8m_glu_lstm_layer_fwd / _bwd at (B, H, F, D, lds) = (3, 256, 5, 64, 8): one unit per thread, odd B, float frames, zv and pv
     matrices of their own; (5, 2048, 4, 1152, 16): the widest supported, the reader's bytes, two passes of the loop over D, padding
-    columns in zs / dzs, windows of one 4H-wide tensor; (128, 1024, 6, 1024, 8): the plugins' shape, ldu = 2H + 64.  Lengths mix F,
+    columns in zs / dzs, windows of one 4H-wide tensor; (128, 1024, 6, 1024, 8): the plugins' shape, ldu = 2H + 64;
+    (4, 512, 3, 64, 8): two units per thread.  Lengths mix F,
     F - 1, F / 2, 1 and 0.  Every tape (o, g, the four scalar gates, hs, cs, xm, n2, qv, qs), c_last and every emitted gradient block
     (dzv, dpv, dzs, dps, dx_direct on float frames) against fp64; with dout null, every emitted gradient is exactly zero at and past
     each row's num_frames; the padding columns keep the caller's bits; x.V* is read only."""

@@ -11,11 +11,6 @@
 
 namespace {
 
-__device__ __forceinline__ int64_t clamp_frames(const int32_t* nf, int64_t b, int64_t F) {
-  const int64_t n = nf[b];
-  return n < 0 ? 0 : (n > F ? F : n);
-}
-
 __device__ __forceinline__ int64_t half_len(int64_t n) { return n / 2 > 1 ? n / 2 : 1; }
 
 // [B,F,D] -> [3B,F,D]: V = a 16-byte vector (rows of a multiple of 16 bytes) or one element; nv = V units per frame row.  A grid-stride

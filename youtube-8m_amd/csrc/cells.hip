@@ -107,29 +107,9 @@ __global__ __launch_bounds__(256) void gru_bwd2_kernel(const float* __restrict__
 }
 
 // ========================================= LayerNormBasicLSTMCell ==========================================================
-// Gate non-linearities on v_exp_f32 / v_rcp_f32, as the persistent recurrences use them (<= ~1.5e-7 absolute per value against libm's
-// expf / tanhf, whose range checks and branches were most of these kernels' ~2 400 instructions on ONE wave per SIMD: round 6).
-__device__ __forceinline__ float ln_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
-__device__ __forceinline__ float ln_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.8853900817779268f * x)); }
-constexpr int LN_PT = 8;                       // units per thread: H <= 256 * LN_PT
+// Gate non-linearities: common.h's fast_sigmoid / fast_tanh, as the persistent recurrences use them (libm's expf / tanhf, with their
+// range checks and branches, were most of these kernels' ~2 400 instructions on ONE wave per SIMD: round 6).
 constexpr float LN_EPS = 1e-12f;               // tf.contrib.layers.layer_norm variance_epsilon
-
-struct F4 { float v[4]; };
-__device__ __forceinline__ F4 block_sum4_256(F4 a, float* red /* 16 floats */) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) a.v[k] = wave_sum(a.v[k]);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) red[w * 4 + k] = a.v[k];
-  }
-  __syncthreads();
-  F4 o;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) o.v[k] = red[k] + red[4 + k] + red[8 + k] + red[12 + k];
-  return o;
-}
 
 // one workgroup per batch row.  z row [4H] stays RAW (pre-normalisation): backward recomputes from it and `stats`.
 // Round 6: the kernel is a chain of dependent round trips on one wave per SIMD (128 workgroups at B = 128), so EVERYTHING it reads --
@@ -174,24 +154,24 @@ __global__ __launch_bounds__(256) void lnlstm_fwd_kernel(const float* __restrict
     }
     return;
   }
-  F4 s = {{0.f, 0.f, 0.f, 0.f}};
+  float mean[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int p = 0; p < PT; ++p)
 #pragma unroll
-    for (int g = 0; g < 4; ++g) s.v[g] += zv[g][p];
-  F4 mean = block_sum4_256(s, red);
+    for (int g = 0; g < 4; ++g) mean[g] += zv[g][p];
+  block_sums_256<4>(mean, red);
 #pragma unroll
-  for (int g = 0; g < 4; ++g) mean.v[g] *= invH;
-  F4 q = {{0.f, 0.f, 0.f, 0.f}};
+  for (int g = 0; g < 4; ++g) mean[g] *= invH;
+  float rstd[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int p = 0; p < PT; ++p) {
     const int64_t h = tid + p * 256;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) { const float d = zv[g][p] - mean.v[g]; if (h < H) q.v[g] += d * d; }
+    for (int g = 0; g < 4; ++g) { const float d = zv[g][p] - mean[g]; if (h < H) rstd[g] += d * d; }
   }
-  F4 rstd = block_sum4_256(q, red);
+  block_sums_256<4>(rstd, red);
 #pragma unroll
-  for (int g = 0; g < 4; ++g) rstd.v[g] = rsqrtf(rstd.v[g] * invH + LN_EPS);
+  for (int g = 0; g < 4; ++g) rstd[g] = rsqrtf(rstd[g] * invH + LN_EPS);
   float cp[PT], og[PT];
   float sc = 0.f;
 #pragma unroll
@@ -201,11 +181,11 @@ __global__ __launch_bounds__(256) void lnlstm_fwd_kernel(const float* __restrict
     if (h < H) {
       float y[4];
 #pragma unroll
-      for (int g = 0; g < 4; ++g) y[g] = (zv[g][p] - mean.v[g]) * rstd.v[g] * gm[g][p] + bt[g][p];
-      const float i = ln_sigmoid(y[0]);
-      const float gg = ln_tanh(y[1]) * keep_scale((uint64_t)(((int64_t)t * B + b) * H + h), seed, keep);
-      const float f = ln_sigmoid(y[2] + fb);
-      og[p] = ln_sigmoid(y[3]);
+      for (int g = 0; g < 4; ++g) y[g] = (zv[g][p] - mean[g]) * rstd[g] * gm[g][p] + bt[g][p];
+      const float i = fast_sigmoid(y[0]);
+      const float gg = fast_tanh(y[1]) * keep_scale((uint64_t)(((int64_t)t * B + b) * H + h), seed, keep);
+      const float f = fast_sigmoid(y[2] + fb);
+      og[p] = fast_sigmoid(y[3]);
       cp[p] = cpv[p] * f + i * gg;
       sc += cp[p];
     }
@@ -220,13 +200,13 @@ __global__ __launch_bounds__(256) void lnlstm_fwd_kernel(const float* __restrict
     const int64_t h = tid + p * 256;
     if (h < H) {
       const float cn = (cp[p] - mean_s) * rstd_s * gm[4][p] + bt[4][p];
-      const float hn = ln_tanh(cn) * og[p];
+      const float hn = fast_tanh(cn) * og[p];
       c_new[b * H + h] = cn;
       h_new[b * H + h] = hn;
       if (out) out[b * H + h] = hn;
     }
   }
-  if (tid < 4) { stats[b * 10 + tid * 2] = mean.v[tid]; stats[b * 10 + tid * 2 + 1] = rstd.v[tid]; }
+  if (tid < 4) { stats[b * 10 + tid * 2] = mean[tid]; stats[b * 10 + tid * 2 + 1] = rstd[tid]; }
   if (tid == 4) { stats[b * 10 + 8] = mean_s; stats[b * 10 + 9] = rstd_s; }
 }
 
@@ -298,15 +278,15 @@ __global__ __launch_bounds__(256) void lnlstm_bwd_kernel(const float* __restrict
         n[g][p] = (zv[g][p] - mean[g]) * rstd[g];
         y[g] = n[g][p] * gm[g][p] + bt[g][p];
       }
-      iv[p] = ln_sigmoid(y[0]);
-      tj[p] = ln_tanh(y[1]);
+      iv[p] = fast_sigmoid(y[0]);
+      tj[p] = fast_tanh(y[1]);
       ks[p] = keep_scale((uint64_t)(((int64_t)t * B + b) * H + h), seed, keep);
       gv[p] = tj[p] * ks[p];
-      fv[p] = ln_sigmoid(y[2] + fb);
-      const float o = ln_sigmoid(y[3]);
+      fv[p] = fast_sigmoid(y[2] + fb);
+      const float o = fast_sigmoid(y[3]);
       const float cpre = cpv[p] * fv[p] + iv[p] * gv[p];
       ns[p] = (cpre - mean[4]) * rstd[4];
-      const float tc = ln_tanh(cnv[p]);
+      const float tc = fast_tanh(cnv[p]);
       const float dh = dhv[p];
       dy[3][p] = dh * tc * o * (1.0f - o);
       const float dcn = dcv[p] + dh * o * (1.0f - tc * tc);
@@ -317,10 +297,10 @@ __global__ __launch_bounds__(256) void lnlstm_bwd_kernel(const float* __restrict
       s2 += dns[p] * ns[p];
     }
   }
-  F4 a = {{s1, s2, 0.f, 0.f}};
-  a = block_sum4_256(a, red);
-  const float m1 = a.v[0] * invH, m2 = a.v[1] * invH;
-  F4 t1 = {{0.f, 0.f, 0.f, 0.f}}, t2 = {{0.f, 0.f, 0.f, 0.f}};
+  float a[4] = {s1, s2, 0.f, 0.f};
+  block_sums_256<4>(a, red);
+  const float m1 = a[0] * invH, m2 = a[1] * invH;
+  float t1[4] = {0.f, 0.f, 0.f, 0.f}, t2[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int p = 0; p < PT; ++p) {
     const int64_t h = tid + p * 256;
@@ -336,20 +316,20 @@ __global__ __launch_bounds__(256) void lnlstm_bwd_kernel(const float* __restrict
         dyb[b * 5 * H + g * H + h] = dy[g][p];
         dyg[b * 5 * H + g * H + h] = dy[g][p] * n[g][p];
         dy[g][p] *= gm[g][p];                         // now d(normalised)
-        t1.v[g] += dy[g][p];
-        t2.v[g] += dy[g][p] * n[g][p];
+        t1[g] += dy[g][p];
+        t2[g] += dy[g][p] * n[g][p];
       }
     }
   }
-  t1 = block_sum4_256(t1, red);
-  t2 = block_sum4_256(t2, red);
+  block_sums_256<4>(t1, red);
+  block_sums_256<4>(t2, red);
 #pragma unroll
   for (int p = 0; p < PT; ++p) {
     const int64_t h = tid + p * 256;
     if (h < H) {
 #pragma unroll
       for (int g = 0; g < 4; ++g)
-        dz[b * 4 * H + g * H + h] = rstd[g] * (dy[g][p] - t1.v[g] * invH - n[g][p] * t2.v[g] * invH);
+        dz[b * 4 * H + g * H + h] = rstd[g] * (dy[g][p] - t1[g] * invH - n[g][p] * t2[g] * invH);
     }
   }
 }
@@ -360,7 +340,7 @@ using namespace yt8m;
 
 static bool packed_ok(int64_t B, int64_t H, int G, void* ws, int64_t ws_bytes) {
   static const bool off = getenv("YT8M_NO_PACKED_CELLS") != nullptr;      // A/B switch for tools/ and tests
-  return !off && ws && cell_packed_supported(B, H) && ws_bytes >= (int64_t)sizeof(float) * H * G * H;
+  return !off && packed_fits(B, H, G, ws, ws_bytes);
 }
 
 extern "C" int yt8m_gru_layer_fwd(float* zg, float* zc, const float* Wg_h, int64_t ldg, const float* Wc_h, int64_t ldc, float* hs,
@@ -468,7 +448,7 @@ extern "C" int yt8m_lnlstm_layer_fwd(float* z, const float* Wh, int64_t ldw, con
                                      float forget_bias, float keep_prob, uint64_t seed, void* gemm_workspace,
                                      int64_t gemm_workspace_bytes, yt8m_stream_t stream) {
   YT8M_REQUIRE(F >= 0 && B >= 0 && H >= 0, YT8M_E_SHAPE, "negative dimension");
-  YT8M_REQUIRE(H <= 256 * LN_PT, YT8M_E_SHAPE, "layer-norm LSTM supports H <= 2048");
+  YT8M_REQUIRE(H <= 256 * ROW_PT, YT8M_E_SHAPE, "layer-norm LSTM supports H <= 2048");
   YT8M_REQUIRE(keep_prob > 0.f && keep_prob <= 1.f, YT8M_E_BADARG, "keep_prob must be in (0, 1]");
   if (F * B * H == 0) return YT8M_OK;
   YT8M_REQUIRE(z && Wh && gamma && beta && stats && cs && hs, YT8M_E_BADARG, "null operand");
@@ -478,8 +458,7 @@ extern "C" int yt8m_lnlstm_layer_fwd(float* z, const float* Wh, int64_t ldw, con
   const bool packed = packed_ok(B, H, 4, gemm_workspace, gemm_workspace_bytes);
   float* Wp = packed ? static_cast<float*>(gemm_workspace) : nullptr;
   if (packed) {
-    ProfScope prof(F_LSTM, s);
-    int rc = cell_pack(Wh, ldw, Wp, nullptr, H, 4, s);
+    int rc = cell_pack_scoped(Wh, ldw, Wp, nullptr, H, 4, s);
     if (rc != YT8M_OK) return rc;
   }
   const StepProduct rec = {Wh, ldw, Wp, nullptr, 4, B, H, gemm_workspace, gemm_workspace_bytes, stream};
@@ -488,7 +467,7 @@ extern "C" int yt8m_lnlstm_layer_fwd(float* z, const float* Wh, int64_t ldw, con
     int rc = rec.add_hW(hs + t * BH, zt);
     if (rc != YT8M_OK) return rc;
     ProfScope prof(F_LSTM, s);
-    auto kfn = H <= 512 ? lnlstm_fwd_kernel<2> : H <= 1024 ? lnlstm_fwd_kernel<4> : lnlstm_fwd_kernel<LN_PT>;
+    auto kfn = YT8M_ROW_KERNEL(lnlstm_fwd_kernel, H, 2);
     hipLaunchKernelGGL(kfn, dim3((unsigned)B), dim3(256), 0, s, zt, gamma, beta, stats + t * B * 10, cs + t * BH,
                        hs + t * BH, cs + (t + 1) * BH, hs + (t + 1) * BH, out ? out + t * BH : nullptr, num_frames, (int)t, B, H,
                        forget_bias, keep_prob, seed);
@@ -503,7 +482,7 @@ extern "C" int yt8m_lnlstm_layer_bwd(const float* z, const float* Wh, int64_t ld
                                      float keep_prob, uint64_t seed, void* gemm_workspace, int64_t gemm_workspace_bytes,
                                      yt8m_stream_t stream) {
   YT8M_REQUIRE(F >= 0 && B >= 0 && H >= 0, YT8M_E_SHAPE, "negative dimension");
-  YT8M_REQUIRE(H <= 256 * LN_PT, YT8M_E_SHAPE, "layer-norm LSTM supports H <= 2048");
+  YT8M_REQUIRE(H <= 256 * ROW_PT, YT8M_E_SHAPE, "layer-norm LSTM supports H <= 2048");
   YT8M_REQUIRE(keep_prob > 0.f && keep_prob <= 1.f, YT8M_E_BADARG, "keep_prob must be in (0, 1]");
   if (F * B * H == 0) return YT8M_OK;
   YT8M_REQUIRE(z && Wh && gamma && beta && stats && cs && dz && dyb && dyg && work, YT8M_E_BADARG, "null operand");
@@ -516,8 +495,7 @@ extern "C" int yt8m_lnlstm_layer_bwd(const float* z, const float* Wh, int64_t ld
   const bool packed = packed_ok(B, H, 4, gemm_workspace, gemm_workspace_bytes);
   float* Wq = packed ? static_cast<float*>(gemm_workspace) : nullptr;
   if (packed) {
-    ProfScope prof(F_LSTM, s);
-    int rc = cell_pack(Wh, ldw, nullptr, Wq, H, 4, s);
+    int rc = cell_pack_scoped(Wh, ldw, nullptr, Wq, H, 4, s);
     if (rc != YT8M_OK) return rc;
   }
   const StepProduct rec = {Wh, ldw, nullptr, Wq, 4, B, H, gemm_workspace, gemm_workspace_bytes, stream};
@@ -525,7 +503,7 @@ extern "C" int yt8m_lnlstm_layer_bwd(const float* z, const float* Wh, int64_t ld
     float* dzt = dz + t * B * 4 * H;
     {
       ProfScope prof(F_LSTM, s);
-      auto kfn = H <= 512 ? lnlstm_bwd_kernel<2> : H <= 1024 ? lnlstm_bwd_kernel<4> : lnlstm_bwd_kernel<LN_PT>;
+      auto kfn = YT8M_ROW_KERNEL(lnlstm_bwd_kernel, H, 2);
       hipLaunchKernelGGL(kfn, dim3((unsigned)B), dim3(256), 0, s, z + t * B * 4 * H, gamma, beta,
                          stats + t * B * 10, cs + t * BH, cs + (t + 1) * BH, g.dh_cur, g.dc_cur, dout ? dout + t * BH : nullptr, dzt,
                          dyb + t * B * 5 * H, dyg + t * B * 5 * H, g.dc_prev, g.dh_prev, num_frames, (int)t, B, H, forget_bias,

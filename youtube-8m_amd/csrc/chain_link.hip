@@ -44,8 +44,6 @@ __device__ __forceinline__ void normal4_at(int64_t e0, uint64_t seed, float n[4]
   for (int k = 0; k < 4; ++k) n[k] = normal_at(e0 + k, seed);
 }
 
-__device__ __forceinline__ float link_r(float ss, float eps, float reps) { return ss > eps ? rsqrtf(ss) : reps; }
-
 // VEC: cols % 4 == 0 and z, y 16-byte aligned (checked by the caller).  reps = 1 / sqrt(eps), rounded once on the host.
 template <bool VEC>
 __global__ __launch_bounds__(256) void chain_link_fwd_kernel(int elu_, const float* __restrict__ z, float* __restrict__ y,
@@ -201,11 +199,6 @@ __global__ __launch_bounds__(256) void chain_link_bwd_kernel(int elu_, const flo
   for (int64_t c = lane; c < cols; c += 64) dr[c] = (unit ? R * (gr[c] - yr[c] * k) : R * gr[c]) * link_act_grad(elu, zr[c]);
 }
 
-inline bool aligned16(const void* a, const void* b, const void* c = nullptr, const void* d = nullptr) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-           reinterpret_cast<uintptr_t>(d)) & 15) == 0;
-}
-
 }  // namespace
 
 using namespace yt8m;
@@ -222,7 +215,7 @@ extern "C" int yt8m_chain_link_fwd(int act, const float* z, float* y, float* rin
   const float reps = (float)(1.0 / sqrt((double)eps));
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   const int elu = act == YT8M_ACT_ELU;
-  if ((cols & 3) == 0 && aligned16(z, y))
+  if ((cols & 3) == 0 && aligned16(z) && aligned16(y))
     hipLaunchKernelGGL(chain_link_fwd_kernel<true>, grid, block, 0, s, elu, z, y, rinv, rows, cols, eps, reps, stddev, seed, offset);
   else
     hipLaunchKernelGGL(chain_link_fwd_kernel<false>, grid, block, 0, s, elu, z, y, rinv, rows, cols, eps, reps, stddev, seed, offset);
@@ -240,7 +233,7 @@ extern "C" int yt8m_chain_link_bwd(int act, const float* z, const float* y, cons
   ProfScope prof(F_ELEMENTWISE, s);
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   const int elu = act == YT8M_ACT_ELU;
-  if ((cols & 3) == 0 && aligned16(z, y, dy, dz))
+  if ((cols & 3) == 0 && aligned16(z) && aligned16(y) && aligned16(dy) && aligned16(dz))
     hipLaunchKernelGGL(chain_link_bwd_kernel<true>, grid, block, 0, s, elu, z, y, rinv, dy, dz, rows, cols);
   else
     hipLaunchKernelGGL(chain_link_bwd_kernel<false>, grid, block, 0, s, elu, z, y, rinv, dy, dz, rows, cols);

@@ -1,4 +1,4 @@
-// common.h -- shared host-side helpers for libyt8m_hip.so (gfx950 only; no CUDA/HIP dual paths).
+// common.h -- shared host and device helpers for libyt8m_hip.so (gfx950 only; no CUDA/HIP dual paths).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -103,6 +103,11 @@ inline int launch_status(const char* what) {
 
 }  // namespace yt8m
 
+// ---- small host helpers (global, like the device helpers below: the kernel files use them inside their own namespaces) ------
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }      // a null pointer counts as aligned
+inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline int64_t up4(int64_t a) { return (a + 3) & ~(int64_t)3; }
+
 // ---- device helpers ---------------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -131,4 +136,59 @@ __device__ __forceinline__ float block_max_256(float v, float* red) {
   __syncthreads();
   return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
+// N block-wide sums for blockDim.x == 256 on one barrier pair: the waves' partials are added in the order 0, 1, 2, 3; the results are
+// valid in all threads
+template <int N>
+__device__ __forceinline__ void block_sums_256(float (&v)[N], float* red /* 4 N floats of LDS */) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = wave_sum(v[k]);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) red[w * N + k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = red[k] + red[N + k] + red[2 * N + k] + red[3 * N + k];
+}
 __device__ __forceinline__ float sigmoidf_(float z) { return 1.0f / (1.0f + expf(-z)); }
+
+// Gate non-linearities of the persistent kernels and of the row-per-workgroup cells: v_exp_f32 / v_rcp_f32 (1 ulp each) instead of
+// the libm-exact expf / tanhf of the per-step kernels -- the epilogue is a single wave's dependent chain on the critical path of the
+// state exchange, and the exact forms cost ~10x the instructions.  Absolute error <= ~1.5e-7 per value (checked against the exact
+// kernels and the fp64 oracle by the parity tests; north_star tolerance 1e-3).
+__device__ __forceinline__ float fast_sigmoid(float x) {
+  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
+}
+__device__ __forceinline__ float fast_tanh(float x) {
+  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.8853900817779268f * x));
+}
+
+// VW floats at p: one 16-byte access (VW = 4; p 16-byte aligned) or a single element (VW = 1)
+template <int VW>
+__device__ __forceinline__ void ldv(const float* p, float (&r)[VW]) {
+  if constexpr (VW == 4) {
+    const float4 q = *reinterpret_cast<const float4*>(p);
+    r[0] = q.x; r[1] = q.y; r[2] = q.z; r[3] = q.w;
+  } else {
+    r[0] = *p;
+  }
+}
+template <int VW>
+__device__ __forceinline__ void stv(float* p, const float (&r)[VW]) {
+  if constexpr (VW == 4) *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
+  else *p = r[0];
+}
+
+// num_frames[b] clamped to [0, F]
+__device__ __forceinline__ int64_t clamp_frames(const int32_t* nf, int64_t b, int64_t F) {
+  const int64_t n = nf[b];
+  return n < 0 ? 0 : (n > F ? F : n);
+}
+
+// the reciprocal of an l2-normalisation: 1 / sqrt(max(ss, eps)), with reps = 1 / sqrt(eps) rounded once on the host
+__device__ __forceinline__ float link_r(float ss, float eps, float reps) { return ss > eps ? rsqrtf(ss) : reps; }
+
+// Dequantize (W/utils.py:23-38) of the reader's bytes: x = a0 q + c0
+constexpr float U8_A0 = 4.0f / 255.0f, U8_C0 = 4.0f / 512.0f - 2.0f;

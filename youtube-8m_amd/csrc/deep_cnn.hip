@@ -133,7 +133,6 @@ __global__ __launch_bounds__(256) void dc_max_pool2_bwd_kernel(const float* __re
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 }  // namespace yt8m

@@ -31,22 +31,6 @@ constexpr int BWD_MAX_CHUNKS = 8;
 constexpr int BWD_MIN_CHUNK = 16;
 constexpr float LOGIT_EPS = 1e-5f;
 
-template <int VW>
-__device__ __forceinline__ void ld(const float* p, float (&r)[VW]) {
-  if constexpr (VW == 4) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    r[0] = q.x; r[1] = q.y; r[2] = q.z; r[3] = q.w;
-  } else {
-    r[0] = *p;
-  }
-}
-
-template <int VW>
-__device__ __forceinline__ void st(float* p, const float (&r)[VW]) {
-  if constexpr (VW == 4) *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
-  else *p = r[0];
-}
-
 template <bool LOGIT>
 __device__ __forceinline__ float xform(float x) {
   if (LOGIT) return logf(__fdividef(LOGIT_EPS + x, (1.0f + LOGIT_EPS) - x));
@@ -75,10 +59,10 @@ __global__ __launch_bounds__(64) void ens_fwd_kernel(const float* __restrict__ x
   for (int k = 0; k < M; ++k) {
     float w[J][VW];
 #pragma unroll
-    for (int j = 0; j < J; ++j) ld<VW>(Wt + j * MV + (size_t)k * V + v0, w[j]);
+    for (int j = 0; j < J; ++j) ldv<VW>(Wt + j * MV + (size_t)k * V + v0, w[j]);
     float xv[FWD_ROWS][VW];
 #pragma unroll
-    for (int i = 0; i < FWD_ROWS; ++i) ld<VW>(x + k * BV + (size_t)row[i] * V + v0, xv[i]);
+    for (int i = 0; i < FWD_ROWS; ++i) ldv<VW>(x + k * BV + (size_t)row[i] * V + v0, xv[i]);
 #pragma unroll
     for (int i = 0; i < FWD_ROWS; ++i) {
 #pragma unroll
@@ -112,10 +96,10 @@ __global__ __launch_bounds__(64) void ens_fwd_kernel(const float* __restrict__ x
         o[c] = (float)(acc[i][c] / s[i][c]);
         l[c] = (float)(1.0 / s[i][c]);
       }
-      st<VW>(out + (size_t)row[i] * V + v0, o);
+      stv<VW>(out + (size_t)row[i] * V + v0, o);
       if (stat) {
-        st<VW>(stat + (size_t)row[i] * V + v0, m[i]);
-        st<VW>(stat + BV + (size_t)row[i] * V + v0, l);
+        stv<VW>(stat + (size_t)row[i] * V + v0, m[i]);
+        stv<VW>(stat + BV + (size_t)row[i] * V + v0, l);
       }
     }
   }
@@ -139,19 +123,19 @@ __global__ __launch_bounds__(64) void ens_bwd_kernel(const float* __restrict__ x
   for (int j = 0; j < J; ++j)
 #pragma unroll
     for (int kk = 0; kk < KR; ++kk) {
-      ld<VW>(Wt + j * MV + (size_t)(k0 + min(kk, nk - 1)) * V + v0, w[j][kk]);
+      ldv<VW>(Wt + j * MV + (size_t)(k0 + min(kk, nk - 1)) * V + v0, w[j][kk]);
 #pragma unroll
       for (int c = 0; c < VW; ++c) a[j][kk][c] = 0.0f;
     }
   const size_t part = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
   for (int b = b0; b < b1; ++b) {
     float go[VW], mx[VW], is[VW], ou[VW], xv[KR][VW], g[J], pg[J];
-    ld<VW>(dout + (size_t)b * V + v0, go);
-    ld<VW>(stat + (size_t)b * V + v0, mx);
-    ld<VW>(stat + BV + (size_t)b * V + v0, is);
-    ld<VW>(out + (size_t)b * V + v0, ou);
+    ldv<VW>(dout + (size_t)b * V + v0, go);
+    ldv<VW>(stat + (size_t)b * V + v0, mx);
+    ldv<VW>(stat + BV + (size_t)b * V + v0, is);
+    ldv<VW>(out + (size_t)b * V + v0, ou);
 #pragma unroll
-    for (int kk = 0; kk < KR; ++kk) ld<VW>(x + (size_t)(k0 + min(kk, nk - 1)) * BV + (size_t)b * V + v0, xv[kk]);
+    for (int kk = 0; kk < KR; ++kk) ldv<VW>(x + (size_t)(k0 + min(kk, nk - 1)) * BV + (size_t)b * V + v0, xv[kk]);
 #pragma unroll
     for (int j = 0; j < J; ++j) {
       g[j] = GATE ? gate[(size_t)b * J + j] : 1.0f;
@@ -190,7 +174,7 @@ __global__ __launch_bounds__(64) void ens_bwd_kernel(const float* __restrict__ x
     for (int j = 0; j < J; ++j)
 #pragma unroll
       for (int kk = 0; kk < KR; ++kk)
-        if (kk < nk) st<VW>(dWp + ((size_t)blockIdx.z * J + j) * MV + (size_t)(k0 + kk) * V + v0, a[j][kk]);
+        if (kk < nk) stv<VW>(dWp + ((size_t)blockIdx.z * J + j) * MV + (size_t)(k0 + kk) * V + v0, a[j][kk]);
   }
 }
 
@@ -215,7 +199,7 @@ __global__ __launch_bounds__(64) void ens_moments_kernel(const float* __restrict
   for (int c = 0; c < VW; ++c) s1[c] = s2[c] = 0.0;
   for (int k = 0; k < M; ++k) {
     float xv[VW];
-    ld<VW>(x + k * BV + at, xv);
+    ldv<VW>(x + k * BV + at, xv);
 #pragma unroll
     for (int c = 0; c < VW; ++c) {
       const double d = (double)xv[c];
@@ -230,18 +214,14 @@ __global__ __launch_bounds__(64) void ens_moments_kernel(const float* __restrict
     mu[c] = (float)mean64;
     va[c] = (float)fmax((s2[c] - s1[c] * mean64) / (double)(M - 1), 0.0);
   }
-  st<VW>(mean + at, mu);
-  if (var) st<VW>(var + at, va);
+  stv<VW>(mean + at, mu);
+  if (var) stv<VW>(var + at, va);
 }
-
-inline bool aligned16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
 
 inline int bwd_chunks(int64_t B) {
   const int64_t n = (B + BWD_MIN_CHUNK - 1) / BWD_MIN_CHUNK;
   return (int)(n < BWD_MAX_CHUNKS ? n : BWD_MAX_CHUNKS);
 }
-
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 constexpr int KR4 = 4, KR1 = 8;          // methods per thread of the backward kernel on the 16-byte and on the single-element path
 

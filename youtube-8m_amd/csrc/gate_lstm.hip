@@ -13,25 +13,6 @@
 
 namespace {
 
-// v_exp_f32 / v_rcp_f32 gate functions, as cells.hip's ln_sigmoid / ln_tanh (<= ~1.5e-7 absolute per value against libm)
-__device__ __forceinline__ float gl_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
-__device__ __forceinline__ float gl_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.8853900817779268f * x)); }
-constexpr int GL_PT = 8;                       // units per thread: H <= 256 * GL_PT
-
-struct F2 { float a, b; };
-// two block-wide sums for blockDim.x == 256 on one barrier pair; the result is valid in all threads
-__device__ __forceinline__ F2 block_sum2_256(float a, float b, float* red /* 8 floats */) {
-  a = wave_sum(a);
-  b = wave_sum(b);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) { red[w * 2] = a; red[w * 2 + 1] = b; }
-  __syncthreads();
-  F2 o;
-  o.a = red[0] + red[2] + red[4] + red[6];
-  o.b = red[1] + red[3] + red[5] + red[7];
-  return o;
-}
 
 // One workgroup per batch row; PT = compile-time units per thread (H <= 256 PT, H % 256 == 0).  zv row [2H] arrives as
 // x.[Wog|Wc] + [bog|bc] + h.[Uog|Uc] and leaves as o | g; zs row (stride lds) arrives as x.[Wi|Wf] + [bi|bf] in columns 0, 1 and leaves
@@ -61,21 +42,21 @@ __global__ __launch_bounds__(256) void gate_lstm_fwd_kernel(float* __restrict__ 
     ui[p] = in ? Us[h] : 0.f;
     uf[p] = in ? Us[H + h] : 0.f;
   }
-  float si = 0.f, sf = 0.f;
+  float s[2] = {0.f, 0.f};                                             // h.Ui, h.Uf
 #pragma unroll
-  for (int p = 0; p < PT; ++p) { si += hp[p] * ui[p]; sf += hp[p] * uf[p]; }
-  const F2 s = block_sum2_256(si, sf, red);
-  const float i = gl_sigmoid(zi + s.a), f = gl_sigmoid(zf + s.b);
+  for (int p = 0; p < PT; ++p) { s[0] += hp[p] * ui[p]; s[1] += hp[p] * uf[p]; }
+  block_sums_256<2>(s, red);
+  const float i = fast_sigmoid(zi + s[0]), f = fast_sigmoid(zf + s[1]);
 #pragma unroll
   for (int p = 0; p < PT; ++p) {
     const int64_t h = tid + p * 256;
     if (h < H) {
-      const float o = gl_sigmoid(zo[p]), g = gl_tanh(zg[p]);
+      const float o = fast_sigmoid(zo[p]), g = fast_tanh(zg[p]);
       const float cn = f * cp[p] + i * g;
       zr[h] = o;
       zr[H + h] = g;
       c_new[b * H + h] = cn;
-      h_new[b * H + h] = o * gl_tanh(cn);
+      h_new[b * H + h] = o * fast_tanh(cn);
       if (last) c_last[b * H + h] = cn;
     }
   }
@@ -116,24 +97,24 @@ __global__ __launch_bounds__(256) void gate_lstm_bwd_kernel(const float* __restr
     ui[p] = in ? Us[h] : 0.f;
     uf[p] = in ? Us[H + h] : 0.f;
   }
-  float sg = 0.f, sc = 0.f;
+  float s[2] = {0.f, 0.f};                                             // sum dc g, sum dc c_prev
 #pragma unroll
   for (int p = 0; p < PT; ++p) {
     const int64_t h = tid + p * 256;
     if (h < H) {
-      const float tc = gl_tanh(cnv[p]);
+      const float tc = fast_tanh(cnv[p]);
       const float dh = dhv[p], o = ov[p], g = gv[p];
       const float dc = dcv[p] + dh * o * (1.0f - tc * tc);
       dcv[p] = dc;
       dzv[b * 2 * H + h] = dh * tc * o * (1.0f - o);
       dzv[b * 2 * H + H + h] = dc * i * (1.0f - g * g);
       dc_prev[b * H + h] = dc * f;
-      sg += dc * g;
-      sc += dc * cpv[p];
+      s[0] += dc * g;
+      s[1] += dc * cpv[p];
     }
   }
-  const F2 s = block_sum2_256(sg, sc, red);
-  const float dzi = s.a * i * (1.0f - i), dzf = s.b * f * (1.0f - f);
+  block_sums_256<2>(s, red);
+  const float dzi = s[0] * i * (1.0f - i), dzf = s[1] * f * (1.0f - f);
 #pragma unroll
   for (int p = 0; p < PT; ++p) {
     const int64_t h = tid + p * 256;
@@ -146,9 +127,9 @@ __global__ __launch_bounds__(256) void gate_lstm_bwd_kernel(const float* __restr
 
 using namespace yt8m;
 
-// what the two step kernels handle: whole 256-unit slices per thread slot, up to GL_PT of them; one workgroup per row
+// what the two step kernels handle: whole 256-unit slices per thread slot, up to ROW_PT of them; one workgroup per row
 extern "C" int yt8m_gate_lstm_supported(int64_t B, int64_t H) {
-  return (B >= 1 && B < (1LL << 31) && H >= 256 && H % 256 == 0 && H <= 256 * GL_PT) ? 1 : 0;
+  return (B >= 1 && B < (1LL << 31) && H >= 256 && H % 256 == 0 && H <= 256 * ROW_PT) ? 1 : 0;
 }
 
 extern "C" int yt8m_gate_lstm_layer_fwd(float* zv, float* zs, int64_t lds, const float* Uv, int64_t ldu, const float* Us, float* hs,
@@ -164,8 +145,7 @@ extern "C" int yt8m_gate_lstm_layer_fwd(float* zv, float* zs, int64_t lds, const
   const int64_t BH = B * H;
   if (c_last) YT8M_HIP_CHECK(hipMemsetAsync(c_last, 0, BH * sizeof(float), s));       // rows with num_frames < 1 (or > F) keep zeros
   const StepProduct rec = {Uv, ldu, nullptr, nullptr, 2, B, H, gemm_workspace, gemm_workspace_bytes, stream};
-  auto kfn = H <= 256 ? gate_lstm_fwd_kernel<1> : H <= 512 ? gate_lstm_fwd_kernel<2> : H <= 1024 ? gate_lstm_fwd_kernel<4>
-                                                                                                   : gate_lstm_fwd_kernel<GL_PT>;
+  auto kfn = YT8M_ROW_KERNEL(gate_lstm_fwd_kernel, H, 1);
   for (int64_t t = 0; t < F; ++t) {
     float* zvt = zv + t * B * 2 * H;
     int rc = rec.add_hW(hs + t * BH, zvt);                                                             // zv_t += h . [Uog|Uc]
@@ -197,17 +177,14 @@ extern "C" int yt8m_gate_lstm_layer_bwd(const float* zv, const float* zs, int64_
   // workspace holds the packed weights; YT8M_GATE_LSTM_PACKED_BWD=0 (read at every call: an A/B switch for tools/ and tests) keeps
   // the grouped GEMM
   const char* sw = getenv("YT8M_GATE_LSTM_PACKED_BWD");
-  const bool packed = !(sw && atoi(sw) == 0) && gemm_workspace && cell_packed_supported(B, H) &&
-                      gemm_workspace_bytes >= (int64_t)sizeof(float) * H * 2 * H;
+  const bool packed = !(sw && atoi(sw) == 0) && packed_fits(B, H, 2, gemm_workspace, gemm_workspace_bytes);
   float* Wq = packed ? static_cast<float*>(gemm_workspace) : nullptr;
   if (packed) {
-    ProfScope prof(F_LSTM, s);
-    int rc = cell_pack(Uv, ldu, nullptr, Wq, H, 2, s);
+    int rc = cell_pack_scoped(Uv, ldu, nullptr, Wq, H, 2, s);
     if (rc != YT8M_OK) return rc;
   }
   const StepProduct rec = {Uv, ldu, nullptr, Wq, 2, B, H, gemm_workspace, gemm_workspace_bytes, stream};
-  auto kfn = H <= 256 ? gate_lstm_bwd_kernel<1> : H <= 512 ? gate_lstm_bwd_kernel<2> : H <= 1024 ? gate_lstm_bwd_kernel<4>
-                                                                                                   : gate_lstm_bwd_kernel<GL_PT>;
+  auto kfn = YT8M_ROW_KERNEL(gate_lstm_bwd_kernel, H, 1);
   for (int64_t t = F - 1; t >= 0; --t, g.swap()) {
     float* dzvt = dzv + t * B * 2 * H;
     {

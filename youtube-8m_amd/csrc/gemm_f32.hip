@@ -661,7 +661,6 @@ __global__ __launch_bounds__(256) void splitk_fixup_kernel(const GroupArgs G) {
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 constexpr int RESIDENT_PER_CU = 3;   // 76 VGPR + 64 AGPR, 32 KiB LDS => 3 workgroups per CU
 constexpr int NUM_CU = 256;

@@ -17,7 +17,6 @@
 
 namespace {
 
-constexpr float U8_A0 = 4.0f / 255.0f, U8_C0 = 4.0f / 512.0f - 2.0f;
 
 __device__ __forceinline__ float4 load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float4 unpack4(uint32_t u) {

@@ -17,29 +17,8 @@
 
 namespace {
 
-// v_exp_f32 / v_rcp_f32 gate functions, as gate_lstm.hip's (<= ~1.5e-7 absolute per value against libm)
-__device__ __forceinline__ float gu_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
-__device__ __forceinline__ float gu_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.8853900817779268f * x)); }
-constexpr int GU_PT = 8;                       // units per thread: H <= 256 * GU_PT
 constexpr int GU_DMAX = 2048;                  // widest input
 constexpr float GU_EPS = 1e-12f;               // tf.nn.l2_normalize's epsilon
-constexpr float U8_A0 = 4.0f / 255.0f, U8_C0 = 4.0f / 512.0f - 2.0f;      // Dequantize (W/utils.py:23-38): x = r (a0 q + c0)
-
-// N block-wide sums for blockDim.x == 256 on one barrier pair; the results are valid in all threads
-template <int N>
-__device__ __forceinline__ void block_sums_256(float (&v)[N], float* red /* 4 N floats */) {
-#pragma unroll
-  for (int k = 0; k < N; ++k) v[k] = wave_sum(v[k]);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) red[w * N + k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < N; ++k) v[k] = red[k] + red[N + k] + red[2 * N + k] + red[3 * N + k];
-}
 
 // the frame of row b at step t, four values at d: float frames x [F,B,D], or the reader's bytes q [B,F,D] under the frame's scale
 struct Frame {
@@ -114,18 +93,18 @@ __global__ __launch_bounds__(256) void glu_lstm_fwd_kernel(const FwdArgs a) {
   }
   block_sums_256<4>(s, red);
 #pragma unroll
-  for (int k = 0; k < 4; ++k) s[k] = gu_sigmoid(zs[k] + r * qs[k] + s[k]);
+  for (int k = 0; k < 4; ++k) s[k] = fast_sigmoid(zs[k] + r * qs[k] + s[k]);
   const float gi = s[0], gf = s[1], ix = s[2], fx = s[3];
 #pragma unroll
   for (int p = 0; p < PT; ++p) {
     const int64_t h = tid + p * 256;
     if (h < H) {
-      const float o = gu_sigmoid(zo[p] + r * qo[p]), g = gu_tanh(zg[p] + r * qg[p]);
+      const float o = fast_sigmoid(zo[p] + r * qo[p]), g = fast_tanh(zg[p] + r * qg[p]);
       const float cn = gf * cp[p] + gi * g;
       zr[h] = o;
       zr[H + h] = g;
       a.c_new[b * H + h] = cn;
-      a.h_new[b * H + h] = o * gu_tanh(cn);
+      a.h_new[b * H + h] = o * fast_tanh(cn);
       a.qv_new[b * 2 * H + h] = fx * qo[p] + ix * po[p];
       a.qv_new[b * 2 * H + H + h] = fx * qg[p] + ix * pg[p];
       if (last) a.c_last[b * H + h] = cn;
@@ -234,7 +213,7 @@ __global__ __launch_bounds__(256) void glu_lstm_bwd_kernel(const BwdArgs a) {
   for (int p = 0; p < PT; ++p) {
     const int64_t h = tid + p * 256;
     if (h < H) {
-      const float tc = gu_tanh(cnv[p]);
+      const float tc = fast_tanh(cnv[p]);
       const float dh = dhv[p], o = ov[p], g = gv[p];
       const float dc = dcv[p] + dh * o * (1.0f - tc * tc);
       const float dao = dh * tc * o * (1.0f - o), dag = dc * gi * (1.0f - g * g);
@@ -306,11 +285,9 @@ __global__ __launch_bounds__(256) void glu_lstm_bwd_kernel(const BwdArgs a) {
 
 using namespace yt8m;
 
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// what the two step kernels handle: whole 256-unit slices per thread slot, up to GU_PT of them; float4 / 4-byte reads of the frames
+// what the two step kernels handle: whole 256-unit slices per thread slot, up to ROW_PT of them; float4 / 4-byte reads of the frames
 extern "C" int yt8m_glu_lstm_supported(int64_t B, int64_t H, int64_t D) {
-  return (B >= 1 && B < (1LL << 31) && H >= 256 && H % 256 == 0 && H <= 256 * GU_PT && D >= 4 && D % 4 == 0 && D <= GU_DMAX) ? 1 : 0;
+  return (B >= 1 && B < (1LL << 31) && H >= 256 && H % 256 == 0 && H <= 256 * ROW_PT && D >= 4 && D % 4 == 0 && D <= GU_DMAX) ? 1 : 0;
 }
 
 extern "C" int yt8m_glu_lstm_layer_fwd(float* zv, float* pv, int64_t ldv, float* zs, int64_t lds, const float* Uv, int64_t ldu,
@@ -330,17 +307,15 @@ extern "C" int yt8m_glu_lstm_layer_fwd(float* zv, float* pv, int64_t ldv, float*
   hipStream_t s = as_stream(stream);
   const int64_t BH = B * H, BD = B * D;
   if (c_last) YT8M_HIP_CHECK(hipMemsetAsync(c_last, 0, BH * sizeof(float), s));       // rows with num_frames < 1 (or > F) keep zeros
-  auto kfn = H <= 256 ? glu_lstm_fwd_kernel<1> : H <= 512 ? glu_lstm_fwd_kernel<2> : H <= 1024 ? glu_lstm_fwd_kernel<4>
-                                                                                                  : glu_lstm_fwd_kernel<GU_PT>;
+  auto kfn = YT8M_ROW_KERNEL(glu_lstm_fwd_kernel, H, 1);
+  const StepProduct rec = {Uv, ldu, nullptr, nullptr, 2, B, H, gemm_workspace, gemm_workspace_bytes, stream, ldv};
   FwdArgs a;
   a.ldv = ldv; a.lds = lds; a.Us = Us; a.c_last = c_last; a.nf = num_frames; a.xq = xq; a.F = F; a.H = H; a.D = D;
   for (int64_t t = 0; t < F; ++t) {
     a.zv = zv + t * B * ldv;
     a.pv = pv + t * B * ldv;
     a.zs = zs + t * B * lds;
-    // zv_t += h . [Uog|Uc]: StepProduct::add_hW's grouped GEMM, writing rows of stride ldv
-    yt8m_gemm_problem pr = {B, 2 * H, H, hs + t * BH, H, Uv, ldu, a.zv, ldv, nullptr, 1.0f};
-    int rc = yt8m_gemm_f32_grouped(0, 0, 1, &pr, gemm_workspace, gemm_workspace_bytes, stream);
+    int rc = rec.add_hW(hs + t * BH, a.zv);                                                            // zv_t += h . [Uog|Uc]
     if (rc != YT8M_OK) return rc;
     a.c_prev = cs + t * BH; a.h_prev = hs + t * BH; a.qv_prev = qv + t * 2 * BH; a.qs_prev = qs + t * B * 4; a.xm_prev = xm + t * BD;
     a.n2_prev = n2 + t * B;
@@ -387,16 +362,14 @@ extern "C" int yt8m_glu_lstm_layer_bwd(const float* zv, const float* pv, int64_t
   // dzv . [Uog|Uc]^T on the packed step launcher of lstm_fused.hip (cell_step_bwd, G = 2) where the workspace holds the packed
   // weights, as in gate_lstm.hip; the launcher reads contiguous rows, so the kernel leaves it a copy of dzv_t in work
   const char* sw = getenv("YT8M_GLU_LSTM_PACKED_BWD");
-  const bool packed = !(sw && atoi(sw) == 0) && gemm_workspace && cell_packed_supported(B, H) &&
-                      gemm_workspace_bytes >= (int64_t)sizeof(float) * H * 2 * H;
+  const bool packed = !(sw && atoi(sw) == 0) && packed_fits(B, H, 2, gemm_workspace, gemm_workspace_bytes);
   float* Wq = packed ? static_cast<float*>(gemm_workspace) : nullptr;
   if (packed) {
-    ProfScope prof(F_LSTM, s);
-    int rc = cell_pack(Uv, ldu, nullptr, Wq, H, 2, s);
+    int rc = cell_pack_scoped(Uv, ldu, nullptr, Wq, H, 2, s);
     if (rc != YT8M_OK) return rc;
   }
-  auto kfn = H <= 256 ? glu_lstm_bwd_kernel<1> : H <= 512 ? glu_lstm_bwd_kernel<2> : H <= 1024 ? glu_lstm_bwd_kernel<4>
-                                                                                                  : glu_lstm_bwd_kernel<GU_PT>;
+  const StepProduct rec = {Uv, ldu, nullptr, Wq, 2, B, H, gemm_workspace, gemm_workspace_bytes, stream, lddv};
+  auto kfn = YT8M_ROW_KERNEL(glu_lstm_bwd_kernel, H, 1);
   BwdArgs a;
   a.ldv = ldv; a.lds = lds; a.Us = Us; a.dc_last = dc_last; a.lddv = lddv; a.dav = packed ? dav : nullptr; a.dqv = dqv; a.dxm = dxm;
   a.dsc = dsc; a.nf = num_frames; a.xq = xq; a.F = F; a.H = H; a.D = D;
@@ -417,14 +390,7 @@ extern "C" int yt8m_glu_lstm_layer_bwd(const float* zv, const float* pv, int64_t
       ProfScope prof(F_LSTM, s);
       hipLaunchKernelGGL(kfn, dim3((unsigned)B), dim3(256), 0, s, a);
     }
-    int rc;                                                                                            // dh_prev += dzv_t . [Uog|Uc]^T
-    if (packed) {
-      ProfScope prof(F_LSTM, s);
-      rc = cell_step_bwd(dav, Wq, g.dh_prev, B, H, 2, s);
-    } else {
-      yt8m_gemm_problem pr = {B, H, 2 * H, a.dzv, lddv, Uv, ldu, g.dh_prev, H, nullptr, 1.0f};
-      rc = yt8m_gemm_f32_grouped(0, 1, 1, &pr, gemm_workspace, gemm_workspace_bytes, stream);
-    }
+    int rc = rec.add_dzWt(packed ? dav : a.dzv, g.dh_prev);                                            // dh_prev += dzv_t . [Uog|Uc]^T
     if (rc != YT8M_OK) return rc;
   }
   return launch_status("glu_lstm_bwd_kernel");

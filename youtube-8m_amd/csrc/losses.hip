@@ -52,22 +52,6 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
-// block-wide sums of NQ quantities, blockDim.x == 256; red: NQ * 4 floats of LDS; results valid in all threads
-template <int NQ>
-__device__ __forceinline__ void block_sums_256(float (&v)[NQ], float* red) {
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) v[q] = wave_sum(v[q]);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) red[q * 4 + w] = v[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) v[q] = red[q * 4] + red[q * 4 + 1] + red[q * 4 + 2] + red[q * 4 + 3];
-}
-
 // one workgroup of 1024 threads: t[q] = sum_i part[q * n + i] in fp64, fixed order; red: NQ * 16 doubles of LDS
 template <int NQ>
 __device__ __forceinline__ void finish_sums_1024(const float* __restrict__ part, int64_t n, double (&t)[NQ], double* red) {

@@ -168,17 +168,6 @@ __global__ __launch_bounds__(256) void hx_pack_kernel(const float* __restrict__ 
   }
 }
 
-// Gate non-linearities of the persistent kernels: v_exp_f32 / v_rcp_f32 (1 ulp each) instead of the libm-exact expf / tanhf of
-// the per-step kernels -- the epilogue is a single wave's dependent chain on the critical path of the state exchange, and the
-// exact forms cost ~10x the instructions.  Absolute error <= ~1.5e-7 per value (checked against the exact kernels and the fp64
-// oracle by the parity tests; north_star tolerance 1e-3).
-__device__ __forceinline__ float fast_sigmoid(float x) {
-  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
-}
-__device__ __forceinline__ float fast_tanh(float x) {
-  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.8853900817779268f * x));
-}
-
 // value of lane + N within a row of 16 lanes (DPP row_shl: one VALU op; __shfl_down is a ds_bpermute round trip through LDS)
 template <int N>
 __device__ __forceinline__ float row_shl(float v) {

@@ -41,7 +41,6 @@ __device__ __forceinline__ float* seg_at(const Segs& g, int nseg, int64_t row, i
   return reinterpret_cast<float*>(q);
 }
 
-__device__ __forceinline__ float link_r(float ss, float eps, float reps) { return ss > eps ? rsqrtf(ss) : reps; }
 
 // VEC: every width % 4 == 0 and every segment, y 16-byte aligned (checked by the caller).  reps = 1 / sqrt(eps), rounded once on the host.
 template <bool VEC>
@@ -244,8 +243,6 @@ inline bool fill_widths(int nseg, const int64_t* widths, Segs* g, int64_t* cols,
   }
   return *cols <= 0x7fffffffLL;
 }
-
-inline bool aligned16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
 
 }  // namespace
 

@@ -270,7 +270,6 @@ __global__ __launch_bounds__(256) void ms_bwd_apply_kernel(const float* __restri
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // rows per block so that at most max_blocks blocks cover `rows`; every row lane gets a few rows
 inline int rows_per_block(int64_t rows, int max_blocks) {

@@ -147,8 +147,6 @@ __global__ __launch_bounds__(BLOCK) void scale_mix_bwd_kernel(MixIn a, MixOut d,
   if (tail < n) mix_bwd_one<L>(a, d, out, g, tail);
 }
 
-inline bool aligned16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
-
 inline bool shape_ok(int L, int64_t rows, int64_t cols) {
   return L >= 1 && L <= MAX_L && rows >= 1 && cols >= 1 && rows <= 0x7fffffffLL && cols <= 0x7fffffffLL && rows * cols <= (1LL << 40);
 }

@@ -22,7 +22,7 @@
 // No atomics anywhere: a second run gives the same bits.  16-byte accesses (VW = 4) where every operand is 16-byte aligned and every
 // leading dimension is a multiple of 4, single elements (VW = 1) otherwise.
 #include <math.h>
-#include "common.h"
+#include "pooling_common.h"
 
 namespace {
 
@@ -32,26 +32,10 @@ constexpr int RPW = TCH / NW;              // rows per wave in phase 1
 constexpr int RB = 4;                      // rows in flight per thread in phase 2
 constexpr int HMAX = 2048;
 constexpr int AMAX = 8;
-constexpr int SUM_GROUP = 32;              // partials per thread of the first summing kernel
 constexpr float DEN_EPS = 1e-8f;
 
-template <int VW>
-__device__ __forceinline__ void ld(const float* p, float (&r)[VW]) {
-  if constexpr (VW == 4) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    r[0] = q.x; r[1] = q.y; r[2] = q.z; r[3] = q.w;
-  } else {
-    r[0] = *p;
-  }
-}
-
-template <int VW>
-__device__ __forceinline__ void st(float* p, const float (&r)[VW]) {
-  if constexpr (VW == 4) *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
-  else *p = r[0];
-}
-
-__device__ __forceinline__ int clamp_frames(const int32_t* nf, int b, int F) { return min(max(nf[b], 0), F); }
+// common.h's clamp_frames in 32-bit arithmetic: through the 64-bit form the two kernels below compile to other instructions
+__device__ __forceinline__ int clamp_frames_i32(const int32_t* nf, int b, int F) { return min(max(nf[b], 0), F); }
 
 // grid (B, ceil(F / TCH)); den_p [chunks, B, A]; pool_p [chunks, B, A, Hv] (unused with Hv == 0)
 template <int A, int VW>
@@ -64,7 +48,7 @@ __global__ __launch_bounds__(256) void sigattn_fwd_kernel(const float* __restric
   __shared__ float s_sh[TCH][A];
   const int b = blockIdx.x, c = blockIdx.y, t0 = c * TCH;
   const int rows = min(TCH, F - t0);                                      // frames of this chunk
-  const int live = max(0, min(rows, clamp_frames(nf, b, F) - t0));        // ... of which unmasked
+  const int live = max(0, min(rows, clamp_frames_i32(nf, b, F) - t0));        // ... of which unmasked
   const int lane = threadIdx.x & 63, r0 = (threadIdx.x >> 6) * RPW;
   float z[RPW][A];
 #pragma unroll
@@ -88,7 +72,7 @@ __global__ __launch_bounds__(256) void sigattn_fwd_kernel(const float* __restric
 #pragma unroll
       for (int r = 0; r < RPW; ++r) {
         if (r0 + r < live) {
-          ld<VW>(src + ((size_t)(t0 + r0 + r) * B + b) * ld_src + h, x[r]);
+          ldv<VW>(src + ((size_t)(t0 + r0 + r) * B + b) * ld_src + h, x[r]);
         } else {
 #pragma unroll
           for (int k = 0; k < VW; ++k) x[r][k] = 0.0f;
@@ -140,7 +124,7 @@ __global__ __launch_bounds__(256) void sigattn_fwd_kernel(const float* __restric
       for (int k = 0; k < KV; ++k) {
         const int col = (k * 256 + threadIdx.x) * VW;
         if (t + rr < live && col < Hv) {
-          ld<VW>(vals + ((size_t)(t0 + t + rr) * B + b) * ld_vals + col, v[rr][k]);
+          ldv<VW>(vals + ((size_t)(t0 + t + rr) * B + b) * ld_vals + col, v[rr][k]);
         } else {
 #pragma unroll
           for (int e = 0; e < VW; ++e) v[rr][k][e] = 0.0f;
@@ -165,7 +149,7 @@ __global__ __launch_bounds__(256) void sigattn_fwd_kernel(const float* __restric
     const int col = (k * 256 + threadIdx.x) * VW;
     if (col < Hv) {
 #pragma unroll
-      for (int a = 0; a < A; ++a) st<VW>(pool_p + (((size_t)c * B + b) * A + a) * Hv + col, acc[k][a]);
+      for (int a = 0; a < A; ++a) stv<VW>(pool_p + (((size_t)c * B + b) * A + a) * Hv + col, acc[k][a]);
     }
   }
 }
@@ -231,7 +215,7 @@ __global__ __launch_bounds__(256) void sigattn_bwd_kernel(const float* __restric
   __shared__ float a_sh[TCH][A], dz_sh[TCH][A];
   const int b = blockIdx.x, c = blockIdx.y, t0 = c * TCH;
   const int rows = min(TCH, F - t0);
-  const int live = max(0, min(rows, clamp_frames(nf, b, F) - t0));
+  const int live = max(0, min(rows, clamp_frames_i32(nf, b, F) - t0));
   const int lane = threadIdx.x & 63, r0 = (threadIdx.x >> 6) * RPW;
   for (int i = threadIdx.x; i < rows * A; i += 256) {
     const size_t o = ((size_t)b * F + t0) * A + i;
@@ -251,7 +235,7 @@ __global__ __launch_bounds__(256) void sigattn_bwd_kernel(const float* __restric
 #pragma unroll
       for (int a = 0; a < A; ++a) {
         if (G) {
-          ld<VW>(G + ((size_t)b * A + a) * Hv + h, g[a]);
+          ldv<VW>(G + ((size_t)b * A + a) * Hv + h, g[a]);
         } else {
 #pragma unroll
           for (int k = 0; k < VW; ++k) g[a][k] = 0.0f;
@@ -261,7 +245,7 @@ __global__ __launch_bounds__(256) void sigattn_bwd_kernel(const float* __restric
 #pragma unroll
       for (int r = 0; r < RPW; ++r) {
         if (r0 + r < live && G) {
-          ld<VW>(vals + ((size_t)(t0 + r0 + r) * B + b) * ld_vals + h, x[r]);
+          ldv<VW>(vals + ((size_t)(t0 + r0 + r) * B + b) * ld_vals + h, x[r]);
         } else {
 #pragma unroll
           for (int k = 0; k < VW; ++k) x[r][k] = 0.0f;
@@ -284,7 +268,7 @@ __global__ __launch_bounds__(256) void sigattn_bwd_kernel(const float* __restric
             }
           }
         }
-        if (dvals && t < rows) st<VW>(dvals + ((size_t)(t0 + t) * B + b) * ld_dvals + h, o);
+        if (dvals && t < rows) stv<VW>(dvals + ((size_t)(t0 + t) * B + b) * ld_dvals + h, o);
       }
     }
     if (G) {
@@ -330,7 +314,7 @@ __global__ __launch_bounds__(256) void sigattn_bwd_kernel(const float* __restric
       for (int k = 0; k < KV; ++k) {
         const int col = (k * 256 + threadIdx.x) * VW;
         if (t + rr < live && col < Hs) {
-          ld<VW>(src + ((size_t)(t0 + t + rr) * B + b) * ld_src + col, x[rr][k]);
+          ldv<VW>(src + ((size_t)(t0 + t + rr) * B + b) * ld_src + col, x[rr][k]);
         } else {
 #pragma unroll
           for (int e = 0; e < VW; ++e) x[rr][k][e] = 0.0f;
@@ -360,7 +344,7 @@ __global__ __launch_bounds__(256) void sigattn_bwd_kernel(const float* __restric
 #pragma unroll
               for (int e = 0; e < VW; ++e) o[e] = 0.0f;                   // exact zeros whatever Wa holds
             }
-            st<VW>(dsrc + ((size_t)(t0 + t + rr) * B + b) * ld_dsrc + col, o);
+            stv<VW>(dsrc + ((size_t)(t0 + t + rr) * B + b) * ld_dsrc + col, o);
           }
         }
       }
@@ -383,34 +367,6 @@ __global__ __launch_bounds__(256) void sigattn_bwd_kernel(const float* __restric
     p[(size_t)Hs * A + threadIdx.x] = s;
   }
 }
-
-// grid (ceil(n / 256), ceil(parts / SUM_GROUP)): dst[g, i] = sum of src[p, i] over the group's parts in the order of p
-__global__ __launch_bounds__(256) void sigattn_sum_groups_kernel(const float* __restrict__ src, float* __restrict__ dst, int n, int parts) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int p0 = blockIdx.y * SUM_GROUP, p1 = min(parts, p0 + SUM_GROUP);
-  float r = 0.0f;
-  for (int p = p0; p < p1; ++p) r += src[(size_t)p * n + i];
-  dst[(size_t)blockIdx.y * n + i] = r;
-}
-
-// grid (ceil(n / 256)): the groups in their order; element i goes to dWa[i] (i < nW) or dba[i - nW]; either may be null
-__global__ __launch_bounds__(256) void sigattn_sum_final_kernel(const float* __restrict__ src, float* __restrict__ dWa,
-                                                                float* __restrict__ dba, int n, int nW, int groups) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  float r = 0.0f;
-  for (int g = 0; g < groups; ++g) r += src[(size_t)g * n + i];
-  if (i < nW) {
-    if (dWa) dWa[i] = r;
-  } else if (dba) {
-    dba[i - nW] = r;
-  }
-}
-
-inline bool aligned16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-inline int64_t up4(int64_t a) { return (a + 3) & ~(int64_t)3; }
 
 inline bool shape_ok(int64_t B, int64_t F, int64_t Hs, int64_t Hv, int64_t A) {
   return B >= 1 && B <= 65536 && F >= 1 && F <= 65536 && B * cdiv(F, TCH) <= (1 << 21) && Hs >= 4 && Hs <= HMAX && (Hs & 3) == 0 &&
@@ -472,18 +428,6 @@ extern "C" int64_t yt8m_sigattn_workspace_bytes(int64_t B, int64_t F, int64_t Hs
   return Layout(B, F, Hs, Hv, A).bytes;
 }
 
-#define SIGATTN_BY_A(CALL)       \
-  switch (A) {                   \
-    case 1: CALL(1) break;       \
-    case 2: CALL(2) break;       \
-    case 3: CALL(3) break;       \
-    case 4: CALL(4) break;       \
-    case 5: CALL(5) break;       \
-    case 6: CALL(6) break;       \
-    case 7: CALL(7) break;       \
-    default: CALL(8) break;      \
-  }
-
 extern "C" int yt8m_sigattn_fwd(const float* src, int64_t ld_src, const float* vals, int64_t ld_vals, const float* Wa, const float* ba,
                                 const int32_t* num_frames, float* att, float* den, float* pooled, void* workspace,
                                 int64_t workspace_bytes, int64_t B, int64_t F, int64_t Hs, int64_t Hv, int64_t A, yt8m_stream_t stream) {
@@ -502,7 +446,7 @@ extern "C" int yt8m_sigattn_fwd(const float* src, int64_t ld_src, const float* v
   ProfScope prof(F_ELEMENTWISE, s);
   const int b = (int)B, f = (int)F, hs = (int)Hs, hv = (int)Hv;
 #define SIGATTN_FWD(AA) launch_fwd<AA>(vec, src, ld_src, vals, ld_vals, Wa, ba, num_frames, att, den_p, pool_p, f, b, hs, hv, s);
-  SIGATTN_BY_A(SIGATTN_FWD)
+  YT8M_BY_HEADS(A, SIGATTN_FWD)
 #undef SIGATTN_FWD
   int st = launch_status("sigattn_fwd_kernel");
   if (st != YT8M_OK) return st;
@@ -538,16 +482,9 @@ extern "C" int yt8m_sigattn_bwd(const float* src, int64_t ld_src, const float* v
   if (st != YT8M_OK) return st;
 #define SIGATTN_BWD(AA) \
   launch_bwd<AA>(vec, src, ld_src, vals, ld_vals, Wa, num_frames, att, den, G, E, inner, dsrc, ld_dsrc, dvals, ld_dvals, parts, f, b, hs, hv, s);
-  SIGATTN_BY_A(SIGATTN_BWD)
+  YT8M_BY_HEADS(A, SIGATTN_BWD)
 #undef SIGATTN_BWD
   st = launch_status("sigattn_bwd_kernel");
   if (st != YT8M_OK || !parts) return st;
-  const int n = (int)L.n;
-  hipLaunchKernelGGL(sigattn_sum_groups_kernel, dim3((unsigned)cdiv(n, 256), (unsigned)L.groups), dim3(256), 0, s, parts, groups, n,
-                     (int)L.parts);
-  st = launch_status("sigattn_sum_groups_kernel");
-  if (st != YT8M_OK) return st;
-  hipLaunchKernelGGL(sigattn_sum_final_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, groups, dWa, dba, n, (int)(Hs * A),
-                     (int)L.groups);
-  return launch_status("sigattn_sum_final_kernel");
+  return sum_parts(parts, groups, (int)L.n, (int)L.parts, dWa, (int)(Hs * A), dba, s);
 }

@@ -38,7 +38,7 @@
 // No atomics anywhere: a second run gives the same bits.  16-byte accesses (VW = 4) where every operand is 16-byte aligned and every
 // leading dimension is a multiple of 4, single elements (VW = 1) otherwise.
 #include <math.h>
-#include "common.h"
+#include "pooling_common.h"
 
 namespace {
 
@@ -49,23 +49,6 @@ constexpr int RPW = 8;                     // rows per wave and batch in phase 1
 constexpr int RB = 4;                      // rows in flight per thread in phase 2
 constexpr int HMAX = 2048;
 constexpr int EMAX = 8;
-constexpr int SUM_GROUP = 32;              // partials per thread of the first summing kernel
-
-template <int VW>
-__device__ __forceinline__ void ld(const float* p, float (&r)[VW]) {
-  if constexpr (VW == 4) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    r[0] = q.x; r[1] = q.y; r[2] = q.z; r[3] = q.w;
-  } else {
-    r[0] = *p;
-  }
-}
-
-template <int VW>
-__device__ __forceinline__ void st(float* p, const float (&r)[VW]) {
-  if constexpr (VW == 4) *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
-  else *p = r[0];
-}
 
 // head e's window of video b clamped to the frames there are: [max(lo, 0), min(hi, F - 1)], empty where the first exceeds the second
 __device__ __forceinline__ void window(const int32_t* lo, const int32_t* hi, int b, int e, int E, int F, int& l, int& h) {
@@ -133,7 +116,7 @@ __global__ __launch_bounds__(256) void smattn_fwd_kernel(const float* __restrict
 #pragma unroll
         for (int r = 0; r < RPW; ++r) {
           if ((live >> (r0 + r)) & 1ull) {
-            ld<VW>(src + ((size_t)(t0 + r0 + r) * B + b) * ld_src + h, x[r]);
+            ldv<VW>(src + ((size_t)(t0 + r0 + r) * B + b) * ld_src + h, x[r]);
           } else {
 #pragma unroll
             for (int k = 0; k < VW; ++k) x[r][k] = 0.0f;
@@ -198,7 +181,7 @@ __global__ __launch_bounds__(256) void smattn_fwd_kernel(const float* __restrict
 #pragma unroll
       for (int rr = 0; rr < RB; ++rr) {
         if (t + rr < thi && ((live >> (t + rr)) & 1ull)) {
-          ld<VW>(vals + ((size_t)(t0 + t + rr) * B + b) * ld_vals + col, v[rr]);
+          ldv<VW>(vals + ((size_t)(t0 + t + rr) * B + b) * ld_vals + col, v[rr]);
         } else {
 #pragma unroll
           for (int j = 0; j < VW; ++j) v[rr][j] = 0.0f;
@@ -222,7 +205,7 @@ __global__ __launch_bounds__(256) void smattn_fwd_kernel(const float* __restrict
       }
     }
 #pragma unroll
-    for (int e = 0; e < E; ++e) st<VW>(pool_p + (((size_t)c * B + b) * E + e) * Hv + col, acc[e]);
+    for (int e = 0; e < E; ++e) stv<VW>(pool_p + (((size_t)c * B + b) * E + e) * Hv + col, acc[e]);
   }
 }
 
@@ -314,14 +297,14 @@ __global__ __launch_bounds__(256) void smattn_bwd_kernel(const float* __restrict
         float g[E][VW], pl[E][VW];
 #pragma unroll
         for (int e = 0; e < E; ++e) {
-          ld<VW>(G + ((size_t)b * E + e) * Hv + h, g[e]);
-          ld<VW>(pooled + ((size_t)b * E + e) * Hv + h, pl[e]);
+          ldv<VW>(G + ((size_t)b * E + e) * Hv + h, g[e]);
+          ldv<VW>(pooled + ((size_t)b * E + e) * Hv + h, pl[e]);
         }
         float x[RPW][VW];
 #pragma unroll
         for (int r = 0; r < RPW; ++r) {
           if ((live >> (r0 + r)) & 1ull) {
-            ld<VW>(vals + ((size_t)(t0 + r0 + r) * B + b) * ld_vals + h, x[r]);
+            ldv<VW>(vals + ((size_t)(t0 + r0 + r) * B + b) * ld_vals + h, x[r]);
           } else {
 #pragma unroll
             for (int k = 0; k < VW; ++k) x[r][k] = 0.0f;
@@ -345,7 +328,7 @@ __global__ __launch_bounds__(256) void smattn_bwd_kernel(const float* __restrict
             }
           }
           if constexpr (!SHARED) {
-            if (dvals && t < rows) st<VW>(dvals + ((size_t)(t0 + t) * B + b) * ld_dvals + h, o);
+            if (dvals && t < rows) stv<VW>(dvals + ((size_t)(t0 + t) * B + b) * ld_dvals + h, o);
           }
         }
       }
@@ -384,14 +367,14 @@ __global__ __launch_bounds__(256) void smattn_bwd_kernel(const float* __restrict
     }
     if constexpr (SHARED) {
 #pragma unroll
-      for (int e = 0; e < E; ++e) ld<VW>(G + ((size_t)b * E + e) * Hv + col, g[e]);
+      for (int e = 0; e < E; ++e) ldv<VW>(G + ((size_t)b * E + e) * Hv + col, g[e]);
     }
     for (int t = 0; t < rows; t += RB) {
       float x[RB][VW];
 #pragma unroll
       for (int rr = 0; rr < RB; ++rr) {
         if (t + rr < rows && ((live >> (t + rr)) & 1ull)) {
-          ld<VW>(src + ((size_t)(t0 + t + rr) * B + b) * ld_src + col, x[rr]);
+          ldv<VW>(src + ((size_t)(t0 + t + rr) * B + b) * ld_src + col, x[rr]);
         } else {
 #pragma unroll
           for (int j = 0; j < VW; ++j) x[rr][j] = 0.0f;
@@ -419,7 +402,7 @@ __global__ __launch_bounds__(256) void smattn_bwd_kernel(const float* __restrict
               }
             }
           }
-          st<VW>(dsrc + ((size_t)(t0 + t + rr) * B + b) * ld_dsrc + col, o);      // exact zeros on the rows no head unmasks
+          stv<VW>(dsrc + ((size_t)(t0 + t + rr) * B + b) * ld_dsrc + col, o);      // exact zeros on the rows no head unmasks
         }
       }
     }
@@ -429,29 +412,6 @@ __global__ __launch_bounds__(256) void smattn_bwd_kernel(const float* __restrict
     }
   }
 }
-
-// grid (ceil(n / 256), ceil(parts / SUM_GROUP)): dst[g, i] = sum of src[p, i] over the group's parts in the order of p
-__global__ __launch_bounds__(256) void smattn_sum_groups_kernel(const float* __restrict__ src, float* __restrict__ dst, int n, int parts) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int p0 = blockIdx.y * SUM_GROUP, p1 = min(parts, p0 + SUM_GROUP);
-  float r = 0.0f;
-  for (int p = p0; p < p1; ++p) r += src[(size_t)p * n + i];
-  dst[(size_t)blockIdx.y * n + i] = r;
-}
-
-// grid (ceil(n / 256)): the groups in their order
-__global__ __launch_bounds__(256) void smattn_sum_final_kernel(const float* __restrict__ src, float* __restrict__ dW1, int n, int groups) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  float r = 0.0f;
-  for (int g = 0; g < groups; ++g) r += src[(size_t)g * n + i];
-  dW1[i] = r;
-}
-
-inline bool aligned16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-inline int64_t up4(int64_t a) { return (a + 3) & ~(int64_t)3; }
 
 inline bool shape_ok(int64_t B, int64_t F, int64_t Hs, int64_t Hv, int64_t E) {
   return B >= 1 && B <= 65536 && F >= 1 && F <= 65536 && B * cdiv(F, 32) <= (1 << 21) && Hs >= 4 && Hs <= HMAX && (Hs & 3) == 0 &&
@@ -515,18 +475,6 @@ extern "C" int64_t yt8m_smattn_workspace_bytes(int64_t B, int64_t F, int64_t Hs,
   return Layout(B, F, Hs, Hv, E).bytes;
 }
 
-#define SMATTN_BY_E(CALL)        \
-  switch (E) {                   \
-    case 1: CALL(1) break;       \
-    case 2: CALL(2) break;       \
-    case 3: CALL(3) break;       \
-    case 4: CALL(4) break;       \
-    case 5: CALL(5) break;       \
-    case 6: CALL(6) break;       \
-    case 7: CALL(7) break;       \
-    default: CALL(8) break;      \
-  }
-
 extern "C" int yt8m_smattn_fwd(const float* src, int64_t ld_src, const float* vals, int64_t ld_vals, const float* W1, const float* b1,
                                const float* extra, const uint8_t* valid, const int32_t* lo, const int32_t* hi, float* att, float* pooled,
                                void* workspace, int64_t workspace_bytes, int64_t B, int64_t F, int64_t Hs, int64_t Hv, int64_t E,
@@ -545,7 +493,7 @@ extern "C" int yt8m_smattn_fwd(const float* src, int64_t ld_src, const float* va
   ProfScope prof(F_ELEMENTWISE, s);
   const int b = (int)B, f = (int)F, hs = (int)Hs, hv = (int)Hv;
 #define SMATTN_FWD(EE) launch_fwd<EE>(vec, src, ld_src, vals, ld_vals, W1, b1, extra, valid, lo, hi, att, m_p, l_p, pool_p, f, b, hs, hv, s);
-  SMATTN_BY_E(SMATTN_FWD)
+  YT8M_BY_HEADS(E, SMATTN_FWD)
 #undef SMATTN_FWD
   int st = launch_status("smattn_fwd_kernel");
   if (st != YT8M_OK) return st;
@@ -582,16 +530,10 @@ extern "C" int yt8m_smattn_bwd(const float* src, int64_t ld_src, const float* va
   else                                                                                                                                   \
     launch_bwd<EE, false>(vec, src, ld_src, vals, ld_vals, W1, valid, lo, hi, att, pooled, G, dsrc, ld_dsrc, dvals, ld_dvals, dextra,    \
                           parts, f, b, hs, hv, s);
-  SMATTN_BY_E(SMATTN_BWD)
+  YT8M_BY_HEADS(E, SMATTN_BWD)
 #undef SMATTN_BWD
   st = launch_status("smattn_bwd_kernel");
   if (st == YT8M_OK && db1 && hipMemsetAsync(db1, 0, (size_t)E * sizeof(float), s) != hipSuccess) st = launch_status("the memset of db1");
   if (st != YT8M_OK || !parts) return st;
-  const int n = (int)L.n;
-  hipLaunchKernelGGL(smattn_sum_groups_kernel, dim3((unsigned)cdiv(n, 256), (unsigned)L.groups), dim3(256), 0, s, parts, groups, n,
-                     (int)L.parts);
-  st = launch_status("smattn_sum_groups_kernel");
-  if (st != YT8M_OK) return st;
-  hipLaunchKernelGGL(smattn_sum_final_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, groups, dW1, n, (int)L.groups);
-  return launch_status("smattn_sum_final_kernel");
+  return sum_parts(parts, groups, (int)L.n, (int)L.parts, dW1, (int)L.n, nullptr, s);
 }

@@ -27,6 +27,8 @@ int gru_step_bwd_cand(const float* dzc, const float* Wq_c, float* dh_prev, const
 
 // ---- the recurrent product of one step: the packed launcher when packed weights are present, else one grouped fp32 GEMM ----
 // (the GEMM takes host-side split-K decisions and opens its own ProfScope; a packed launch is counted under F_LSTM)
+// The packed launchers read and write contiguous rows: a caller whose z / dz rows have another stride gives ldz and either no packed
+// weights or a contiguous copy of the rows.
 struct StepProduct {
   const float* Wh;          // [H, G*H], leading dimension ld
   int64_t ld;
@@ -37,6 +39,7 @@ struct StepProduct {
   void* ws;                 // GEMM workspace
   int64_t ws_bytes;
   yt8m_stream_t stream;
+  int64_t ldz = G * H;      // row stride of z / dz on the GEMM route
 
   // z[B, G*H] += h[B, H] . Wh
   int add_hW(const float* h, float* z) const {
@@ -44,7 +47,7 @@ struct StepProduct {
       ProfScope prof(F_LSTM, as_stream(stream));
       return cell_step_add4(z, Wp, h, B, H, as_stream(stream));
     }
-    yt8m_gemm_problem pr = {B, G * H, H, h, H, Wh, ld, z, G * H, nullptr, 1.0f};
+    yt8m_gemm_problem pr = {B, G * H, H, h, H, Wh, ld, z, ldz, nullptr, 1.0f};
     return yt8m_gemm_f32_grouped(0, 0, 1, &pr, ws, ws_bytes, stream);
   }
   // dh_prev[B, H] += dz[B, G*H] . Wh^T   (Wh stored [H, G*H] => transB).  in_scope: the caller's F_LSTM scope covers a packed launch
@@ -54,10 +57,26 @@ struct StepProduct {
       ProfScope prof(F_LSTM, as_stream(stream));
       return cell_step_bwd(dz, Wq, dh_prev, B, H, G, as_stream(stream));
     }
-    yt8m_gemm_problem pr = {B, H, G * H, dz, G * H, Wh, ld, dh_prev, H, nullptr, 1.0f};
+    yt8m_gemm_problem pr = {B, H, G * H, dz, ldz, Wh, ld, dh_prev, H, nullptr, 1.0f};
     return yt8m_gemm_f32_grouped(0, 1, 1, &pr, ws, ws_bytes, stream);
   }
 };
+
+// ---- what every row-per-workgroup cell driver repeats (cells.hip's LN-LSTM, gate_lstm.hip, glu_lstm.hip) ------------------
+// whether the packed weights of G gates fit the workspace and the packed launchers take the shape; the environment switches that
+// keep the grouped GEMM stay with each caller
+inline bool packed_fits(int64_t B, int64_t H, int G, const void* ws, int64_t ws_bytes) {
+  return ws && cell_packed_supported(B, H) && ws_bytes >= (int64_t)sizeof(float) * H * G * H;
+}
+// cell_pack under an F_LSTM scope of its own
+inline int cell_pack_scoped(const float* Wh, int64_t ldw, float* Wp, float* Wq, int64_t H, int G, hipStream_t s) {
+  ProfScope prof(F_LSTM, s);
+  return cell_pack(Wh, ldw, Wp, Wq, H, G, s);
+}
+// K<PT>, the step kernel template K at the fewest units per thread that cover H with 256 threads: PT = MIN_PT (1 or 2), 2, 4 or ROW_PT
+constexpr int ROW_PT = 8;                      // H <= 256 * ROW_PT
+#define YT8M_ROW_KERNEL(K, H, MIN_PT) \
+  ((H) <= 256 * (MIN_PT) ? K<MIN_PT> : (H) <= 512 ? K<2> : (H) <= 1024 ? K<4> : K<yt8m::ROW_PT>)
 
 // dst[n] = src[n], or zeros when there is no src (the gradients of the final state)
 inline hipError_t seed_state(float* dst, const float* src, int64_t n, hipStream_t s) {

@@ -12,11 +12,8 @@
 
 namespace {
 
-__device__ __forceinline__ int64_t clamp_frames(const int32_t* nf, int64_t b, int64_t F) {
-  if (!nf) return F;
-  const int64_t n = nf[b];
-  return n < 0 ? 0 : (n > F ? F : n);
-}
+// the frames of video b; every frame where no num_frames is given
+__device__ __forceinline__ int64_t frames_of(const int32_t* nf, int64_t b, int64_t F) { return nf ? clamp_frames(nf, b, F) : F; }
 
 // One load unit of a row: W elements of type E held as V, added element-wise into W accumulators of type A.
 template <typename V> struct Unit;
@@ -76,14 +73,14 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void resolution_mean_kernel(co
   const int64_t F2 = F / r, rows = B * F2;
   if (nf_out) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < B; b += stride) nf_out[b] = (int32_t)(clamp_frames(nf, b, F) / r);
+    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < B; b += stride) nf_out[b] = (int32_t)(frames_of(nf, b, F) / r);
   }
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
   if (row >= rows || nv == 0) return;
   const int64_t b = row / F2, g = row - b * F2;
   int64_t k = r;                                                                   // input rows to add: bytes, the real frames only
-  if (BYTES) k = std::min<int64_t>(std::max<int64_t>(clamp_frames(nf, b, F) - g * r, 0), r);
+  if (BYTES) k = std::min<int64_t>(std::max<int64_t>(frames_of(nf, b, F) - g * r, 0), r);
   const V* xr = x + (b * F + g * r) * nv;
   float* yr = y + row * nv * W;
   // bytes: (sc sum + k bias) / r with sc = 4/255 and bias = 4/512 - 2 = -255/128 is (512 sum - 65025 k) / (32640 r).  The numerator is

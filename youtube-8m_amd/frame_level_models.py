@@ -1260,15 +1260,22 @@ class GatedNetVLADAttentionChainModel(GatedNetVLADModel):
 GATE_LSTM_VARS = ("Wi", "Ui", "bi", "Wf", "Uf", "bf", "Wog", "Uog", "bog", "Wc", "Uc", "bc")      # create_recurrent_unit's order
 
 
-def _gate_lstm_unit(d_in, hidden, l2_penalty):
-    """create_recurrent_unit (Z/frame_level_models.py:1583-1611, :1733-1761) in the current scope: the twelve Variables with the
-    reference's names, shapes and initial values -- weights truncated_normal(stddev=0.1), bi = bog = bc = 0.1, bf = 1.0 -- every one
-    of them, biases included, under l2_penalty * l2_loss."""
+def _scalar_gate_unit(names, d_in, hidden, l2_penalty):
+    """create_recurrent_unit of the scalar-gate cell (Z/frame_level_models.py:1583-1611, :1733-1761: GATE_LSTM_VARS) and of the
+    input-memory cell (:695-749: GLU_LSTM_VARS) in the current scope: the Variables `names`, in that order, with the reference's names,
+    shapes and initial values -- weights truncated_normal(stddev=0.1), the forget biases bf = bfx = 1.0, the other biases 0.1 -- every
+    one of them, biases included, under l2_penalty * l2_loss.  W* act on the frame, V* on the l2-normalised input memory, U* on h; the
+    output gate "og" and the candidate "c" are `hidden` wide, every other gate is one scalar per video."""
     g = get_default_graph()
-    shapes = {"Wi": (d_in, 1), "Ui": (hidden, 1), "bi": (1,), "Wf": (d_in, 1), "Uf": (hidden, 1), "bf": (1,),
-              "Wog": (d_in, hidden), "Uog": (hidden, hidden), "bog": (hidden,), "Wc": (d_in, hidden), "Uc": (hidden, hidden), "bc": (hidden,)}
-    inits = {"bi": constant(0.1), "bf": constant(1.0), "bog": constant(0.1), "bc": constant(0.1)}
-    return {n: g.get_variable(n, shapes[n], inits.get(n, truncated_normal(0.1)), l2=l2_penalty) for n in GATE_LSTM_VARS}
+
+    def shape(n):
+        width = hidden if n[1:] in ("og", "c") else 1
+        return (width,) if n[0] == "b" else (hidden if n[0] == "U" else d_in, width)
+
+    def init(n):
+        return truncated_normal(0.1) if n[0] != "b" else constant(1.0 if n in ("bf", "bfx") else 0.1)
+
+    return {n: g.get_variable(n, shape(n), init(n), l2=l2_penalty) for n in names}
 
 
 def _gate_lstm_layer(x_tm, num_frames, hidden, scope, l2_penalty):
@@ -1277,63 +1284,61 @@ def _gate_lstm_layer(x_tm, num_frames, hidden, scope, l2_penalty):
     Returns (out_tm [F,B,H], the memory gathered at frame num_frames - 1 [B,H])."""
     d_in = x_tm.D if isinstance(x_tm, seq_ops.U8FrameImages) else x_tm.shape[2]
     with get_default_graph().variable_scope(scope):
-        v = {n: ops.as_tensor(var) for n, var in _gate_lstm_unit(d_in, hidden, l2_penalty).items()}
+        v = {n: ops.as_tensor(var) for n, var in _scalar_gate_unit(GATE_LSTM_VARS, d_in, hidden, l2_penalty).items()}
     Wv, bv = torch.cat([v["Wog"], v["Wc"]], dim=1), torch.cat([v["bog"], v["bc"]])
     Ws, bs = torch.cat([v["Wi"], v["Wf"]], dim=1), torch.cat([v["bi"], v["bf"]])
     Uv, Us = torch.cat([v["Uog"], v["Uc"]], dim=1), torch.cat([v["Ui"], v["Uf"]], dim=1).t()
     return seq_ops.gate_lstm_layer(x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames)
 
 
-class LstmGateModel(models.BaseModel):
+class _CellLayerModel(models.BaseModel):
+    """One layer of a while_loop cell under "lstm_forward"; the head reads the gathered memory.  `layer` is the cell's layer function."""
+    accepts_quantized_input = True
+    layer = None
+
+    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
+        x_tm = _hoisted_input(model_input, num_frames)
+        _, state = self.layer(x_tm, num_frames, int(FLAGS.lstm_cells), "lstm_forward", l2_penalty)
+        return _classify(state, model_input, vocab_size, **unused_params)
+
+
+class _CellMultilayerModel(models.BaseModel):
+    """--lstm_layers layers of a while_loop cell, layer i under "lstm_lsyer<i>lstm_forward"; the head reads the layers' gathered
+    memories concatenated.  `layer` is the cell's layer function."""
+    accepts_quantized_input = True
+    layer = None
+
+    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
+        hidden_outputs = _hoisted_input(model_input, num_frames)
+        state_outputs = []
+        for i in range(FLAGS.lstm_layers):
+            # rnn_gate takes its own l2_penalty=1e-8 (Z/frame_level_models.py:1674, :826); create_model's is not forwarded to it
+            hidden_outputs, state = self.layer(hidden_outputs, num_frames, int(FLAGS.lstm_cells), "lstm_lsyer%dlstm_forward" % i, 1e-8)
+            state_outputs.append(state)
+        return _classify(torch.cat(state_outputs, dim=1), model_input, vocab_size, **unused_params)
+
+
+class LstmGateModel(_CellLayerModel):
     """Z/frame_level_models.py:1521-1640: one layer of the scalar-gate LSTM cell (input and forget gate one scalar per video, output
     gate and candidate vectors) run over all max_frames steps by a tf.while_loop -- no dynamic_rnn copy-through; the head
     (--video_level_classifier_model) reads the memory c gathered at frame num_frames - 1 (:1570-1574).  H = --lstm_cells.  Variables
     lstm_forward/{Wi,Ui,bi,Wf,Uf,bf,Wog,Uog,bog,Wc,Uc,bc}.  A row with num_frames < 1 (the reference gathers the previous video's last
     frame there, out of range for the first video) hands zeros to the head and receives no gradient.
     accepts_quantized_input: _hoisted_input -- the layer reads the reader's bytes where the byte products cover the shape."""
-    accepts_quantized_input = True
-
-    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
-        x_tm = _hoisted_input(model_input, num_frames)
-        _, state = _gate_lstm_layer(x_tm, num_frames, int(FLAGS.lstm_cells), "lstm_forward", l2_penalty)
-        return _classify(state, model_input, vocab_size, **unused_params)
+    layer = staticmethod(_gate_lstm_layer)
 
 
-class LstmGateMultilayerModel(models.BaseModel):
+class LstmGateMultilayerModel(_CellMultilayerModel):
     """Z/frame_level_models.py:1642-1790: --lstm_layers layers of the scalar-gate cell (rnn_gate, :1674-1731); layer l + 1 reads all
     max_frames hidden outputs h of layer l, the head reads the layers' gathered memories concatenated (:1666).  Layer i's Variables
     live under "lstm_lsyer<i>lstm_forward/" -- the reference's spelling, which checkpoints carry.  Rows with num_frames < 1: as
     LstmGateModel.  accepts_quantized_input: _hoisted_input -- layer 0 reads the reader's bytes."""
-    accepts_quantized_input = True
-
-    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
-        hidden_outputs = _hoisted_input(model_input, num_frames)
-        state_outputs = []
-        for i in range(FLAGS.lstm_layers):
-            # rnn_gate takes its own l2_penalty=1e-8 (:1674); create_model's is not forwarded to it
-            hidden_outputs, state = _gate_lstm_layer(hidden_outputs, num_frames, int(FLAGS.lstm_cells), "lstm_lsyer%dlstm_forward" % i, 1e-8)
-            state_outputs.append(state)
-        return _classify(torch.cat(state_outputs, dim=1), model_input, vocab_size, **unused_params)
+    layer = staticmethod(_gate_lstm_layer)
 
 
 # ---- Z: the input-memory LSTM models (LstmGlu2Model, LstmGlu2MultilayerModel) -----------------------------------------------------
 GLU_LSTM_VARS = ("Wi", "Ui", "Vi", "bi", "Wf", "Vf", "Uf", "bf", "Wog", "Vog", "Uog", "bog", "Wc", "Vc", "Uc", "bc",
                  "Wix", "Vix", "Uix", "bix", "Wfx", "Vfx", "Ufx", "bfx")                       # create_recurrent_unit's order
-
-
-def _glu_lstm_unit(d_in, hidden, l2_penalty):
-    """create_recurrent_unit (Z/frame_level_models.py:695-749) in the current scope: the 24 Variables with the reference's names, shapes
-    and initial values -- weights truncated_normal(stddev=0.1), bi = bog = bc = bix = 0.1, bf = bfx = 1.0 -- every one of them, biases
-    included, under l2_penalty * l2_loss.  W* act on the frame, V* on the l2-normalised input memory, U* on h."""
-    g = get_default_graph()
-
-    def shape(n):
-        if n[0] == "b":
-            return (hidden,) if n in ("bog", "bc") else (1,)
-        return (hidden if n[0] == "U" else d_in, hidden if n[1:] in ("og", "c") else 1)
-
-    inits = {"bi": constant(0.1), "bf": constant(1.0), "bog": constant(0.1), "bc": constant(0.1), "bix": constant(0.1), "bfx": constant(1.0)}
-    return {n: g.get_variable(n, shape(n), inits.get(n, truncated_normal(0.1)), l2=l2_penalty) for n in GLU_LSTM_VARS}
 
 
 def _glu_lstm_layer(x_tm, num_frames, hidden, scope, l2_penalty):
@@ -1343,7 +1348,7 @@ def _glu_lstm_layer(x_tm, num_frames, hidden, scope, l2_penalty):
     num_frames - 1 [B,H])."""
     d_in = x_tm.D if isinstance(x_tm, seq_ops.U8FrameImages) else x_tm.shape[2]
     with get_default_graph().variable_scope(scope):
-        v = {n: ops.as_tensor(var) for n, var in _glu_lstm_unit(d_in, hidden, l2_penalty).items()}
+        v = {n: ops.as_tensor(var) for n, var in _scalar_gate_unit(GLU_LSTM_VARS, d_in, hidden, l2_penalty).items()}
     sc = ("i", "f", "ix", "fx")
     Wv, Vv, Uv = (torch.cat([v[k + "og"], v[k + "c"]], dim=1) for k in "WVU")
     Ws, Vs, Us = (torch.cat([v[k + n] for n in sc], dim=1) for k in "WVU")
@@ -1351,7 +1356,7 @@ def _glu_lstm_layer(x_tm, num_frames, hidden, scope, l2_penalty):
     return seq_ops.glu_lstm_layer(x_tm, Wv, bv, Ws, bs, Vv, Vs, Uv, Us.t(), num_frames)
 
 
-class LstmGlu2Model(models.BaseModel):
+class LstmGlu2Model(_CellLayerModel):
     """Z/frame_level_models.py:631-792: one layer of the input-memory LSTM cell -- the scalar-gate cell (LstmGateModel) with a second
     recurrent state over the INPUT, x_prev' = fx x_prev + ix x under two more scalar gates, whose l2-normalised value enters all six
     gates through V* -- run over all max_frames steps by a tf.while_loop; the head (--video_level_classifier_model) reads the memory
@@ -1359,29 +1364,15 @@ class LstmGlu2Model(models.BaseModel):
     Wc,Vc,Uc,bc,Wix,Vix,Uix,bix,Wfx,Vfx,Ufx,bfx}.  A row with num_frames < 1 hands zeros to the head and receives no gradient (as
     LstmGateModel).  accepts_quantized_input: _hoisted_input -- the layer reads the reader's bytes where the byte products cover the
     shape."""
-    accepts_quantized_input = True
-
-    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
-        x_tm = _hoisted_input(model_input, num_frames)
-        _, state = _glu_lstm_layer(x_tm, num_frames, int(FLAGS.lstm_cells), "lstm_forward", l2_penalty)
-        return _classify(state, model_input, vocab_size, **unused_params)
+    layer = staticmethod(_glu_lstm_layer)
 
 
-class LstmGlu2MultilayerModel(models.BaseModel):
+class LstmGlu2MultilayerModel(_CellMultilayerModel):
     """Z/frame_level_models.py:794-885: --lstm_layers layers of the input-memory cell (rnn_gate, :826-885); layer l + 1 reads all
     max_frames hidden outputs h of layer l, the head reads the layers' gathered memories concatenated (:818).  Layer i's Variables
     live under "lstm_lsyer<i>lstm_forward/" -- the reference's spelling, which checkpoints carry.  Rows with num_frames < 1: as
     LstmGlu2Model.  accepts_quantized_input: _hoisted_input -- layer 0 reads the reader's bytes."""
-    accepts_quantized_input = True
-
-    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
-        hidden_outputs = _hoisted_input(model_input, num_frames)
-        state_outputs = []
-        for i in range(FLAGS.lstm_layers):
-            # rnn_gate takes its own l2_penalty=1e-8 (:826); create_model's is not forwarded to it
-            hidden_outputs, state = _glu_lstm_layer(hidden_outputs, num_frames, int(FLAGS.lstm_cells), "lstm_lsyer%dlstm_forward" % i, 1e-8)
-            state_outputs.append(state)
-        return _classify(torch.cat(state_outputs, dim=1), model_input, vocab_size, **unused_params)
+    layer = staticmethod(_glu_lstm_layer)
 
 
 # ---- Z: the Extend attention models (LstmExtendModel, InputExtendModel) ------------------------------------------------------------

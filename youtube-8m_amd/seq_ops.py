@@ -347,16 +347,30 @@ def _gate_last_memory(cs, num_frames):
     return cs[(nf - 1).clamp(0, F - 1), torch.arange(B, device=cs.device)] * valid
 
 
+def _composed_cell_input(x_tm, Wv, bv, Ws, bs):
+    """The prologue of the composed cells: x_tm as float frames [F,B,D] (U8FrameImages in the bytes' meaning: dequantised, padding
+    zeroed, l2-normalised) and its hoisted projections zv [F,B,2H], zs [F,B,number of scalar gates]."""
+    if isinstance(x_tm, U8FrameImages):
+        x_tm = ops.dequant_l2norm(x_tm.q, x_tm.nf).transpose(0, 1)
+    F, B, D = x_tm.shape
+    x2 = x_tm.reshape(F * B, D)
+    return x_tm, (x2 @ Wv + bv).view(F, B, Wv.shape[1]), (x2 @ Ws + bs).view(F, B, Ws.shape[1])
+
+
+def _cell_frames_shape(x_tm):
+    """(B, D) of frames the cells' step kernels read -- U8FrameImages, or float32 device frames [F,B,D] -- else None."""
+    if isinstance(x_tm, U8FrameImages):
+        return x_tm.B, x_tm.D
+    if x_tm.is_cuda and x_tm.dtype == torch.float32:
+        return x_tm.shape[1], x_tm.shape[2]
+    return None
+
+
 def gate_lstm_layer_composed(x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames):
     """gate_lstm_layer in plain torch under autograd: a Python time loop over all F steps, in the dtype of its operands."""
     GATE_LSTM_CALLS["composed"] += 1
-    if isinstance(x_tm, U8FrameImages):                       # the bytes' meaning: dequantised, padding zeroed, l2-normalised
-        x_tm = ops.dequant_l2norm(x_tm.q, x_tm.nf).transpose(0, 1)
-    F, B, D = x_tm.shape
-    H = Uv.shape[0]
-    x2 = x_tm.reshape(F * B, D)
-    zv = (x2 @ Wv + bv).view(F, B, 2 * H)
-    zs = (x2 @ Ws + bs).view(F, B, 2)
+    x_tm, zv, zs = _composed_cell_input(x_tm, Wv, bv, Ws, bs)
+    (F, B), H = x_tm.shape[:2], Uv.shape[0]
     h = c = torch.zeros((B, H), dtype=zv.dtype, device=zv.device)
     hs, cs = [], []
     for t in range(F):
@@ -454,15 +468,8 @@ class _GateLstmLayer(torch.autograd.Function):
 
 def gate_lstm_supported(x_tm, H):
     """Whether gate_lstm_layer runs x_tm (U8FrameImages, or float frames [F,B,in]) at H cells on the step kernels."""
-    if not GATE_LSTM_FUSED:
-        return False
-    if isinstance(x_tm, U8FrameImages):
-        B = x_tm.B
-    elif x_tm.is_cuda and x_tm.dtype == torch.float32:
-        B = x_tm.shape[1]
-    else:
-        return False
-    return bool(_lib.lib().yt8m_gate_lstm_supported(int(B), int(H)))
+    shape = _cell_frames_shape(x_tm) if GATE_LSTM_FUSED else None
+    return shape is not None and bool(_lib.lib().yt8m_gate_lstm_supported(int(shape[0]), int(H)))
 
 
 def gate_lstm_layer(x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames):
@@ -494,13 +501,8 @@ def glu_lstm_layer_composed(x_tm, Wv, bv, Ws, bs, Vv, Vs, Uv, Us, num_frames):
     """glu_lstm_layer in plain torch under autograd, in the reference's form: a Python time loop over all F steps that carries xm and
     multiplies hx = l2_normalize(xm) by [Vog|Vc] and Vs at every step; in the dtype of its operands."""
     GLU_LSTM_CALLS["composed"] += 1
-    if isinstance(x_tm, U8FrameImages):                       # the bytes' meaning: dequantised, padding zeroed, l2-normalised
-        x_tm = ops.dequant_l2norm(x_tm.q, x_tm.nf).transpose(0, 1)
-    F, B, D = x_tm.shape
-    H = Uv.shape[0]
-    x2 = x_tm.reshape(F * B, D)
-    zv = (x2 @ Wv + bv).view(F, B, 2 * H)
-    zs = (x2 @ Ws + bs).view(F, B, 4)
+    x_tm, zv, zs = _composed_cell_input(x_tm, Wv, bv, Ws, bs)
+    (F, B, D), H = x_tm.shape, Uv.shape[0]
     h = c = torch.zeros((B, H), dtype=zv.dtype, device=zv.device)
     xm = torch.zeros((B, D), dtype=zv.dtype, device=zv.device)
     hs, cs = [], []
@@ -624,15 +626,8 @@ class _GluLstmLayer(torch.autograd.Function):
 
 def glu_lstm_supported(x_tm, H):
     """Whether glu_lstm_layer runs x_tm (U8FrameImages, or float frames [F,B,in]) at H cells on the step kernels."""
-    if not GLU_LSTM_FUSED:
-        return False
-    if isinstance(x_tm, U8FrameImages):
-        B, D = x_tm.B, x_tm.D
-    elif x_tm.is_cuda and x_tm.dtype == torch.float32:
-        B, D = x_tm.shape[1], x_tm.shape[2]
-    else:
-        return False
-    return bool(_lib.lib().yt8m_glu_lstm_supported(int(B), int(H), int(D)))
+    shape = _cell_frames_shape(x_tm) if GLU_LSTM_FUSED else None
+    return shape is not None and bool(_lib.lib().yt8m_glu_lstm_supported(int(shape[0]), int(H), int(shape[1])))
 
 
 def glu_lstm_layer(x_tm, Wv, bv, Ws, bs, Vv, Vs, Uv, Us, num_frames):
@@ -2603,17 +2598,28 @@ def _is_variable(v):
     return hasattr(v, "_graph") and not torch.is_tensor(v)
 
 
+def _attention_fc(src_tm, W, b):
+    """The composed attention forms' FC on the [F B, Hs] view of src_tm: ops.linear on the device when W, b are Variables, else a plain
+    product with their tensors.  Returns [F B, heads]."""
+    F, B, Hs = src_tm.shape
+    if _is_variable(W) and src_tm.is_cuda:
+        return ops.linear(src_tm.reshape(F * B, Hs), W, b)
+    Wt, bt = (ops.as_tensor(v) if _is_variable(v) else v for v in (W, b))
+    return src_tm.reshape(F * B, Hs) @ Wt + bt
+
+
+def _attention_ws(nbytes, dev):
+    """The workspace of an attention kernel call: nbytes as float32 elements, never empty."""
+    return torch.empty((max(nbytes, 16) // 4,), dtype=torch.float32, device=dev)
+
+
 def sigmoid_attention_composed(src_tm, Wa, ba, num_frames, values_tm=None):
     """sigmoid_attention from existing ops, as the reference writes it, in the dtype of its operands: the FC on the [F B, Hs] view
     (ops.linear on the device when Wa, ba are Variables, else a plain product), torch sigmoid / mask / sum / divide, and pool_tn on a
     batch-major copy of the values (an einsum off the device)."""
     SIGMOID_ATTENTION_CALLS["composed"] += 1
-    F, B, Hs = src_tm.shape
-    if _is_variable(Wa) and src_tm.is_cuda:
-        z = ops.linear(src_tm.reshape(F * B, Hs), Wa, ba)
-    else:
-        Wt, bt = (ops.as_tensor(v) if _is_variable(v) else v for v in (Wa, ba))
-        z = src_tm.reshape(F * B, Hs) @ Wt + bt
+    F, B = src_tm.shape[:2]
+    z = _attention_fc(src_tm, Wa, ba)
     A = z.shape[1]
     n = num_frames.to(src_tm.device).to(torch.int64).clamp(0, F)
     mask = (torch.arange(F, device=src_tm.device)[:, None] < n[None, :]).to(z.dtype)              # [F,B]
@@ -2659,7 +2665,7 @@ class _SigmoidAttention(torch.autograd.Function):
         den = torch.empty((B, A), dtype=torch.float32, device=dev)
         pooled = torch.empty((B, A, Hv), dtype=torch.float32, device=dev) if Hv else None
         nbytes = int(lib.yt8m_sigattn_workspace_bytes(B, F, Hs, Hv, A))
-        ws = torch.empty((max(nbytes, 16) // 4,), dtype=torch.float32, device=dev)
+        ws = _attention_ws(nbytes, dev)
         _lib.check(lib.yt8m_sigattn_fwd(_p(src), ld_src, _p(vals), ld_vals, _p(Wa), _p(ba), _p(nf), _p(att), _p(den), _p(pooled), _p(ws),
                                         nbytes, B, F, Hs, Hv, A, _stream()))
         SIGMOID_ATTENTION_CALLS["kernels"] += 1
@@ -2685,7 +2691,7 @@ class _SigmoidAttention(torch.autograd.Function):
         dWa = torch.empty((Hs, A), dtype=torch.float32, device=dev) if need[1] else None
         dba = torch.empty((A,), dtype=torch.float32, device=dev) if need[2] else None
         ld_src, ld_vals = src.stride(1), (vals.stride(1) if vals is not None else 0)
-        ws = torch.empty((max(ctx.nbytes, 16) // 4,), dtype=torch.float32, device=dev)
+        ws = _attention_ws(ctx.nbytes, dev)
         _lib.check(_lib.lib().yt8m_sigattn_bwd(_p(src), ld_src, _p(vals), ld_vals, _p(Wa), _p(ctx.nf), _p(att), _p(den), _p(pooled), _p(G),
                                                _p(E), _p(dsrc), Hs, _p(dvals), Hv, _p(dWa), _p(dba), _p(ws), ctx.nbytes, B, F, Hs, Hv, A,
                                                _stream()))
@@ -2750,12 +2756,8 @@ def softmax_attention_tm_composed(src_tm, W1, b1, values_tm, extra=None, valid=N
     where the reference's softmax-times-mask underflows), and pool_tn on a batch-major copy of the values (an einsum off the device).
     A (b, e) without an unmasked frame gets att = 0 and pooled = 0 and neither receives nor sends a gradient; att is detached."""
     SOFTMAX_ATTENTION_CALLS["composed"] += 1
-    F, B, Hs = src_tm.shape
-    if _is_variable(W1) and src_tm.is_cuda:
-        z = ops.linear(src_tm.reshape(F * B, Hs), W1, b1)
-    else:
-        Wt, bt = (ops.as_tensor(v) if _is_variable(v) else v for v in (W1, b1))
-        z = src_tm.reshape(F * B, Hs) @ Wt + bt
+    F, B = src_tm.shape[:2]
+    z = _attention_fc(src_tm, W1, b1)
     E = z.shape[1]
     z = z.view(F, B, E).permute(1, 0, 2)                                                          # [B,F,E]
     if extra is not None:
@@ -2802,7 +2804,7 @@ class _SoftmaxAttentionTM(torch.autograd.Function):
         att = torch.empty((B, F, E), dtype=torch.float32, device=dev)
         pooled = torch.empty((B, E, Hv), dtype=torch.float32, device=dev)
         nbytes = int(lib.yt8m_smattn_workspace_bytes(B, F, Hs, Hv, E))
-        ws = torch.empty((max(nbytes, 16) // 4,), dtype=torch.float32, device=dev)
+        ws = _attention_ws(nbytes, dev)
         _lib.check(lib.yt8m_smattn_fwd(_p(src), ld_src, _p(vals), ld_vals, _p(W1), _p(b1), _p(extra), _p(valid), _p(lo), _p(hi), _p(att),
                                        _p(pooled), _p(ws), nbytes, B, F, Hs, Hv, E, _stream()))
         SOFTMAX_ATTENTION_CALLS["kernels"] += 1
@@ -2832,7 +2834,7 @@ class _SoftmaxAttentionTM(torch.autograd.Function):
         dextra = torch.empty((B, F, E), dtype=torch.float32, device=dev) if (ctx.has_extra and need[4]) else None
         ld_src = src.stride(1)
         v, ld_vals = (src, ld_src) if shared else (vals, vals.stride(1))
-        ws = torch.empty((max(ctx.nbytes, 16) // 4,), dtype=torch.float32, device=dev)
+        ws = _attention_ws(ctx.nbytes, dev)
         _lib.check(_lib.lib().yt8m_smattn_bwd(_p(src), ld_src, _p(v), ld_vals, _p(W1), _p(valid), _p(lo), _p(hi), _p(att), _p(pooled), _p(G),
                                               _p(dsrc), Hs, _p(dvals), Hv, _p(dW1), _p(db1), _p(dextra), _p(ws), ctx.nbytes, B, F, Hs, Hv, E,
                                               _stream()))
