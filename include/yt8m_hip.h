@@ -523,6 +523,41 @@ int yt8m_gate_lstm_layer_bwd(const float* zv, const float* zs, int64_t lds, cons
                              float* work, const int32_t* num_frames, int64_t F, int64_t B, int64_t H, void* gemm_workspace,
                              int64_t gemm_workspace_bytes, yt8m_stream_t stream);
 
+/* ---- scalar-gate LSTM layer over frames in a per-video order (csrc/bigate_lstm.hip), time-major, generic per-step form ---------
+ * The same cell for LstmBigluModel (Z/frame_level_models.py:887-1158): its first unit (:975-1032) runs over
+ * tf.reverse_sequence(model_input, num_frames) (:906, :923-934) and tf.reverse_sequence of its hidden outputs (:941) enters every
+ * gate of the second unit (:1034-1101), which runs over the frames in order (:952-963).  Here every time-indexed operand the caller
+ * sees is in FRAME order and `reverse` selects the frame that step i of row b visits:
+ *   reverse = 0: r(i, b) = i;   reverse = 1: r(i, b) = n_b - 1 - i while i < n_b, else i -- for every b a bijection of 0..F-1.
+ *   n_b = num_frames[b] clamped to [0, F], the rule of yt8m_reverse_sequence_u8 / _f32_tm: a negative num_frames takes the identity, one
+ *   above F reverses all F frames (as those kernels do: the two forms of a caller that A/Bs against reversed copies then agree).
+ * Step i of row b, with row = r(i, b) B + b:
+ *   zv: rows of stride ldz >= 2H, 2H columns from the pointer given (a column window of a wider buffer will do): in = x.[Wog|Wc] +
+ *     [bog|bc] of frame r (hoisted by the caller), out = the activations o | g, in place; zs: rows of stride lds >= 2, columns 0 and 1
+ *     from the pointer given: in = x.[Wi|Wf] + [bi|bf], out = i | f.  No other column of either row is read or written;
+ *   Uv = [Uog|Uc] [H,2H] with leading dimension ldu, Us [2,H] = the rows Ui, Uf;
+ *   y [F,B,H]: h_{i+1} at frame r -- the layer's output in frame order; hprev [F,B,H]: h_i, the state the step came from, at frame r
+ *     (the U gradients are products of frame-order tensors; under reverse, hprev is not a shifted view of y);
+ *   cs [F+1,B,H] in STEP order, row 0 = the initial memory (zeroed by the caller), row i + 1 = the memory after step i;
+ *   c_last [B,H] (optional) receives cs[num_frames[b]][b], written by the step with i + 1 == num_frames[b]; zeros for rows with
+ *     num_frames[b] < 1 or > F;
+ *   work >= 4 B H floats (forward: h in step order, two buffers, and the recurrent product of one step [B,2H], written with beta = 0).
+ *   num_frames may be NULL only with reverse = 0 and without c_last / dc_last.  Every row of y, hprev, zv, zs is written exactly once.
+ * Backward, steps F-1 .. 0: dy [F,B,H] (optional, w.r.t. y, frame order), dc_last [B,H] (optional) -> the dzv row of step i at
+ * (r B + b) lddz (lddz >= 2H, 2H columns from the pointer given) and the dzs row at (r B + b) ldds (ldds >= 2, columns 0 and 1);
+ * work >= 6 B H floats (the running gradients and a contiguous [B,2H] copy of the step's dzv rows for dz . [Uog|Uc]^T, which runs on
+ * the packed step launcher unless YT8M_GATE_LSTM_PACKED_BWD=0, read at every call, keeps the grouped GEMM).  A step at or past a
+ * row's num_frames with nothing arriving through dy yields exact zeros.  No atomics: reruns are bit-equal.
+ * yt8m_gate_lstm_frames_supported: H % 256 == 0, H <= 2048; both entry points refuse other shapes with YT8M_E_SHAPE. */
+int yt8m_gate_lstm_frames_supported(int64_t B, int64_t H);
+int yt8m_gate_lstm_frames_fwd(float* zv, int64_t ldz, float* zs, int64_t lds, const float* Uv, int64_t ldu, const float* Us, float* y,
+                              float* hprev, float* cs, float* c_last, float* work, const int32_t* num_frames, int reverse, int64_t F,
+                              int64_t B, int64_t H, void* gemm_workspace, int64_t gemm_workspace_bytes, yt8m_stream_t stream);
+int yt8m_gate_lstm_frames_bwd(const float* zv, int64_t ldz, const float* zs, int64_t lds, const float* Uv, int64_t ldu, const float* Us,
+                              const float* cs, const float* dy, const float* dc_last, float* dzv, int64_t lddz, float* dzs,
+                              int64_t ldds, float* work, const int32_t* num_frames, int reverse, int64_t F, int64_t B, int64_t H,
+                              void* gemm_workspace, int64_t gemm_workspace_bytes, yt8m_stream_t stream);
+
 /* ---- input-memory LSTM layer (csrc/glu_lstm.hip), time-major, generic per-step form ------------------------------------
  * The recurrent unit of Z/frame_level_models.py:695-792 (LstmGlu2Model; LstmGlu2MultilayerModel :794-885) under a plain tf.while_loop
  * over all F steps -- no copy-through, no masking; every state starts at 0.  Beside h and c the cell carries xm [B,D], a memory of

@@ -1,0 +1,258 @@
+"""CPU checks of LstmBigluModel (Z/frame_level_models.py:887-1158) and of the frame-order scalar-gate recurrence's C ABI
+(csrc/bigate_lstm.hip): the lookup by name, the 12 + 16 + 3 Variables (order, names, shapes, l2, initial values), the head's names,
+the header / signature table / exports, argument validation without a device, and the composed form of seq_ops.bigate_lstm_layer and
+the model on the CPU against the fp64 restatement (tests/bigate_lstm_restatement.py), which makes the reference's reverse_sequence copies."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import bigate_lstm_restatement as R
+import yt8m_amd._lib as L
+from conftest import ROOT
+
+SYMBOLS = ("yt8m_gate_lstm_frames_supported", "yt8m_gate_lstm_frames_fwd", "yt8m_gate_lstm_frames_bwd")
+HEAD = ["gatesbackward/weights", "expertsbackward/weights", "expertsbackward/biases"]
+
+
+def test_find_class_by_name_resolves_the_model():
+    import yt8m_amd.frame_level_models as flm
+    import yt8m_amd.train as train
+    import yt8m_amd.video_level_models as vlm
+    cls = train.find_class_by_name("LstmBigluModel", [flm, vlm])
+    assert cls is flm.LstmBigluModel and not hasattr(vlm, "LstmBigluModel")
+    assert cls.accepts_quantized_input is True
+    assert not hasattr(flm, "LstmBiglu2Model")                           # named as not built, with its reason
+    src = open(os.path.join(ROOT, "youtube-8m_amd", "frame_level_models.py")).read()
+    assert "LstmBiglu2Model:" in src and "LstmBiglu*:" not in src
+
+
+def test_library_exports_and_header_declares_the_frame_order_symbols():
+    src = open(os.path.join(ROOT, "include", "yt8m_hip.h")).read()
+    lib = L.lib()
+    for name in SYMBOLS:
+        assert re.search(r"\bint\s+%s\s*\(" % name, src), name
+        assert name in L.SIGNATURES
+        assert getattr(lib, name) is not None
+    assert "Z/frame_level_models.py:887-1158" in src and "yt8m_reverse_sequence_u8" in src
+    assert L.ABI_VERSION == 4 and lib.yt8m_abi_version() == 4            # symbols were added, nothing else moved
+    for name in ("yt8m_gate_lstm_supported", "yt8m_gate_lstm_layer_fwd", "yt8m_gate_lstm_layer_bwd"):
+        assert name in L.SIGNATURES and getattr(lib, name) is not None   # the step-order entry points stay
+
+
+def test_supported_states_the_kernels_limits():
+    lib = L.lib()
+    for B, H, ok in ((128, 1024, 1), (3, 256, 1), (5, 2048, 1), (1, 512, 1), (128, 192, 0), (128, 2304, 0), (128, 0, 0), (0, 1024, 0),
+                     (128, 128, 0), (128, 2048 + 256, 0)):
+        assert lib.yt8m_gate_lstm_frames_supported(B, H) == ok, (B, H)
+        assert lib.yt8m_gate_lstm_frames_supported(B, H) == lib.yt8m_gate_lstm_supported(B, H)
+
+
+def test_argument_validation_without_device():
+    """Every call here fails validation or has nothing to do: nothing is launched and no device is needed."""
+    lib = L.lib()
+    OK, BADARG, SHAPE = 0, -1, -2
+    p = [ctypes.c_void_p(256 * k) for k in range(1, 20)]
+    H = 256
+
+    def fwd(zv=p[0], ldz=2 * H, zs=p[1], lds=2, Uv=p[2], ldu=2 * H, Us=p[3], y=p[4], hprev=p[5], cs=p[6], c_last=p[7], work=p[8], nf=p[9],
+            reverse=1, F=4, B=3, H=H):
+        return lib.yt8m_gate_lstm_frames_fwd(zv, ldz, zs, lds, Uv, ldu, Us, y, hprev, cs, c_last, work, nf, reverse, F, B, H, None, 0, None)
+
+    def bwd(zv=p[0], ldz=2 * H, zs=p[1], lds=2, Uv=p[2], ldu=2 * H, Us=p[3], cs=p[6], dy=p[10], dc_last=p[11], dzv=p[12], lddz=2 * H,
+            dzs=p[13], ldds=2, work=p[8], nf=p[9], reverse=1, F=4, B=3, H=H):
+        return lib.yt8m_gate_lstm_frames_bwd(zv, ldz, zs, lds, Uv, ldu, Us, cs, dy, dc_last, dzv, lddz, dzs, ldds, work, nf, reverse, F, B, H,
+                                             None, 0, None)
+
+    for call in (fwd, bwd):
+        assert call(F=-1) == SHAPE and call(B=-1) == SHAPE and call(H=-256) == SHAPE           # negative size
+        assert call(ldu=2 * H - 1) == SHAPE                                                     # small ldu
+        assert call(ldz=2 * H - 1) == SHAPE and call(ldz=0) == SHAPE                            # ldz < 2H
+        assert call(lds=1) == SHAPE and call(lds=0) == SHAPE                                    # lds < 2
+        assert call(H=192, ldu=384, ldz=384) == SHAPE and call(H=2304, ldu=4608, ldz=4608) == SHAPE       # what _supported refuses
+        for name in ("zv", "zs", "Uv", "Us", "cs", "work"):
+            assert call(**{name: None}) == BADARG, name                                         # null operand
+        for r in (-1, 2, 7):
+            assert call(reverse=r) == BADARG, r                                                 # reverse outside {0, 1}
+        assert call(F=0) == OK and call(B=0) == OK and call(H=0) == OK                          # nothing to do
+        assert call(F=0, zv=None, zs=None, Uv=None, Us=None, cs=None, work=None, nf=None, reverse=5, ldz=0) == OK    # ... before anything else
+        # num_frames may be null only with reverse = 0 and without c_last / dc_last
+        assert call(nf=None) == BADARG and call(nf=None, reverse=0) == BADARG
+    assert fwd(nf=None, c_last=None, reverse=1) == BADARG and bwd(nf=None, dc_last=None, reverse=1) == BADARG
+    for name in ("y", "hprev"):
+        assert fwd(**{name: None}) == BADARG, name
+    for name in ("dzv", "dzs"):
+        assert bwd(**{name: None}) == BADARG, name
+    assert bwd(lddz=2 * H - 1) == SHAPE and bwd(lddz=0) == SHAPE and bwd(ldds=1) == SHAPE       # the gradients' leading dimensions
+    assert b"gate_lstm_frames" in lib.yt8m_last_error()
+
+
+# ---- the plugin's Variables on the CPU graph ----------------------------------------------------------------------------------------
+def _graph():
+    from yt8m_amd.variables import reset_default_graph
+    return reset_default_graph(device=torch.device("cpu"), seed=0)
+
+
+def _stub_head(monkeypatch):
+    """ops.moe_head has no CPU form: the MoE of the restatement on the Variables' data stands in for it."""
+    import yt8m_amd.ops as ops
+    monkeypatch.setattr(ops, "moe_head", lambda x, Wg, We, be, V_, M_, **k: R.moe(x, Wg.data, We.data, be.data, M_))
+
+
+def test_lstm_biglu_model_variables(monkeypatch, flags):
+    import yt8m_amd.frame_level_models as flm
+    _stub_head(monkeypatch)
+    H, M = 16, 2
+    flags.lstm_cells, flags.moe_num_mixtures = str(H), M
+    flags.video_level_classifier_model = "LogisticModel"                 # the head is the model's own MoE whatever this flag says
+    g = _graph()
+    B, F, D, V = 3, 5, 8, 10
+    res = flm.LstmBigluModel().create_model(torch.randn(B, F, D), vocab_size=V, num_frames=torch.tensor([5, 1, 3]))
+    assert tuple(res["predictions"].shape) == (B, V)
+    names = ["lstm_forward/" + n for n in R.NAMES_FW] + ["lstm_backward/" + n for n in R.NAMES_BW] + HEAD
+    assert list(g.vars) == names and len(names) == 28 + 3
+    for scope, unit in (("lstm_forward", R.NAMES_FW), ("lstm_backward", R.NAMES_BW)):
+        for n, shape in R.shapes(unit, D, H).items():
+            v = g.vars["%s/%s" % (scope, n)]
+            assert tuple(v.data.shape) == shape and v.l2 == 1e-8 and v.trainable, (scope, n)
+            if n[0] == "b":
+                assert bool((v.data == np.float32(0.1)).all()), (scope, n)                     # bf too: :988, :1051
+            else:
+                assert float(v.data.abs().max()) <= 0.2 + 1e-7, (scope, n)                     # truncated at two stddev of 0.1
+                if v.data.numel() >= 64:
+                    assert float(v.data.std()) > 0.03, (scope, n)
+    for n in ("Vi", "Vf", "Vog", "Vc"):
+        assert g.vars["lstm_backward/" + n].data.shape[0] == H                                  # V* act on y, not on the input
+    assert tuple(g.vars["gatesbackward/weights"].data.shape) == (2 * H, V * (M + 1))             # [c1 | c2]
+    assert tuple(g.vars["expertsbackward/weights"].data.shape) == (2 * H, V * M)
+    assert tuple(g.vars["expertsbackward/biases"].data.shape) == (V * M,)
+    assert g.vars["gatesbackward/weights"].l2 == 1e-8 and g.vars["expertsbackward/weights"].l2 == 1e-8
+
+
+def test_scalar_gate_unit_arguments_and_their_defaults(flags):
+    """The arguments LstmBigluModel added: forget_bias and v_rows do what they say, and their defaults keep LstmGateModel's and
+    LstmGlu2Model's units as they were (bf = 1.0, V* d_in tall)."""
+    import yt8m_amd.frame_level_models as flm
+    g = _graph()
+    with g.variable_scope("a"):
+        v = flm._scalar_gate_unit(flm.GLU_LSTM_VARS, 8, 16, 1e-8)
+    assert float(v["bf"].data) == 1.0 and float(v["bfx"].data) == 1.0 and tuple(v["Vog"].data.shape) == (8, 16)
+    with g.variable_scope("b"):
+        v = flm._scalar_gate_unit(flm.BIGATE_LSTM_BW_VARS, 8, 16, 1e-8, forget_bias=0.1, v_rows=16)
+    assert list(v) == list(R.NAMES_BW) and float(v["bf"].data) == np.float32(0.1)
+    assert tuple(v["Vog"].data.shape) == (16, 16) and tuple(v["Vi"].data.shape) == (16, 1) and tuple(v["Wog"].data.shape) == (8, 16)
+
+
+# ---- the composed form against the restatement ------------------------------------------------------------------------------------
+F_, B_, D_, H_ = 6, 3, 8, 16
+OPERANDS = ("Wv", "bv", "Ws", "bs", "Uv1", "Us1", "Vv", "Vs", "Uv2", "Us2")
+
+
+def _case(seed):
+    rs = np.random.RandomState(seed)
+    Pf, Pb = R.random_unit(rs, R.NAMES_FW, D_, H_), R.random_unit(rs, R.NAMES_BW, D_, H_)
+    x = rs.randn(F_, B_, D_).astype(np.float32)
+    grads = [rs.randn(F_, B_, H_).astype(np.float32), rs.randn(F_, B_, H_).astype(np.float32), rs.randn(B_, H_).astype(np.float32),
+             rs.randn(B_, H_).astype(np.float32)]
+    return Pf, Pb, x, grads
+
+
+def _run_op(x, Pf, Pb, nf, grads):
+    import yt8m_amd.seq_ops as seq_ops
+    Pft, Pbt = R.to_torch(Pf, torch.float64, True), R.to_torch(Pb, torch.float64, True)
+    xt = torch.from_numpy(x).double().requires_grad_(True)
+    outs = seq_ops.bigate_lstm_layer(xt, *R.operands(Pft, Pbt), torch.tensor(nf))
+    sum((o * torch.from_numpy(g).double()).sum() for o, g in zip(outs, grads)).backward()           # through all four returns
+    got = dict(zip(("y", "out2", "c1_last", "c2_last"), outs), dx=xt.grad)
+    got.update({"dfw/" + n: Pft[n].grad for n in R.NAMES_FW})
+    got.update({"dbw/" + n: Pbt[n].grad for n in R.NAMES_BW})
+    return got
+
+
+@pytest.mark.parametrize("nf", [[6, 1, 3], [0, 6, 2]])
+def test_composed_form_matches_the_restatement_in_fp64(nf):
+    import yt8m_amd.seq_ops as seq_ops
+    Pf, Pb, x, grads = _case(11)
+    ref = R.layer_with_grads(x, nf, Pf, Pb, *grads, torch.float64)
+    before = dict(seq_ops.BIGATE_LSTM_CALLS)
+    got = _run_op(x, Pf, Pb, nf, grads)
+    assert seq_ops.BIGATE_LSTM_CALLS["composed"] == before["composed"] + 1
+    assert all(seq_ops.BIGATE_LSTM_CALLS[k] == before[k] for k in ("frame_order", "reversed_copies"))
+    assert tuple(got["y"].shape) == (F_, B_, H_) and tuple(got["out2"].shape) == (F_, B_, H_)
+    assert tuple(got["c1_last"].shape) == (B_, H_) and tuple(got["c2_last"].shape) == (B_, H_)
+    assert set(ref) == set(got) and len(ref) == 5 + 28
+    for k in ref:
+        assert R.err(got[k], ref[k]) < 1e-12, k
+        assert float(np.abs(ref[k]).max()) > 0.0, k
+    for b, n in enumerate(nf):
+        if n < 1:
+            assert float(got["c1_last"][b].detach().abs().max()) == 0.0 and float(got["c2_last"][b].detach().abs().max()) == 0.0
+    if 0 in nf:
+        # the dead row's dc1_last / dc2_last reach no gradient: the same gradient bits with other values in that row
+        b0 = nf.index(0)
+        grads2 = [g.copy() for g in grads]
+        grads2[2][b0] += 5.0
+        grads2[3][b0] -= 3.0
+        got2 = _run_op(x, Pf, Pb, nf, grads2)
+        for k in got:
+            if k.startswith("d"):
+                assert torch.equal(got2[k], got[k]), k
+        ref2 = R.layer_with_grads(x, nf, Pf, Pb, *grads2, torch.float64)
+        assert R.err(got2["dx"], ref2["dx"]) < 1e-12
+
+
+def test_frame_order_equals_reversed_copies_bit_for_bit_in_fp64():
+    """The claim the kernels rest on: pass 1 reading frame r(i, b) and writing y[r(i, b), b] is the recurrence over reverse_sequence
+    copies.  Both restated on the CPU in fp64 (the row map as an index table here, flips in the restatement): equal bits; and the op's
+    composed form, which makes the copies by an index table of its own, gives the same y."""
+    import yt8m_amd.seq_ops as seq_ops
+    Pf, Pb, x, _ = _case(5)
+    nf = [0, F_, F_ // 2]
+    P = R.to_torch(Pf, torch.float64)
+    xt = torch.from_numpy(x).double()
+    ref = R.model_states(xt.transpose(0, 1), torch.tensor(nf), P, R.to_torch(Pb, torch.float64))[2].transpose(0, 1)      # y [F,B,H]
+    assert R.err(seq_ops.bigate_lstm_layer(xt, *R.operands(P, R.to_torch(Pb, torch.float64)), torch.tensor(nf))[0], ref.numpy()) < 1e-12
+    # num_frames outside 0..F: clamped, as yt8m_reverse_sequence_u8 clamps it (-1: the identity; F + 2: all F frames reversed)
+    rev = seq_ops._reverse_sequence_tm_torch(xt, torch.tensor([-1, F_ + 2, 2]))
+    assert torch.equal(rev, R.reverse_sequence(xt.transpose(0, 1), [-1, F_ + 2, 2]).transpose(0, 1))
+    assert torch.equal(rev[:, 0], xt[:, 0]) and torch.equal(rev[:, 1], xt[:, 1].flip(0))
+    y = torch.zeros((F_, B_, H_), dtype=torch.float64)
+    h = c = torch.zeros((B_, H_), dtype=torch.float64)
+    rows = torch.arange(B_)
+    for i in range(F_):
+        r = torch.tensor([n - 1 - i if i < n else i for n in nf])
+        _, _, _, _, c, h = R.forward_unit(xt[r, rows], h, c, P)
+        y[r, rows] = h
+    assert torch.equal(y, ref)
+
+
+def test_lstm_biglu_model_on_cpu_matches_restatement_and_moe_head(monkeypatch, flags):
+    import yt8m_amd.frame_level_models as flm
+    _stub_head(monkeypatch)
+    V, M = 10, 2
+    flags.lstm_cells, flags.moe_num_mixtures = str(H_), M
+    g = _graph()
+    rs = np.random.RandomState(12)
+    x = torch.from_numpy(rs.randn(B_, F_, D_).astype(np.float32))
+    nf = torch.tensor([6, 1, 3])
+    p = flm.LstmBigluModel().create_model(x, vocab_size=V, num_frames=nf)["predictions"]
+    head = lambda: [g.vars[k].data.double() for k in HEAD]
+    units = lambda grad: ({n: g.vars["lstm_forward/" + n].data.double().requires_grad_(grad) for n in R.NAMES_FW},
+                          {n: g.vars["lstm_backward/" + n].data.double().requires_grad_(grad) for n in R.NAMES_BW})
+    want = R.model_forward(x.double(), nf, *units(False), *head(), M)
+    assert R.err(p, want.numpy()) < 2e-6
+    # and the gradient lands in every one of the 28 Variables' slots
+    g.finalize()
+    g.begin_step()
+    p = flm.LstmBigluModel().create_model(x, vocab_size=V, num_frames=nf)["predictions"]
+    Pf, Pb = units(True)
+    go = torch.from_numpy(rs.randn(B_, V).astype(np.float32))
+    (R.model_forward(x.double(), nf, Pf, Pb, *head(), M) * go.double()).sum().backward()
+    (p * go).sum().backward()
+    for scope, P in (("lstm_forward", Pf), ("lstm_backward", Pb)):
+        for n, t in P.items():
+            assert float(t.grad.abs().max()) > 0.0, (scope, n)
+            assert R.err(g.vars["%s/%s" % (scope, n)].grad, t.grad.numpy()) < 5e-6, (scope, n)

@@ -164,6 +164,10 @@ SIGNATURES = {
     "yt8m_gate_lstm_layer_fwd": (c_int, [P, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int64, c_int64, P, c_int64, P]),
     "yt8m_gate_lstm_layer_bwd": (c_int, [P, P, c_int64, P, c_int64, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, P, c_int64,
                                          P]),
+    "yt8m_gate_lstm_frames_supported": (c_int, [c_int64, c_int64]),
+    "yt8m_gate_lstm_frames_fwd": (c_int, [P, c_int64, P, c_int64, P, c_int64] + [P] * 7 + [c_int] + [c_int64] * 3 + [P, c_int64, P]),
+    "yt8m_gate_lstm_frames_bwd": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, P, c_int64, P, P, c_int] +
+                                          [c_int64] * 3 + [P, c_int64, P]),
     "yt8m_glu_lstm_supported": (c_int, [c_int64, c_int64, c_int64]),
     "yt8m_glu_lstm_layer_fwd": (c_int, [P, P, c_int64, P, c_int64, P, c_int64] + [P] * 12 + [c_int64] * 4 + [P, c_int64, P]),
     "yt8m_glu_lstm_layer_bwd": (c_int, [P, P, c_int64, P, c_int64, P, c_int64] + [P] * 14 + [c_int64] + [P] * 4 + [c_int64] * 4 +

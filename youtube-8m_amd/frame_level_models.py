@@ -1245,7 +1245,7 @@ class GatedNetVLADAttentionChainModel(GatedNetVLADModel):
 # ---- Z = youtube-8m-zhangteng: the scalar-gate LSTM models ------------------------------------------------------------------------
 # Not built from Z/frame_level_models.py (one line each):
 #   MoeDistillChain* heads: Z's video-level chain heads, a separate family from --video_level_classifier_model's;
-#   LstmBiglu*: a gate layer on reversed frames feeding a layer with a second hoisted input;
+#   LstmBiglu2Model: LstmBigluModel's pair of passes on LstmGlu2Model's input-memory cell (:1160), and not in the final submission's list;
 #   LstmMultiscale3Model: LstmMultiscale2Model on LstmGlu2Model's input-memory cell with the HIDDEN state gathered at frame num_frames - 1,
 #   not the memory (:3375, :3507): seq_ops.glu_lstm_layer hands back the gathered memory only, so it needs a second gather and its gradient;
 #   LstmMultiscaleRebuildModel: a second training stage that fits ensemble_weight2d alone behind stop_gradient on restored scales; it has
@@ -1260,20 +1260,22 @@ class GatedNetVLADAttentionChainModel(GatedNetVLADModel):
 GATE_LSTM_VARS = ("Wi", "Ui", "bi", "Wf", "Uf", "bf", "Wog", "Uog", "bog", "Wc", "Uc", "bc")      # create_recurrent_unit's order
 
 
-def _scalar_gate_unit(names, d_in, hidden, l2_penalty):
+def _scalar_gate_unit(names, d_in, hidden, l2_penalty, forget_bias=1.0, v_rows=None):
     """create_recurrent_unit of the scalar-gate cell (Z/frame_level_models.py:1583-1611, :1733-1761: GATE_LSTM_VARS) and of the
     input-memory cell (:695-749: GLU_LSTM_VARS) in the current scope: the Variables `names`, in that order, with the reference's names,
-    shapes and initial values -- weights truncated_normal(stddev=0.1), the forget biases bf = bfx = 1.0, the other biases 0.1 -- every
-    one of them, biases included, under l2_penalty * l2_loss.  W* act on the frame, V* on the l2-normalised input memory, U* on h; the
-    output gate "og" and the candidate "c" are `hidden` wide, every other gate is one scalar per video."""
+    shapes and initial values -- weights truncated_normal(stddev=0.1), the forget biases bf = bfx = forget_bias, the other biases 0.1
+    -- every one of them, biases included, under l2_penalty * l2_loss.  W* act on the frame, V* on the l2-normalised input memory
+    (v_rows None: d_in rows) or on whatever v_rows-wide tensor the calling cell feeds them, U* on h; the output gate "og" and the
+    candidate "c" are `hidden` wide, every other gate is one scalar per video."""
     g = get_default_graph()
 
     def shape(n):
         width = hidden if n[1:] in ("og", "c") else 1
-        return (width,) if n[0] == "b" else (hidden if n[0] == "U" else d_in, width)
+        rows = hidden if n[0] == "U" else (v_rows if n[0] == "V" and v_rows is not None else d_in)
+        return (width,) if n[0] == "b" else (rows, width)
 
     def init(n):
-        return truncated_normal(0.1) if n[0] != "b" else constant(1.0 if n in ("bf", "bfx") else 0.1)
+        return truncated_normal(0.1) if n[0] != "b" else constant(forget_bias if n in ("bf", "bfx") else 0.1)
 
     return {n: g.get_variable(n, shape(n), init(n), l2=l2_penalty) for n in names}
 
@@ -1334,6 +1336,43 @@ class LstmGateMultilayerModel(_CellMultilayerModel):
     live under "lstm_lsyer<i>lstm_forward/" -- the reference's spelling, which checkpoints carry.  Rows with num_frames < 1: as
     LstmGateModel.  accepts_quantized_input: _hoisted_input -- layer 0 reads the reader's bytes."""
     layer = staticmethod(_gate_lstm_layer)
+
+
+BIGATE_LSTM_BW_VARS = ("Wi", "Ui", "Vi", "bi", "Wf", "Vf", "Uf", "bf", "Wog", "Vog", "Uog", "bog", "Wc", "Vc", "Uc", "bc")   # :1036-1070
+
+
+class LstmBigluModel(models.BaseModel):
+    """Z/frame_level_models.py:887-1158: two passes of the scalar-gate LSTM cell, each a tf.while_loop over all max_frames steps.  The
+    first (create_forward_recurrent_unit, Variables lstm_forward/{Wi,Ui,bi,Wf,Uf,bf,Wog,Uog,bog,Wc,Uc,bc}) reads
+    tf.reverse_sequence(model_input, num_frames); tf.reverse_sequence of its hidden outputs, y, enters every gate of the second
+    (create_backward_recurrent_unit, lstm_backward/{Wi,Ui,Vi,bi,Wf,Vf,Uf,bf,Wog,Vog,Uog,bog,Wc,Vc,Uc,bc}) through V*, which runs over
+    the frames in order.  The head is the model's own sub_moe (--moe_num_mixtures, gatesbackward / expertsbackward; never
+    --video_level_classifier_model) on [c1 | c2], both memories gathered at step num_frames - 1 (:939-943, :967-968).  H = --lstm_cells.
+    Against LstmGateModel: bf starts at 0.1 in both units (:988, :1051), V* are [H,1] / [H,H] (they act on y), and sub_moe takes its
+    own l2_penalty of 1e-8.  A row with num_frames < 1 hands zeros to the head and receives no gradient (as LstmGateModel).
+    accepts_quantized_input: _hoisted_input -- both passes read the reader's bytes through one operand image where the byte products
+    cover the shape (seq_ops.bigate_lstm_layer)."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
+        hidden = int(FLAGS.lstm_cells)
+        x_tm = _hoisted_input(model_input, num_frames)
+        d_in = x_tm.D if isinstance(x_tm, seq_ops.U8FrameImages) else x_tm.shape[2]
+        g = get_default_graph()
+        with g.variable_scope("lstm_forward"):
+            fw = {n: ops.as_tensor(var) for n, var in _scalar_gate_unit(GATE_LSTM_VARS, d_in, hidden, l2_penalty, forget_bias=0.1).items()}
+        with g.variable_scope("lstm_backward"):
+            bw = {n: ops.as_tensor(var) for n, var in
+                  _scalar_gate_unit(BIGATE_LSTM_BW_VARS, d_in, hidden, l2_penalty, forget_bias=0.1, v_rows=hidden).items()}
+        # the units' Variables as views into the op's operands, as _gate_lstm_layer: the gradients come back through the same glue
+        Wv, bv = torch.cat([fw["Wog"], fw["Wc"], bw["Wog"], bw["Wc"]], dim=1), torch.cat([fw["bog"], fw["bc"], bw["bog"], bw["bc"]])
+        Ws, bs = torch.cat([fw["Wi"], fw["Wf"], bw["Wi"], bw["Wf"]], dim=1), torch.cat([fw["bi"], fw["bf"], bw["bi"], bw["bf"]])
+        Uv1, Us1 = torch.cat([fw["Uog"], fw["Uc"]], dim=1), torch.cat([fw["Ui"], fw["Uf"]], dim=1).t()
+        Uv2, Us2 = torch.cat([bw["Uog"], bw["Uc"]], dim=1), torch.cat([bw["Ui"], bw["Uf"]], dim=1).t()
+        Vv, Vs = torch.cat([bw["Vog"], bw["Vc"]], dim=1), torch.cat([bw["Vi"], bw["Vf"]], dim=1)
+        _, _, c1, c2 = seq_ops.bigate_lstm_layer(x_tm, Wv, bv, Ws, bs, Uv1, Us1, Vv, Vs, Uv2, Us2, num_frames)
+        # sub_moe(moe_input, vocab_size, scopename="backward") (:970, :1104-1158): its own l2_penalty = 1e-8, "gates" + scopename
+        return {"predictions": moe_stage(torch.cat([c1, c2], dim=1), vocab_size, l2_penalty=1e-8, sub_scope="backward", hyphen=False)}
 
 
 # ---- Z: the input-memory LSTM models (LstmGlu2Model, LstmGlu2MultilayerModel) -----------------------------------------------------

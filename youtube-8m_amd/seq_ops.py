@@ -489,6 +489,262 @@ def gate_lstm_layer(x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames):
     return gate_lstm_layer_composed(x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames)
 
 
+# ---- the scalar-gate pair of LstmBigluModel (Z/frame_level_models.py:887-1158; csrc/bigate_lstm.hip) -----------------------------
+BIGATE_LSTM_FUSED = os.environ.get("YT8M_BIGATE_LSTM_FUSED", "1") != "0"   # 0: the composed torch form everywhere (A/B runs, tests)
+# The form the kernels run in.  0: frame order -- the first pass walks every video's frames backwards inside the kernels, ONE byte
+# image, ONE [D,4H] and ONE [D,4] hoisted product for both passes, nothing reversed anywhere.  1: reversed copies -- the first pass
+# runs in step order over a reversed copy of the frames with an operand image and hoisted products of its own, and y and its gradient
+# are reversed by the copy kernel.  The default follows the project's rule (tools/bigate_lstm_step.py, DESIGN_LOG.md 37).
+BIGATE_LSTM_REVERSED = os.environ.get("YT8M_BIGATE_LSTM_REVERSED", "0") != "0"
+BIGATE_LSTM_CALLS = {"frame_order": 0, "reversed_copies": 0, "composed": 0}     # which form ran (tests assert it)
+
+
+def _reverse_sequence_tm_torch(x, num_frames):
+    """tf.reverse_sequence on time-major x [F,B,...] in plain torch (any device and dtype, under autograd); num_frames clamped to 0..F
+    as the copy kernels clamp it."""
+    F, B = x.shape[:2]
+    t = torch.arange(F, device=x.device).unsqueeze(1)
+    n = num_frames.to(device=x.device, dtype=torch.int64).clamp(0, F).unsqueeze(0)
+    return x[torch.where(t < n, n - 1 - t, t), torch.arange(B, device=x.device).unsqueeze(0)]
+
+
+def _bigate_pass_composed(x, y, W, b, Wsc, bsc, V, Vsc, Uv, Us):
+    """One while_loop of LstmBigluModel over x [F,B,D] (and y [F,B,H] through V* where given), in the reference's order of operations
+    x.W + y.V + h.U + b: every step's h and c, [F,B,H] each."""
+    (F, B), H = x.shape[:2], Uv.shape[0]
+    h = c = torch.zeros((B, H), dtype=x.dtype, device=x.device)
+    hs, cs = [], []
+    for t in range(F):
+        s, v = x[t] @ Wsc, x[t] @ W
+        if y is not None:
+            s, v = s + y[t] @ Vsc, v + y[t] @ V
+        s = torch.sigmoid(s + h @ Us.t() + bsc)
+        v = v + h @ Uv + b
+        o, g = torch.sigmoid(v[:, :H]), torch.tanh(v[:, H:])
+        c = s[:, 1:2] * c + s[:, 0:1] * g
+        h = o * torch.tanh(c)
+        hs.append(h)
+        cs.append(c)
+    return torch.stack(hs), torch.stack(cs)
+
+
+def bigate_lstm_layer_composed(x_tm, Wv, bv, Ws, bs, Uv1, Us1, Vv, Vs, Uv2, Us2, num_frames):
+    """bigate_lstm_layer in plain torch under autograd, in the reference's form: two Python time loops over all F steps WITH the two
+    reverse_sequence copies (of the frames and of the first pass' hidden outputs); in the dtype of its operands."""
+    BIGATE_LSTM_CALLS["composed"] += 1
+    if isinstance(x_tm, U8FrameImages):
+        x_tm = ops.dequant_l2norm(x_tm.q, x_tm.nf).transpose(0, 1)
+    H = Uv1.shape[0]
+    bv, bs = bv.reshape(-1), bs.reshape(-1)
+    h1, cs1 = _bigate_pass_composed(_reverse_sequence_tm_torch(x_tm, num_frames), None, Wv[:, :2 * H], bv[:2 * H], Ws[:, :2], bs[:2],
+                                    None, None, Uv1, Us1)
+    y = _reverse_sequence_tm_torch(h1, num_frames)
+    out2, cs2 = _bigate_pass_composed(x_tm, y, Wv[:, 2 * H:], bv[2 * H:], Ws[:, 2:], bs[2:], Vv, Vs, Uv2, Us2)
+    return y, out2, _gate_last_memory(cs1, num_frames), _gate_last_memory(cs2, num_frames)
+
+
+def _pad4(W, b, dev):
+    """[D,2], [2] -> zero-padded to _GATE_U8_LDS columns: the scalar block of ONE pass as a byte product wants it"""
+    Wp = torch.zeros((W.shape[0], _GATE_U8_LDS), dtype=torch.float32, device=dev)
+    bp = torch.zeros((_GATE_U8_LDS,), dtype=torch.float32, device=dev)
+    Wp[:, :2].copy_(W)
+    bp[:2].copy_(b)
+    return Wp, bp
+
+
+class _BigateLstmLayer(torch.autograd.Function):
+    """Both passes of LstmBigluModel on the frame-order step kernels (yt8m_gate_lstm_frames_fwd / _bwd hold the time loops); the
+    parameters are tensors under autograd.  A pass owns a column window (zv [F B, 2H], zs [F B, 2]) of the hoisted pre-activations; the
+    kernels take windows of wider buffers.
+    Frame order (reversed_copies False): the windows are the halves of ONE zv [F B, 4H] and ONE zs [F B, 4], filled by one product
+    each; pass 1 runs with reverse = 1 and writes y in frame order; y.[Vog|Vc] and y.[Vi|Vf] are added to pass 2's windows as hoisted
+    products over all steps; backward mirrors it and ends in one weight-gradient product per block over the joint dzv / dzs.
+    Reversed copies: the way reverse_sequence_u8 / _reverse_tm_into and gate_lstm_layer's own products would have done it -- pass 1 with
+    reverse = 0 over a reversed copy of the frames with its own image, buffers and products (the scalar blocks zero-padded to four
+    columns), y and dy reversed by the copy kernel.  Same kernels, same arithmetic per step: what the frame-order form is measured
+    against."""
+
+    @staticmethod
+    def forward(ctx, x_tm, Wv, bv, Ws, bs, Uv1, Us1, Vv, Vs, Uv2, Us2, num_frames, reversed_copies):
+        bf = ops.FLAGS.compute_dtype == "bfloat16"
+        frames = _hoisted_input(x_tm, bf)
+        F, B, Din, dev = frames.F, frames.B, frames.D, frames.device
+        H = Uv1.shape[0]
+        assert tuple(Wv.shape) == (Din, 4 * H) and tuple(Ws.shape) == (Din, 4) and bv.numel() == 4 * H and bs.numel() == 4 \
+            and tuple(Uv1.shape) == (H, 2 * H) and tuple(Uv2.shape) == (H, 2 * H) and tuple(Us1.shape) == (2, H) \
+            and tuple(Us2.shape) == (2, H) and tuple(Vv.shape) == (H, 2 * H) and tuple(Vs.shape) == (H, 2), \
+            "bigate LSTM operands: Wv [in,4H], Ws [in,4], Uv1, Uv2, Vv [H,2H], Us1, Us2 [2,H], Vs [H,2]"
+        Wv, bv, Ws, bs, Uv1, Us1, Vv, Vs, Uv2, Us2 = (_f32c(t.detach()) for t in (Wv, bv, Ws, bs, Uv1, Us1, Vv, Vs, Uv2, Us2))
+        bv, bs = bv.view(-1), bs.view(-1)
+        nf = _nf(num_frames)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        frames1 = split = None
+        if not reversed_copies:
+            zv, zs = new(F * B, 4 * H), new(F * B, 4)
+            frames.project(Wv, bv, zv)
+            frames.project(Ws, bs, zs)
+            win1, win2 = (zv[:, :2 * H], zs[:, :2]), (zv[:, 2 * H:], zs[:, 2:])
+        else:
+            if isinstance(frames, U8FrameImages):
+                frames1 = U8FrameImages(reverse_sequence_u8(frames.q, nf), nf)
+            else:
+                frames1 = _FloatFrames(_reverse_tm_into(frames.saved, nf, torch.empty_like(frames.saved), 0), bf)
+            split = [(Wv[:, k * 2 * H:(k + 1) * 2 * H].contiguous(),) + _pad4(Ws[:, 2 * k:2 * k + 2], bs[2 * k:2 * k + 2], dev) for k in (0, 1)]
+            wins = []
+            for k, fr in enumerate((frames1, frames)):
+                zvk, zsk = new(F * B, 2 * H), new(F * B, _GATE_U8_LDS)
+                fr.project(split[k][0], bv[k * 2 * H:(k + 1) * 2 * H], zvk)
+                fr.project(split[k][1], split[k][2], zsk)
+                wins.append((zvk, zsk[:, :2]))
+            win1, win2 = wins
+        ws = ops._workspace(dev)
+        lib = _lib.lib()
+
+        def run(win, Uv, Us, reverse):
+            out, hprev, cs, c_last = new(F, B, H), new(F, B, H), new(F + 1, B, H), new(B, H)
+            cs[0].zero_()
+            work = new(4, B, H)
+            _lib.check(lib.yt8m_gate_lstm_frames_fwd(_p(win[0]), win[0].stride(0), _p(win[1]), win[1].stride(0), _p(Uv), 2 * H, _p(Us),
+                                                     _p(out), _p(hprev), _p(cs), _p(c_last), _p(work), _p(nf), reverse, F, B, H, _p(ws),
+                                                     ws.numel() * 4, _stream()))
+            return out, hprev, cs, c_last
+
+        if not reversed_copies:
+            y, hp1, cs1, c1_last = run(win1, Uv1, Us1, 1)
+        else:
+            h1, hp1, cs1, c1_last = run(win1, Uv1, Us1, 0)                                   # step order
+            y = _reverse_tm_into(h1, nf, new(F, B, H), 0)
+        y2 = y.view(F * B, H)
+        ops.gemm_any(y2, Vv, out=win2[0], beta=1.0, bf16=bf, role=ops._hoisted_role(F * B, 2 * H, H, bf))
+        ops.gemm_any(y2, Vs, out=win2[1], beta=1.0, bf16=bf)
+        out2, hp2, cs2, c2_last = run(win2, Uv2, Us2, 0)
+        BIGATE_LSTM_CALLS["reversed_copies" if reversed_copies else "frame_order"] += 1
+        ctx.save_for_backward(frames.saved, y)                       # (y is an output: saved through autograd, not on ctx)
+        ctx.frames = frames
+        ctx.state = (bool(reversed_copies), frames1, split, win1, win2, hp1, hp2, cs1, cs2, nf, Wv, Ws, Uv1, Us1, Vv, Vs, Uv2, Us2)
+        ctx.bf16 = bf
+        ctx.set_materialize_grads(False)
+        return y, out2, c1_last, c2_last
+
+    @staticmethod
+    def backward(ctx, dy_in, dout2, dc1_last, dc2_last):
+        _, y = ctx.saved_tensors                                     # (the frames' tensor: checked against in-place changes)
+        frames = ctx.frames
+        reversed_copies, frames1, split, win1, win2, hp1, hp2, cs1, cs2, nf, Wv, Ws, Uv1, Us1, Vv, Vs, Uv2, Us2 = ctx.state
+        ctx.state = ctx.frames = None
+        F, B, Din, dev = frames.F, frames.B, frames.D, frames.device
+        H = Uv1.shape[0]
+        bf = ctx.bf16
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        if not reversed_copies:
+            dzv, dzs = new(F * B, 4 * H), new(F * B, 4)                                        # every column is written by a pass
+            dw1, dw2 = (dzv[:, :2 * H], dzs[:, :2]), (dzv[:, 2 * H:], dzs[:, 2:])
+        else:
+            # the padding columns are zeroed once: the kernel writes columns 0 and 1 only, the hoisted products read every column
+            dzvs = [new(F * B, 2 * H), new(F * B, 2 * H)]
+            dzss = [torch.zeros((F * B, _GATE_U8_LDS), dtype=torch.float32, device=dev) for _ in (0, 1)]
+            dw1, dw2 = (dzvs[0], dzss[0][:, :2]), (dzvs[1], dzss[1][:, :2])
+        ws = ops._workspace(dev)
+        lib = _lib.lib()
+        opt = lambda t: None if t is None else _f32c(t)
+
+        def run(win, Uv, Us, cs, dy, dc_last, dw, reverse):
+            work = new(6, B, H)
+            _lib.check(lib.yt8m_gate_lstm_frames_bwd(_p(win[0]), win[0].stride(0), _p(win[1]), win[1].stride(0), _p(Uv), 2 * H, _p(Us),
+                                                     _p(cs), _p(dy), _p(dc_last), _p(dw[0]), dw[0].stride(0), _p(dw[1]), dw[1].stride(0),
+                                                     _p(work), _p(nf), reverse, F, B, H, _p(ws), ws.numel() * 4, _stream()))
+
+        run(win2, Uv2, Us2, cs2, opt(dout2), opt(dc2_last), dw2, 0)
+        # dy = dzv2 . [Vog|Vc]^T + dzs2 . [Vi|Vf]^T (+ the caller's gradient of y)
+        dy = None if dy_in is None else _f32c(dy_in).clone().view(F * B, H)
+        dy = ops.gemm_any(dw2[0], Vv, out=dy, transB=True, beta=0.0 if dy is None else 1.0, bf16=bf)
+        ops.gemm_any(dw2[1], Vs, out=dy, transB=True, beta=1.0, bf16=bf)
+        dy = dy.view(F, B, H)
+        if not reversed_copies:
+            run(win1, Uv1, Us1, cs1, dy, opt(dc1_last), dw1, 1)
+        else:
+            run(win1, Uv1, Us1, cs1, _reverse_tm_into(dy, nf, new(F, B, H), 0), opt(dc1_last), dw1, 0)
+        need = ctx.needs_input_grad
+        gWv = gbv = gWs = gbs = gUv1 = gUs1 = gVv = gVs = gUv2 = gUs2 = dx = None
+        colsum = lambda t: ops.colsum(t, new(t.shape[1]))
+        if not reversed_copies:
+            if need[1]:
+                gWv = new(Din, 4 * H)
+                frames.weight_grad(dzv, gWv, 0.0)
+            if need[2]:
+                gbv = colsum(dzv)
+            if need[3]:
+                gWs = new(Din, 4)
+                frames.weight_grad(dzs, gWs, 0.0)
+            if need[4]:
+                gbs = colsum(dzs)
+            if need[0]:
+                dx = frames.dx(dzs, Ws, into=frames.dx(dzv, Wv))
+        else:
+            both = (frames1, frames)
+            if need[1]:
+                parts = [new(Din, 2 * H), new(Din, 2 * H)]
+                for k in (0, 1):
+                    both[k].weight_grad(dzvs[k], parts[k], 0.0)
+                gWv = torch.cat(parts, dim=1)                                                  # (layout glue)
+            if need[2]:
+                gbv = torch.cat([colsum(dzvs[0]), colsum(dzvs[1])])
+            if need[3]:
+                parts = [new(Din, _GATE_U8_LDS), new(Din, _GATE_U8_LDS)]
+                for k in (0, 1):
+                    both[k].weight_grad(dzss[k], parts[k], 0.0)
+                gWs = torch.cat([parts[0][:, :2], parts[1][:, :2]], dim=1)
+            if need[4]:
+                gbs = torch.cat([colsum(dzss[0])[:2], colsum(dzss[1])[:2]])
+            if need[0]:
+                dxs = [both[k].dx(dzss[k], split[k][1], into=both[k].dx(dzvs[k], split[k][0])) for k in (0, 1)]
+                if dxs[1] is not None:
+                    dx = dxs[1].add_(_reverse_tm_into(dxs[0], nf, new(F, B, Din), 0))          # pass 1 saw the reversed frames
+        # the recurrent and the y weights: products of tensors in one order (frame order; step order for pass 1 on reversed copies)
+        dw = lambda A, Bm: ops.gemm_any(A, Bm, transA=True, role="dw", bf16=bf)
+        h1, h2, y2 = hp1.view(F * B, H), hp2.view(F * B, H), y.view(F * B, H)
+        if need[5]:
+            gUv1 = dw(h1, dw1[0])
+        if need[6]:
+            gUs1 = dw(dw1[1], h1)
+        if need[7]:
+            gVv = dw(y2, dw2[0])
+        if need[8]:
+            gVs = dw(y2, dw2[1])
+        if need[9]:
+            gUv2 = dw(h2, dw2[0])
+        if need[10]:
+            gUs2 = dw(dw2[1], h2)
+        return dx, gWv, gbv, gWs, gbs, gUv1, gUs1, gVv, gVs, gUv2, gUs2, None, None
+
+
+def bigate_lstm_supported(x_tm, H):
+    """Whether bigate_lstm_layer runs x_tm (U8FrameImages, or float frames [F,B,in]) at H cells on the frame-order step kernels."""
+    shape = _cell_frames_shape(x_tm) if BIGATE_LSTM_FUSED else None
+    return shape is not None and bool(_lib.lib().yt8m_gate_lstm_frames_supported(int(shape[0]), int(H)))
+
+
+def bigate_lstm_layer(x_tm, Wv, bv, Ws, bs, Uv1, Us1, Vv, Vs, Uv2, Us2, num_frames):
+    """The two scalar-gate recurrences of LstmBigluModel (Z/frame_level_models.py:887-1101), time-major.  With n_b = num_frames[b] and
+    rev = tf.reverse_sequence(., num_frames) (frames 0 .. n_b - 1 of every video reversed, the padding frames left where they are):
+      pass 1 (create_forward_recurrent_unit, :975-1032), over rev(x) from h = c = 0, all F steps:
+        i = sigmoid(x.Wi1 + h.Ui1 + bi1) [B,1]     f = sigmoid(x.Wf1 + h.Uf1 + bf1) [B,1]
+        o = sigmoid(x.Wog1 + h.Uog1 + bog1) [B,H]  g = tanh(x.Wc1 + h.Uc1 + bc1) [B,H]     c' = f c + i g,  h' = o tanh(c');
+      y = rev(its hidden outputs) (:941);
+      pass 2 (create_backward_recurrent_unit, :1034-1101), over x in frame order: the same cell where every gate also gets y_t . V*.
+    x_tm: float frames [F,B,in] or U8FrameImages; Wv = [Wog1|Wc1|Wog2|Wc2] [in,4H], bv [4H] alike, Ws = [Wi1|Wf1|Wi2|Wf2] [in,4], bs [4]
+    alike, Uv1, Uv2 = [Uog|Uc] [H,2H], Us1, Us2 = [Ui^T; Uf^T] [2,H], Vv = [Vog|Vc] [H,2H], Vs = [Vi|Vf] [H,2]: tensors under autograd.
+    Returns (y_tm [F,B,H], out2_tm [F,B,H] = pass 2's hidden outputs, c1_last [B,H] = pass 1's memory after STEP num_frames - 1 (:943),
+    c2_last [B,H] = pass 2's (:967)), all four differentiable.  Rows with num_frames < 1: c1_last and c2_last are zeros and the row
+    receives no gradient through them (as gate_lstm_layer).
+    Device tensors at shapes yt8m_gate_lstm_frames_supported takes run on the step kernels of csrc/bigate_lstm.hip -- in frame order, or
+    with YT8M_BIGATE_LSTM_REVERSED=1 over reversed copies; CPU tensors, other dtypes and shapes and YT8M_BIGATE_LSTM_FUSED=0 take
+    bigate_lstm_layer_composed, which computes the same function in the reference's form."""
+    if bigate_lstm_supported(x_tm, Uv1.shape[0]):
+        return _BigateLstmLayer.apply(x_tm, Wv, bv, Ws, bs, Uv1, Us1, Vv, Vs, Uv2, Us2, num_frames, BIGATE_LSTM_REVERSED)
+    return bigate_lstm_layer_composed(x_tm, Wv, bv, Ws, bs, Uv1, Us1, Vv, Vs, Uv2, Us2, num_frames)
+
+
 # ---- input-memory LSTM layer (Z/frame_level_models.py:631-885; csrc/glu_lstm.hip) -------------------------------------------
 # The default form follows the project's rule: the kernels only if their median is the lower one at every shape of tools/glu_lstm_step.py
 # in both runs (DESIGN_LOG.md 32).  1: the step kernels where the shape is supported; 0: the composed torch form everywhere.
