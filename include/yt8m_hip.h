@@ -1124,6 +1124,26 @@ int yt8m_lstm_steps_bwd(const float* gates, const float* Wh, int64_t ldw, const 
                         int64_t T, int64_t B, int64_t H, void* gemm_workspace, int64_t gemm_workspace_bytes,
                         yt8m_stream_t stream);
 
+/* The forward step at MANY rows (csrc/lstm_wide.hip): LstmLayerModel's clip pass, Z/frame_level_models.py:3653-3668, runs one BasicLSTMCell
+ * over B * (F / lstm_length) rows -- 3840 at B = 128 -- for lstm_length steps with sequence_length=None.  There the recurrent product of a
+ * step is a full-size GEMM: one launch per step, 128 rows x 32 units (their 128 gate columns) per workgroup, three f16 MFMA products of h2
+ * images (the image of W_h^T under its measured scale, made by yt8m_lstm_wide_prepare once per call chain; h under the static scale 2^13,
+ * written by each step's epilogue for the next), the gates and the cell update of yt8m_lstm_gates_fwd as the epilogue.  Same tape contract
+ * as yt8m_lstm_steps_fwd (z overwritten by the activated gates, cs / hs [.., B, H] whole-layer base pointers, slot t0 read, slots
+ * t0 + 1 .. t0 + T written) with out = NULL.  num_frames must be NULL: every row runs every step, no copy-through.
+ *   yt8m_lstm_wide_supported      : 1 for H % 32 == 0, 32 <= H <= 4096, 1 <= B <= 2^20 (partial row tiles are handled in the kernel)
+ *   yt8m_lstm_wide_row_tile       : rows of a workgroup (128)
+ *   yt8m_lstm_wide_workspace_bytes: the scale word + the image of W_h^T + two images of h; 0 for an unsupported shape.  256-byte aligned.
+ *   yt8m_lstm_wide_prepare        : W_h ([H, 4H], row stride ldw) -> scale word and image in `workspace`
+ *   yt8m_lstm_wide_steps_fwd      : steps [t0, t0 + T) as plain launches on `stream`; the h images in `workspace` are scratch. */
+int yt8m_lstm_wide_supported(int64_t B, int64_t H);
+int yt8m_lstm_wide_row_tile(void);
+int64_t yt8m_lstm_wide_workspace_bytes(int64_t B, int64_t H);
+int yt8m_lstm_wide_prepare(const float* Wh, int64_t ldw, int64_t B, int64_t H, void* workspace, int64_t workspace_bytes,
+                           yt8m_stream_t stream);
+int yt8m_lstm_wide_steps_fwd(float* z, void* workspace, int64_t workspace_bytes, float* cs, float* hs, const int32_t* num_frames,
+                             int64_t t0, int64_t T, int64_t B, int64_t H, float forget_bias, yt8m_stream_t stream);
+
 /* The packed-weight step chains above are launch-bound (75-300 steps x 1-2 kernels of ~20 us): each distinct argument tuple is
  * captured once on the caller's stream and replayed as ONE hipGraph launch afterwards (LRU cache inside the library; off
  * while yt8m_prof_enable(1) is active or with YT8M_NO_GRAPH set in the environment). */

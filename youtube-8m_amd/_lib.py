@@ -365,6 +365,11 @@ SIGNATURES = {
     "yt8m_scale_mix_supported": (c_int, [c_int, c_int64, c_int64]),
     "yt8m_scale_mix_fwd": (c_int, [c_int, PP, PP, P, c_int64, c_int64, P]),
     "yt8m_scale_mix_bwd": (c_int, [c_int, PP, PP, P, P, PP, PP, c_int64, c_int64, P]),
+    "yt8m_lstm_wide_supported": (c_int, [c_int64, c_int64]),
+    "yt8m_lstm_wide_row_tile": (c_int, []),
+    "yt8m_lstm_wide_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "yt8m_lstm_wide_prepare": (c_int, [P, c_int64, c_int64, c_int64, P, c_int64, P]),
+    "yt8m_lstm_wide_steps_fwd": (c_int, [P, P, c_int64, P, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P]),
 }
 
 # The ABI this host binds (include/yt8m_hip.h, yt8m_abi_version): workspace layouts and argument meanings, not just symbols.

@@ -1245,6 +1245,7 @@ class GatedNetVLADAttentionChainModel(GatedNetVLADModel):
 # ---- Z = youtube-8m-zhangteng: the scalar-gate LSTM models ------------------------------------------------------------------------
 # Not built from Z/frame_level_models.py (one line each):
 #   MoeDistillChain* heads: Z's video-level chain heads, a separate family from --video_level_classifier_model's;
+#   LstmRandomModel: LstmMemoryModel as committed -- its frame selection sits behind FLAGS.train=="train", and --train is a bool flag (:54, :4037);
 #   LstmBiglu2Model: LstmBigluModel's pair of passes on LstmGlu2Model's input-memory cell (:1160), and not in the final submission's list;
 #   LstmMultiscale3Model: LstmMultiscale2Model on LstmGlu2Model's input-memory cell with the HIDDEN state gathered at frame num_frames - 1,
 #   not the memory (:3375, :3507): seq_ops.glu_lstm_layer hands back the gathered memory only, so it needs a second gather and its gradient;
@@ -1336,6 +1337,37 @@ class LstmGateMultilayerModel(_CellMultilayerModel):
     live under "lstm_lsyer<i>lstm_forward/" -- the reference's spelling, which checkpoints carry.  Rows with num_frames < 1: as
     LstmGateModel.  accepts_quantized_input: _hoisted_input -- layer 0 reads the reader's bytes."""
     layer = staticmethod(_gate_lstm_layer)
+
+
+DEFINE_integer("lstm_length", 10, "The length of each LSTM clip; only used in LstmLayerModel.")          # Z/frame_level_models.py: lstm_length
+
+
+class LstmLayerModel(models.BaseModel):
+    """Z/frame_level_models.py:3629-3683: a two-level LSTM.  Every video is cut into U2 = F // U1 clips of U1 = --lstm_length frames (the
+    frames at or past U1 U2 are dropped, :3649-3651).  RNN-1: one BasicLSTMCell(H, forget_bias=1.0) in a MultiRNNCell under
+    variable_scope("RNN-1") runs over all B U2 clips as one batch for U1 steps with sequence_length=None (:3653-3667): every row runs
+    every step, padding frames are zero vectors.  RNN-2: the same cell construction under variable_scope("RNN-2"), with Variables of its
+    own, runs over the U2 clip memories state_c of every video with sequence_length = num_frames // U1 (:3668-3675); the head
+    (--video_level_classifier_model) reads its final memory [B, H] (:3677-3683).  H = --lstm_cells.  --lstm_layers is read and not used:
+    both MultiRNNCells are built over range(1) (:3647, :3659).  Variable names, with this project's mapping of a scope-less dynamic_rnn
+    (as for LstmModel): RNN-1/multi_rnn_cell/cell_0/basic_lstm_cell/{weights [D + H, 4H], biases [4H]} and
+    RNN-2/multi_rnn_cell/cell_0/basic_lstm_cell/{weights [2H, 4H], biases [4H]}.  A video with num_frames < U1 hands zeros to the head,
+    as dynamic_rnn does at length 0.
+    accepts_quantized_input: RNN-1 (seq_ops.lstm_clip_layer) reads the reader's bytes where the byte projection covers the width."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, **unused_params):
+        lstm_size = int(FLAGS.lstm_cells)
+        unit_layer_1 = FLAGS.lstm_length
+        g = get_default_graph()
+        frames, _ = _bytes_or_floats(model_input, num_frames, lambda q: q.is_cuda and _lib_u8_ok(q.shape[2]))
+        with g.variable_scope("RNN-1"):
+            (W1, b1), = _lstm_cells(model_input.shape[2], lstm_size, 1)
+        with g.variable_scope("RNN-2"):
+            wb2 = _lstm_cells(lstm_size, lstm_size, 1)
+        state_c = seq_ops.lstm_clip_layer(frames, num_frames, unit_layer_1, ops.as_tensor(W1), ops.as_tensor(b1))    # [U2, B, H]
+        _, finals = _native_stack(state_c, num_frames // unit_layer_1, wb2, slot=1)
+        return _classify(finals[0][0], model_input, vocab_size, **unused_params)
 
 
 BIGATE_LSTM_BW_VARS = ("Wi", "Ui", "Vi", "bi", "Wf", "Vf", "Uf", "bf", "Wog", "Vog", "Uog", "bog", "Wc", "Vc", "Uc", "bc")   # :1036-1070

@@ -1700,6 +1700,159 @@ def lstm_stack(x_tm, num_frames, weights_biases, forget_bias=1.0, chunks=4, inpu
     return res[0], [(res[1 + 2 * l], res[2 + 2 * l]) for l in range(len(weights_biases))]
 
 
+# ---- LstmLayerModel's clip pass (Z/frame_level_models.py:3653-3668): one BasicLSTMCell over every clip of every video as ONE batch ---------
+# YT8M_LSTM_WIDE: 1 = the wide step kernel (csrc/lstm_wide.hip) runs the forward recurrence of lstm_clip_layer at B' >= WIDE_MIN_ROWS rows
+# where yt8m_lstm_wide_supported takes the shape; 0 = an existing per-step route always.  The default and WIDE_MIN_ROWS come from
+# tools/lstm_layer_step.py (profiles/lstm_layer_step.jsonl, DESIGN_LOG.md 38); nothing but lstm_clip_layer reaches the kernel.
+WIDE = os.environ.get("YT8M_LSTM_WIDE", "1") != "0"      # on: its median was below both existing routes at every op-leg shape in both runs
+# the smallest B' of the kernel leg (960 and 3840 rows x H = 512 and 1024): the wide step was below both existing routes at all four
+# shapes in both runs, 26 us against 34 (packed) at 960 x 512 and 126 against 376 at 3840 x 1024; nothing below 960 rows was measured
+WIDE_MIN_ROWS = 960
+# the forward route without the wide kernel -- "packed" (yt8m_lstm_steps_fwd with Wp) | "gemm" (Wp = NULL): packed was the faster existing
+# route at every op-leg shape in both runs
+CLIP_FWD_EXISTING = "packed"
+# the backward route -- "packed" (yt8m_lstm_steps_bwd with Wq) | "gemm" (Wq = NULL).  Neither was lower at EVERY op-leg shape in both runs
+# (gemm by 1-7 % at 1280 and 3840 rows, the two within 1 % of each other and in either order at 960 rows), so the rule picks neither and
+# the route every other caller of the step kernels takes stays
+CLIP_BWD = "packed"
+LSTM_CLIP_CALLS = {"wide": 0, "packed": 0, "gemm": 0, "composed": 0}     # which forward form ran (tests assert it)
+
+
+def clip_lengths(num_frames, clip, clips):
+    """The valid frames of every clip, [B * clips] int32 by row b * clips + j: min(max(n_b - clip j, 0), clip)."""
+    j = torch.arange(clips, device=num_frames.device, dtype=torch.int64)
+    return (num_frames.to(torch.int64)[:, None] - clip * j[None, :]).clamp(0, clip).reshape(-1).to(torch.int32)
+
+
+def lstm_clip_layer_composed(x, num_frames, clip, W, b, forget_bias=1.0):
+    """lstm_clip_layer in plain torch under autograd: a Python time loop over the `clip` steps, in the dtype of its operands."""
+    LSTM_CLIP_CALLS["composed"] += 1
+    if x.dtype == torch.uint8:
+        x = ops.dequant_l2norm(x, num_frames)
+    B, F, D = x.shape
+    U2, H = F // clip, W.shape[1] // 4
+    live = (torch.arange(F, device=x.device)[None, :] < num_frames.to(x.device)[:, None]).to(x.dtype)
+    xc = (x * live[:, :, None])[:, :clip * U2].reshape(B * U2, clip, D).to(W.dtype)
+    h = c = torch.zeros((B * U2, H), dtype=W.dtype, device=x.device)
+    for t in range(clip):
+        i, j, f, o = (torch.cat([xc[:, t], h], dim=1) @ W + b).split(H, dim=1)
+        c = c * torch.sigmoid(f + forget_bias) + torch.sigmoid(i) * torch.tanh(j)
+        h = torch.tanh(c) * torch.sigmoid(o)
+    return c.view(B, U2, H).transpose(0, 1)
+
+
+def _on_rec_stream(dev, fn):
+    """fn's launches on a recurrence side stream, between two joins with the current stream: the packed step chains are captured and
+    replayed as hipGraphs (csrc/runtime.hip), which a capture on the legacy default stream cannot do."""
+    main = torch.cuda.current_stream(dev)
+    side = _side_stream(dev, "clip", REC_STREAM_PRIORITY)
+    side.wait_stream(main)
+    with torch.cuda.stream(side):
+        fn()
+    main.wait_stream(side)
+
+
+class _ClipParam(object):
+    """What _StackLayer reads of a Variable, for a parameter that reaches the op as a tensor under autograd."""
+
+    def __init__(self, data):
+        self.data, self.grad = data, None
+
+
+class _LstmClipLayer(torch.autograd.Function):
+    """lstm_clip_layer on the device: _StackLayer's hoisted products and buffers (the byte and float product forms of the orchestrated
+    stack) around U1 recurrence steps over B' = B U2 rows -- the wide step kernel, or yt8m_lstm_steps_fwd -- and yt8m_lstm_steps_bwd
+    seeded with the final memories' gradient alone.  The wide steps and every product run on the current stream, the existing step
+    routes on a side stream joined at both ends (_on_rec_stream); the frames are data (no dx)."""
+
+    @staticmethod
+    def forward(ctx, frames, W, b, nf_clip, B, forget_bias, route, bwd_route):
+        lib = _lib.lib()
+        u8 = frames.dtype == torch.uint8
+        U1 = frames.shape[1] if u8 else frames.shape[0]
+        q = _ByteFrames(lib, frames, nf_clip, [(0, U1)]) if u8 else None
+        x_tm = q.x_tm if u8 else _f32c(frames)
+        _dev(x_tm)
+        st = _StackLayer(lib, x_tm, _ClipParam(_f32c(W.detach())), _ClipParam(_f32c(b.detach())), None, forget_bias, False, None, None,
+                         None, q)
+        st.out = None                                               # only the final memories leave the op
+        if route != "packed":
+            st.Wp = None
+        Bp, H, dev = st.B, st.H, x_tm.device
+        st.prepare_fwd()
+        st.project(0, U1)
+        if route == "wide":
+            need = lib.yt8m_lstm_wide_workspace_bytes(Bp, H)
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            _lib.check(lib.yt8m_lstm_wide_prepare(_p(st.W.data[st.Din:]), 4 * H, Bp, H, _p(ws), need, _stream()))
+            _lib.check(lib.yt8m_lstm_wide_steps_fwd(_p(st.z), _p(ws), need, _p(st.cs), _p(st.hs), None, 0, U1, Bp, H, st.forget_bias,
+                                                    _stream()))
+        else:
+            _on_rec_stream(dev, lambda: st.recur_fwd(0, U1))
+        LSTM_CLIP_CALLS[route] += 1
+        st.release(("undropped", "bytes"))
+        ctx.st, ctx.B, ctx.bwd_route = st, B, bwd_route
+        return st.cs[U1].view(B, Bp // B, H).transpose(0, 1).contiguous()          # row b U2 + j -> (j, b)
+
+    @staticmethod
+    def backward(ctx, dout):
+        st, B = ctx.st, ctx.B
+        ctx.st = None
+        if dout is None:
+            return (None,) * 8
+        U1, Bp, H = st.F, st.B, st.H
+        dc = _f32c(dout).transpose(0, 1).contiguous().view(Bp, H)   # (j, b) -> row b U2 + j
+        st.release(st.FWD_ONLY)
+        st.alloc_bwd(None, True, False)
+        if ctx.bwd_route != "packed":
+            st.Wq = None
+        st.prepare_bwd(None, dc)
+        _on_rec_stream(dc.device, lambda: st.recur_bwd(0, U1))
+        dz = st.dx_operands(0, U1)
+        gW = gb = None
+        if ctx.needs_input_grad[1]:
+            gW = st.W.grad = torch.empty_like(st.W.data)
+            st.weight_grad(0, U1, 0.0, dz)
+        if ctx.needs_input_grad[2]:
+            gb = st.b.grad = torch.empty_like(st.b.data)
+            st.bias_grad(0, U1, 0.0)
+        return None, gW, gb, None, None, None, None, None
+
+
+def lstm_clip_route(rows, H):
+    """The forward route lstm_clip_layer takes at `rows` clip rows of H cells: "wide" | CLIP_FWD_EXISTING."""
+    if WIDE and rows >= WIDE_MIN_ROWS and _lib.lib().yt8m_lstm_wide_supported(int(rows), int(H)):
+        return "wide"
+    return CLIP_FWD_EXISTING
+
+
+def lstm_clip_layer(x, num_frames, clip, W, b, forget_bias=1.0):
+    """RNN-1 of Z/frame_level_models.py:3629-3683 (LstmLayerModel) as one op: every video of x [B,F,D] -- the reader's bytes or float
+    frames -- is cut into U2 = F // clip clips of `clip` frames (the frames past clip U2 are dropped), one BasicLSTMCell(forget_bias) runs
+    over all B U2 clips as one batch for `clip` steps from zero state with no lengths (dynamic_rnn, sequence_length=None), and the final
+    MEMORIES come back time-major for the second LSTM: [U2, B, H], row (j, b) = clip j of video b.  Frames at or past num_frames are zero
+    vectors, as the reader pads them: on the bytes the image builders mask them by the clip's valid count clip_lengths(), on floats by a
+    multiply.  W [D + H, 4H], b [4H]: tensors under autograd (ops.as_tensor of the cell's Variables); the frames are data, no dx.
+    Device: the hoisted projection and the weight gradients are the orchestrated stack's products (_StackLayer); the recurrence runs on
+    the wide step kernel (lstm_clip_route) or an existing per-step route, the backward on yt8m_lstm_steps_bwd; --compute_dtype=bfloat16 does not reach this op (its
+    products keep the fp32-grade forms).  CPU tensors take lstm_clip_layer_composed, which computes the same function."""
+    clip = int(clip)
+    B, F, D = x.shape
+    U2, H = F // clip, W.shape[1] // 4
+    assert clip >= 1 and U2 >= 1, "lstm_clip_layer needs at least one whole clip"
+    if not x.is_cuda:
+        return lstm_clip_layer_composed(x, num_frames, clip, W, b, forget_bias)
+    if F != clip * U2:
+        x = x[:, :clip * U2].contiguous()
+    nf = num_frames.to(x.device)
+    if x.dtype == torch.uint8:
+        frames, nf_clip = x.contiguous().view(B * U2, clip, D), clip_lengths(nf, clip, U2)
+    else:                                                           # (layout glue on data: the mask and the time-major copy in one pass)
+        live = (torch.arange(clip * U2, device=x.device)[None, :] < nf[:, None]).to(x.dtype)
+        frames, nf_clip = (x * live[:, :, None]).view(B * U2, clip, D).transpose(0, 1).contiguous(), None
+    return _LstmClipLayer.apply(frames, W, b, nf_clip, B, float(forget_bias), lstm_clip_route(B * U2, H), CLIP_BWD)
+
+
 # ---- tf.nn.bidirectional_dynamic_rnn: time reversal per video + the two directions' stacks -----------------------------------------
 def reverse_sequence_u8(q, num_frames):
     """tf.reverse_sequence(q, num_frames, seq_axis=1) on the reader's bytes [B,F,D] (csrc/sequence.hip): frames 0 .. n_b - 1 of
