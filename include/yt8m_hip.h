@@ -1508,6 +1508,37 @@ int yt8m_scale_mix_supported(int L, int64_t rows, int64_t cols);
 int yt8m_scale_mix_fwd(int L, const float* const* p, const float* const* z, float* out, int64_t rows, int64_t cols, yt8m_stream_t stream);
 int yt8m_scale_mix_bwd(int L, const float* const* p, const float* const* z, const float* out, const float* g, float* const* dp,
                        float* const* dz, int64_t rows, int64_t cols, yt8m_stream_t stream);
+/* What the MoeDistillChain* / MoeDistillSplit heads do around their MoE block (csrc/distill_head.hip; Z/video_level_models.py:286-582).
+ * yt8m_distill_input_*: the head input [x | class part] [rows, D + C] from the features x [rows, D], the pre-activation z [rows, C] of
+ * the "class_inputs" layer and another model's predictions t (row pitch ldt, read from column v0 to V), in one pass each way.  mode is a
+ * sum of YT8M_DISTILL_NORM_X (l2-normalise x), YT8M_DISTILL_RELU (relu, else no activation), YT8M_DISTILL_DIV (divide by the row sum of
+ * t[:, v0:V]) and YT8M_DISTILL_NORM_C (l2-normalise the class part): MoeDistillChainModel and MoeDistillSplitModel are RELU,
+ * MoeDistillChainNormModel NORM_X + DIV + NORM_C, MoeDistillChainNorm2Model all four.
+ *   fwd, per row: s = sum t[v0:V] (DIV only); a = act(z), with DIV a / s as a true division and 0 where s == 0 (the reference has 0 / 0
+ *     there); a normalised part p becomes p * r, r = rsqrt(max(sum p^2, eps)) (1 / sqrt(eps), rounded once on the host, when the sum is
+ *     <= eps); y = [x' | a'].  rx[row], rc[row] = r when the sum was > eps, else -r (as yt8m_chain_link_fwd; 1 for a part that is not
+ *     normalised); sinv[row] = 1 / s, 0 where s == 0, 1 without DIV.  t may be NULL without DIV.
+ *   bwd, per row and part: R = |r|, k = sum(y * dy) over the part; da = R * (dy - y * k) when r > 0, else R * dy; dy itself for a part
+ *     that is not normalised.  dz = da * act'(z) * sinv, act' from the INPUT z (a relu tie at 0 gets 0; a zero-sum row gets zeros);
+ *     dx = da of the x part.  A NULL dx is skipped, and the x part of dy is then never read.  Saved for it: z, y, rx, rc, sinv.
+ * One wave per row; a part of up to 1024 columns is read once, a wider one twice; 16-byte accesses when D % 4 == 0, C % 4 == 0 and x, z,
+ * y (dy, dx, dz) are 16-byte aligned; t takes any alignment.  Fixed summation order, no atomics, every output element written once.
+ * yt8m_distill_input_supported: 1 <= D, C <= 2^24, 1 <= V < 2^31; no device is touched.
+ * yt8m_distill_blend_*: the heads' last line, out [rows, V] = concat(p1 [rows, V1], t[:, V1:]) * w + t * (1 - w) with 1 - w formed in
+ * fp32 and both products rounded before the sum; bwd: dp1 = w * dout[:, :V1].  Elementwise; 16-byte accesses when V, V1 and ldt are
+ * multiples of 4 and the operands 16-byte aligned.  yt8m_distill_blend_supported: rows >= 1, 1 <= V1 <= V < 2^31, rows * V <= 2^38.
+ * Unsupported shapes: YT8M_E_SHAPE; a null required operand, a mode outside 0..15, eps <= 0, v0 outside [0, V) or ldt < V:
+ * YT8M_E_BADARG.  Nothing is launched then. */
+enum yt8m_distill_mode { YT8M_DISTILL_NORM_X = 1, YT8M_DISTILL_RELU = 2, YT8M_DISTILL_DIV = 4, YT8M_DISTILL_NORM_C = 8 };
+int yt8m_distill_input_supported(int64_t D, int64_t C, int64_t V);
+int yt8m_distill_input_fwd(int mode, const float* x, const float* z, const float* t, int64_t ldt, int64_t v0, int64_t V, float* y,
+                           float* rx, float* rc, float* sinv, int64_t rows, int64_t D, int64_t C, float eps, yt8m_stream_t stream);
+int yt8m_distill_input_bwd(int mode, const float* z, const float* y, const float* rx, const float* rc, const float* sinv,
+                           const float* dy, float* dx, float* dz, int64_t rows, int64_t D, int64_t C, yt8m_stream_t stream);
+int yt8m_distill_blend_supported(int64_t rows, int64_t V, int64_t V1);
+int yt8m_distill_blend_fwd(const float* p1, const float* t, int64_t ldt, float* out, int64_t rows, int64_t V, int64_t V1, float w,
+                           yt8m_stream_t stream);
+int yt8m_distill_blend_bwd(const float* dout, float* dp1, int64_t rows, int64_t V, int64_t V1, float w, yt8m_stream_t stream);
 
 #ifdef __cplusplus
 }

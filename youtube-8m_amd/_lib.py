@@ -370,6 +370,12 @@ SIGNATURES = {
     "yt8m_lstm_wide_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "yt8m_lstm_wide_prepare": (c_int, [P, c_int64, c_int64, c_int64, P, c_int64, P]),
     "yt8m_lstm_wide_steps_fwd": (c_int, [P, P, c_int64, P, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P]),
+    "yt8m_distill_input_supported": (c_int, [c_int64, c_int64, c_int64]),
+    "yt8m_distill_input_fwd": (c_int, [c_int, P, P, P, c_int64, c_int64, c_int64, P, P, P, P, c_int64, c_int64, c_int64, c_float, P]),
+    "yt8m_distill_input_bwd": (c_int, [c_int, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, P]),
+    "yt8m_distill_blend_supported": (c_int, [c_int64, c_int64, c_int64]),
+    "yt8m_distill_blend_fwd": (c_int, [P, P, c_int64, P, c_int64, c_int64, c_int64, c_float, P]),
+    "yt8m_distill_blend_bwd": (c_int, [P, P, c_int64, c_int64, c_int64, c_float, P]),
 }
 
 # The ABI this host binds (include/yt8m_hip.h, yt8m_abi_version): workspace layouts and argument meanings, not just symbols.

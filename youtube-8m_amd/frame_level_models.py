@@ -1244,7 +1244,12 @@ class GatedNetVLADAttentionChainModel(GatedNetVLADModel):
 
 # ---- Z = youtube-8m-zhangteng: the scalar-gate LSTM models ------------------------------------------------------------------------
 # Not built from Z/frame_level_models.py (one line each):
-#   MoeDistillChain* heads: Z's video-level chain heads, a separate family from --video_level_classifier_model's;
+#   MoeDistillModel, MoeDistillEmbeddingModel (Z/video_level_models.py:157, :233): heads of the cascade family that are not in the final
+#   submission's list (MoeDistillChainModel, -NormModel, -Norm2Model and MoeDistillSplitModel are built: video_level_models.py);
+#   MoeDistillSplit2Model, MoeDistillSplit3Model, MoeDistillSplit4Model (Z/video_level_models.py:584 on): not in the list either;
+#   CnnDCCDistillChainModel (entry 51, :6249): returns predictions_class and is trained by Z's calculate_loss_mix, a training rule that
+#   train.py does not have;
+#   Z's --distillation_type 1-3 losses: the cascade scripts say --distillation_type=0, the plain label loss;
 #   LstmRandomModel: LstmMemoryModel as committed -- its frame selection sits behind FLAGS.train=="train", and --train is a bool flag (:54, :4037);
 #   LstmBiglu2Model: LstmBigluModel's pair of passes on LstmGlu2Model's input-memory cell (:1160), and not in the final submission's list;
 #   LstmMultiscale3Model: LstmMultiscale2Model on LstmGlu2Model's input-memory cell with the HIDDEN state gathered at frame num_frames - 1,

@@ -2,8 +2,8 @@
 
 torch is used for device memory, streams and the autograd tape only; every FLOP of the hot path is a
 HIP kernel in libyt8m_hip.so.  No op has a CPU / eager fallback: host tensors raise.  (Documented exceptions: ens_combine /
-ens_moments of the ensemble stage and scale_mix have a composed torch form that inputs outside the kernels' layout take by rule, not by
-failure; linear_group multiplies CPU tensors with torch, for the host tests.)
+ens_moments of the ensemble stage, scale_mix, distill_input and distill_blend have a composed form that inputs outside the kernels'
+layout take by rule, not by failure; linear_group multiplies CPU tensors with torch, for the host tests.)
 
 Gradient routing: parameters are NOT autograd leaves.  Each op's backward writes dW directly into the
 variable's slice of the gradient arena (GEMM beta = 0 on first write, 1 afterwards) and returns None for
@@ -1401,6 +1401,140 @@ def scale_mix(ps, zs):
     if not fused:
         return scale_mix_composed(ps, zs)
     return _ScaleMix.apply(L, *ps, *zs)
+
+
+# 0 (the default): distill_input / distill_blend compose the existing ops and torch glue; anything else: the kernels of
+# csrc/distill_head.hip.  A kernel is the default only where tools/distill_head_step.py's `kernels` leg has shown its median below the
+# composed form's at every shape in both runs; neither did: distill_input in 13 rows of 14 (2.6-2.8x in the Norm2 mode, level with a relu
+# and a cat in the Chain mode), distill_blend in 2 of 8 (two multiplies and an add beat a Python autograd Function on the host).  Whole
+# steps move by at most 0.06 ms either way (DESIGN_LOG.md section 39).
+DISTILL_INPUT_FUSED = os.environ.get("YT8M_DISTILL_INPUT_FUSED", "0") != "0"
+DISTILL_BLEND_FUSED = os.environ.get("YT8M_DISTILL_BLEND_FUSED", "0") != "0"
+DISTILL_CALLS = {"input_kernels": 0, "input_composed": 0, "blend_kernels": 0, "blend_composed": 0}      # which form ran (tests)
+# mode -> (l2-normalise x, relu, divide by the row sum of t[:, v0:], l2-normalise the class part): the heads of Z/video_level_models.py
+DISTILL_MODES = {"chain": (False, True, False, False), "norm": (True, False, True, True), "norm2": (True, True, True, True),
+                 "split": (False, True, False, False)}
+
+
+def _distill_mode_bits(mode):
+    norm_x, relu, div, norm_c = DISTILL_MODES[mode]
+    return int(norm_x) | int(relu) << 1 | int(div) << 2 | int(norm_c) << 3       # enum yt8m_distill_mode
+
+
+def distill_input_composed(x, z, t, mode, v0=0, eps=1e-12):
+    """distill_input as activation, a torch sum and divide, l2_normalize and torch.cat."""
+    norm_x, relu, div, norm_c = DISTILL_MODES[mode]
+    a = activation(z, "relu") if relu else z
+    if div:
+        s = t[:, v0:].sum(dim=1, keepdim=True).to(a.dtype)
+        live = s != 0                                                     # a zero-sum row: zeros, and a zero gradient for its z
+        a = a / torch.where(live, s, torch.ones_like(s)) * live.to(a.dtype)
+    return torch.cat([l2_normalize(x, eps) if norm_x else x, l2_normalize(a, eps) if norm_c else a], dim=1)
+
+
+class _DistillInput(torch.autograd.Function):
+    """csrc/distill_head.hip: the head input [x' | class part] in one pass each way.  Saved for backward: z (the linear's output), y (the
+    MoE block's input) and the three per-row scalars."""
+
+    @staticmethod
+    def forward(ctx, x, z, t, bits, v0, eps):
+        x, z = _f32c(x), _f32c(z)
+        t, ldt = _rowmajor2d(t)
+        _dev(x, z, t)
+        rows, D = x.shape
+        C = z.shape[1]
+        y = torch.empty((rows, D + C), dtype=torch.float32, device=x.device)
+        stats = torch.empty((3, rows), dtype=torch.float32, device=x.device)             # rx, rc, 1 / s
+        _lib.check(_lib.lib().yt8m_distill_input_fwd(bits, _p(x), _p(z), _p(t), ldt, int(v0), t.shape[1], _p(y), _p(stats[0]), _p(stats[1]),
+                                                     _p(stats[2]), rows, D, C, float(eps), _stream()))
+        ctx.bits, ctx.D = bits, D
+        ctx.save_for_backward(z, y, stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, y, stats = ctx.saved_tensors
+        dy = _f32c(dy)
+        rows, C = z.shape
+        dx = torch.empty((rows, ctx.D), dtype=torch.float32, device=z.device) if ctx.needs_input_grad[0] else None
+        dz = torch.empty_like(z)
+        _lib.check(_lib.lib().yt8m_distill_input_bwd(ctx.bits, _p(z), _p(y), _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(dy), _p(dx), _p(dz),
+                                                     rows, ctx.D, C, _stream()))
+        return dx, dz, None, None, None, None
+
+
+def distill_input(x, z, t, mode, v0=0, eps=1e-12):
+    """[B, D + C]: the input of the MoeDistillChain* / MoeDistillSplit heads' MoE block (Z/video_level_models.py:316-324, :389-399,
+    :464-474, :541-550) from the head's features x [B, D], z = t_window W + b [B, C] (ops.linear under "class_inputs") and another
+    model's predictions t [B, V], which are data.  mode (DISTILL_MODES): "chain" and "split" [x | relu(z)]; "norm"
+    [l2norm(x) | l2norm(z / sum_v t[:, v0:])]; "norm2" the same with relu before the division.  A row whose t sums to exactly 0 (0 / 0 in
+    the reference) gets a class part of zeros and a zero gradient for its z.  Differentiable in x and z.
+    YT8M_DISTILL_INPUT_FUSED (read at import): 0, the default, is the composed form (distill_input_composed); 1 is the fused kernel
+    pair, which CPU tensors, non-float32 tensors and shapes yt8m_distill_input_supported refuses never take."""
+    if mode not in DISTILL_MODES:
+        raise ValueError("distill_input: mode must be one of %s, got %r" % (sorted(DISTILL_MODES), mode))
+    if x.dim() != 2 or z.dim() != 2 or t.dim() != 2 or not (x.shape[0] == z.shape[0] == t.shape[0]) or not 0 <= v0 < t.shape[1]:
+        raise ValueError("distill_input: x [B, D], z [B, C], t [B, V] and 0 <= v0 < V, got %s, %s, %s, v0 = %d"
+                         % (tuple(x.shape), tuple(z.shape), tuple(t.shape), v0))
+    t = t.detach()
+    fused = (DISTILL_INPUT_FUSED and x.shape[0] > 0 and all(a.is_cuda and a.dtype == torch.float32 for a in (x, z, t))
+             and bool(_lib.lib().yt8m_distill_input_supported(x.shape[1], z.shape[1], t.shape[1])))
+    DISTILL_CALLS["input_kernels" if fused else "input_composed"] += 1
+    if not fused:
+        return distill_input_composed(x, z, t, mode, v0, eps)
+    return _DistillInput.apply(x, z, t, _distill_mode_bits(mode), v0, eps)
+
+
+def distill_blend_composed(p1, t, w):
+    """distill_blend as torch.cat, two multiplies and an add, 1 - w formed in fp32."""
+    w32 = torch.tensor(w, dtype=torch.float32)
+    V1 = p1.shape[1]
+    both = p1 if V1 == t.shape[1] else torch.cat([p1, t[:, V1:]], dim=1)
+    return both * float(w32) + t * float(1.0 - w32)
+
+
+class _DistillBlend(torch.autograd.Function):
+    """csrc/distill_head.hip: concat(p1, t[:, V1:]) * w + t * (1 - w) in one pass each way.  Nothing is saved for backward."""
+
+    @staticmethod
+    def forward(ctx, p1, t, w):
+        p1 = _f32c(p1)
+        t, ldt = _rowmajor2d(t)
+        _dev(p1, t)
+        rows, V = t.shape
+        out = torch.empty((rows, V), dtype=torch.float32, device=t.device)
+        _lib.check(_lib.lib().yt8m_distill_blend_fwd(_p(p1), _p(t), ldt, _p(out), rows, V, p1.shape[1], float(w), _stream()))
+        ctx.w, ctx.V1 = float(w), p1.shape[1]
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        dout = _f32c(dout)
+        rows, V = dout.shape
+        dp1 = torch.empty((rows, ctx.V1), dtype=torch.float32, device=dout.device)
+        _lib.check(_lib.lib().yt8m_distill_blend_bwd(_p(dout), _p(dp1), rows, V, ctx.V1, ctx.w, _stream()))
+        return dp1, None, None
+
+
+def distill_blend(p1, t, w, bound):
+    """[B, V] = concat(p1 [B, bound], t[:, bound:]) * w + t * (1 - w): the last line of the MoeDistillChain* / MoeDistillSplit heads
+    (Z/video_level_models.py:355, :578-580), w = --ensemble_w, bound = the number of labels the head predicts itself (V for the Chain
+    heads).  t is data; 1 - w is formed in fp32.  With w == 1.0 and bound == V -- the Chain heads' training setting -- the op returns p1
+    ITSELF: the reference's p * 1.0 + t * 0.0 equals p bit for bit for finite t.
+    YT8M_DISTILL_BLEND_FUSED (read at import): 0, the default, is the composed form (distill_blend_composed); 1 is the fused kernel pair,
+    which CPU tensors, non-float32 tensors and shapes yt8m_distill_blend_supported refuses never take."""
+    if p1.dim() != 2 or t.dim() != 2 or p1.shape[0] != t.shape[0] or p1.shape[1] != bound or not 0 < bound <= t.shape[1]:
+        raise ValueError("distill_blend: p1 [B, bound], t [B, V] and 0 < bound <= V, got %s, %s, bound = %d"
+                         % (tuple(p1.shape), tuple(t.shape), bound))
+    if float(w) == 1.0 and bound == t.shape[1]:
+        return p1
+    t = t.detach()
+    fused = (DISTILL_BLEND_FUSED and p1.shape[0] > 0 and p1.is_cuda and t.is_cuda and p1.dtype == t.dtype == torch.float32
+             and bool(_lib.lib().yt8m_distill_blend_supported(t.shape[0], t.shape[1], bound)))
+    DISTILL_CALLS["blend_kernels" if fused else "blend_composed"] += 1
+    if not fused:
+        return distill_blend_composed(p1, t, w)
+    return _DistillBlend.apply(p1, t, w)
 
 
 class _LinearGroup(torch.autograd.Function):

@@ -7,7 +7,7 @@ torch tensors on the MI355X and all arithmetic runs in libyt8m_hip.so (ops.py).
 import torch
 
 from . import models, ops
-from .flags import FLAGS, DEFINE_integer, DEFINE_string, DEFINE_bool
+from .flags import FLAGS, DEFINE_integer, DEFINE_string, DEFINE_bool, DEFINE_float
 from .variables import get_default_graph, xavier_uniform, zeros
 
 # W/video_level_models.py:19-47
@@ -17,6 +17,8 @@ DEFINE_integer("deep_chain_relu_cells", 200, "The number of relu cells used for 
 DEFINE_string("deep_chain_relu_type", "relu", "The type of relu cells used for DeepChainModel (options are elu and relu)")
 DEFINE_bool("deep_chain_use_length", False, "unused by DeepCombineChainModel (kept for flag compatibility)")
 DEFINE_integer("moe_num_extend", 8, "The number of attention outputs, used for MoeExtendModel.")      # Z/video_level_models.py:31
+DEFINE_float("ensemble_w", 1.0, "ensemble weight used in distill chain models.")                        # Z/video_level_models.py:52-58
+DEFINE_integer("softmax_bound", 1000, "The number of labels to be a group, used for MoeSoftmaxModel and MoeDistillSplitModel.")
 # new: MoeModel may return its own "loss" (W/train.py:384-385 honours it) computed by the fused mixing+cross-entropy pass
 DEFINE_bool("fused_head_loss", True, "MoeModel returns {'loss': CrossEntropyLoss(predictions, labels)} from a fused kernel "
             "when labels are given, --label_loss=CrossEntropyLoss, no label smoothing and no --multitask.")
@@ -241,3 +243,55 @@ class MoeExtendDistillChainModel(MoeExtendModel):
         B = class_input.shape[0]
         tiled = class_input.unsqueeze(1).expand(B, num_extends, self.CLASS_SIZE).reshape(B * num_extends, self.CLASS_SIZE)
         return torch.cat([model_input, tiled], dim=1)
+
+
+# ---- Z's cascade heads: a MoeModel that also reads another model's predictions -------------------------------------------------------
+def distill_chain_head(model_input, vocab_size, distillation_predictions, mode, num_mixtures=None, l2_penalty=1e-8, split=False):
+    """The body of the four heads below.  t = distillation_predictions [B, V] (the reference's distill_labels), cast to fp32, is data.
+    z = FC(t[:, v0:]) under "class_inputs", CLASS_SIZE = 256 wide; the MoE block (scopes "gates" and "experts") reads
+    ops.distill_input(model_input, z, t, mode, v0) and predicts the first V1 labels; predictions = ops.distill_blend(p1, t, --ensemble_w,
+    V1).  split: V1 = v0 = --softmax_bound, else V1 = V and v0 = 0.  Variables in the order class_inputs/weights, class_inputs/biases,
+    gates/weights, experts/weights, experts/biases.  model_input is data in video-level use (no head gradient is computed for it) and an
+    LSTM memory in frame-level use."""
+    assert distillation_predictions is not None, "distillation feature must be used"
+    t = distillation_predictions.detach().to(torch.float32)
+    bound = vocab_size
+    if split:
+        bound = int(FLAGS.softmax_bound)
+        assert 0 < bound < vocab_size, "MoeDistillSplitModel wants 0 < --softmax_bound = %d < %d labels" % (bound, vocab_size)
+    v0 = bound if split else 0
+    z = fully_connected(t[:, v0:] if v0 else t, MoeExtendDistillChainModel.CLASS_SIZE, "class_inputs", l2_penalty=l2_penalty)
+    frozen = 0 if model_input.requires_grad else int(model_input.shape[1])
+    head_input = ops.distill_input(model_input, z, t, mode, v0)
+    p1 = moe_block(head_input, bound, num_mixtures or FLAGS.moe_num_mixtures, l2_penalty, "gates", "experts", frozen_cols=frozen)
+    return {"predictions": ops.distill_blend(p1, t, FLAGS.ensemble_w, bound)}
+
+
+class MoeDistillChainModel(models.BaseModel):
+    """Z/video_level_models.py:286-357: MoeModel on [model_input | relu(FC(t))], t another model's predictions, FC under "class_inputs"
+    (256 wide, no normalisation), then predictions * --ensemble_w + t * (1 - --ensemble_w).  Without t the reference dereferences None
+    at its last line; here the assertion of distill_link is raised."""
+    MODE, SPLIT = "chain", False
+
+    def create_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, distillation_predictions=None,
+                     original_input=None, **unused_params):
+        return distill_chain_head(model_input, vocab_size, distillation_predictions, self.MODE, num_mixtures, l2_penalty, self.SPLIT)
+
+
+class MoeDistillChainNormModel(MoeDistillChainModel):
+    """Z/video_level_models.py:359-432: the head input is [l2norm(model_input) | l2norm(FC(t) / sum_v t)], no activation.  One deliberate
+    difference from the reference: a row whose t sums to exactly 0 is 0 / 0 = NaN there; here its class part is zeros and its
+    pre-activation receives a zero gradient (teacher predictions are sigmoid outputs: this never happens on real data)."""
+    MODE = "norm"
+
+
+class MoeDistillChainNorm2Model(MoeDistillChainModel):
+    """Z/video_level_models.py:434-507: MoeDistillChainNormModel with relu before the division; the same zero-sum rule."""
+    MODE = "norm2"
+
+
+class MoeDistillSplitModel(MoeDistillChainModel):
+    """Z/video_level_models.py:509-582: V1 = --softmax_bound.  "class_inputs" reads t[:, V1:], the MoE block on [model_input | relu(FC)]
+    predicts the first V1 labels only, and predictions = concat(p1, t[:, V1:]) * --ensemble_w + t * (1 - --ensemble_w): the other labels
+    are the teacher's own.  0 < V1 < V is asserted."""
+    MODE, SPLIT = "split", True
