@@ -1539,6 +1539,30 @@ int yt8m_distill_blend_supported(int64_t rows, int64_t V, int64_t V1);
 int yt8m_distill_blend_fwd(const float* p1, const float* t, int64_t ldt, float* out, int64_t rows, int64_t V, int64_t V1, float w,
                            yt8m_stream_t stream);
 int yt8m_distill_blend_bwd(const float* dout, float* dp1, int64_t rows, int64_t V, int64_t V1, float w, yt8m_stream_t stream);
+/* The step between two MoE stages of the MoeMix4 / MoeKnowledge heads (csrc/mix_link.hip; Z/video_level_models.py:1872-2044 and
+ * :1331-1438), in one pass each way.  The host hands over ONE product z [rows, 2 C] = p . [W1 | W2] (MoeKnowledge: z2 = (p . seq) . W2,
+ * no bias in either) and u [2 C] = [b1 | u2]; mode is a sum of YT8M_MIX_LINK_PLAIN (second pre-activation z2 + u2, u2 = b2; without it
+ * the complement u2 - z2 with u2 = colsum(W2) + b2, which is (1 - p) . W2 + b2 with no 1 - p tensor) and YT8M_MIX_LINK_NONE (no
+ * normalisation: the --frame_features form).
+ *   fwd, per row: a1 = elu(z1 + u1), a2 = elu(+-z2 + u2); y_k = (a_k * r_k) * scale with r_k = rsqrt(max(sum a_k^2, eps)) per segment
+ *     (1 / sqrt(eps), rounded once on the host, when the sum is <= eps), or a_k itself with NONE; out [rows, Wprev + 2 C] =
+ *     [prev | y1 | y2]; stats [2, rows]: stats[k * rows + row] = r_k when the sum was > eps, else -r_k (as yt8m_chain_link_fwd); 1 with NONE.
+ *   bwd, per row: dprev[:, dx_from:] = dy[:, dx_from:Wprev] -- the leading dx_from columns of dprev [rows, Wprev] are data columns and are
+ *     neither computed nor written, as with the MoE head's dx_from; a NULL dprev is skipped.  Per segment, with a and elu' recomputed
+ *     from z and u: yh = a R, R = |r|, k = sum(yh * dy); da = scale R (dy - yh k) when r > 0, else scale R dy; dy itself with NONE;
+ *     dz1 = da1 elu'(z1 + u1), dz2 = da2 elu'(z2 + u2) with PLAIN, else -da2 elu'(u2 - z2): the complement's sign is in dz [rows, 2 C], so
+ *     that dp is one product dz . [W1 | W2]^T, dW one p^T . dz, and du = [colsum(dz1) | -+colsum(dz2)].  Saved for it: z, u, stats.
+ * One wave per row, a segment stays in registers between its reduction and the write; 16-byte accesses when Wprev % 4 == 0, C % 4 == 0
+ * (bwd: dx_from % 4 == 0 too) and the operands are 16-byte aligned.  Fixed summation order, no atomics, every output element written once.
+ * yt8m_mix_link_supported: 1 <= Wprev <= 2^24 and 1 <= C <= 1024; no device is touched.  Unsupported shapes and rows < 1: YT8M_E_SHAPE;
+ * a null required operand, a mode outside 0..3, eps <= 0, scale <= 0 or dx_from outside [0, Wprev]: YT8M_E_BADARG.  Nothing is launched
+ * then. */
+enum yt8m_mix_link_mode { YT8M_MIX_LINK_PLAIN = 1, YT8M_MIX_LINK_NONE = 2 };
+int yt8m_mix_link_supported(int64_t Wprev, int64_t C);
+int yt8m_mix_link_fwd(int mode, const float* prev, const float* z, const float* u, float* out, float* stats, int64_t rows, int64_t Wprev,
+                      int64_t C, float scale, float eps, yt8m_stream_t stream);
+int yt8m_mix_link_bwd(int mode, const float* z, const float* u, const float* stats, const float* dy, float* dprev, float* dz, int64_t rows,
+                      int64_t Wprev, int64_t C, int64_t dx_from, float scale, yt8m_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -20,13 +20,6 @@ constexpr int REG_COLS = 1024;           // widest register-resident row: 16 flo
 constexpr int PASSES = REG_COLS / 64;    // single-element passes of a wave over such a row
 constexpr int PASSES4 = REG_COLS / 256;  // 16-byte passes
 
-__device__ __forceinline__ float link_act(bool elu, float z) {           // act_apply (elementwise.hip) for the two kinds a link takes
-  return elu ? (z > 0.f ? z : expf(z) - 1.0f) : fmaxf(z, 0.f);
-}
-__device__ __forceinline__ float link_act_grad(bool elu, float z) {      // from the INPUT: a relu tie at 0 gets 0, as act_bwd from y
-  return z > 0.f ? 1.f : (elu ? expf(z) : 0.f);
-}
-
 // N(0,1) of logical element e: word (e & 3) of block e >> 2, the layout of noise_kernel
 __device__ __forceinline__ float normal_at(int64_t e, uint64_t seed) {
   float n[4];

@@ -189,6 +189,10 @@ __device__ __forceinline__ int64_t clamp_frames(const int32_t* nf, int64_t b, in
 
 // the reciprocal of an l2-normalisation: 1 / sqrt(max(ss, eps)), with reps = 1 / sqrt(eps) rounded once on the host
 __device__ __forceinline__ float link_r(float ss, float eps, float reps) { return ss > eps ? rsqrtf(ss) : reps; }
+// the two activations a link takes (chain_link.hip, mix_link.hip): act_apply of elementwise.hip for elu and relu ...
+__device__ __forceinline__ float link_act(bool elu, float z) { return elu ? (z > 0.f ? z : expf(z) - 1.0f) : fmaxf(z, 0.f); }
+// ... and their derivative from the INPUT: a relu tie at 0 gets 0, as act_bwd from y
+__device__ __forceinline__ float link_act_grad(bool elu, float z) { return z > 0.f ? 1.f : (elu ? expf(z) : 0.f); }
 
 // Dequantize (W/utils.py:23-38) of the reader's bytes: x = a0 q + c0
 constexpr float U8_A0 = 4.0f / 255.0f, U8_C0 = 4.0f / 512.0f - 2.0f;

@@ -1247,8 +1247,10 @@ class GatedNetVLADAttentionChainModel(GatedNetVLADModel):
 #   MoeDistillModel, MoeDistillEmbeddingModel (Z/video_level_models.py:157, :233): heads of the cascade family that are not in the final
 #   submission's list (MoeDistillChainModel, -NormModel, -Norm2Model and MoeDistillSplitModel are built: video_level_models.py);
 #   MoeDistillSplit2Model, MoeDistillSplit3Model, MoeDistillSplit4Model (Z/video_level_models.py:584 on): not in the list either;
-#   CnnDCCDistillChainModel (entry 51, :6249): returns predictions_class and is trained by Z's calculate_loss_mix, a training rule that
-#   train.py does not have;
+#   CnnDCCDistillChainModel (entry 51, :6249): the plugin itself is not built, though the rule it is trained by, Z's calculate_loss_mix
+#   on its predictions_class, now exists (train.TrainGraph._mix_loss);
+#   MoeSoftmaxModel (entry 29.4, Z/video_level_models.py): needs Z's SoftmaxLoss and a softmax-over-labels expert kernel, the step after
+#   the combine chain heads; MoeMix4Model's --moe_group=True path (label groups of --class_size): no script of the list sets it;
 #   Z's --distillation_type 1-3 losses: the cascade scripts say --distillation_type=0, the plain label loss;
 #   LstmRandomModel: LstmMemoryModel as committed -- its frame selection sits behind FLAGS.train=="train", and --train is a bool flag (:54, :4037);
 #   LstmBiglu2Model: LstmBigluModel's pair of passes on LstmGlu2Model's input-memory cell (:1160), and not in the final submission's list;
@@ -1261,8 +1263,7 @@ class GatedNetVLADAttentionChainModel(GatedNetVLADModel):
 #   LstmExtendInputModel: the attention pools the input frames themselves (:5336);
 #   LstmExtendOrthoModel: calculate_ortho(W1) is added to the regularisation losses (:5503);
 #   LstmGateExtendModel, LstmGluExtendModel: the outputs come from a scalar-gate / glu cell's while_loop, not dynamic_rnn (:5574, :5675);
-#   LstmExtendParallelModel: an LSTM over the rgb part only, whose attention also pools the raw audio part (:5778);
-#   LstmExtendCombineModel: ends in MoeMix4Model, a head that is not built here, and its predictions_class (:5852).
+#   LstmExtendParallelModel: an LSTM over the rgb part only, whose attention also pools the raw audio part (:5778).
 GATE_LSTM_VARS = ("Wi", "Ui", "bi", "Wf", "Uf", "bf", "Wog", "Uog", "bog", "Wc", "Uc", "bc")      # create_recurrent_unit's order
 
 
@@ -1489,7 +1490,8 @@ class LstmExtendModel(models.BaseModel):
     pooling are one pass over the stack's time-major outputs in the shared mode of seq_ops.softmax_attention_tm."""
     accepts_quantized_input = True
 
-    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
+    def _pooled_rows(self, model_input, num_frames, l2_penalty):
+        """(the B E attention-pooled rows [B E, H], the input as the stack read it, the attention [B, F, E])"""
         lstm_size = int(FLAGS.lstm_cells)
         num_extend = FLAGS.moe_num_extend
         model_input, u8 = _bytes_or_floats(model_input, num_frames,
@@ -1503,9 +1505,31 @@ class LstmExtendModel(models.BaseModel):
         else:
             mask = dict(valid=(model_input.abs().sum(dim=2) > 0).to(torch.uint8))
         attention, pooled = seq_ops.softmax_attention_tm(out_tm, W1, b1, out_tm, extra=extra, **mask)
-        result = _classify(pooled.reshape(B * num_extend, lstm_size), model_input, vocab_size, **unused_params)
-        result["attention_weight"] = attention.detach().transpose(1, 2).reshape(B, num_extend * F)
+        return pooled.reshape(B * num_extend, lstm_size), model_input, attention
+
+    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
+        pooled, model_input, attention = self._pooled_rows(model_input, num_frames, l2_penalty)
+        B, F, E = attention.shape
+        result = _classify(pooled, model_input, vocab_size, **unused_params)
+        result["attention_weight"] = attention.detach().transpose(1, 2).reshape(B, E * F)
         return result
+
+
+class LstmExtendCombineModel(LstmExtendModel):
+    """Z/frame_level_models.py:5852-5924: LstmExtendModel's stack and attention pooling, on the reader's bytes on LstmExtendModel's
+    terms, with video_level_models.MoeMix4Model -- always that head, as in the reference -- on the B E pooled rows; its "predictions"
+    and every stage's [B E, V] piece of its "predictions_class" are reduced by the maximum over a video's E rows (each piece is pooled
+    before the concatenation: the maximum over rows commutes with it), so the result is trained by Z's mix loss
+    (train.TrainGraph._mix_loss).  The scripts run it with --frame_features, which leaves the head's class inputs unnormalised.  The
+    reference does not return "attention_weight" here; neither does this."""
+
+    def create_model(self, model_input, vocab_size, num_frames, l2_penalty=1e-8, **unused_params):
+        num_extend = FLAGS.moe_num_extend
+        pooled, model_input = self._pooled_rows(model_input, num_frames, l2_penalty)[:2]
+        unused_params.pop("original_input", None)
+        pool = lambda p_: ops.frame_pool(p_.view(-1, num_extend, vocab_size), "max")        # tf.reduce_max over a video's rows
+        return video_level_models.MoeMix4Model().create_model(pooled, vocab_size, original_input=model_input, support_pool=pool,
+                                                              **unused_params)
 
 
 def input_extend_windows(num_frames, num_extend):

@@ -11,7 +11,13 @@ Left out of W/losses.py:
   SoftmaxLoss, MultiTaskCrossEntropyAndSoftmaxLoss              a row-softmax loss is a kernel of its own: the next step.
   MultiTaskDivergenceCrossEntropyLoss,                          they take [batch, models, classes] support predictions from plugins
   MultiTaskDivergenceCrossEntropyAndMSELoss                     this repository does not have.
---label_loss with one of these names ends in StopIteration at train.find_class_by_name, as any unknown name does."""
+--label_loss with one of these names ends in StopIteration at train.find_class_by_name, as any unknown name does.
+
+From Z/losses.py (Z = youtube-8m-zhangteng): calculate_loss_mix's default branch -- calculate_loss(predictions) + 0.1 *
+calculate_loss(predictions_class, the labels tiled) -- is a training rule, not a loss class: train.TrainGraph._mix_loss.  Left out of it:
+  its --support_type branches "class", "frequent", "encoder"    --support_type is W's flag here and has W's meaning; no model of the
+                                                                final submission's list sets Z's.
+  calculate_loss_mix2                                           it reads "predictions_encoder" and autoencoder files no plugin here has."""
 import torch
 
 from . import ops

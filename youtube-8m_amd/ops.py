@@ -1537,6 +1537,148 @@ def distill_blend(p1, t, w, bound):
     return _DistillBlend.apply(p1, t, w)
 
 
+# YT8M_MIX_LINK_FUSED, 0: mix_link composes the existing ops in the reference's order; anything else (the default): one product and the
+# kernels of csrc/mix_link.hip.  Fused is the default because tools/mix_chain_step.py's op leg measured its median below the composed
+# form's at every one of the four shapes in both runs of the leg, 1.4 - 1.9 x (DESIGN_LOG.md section 40).  The form with a given q
+# (MoeKnowledgeModel) has a switch of its own, YT8M_MIX_LINK_FUSED_Q, and stays composed by default: its row was below the composed form's
+# in one run of two (320 against 375 us, then 451 against 433 on a noisy machine), and its whole step is level.
+MIX_LINK_FUSED = os.environ.get("YT8M_MIX_LINK_FUSED", "1") != "0"
+MIX_LINK_FUSED_Q = os.environ.get("YT8M_MIX_LINK_FUSED_Q", "0") != "0"
+MIX_LINK_CALLS = {"kernels": 0, "composed": 0}       # which form ran (tests)
+MIX_LINK_PLAIN, MIX_LINK_NONE = 1, 2                 # enum yt8m_mix_link_mode
+
+
+def mix_link_composed(prev, p, W1, b1, W2, b2, q=None, norm=True, scale=1.0, eps=1e-12):
+    """mix_link as the reference writes it: two products on p and on a materialised 1 - p (or on q), two elu passes, two
+    l2-normalisations with a scale and torch.cat."""
+    c1 = activation(linear(p, W1, b1), "elu")
+    c2 = activation(linear((1.0 - p) if q is None else q, W2, b2), "elu")
+    if norm:
+        c1, c2 = l2_normalize(c1, eps) * scale, l2_normalize(c2, eps) * scale
+    return torch.cat([prev, c1, c2], dim=1)
+
+
+class _MixProduct(torch.autograd.Function):
+    """The host's half of a fused mix_link in the complement mode: z [rows, 2 C] = x . [W1 | W2], ONE product without biases, and
+    u [2 C] = [b1 | colsum(W2) + b2], the column sum taken in float64 and rounded once, so that the kernel's u2 - z2 is
+    (1 - x) . W2 + b2.  Backward: the weight gradients x^T . dz as one grouped launch into the Variables' arena slots, the biases' from
+    du, colsum(W2)'s share du2 broadcast onto W2's gradient, and dx as ONE product dz . [W1 | W2]^T (the complement's sign is already
+    in dz)."""
+
+    @staticmethod
+    def forward(ctx, token, W1, b1, W2, b2, x):
+        x = _f32c(x)
+        Wcat = torch.cat([W1.data, W2.data], dim=1)
+        z = gemm(x, Wcat)
+        u2 = (W2.data.sum(dim=0, dtype=torch.float64) + b2.data.double()).float()
+        ctx.save_for_backward(x, Wcat)
+        ctx.vars = (W1, b1, W2, b2)
+        return z, torch.cat([b1.data.view(-1), u2.view(-1)])
+
+    @staticmethod
+    def backward(ctx, dz, du):
+        W1, b1, W2, b2 = ctx.vars
+        x, Wcat = ctx.saved_tensors
+        dz, du = _f32c(dz), _f32c(du)
+        C = W1.data.shape[1]
+        dx = gemm(dz, Wcat, transB=True) if ctx.needs_input_grad[5] else None
+        items = [dict(A=x, B=dz[:, k * C:(k + 1) * C], out=W.grad, beta=W.grad_beta())
+                 for k, W in enumerate((W1, W2)) if W.trainable and W.grad is not None]
+        if items:
+            gemm_grouped(items, transA=True, role="dw")
+        if W2.trainable and W2.grad is not None:
+            W2.grad.add_(du[C:])                                          # colsum(W2) reaches every row of W2 alike
+        for b, g in ((b1, du[:C]), (b2, du[C:])):
+            if b.trainable and b.grad is not None:
+                if b.grad_beta() == 0.0:
+                    b.grad.view(-1).copy_(g)
+                else:
+                    b.grad.view(-1).add_(g)
+        return None, None, None, None, None, dx
+
+
+class _MixLink(torch.autograd.Function):
+    """csrc/mix_link.hip: [prev | y1 | y2] from z and u in one pass each way.  Saved for backward: z, u and stats [2, rows]."""
+
+    @staticmethod
+    def forward(ctx, prev, z, u, bits, scale, dx_from, eps):
+        prev, z, u = _f32c(prev), _f32c(z), _f32c(u)
+        _dev(prev, z, u)
+        rows, Wprev = prev.shape
+        C = z.shape[1] // 2
+        out = torch.empty((rows, Wprev + 2 * C), dtype=torch.float32, device=prev.device)
+        stats = torch.empty((2, rows), dtype=torch.float32, device=prev.device)
+        _lib.check(_lib.lib().yt8m_mix_link_fwd(bits, _p(prev), _p(z), _p(u), _p(out), _p(stats), rows, Wprev, C, float(scale), float(eps),
+                                                _stream()))
+        ctx.bits, ctx.scale, ctx.Wprev, ctx.dx_from = bits, float(scale), Wprev, int(dx_from)
+        ctx.save_for_backward(z, u, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, u, stats = ctx.saved_tensors
+        dy = _f32c(dy)
+        rows, C = z.shape[0], z.shape[1] // 2
+        dprev = None
+        if ctx.needs_input_grad[0]:                                       # the data columns in front hold zeros
+            dprev = (torch.zeros if ctx.dx_from else torch.empty)((rows, ctx.Wprev), dtype=torch.float32, device=z.device)
+        dz = torch.empty_like(z)
+        _lib.check(_lib.lib().yt8m_mix_link_bwd(ctx.bits, _p(z), _p(u), _p(stats), _p(dy), _p(dprev), _p(dz), rows, ctx.Wprev, C, ctx.dx_from,
+                                                ctx.scale, _stream()))
+        du = colsum(dz, torch.empty(2 * C, dtype=torch.float32, device=z.device))
+        if not ctx.bits & MIX_LINK_PLAIN:
+            du[C:].neg_()                                                 # dz2 carries the complement's sign, u2's gradient does not
+        return dprev, dz, du, None, None, None, None
+
+
+def mix_link(prev, p, W1, b1, W2, b2, q=None, norm=True, scale=1.0, dx_from=0, eps=1e-12):
+    """[rows, Wprev + 2 C]: the input of the next MoE stage of the MoeMix4 / MoeKnowledge heads (Z/video_level_models.py:1997-2013,
+    :1391-1407) from the previous stage's input prev [rows, Wprev] and its prediction p [rows, V]:
+        c1 = elu(p . W1 + b1);  c2 = elu((1 - p) . W2 + b2), or elu(q . W2 + b2) for a given q [rows, K] (MoeKnowledge: q = p . seq);
+        norm: c_k = l2_normalize(c_k) * scale;  out = [prev | c1 | c2].
+    W1, b1, W2, b2 are Variables (class_inputs1-<i>, class_inputs2-<i>).  dx_from: the leading columns of prev that are data (no
+    gradient is computed for them; the returned gradient holds zeros there).
+    YT8M_MIX_LINK_FUSED (read at import): 1, the default, is one product z = p . [W1 | W2] and the fused kernel pair, where the
+    complement is u2 - z2 with u2 = colsum(W2) + b2 and no 1 - p tensor exists; 0 is the composed form (mix_link_composed).  With q
+    the switch is YT8M_MIX_LINK_FUSED_Q, 0 by default: the composed form, 1: the two products, then the kernel pair.  CPU tensors,
+    non-float32 tensors and shapes yt8m_mix_link_supported refuses (C > 1024) always take the composed form."""
+    C = W1.data.shape[1]
+    if prev.dim() != 2 or p.dim() != 2 or prev.shape[0] != p.shape[0] or (q is not None and (q.dim() != 2 or q.shape[0] != p.shape[0])) \
+            or tuple(W2.data.shape) != ((p if q is None else q).shape[1], C) or W1.data.shape[0] != p.shape[1] or not 0 <= dx_from <= prev.shape[1]:
+        raise ValueError("mix_link: prev [rows, Wprev], p [rows, V], q [rows, K] or None, W1 [V, C], W2 [V or K, C] and 0 <= dx_from <= Wprev, "
+                         "got %s, %s, %s, %s, %s, dx_from = %d" % (tuple(prev.shape), tuple(p.shape), None if q is None else tuple(q.shape),
+                                                                  tuple(W1.data.shape), tuple(W2.data.shape), dx_from))
+    fused = ((MIX_LINK_FUSED if q is None else MIX_LINK_FUSED_Q) and prev.shape[0] > 0 and all(t.is_cuda and t.dtype == torch.float32 for t in (prev, p) + (() if q is None else (q,)))
+             and bool(_lib.lib().yt8m_mix_link_supported(prev.shape[1], C)))
+    MIX_LINK_CALLS["kernels" if fused else "composed"] += 1
+    if not fused:
+        return mix_link_composed(prev, p, W1, b1, W2, b2, q, norm, scale, eps)
+    if q is None:
+        z, u = _MixProduct.apply(_token(W1._graph), W1, b1, W2, b2, p)
+    else:                                                                 # two inputs: the composed form's own two products
+        z, u = torch.cat([linear(p, W1), linear(q, W2)], dim=1), torch.cat([as_tensor(b1), as_tensor(b2)])
+    bits = (0 if q is None else MIX_LINK_PLAIN) | (0 if norm else MIX_LINK_NONE)
+    return _MixLink.apply(prev, z, u, bits, scale, dx_from, eps)
+
+
+class _MatConst(torch.autograd.Function):
+    """x . S for a constant matrix S [V, K] (MoeKnowledgeModel's class matrix): dx = dy . S^T."""
+
+    @staticmethod
+    def forward(ctx, x, S):
+        ctx.S = S
+        return gemm(_f32c(x), S)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return gemm(_f32c(dy), ctx.S, transB=True), None
+
+
+def matmul_const(x, S):
+    """x [rows, V] . S [V, K], S a constant of the model (no gradient).  CPU tensors take torch.matmul (host tests)."""
+    return _MatConst.apply(x, S) if x.is_cuda else x @ S
+
+
 class _LinearGroup(torch.autograd.Function):
     """y_k = x_k . W_k (+ b_k) for n products of one shape family, each direction one grouped launch (gemm_grouped): the forward
     products, the weight gradients x_k^T . dy_k (role "dw") into the Variables' arena slots, and dx_k = dy_k . W_k^T for the inputs that

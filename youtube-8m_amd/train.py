@@ -152,6 +152,8 @@ class TrainGraph(object):
     def _label_loss(self, result, labels, weights):
         if "prediction_frames" in result:
             return self._frames_loss(result["prediction_frames"], labels, weights)
+        if "predictions_class" in result:
+            return self._mix_loss(result["predictions"], result["predictions_class"], labels, weights)
         if self.multitask:                                        # W/train.py:394-413
             return self.label_loss_fn.calculate_loss(result["predictions"], result["support_predictions"], labels, weights=weights)
         return self.label_loss_fn.calculate_loss(result["predictions"], labels, weights=weights)
@@ -173,6 +175,23 @@ class TrainGraph(object):
         if weights is not None and L != 1:
             weights = weights.repeat_interleave(L, dim=0)
         return self.label_loss_fn.calculate_loss(prediction_frames, labels_frames, weights=weights)
+
+    def _mix_loss(self, predictions, predictions_class, labels, weights):
+        """The Z training rule for a result that holds "predictions_class" [B, L V] (Z/train.py:318-349, Z/losses.py:280-313
+        calculate_loss_mix, its default branch): calculate_loss(predictions, labels) + 0.1 * calculate_loss(predictions_class, labels
+        tiled L times along the columns) -- with --label_loss=CrossEntropyLoss one sum over all L V columns and a mean over the batch.
+        Left out: Z's --support_type branches of this loss ("class", "frequent", "encoder" -- --support_type is W's flag here and has
+        W's meaning) and calculate_loss_mix2 (results with "predictions_encoder"); no model of the final submission's list takes them."""
+        if self.multitask:
+            raise ValueError("--multitask takes its loss from predictions and support_predictions; a model that returns "
+                             "predictions_class is trained by Z's mix loss (Z/losses.py:280-313) and has no such combination")
+        V, width = labels.shape[1], predictions_class.shape[1]
+        if V == 0 or width == 0 or width % V != 0:
+            raise ValueError("predictions_class is %d wide for %d labels: not a whole multiple" % (width, V))
+        L = width // V
+        labels_class = labels if L == 1 else labels.repeat(1, L)
+        return self.label_loss_fn.calculate_loss(predictions, labels, weights=weights) + \
+            0.1 * self.label_loss_fn.calculate_loss(predictions_class, labels_class, weights=weights)
 
     def loss(self, result, labels_batch, weights=None, distill_labels_batch=None):
         """W/train.py:384-430: a model-provided "loss" wins; otherwise the label loss, optionally blended with / replaced by

@@ -19,6 +19,10 @@ DEFINE_bool("deep_chain_use_length", False, "unused by DeepCombineChainModel (ke
 DEFINE_integer("moe_num_extend", 8, "The number of attention outputs, used for MoeExtendModel.")      # Z/video_level_models.py:31
 DEFINE_float("ensemble_w", 1.0, "ensemble weight used in distill chain models.")                        # Z/video_level_models.py:52-58
 DEFINE_integer("softmax_bound", 1000, "The number of labels to be a group, used for MoeSoftmaxModel and MoeDistillSplitModel.")
+DEFINE_integer("moe_layers", 1, "The number of combine layers, used for combine related models.")      # Z/video_level_models.py:36-56
+DEFINE_integer("class_size", 200, "The dimention of prediction projection, used for all chain models.")
+DEFINE_bool("moe_group", False, "Whether to split the 4716 labels into different groups, used in MoeMix4Model (not built here)")
+DEFINE_string("class_file", "./resources/labels_knowledge.out", "The label-to-class matrix [V, K] that MoeKnowledgeModel reads (np.loadtxt).")
 # new: MoeModel may return its own "loss" (W/train.py:384-385 honours it) computed by the fused mixing+cross-entropy pass
 DEFINE_bool("fused_head_loss", True, "MoeModel returns {'loss': CrossEntropyLoss(predictions, labels)} from a fused kernel "
             "when labels are given, --label_loss=CrossEntropyLoss, no label smoothing and no --multitask.")
@@ -295,3 +299,82 @@ class MoeDistillSplitModel(MoeDistillChainModel):
     predicts the first V1 labels only, and predictions = concat(p1, t[:, V1:]) * --ensemble_w + t * (1 - --ensemble_w): the other labels
     are the teacher's own.  0 < V1 < V is asserted."""
     MODE, SPLIT = "split", True
+
+
+# ---- Z's combine chain heads: MoE stages chained through a pair of elu "class inputs" per stage -------------------------------------
+_CLASS_MATRICES = {}      # (file, device) -> device tensor [V, K] (the reference's tf.constant of np.loadtxt(--class_file))
+
+
+def _class_matrix(device):
+    """--class_file as a float32 [V, K] constant on `device`, loaded once per (file, device) as losses._vertical_mapping does."""
+    key = (FLAGS.class_file, str(device))
+    seq = _CLASS_MATRICES.get(key)
+    if seq is None:
+        import numpy as np
+        seq = torch.from_numpy(np.atleast_2d(np.loadtxt(FLAGS.class_file)).astype(np.float32)).to(device).contiguous()
+        _CLASS_MATRICES[key] = seq
+    return seq
+
+
+def mix_chain_head(model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, knowledge=False, normalize=True, support_pool=None):
+    """The body of the two heads below.  An MoE block under "gates" / "experts" gives p; for i < --moe_layers, ops.mix_link under
+    "class_inputs1-<i>" and "class_inputs2-<i>" (--class_size wide each: c1 = elu(FC(p)), c2 = elu(FC(1 - p)), or elu(FC(p . seq)) with
+    `knowledge`; with `normalize` each l2-normalised and multiplied by sqrt(class_size / D), D the width of the head's own input) grows
+    the stage input to [previous input | c1 | c2], and the MoE block under "gates-<i>" / "experts-<i>" gives the next p.  Returns
+    "predictions", the last p, and "predictions_class", the first --moe_layers of the --moe_layers + 1 predictions side by side
+    (support_pool, where given, applied to each piece and to the predictions first, as DeepCombineChainModel's).  Variables in the
+    reference's order: gates, experts, then per stage class_inputs1-i, class_inputs2-i, gates-i, experts-i; xavier weights under
+    l2_penalty, zero biases, no bias on the gates.  model_input is data in video-level use (no head computes a gradient for its
+    columns) and an attention-pooled LSTM output in frame-level use."""
+    g = get_default_graph()
+    M = num_mixtures or FLAGS.moe_num_mixtures
+    C, layers = int(FLAGS.class_size), int(FLAGS.moe_layers)
+    D = int(model_input.shape[1])
+    scale = float(torch.sqrt(torch.tensor(float(C), dtype=torch.float32) / D))       # tf.sqrt(tf.cast(class_size, tf.float32) / shape)
+    frozen = 0 if model_input.requires_grad else D
+    seq = _class_matrix(model_input.device) if knowledge else None
+    if seq is not None and seq.shape[0] != vocab_size:
+        raise ValueError("--class_file=%s holds %d rows for %d labels" % (FLAGS.class_file, seq.shape[0], vocab_size))
+    pool = support_pool or (lambda t: t)
+    stage_input = model_input
+    p = moe_block(stage_input, vocab_size, M, l2_penalty, "gates", "experts", frozen_cols=frozen)
+    pieces = []
+    for i in range(layers):
+        pieces.append(pool(p))
+        W1 = g.get_variable("class_inputs1-%d/weights" % i, (vocab_size, C), xavier_uniform, l2=l2_penalty)
+        b1 = g.get_variable("class_inputs1-%d/biases" % i, (C,), zeros)
+        q = ops.matmul_const(p, seq) if knowledge else None
+        W2 = g.get_variable("class_inputs2-%d/weights" % i, (vocab_size if q is None else q.shape[1], C), xavier_uniform, l2=l2_penalty)
+        b2 = g.get_variable("class_inputs2-%d/biases" % i, (C,), zeros)
+        stage_input = ops.mix_link(stage_input, p, W1, b1, W2, b2, q=q, norm=normalize, scale=scale, dx_from=frozen)
+        p = moe_block(stage_input, vocab_size, M, l2_penalty, "gates-%d" % i, "experts-%d" % i, frozen_cols=frozen)
+    res = {"predictions": pool(p)}
+    if pieces:
+        res["predictions_class"] = pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=1)
+    return res
+
+
+class MoeMix4Model(models.BaseModel):
+    """Z/video_level_models.py:1872-2044, the --moe_group=False path: mix_chain_head with c2 = elu(FC(1 - p)); the class inputs are
+    normalised unless --frame_features.  Its result holds "predictions_class" [B, --moe_layers V], which train.TrainGraph trains by
+    Z's mix loss (TrainGraph._mix_loss).  With --moe_layers=0 the reference returns its one prediction under both keys."""
+
+    def create_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, original_input=None, support_pool=None,
+                     **unused_params):
+        if FLAGS.moe_group:
+            raise NotImplementedError("MoeMix4Model --moe_group=True (label groups of --class_size) is not built: no script of the final "
+                                      "submission's list sets it")
+        frame_features = "frame_features" in FLAGS and FLAGS.frame_features
+        res = mix_chain_head(model_input, vocab_size, num_mixtures, l2_penalty, normalize=not frame_features, support_pool=support_pool)
+        res.setdefault("predictions_class", res["predictions"])
+        return res
+
+
+class MoeKnowledgeModel(models.BaseModel):
+    """Z/video_level_models.py:1331-1438: MoeMix4Model's chain with c2 = elu(FC(p . seq)), seq [V, K] the constant matrix of
+    np.loadtxt(--class_file); as in the reference its class inputs are normalised whatever --frame_features says."""
+
+    def create_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, original_input=None, **unused_params):
+        res = mix_chain_head(model_input, vocab_size, num_mixtures, l2_penalty, knowledge=True)
+        res.setdefault("predictions_class", res["predictions"])
+        return res
