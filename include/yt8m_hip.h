@@ -499,7 +499,7 @@ int yt8m_lnlstm_layer_bwd(const float* z, const float* Wh, int64_t ldw, const fl
                           float keep_prob, uint64_t seed, void* gemm_workspace, int64_t gemm_workspace_bytes,
                           yt8m_stream_t stream);
 
-/* ---- scalar-gate LSTM layer (csrc/gate_lstm.hip), time-major, generic per-step form ---------------------------------
+/* ---- scalar-gate LSTM layer (csrc/gate_cell.hip, step order), time-major, generic per-step form ---------------------
  * The recurrent unit of Z/frame_level_models.py:1583-1640 (LstmGateModel; LstmGateMultilayerModel :1733-1790) under a plain
  * tf.while_loop over all F steps -- no copy-through, no masking; h_0 = c_0 = 0:
  *   i = sigmoid(x.Wi + h.Ui + bi) [B,1],  f = sigmoid(x.Wf + h.Uf + bf) [B,1],  o = sigmoid(x.Wog + h.Uog + bog) [B,H],
@@ -523,7 +523,7 @@ int yt8m_gate_lstm_layer_bwd(const float* zv, const float* zs, int64_t lds, cons
                              float* work, const int32_t* num_frames, int64_t F, int64_t B, int64_t H, void* gemm_workspace,
                              int64_t gemm_workspace_bytes, yt8m_stream_t stream);
 
-/* ---- scalar-gate LSTM layer over frames in a per-video order (csrc/bigate_lstm.hip), time-major, generic per-step form ---------
+/* ---- scalar-gate LSTM layer over frames in a per-video order (csrc/gate_cell.hip, frame order), time-major, generic per-step form -
  * The same cell for LstmBigluModel (Z/frame_level_models.py:887-1158): its first unit (:975-1032) runs over
  * tf.reverse_sequence(model_input, num_frames) (:906, :923-934) and tf.reverse_sequence of its hidden outputs (:941) enters every
  * gate of the second unit (:1034-1101), which runs over the frames in order (:952-963).  Here every time-indexed operand the caller

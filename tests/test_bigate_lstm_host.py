@@ -1,5 +1,5 @@
 """CPU checks of LstmBigluModel (Z/frame_level_models.py:887-1158) and of the frame-order scalar-gate recurrence's C ABI
-(csrc/bigate_lstm.hip): the lookup by name, the 12 + 16 + 3 Variables (order, names, shapes, l2, initial values), the head's names,
+(csrc/gate_cell.hip): the lookup by name, the 12 + 16 + 3 Variables (order, names, shapes, l2, initial values), the head's names,
 the header / signature table / exports, argument validation without a device, and the composed form of seq_ops.bigate_lstm_layer and
 the model on the CPU against the fp64 restatement (tests/bigate_lstm_restatement.py), which makes the reference's reverse_sequence copies."""
 import ctypes

@@ -1,4 +1,4 @@
-"""CPU checks of the scalar-gate LSTM plugins (Z/frame_level_models.py:1521-1790) and of their layer's C ABI (csrc/gate_lstm.hip): the
+"""CPU checks of the scalar-gate LSTM plugins (Z/frame_level_models.py:1521-1790) and of their layer's C ABI (csrc/gate_cell.hip): the
 lookup by name, the twelve Variables per layer (names, shapes, l2, initial values), the header / signature table / exports, argument
 validation without a device, and the composed form of seq_ops.gate_lstm_layer against the fp64 restatement."""
 import ctypes

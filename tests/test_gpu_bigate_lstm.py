@@ -1,4 +1,4 @@
-"""-m gpu: the frame-order scalar-gate recurrence (csrc/bigate_lstm.hip), seq_ops.bigate_lstm_layer in its three forms and
+"""-m gpu: the frame-order scalar-gate recurrence (csrc/gate_cell.hip), seq_ops.bigate_lstm_layer in its three forms and
 LstmBigluModel against the fp64 restatement (tests/bigate_lstm_restatement.py), which makes the reference's reverse_sequence copies.
 
 Bounds.  As tests/test_gpu_gate_lstm.py: the measure is max |got - ref| / max(1, max |ref|); per quantity the bound is EIGHT times the

@@ -1,4 +1,4 @@
-"""-m gpu: the scalar-gate LSTM layer (csrc/gate_lstm.hip, seq_ops.gate_lstm_layer) and LstmGateMultilayerModel against the fp64
+"""-m gpu: the scalar-gate LSTM layer (csrc/gate_cell.hip, seq_ops.gate_lstm_layer) and LstmGateMultilayerModel against the fp64
 restatement (tests/gate_lstm_restatement.py).
 
 Bounds.  The measure is the fp64 tests' max |got - ref| / max(1, max |ref|).  Per quantity the bound is EIGHT times the error of the

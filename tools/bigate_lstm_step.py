@@ -1,10 +1,10 @@
-"""The scalar-gate pair of LstmBigluModel (seq_ops.bigate_lstm_layer, csrc/bigate_lstm.hip) and the model at the training scripts' shapes.
+"""The scalar-gate pair of LstmBigluModel (seq_ops.bigate_lstm_layer, the frame-order form of csrc/gate_cell.hip) and the model at the training scripts' shapes.
 `op` (timed first, and run twice by the driver: two runs of the leg): forward + backward of the op through autograd in its three forms
 -- the frame-order kernels, the same kernels over reversed copies (YT8M_BIGATE_LSTM_REVERSED=1) and the composed torch loops (a few
 iterations only) -- at [F, B, D, H] = [300, 128, 1152, 1024] and [300, 32, 1152, 1024] on the reader's bytes and [300, 128, 1024, 1024] on
 floats: hip events around back-to-back calls, the two kernel forms alternating inside every repeat, the spread over the repeats
 recorded, values and gradients compared.  Each row also times ONE pass alone on given hoisted inputs, per step: the frame-order entry
-points with either row map beside the step-order ones of csrc/gate_lstm.hip (yt8m_gate_lstm_layer_fwd / _bwd).  The driver adds an `op_summary` row: whether the frame-order median was below the
+points with either row map beside the step-order ones of the same file (yt8m_gate_lstm_layer_fwd / _bwd).  The driver adds an `op_summary` row: whether the frame-order median was below the
 reversed-copies one at every shape in both runs of the leg -- what decides the default of the switch.
 `step`: whole training steps (fp32, clip + Adam, learning rate 0) of LstmBigluModel (--moe_num_mixtures=8) in both kernel forms and of
 LstmGateModel and LstmGlu2Model, in ONE process and in turn inside every repeat, on raw uint8 frames [128, 300, 1152].
@@ -63,7 +63,7 @@ def op(iters, repeats):
         (of, gf), (orv, grv), (oc, gc) = run(True, False), run(True, True), run(False, False)
         seq_ops.BIGATE_LSTM_FUSED, seq_ops.BIGATE_LSTM_REVERSED = True, default
         # one pass alone on given hoisted inputs: the frame-order entry points with either row map beside the step-order ones of
-        # csrc/gate_lstm.hip (the same cell; their product accumulates in place, theirs needs no scratch row and no hprev)
+        # csrc/gate_cell.hip (the same cell; their product accumulates in place, theirs needs no scratch row and no hprev)
         new = lambda *s: torch.empty(s, device=dev)
         zv0, zs0 = torch.randn((F_, B_, 2 * H), device=dev, generator=gen) * 0.5, torch.randn((F_, B_, 2), device=dev, generator=gen) * 0.5
         zv, zs, yb, hp, c_last, dzv, dzs = zv0.clone(), zs0.clone(), new(F_, B_, H), new(F_, B_, H), new(B_, H), new(F_, B_, 2 * H), new(F_, B_, 2)

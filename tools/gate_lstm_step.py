@@ -1,4 +1,4 @@
-"""The scalar-gate LSTM layer (seq_ops.gate_lstm_layer, csrc/gate_lstm.hip) and LstmGateModel at the training scripts' shapes.
+"""The scalar-gate LSTM layer (seq_ops.gate_lstm_layer, csrc/gate_cell.hip) and LstmGateModel at the training scripts' shapes.
 `op` (timed first, and run twice by the driver: two runs of the leg): forward + backward of ONE layer through autograd, the step kernels
 against the composed torch form (the YT8M_GATE_LSTM_FUSED=0 form), at [F, B, D, H] = [300, 128, 1152, 1024] and [300, 32, 1152, 1024] on
 the reader's bytes and [300, 128, 1024, 1024] on floats (a second layer): hip events around back-to-back calls, the two forms alternating

@@ -12,7 +12,8 @@
 // and are carried as states of their own: no product with K = D inside the time loop.  Per step there is one grouped-GEMM launch for
 // h.[Uog|Uc] and one pointwise kernel, one workgroup per batch row: four (forward) or five (backward) block-wide row sums on one
 // barrier pair, in the forward kernel a second pair for n2'.
-#include <stdlib.h>
+// The kernels stay apart from the two-gate cell of gate_cell.hip: four scalar gates, the r q terms in every pre-activation, five sums
+// on the barrier and the xm pass would each be a hook in a shared body, and the hooks would cost more than the lines they save.
 #include "step_kernels.h"
 
 namespace {
@@ -360,18 +361,14 @@ extern "C" int yt8m_glu_lstm_layer_bwd(const float* zv, const float* pv, int64_t
   YT8M_HIP_CHECK(seed_state(dqv, nullptr, 2 * BH, s));
   YT8M_HIP_CHECK(seed_state(dxm, nullptr, BD + 8 * B, s));
   // dzv . [Uog|Uc]^T on the packed step launcher of lstm_fused.hip (cell_step_bwd, G = 2) where the workspace holds the packed
-  // weights, as in gate_lstm.hip; the launcher reads contiguous rows, so the kernel leaves it a copy of dzv_t in work
-  const char* sw = getenv("YT8M_GLU_LSTM_PACKED_BWD");
-  const bool packed = !(sw && atoi(sw) == 0) && packed_fits(B, H, 2, gemm_workspace, gemm_workspace_bytes);
-  float* Wq = packed ? static_cast<float*>(gemm_workspace) : nullptr;
-  if (packed) {
-    int rc = cell_pack_scoped(Uv, ldu, nullptr, Wq, H, 2, s);
-    if (rc != YT8M_OK) return rc;
-  }
+  // weights, as in gate_cell.hip; the launcher reads contiguous rows, so the kernel leaves it a copy of dzv_t in work
+  const float* Wq;
+  int rc = packed_bwd_weights("YT8M_GLU_LSTM_PACKED_BWD", Uv, ldu, B, H, 2, gemm_workspace, gemm_workspace_bytes, s, &Wq);
+  if (rc != YT8M_OK) return rc;
   const StepProduct rec = {Uv, ldu, nullptr, Wq, 2, B, H, gemm_workspace, gemm_workspace_bytes, stream, lddv};
   auto kfn = YT8M_ROW_KERNEL(glu_lstm_bwd_kernel, H, 1);
   BwdArgs a;
-  a.ldv = ldv; a.lds = lds; a.Us = Us; a.dc_last = dc_last; a.lddv = lddv; a.dav = packed ? dav : nullptr; a.dqv = dqv; a.dxm = dxm;
+  a.ldv = ldv; a.lds = lds; a.Us = Us; a.dc_last = dc_last; a.lddv = lddv; a.dav = Wq ? dav : nullptr; a.dqv = dqv; a.dxm = dxm;
   a.dsc = dsc; a.nf = num_frames; a.xq = xq; a.F = F; a.H = H; a.D = D;
   for (int64_t t = F - 1; t >= 0; --t, g.swap()) {
     a.zv = zv + t * B * ldv;
@@ -390,7 +387,7 @@ extern "C" int yt8m_glu_lstm_layer_bwd(const float* zv, const float* pv, int64_t
       ProfScope prof(F_LSTM, s);
       hipLaunchKernelGGL(kfn, dim3((unsigned)B), dim3(256), 0, s, a);
     }
-    int rc = rec.add_dzWt(packed ? dav : a.dzv, g.dh_prev);                                            // dh_prev += dzv_t . [Uog|Uc]^T
+    rc = rec.add_dzWt(Wq ? dav : a.dzv, g.dh_prev);                                                // dh_prev += dzv_t . [Uog|Uc]^T
     if (rc != YT8M_OK) return rc;
   }
   return launch_status("glu_lstm_bwd_kernel");

@@ -1,6 +1,7 @@
 // step_kernels.h -- the per-step recurrence launchers of lstm_fused.hip, declared once for the drivers that sequence them
 // (sequence.hip, cells.hip, lstm_bf16.hip), and the small host pieces every time loop shares.  No launcher opens a ProfScope.
 #pragma once
+#include <stdlib.h>
 #include <algorithm>
 #include <initializer_list>
 #include "common.h"
@@ -62,9 +63,9 @@ struct StepProduct {
   }
 };
 
-// ---- what every row-per-workgroup cell driver repeats (cells.hip's LN-LSTM, gate_lstm.hip, glu_lstm.hip) ------------------
+// ---- what every row-per-workgroup cell driver repeats (cells.hip's LN-LSTM, gate_cell.hip, glu_lstm.hip) ------------------
 // whether the packed weights of G gates fit the workspace and the packed launchers take the shape; the environment switches that
-// keep the grouped GEMM stay with each caller
+// keep the grouped GEMM stay with each caller (cells.hip reads its own once per process) or with packed_bwd_weights below
 inline bool packed_fits(int64_t B, int64_t H, int G, const void* ws, int64_t ws_bytes) {
   return ws && cell_packed_supported(B, H) && ws_bytes >= (int64_t)sizeof(float) * H * G * H;
 }
@@ -73,10 +74,23 @@ inline int cell_pack_scoped(const float* Wh, int64_t ldw, float* Wp, float* Wq, 
   ProfScope prof(F_LSTM, s);
   return cell_pack(Wh, ldw, Wp, Wq, H, G, s);
 }
-// K<PT>, the step kernel template K at the fewest units per thread that cover H with 256 threads: PT = MIN_PT (1 or 2), 2, 4 or ROW_PT
+// The weights of a backward recurrence's product dz . Wh^T (StepProduct::Wq): *Wq = the head of the workspace, filled by cell_pack
+// under an F_LSTM scope of its own, where packed_fits; *Wq = null (the grouped GEMM) where not, or where the environment switch
+// `sw_name` is set to 0.  The switch is read at every call: an A/B switch for tools/ and tests.
+inline int packed_bwd_weights(const char* sw_name, const float* Wh, int64_t ldw, int64_t B, int64_t H, int G, void* ws,
+                              int64_t ws_bytes, hipStream_t s, const float** Wq) {
+  const char* sw = getenv(sw_name);
+  *Wq = nullptr;
+  if ((sw && atoi(sw) == 0) || !packed_fits(B, H, G, ws, ws_bytes)) return YT8M_OK;
+  *Wq = static_cast<float*>(ws);
+  return cell_pack_scoped(Wh, ldw, nullptr, static_cast<float*>(ws), H, G, s);
+}
+// K<PT, ...>, the step kernel template K at the fewest units per thread that cover H with 256 threads: PT = MIN_PT (1 or 2), 2, 4 or
+// ROW_PT; further template arguments of K follow MIN_PT
 constexpr int ROW_PT = 8;                      // H <= 256 * ROW_PT
-#define YT8M_ROW_KERNEL(K, H, MIN_PT) \
-  ((H) <= 256 * (MIN_PT) ? K<MIN_PT> : (H) <= 512 ? K<2> : (H) <= 1024 ? K<4> : K<yt8m::ROW_PT>)
+#define YT8M_ROW_KERNEL(K, H, MIN_PT, ...)                                                                                \
+  ((H) <= 256 * (MIN_PT) ? K<MIN_PT, ##__VA_ARGS__> : (H) <= 512 ? K<2, ##__VA_ARGS__> : (H) <= 1024 ? K<4, ##__VA_ARGS__> \
+                                                                                                     : K<yt8m::ROW_PT, ##__VA_ARGS__>)
 
 // dst[n] = src[n], or zeros when there is no src (the gradients of the final state)
 inline hipError_t seed_state(float* dst, const float* src, int64_t n, hipStream_t s) {

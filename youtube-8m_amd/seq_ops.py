@@ -167,6 +167,48 @@ def _hoisted_input(x_tm, bf16):
     return x_tm if isinstance(x_tm, U8FrameImages) else _FloatFrames(x_tm, bf16)
 
 
+class _Hoisted(object):
+    """One hoisted input block of a cell layer and its share of backward: z [F B, N] = frames . W + b over all steps at once.  W [D,n]
+    and b [n] are detached to contiguous fp32; with pad_to > n both are zero-padded to N = pad_to columns in scratch (the byte
+    products' scaled epilogue stores float4: N % 4 == 0) -- the step kernels touch the first n columns of such rows, the gradients
+    come back with the padding sliced off."""
+
+    def __init__(self, frames, W, b, pad_to=0):
+        self.frames, self.n = frames, W.shape[1]
+        W, b = W.detach().float().contiguous(), b.detach().float().reshape(-1)
+        if pad_to > self.n:
+            Wp, bp = self._new(W.shape[0], pad_to, zero=True), self._new(pad_to, zero=True)
+            Wp[:, :self.n].copy_(W)
+            bp[:self.n].copy_(b)
+            W, b = Wp, bp
+        self.W = W
+        self.z = self._new(frames.F * frames.B, W.shape[1])
+        frames.project(W, b, self.z)
+
+    def _new(self, *shape, zero=False):
+        return (torch.zeros if zero else torch.empty)(shape, dtype=torch.float32, device=self.frames.device)
+
+    def dz_buffer(self):
+        """dz [F B, N] for the kernels to fill."""
+        # the padding columns are zeroed once: the kernel writes the block's own columns only, the hoisted products read every column
+        return self._new(*self.z.shape, zero=self.z.shape[1] > self.n)
+
+    def grads(self, dz, need_W, need_b):
+        """(gW [D,n], gb [n]) from dz [F B, N]; None for what is not needed."""
+        gW = gb = None
+        if need_W:
+            gW = self._new(*self.W.shape)
+            self.frames.weight_grad(dz, gW, 0.0)
+            gW = gW[:, :self.n]
+        if need_b:
+            gb = ops.colsum(dz, self._new(dz.shape[1]))[:self.n]
+        return gW, gb
+
+    def dx(self, dz, into=None):
+        """dx [F,B,D] = dz . W^T, added to `into` where given (None on byte frames: they are data)."""
+        return self.frames.dx(dz, self.W, into=into)
+
+
 class _GruLayer(torch.autograd.Function):
     """One tf.contrib.rnn.GRUCell layer under tf.nn.dynamic_rnn (W/all_frame_models/gru_pooling_model.py:34-47), time-major.
     x_tm [F,B,in]; Wg "gates/weights" [in+H, 2H] (r | u), bg "gates/biases" [2H]; Wc "candidate/weights" [in+H, H],
@@ -333,7 +375,7 @@ def lnlstm_layer(x_tm, W, gammas, betas, num_frames, forget_bias=1.0, keep_prob=
     return _LnLstmLayer.apply(x_tm, _token(W._graph), W, tuple(gammas), tuple(betas), num_frames, forget_bias, keep_prob, seed)
 
 
-# ---- scalar-gate LSTM layer (Z/frame_level_models.py:1521-1790; csrc/gate_lstm.hip) ------------------------------------
+# ---- scalar-gate LSTM layer (Z/frame_level_models.py:1521-1790; csrc/gate_cell.hip, step order) ----------------------
 GATE_LSTM_FUSED = os.environ.get("YT8M_GATE_LSTM_FUSED", "1") != "0"   # 0: the composed torch form everywhere (A/B runs, tests)
 GATE_LSTM_CALLS = {"kernels": 0, "composed": 0}     # which form ran (tests assert that the kernels engaged)
 _GATE_U8_LDS = 4                                    # the byte products' scaled epilogue stores float4: N % 4 == 0
@@ -399,15 +441,8 @@ class _GateLstmLayer(torch.autograd.Function):
         assert tuple(Wv.shape) == (Din, 2 * H) and tuple(Ws.shape) == (Din, 2) and tuple(Uv.shape) == (H, 2 * H) \
             and tuple(Us.shape) == (2, H) and bv.numel() == 2 * H and bs.numel() == 2, "gate LSTM operands: Wv [in,2H], Ws [in,2], Uv [H,2H], Us [2,H]"
         lds = _GATE_U8_LDS if isinstance(frames, U8FrameImages) else 2
-        Wv, bv, Uv, Us = (_f32c(t.detach()) for t in (Wv, bv, Uv, Us))
-        Wsp = torch.zeros((Din, lds), dtype=torch.float32, device=dev)
-        bsp = torch.zeros((lds,), dtype=torch.float32, device=dev)
-        Wsp[:, :2].copy_(Ws.detach())
-        bsp[:2].copy_(bs.detach().view(-1))
-        zv = torch.empty((F, B, 2 * H), dtype=torch.float32, device=dev)
-        zs = torch.empty((F * B, lds), dtype=torch.float32, device=dev)
-        frames.project(Wv, bv.view(-1), zv.view(F * B, 2 * H))
-        frames.project(Wsp, bsp, zs)
+        Uv, Us = _f32c(Uv.detach()), _f32c(Us.detach())
+        v, sc = _Hoisted(frames, Wv, bv), _Hoisted(frames, Ws, bs, pad_to=lds)
         hs = torch.empty((F + 1, B, H), dtype=torch.float32, device=dev)
         cs = torch.empty((F + 1, B, H), dtype=torch.float32, device=dev)
         hs[0].zero_()
@@ -415,12 +450,12 @@ class _GateLstmLayer(torch.autograd.Function):
         c_last = torch.empty((B, H), dtype=torch.float32, device=dev)
         nf = _nf(num_frames)
         ws = ops._workspace(dev)
-        _lib.check(_lib.lib().yt8m_gate_lstm_layer_fwd(_p(zv), _p(zs), lds, _p(Uv), 2 * H, _p(Us), _p(hs), _p(cs), _p(c_last), _p(nf),
+        _lib.check(_lib.lib().yt8m_gate_lstm_layer_fwd(_p(v.z), _p(sc.z), lds, _p(Uv), 2 * H, _p(Us), _p(hs), _p(cs), _p(c_last), _p(nf),
                                                        F, B, H, _p(ws), ws.numel() * 4, _stream()))
         GATE_LSTM_CALLS["kernels"] += 1
         ctx.save_for_backward(frames.saved)
         ctx.frames = frames
-        ctx.state = (zv, zs, hs, cs, nf, Wv, Wsp, Uv, Us, lds)
+        ctx.state = (v, sc, hs, cs, nf, Uv, Us, lds)
         ctx.bf16 = bf
         ctx.set_materialize_grads(False)
         return hs[1:], c_last
@@ -429,40 +464,28 @@ class _GateLstmLayer(torch.autograd.Function):
     def backward(ctx, dout, dc_last):
         ctx.saved_tensors                                            # (the frames' tensor: checked against in-place changes)
         frames = ctx.frames
-        zv, zs, hs, cs, nf, Wv, Wsp, Uv, Us, lds = ctx.state
+        v, sc, hs, cs, nf, Uv, Us, lds = ctx.state
         ctx.state = ctx.frames = None
-        F, B, Din, dev = frames.F, frames.B, frames.D, frames.device
+        F, B, dev = frames.F, frames.B, frames.device
         H = Uv.shape[0]
-        dzv = torch.empty((F, B, 2 * H), dtype=torch.float32, device=dev)
-        # the padding columns are zeroed once: the kernel writes columns 0 and 1 only, the hoisted products read every column
-        dzs = (torch.zeros if lds > 2 else torch.empty)((F * B, lds), dtype=torch.float32, device=dev)
+        v2, dzs = v.dz_buffer(), sc.dz_buffer()
         work = torch.empty((4, B, H), dtype=torch.float32, device=dev)
         dout = None if dout is None else _f32c(dout)
         dc_last = None if dc_last is None else _f32c(dc_last)
         ws = ops._workspace(dev)
-        _lib.check(_lib.lib().yt8m_gate_lstm_layer_bwd(_p(zv), _p(zs), lds, _p(Uv), 2 * H, _p(Us), _p(hs), _p(cs), _p(dout), _p(dc_last),
-                                                       _p(dzv), _p(dzs), _p(work), _p(nf), F, B, H, _p(ws), ws.numel() * 4, _stream()))
-        v2 = dzv.view(F * B, 2 * H)
+        _lib.check(_lib.lib().yt8m_gate_lstm_layer_bwd(_p(v.z), _p(sc.z), lds, _p(Uv), 2 * H, _p(Us), _p(hs), _p(cs), _p(dout), _p(dc_last),
+                                                       _p(v2), _p(dzs), _p(work), _p(nf), F, B, H, _p(ws), ws.numel() * 4, _stream()))
         h2 = hs[:F].view(F * B, H)
         need = ctx.needs_input_grad
-        gWv = gbv = gWs = gbs = gUv = gUs = dx = None
-        if need[1]:
-            gWv = torch.empty((Din, 2 * H), dtype=torch.float32, device=dev)
-            frames.weight_grad(v2, gWv, 0.0)
-        if need[2]:
-            gbv = ops.colsum(v2, torch.empty((2 * H,), dtype=torch.float32, device=dev))
-        if need[3]:
-            gWsp = torch.empty((Din, lds), dtype=torch.float32, device=dev)
-            frames.weight_grad(dzs, gWsp, 0.0)
-            gWs = gWsp[:, :2]
-        if need[4]:
-            gbs = ops.colsum(dzs, torch.empty((lds,), dtype=torch.float32, device=dev))[:2]
+        gUv = gUs = dx = None
+        gWv, gbv = v.grads(v2, need[1], need[2])
+        gWs, gbs = sc.grads(dzs, need[3], need[4])
         if need[5]:
             gUv = ops.gemm_any(h2, v2, transA=True, role="dw", bf16=ctx.bf16)
         if need[6]:
             gUs = ops.gemm_any(dzs, h2, transA=True, role="dw", bf16=ctx.bf16)[:2]
         if need[0]:
-            dx = frames.dx(dzs, Wsp, into=frames.dx(v2, Wv))
+            dx = sc.dx(dzs, into=v.dx(v2))
         return dx, gWv, gbv, gWs, gbs, gUv, gUs, None
 
 
@@ -482,14 +505,14 @@ def gate_lstm_layer(x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames):
     padding frames are zero rows of x).  Returns (out_tm [F,B,H] = every step's h, c_last [B,H] = the memory after step
     num_frames - 1, the reference's gather at :1570-1574 / :1728-1729).  Rows with num_frames < 1: the reference's flat gather index is then
     the previous video's last frame (out of range for the first video); here such a row's c_last is zeros and it receives no gradient.
-    Device tensors at shapes yt8m_gate_lstm_supported takes run on the step kernels (csrc/gate_lstm.hip); CPU tensors, other shapes and
+    Device tensors at shapes yt8m_gate_lstm_supported takes run on the step kernels (csrc/gate_cell.hip); CPU tensors, other shapes and
     YT8M_GATE_LSTM_FUSED=0 take gate_lstm_layer_composed, which computes the same function."""
     if gate_lstm_supported(x_tm, Uv.shape[0]):
         return _GateLstmLayer.apply(x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames)
     return gate_lstm_layer_composed(x_tm, Wv, bv, Ws, bs, Uv, Us, num_frames)
 
 
-# ---- the scalar-gate pair of LstmBigluModel (Z/frame_level_models.py:887-1158; csrc/bigate_lstm.hip) -----------------------------
+# ---- the scalar-gate pair of LstmBigluModel (Z/frame_level_models.py:887-1158; csrc/gate_cell.hip, frame order) ------------------
 BIGATE_LSTM_FUSED = os.environ.get("YT8M_BIGATE_LSTM_FUSED", "1") != "0"   # 0: the composed torch form everywhere (A/B runs, tests)
 # The form the kernels run in.  0: frame order -- the first pass walks every video's frames backwards inside the kernels, ONE byte
 # image, ONE [D,4H] and ONE [D,4] hoisted product for both passes, nothing reversed anywhere.  1: reversed copies -- the first pass
@@ -543,15 +566,6 @@ def bigate_lstm_layer_composed(x_tm, Wv, bv, Ws, bs, Uv1, Us1, Vv, Vs, Uv2, Us2,
     return y, out2, _gate_last_memory(cs1, num_frames), _gate_last_memory(cs2, num_frames)
 
 
-def _pad4(W, b, dev):
-    """[D,2], [2] -> zero-padded to _GATE_U8_LDS columns: the scalar block of ONE pass as a byte product wants it"""
-    Wp = torch.zeros((W.shape[0], _GATE_U8_LDS), dtype=torch.float32, device=dev)
-    bp = torch.zeros((_GATE_U8_LDS,), dtype=torch.float32, device=dev)
-    Wp[:, :2].copy_(W)
-    bp[:2].copy_(b)
-    return Wp, bp
-
-
 class _BigateLstmLayer(torch.autograd.Function):
     """Both passes of LstmBigluModel on the frame-order step kernels (yt8m_gate_lstm_frames_fwd / _bwd hold the time loops); the
     parameters are tensors under autograd.  A pass owns a column window (zv [F B, 2H], zs [F B, 2]) of the hoisted pre-activations; the
@@ -574,29 +588,23 @@ class _BigateLstmLayer(torch.autograd.Function):
             and tuple(Uv1.shape) == (H, 2 * H) and tuple(Uv2.shape) == (H, 2 * H) and tuple(Us1.shape) == (2, H) \
             and tuple(Us2.shape) == (2, H) and tuple(Vv.shape) == (H, 2 * H) and tuple(Vs.shape) == (H, 2), \
             "bigate LSTM operands: Wv [in,4H], Ws [in,4], Uv1, Uv2, Vv [H,2H], Us1, Us2 [2,H], Vs [H,2]"
-        Wv, bv, Ws, bs, Uv1, Us1, Vv, Vs, Uv2, Us2 = (_f32c(t.detach()) for t in (Wv, bv, Ws, bs, Uv1, Us1, Vv, Vs, Uv2, Us2))
-        bv, bs = bv.view(-1), bs.view(-1)
+        Uv1, Us1, Vv, Vs, Uv2, Us2 = (_f32c(t.detach()) for t in (Uv1, Us1, Vv, Vs, Uv2, Us2))
+        bv, bs = bv.reshape(-1), bs.reshape(-1)
         nf = _nf(num_frames)
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        frames1 = split = None
+        # blocks: the (vector, scalar) hoisted blocks -- one pair for both passes, or one pair per pass; win1, win2: each pass' windows
         if not reversed_copies:
-            zv, zs = new(F * B, 4 * H), new(F * B, 4)
-            frames.project(Wv, bv, zv)
-            frames.project(Ws, bs, zs)
+            blocks = [(_Hoisted(frames, Wv, bv), _Hoisted(frames, Ws, bs))]
+            zv, zs = blocks[0][0].z, blocks[0][1].z
             win1, win2 = (zv[:, :2 * H], zs[:, :2]), (zv[:, 2 * H:], zs[:, 2:])
         else:
             if isinstance(frames, U8FrameImages):
                 frames1 = U8FrameImages(reverse_sequence_u8(frames.q, nf), nf)
             else:
                 frames1 = _FloatFrames(_reverse_tm_into(frames.saved, nf, torch.empty_like(frames.saved), 0), bf)
-            split = [(Wv[:, k * 2 * H:(k + 1) * 2 * H].contiguous(),) + _pad4(Ws[:, 2 * k:2 * k + 2], bs[2 * k:2 * k + 2], dev) for k in (0, 1)]
-            wins = []
-            for k, fr in enumerate((frames1, frames)):
-                zvk, zsk = new(F * B, 2 * H), new(F * B, _GATE_U8_LDS)
-                fr.project(split[k][0], bv[k * 2 * H:(k + 1) * 2 * H], zvk)
-                fr.project(split[k][1], split[k][2], zsk)
-                wins.append((zvk, zsk[:, :2]))
-            win1, win2 = wins
+            blocks = [(_Hoisted(fr, Wv[:, k * 2 * H:(k + 1) * 2 * H], bv[k * 2 * H:(k + 1) * 2 * H]),
+                       _Hoisted(fr, Ws[:, 2 * k:2 * k + 2], bs[2 * k:2 * k + 2], pad_to=_GATE_U8_LDS)) for k, fr in enumerate((frames1, frames))]
+            win1, win2 = ((v.z, sc.z[:, :2]) for v, sc in blocks)
         ws = ops._workspace(dev)
         lib = _lib.lib()
 
@@ -621,7 +629,7 @@ class _BigateLstmLayer(torch.autograd.Function):
         BIGATE_LSTM_CALLS["reversed_copies" if reversed_copies else "frame_order"] += 1
         ctx.save_for_backward(frames.saved, y)                       # (y is an output: saved through autograd, not on ctx)
         ctx.frames = frames
-        ctx.state = (bool(reversed_copies), frames1, split, win1, win2, hp1, hp2, cs1, cs2, nf, Wv, Ws, Uv1, Us1, Vv, Vs, Uv2, Us2)
+        ctx.state = (bool(reversed_copies), blocks, win1, win2, hp1, hp2, cs1, cs2, nf, Uv1, Us1, Vv, Vs, Uv2, Us2)
         ctx.bf16 = bf
         ctx.set_materialize_grads(False)
         return y, out2, c1_last, c2_last
@@ -630,20 +638,18 @@ class _BigateLstmLayer(torch.autograd.Function):
     def backward(ctx, dy_in, dout2, dc1_last, dc2_last):
         _, y = ctx.saved_tensors                                     # (the frames' tensor: checked against in-place changes)
         frames = ctx.frames
-        reversed_copies, frames1, split, win1, win2, hp1, hp2, cs1, cs2, nf, Wv, Ws, Uv1, Us1, Vv, Vs, Uv2, Us2 = ctx.state
+        reversed_copies, blocks, win1, win2, hp1, hp2, cs1, cs2, nf, Uv1, Us1, Vv, Vs, Uv2, Us2 = ctx.state
         ctx.state = ctx.frames = None
         F, B, Din, dev = frames.F, frames.B, frames.D, frames.device
         H = Uv1.shape[0]
         bf = ctx.bf16
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        dzb = [(v.dz_buffer(), sc.dz_buffer()) for v, sc in blocks]                            # as `blocks`
         if not reversed_copies:
-            dzv, dzs = new(F * B, 4 * H), new(F * B, 4)                                        # every column is written by a pass
-            dw1, dw2 = (dzv[:, :2 * H], dzs[:, :2]), (dzv[:, 2 * H:], dzs[:, 2:])
+            dzv, dzsc = dzb[0]                                                                 # every column is written by a pass
+            dw1, dw2 = (dzv[:, :2 * H], dzsc[:, :2]), (dzv[:, 2 * H:], dzsc[:, 2:])
         else:
-            # the padding columns are zeroed once: the kernel writes columns 0 and 1 only, the hoisted products read every column
-            dzvs = [new(F * B, 2 * H), new(F * B, 2 * H)]
-            dzss = [torch.zeros((F * B, _GATE_U8_LDS), dtype=torch.float32, device=dev) for _ in (0, 1)]
-            dw1, dw2 = (dzvs[0], dzss[0][:, :2]), (dzvs[1], dzss[1][:, :2])
+            dw1, dw2 = ((dzv, dzsc[:, :2]) for dzv, dzsc in dzb)
         ws = ops._workspace(dev)
         lib = _lib.lib()
         opt = lambda t: None if t is None else _f32c(t)
@@ -665,41 +671,19 @@ class _BigateLstmLayer(torch.autograd.Function):
         else:
             run(win1, Uv1, Us1, cs1, _reverse_tm_into(dy, nf, new(F, B, H), 0), opt(dc1_last), dw1, 0)
         need = ctx.needs_input_grad
-        gWv = gbv = gWs = gbs = gUv1 = gUs1 = gVv = gVs = gUv2 = gUs2 = dx = None
-        colsum = lambda t: ops.colsum(t, new(t.shape[1]))
+        gUv1 = gUs1 = gVv = gVs = gUv2 = gUs2 = dx = None
+        # per block pair: (gWv, gbv), (gWs, gbs) and dx; pass 1's pair on reversed copies saw the reversed frames
+        gv = [v.grads(dzv, need[1], need[2]) for (v, _), (dzv, _) in zip(blocks, dzb)]
+        gs = [sc.grads(dzsc, need[3], need[4]) for (_, sc), (_, dzsc) in zip(blocks, dzb)]
+        dxs = [sc.dx(dzsc, into=v.dx(dzv)) if need[0] else None for (v, sc), (dzv, dzsc) in zip(blocks, dzb)]
         if not reversed_copies:
-            if need[1]:
-                gWv = new(Din, 4 * H)
-                frames.weight_grad(dzv, gWv, 0.0)
-            if need[2]:
-                gbv = colsum(dzv)
-            if need[3]:
-                gWs = new(Din, 4)
-                frames.weight_grad(dzs, gWs, 0.0)
-            if need[4]:
-                gbs = colsum(dzs)
-            if need[0]:
-                dx = frames.dx(dzs, Ws, into=frames.dx(dzv, Wv))
+            (gWv, gbv), (gWs, gbs), dx = gv[0], gs[0], dxs[0]
         else:
-            both = (frames1, frames)
-            if need[1]:
-                parts = [new(Din, 2 * H), new(Din, 2 * H)]
-                for k in (0, 1):
-                    both[k].weight_grad(dzvs[k], parts[k], 0.0)
-                gWv = torch.cat(parts, dim=1)                                                  # (layout glue)
-            if need[2]:
-                gbv = torch.cat([colsum(dzvs[0]), colsum(dzvs[1])])
-            if need[3]:
-                parts = [new(Din, _GATE_U8_LDS), new(Din, _GATE_U8_LDS)]
-                for k in (0, 1):
-                    both[k].weight_grad(dzss[k], parts[k], 0.0)
-                gWs = torch.cat([parts[0][:, :2], parts[1][:, :2]], dim=1)
-            if need[4]:
-                gbs = torch.cat([colsum(dzss[0])[:2], colsum(dzss[1])[:2]])
-            if need[0]:
-                dxs = [both[k].dx(dzss[k], split[k][1], into=both[k].dx(dzvs[k], split[k][0])) for k in (0, 1)]
-                if dxs[1] is not None:
-                    dx = dxs[1].add_(_reverse_tm_into(dxs[0], nf, new(F, B, Din), 0))          # pass 1 saw the reversed frames
+            cat = lambda parts, dim: None if parts[0] is None else torch.cat(parts, dim=dim)     # (layout glue)
+            gWv, gbv = cat([g[0] for g in gv], 1), cat([g[1] for g in gv], 0)
+            gWs, gbs = cat([g[0] for g in gs], 1), cat([g[1] for g in gs], 0)
+            if dxs[1] is not None:
+                dx = dxs[1].add_(_reverse_tm_into(dxs[0], nf, new(F, B, Din), 0))
         # the recurrent and the y weights: products of tensors in one order (frame order; step order for pass 1 on reversed copies)
         dw = lambda A, Bm: ops.gemm_any(A, Bm, transA=True, role="dw", bf16=bf)
         h1, h2, y2 = hp1.view(F * B, H), hp2.view(F * B, H), y.view(F * B, H)
@@ -737,7 +721,7 @@ def bigate_lstm_layer(x_tm, Wv, bv, Ws, bs, Uv1, Us1, Vv, Vs, Uv2, Us2, num_fram
     Returns (y_tm [F,B,H], out2_tm [F,B,H] = pass 2's hidden outputs, c1_last [B,H] = pass 1's memory after STEP num_frames - 1 (:943),
     c2_last [B,H] = pass 2's (:967)), all four differentiable.  Rows with num_frames < 1: c1_last and c2_last are zeros and the row
     receives no gradient through them (as gate_lstm_layer).
-    Device tensors at shapes yt8m_gate_lstm_frames_supported takes run on the step kernels of csrc/bigate_lstm.hip -- in frame order, or
+    Device tensors at shapes yt8m_gate_lstm_frames_supported takes run on the frame-order step kernels of csrc/gate_cell.hip -- in frame order, or
     with YT8M_BIGATE_LSTM_REVERSED=1 over reversed copies; CPU tensors, other dtypes and shapes and YT8M_BIGATE_LSTM_FUSED=0 take
     bigate_lstm_layer_composed, which computes the same function in the reference's form."""
     if bigate_lstm_supported(x_tm, Uv1.shape[0]):
@@ -794,16 +778,10 @@ class _GluLstmLayer(torch.autograd.Function):
         u8 = isinstance(frames, U8FrameImages)
         lds = _GLU_LDS
         Uv, Us = _f32c(Uv.detach()), _f32c(Us.detach())
-        W4 = torch.cat([Wv.detach(), Vv.detach()], dim=1).float().contiguous()
-        b4 = torch.zeros((4 * H,), dtype=torch.float32, device=dev)
-        b4[:2 * H].copy_(bv.detach().view(-1))
-        W8 = torch.cat([Ws.detach(), Vs.detach()], dim=1).float().contiguous()
-        b8 = torch.zeros((lds,), dtype=torch.float32, device=dev)
-        b8[:4].copy_(bs.detach().view(-1))
-        zvp = torch.empty((F * B, 4 * H), dtype=torch.float32, device=dev)
-        zs = torch.empty((F * B, lds), dtype=torch.float32, device=dev)
-        frames.project(W4, b4, zvp)
-        frames.project(W8, b8, zs)
+        pad = torch.nn.functional.pad                                # the V halves (pv, ps) carry no bias
+        v = _Hoisted(frames, torch.cat([Wv.detach(), Vv.detach()], dim=1), pad(bv.detach().reshape(-1), (0, 2 * H)))
+        sc = _Hoisted(frames, torch.cat([Ws.detach(), Vs.detach()], dim=1), pad(bs.detach().reshape(-1), (0, 4)))
+        zvp, zs = v.z, sc.z
         tape = lambda *shape: torch.empty((F + 1,) + shape, dtype=torch.float32, device=dev)
         hs, cs, qv, qs, xm, n2 = tape(B, H), tape(B, H), tape(B, 2 * H), tape(B, 4), tape(B, Din), tape(B)
         for s in (hs, cs, qv, qs, xm, n2):
@@ -818,7 +796,7 @@ class _GluLstmLayer(torch.autograd.Function):
         GLU_LSTM_CALLS["kernels"] += 1
         ctx.save_for_backward(frames.saved)
         ctx.frames = frames
-        ctx.state = (zvp, zs, hs, cs, qv, qs, xm, n2, nf, W4, W8, Uv, Us, xin)
+        ctx.state = (v, sc, hs, cs, qv, qs, xm, n2, nf, Uv, Us, xin)
         ctx.bf16 = bf
         ctx.set_materialize_grads(False)
         return hs[1:], c_last
@@ -827,14 +805,15 @@ class _GluLstmLayer(torch.autograd.Function):
     def backward(ctx, dout, dc_last):
         ctx.saved_tensors                                            # (the frames' tensor: checked against in-place changes)
         frames = ctx.frames
-        zvp, zs, hs, cs, qv, qs, xm, n2, nf, W4, W8, Uv, Us, xin = ctx.state
+        v, sc, hs, cs, qv, qs, xm, n2, nf, Uv, Us, xin = ctx.state
+        zvp, zs = v.z, sc.z
         ctx.state = ctx.frames = None
         F, B, Din, dev = frames.F, frames.B, frames.D, frames.device
         H = Uv.shape[0]
         lds = _GLU_LDS
         need = ctx.needs_input_grad
-        dv4 = torch.empty((F * B, 4 * H), dtype=torch.float32, device=dev)          # dzv | dpv
-        ds8 = torch.empty((F * B, lds), dtype=torch.float32, device=dev)            # dzs | dps: the kernel writes all eight columns
+        dv4 = v.dz_buffer()                                                         # dzv | dpv
+        ds8 = sc.dz_buffer()                                                        # dzs | dps: the kernel writes all eight columns
         dxd = torch.empty((F, B, Din), dtype=torch.float32, device=dev) if (need[0] and xin[0] is not None) else None
         work = torch.empty((B * (8 * H + Din + 8),), dtype=torch.float32, device=dev)
         dout = None if dout is None else _f32c(dout)
@@ -850,31 +829,30 @@ class _GluLstmLayer(torch.autograd.Function):
         # epsilon and x_t = 0.  On bytes the kernel writes those rows as zeros; on float frames they are kept (dx reads them), so the
         # products over dpv / dps keep the fp32-grade form instead of the weight-gradient role's one scale per matrix.
         u8 = xin[0] is None
-        if need[1] or need[5]:
-            gW4 = torch.empty((Din, 4 * H), dtype=torch.float32, device=dev)
-            if u8:
-                frames.weight_grad(dv4, gW4, 0.0)
-            else:
+        if u8:
+            gW4, gW8 = v.grads(dv4, need[1] or need[5], False)[0], sc.grads(ds8, need[3] or need[6], False)[0]
+        else:
+            gW4 = gW8 = None
+            if need[1] or need[5]:
+                gW4 = torch.empty((Din, 4 * H), dtype=torch.float32, device=dev)
                 frames.weight_grad(dv4[:, :2 * H], gW4[:, :2 * H], 0.0)
                 ops.gemm_any(frames.x2, dv4[:, 2 * H:], out=gW4[:, 2 * H:], transA=True, bf16=ctx.bf16)
+            if need[3] or need[6]:
+                gW8 = ops.gemm_any(frames.x2, ds8, out=torch.empty((Din, lds), dtype=torch.float32, device=dev), transA=True, bf16=ctx.bf16)
+        if gW4 is not None:
             gWv, gVv = gW4[:, :2 * H], gW4[:, 2 * H:]
+        if gW8 is not None:
+            gWs, gVs = gW8[:, :4], gW8[:, 4:8]
         if need[2]:
             gbv = ops.colsum(dv4[:, :2 * H], torch.empty((2 * H,), dtype=torch.float32, device=dev))
-        if need[3] or need[6]:
-            gW8 = torch.empty((Din, lds), dtype=torch.float32, device=dev)
-            if u8:
-                frames.weight_grad(ds8, gW8, 0.0)
-            else:
-                ops.gemm_any(frames.x2, ds8, out=gW8, transA=True, bf16=ctx.bf16)
-            gWs, gVs = gW8[:, :4], gW8[:, 4:8]
         if need[4]:
-            gbs = ops.colsum(ds8, torch.empty((lds,), dtype=torch.float32, device=dev))[:4]
+            gbs = sc.grads(ds8, False, True)[1][:4]
         if need[7]:
             gUv = ops.gemm_any(h2, dv4[:, :2 * H], transA=True, role="dw", bf16=ctx.bf16)
         if need[8]:
             gUs = ops.gemm_any(ds8[:, :4], h2, transA=True, role="dw", bf16=ctx.bf16)
         if need[0]:
-            dx = frames.dx(ds8, W8, into=frames.dx(dv4, W4))
+            dx = sc.dx(ds8, into=v.dx(dv4))
             if dx is not None:
                 dx.add_(dxd)
         return dx, gWv, gbv, gWs, gbs, gVv, gVs, gUv, gUs, None
