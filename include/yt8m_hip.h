@@ -1564,6 +1564,52 @@ int yt8m_mix_link_fwd(int mode, const float* prev, const float* z, const float* 
 int yt8m_mix_link_bwd(int mode, const float* z, const float* u, const float* stats, const float* dy, float* dprev, float* dz, int64_t rows,
                       int64_t Wprev, int64_t C, int64_t dx_from, float scale, yt8m_stream_t stream);
 
+/* The label-softmax mixture block of MoeSoftmaxModel (csrc/softmax_moe.hip; Z/video_level_models.py:877-960, the softmax part of
+ * sub_model, :927-957), in one launch each way.  S = vocab_size - softmax_bound + 1 labels, the last of which stands for "none of the
+ * infrequent labels" and is dropped from the result; M mixtures.  Zg [rows, S (M + 1)] (column s (M + 1) + m, no bias) and
+ * Ze [rows, S M] (column s M + m, bias added) are the two products' outputs.
+ *   fwd, per row: g[s, :] = softmax over the M + 1 gates; e[:, m] = softmax over the S LABELS; p[s] = sum_{m < M} g[s, m] e[s, m];
+ *     T = sum_s p[s]; out [rows, V1 + S - 1] = [head (V1 columns, copied; NULL exactly when V1 = 0) | p[0 .. S - 2] / T]: the whole
+ *     prediction row.  stats [rows, 2 M + 1]: the M column maxima of Ze, the M column sums of exp(Ze - max), T.
+ *   bwd, per row: dq[s] = dout[row * ldd + c0 + s] for s < S - 1 (dout is read in place: ldd its row pitch, c0 the column where the
+ *     softmax part starts, V1 in a whole prediction row), dq of the dropped label = 0.  D = sum dq q, A_m = sum e g dq, C_m = sum e g,
+ *     dp_s = (dq_s - D) / T;  dZe[s, m] = e (g dp_s - (A_m - D C_m) / T);  dZg[s, m] = g dp_s (e [m < M] - p_s), m <= M.  dZg / dZe may be
+ *     Zg / Ze themselves (as yt8m_moe_mix_bwd writes over its logits).  The head's gradient is dout's leading columns: no kernel.
+ * One workgroup per row, thread t owns labels t, t + 256, ...; single-element accesses (S (M + 1) is odd at the workload, 1717 * 5: rows
+ * are not 16-byte aligned).  A thread's labels stay in registers between the reductions and the write for S <= 256 * (36 / (M + 1))
+ * (integer division; M = 4: S <= 1792, S M <= 7168; yt8m_softmax_moe_resident says so per (S, M)); above it each pass reads the logits
+ * again, from L2, and recomputes the same expressions.  Fixed summation order, no atomics: reruns are bit-equal.
+ * yt8m_softmax_moe_supported: 2 <= S <= 65536 and 1 <= M <= 8; no device is touched.  Unsupported shapes, rows < 1 and V1 outside
+ * [0, 2^24]: YT8M_E_SHAPE; a null required operand, a head that does not go with V1, c0 < 0 or ldd < c0 + S - 1: YT8M_E_BADARG.  Nothing
+ * is launched then. */
+int yt8m_softmax_moe_supported(int64_t S, int64_t M);
+int yt8m_softmax_moe_resident(int64_t S, int64_t M);
+int yt8m_softmax_moe_fwd(const float* Zg, const float* Ze, const float* head, float* out, float* stats, int64_t rows, int64_t S, int64_t M,
+                         int64_t V1, yt8m_stream_t stream);
+int yt8m_softmax_moe_bwd(const float* Zg, const float* Ze, const float* stats, const float* dout, int64_t ldd, int64_t c0, float* dZg,
+                         float* dZe, int64_t rows, int64_t S, int64_t M, yt8m_stream_t stream);
+/* SplitSoftmaxLoss, Z's SoftmaxLoss (csrc/softmax_moe.hip; Z/losses.py:412-456): with V1 = bound, p[b, v] read in place at
+ * p[b * ldp + c0 + v] and labels [B, V] contiguous, uint8 {0,1} or float32,
+ *   loss = mean_b ( sum_{v < V1} -(y log(p + eps_ce) + (1 - y) log(1 - p + eps_ce))
+ *                   - sum_{v >= V1} (n log(p + eps_sm) + (1 - n) log(1 - p + eps_sm)) - (a log(o + eps_sm) + (1 - a) log(1 - o + eps_sm)) ),
+ *   n = y / max(sum_{v >= V1} y, eps_sm), a = 1 - max_{v >= V1} y, o = max(1 - sum_{v >= V1} p, 0); the reference's eps_ce = 10e-6 and
+ *   eps_sm = 10e-8.  ONE deliberate difference from the reference: o is clamped at 0 (the reference takes 1 - sum as it falls, which in
+ *   float32 reaches -1.19e-7 < -eps_sm for MoeSoftmaxModel's own output whenever the dropped label holds little mass, and log gives
+ *   NaN); its gradient is taken as if unclamped, d o / d p = -1.
+ * fwd_bwd: loss_out device float[1]; dp [B, V] contiguous may be NULL; dp = dloss/dp * upstream; workspace >=
+ * yt8m_split_softmax_loss_workspace_bytes(B).  bwd: dp = dloss/dp * upstream * (upstream_dev ? *upstream_dev : 1), as yt8m_xent_bwd.
+ * One workgroup per row: the value in one pass over the row (seven sums reduced once), the gradient after the row's scalars in a
+ * second read; the rows' partials are summed in fp64 in a fixed order.  No atomics, no host synchronisation.
+ * B < 1, V < 2 or bound outside (0, V): YT8M_E_SHAPE; a null required operand, a label dtype, c0 < 0, ldp < c0 + V or an eps <= 0:
+ * YT8M_E_BADARG.  Nothing is launched then. */
+int64_t yt8m_split_softmax_loss_workspace_bytes(int64_t B);
+int yt8m_split_softmax_loss_fwd_bwd(const float* p, int64_t ldp, int64_t c0, const void* labels, int label_dtype, float* loss_out, float* dp,
+                                    int64_t B, int64_t V, int64_t bound, float eps_ce, float eps_sm, float upstream, void* workspace,
+                                    yt8m_stream_t stream);
+int yt8m_split_softmax_loss_bwd(const float* p, int64_t ldp, int64_t c0, const void* labels, int label_dtype, const float* upstream_dev,
+                                float* dp, int64_t B, int64_t V, int64_t bound, float eps_ce, float eps_sm, float upstream,
+                                yt8m_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -379,6 +379,13 @@ SIGNATURES = {
     "yt8m_mix_link_supported": (c_int, [c_int64, c_int64]),
     "yt8m_mix_link_fwd": (c_int, [c_int, P, P, P, P, P, c_int64, c_int64, c_int64, c_float, c_float, P]),
     "yt8m_mix_link_bwd": (c_int, [c_int, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P]),
+    "yt8m_softmax_moe_supported": (c_int, [c_int64, c_int64]),
+    "yt8m_softmax_moe_resident": (c_int, [c_int64, c_int64]),
+    "yt8m_softmax_moe_fwd": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, P]),
+    "yt8m_softmax_moe_bwd": (c_int, [P, P, P, P, c_int64, c_int64, P, P, c_int64, c_int64, c_int64, P]),
+    "yt8m_split_softmax_loss_workspace_bytes": (c_int64, [c_int64]),
+    "yt8m_split_softmax_loss_fwd_bwd": (c_int, [P, c_int64, c_int64, P, c_int, P, P, c_int64, c_int64, c_int64, c_float, c_float, c_float, P, P]),
+    "yt8m_split_softmax_loss_bwd": (c_int, [P, c_int64, c_int64, P, c_int, P, P, c_int64, c_int64, c_int64, c_float, c_float, c_float, P]),
 }
 
 # The ABI this host binds (include/yt8m_hip.h, yt8m_abi_version): workspace layouts and argument meanings, not just symbols.

@@ -1249,8 +1249,10 @@ class GatedNetVLADAttentionChainModel(GatedNetVLADModel):
 #   MoeDistillSplit2Model, MoeDistillSplit3Model, MoeDistillSplit4Model (Z/video_level_models.py:584 on): not in the list either;
 #   CnnDCCDistillChainModel (entry 51, :6249): the plugin itself is not built, though the rule it is trained by, Z's calculate_loss_mix
 #   on its predictions_class, now exists (train.TrainGraph._mix_loss);
-#   MoeSoftmaxModel (entry 29.4, Z/video_level_models.py): needs Z's SoftmaxLoss and a softmax-over-labels expert kernel, the step after
-#   the combine chain heads; MoeMix4Model's --moe_group=True path (label groups of --class_size): no script of the list sets it;
+#   MoeSoftmaxModel (entry 29.4) is built in video_level_models.py with its loss, losses.SplitSoftmaxLoss; of it, not built: `channels` other
+#   than the reference's constant 1 (Z/video_level_models.py:920), and W's SoftmaxLoss / MultiTaskCrossEntropyAndSoftmaxLoss, a different
+#   function (tf.nn.softmax of the predictions) under the name Z uses;
+#   MoeMix4Model's --moe_group=True path (label groups of --class_size): no script of the list sets it;
 #   Z's --distillation_type 1-3 losses: the cascade scripts say --distillation_type=0, the plain label loss;
 #   LstmRandomModel: LstmMemoryModel as committed -- its frame selection sits behind FLAGS.train=="train", and --train is a bool flag (:54, :4037);
 #   LstmBiglu2Model: LstmBigluModel's pair of passes on LstmGlu2Model's input-memory cell (:1160), and not in the final submission's list;

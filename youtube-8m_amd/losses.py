@@ -1,14 +1,17 @@
 """Label losses; names, flags and semantics mirror W/losses.py (W = /root/reference/youtube-8m-wangheda).
 
 Here: CrossEntropyLoss, WeightedCrossEntropyLoss, MeanSquareErrorLoss, HingeLoss, MultiTaskCrossEntropyLoss,
-BatchAgreementCrossEntropyLoss and TopKBatchAgreementCrossEntropyLoss.  Every one runs as HIP kernels (csrc/elementwise.hip for the
-plain cross entropy, csrc/losses.hip for the others), forward and backward.
+BatchAgreementCrossEntropyLoss and TopKBatchAgreementCrossEntropyLoss, and SplitSoftmaxLoss from Z/losses.py.  Every one runs as HIP
+kernels (csrc/elementwise.hip for the plain cross entropy, csrc/softmax_moe.hip for SplitSoftmaxLoss, csrc/losses.hip for the others),
+forward and backward.
 
 Left out of W/losses.py:
   PairwiseHingeLoss, MixedLoss                                  they unstack the batch by --batch_size and draw TF random integers
                                                                 (tf.random_uniform, dtype int32), for which this repository has no
                                                                 parity definition.
-  SoftmaxLoss, MultiTaskCrossEntropyAndSoftmaxLoss              a row-softmax loss is a kernel of its own: the next step.
+  SoftmaxLoss, MultiTaskCrossEntropyAndSoftmaxLoss              W's classes of these names put tf.nn.softmax over the PREDICTIONS and
+                                                                no script of either submission uses them.  Z's SoftmaxLoss is a
+                                                                different function under the same name: SplitSoftmaxLoss below.
   MultiTaskDivergenceCrossEntropyLoss,                          they take [batch, models, classes] support predictions from plugins
   MultiTaskDivergenceCrossEntropyAndMSELoss                     this repository does not have.
 --label_loss with one of these names ends in StopIteration at train.find_class_by_name, as any unknown name does.
@@ -17,7 +20,9 @@ From Z/losses.py (Z = youtube-8m-zhangteng): calculate_loss_mix's default branch
 calculate_loss(predictions_class, the labels tiled) -- is a training rule, not a loss class: train.TrainGraph._mix_loss.  Left out of it:
   its --support_type branches "class", "frequent", "encoder"    --support_type is W's flag here and has W's meaning; no model of the
                                                                 final submission's list sets Z's.
-  calculate_loss_mix2                                           it reads "predictions_encoder" and autoencoder files no plugin here has."""
+  calculate_loss_mix2                                           it reads "predictions_encoder" and autoencoder files no plugin here has.
+Z's SoftmaxLoss (Z/losses.py:412-456), the loss written for MoeSoftmaxModel, is here under the name SplitSoftmaxLoss (the name
+SoftmaxLoss stays W's, above): --label_loss=SplitSoftmaxLoss; csrc/softmax_moe.hip."""
 import torch
 
 from . import ops
@@ -139,6 +144,35 @@ class TopKBatchAgreementCrossEntropyLoss(BaseLoss):
 
     def calculate_loss(self, predictions, labels, topk=20, **unused_params):
         return ops.topk_batch_agreement_cross_entropy(predictions, labels, FLAGS.batch_agreement)
+
+
+class SplitSoftmaxLoss(BaseLoss):
+    """Z/losses.py:412-456, Z's SoftmaxLoss: cross entropy on the first --softmax_bound labels; the others' labels are divided by their
+    row sum (at least 10e-8) with 1 - max appended, their predictions get 1 - sum appended, and the two-sided log loss with eps = 10e-8
+    is summed over the row; the mean over the batch of both.  ops.split_softmax_loss (csrc/softmax_moe.hip).
+    One deliberate difference from the reference: the appended probability is max(1 - sum, 0), its gradient taken as if unclamped.  In
+    exact arithmetic it is MoeSoftmaxModel's dropped column q >= 0; in float32 the model's own output gives 1 - sum = -1.19e-7 < -10e-8
+    whenever the dropped column holds little mass, and the reference's log returns NaN (as with MoeDistillChainNormModel's 0 / 0 rule,
+    video_level_models.py).
+    Z defines no `weights`: one that is not None raises ValueError.  Label smoothing does not apply (the labels are renormalised)."""
+
+    def calculate_loss(self, predictions, labels, weights=None, scale=1.0, **unused_params):
+        from . import video_level_models  # noqa: F401  (defines --softmax_bound and --moe_layers)
+        if weights is not None:
+            raise ValueError("SplitSoftmaxLoss takes no per-example weights (Z/losses.py:424 defines none)")
+        return ops.split_softmax_loss(predictions, labels, int(FLAGS.softmax_bound), scale)
+
+    def calculate_loss_mix(self, predictions, predictions_class, labels, weights=None, **unused_params):
+        """Z/losses.py:448-456: calculate_loss(predictions) + 0.1 * sum_{i < --moe_layers} calculate_loss(predictions_class[:, i V:(i + 1) V]):
+        the bound splits every V-wide piece, which is read in place."""
+        from . import video_level_models  # noqa: F401
+        V, layers = labels.shape[1], int(FLAGS.moe_layers)
+        if predictions_class.shape[1] < layers * V:
+            raise ValueError("predictions_class is %d wide for --moe_layers=%d pieces of %d labels" % (predictions_class.shape[1], layers, V))
+        loss = self.calculate_loss(predictions, labels, weights=weights)
+        for i in range(layers):
+            loss = loss + self.calculate_loss(predictions_class[:, i * V:(i + 1) * V], labels, weights=weights, scale=0.1)
+        return loss
 
 
 class MultiTaskLoss(BaseLoss):

@@ -2,8 +2,8 @@
 
 torch is used for device memory, streams and the autograd tape only; every FLOP of the hot path is a
 HIP kernel in libyt8m_hip.so.  No op has a CPU / eager fallback: host tensors raise.  (Documented exceptions: ens_combine /
-ens_moments of the ensemble stage, scale_mix, distill_input and distill_blend have a composed form that inputs outside the kernels'
-layout take by rule, not by failure; linear_group multiplies CPU tensors with torch, for the host tests.)
+ens_moments of the ensemble stage, scale_mix, distill_input, distill_blend, softmax_moe and split_softmax_loss have a composed form that
+inputs outside the kernels' layout take by rule, not by failure; linear_group multiplies CPU tensors with torch, for the host tests.)
 
 Gradient routing: parameters are NOT autograd leaves.  Each op's backward writes dW directly into the
 variable's slice of the gradient arena (GEMM beta = 0 on first write, 1 afterwards) and returns None for
@@ -1659,6 +1659,154 @@ def mix_link(prev, p, W1, b1, W2, b2, q=None, norm=True, scale=1.0, dx_from=0, e
         z, u = torch.cat([linear(p, W1), linear(q, W2)], dim=1), torch.cat([as_tensor(b1), as_tensor(b2)])
     bits = (0 if q is None else MIX_LINK_PLAIN) | (0 if norm else MIX_LINK_NONE)
     return _MixLink.apply(prev, z, u, bits, scale, dx_from, eps)
+
+
+# YT8M_SOFTMAX_MOE_FUSED, 0: softmax_moe composes torch ops in the reference's order; anything else: the kernels of csrc/softmax_moe.hip.
+# YT8M_SPLIT_SOFTMAX_LOSS_FUSED: the same for split_softmax_loss.  Each default follows the project's rule on its own -- the kernels only
+# where tools/softmax_moe_step.py measured their median below the composed form's at every shape in both runs.  Both did: the block
+# 1.4 - 4.1 x at its four shapes, the loss 3.4 - 5.6 x at its two (DESIGN_LOG.md section 42), so both defaults are 1.
+SOFTMAX_MOE_FUSED = os.environ.get("YT8M_SOFTMAX_MOE_FUSED", "1") != "0"
+SPLIT_SOFTMAX_LOSS_FUSED = os.environ.get("YT8M_SPLIT_SOFTMAX_LOSS_FUSED", "1") != "0"
+SOFTMAX_MOE_CALLS = {"kernels": 0, "composed": 0}                # which form ran (tests)
+SPLIT_SOFTMAX_LOSS_CALLS = {"kernels": 0, "composed": 0}
+SOFTMAX_LOSS_EPS = 10e-8  # Z/losses.py:428
+
+
+def softmax_moe_composed(Zg, Ze, S, M, head=None):
+    """softmax_moe as the reference writes it (Z/video_level_models.py:941-957): two softmaxes -- over the M + 1 gates and, per mixture,
+    over the S labels --, the product's sum over the mixtures, the division by the row sum, the last label dropped and torch.cat."""
+    rows = Zg.shape[0]
+    g = torch.softmax(Zg.reshape(rows, S, M + 1), dim=2)
+    e = torch.softmax(Ze.reshape(rows, S, M), dim=1)
+    p = (g[:, :, :M] * e).sum(dim=2)
+    q = (p / p.sum(dim=1, keepdim=True))[:, :-1]
+    return q if head is None else torch.cat([head, q], dim=1)
+
+
+class _SoftmaxMoe(torch.autograd.Function):
+    """csrc/softmax_moe.hip: the whole prediction row [head | q] from the two logit matrices in one launch each way.  Saved for backward:
+    Zg, Ze and stats [rows, 2 M + 1].  overwrite: the backward pass writes dZg / dZe over the logits (the model's own, which nothing else
+    reads); otherwise into fresh tensors."""
+
+    @staticmethod
+    def forward(ctx, Zg, Ze, head, S, M, overwrite):
+        Zg, Ze = _f32c(Zg), _f32c(Ze)
+        head = None if head is None else _f32c(head)
+        _dev(Zg, Ze, head)
+        rows = Zg.shape[0]
+        V1 = 0 if head is None else head.shape[1]
+        out = torch.empty((rows, V1 + S - 1), dtype=torch.float32, device=Zg.device)
+        stats = torch.empty((rows, 2 * M + 1), dtype=torch.float32, device=Zg.device)
+        _lib.check(_lib.lib().yt8m_softmax_moe_fwd(_p(Zg), _p(Ze), _p(head), _p(out), _p(stats), rows, S, M, V1, _stream()))
+        ctx.S, ctx.M, ctx.V1, ctx.overwrite = S, M, V1, bool(overwrite)
+        ctx.save_for_backward(Zg, Ze, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        Zg, Ze, stats = ctx.saved_tensors
+        dout, ldd = _rowmajor2d(dout)
+        dZg, dZe = (Zg, Ze) if ctx.overwrite else (torch.empty_like(Zg), torch.empty_like(Ze))
+        _lib.check(_lib.lib().yt8m_softmax_moe_bwd(_p(Zg), _p(Ze), _p(stats), _p(dout), ldd, ctx.V1, _p(dZg), _p(dZe), Zg.shape[0], ctx.S,
+                                                   ctx.M, _stream()))
+        dhead = dout[:, :ctx.V1] if (ctx.V1 and ctx.needs_input_grad[2]) else None       # the head's gradient: dout's leading columns
+        return dZg, dZe, dhead, None, None, None
+
+
+def softmax_moe(Zg, Ze, S, M, head=None, overwrite_logits=False):
+    """[rows, V1 + S - 1] = [head | q[:, :S - 1]]: the label-softmax mixture block of MoeSoftmaxModel (Z/video_level_models.py:927-959)
+    from its gate logits Zg [rows, S (M + 1)] (column s (M + 1) + m), its expert logits Ze [rows, S M] (column s M + m) and, where
+    given, the sigmoid part head [rows, V1]:  g = softmax over the M + 1 gates, e = softmax over the S LABELS per mixture,
+    p = sum_{m < M} g e, q = p / sum_s p; the last label ("none of the infrequent labels") is dropped.  Differentiable in all three.
+    overwrite_logits: the fused backward may write the gradients over Zg and Ze (for logits nothing else reads).
+    YT8M_SOFTMAX_MOE_FUSED (read at import): 0 is the composed form (softmax_moe_composed), anything else the kernel pair; CPU tensors,
+    non-float32 tensors and shapes yt8m_softmax_moe_supported refuses (S < 2, S > 65536, M > 8) always take the composed form."""
+    S, M = int(S), int(M)
+    if Zg.dim() != 2 or Ze.dim() != 2 or S < 2 or M < 1 or tuple(Zg.shape) != (Ze.shape[0], S * (M + 1)) or Ze.shape[1] != S * M \
+            or (head is not None and (head.dim() != 2 or head.shape[0] != Zg.shape[0])):
+        raise ValueError("softmax_moe: Zg [rows, S (M + 1)], Ze [rows, S M], head [rows, V1] or None with S >= 2 and M >= 1, got %s, %s, %s, "
+                         "S = %d, M = %d" % (tuple(Zg.shape), tuple(Ze.shape), None if head is None else tuple(head.shape), S, M))
+    if head is not None and head.shape[1] == 0:
+        head = None
+    ts = (Zg, Ze) + (() if head is None else (head,))
+    fused = (SOFTMAX_MOE_FUSED and Zg.shape[0] > 0 and all(t.is_cuda and t.dtype == torch.float32 for t in ts)
+             and bool(_lib.lib().yt8m_softmax_moe_supported(S, M)))
+    SOFTMAX_MOE_CALLS["kernels" if fused else "composed"] += 1
+    if not fused:
+        return softmax_moe_composed(Zg, Ze, S, M, head)
+    return _SoftmaxMoe.apply(Zg, Ze, head, S, M, bool(overwrite_logits))
+
+
+def split_softmax_loss_composed(p, labels, bound, scale=1.0):
+    """split_softmax_loss as the reference writes it (Z/losses.py:424-446), in torch: cross entropy on the first `bound` columns; on the
+    others the labels divided by their row sum with 1 - max appended, the predictions with max(1 - sum, 0) appended (the clamp is this
+    repository's; its gradient is taken as if unclamped), and the two-sided log loss with eps = 10e-8."""
+    y = labels.to(p.dtype)
+    y1, p1, y2, p2 = y[:, :bound], p[:, :bound], y[:, bound:], p[:, bound:]
+    cross_entropy_loss = -(y1 * torch.log(p1 + XENT_EPS) + (1 - y1) * torch.log(1 - p1 + XENT_EPS)).sum(dim=1).mean()
+    label_rowsum = torch.clamp(y2.sum(dim=1, keepdim=True), min=SOFTMAX_LOSS_EPS)
+    norm_float_labels = torch.cat((y2 / label_rowsum, 1.0 - y2.max(dim=1, keepdim=True)[0]), dim=1)
+    predictions_append = 1.0 - p2.sum(dim=1, keepdim=True)
+    predictions_append = predictions_append + (torch.clamp(predictions_append, min=0.0) - predictions_append).detach()
+    softmax_outputs = torch.cat((p2, predictions_append), dim=1)
+    softmax_loss = -(norm_float_labels * torch.log(softmax_outputs + SOFTMAX_LOSS_EPS)
+                     + (1 - norm_float_labels) * torch.log(1 - softmax_outputs + SOFTMAX_LOSS_EPS)).sum(dim=1)
+    loss = softmax_loss.mean() + cross_entropy_loss
+    return loss * scale if scale != 1.0 else loss
+
+
+def _split_softmax_loss_args(p, labels):
+    p, ldp = _rowmajor2d(p)
+    lab, ldt = _labels_arg(labels)
+    return p, ldp, lab, ldt
+
+
+class _SplitSoftmaxLoss(torch.autograd.Function):
+    """csrc/softmax_moe.hip: p is read in place through its row pitch (a piece of predictions_class goes in without a copy); backward
+    recomputes dL/dp from (p, y) with the upstream scalar read on the device, as _Xent."""
+
+    @staticmethod
+    def forward(ctx, p, labels, bound, scale):
+        _dev(p, labels)
+        pp, ldp, lab, ldt = _split_softmax_loss_args(p, labels)
+        B, V = pp.shape
+        L = _lib.lib()
+        ws = _loss_workspace(L.yt8m_split_softmax_loss_workspace_bytes(B), pp.device)
+        loss = torch.empty((), dtype=torch.float32, device=pp.device)
+        _lib.check(L.yt8m_split_softmax_loss_fwd_bwd(_p(pp), ldp, 0, _p(lab), ldt, _p(loss), None, B, V, bound, XENT_EPS, SOFTMAX_LOSS_EPS, 1.0,
+                                                     _p(ws), _stream()))
+        ctx.save_for_backward(p)
+        ctx.labels, ctx.bound, ctx.scale = labels, bound, scale
+        return loss * scale if scale != 1.0 else loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (p,) = ctx.saved_tensors
+        pp, ldp, lab, ldt = _split_softmax_loss_args(p, ctx.labels)
+        B, V = pp.shape
+        dp = torch.empty((B, V), dtype=torch.float32, device=pp.device)
+        _lib.check(_lib.lib().yt8m_split_softmax_loss_bwd(_p(pp), ldp, 0, _p(lab), ldt, _p(_f32c(dloss.reshape(1))), _p(dp), B, V, ctx.bound,
+                                                          XENT_EPS, SOFTMAX_LOSS_EPS, ctx.scale, _stream()))
+        return dp, None, None, None
+
+
+def split_softmax_loss(p, labels, bound, scale=1.0):
+    """Z's SoftmaxLoss (Z/losses.py:412-446; losses.SplitSoftmaxLoss) times `scale`: cross entropy (eps 10e-6) on the columns [0, bound)
+    of p [B, V] plus, on the others, -sum (n log(o + 10e-8) + (1 - n) log(1 - o + 10e-8)) with n = [y2 / max(sum y2, 10e-8) | 1 - max y2]
+    and o = [p2 | max(1 - sum p2, 0)], mean over the batch.  The clamp is this repository's (the reference's 1 - sum falls below -10e-8 in
+    float32 and gives NaN); its gradient is taken as if unclamped.  p may be a column window of a wider tensor.
+    YT8M_SPLIT_SOFTMAX_LOSS_FUSED (read at import): 0 is the composed form (split_softmax_loss_composed), anything else the kernel; CPU
+    tensors, non-float32 predictions and labels that are not bool / uint8 / float32 always take the composed form."""
+    bound = int(bound)
+    if p.dim() != 2 or tuple(labels.shape) != tuple(p.shape) or not 0 < bound < p.shape[1]:
+        raise ValueError("split_softmax_loss: p and labels [B, V] and 0 < bound < V, got %s, %s, bound = %d"
+                         % (tuple(p.shape), tuple(labels.shape), bound))
+    fused = (SPLIT_SOFTMAX_LOSS_FUSED and p.shape[0] > 0 and p.is_cuda and labels.is_cuda and p.dtype == torch.float32
+             and labels.dtype in (torch.bool, torch.uint8, torch.float32))
+    SPLIT_SOFTMAX_LOSS_CALLS["kernels" if fused else "composed"] += 1
+    if not fused:
+        return split_softmax_loss_composed(p, labels, bound, scale)
+    return _SplitSoftmaxLoss.apply(p, labels, bound, float(scale))
 
 
 class _MatConst(torch.autograd.Function):

@@ -181,13 +181,18 @@ class TrainGraph(object):
         calculate_loss_mix, its default branch): calculate_loss(predictions, labels) + 0.1 * calculate_loss(predictions_class, labels
         tiled L times along the columns) -- with --label_loss=CrossEntropyLoss one sum over all L V columns and a mean over the batch.
         Left out: Z's --support_type branches of this loss ("class", "frequent", "encoder" -- --support_type is W's flag here and has
-        W's meaning) and calculate_loss_mix2 (results with "predictions_encoder"); no model of the final submission's list takes them."""
+        W's meaning) and calculate_loss_mix2 (results with "predictions_encoder"); no model of the final submission's list takes them.
+        A --label_loss class that has a calculate_loss_mix of its own (SplitSoftmaxLoss, whose bound splits every V-wide piece:
+        Z/losses.py:448-456) is handed the three tensors instead; every other loss takes the path above."""
         if self.multitask:
             raise ValueError("--multitask takes its loss from predictions and support_predictions; a model that returns "
                              "predictions_class is trained by Z's mix loss (Z/losses.py:280-313) and has no such combination")
         V, width = labels.shape[1], predictions_class.shape[1]
         if V == 0 or width == 0 or width % V != 0:
             raise ValueError("predictions_class is %d wide for %d labels: not a whole multiple" % (width, V))
+        mix = getattr(self.label_loss_fn, "calculate_loss_mix", None)
+        if mix is not None:                                       # a loss written for the pieces (losses.SplitSoftmaxLoss)
+            return mix(predictions, predictions_class, labels, weights=weights)
         L = width // V
         labels_class = labels if L == 1 else labels.repeat(1, L)
         return self.label_loss_fn.calculate_loss(predictions, labels, weights=weights) + \

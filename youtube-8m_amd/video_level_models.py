@@ -316,7 +316,8 @@ def _class_matrix(device):
     return seq
 
 
-def mix_chain_head(model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, knowledge=False, normalize=True, support_pool=None):
+def mix_chain_head(model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, knowledge=False, normalize=True, support_pool=None,
+                   block=None, first_name=""):
     """The body of the two heads below.  An MoE block under "gates" / "experts" gives p; for i < --moe_layers, ops.mix_link under
     "class_inputs1-<i>" and "class_inputs2-<i>" (--class_size wide each: c1 = elu(FC(p)), c2 = elu(FC(1 - p)), or elu(FC(p . seq)) with
     `knowledge`; with `normalize` each l2-normalised and multiplied by sqrt(class_size / D), D the width of the head's own input) grows
@@ -325,7 +326,9 @@ def mix_chain_head(model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, 
     (support_pool, where given, applied to each piece and to the predictions first, as DeepCombineChainModel's).  Variables in the
     reference's order: gates, experts, then per stage class_inputs1-i, class_inputs2-i, gates-i, experts-i; xavier weights under
     l2_penalty, zero biases, no bias on the gates.  model_input is data in video-level use (no head computes a gradient for its
-    columns) and an attention-pooled LSTM output in frame-level use."""
+    columns) and an attention-pooled LSTM output in frame-level use.
+    block(stage_input, name, frozen_cols) -> [B, vocab_size], where given, stands for the MoE block and makes its own Variables under
+    scopes that end in `name`: first_name for the first prediction, "-<i>" for stage i (MoeSoftmaxModel: "pre", then "-0", "-1", ...)."""
     g = get_default_graph()
     M = num_mixtures or FLAGS.moe_num_mixtures
     C, layers = int(FLAGS.class_size), int(FLAGS.moe_layers)
@@ -336,8 +339,10 @@ def mix_chain_head(model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, 
     if seq is not None and seq.shape[0] != vocab_size:
         raise ValueError("--class_file=%s holds %d rows for %d labels" % (FLAGS.class_file, seq.shape[0], vocab_size))
     pool = support_pool or (lambda t: t)
+    if block is None:
+        block = lambda x, name, frozen_cols: moe_block(x, vocab_size, M, l2_penalty, "gates" + name, "experts" + name, frozen_cols=frozen_cols)
     stage_input = model_input
-    p = moe_block(stage_input, vocab_size, M, l2_penalty, "gates", "experts", frozen_cols=frozen)
+    p = block(stage_input, first_name, frozen)
     pieces = []
     for i in range(layers):
         pieces.append(pool(p))
@@ -347,7 +352,7 @@ def mix_chain_head(model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, 
         W2 = g.get_variable("class_inputs2-%d/weights" % i, (vocab_size if q is None else q.shape[1], C), xavier_uniform, l2=l2_penalty)
         b2 = g.get_variable("class_inputs2-%d/biases" % i, (C,), zeros)
         stage_input = ops.mix_link(stage_input, p, W1, b1, W2, b2, q=q, norm=normalize, scale=scale, dx_from=frozen)
-        p = moe_block(stage_input, vocab_size, M, l2_penalty, "gates-%d" % i, "experts-%d" % i, frozen_cols=frozen)
+        p = block(stage_input, "-%d" % i, frozen)
     res = {"predictions": pool(p)}
     if pieces:
         res["predictions_class"] = pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=1)
@@ -376,5 +381,39 @@ class MoeKnowledgeModel(models.BaseModel):
 
     def create_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, original_input=None, **unused_params):
         res = mix_chain_head(model_input, vocab_size, num_mixtures, l2_penalty, knowledge=True)
+        res.setdefault("predictions_class", res["predictions"])
+        return res
+
+
+def softmax_moe_block(model_input, vocab_size, bound, num_mixtures, l2_penalty, name, frozen_cols=0):
+    """MoeSoftmaxModel.sub_model (Z/video_level_models.py:879-960) under scopes that end in `name`: the MoE block for the first `bound`
+    labels ("gates<name>", "experts<name>") and the label-softmax mixture for the other V - bound and one more that stands for none of
+    them ("class_gates-0<name>", no bias; "class_experts-0<name>"): two products through ops.linear -- S (M + 1) is odd at the workload, so
+    neither takes an N % 4 form -- and ops.softmax_moe, which writes the whole row [sigmoid part | q[:, :S - 1]].  The reference's
+    `channels` is the constant 1; its loop is not generalised."""
+    g = get_default_graph()
+    d_in, M = model_input.shape[-1], num_mixtures
+    S = vocab_size - bound + 1
+    head = moe_block(model_input, bound, M, l2_penalty, "gates" + name, "experts" + name, frozen_cols=frozen_cols)
+    Wg = g.get_variable("class_gates-0%s/weights" % name, (d_in, S * (M + 1)), xavier_uniform, l2=l2_penalty)
+    We = g.get_variable("class_experts-0%s/weights" % name, (d_in, S * M), xavier_uniform, l2=l2_penalty)
+    be = g.get_variable("class_experts-0%s/biases" % name, (S * M,), zeros)
+    x = model_input.reshape(-1, d_in)
+    return ops.softmax_moe(ops.linear(x, Wg), ops.linear(x, We, be), S, M, head=head, overwrite_logits=True)
+
+
+class MoeSoftmaxModel(models.BaseModel):
+    """Z/video_level_models.py:877-1017: the sigmoid MoE block predicts the first --softmax_bound labels and a mixture whose experts are
+    a softmax over the labels predicts the others; the blocks are chained as MoeMix4Model's (mix_chain_head: "pre", then "-<i>" behind
+    class_inputs1-<i> / class_inputs2-<i>, always normalised -- the reference has no --frame_features branch here).  The result holds
+    "predictions_class", so train.TrainGraph trains it by the mix rule: under --label_loss=CrossEntropyLoss, the reference's script as
+    committed, by TrainGraph._mix_loss; under SplitSoftmaxLoss by that class's calculate_loss_mix.  With --moe_layers=0 the one
+    prediction is under both keys.  0 < --softmax_bound < vocab_size is asserted."""
+
+    def create_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, original_input=None, **unused_params):
+        M, bound = num_mixtures or FLAGS.moe_num_mixtures, int(FLAGS.softmax_bound)
+        assert 0 < bound < vocab_size, "MoeSoftmaxModel wants 0 < --softmax_bound = %d < %d labels" % (bound, vocab_size)
+        block = lambda x, name, frozen_cols: softmax_moe_block(x, vocab_size, bound, M, l2_penalty, name, frozen_cols)
+        res = mix_chain_head(model_input, vocab_size, num_mixtures, l2_penalty, block=block, first_name="pre")
         res.setdefault("predictions_class", res["predictions"])
         return res
