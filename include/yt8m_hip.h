@@ -1429,6 +1429,32 @@ int yt8m_ens_combine_bwd(const float* x, const float* Wt, const float* gate, int
                          int64_t M, int J, yt8m_stream_t stream);
 int yt8m_ens_moments(const float* x, float* mean, float* var, int64_t B, int64_t V, int64_t M, yt8m_stream_t stream);
 
+/* ---- the ensemble stage's per-class matrix mix and per-video mix (csrc/ensemble_tensor.hip; E/all_ensemble_models/moe_model.py:51-54,
+ * input_moe_model.py:33, attention_moe_model.py:41) ---------------------------------------------------------------------------------
+ * x [M, B, V] method-major as above, data.  tensor: Wt [M, M, V] = W[v,k,l] at (k M + l) V + v (the INPUT method k outermost, v innermost),
+ * bt [M, V] = b[v,l] at l V + v.
+ *   g[b,v,l] = sum_k x[k,b,v] Wt[k,l,v] + bt[l,v];  out[b,v] = sum_l softmax_l(g)[l] x[l,b,v];
+ *   stat [2, B, V]: stat[0] = max_l g, stat[1] = 1 / sum_l exp(g - max)
+ * fwd: x read once from HBM; stat may be null (no backward pass will follow).
+ * bwd: with the forward's out and stat: dWt[k,l,v] = sum_b x[k,b,v] dg, dbt[l,v] = sum_b dg, dg = dout exp(g - stat[0]) stat[1] (x[l,b,v] - out).
+ *   One workgroup walks every row of its (l group, class tile): no partial sums, no atomics, a second run gives the same bits;
+ *   yt8m_ens_tensor_bwd_workspace_bytes is 0 for every accepted size (-1 for sizes the calls refuse) and workspace may then be null.
+ * Single-element accesses, a lane per class: coalesced for any M, V and alignment.  A null operand, a non-positive size, M above
+ * yt8m_ens_tensor_max_methods() = 80, workspace_bytes below yt8m_ens_tensor_bwd_workspace_bytes: YT8M_E_BADARG; B > 2^24, V > 64 x 65535:
+ * YT8M_E_SHAPE.  Nothing is launched then.
+ * mix: a [B, M] one mixing row per video.  fwd: out[b,v] = sum_k a[b,k] x[k,b,v] (fp64 sums; 16-byte accesses where V % 4 == 0 and x, out
+ *   are 16-byte aligned).  bwd: da[b,k] = sum_v dout[b,v] x[k,b,v], fp64 sums finished in a fixed order.  A null operand, a non-positive
+ *   size: YT8M_E_BADARG; V > 2^24, M > 2^16, B M or B ceil(V / 64) >= 2^31: YT8M_E_SHAPE. */
+int yt8m_ens_tensor_max_methods(void);
+int yt8m_ens_tensor_fwd(const float* x, const float* Wt, const float* bt, float* out, float* stat, int64_t B, int64_t V, int64_t M,
+                        yt8m_stream_t stream);
+int64_t yt8m_ens_tensor_bwd_workspace_bytes(int64_t B, int64_t V, int64_t M);
+int yt8m_ens_tensor_bwd(const float* x, const float* Wt, const float* bt, const float* out, const float* stat, const float* dout,
+                        float* dWt, float* dbt, void* workspace, int64_t workspace_bytes, int64_t B, int64_t V, int64_t M,
+                        yt8m_stream_t stream);
+int yt8m_ens_mix_fwd(const float* x, const float* a, float* out, int64_t B, int64_t V, int64_t M, yt8m_stream_t stream);
+int yt8m_ens_mix_bwd(const float* x, const float* dout, float* da, int64_t B, int64_t V, int64_t M, yt8m_stream_t stream);
+
 /* ---- sigmoid attention pooling over TIME-major rows (csrc/sigmoid_attention.hip; W/all_frame_models/lstm_attention_model.py:61-73,
  * lstm_attention_lstm_model.py:78-92, lstm_multi_attention_model.py:63-78) ----------------------------------------------------------
  * m[t,b] = 1 for t < clamp(num_frames[b], 0, F), else 0.  Row (t, b) of src / vals / dsrc / dvals starts at (t B + b) ld floats.

@@ -354,6 +354,12 @@ SIGNATURES = {
     "yt8m_ens_combine_bwd_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int]),
     "yt8m_ens_combine_bwd": (c_int, [P, P, P, c_int, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int, P]),
     "yt8m_ens_moments": (c_int, [P, P, P, c_int64, c_int64, c_int64, P]),
+    "yt8m_ens_tensor_max_methods": (c_int, []),
+    "yt8m_ens_tensor_fwd": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, P]),
+    "yt8m_ens_tensor_bwd_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "yt8m_ens_tensor_bwd": (c_int, [P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, P]),
+    "yt8m_ens_mix_fwd": (c_int, [P, P, P, c_int64, c_int64, c_int64, P]),
+    "yt8m_ens_mix_bwd": (c_int, [P, P, P, c_int64, c_int64, c_int64, P]),
     "yt8m_sigattn_supported": (c_int, [c_int64] * 5),
     "yt8m_sigattn_workspace_bytes": (c_int64, [c_int64] * 5),
     "yt8m_sigattn_fwd": (c_int, [P, c_int64, P, c_int64, P, P, P, P, P, P, P, c_int64] + [c_int64] * 5 + [P]),

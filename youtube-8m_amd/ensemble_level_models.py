@@ -1,17 +1,23 @@
 """Ensemble-level models on stacked predictions model_input [B, V, M] (M methods); class names, flags, scopes and variable names mirror
 E/ensemble_level_models.py + E/all_ensemble_models/ (E = youtube-8m-ensemble of the reference).
 
-Every plugin is ops.ens_combine -- the softmax over the methods of gated logit tables and the weighted sum, one fused pass over the
+Eight plugins end in ops.ens_combine -- the softmax over the methods of gated logit tables and the weighted sum, one fused pass over the
 predictions each way (csrc/ensemble.hip) or its composed torch form -- plus tiny differentiable torch ops on [J, V, M]-sized or smaller
 tensors (the rank-R product of ensemble_weightx and ensemble_weighty, broadcasts of the per-method weights) and the gate's fully-connected
-layers through video_level_models.fully_connected.  Variables enter those torch ops through ops.as_tensor, which lands their gradient in
-the arena.  tf.get_variable without an initializer: variables.glorot_uniform.
+layers through video_level_models.fully_connected.  Three more mix in ways that ens_combine cannot express (csrc/ensemble_tensor.hip):
+MoeModel's weights come from the predictions themselves through a per-class [M, M] matrix (ops.ens_tensor_moe; it is NOT the video-level
+MoE head), InputMoeModel and AttentionMoeModel mix with one softmax row per video (ops.ens_mix).  Variables enter the torch ops through
+ops.as_tensor, which lands their gradient in the arena.  tf.get_variable without an initializer: variables.glorot_uniform.
 
 Left out, with the reason:
   AttentionRectifiedLinearModel   cannot run in the reference: `rel_gated_weight` (attention_rectified_linear_model.py:44) is undefined
-  InputMoeModel, AttentionMoeModel, and the ensemble copies of LogisticModel / MoeModel / DeepCombineChainModel
-                                  heads over the flattened or averaged predictions: the MoE and logistic heads of video_level_models.py
-                                  applied to another input, not part of the final submission's entries 29-46
+  DeepCombineChainModel (the ensemble copy)
+                                  cannot run in the reference: its first slim.fully_connected(..., reuse=True, scope="transform")
+                                  (deep_combine_chain_model.py:30-36) asks for variables that nothing has created yet, and the `new_relu`
+                                  it computes from each prediction (:62-68) is never fed back (prev_relu stays mean_relu)
+  LogisticModel (the ensemble copy)
+                                  slim.fully_connected over the 3-D model_input [B, V, M] (logistic_model.py:24-26) contracts the method
+                                  axis only and yields [B, V, V] "predictions": not a model of this stage
   EnsembleFrameReader, the model-selection scripts
                                   offline tooling around the readers
 """
@@ -20,7 +26,7 @@ import torch
 from . import models, ops
 from . import video_level_models as vlm
 from .flags import FLAGS, DEFINE_integer
-from .variables import get_default_graph, glorot_uniform
+from .variables import get_default_graph, glorot_uniform, xavier_uniform, zeros
 
 # E/ensemble_level_models.py:40-45 (moe_num_mixtures: video_level_models.py)
 DEFINE_integer("attention_matrix_rank", 3, "The rank of weight matrix used for AttentionMatrixModel.")
@@ -148,3 +154,56 @@ class AttentionMoeMatrixModel(AttentionMatrixModel):
         relus = [_whole_l2_normalize(self.relu(t, num_relu, sub_scope=s))
                  for t, s in ((original_input.to(torch.float32), "origin"), (mean_input, "mean"), (std_input, "std"))]
         return torch.softmax(vlm.fully_connected(torch.cat(relus, dim=1), J, "gates" + sub_scope, l2_penalty=l2_penalty), dim=-1)
+
+
+class MoeModel(models.BaseModel):
+    """moe_model.py (the ensemble's own, not video_level_models.MoeModel): per class a matrix tensor_weight [V, M, M] and a bias
+    tensor_bias [V, M] turn the M predictions of a (video, class) into M logits; their softmax mixes the same M predictions."""
+
+    def create_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", original_input=None,
+                     **unused_params):
+        V, M = model_input.shape[1:]
+        tensor_weight = _var("tensor_weight", (V, M, M), l2_penalty)
+        tensor_bias = ops.as_tensor(get_default_graph().get_variable("tensor_bias", (V, M), zeros, l2=l2_penalty))
+        return {"predictions": ops.ens_tensor_moe(model_input, tensor_weight, tensor_bias)}
+
+
+class InputMoeModel(models.BaseModel):
+    """input_moe_model.py: one softmax row over the methods per video, FC "gates" over l2_normalize(original_input)."""
+
+    def create_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", original_input=None,
+                     **unused_params):
+        if original_input is None:
+            raise ValueError("InputMoeModel needs original_input (--input_data_pattern)")
+        M = model_input.shape[2]
+        gate_input = ops.l2norm_fwd(original_input.to(torch.float32))
+        gate_activations = torch.softmax(vlm.fully_connected(gate_input, M, "gates" + sub_scope, l2_penalty=l2_penalty), dim=-1)
+        return {"predictions": ops.ens_mix(model_input, gate_activations)}
+
+
+class AttentionMoeModel(models.BaseModel):
+    """attention_moe_model.py: --attention_relu_cells relu cells over l2_normalize(original_input) ("relu-input") and over each method's
+    predictions ("relu-sub<i>": method i's plane of the method-major buffer, no copy; the M layers are one grouped launch per direction
+    and the planes, being data, get no gradient); "gate", an FC without bias over the (M + 1) cells, and its softmax mix the methods per
+    video."""
+
+    def relu(self, model_input, relu_cells, l2_penalty=1e-8, sub_scope=""):
+        return vlm.fully_connected(model_input, relu_cells, "relu-" + sub_scope, activation="relu", l2_penalty=l2_penalty)
+
+    def create_model(self, model_input, vocab_size, num_mixtures=None, l2_penalty=1e-8, sub_scope="", original_input=None,
+                     **unused_params):
+        if original_input is None:
+            raise ValueError("AttentionMoeModel needs original_input (--input_data_pattern)")
+        g = get_default_graph()
+        num_relu = FLAGS.attention_relu_cells
+        V, M = model_input.shape[1:]
+        relu_input = self.relu(ops.l2norm_fwd(original_input.to(torch.float32)), num_relu, sub_scope="input")
+        spec = []
+        for i in range(M):
+            scope = "relu-sub%d" % i
+            spec.append((g.get_variable(scope + "/weights", (V, num_relu), xavier_uniform, l2=1e-8), None,
+                         g.get_variable(scope + "/biases", (num_relu,), zeros)))
+        subs = ops.linear_group([model_input[:, :, i] for i in range(M)], spec)
+        relu_units = torch.cat([relu_input, ops.activation(torch.cat(subs, dim=1), "relu")], dim=1)
+        gate = torch.softmax(vlm.fully_connected(relu_units, M, "gate", use_bias=False, l2_penalty=l2_penalty), dim=-1)
+        return {"predictions": ops.ens_mix(model_input, gate)}

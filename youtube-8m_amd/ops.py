@@ -2,7 +2,7 @@
 
 torch is used for device memory, streams and the autograd tape only; every FLOP of the hot path is a
 HIP kernel in libyt8m_hip.so.  No op has a CPU / eager fallback: host tensors raise.  (Documented exceptions: ens_combine /
-ens_moments of the ensemble stage, scale_mix, distill_input, distill_blend, softmax_moe and split_softmax_loss have a composed form that
+ens_moments / ens_tensor_moe / ens_mix of the ensemble stage, scale_mix, distill_input, distill_blend, softmax_moe and split_softmax_loss have a composed form that
 inputs outside the kernels' layout take by rule, not by failure; linear_group multiplies CPU tensors with torch, for the host tests.)
 
 Gradient routing: parameters are NOT autograd leaves.  Each op's backward writes dW directly into the
@@ -1985,6 +1985,122 @@ def ens_moments(x, variance=False):
         var = torch.empty_like(mean) if variance else None
         _lib.check(_lib.lib().yt8m_ens_moments(_p(x), _p(mean), _p(var), B, V, M, _stream()))
         return mean, var
+
+
+# The per-class matrix mix and the per-video mix of the ensemble stage (csrc/ensemble_tensor.hip).  Each switch is read at import; 0 takes
+# the composed torch form everywhere.  The defaults follow tools/ensemble_moe_step.py's op legs (profiles/ensemble_moe_step.jsonl,
+# DESIGN_LOG.md section 43): fused is the default of an op only if its median was below the composed form's at every shape in both
+# runs of the leg.  ens_tensor_moe: it was, 1.5 - 2.7 x: fused.  ens_mix: 25 - 92 x below at B = 1024, but at [128, 4716, 74] the first
+# run measured 168 us against 156 us (the second 76 against 136; both forms are bound by the host there): composed stays the default and
+# YT8M_ENS_MIX_FUSED=1 opts in -- which a run at the training scripts' B = 1024 should do (InputMoeModel's step: 0.85 ms against 18.4 ms).
+ENS_TENSOR_FUSED = os.environ.get("YT8M_ENS_TENSOR_FUSED", "1") != "0"
+ENS_MIX_FUSED = os.environ.get("YT8M_ENS_MIX_FUSED", "0") != "0"
+ENS_TENSOR_CALLS = {"kernels": 0, "composed": 0}
+ENS_MIX_CALLS = {"kernels": 0, "composed": 0}
+
+
+def _ens_layout_ok(x):
+    return x.is_cuda and x.dtype == torch.float32 and not x.requires_grad and ens_method_major(x)
+
+
+def _ens_tensor_fused(x):
+    return ENS_TENSOR_FUSED and _ens_layout_ok(x) and x.shape[2] <= _lib.lib().yt8m_ens_tensor_max_methods()
+
+
+def _ens_mix_fused(x):
+    return ENS_MIX_FUSED and _ens_layout_ok(x)
+
+
+def ens_tensor_moe_composed(x, W, b):
+    """moe_model.py:51-54 in torch ops: the einsum, its softmax over the methods and the sum."""
+    gate_activations = torch.einsum("ijk,jkl->ijl", x, W) + b.unsqueeze(0)
+    return (x * torch.softmax(gate_activations, dim=-1)).sum(dim=2)
+
+
+class _EnsTensorMoe(torch.autograd.Function):
+    """csrc/ensemble_tensor.hip.  Saved for backward: x (data), the [M, M, V] and [M, V] re-layouts of W and b, out [B, V] and the softmax
+    statistics [2, B, V] -- nothing of size [B, V, M]."""
+
+    @staticmethod
+    def forward(ctx, x, W, b):
+        B, V, M = x.shape
+        Wt = W.detach().permute(1, 2, 0).contiguous()                    # [k, l, V], v innermost: 103 MB at V = 4716, M = 74
+        bt = b.detach().t().contiguous()
+        need = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        out = torch.empty((B, V), dtype=torch.float32, device=x.device)
+        stat = torch.empty((2, B, V), dtype=torch.float32, device=x.device) if need else None
+        _lib.check(_lib.lib().yt8m_ens_tensor_fwd(_p(x), _p(Wt), _p(bt), _p(out), _p(stat), B, V, M, _stream()))
+        if need:
+            ctx.save_for_backward(x, Wt, bt, out, stat)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, Wt, bt, out, stat = ctx.saved_tensors
+        B, V, M = x.shape
+        dout = _f32c(dout)
+        dWt, dbt = torch.empty_like(Wt), torch.empty_like(bt)
+        nbytes = _lib.lib().yt8m_ens_tensor_bwd_workspace_bytes(B, V, M)
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes > 0 else None
+        _lib.check(_lib.lib().yt8m_ens_tensor_bwd(_p(x), _p(Wt), _p(bt), _p(out), _p(stat), _p(dout), _p(dWt), _p(dbt), _p(ws), nbytes,
+                                                  B, V, M, _stream()))
+        return None, dWt.permute(2, 0, 1), dbt.t()
+
+
+def ens_tensor_moe(x, W, b):
+    """out [B, V] = sum_l softmax_l(sum_k x[b, v, k] W[v, k, l] + b[v, l]) x[b, v, l]: the ensemble MoeModel's per-class matrix over the
+    methods.  x [B, V, M]: stacked predictions, data.  W [V, M, M], b [V, M]: gradients reach both.
+    The fused kernels take device tensors in ensemble.EnsembleInput's method-major layout with up to yt8m_ens_tensor_max_methods() = 80
+    methods unless YT8M_ENS_TENSOR_FUSED (read at import) is 0; CPU tensors, contiguous [B, V, M] inputs, other dtypes, an x that requires
+    a gradient and more methods take ens_tensor_moe_composed, which computes the same thing."""
+    if x.dim() != 3 or tuple(W.shape) != (x.shape[1], x.shape[2], x.shape[2]) or tuple(b.shape) != tuple(x.shape[1:]):
+        raise ValueError("ens_tensor_moe: x [B, V, M], W [V, M, M] and b [V, M], got %s, %s and %s"
+                         % (tuple(x.shape), tuple(W.shape), tuple(b.shape)))
+    fused = _ens_tensor_fused(x)
+    ENS_TENSOR_CALLS["kernels" if fused else "composed"] += 1
+    if not fused:
+        return ens_tensor_moe_composed(x, W, b)
+    return _EnsTensorMoe.apply(x, W, b)
+
+
+def ens_mix_composed(x, a):
+    return torch.einsum("ijk,ik->ij", x, a)
+
+
+class _EnsMix(torch.autograd.Function):
+    """csrc/ensemble_tensor.hip: one pass over the method-major predictions each way; saved for backward: x (data) alone."""
+
+    @staticmethod
+    def forward(ctx, x, a):
+        B, V, M = x.shape
+        a32 = _f32c(a.detach())
+        out = torch.empty((B, V), dtype=torch.float32, device=x.device)
+        _lib.check(_lib.lib().yt8m_ens_mix_fwd(_p(x), _p(a32), _p(out), B, V, M, _stream()))
+        if ctx.needs_input_grad[1]:
+            ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, = ctx.saved_tensors
+        B, V, M = x.shape
+        dout = _f32c(dout)
+        da = torch.empty((B, M), dtype=torch.float32, device=x.device)
+        _lib.check(_lib.lib().yt8m_ens_mix_bwd(_p(x), _p(dout), _p(da), B, V, M, _stream()))
+        return None, da
+
+
+def ens_mix(x, a):
+    """out [B, V] = sum_k a[b, k] x[b, v, k]: one mixing row per video (InputMoeModel, AttentionMoeModel).  x [B, V, M]: stacked
+    predictions, data; the gradient reaches a [B, M].  Kernels under the conditions of ens_tensor_moe (any M) unless YT8M_ENS_MIX_FUSED
+    (read at import) is 0, ens_mix_composed otherwise."""
+    if x.dim() != 3 or tuple(a.shape) != (x.shape[0], x.shape[2]):
+        raise ValueError("ens_mix: x [B, V, M] and a [B, M], got %s and %s" % (tuple(x.shape), tuple(a.shape)))
+    fused = _ens_mix_fused(x)
+    ENS_MIX_CALLS["kernels" if fused else "composed"] += 1
+    if not fused:
+        return ens_mix_composed(x, a)
+    return _EnsMix.apply(x, a)
 
 
 class _MoeHead(torch.autograd.Function):
