@@ -1184,6 +1184,22 @@ int yt8m_half_segment_means_u8(const uint8_t* q, const int32_t* num_frames, floa
 int yt8m_dequant_noise_u8(const uint8_t* q, const int32_t* num_frames, float* y, int64_t B, int64_t F, int64_t D, float stddev,
                           uint64_t seed, yt8m_stream_t stream);
 
+/* ---- random half-frame inference (Z = youtube-8m-zhangteng, frame_level_models.py:6189-6217; csrc/frame_subset.hip) ---------------
+ * E replicas of every video, each an order-preserving random K-subset of its F frames; ONE subset per replica, shared by the batch.
+ * yt8m_frame_subset_draw: index [E,K] int32.  Frame f of replica e takes the key w(e,f) = the 32-bit word of logical element
+ *   e F4 + f (F4 = F rounded up to a multiple of 4) in yt8m_add_noise_f32's Philox layout (counter (element >> 2, 0), word element & 3,
+ *   key = seed, offset 0); the subset is the K frames with the smallest (w, f) pairs, written in ascending order of f.  No atomics:
+ *   reruns are bit-equal.  2 <= F <= 1024 and 1 <= K <= F, else YT8M_E_SHAPE.
+ * yt8m_frame_subset_gather_*: x [B,F,D], index [E,K] -> y [B E,K,D] and num_frames_out [B E].  With n_b = num_frames[b] clamped to
+ *   [0, F]: y[b E + e, j, :] = x[b, index[e,j], :] where 0 <= index[e,j] < n_b, else zeros WITHOUT reading x (padding content is not
+ *   trusted; an index outside [0, F) is never dereferenced); num_frames_out[b E + e] = the number of such j.  Out of place (every
+ *   operand disjoint); 16-byte accesses when the rows allow them; at most 2^32 items (16-byte vectors, or elements), else YT8M_E_SHAPE. */
+int yt8m_frame_subset_draw(int32_t* index, int64_t E, int64_t F, int64_t K, uint64_t seed, yt8m_stream_t stream);
+int yt8m_frame_subset_gather_u8(const uint8_t* x, const int32_t* num_frames, const int32_t* index, uint8_t* y, int32_t* num_frames_out,
+                                int64_t B, int64_t F, int64_t D, int64_t E, int64_t K, yt8m_stream_t stream);
+int yt8m_frame_subset_gather_f32(const float* x, const int32_t* num_frames, const int32_t* index, float* y, int32_t* num_frames_out,
+                                 int64_t B, int64_t F, int64_t D, int64_t E, int64_t K, yt8m_stream_t stream);
+
 /* ---- masked softmax over frames + renormalise (lstm_attention_max_pooling_model.py:59-60) -------
  * act [B,F,A] -> w [B,F,A]: w = mask * softmax_F(act) / sum_F(mask * softmax_F(act)).  bwd: dact from dw. */
 int yt8m_attn_softmax_fwd(const float* act, const int32_t* num_frames, float* w, int64_t B, int64_t F,

@@ -340,6 +340,9 @@ SIGNATURES = {
     "yt8m_half_segments_f32": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, P]),
     "yt8m_half_segment_means_u8": (c_int, [P, P, P, c_int64, c_int64, c_int64, c_int, c_float, P]),
     "yt8m_dequant_noise_u8": (c_int, [P, P, P, c_int64, c_int64, c_int64, c_float, ctypes.c_uint64, P]),
+    "yt8m_frame_subset_draw": (c_int, [P, c_int64, c_int64, c_int64, ctypes.c_uint64, P]),
+    "yt8m_frame_subset_gather_u8": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, P]),
+    "yt8m_frame_subset_gather_f32": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, P]),
     "yt8m_resolution_mean_u8": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int, c_float, P]),
     "yt8m_resolution_mean_f32": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int, c_float, P]),
     "yt8m_multiscale_workspace_bytes": (c_int64, [c_int64]),

@@ -1254,7 +1254,8 @@ class GatedNetVLADAttentionChainModel(GatedNetVLADModel):
 #   function (tf.nn.softmax of the predictions) under the name Z uses;
 #   MoeMix4Model's --moe_group=True path (label groups of --class_size): no script of the list sets it;
 #   Z's --distillation_type 1-3 losses: the cascade scripts say --distillation_type=0, the plain label loss;
-#   LstmRandomModel: LstmMemoryModel as committed -- its frame selection sits behind FLAGS.train=="train", and --train is a bool flag (:54, :4037);
+#   of the random half-frame family (:4017, :6076-6247; built near the end of this file: LstmRandomModel, FrameRandomEvalModel,
+#   FrameAttentionEvalModel), not built: VideoFrameEvalModel (:6076), which no script uses, and per-video rather than per-batch subsets;
 #   LstmBiglu2Model: LstmBigluModel's pair of passes on LstmGlu2Model's input-memory cell (:1160), and not in the final submission's list;
 #   LstmMultiscale3Model: LstmMultiscale2Model on LstmGlu2Model's input-memory cell with the HIDDEN state gathered at frame num_frames - 1,
 #   not the memory (:3375, :3507): seq_ops.glu_lstm_layer hands back the gathered memory only, so it needs a second gather and its gradient;
@@ -1575,6 +1576,78 @@ class InputExtendModel(models.BaseModel):
         lo, hi = input_extend_windows(num_frames, num_extend)
         _, pooled = seq_ops.softmax_attention_tm(outputs, W1, b1, outputs_features, extra=extra, lo=lo, hi=hi)
         return _classify(pooled.reshape(B * num_extend, lstm_size), model_input, vocab_size, **unused_params)
+
+
+# ---- Z: random half-frame inference (LstmRandomModel, FrameRandomEvalModel, FrameAttentionEvalModel) -------------------------------
+# VideoFrameEvalModel (Z/frame_level_models.py:6076-6131), the fourth class of the family, is not built: no script uses it.
+DEFINE_bool("lstm_random_frames", False, "LstmRandomModel: run every TRAINING step on one random, order-preserving half of the frames "
+            "(what the reference's test FLAGS.train==\"train\" was written to do and, comparing a bool flag with a string, never does).")
+
+
+def _random_halves(model_input, num_frames, replicas, seed):
+    """(frames [B E, F // 2, D], num_frames [B E]): E replicas of every video, replica e on the e-th random half of the frame indices
+    (ops.frame_subset: one order-preserving F // 2 subset per replica, shared by the batch; row b E + e = replica e of video b).  On
+    the reader's bytes and on float frames alike; a replica's chosen padding frames are zero rows behind its real ones."""
+    y, nf, _ = ops.frame_subset(model_input, num_frames, replicas, seed=seed)
+    return y, nf
+
+
+def _mean_over_replicas(predictions, replicas):
+    """tf.reduce_mean(reshape(predictions, [-1, E, V]), axis=1)"""
+    rows, V = predictions.shape
+    return ops.frame_pool(predictions.reshape(rows // replicas, replicas, V), "average")
+
+
+class LstmRandomModel(LstmMemoryModel):
+    """Z/frame_level_models.py:4017-4079: LstmMemoryModel's function and variables (RNN/multi_rnn_cell/cell_<l>/basic_lstm_cell/
+    {weights,biases}, then the head's).  The reference selects a random half of the frames behind `FLAGS.train=="train"`; --train is a
+    bool flag (:54), so the test never holds and the model as committed is LstmMemoryModel in training and in evaluation alike.
+    --lstm_random_frames=False (the default) is that.  True runs every training step (is_training) on one random, order-preserving half
+    of the frames (E = 1, K = F // 2: ops.frame_subset), which is what the final submission's list says the model was trained with;
+    evaluation and inference never select, as under the scripts' --train=False.  frame_subset_seed: the key of the draw (default: the
+    graph's next random-op key)."""
+
+    def create_model(self, model_input, vocab_size, num_frames, is_training=True, frame_subset_seed=None, **unused_params):
+        if FLAGS.lstm_random_frames and is_training:
+            model_input, num_frames = _random_halves(model_input, num_frames, 1, frame_subset_seed)
+        if not is_training:
+            unused_params["is_training"] = False
+        return super().create_model(model_input, vocab_size, num_frames, **unused_params)
+
+
+class FrameRandomEvalModel(models.BaseModel):
+    """Z/frame_level_models.py:6182-6247, the test-time augmentation of LstmRandomModel's checkpoints: E = --moe_num_extend replicas of
+    every video, each on a random, order-preserving half of its frames (unconditionally: this is an inference plugin), go through
+    LstmMemoryModel's function as ONE batch of B E rows of F // 2 frames; the head reads the concatenated final memories and the
+    predictions are averaged over a video's E rows.  Variables: exactly LstmMemoryModel's names and shapes, so a checkpoint trained as
+    LstmMemoryModel or LstmRandomModel loads.  A replica that keeps none of a video's frames runs at length 0 and hands the zero state
+    to the head, as dynamic_rnn does.  frame_subset_seed: the key of the draw (default: the graph's next random-op key).  The labels
+    are not forwarded: the head sees B E rows.
+    accepts_quantized_input: the replicas are gathered from the reader's bytes and the stack reads them (see _lstm_stack)."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, frame_subset_seed=None, **unused_params):
+        num_extend = FLAGS.moe_num_extend
+        unused_params.pop("labels", None)
+        model_input, num_frames = _random_halves(model_input, num_frames, num_extend, frame_subset_seed)
+        result = LstmMemoryModel().create_model(model_input, vocab_size, num_frames, **unused_params)
+        return {"predictions": _mean_over_replicas(result["predictions"], num_extend)}
+
+
+class FrameAttentionEvalModel(models.BaseModel):
+    """Z/frame_level_models.py:6133-6180, the same test-time augmentation in front of LstmExtendModel().create_model: its predictions on
+    the B E replicas are clipped to [0, 1] and averaged over a video's E rows.  As in the reference the one flag --moe_num_extend is both
+    the number of replicas and LstmExtendModel's number of attention heads.  Variables: LstmExtendModel's.  frame_subset_seed and the
+    labels: as FrameRandomEvalModel.
+    accepts_quantized_input: the replicas are gathered from the reader's bytes, which LstmExtendModel reads on its own terms."""
+    accepts_quantized_input = True
+
+    def create_model(self, model_input, vocab_size, num_frames, frame_subset_seed=None, **unused_params):
+        num_extend = FLAGS.moe_num_extend
+        unused_params.pop("labels", None)
+        model_input, num_frames = _random_halves(model_input, num_frames, num_extend, frame_subset_seed)
+        result = LstmExtendModel().create_model(model_input, vocab_size, num_frames, **unused_params)
+        return {"predictions": _mean_over_replicas(result["predictions"].clamp(0.0, 1.0), num_extend)}
 
 
 # ---- Z: the LstmMultiscale models -- the scale loop of MultiscaleCnnLstmModel with a learned per-label mix of the scales --------------------

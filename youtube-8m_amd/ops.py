@@ -3,7 +3,8 @@
 torch is used for device memory, streams and the autograd tape only; every FLOP of the hot path is a
 HIP kernel in libyt8m_hip.so.  No op has a CPU / eager fallback: host tensors raise.  (Documented exceptions: ens_combine /
 ens_moments / ens_tensor_moe / ens_mix of the ensemble stage, scale_mix, distill_input, distill_blend, softmax_moe and split_softmax_loss have a composed form that
-inputs outside the kernels' layout take by rule, not by failure; linear_group multiplies CPU tensors with torch, for the host tests.)
+inputs outside the kernels' layout take by rule, not by failure; so has frame_subset, whose draw is also restated on the host for CPU
+tensors; linear_group multiplies CPU tensors with torch, for the host tests.)
 
 Gradient routing: parameters are NOT autograd leaves.  Each op's backward writes dW directly into the
 variable's slice of the gradient arena (GEMM beta = 0 on first write, 1 afterwards) and returns None for
@@ -530,6 +531,97 @@ def half_segments(x, num_frames):
         raise TypeError("expected uint8 or float32 frames, got %s" % x.dtype)
     _lib.check(fn(_p(x), _p(nf), _p(y), _p(nf_out), B, F, D, _stream()))
     return y, nf_out
+
+
+# ---- random half-frame inference (csrc/frame_subset.hip; FrameRandomEvalModel, FrameAttentionEvalModel, LstmRandomModel) ------------
+# anything but 0 (the default): frame_subset gathers with the kernel of csrc/frame_subset.hip; 0: with index_select, a comparison and a
+# sum (A/B runs, tests).  The draw has one form per device either way.  The kernel is the default because tools/frame_subset_step.py's op
+# leg showed its median below the composed form's at every shape in both runs (3.8 - 8.3 x: DESIGN_LOG.md section 44).
+FRAME_SUBSET_FUSED = os.environ.get("YT8M_FRAME_SUBSET_FUSED", "1") != "0"
+FRAME_SUBSET_CALLS = {"kernels": 0, "composed": 0}      # which form gathered (tests)
+FRAME_SUBSET_MAX_F = 1024                               # csrc/frame_subset.hip DRAW_MAX_F
+
+
+def _philox_words_host(n, seed):
+    """The uint32 Philox4x32-10 word of logical elements 0..n-1 under key = seed (csrc/philox.h: counter (element >> 2, 0), word
+    element & 3), in numpy integer arithmetic: the host form of the draw, for CPU tensors."""
+    import numpy as np
+    u, mask = np.uint64, np.uint64(0xFFFFFFFF)
+    ctr = np.arange((n + 3) // 4, dtype=np.uint64)
+    c0, c1, c2, c3 = ctr & mask, ctr >> u(32), np.zeros_like(ctr), np.zeros_like(ctr)
+    k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = c0 * u(0xD2511F53), c2 * u(0xCD9E8D57)
+        c0, c1, c2, c3 = (p1 >> u(32)) ^ c1 ^ u(k0), p1 & mask, (p0 >> u(32)) ^ c3 ^ u(k1), p0 & mask
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return np.stack([c0, c1, c2, c3], axis=1).reshape(-1)[:n]
+
+
+def frame_subset_index(E, F, K, seed=None, device=None):
+    """index [E,K] int32: per replica one uniformly random K-subset of the frame indices 0..F-1 in ascending order -- what the first K
+    entries of tf.random_shuffle's permutation are after Z/frame_level_models.py:6195-6199 has sorted them -- shared by every video of
+    the batch.  Frame f of replica e takes the Philox word of logical element e F4 + f (F4 = F rounded up to a multiple of 4) under
+    key = seed; the subset is the K frames with the smallest (word, f) pairs.  seed None: the graph's next random-op key; device None:
+    the graph's.  A CPU device restates the draw on the host: for one seed, CPU and device hold the same index."""
+    E, F, K = int(E), int(F), int(K)
+    if seed is None:
+        seed = get_default_graph().next_random_seed()
+    device = torch.device(device) if device is not None else get_default_graph().device
+    if E < 0 or not 2 <= F <= FRAME_SUBSET_MAX_F or not 1 <= K <= F:
+        raise ValueError("frame_subset_index: E >= 0, 2 <= F <= %d and 1 <= K <= F, got E = %d, F = %d, K = %d" % (FRAME_SUBSET_MAX_F, E, F, K))
+    if device.type != "cuda":
+        import numpy as np
+        F4 = (F + 3) // 4 * 4
+        w = _philox_words_host(E * F4, seed).reshape(E, F4)[:, :F]
+        order = np.argsort(w, axis=1, kind="stable")                            # stable: ties go to the smaller f
+        return torch.from_numpy(np.sort(order[:, :K], axis=1).astype(np.int32)).to(device)
+    index = torch.empty((E, K), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().yt8m_frame_subset_draw(_p(index), E, F, K, int(seed), _stream()))
+    return index
+
+
+def frame_subset_composed(x, num_frames, index):
+    """frame_subset's gather in torch ops: index_select, the count from a comparison and a sum, padding rows multiplied to zero."""
+    B, F, D = x.shape
+    E, K = index.shape
+    idx = index.to(torch.int64)
+    inside = (idx >= 0) & (idx < F)
+    live = inside[None] & (idx[None] < num_frames.clamp(0, F).to(torch.int64).view(B, 1, 1))        # [B,E,K]
+    y = x.index_select(1, idx.clamp(0, F - 1).flatten()).view(B * E, K, D)
+    return y * live.view(B * E, K, 1).to(x.dtype), live.sum(dim=2).view(B * E).to(torch.int32)
+
+
+def frame_subset(x, num_frames, E, K=None, seed=None, index=None):
+    """E replicas of every video on a random, order-preserving K-subset of its frames (Z/frame_level_models.py:6189-6217; K None: F // 2):
+    uint8 or float32 frames [B,F,D] -> (y [B E,K,D] of the same dtype, num_frames_out [B E] int32, index [E,K] int32), row b E + e =
+    replica e of video b.  y[b E + e, j] = x[b, index[e,j]] where index[e,j] < num_frames[b] (clamped to [0, F]), else a zero row;
+    num_frames_out counts the former.  The indices ascend, so a replica is a padded video: its real frames first, then zeros.  index
+    None: frame_subset_index(E, F, K, seed) on the frames' device.  An index outside [0, F) is padding.  Frames are data: no gradient.
+    The gather runs csrc/frame_subset.hip where FRAME_SUBSET_FUSED is on; CPU tensors, other dtypes and the switch's 0 take
+    frame_subset_composed."""
+    if x.dim() != 3:
+        raise ValueError("expected frames [B,F,D], got %d dimensions" % x.dim())
+    if num_frames is None:
+        raise ValueError("frame_subset needs num_frames")
+    B, F, D = x.shape
+    E = int(E)
+    if index is None:
+        index = frame_subset_index(E, F, F // 2 if K is None else K, seed=seed, device=x.device)
+    index = index.to(device=x.device, dtype=torch.int32).contiguous()
+    if index.dim() != 2 or index.shape[0] != E or (K is not None and index.shape[1] != int(K)):
+        raise ValueError("frame_subset: index must be [E = %d, K], got %s" % (E, tuple(index.shape)))
+    K = index.shape[1]
+    x, nf = x.contiguous(), num_frames.to(device=x.device, dtype=torch.int32).contiguous()
+    fused = FRAME_SUBSET_FUSED and x.is_cuda and x.dtype in (torch.uint8, torch.float32)
+    FRAME_SUBSET_CALLS["kernels" if fused else "composed"] += 1
+    if not fused:
+        return frame_subset_composed(x, nf, index) + (index,)
+    y = torch.empty((B * E, K, D), dtype=x.dtype, device=x.device)
+    nf_out = torch.empty((B * E,), dtype=torch.int32, device=x.device)
+    fn = _lib.lib().yt8m_frame_subset_gather_u8 if x.dtype == torch.uint8 else _lib.lib().yt8m_frame_subset_gather_f32
+    _lib.check(fn(_p(x), _p(nf), _p(index), _p(y), _p(nf_out), B, F, D, E, K, _stream()))
+    return y, nf_out, index
 
 
 def half_segment_means(q, num_frames, l2norm=False, eps=1e-12):
