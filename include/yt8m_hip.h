@@ -733,6 +733,36 @@ int yt8m_pointwise_loss_fwd_bwd(int kind, const float* p, const void* labels, in
 int yt8m_pointwise_loss_bwd(int kind, const float* p, const void* labels, int label_dtype, const float* upstream_dev, float* dp,
                             int64_t B, int64_t V, float c0, float c1, float eps, float upstream, yt8m_stream_t stream);
 
+/* ---- the --loss_function branches of Z's CrossEntropyLoss (Z/losses.py:64-168); csrc/xent_variants.hip ---------------------------
+ * Operands, passes, `workspace` (>= yt8m_xent_variant_workspace_bytes(B, V)) and the upstream scalars as for the losses above; also
+ * V <= INT_MAX - 1024.  loss = mean_b sum_v -c + m with e = eps and ce(q, t) = t log(q + e) + (1 - t) log(1 - q + e):
+ *   SQUARE   c = ce(p p, y)            SQRT   c = ce(sqrt p, y)            WEIGHT   c = 10 y log(p + e) + (1 - y) log(1 - p + e)
+ *   JSD      a = c0, d = (1 - a) y + a p: c = ((1 - a) p + a y) log(d + e) + ((1 - a)(1 - p) + a (1 - y)) log(1 - d + e)
+ *                                            - (1 - a) (p log(p + e) + (1 - p) log(1 - p + e))
+ *   MIX      c = ce(p, y) + ce(y, p) - ce(p, p)
+ *   MARGIN   c = ce(p, y), m = -(pos - neg); pos = sum(p wp) / sum(wp) mean_b(sum_v y), wp = (0.5 - log(p + e)) y; neg =
+ *            sum(p wn) / sum(wn) mean_b(sum_v (1 - y)), wn = (1 - y)(0.5 - log(1 - p + e)); the sums span the whole [B, V] and both
+ *            quotients are differentiated.  No positive in the batch: 0 / 0, NaN.
+ *   RELABEL  c = 0; pre = mean_b sum_v -ce(p, y); m = pre when pre < 10, else the same on y' = y + add (1 - y), add the one-hot of the
+ *            row's argmax of p (the lowest column of a tie).  The branch is taken on the device; branch, argmax and y' carry no gradient.
+ * c0 is read by JSD alone.  stats: float[YT8M_XV_STATS_FLOATS], written whole by every forward call; the named floats below, the rest
+ * csrc/xent_variants.hip's.  argmax: int32[B], RELABEL only (NULL otherwise), written by every RELABEL forward call whatever the branch.
+ * The backward call of MARGIN and RELABEL reads the forward call's stats (and argmax); the other kinds take NULL for both. */
+enum yt8m_xent_variant { YT8M_XV_SQUARE = 0, YT8M_XV_SQRT = 1, YT8M_XV_JSD = 2, YT8M_XV_MIX = 3, YT8M_XV_WEIGHT = 4, YT8M_XV_MARGIN = 5,
+                         YT8M_XV_RELABEL = 6 };
+#define YT8M_XV_STATS_FLOATS 16
+#define YT8M_XV_STAT_LOSS 0   /* the loss */
+#define YT8M_XV_STAT_PRE 1    /* MARGIN, RELABEL: mean_b sum_v -ce(p, y) */
+#define YT8M_XV_STAT_FLAG 2   /* RELABEL: 1 when the relabelled branch was taken, else 0 */
+#define YT8M_XV_STAT_POS 3    /* MARGIN: pos, neg */
+#define YT8M_XV_STAT_NEG 4
+int64_t yt8m_xent_variant_workspace_bytes(int64_t B, int64_t V);
+int yt8m_xent_variant_fwd(int kind, const float* p, const void* labels, int label_dtype, float* loss_out, float* stats, int32_t* argmax,
+                          int64_t B, int64_t V, float c0, float eps, void* workspace, yt8m_stream_t stream);
+int yt8m_xent_variant_bwd(int kind, const float* p, const void* labels, int label_dtype, const float* stats, const int32_t* argmax,
+                          const float* upstream_dev, float* dp, int64_t B, int64_t V, float c0, float eps, float upstream,
+                          yt8m_stream_t stream);
+
 /* ---- optimiser slice of build_graph (W/train.py:435-466, W/utils.py:164-174, tf.train.AdamOptimizer)
  * The parameters live in one flat fp32 arena; `chunks` (device, int32[nchunks*4]) describes it as
  * {offset, count, tensor_id, unused} with no chunk spanning two tensors; count <= 4096.

@@ -1,9 +1,9 @@
 """Label losses; names, flags and semantics mirror W/losses.py (W = /root/reference/youtube-8m-wangheda).
 
 Here: CrossEntropyLoss, WeightedCrossEntropyLoss, MeanSquareErrorLoss, HingeLoss, MultiTaskCrossEntropyLoss,
-BatchAgreementCrossEntropyLoss and TopKBatchAgreementCrossEntropyLoss, and SplitSoftmaxLoss from Z/losses.py.  Every one runs as HIP
-kernels (csrc/elementwise.hip for the plain cross entropy, csrc/softmax_moe.hip for SplitSoftmaxLoss, csrc/losses.hip for the others),
-forward and backward.
+BatchAgreementCrossEntropyLoss and TopKBatchAgreementCrossEntropyLoss, and from Z/losses.py SplitSoftmaxLoss and the --loss_function
+branches of its CrossEntropyLoss.  Every one runs as HIP kernels (csrc/elementwise.hip for the plain cross entropy, csrc/softmax_moe.hip
+for SplitSoftmaxLoss, csrc/xent_variants.hip for --loss_function, csrc/losses.hip for the others), forward and backward.
 
 Left out of W/losses.py:
   PairwiseHingeLoss, MixedLoss                                  they unstack the batch by --batch_size and draw TF random integers
@@ -22,7 +22,16 @@ calculate_loss(predictions_class, the labels tiled) -- is a training rule, not a
                                                                 final submission's list sets Z's.
   calculate_loss_mix2                                           it reads "predictions_encoder" and autoencoder files no plugin here has.
 Z's SoftmaxLoss (Z/losses.py:412-456), the loss written for MoeSoftmaxModel, is here under the name SplitSoftmaxLoss (the name
-SoftmaxLoss stays W's, above): --label_loss=SplitSoftmaxLoss; csrc/softmax_moe.hip."""
+SoftmaxLoss stays W's, above): --label_loss=SplitSoftmaxLoss; csrc/softmax_moe.hip.
+Z's --loss_function (Z/losses.py:64-168) selects a branch inside CrossEntropyLoss.calculate_loss: loss_square, loss_sqrt, loss_jsd (with
+--jsd_pi), loss_mix, loss_weight, loss_margin and loss_relabel are here (CrossEntropyLoss below); the final submission's entries 1 and
+29.2 train MoeMix4Model under loss_relabel and loss_weight.  Left out of the rest of Z/losses.py:
+  loss_smoothing                                                it reads ./resources/embedding_matrix.model, a file this repository has
+                                                                no source for: --loss_function=loss_smoothing raises ValueError.
+  calculate_loss_distill* (the whole family),                   they take distillation labels, negative samples or post-processing
+  calculate_loss_negative, calculate_loss_max,                  inputs through call sites of Z/train.py that no plugin of the final
+  calculate_loss_postprocess                                    submission's list here goes through.
+  CrossEntropyLoss_weight                                       a class of its own that reads per-class weights from a file."""
 import torch
 
 from . import ops
@@ -41,6 +50,11 @@ DEFINE_string("vertical_file", "resources/vertical.tsv", "Location of label-vert
 DEFINE_float("batch_agreement", 0.1, "the batch_agreement parameter")
 DEFINE_bool("label_smoothing", False, "whether do label smoothing")
 DEFINE_float("label_smoothing_epsilon", 0.1, "whether do label smoothing")
+# Z/losses.py:33-38
+DEFINE_string("loss_function", None, "different loss functions used in CrossEntropyLoss.")
+DEFINE_float("jsd_pi", 0.5, "weight used when loss function is loss_jsd.")
+
+LOSS_FUNCTIONS = ("loss_square", "loss_sqrt", "loss_jsd", "loss_mix", "loss_weight", "loss_margin", "loss_relabel")
 
 
 def smoothing(labels):
@@ -86,9 +100,41 @@ class BaseLoss(object):
 
 class CrossEntropyLoss(BaseLoss):
     """W/losses.py:110-130: probability-space cross entropy, epsilon = 10e-6, sum over classes, mean over batch,
-    optional per-example weights."""
+    optional per-example weights.
+
+    --loss_function (Z/losses.py:64-168) replaces it, here as in Z and so for everything that calls this method (the mix loss, the
+    frames loss and both terms of MultiTaskCrossEntropyLoss), by mean_b sum_v -c + m, with e = 10e-6 and
+    ce(q, t) = t log(q + e) + (1 - t) log(1 - q + e):
+      loss_square   c = ce(p p, y)                    loss_sqrt   c = ce(sqrt(p), y)
+      loss_jsd      a = --jsd_pi, d = (1 - a) y + a p: c = (1 - a) p log(d + e) + (1 - a)(1 - p) log(1 - d + e) + a y log(d + e)
+                    + a (1 - y) log(1 - d + e) - (1 - a) p log(p + e) - (1 - a)(1 - p) log(1 - p + e)
+      loss_mix      c = ce(p, y) + p log(y + e) + (1 - p) log(1 - y + e) - p log(p + e) - (1 - p) log(1 - p + e)
+      loss_weight   c = 10 y log(p + e) + (1 - y) log(1 - p + e)
+      loss_margin   c = ce(p, y), m = -(pos - neg), pos = sum(p wp) / sum(wp) mean_b(sum_v y) with wp = (0.5 - log(p + e)) y and
+                    neg = sum(p wn) / sum(wn) mean_b(sum_v (1 - y)) with wn = (1 - y)(0.5 - log(1 - p + e)), every sum over the whole
+                    tensor of the call.  A batch without a positive is 0 / 0: NaN, as in the reference.
+      loss_relabel  c = 0 (the reference multiplies it by 0.0); with pre = mean_b sum_v -ce(p, y): m = pre if pre < 10, else the same
+                    on y' = y + add (1 - y), add the one-hot of the row's argmax of p (lowest index of a tie, over the whole row of the
+                    call: one added label per L V-wide row of predictions_class).  The branch is taken on the device.
+    The reference puts no stop_gradient in this chain: the gradient runs through every p above, both quotients of loss_margin
+    included; the condition, the argmax and y' of loss_relabel carry none.  `scale` multiplies the whole result, m included.
+    With --loss_function set: `weights` that are not None raise ValueError (Z defines none), so does --label_smoothing (neither
+    reference defines the combination), loss_smoothing (above) and -- a deliberate difference: Z falls through to the plain cross
+    entropy silently, and a typo must not train the wrong loss -- any other unknown value."""
 
     def calculate_loss(self, predictions, labels, weights=None, scale=1.0, **unused_params):
+        kind = FLAGS.loss_function
+        if kind is not None:
+            if kind == "loss_smoothing":
+                raise ValueError("--loss_function=loss_smoothing reads ./resources/embedding_matrix.model (Z/losses.py:144), "
+                                 "a file this repository has no source for")
+            if kind not in LOSS_FUNCTIONS:
+                raise ValueError("unknown --loss_function=%r: one of %s" % (kind, ", ".join(LOSS_FUNCTIONS)))
+            if weights is not None:
+                raise ValueError("--loss_function=%s takes no per-example weights (Z/losses.py:64 defines none)" % kind)
+            if FLAGS.label_smoothing:
+                raise ValueError("--label_smoothing with --loss_function=%s: neither reference defines the combination" % kind)
+            return ops.xent_variant(predictions, labels, kind, c0=FLAGS.jsd_pi, scale=scale)
         y = smoothing(labels) if FLAGS.label_smoothing else labels
         return ops.cross_entropy(predictions, y, weights, scale)
 

@@ -2728,3 +2728,60 @@ def topk_batch_agreement_cross_entropy(p, labels, agreement):
 def pointwise_loss(p, labels, kind, c0=1.0, c1=1.0):
     """kind: "weighted_xent" (c0 / c1 = false negative / false positive punishment), "mse" or "hinge" (c0 = b)."""
     return _PointwiseLoss.apply(p, labels, kind, float(c0), float(c1))
+
+
+# ---- the --loss_function branches of Z's CrossEntropyLoss (Z/losses.py:64-168); csrc/xent_variants.hip --------------------------
+XENT_VARIANTS = {"loss_square": 0, "loss_sqrt": 1, "loss_jsd": 2, "loss_mix": 3, "loss_weight": 4, "loss_margin": 5,
+                 "loss_relabel": 6}                                   # enum yt8m_xent_variant
+XV_STATS_FLOATS = 16                  # YT8M_XV_STATS_FLOATS
+XV_STATS = {"loss": 0, "pre": 1, "flag": 2, "pos": 3, "neg": 4}       # YT8M_XV_STAT_*
+
+
+def xent_variant_fwd(p, labels, kind, c0=0.5, eps=XENT_EPS):
+    """(loss, stats, argmax) of one --loss_function kind, unscaled.  stats: XV_STATS_FLOATS device floats (XV_STATS names the readable
+    ones); argmax: the rows' argmax of p as [B] int32 for "loss_relabel", None for the other kinds.  c0: --jsd_pi ("loss_jsd" alone)."""
+    code = XENT_VARIANTS[kind]
+    p, lab, ldt, B, V = _loss_args(p, labels)
+    L = _lib.lib()
+    ws = _loss_workspace(L.yt8m_xent_variant_workspace_bytes(B, V), p.device)
+    loss = torch.empty((), dtype=torch.float32, device=p.device)
+    stats = torch.empty(XV_STATS_FLOATS, dtype=torch.float32, device=p.device)
+    argmax = torch.empty(B, dtype=torch.int32, device=p.device) if kind == "loss_relabel" else None
+    _lib.check(L.yt8m_xent_variant_fwd(code, _p(p), _p(lab), ldt, _p(loss), _p(stats), _p(argmax), B, V, c0, eps, _p(ws), _stream()))
+    return loss, stats, argmax
+
+
+def xent_variant_bwd(p, labels, kind, stats, argmax, upstream_dev, c0=0.5, eps=XENT_EPS, upstream=1.0):
+    code = XENT_VARIANTS[kind]
+    p, lab, ldt, B, V = _loss_args(p, labels)
+    _dev(stats, argmax, upstream_dev)
+    dp = torch.empty_like(p)
+    up = None if upstream_dev is None else _f32c(upstream_dev)
+    _lib.check(_lib.lib().yt8m_xent_variant_bwd(code, _p(p), _p(lab), ldt, _p(None if stats is None else _f32c(stats)), _p(argmax), _p(up),
+                                                _p(dp), B, V, c0, eps, upstream, _stream()))
+    return dp
+
+
+class _XentVariant(torch.autograd.Function):
+    """Saves p, the 16 floats of stats and (loss_relabel) the rows' argmax; the backward pass recomputes dL/dp from (p, y) and them, with
+    the upstream scalar read on the device: no host sync, nothing of size [B, V] kept beyond p."""
+
+    @staticmethod
+    def forward(ctx, p, labels, kind, c0, scale):
+        loss, stats, argmax = xent_variant_fwd(p, labels, kind, c0)
+        ctx.save_for_backward(p, stats)
+        ctx.args = labels, kind, c0, scale, argmax
+        return loss * scale if scale != 1.0 else loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        p, stats = ctx.saved_tensors
+        labels, kind, c0, scale, argmax = ctx.args
+        return xent_variant_bwd(p, labels, kind, stats, argmax, dloss.reshape(1), c0, upstream=scale), None, None, None, None
+
+
+def xent_variant(p, labels, kind, c0=0.5, scale=1.0):
+    """kind: a key of XENT_VARIANTS (the reference's --loss_function names); c0: --jsd_pi; scale multiplies the whole loss."""
+    if kind not in XENT_VARIANTS:
+        raise ValueError("unknown loss kind %r: one of %s" % (kind, ", ".join(XENT_VARIANTS)))
+    return _XentVariant.apply(p, labels, kind, float(c0), float(scale))

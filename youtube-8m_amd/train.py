@@ -246,9 +246,10 @@ class TrainGraph(object):
         # learning-rate staircase still counts batch_size examples per step (:303-307), whatever the augmenter made of the batch.
         model_input_raw, labels_batch, num_frames, transformed = self._augment(model_input_raw, labels_batch, num_frames, weights, distill)
         # (the fused mixing + loss of MoeModel is this build's addition: it must not pre-empt weights / distillation)
-        # and it computes exactly CrossEntropyLoss: any other configured loss (TrainGraph(label_loss_fn=...), multitask) wins
+        # and it computes exactly CrossEntropyLoss: any other configured loss (TrainGraph(label_loss_fn=...), multitask,
+        # --loss_function) wins
         fuse = (weights is None and distill is None and not self.multitask
-                and type(self.label_loss_fn) is losses.CrossEntropyLoss)
+                and type(self.label_loss_fn) is losses.CrossEntropyLoss and FLAGS.loss_function is None)
         # a model trained on its prediction_frames (Z/train.py:359-379) is told that this forward pass feeds a training step (only such a
         # model: subclasses' forward() keep their signature)
         frames_kw = {"train_step": True} if getattr(self.model, "trains_on_prediction_frames", False) else {}
