@@ -8,57 +8,19 @@ The library is replaced by a recorder: every call is noted with its arguments an
 Everything here holds for the wrappers as they were before they shared one marshaller (same names, same recorded calls) -- the proof
 that the marshalling did not change -- except the tests whose docstrings say how they differ: the two new rejections (`*_new_rejection`),
 bf16-NT groups of more than four, and the allocator's own test (a new name)."""
-import ctypes
-
 import pytest
 import torch
 
 import yt8m_amd._lib as _lib
 import yt8m_amd.ops as ops
+from library_recorder import install
 
 REAL_DEV = ops._dev
-HOST_QUERIES = ("yt8m_x3_image_bytes", "yt8m_moe_mix_bwd_bf16_partial_rows")
-FIELDS = ("M", "N", "K", "A", "lda", "B", "ldb", "C", "ldc", "bias", "beta")
-
-
-def _plain(a):
-    """A ctypes argument as plain Python values, taken when the call is made."""
-    if isinstance(a, ctypes.Array):
-        if a._type_ is _lib.GemmProblem:
-            return [{f: getattr(p, f) for f in FIELDS} for p in a]
-        return [getattr(v, "value", v) for v in a]
-    if isinstance(a, ctypes.c_void_p):
-        return a.value
-    return a
-
-
-class Recorder(object):
-    def __init__(self, real, log):
-        self._real, self.log = real, log
-
-    def __getattr__(self, name):
-        if name in HOST_QUERIES:
-            return getattr(self._real, name)
-
-        def call(*args):
-            self.log.append((name, [_plain(a) for a in args]))
-            return 0
-        return call
-
-    def calls(self, *names):
-        return [(n, a) for n, a in self.log if n in names]
 
 
 @pytest.fixture()
 def rec(monkeypatch):
-    r = Recorder(_lib.lib(), [])
-    ws = torch.empty(64, dtype=torch.float32)
-    monkeypatch.setattr(_lib, "lib", lambda: r)
-    monkeypatch.setattr(ops, "_dev", lambda *ts: None)
-    monkeypatch.setattr(ops, "_stream", lambda: None)
-    monkeypatch.setattr(ops, "_workspace", lambda device: ws)
-    r.ws = ws
-    return r
+    return install(monkeypatch)
 
 
 def f32(*shape):
@@ -507,15 +469,12 @@ class _Var(object):
         self._log.append(("grad_done", self.name))
 
 
-class _Ctx(object):
-    needs_input_grad = (False,) * 9
-    images = None
-
-    def __init__(self, bf16):
-        self.bf16 = bf16
-
-
 B_, D_, NG, NE = 512, 4, 6, 4            # 512 even rows: what the bf16 forms ask of x
+
+
+def _plan(bf16, M=2):
+    """The head's plan at these shapes, no dx: fp32 -> the fp32 backward; bf16 -> the fused mixing backward (M = 2) or the casts (M = 3)."""
+    return ops._moe_head_plan(B_, D_, NG, NE, NE // 2, M, bf16, training=True, need_dx=False)
 
 
 def _head(rec, hook):
@@ -540,11 +499,11 @@ def _tail(rec, launch, Wg, We):
 
 
 FORMS = {
-    "fp32": (lambda x, Zg, Ze, Wg, We, be: ops._moe_head_param_grads(_Ctx(False), x, Zg, Ze, Wg, We, be), AUTO),
-    "bf16": (lambda x, Zg, Ze, Wg, We, be: ops._moe_head_param_grads(_Ctx(True), x, Zg, Ze, Wg, We, be), ("yt8m_gemm_bf16_nt_grouped",)),
-    "bf16_fused": (lambda x, Zg, Ze, Wg, We, be: ops._moe_head_bwd_bf16_fused(_Ctx(True), x, Zg, Ze, Wg, We, be, NE // 2, 2, dp=f32(B_, NE // 2)),
+    "fp32": (lambda x, Zg, Ze, Wg, We, be: ops._moe_head_param_grads(_plan(False), x, Zg, Ze, Wg, We, be), AUTO),
+    "bf16": (lambda x, Zg, Ze, Wg, We, be: ops._moe_head_param_grads(_plan(True, M=3), x, Zg, Ze, Wg, We, be), ("yt8m_gemm_bf16_nt_grouped",)),
+    "bf16_fused": (lambda x, Zg, Ze, Wg, We, be: ops._moe_head_bwd_bf16_fused(_plan(True), {}, x, Zg, Ze, Wg, We, be, NE // 2, 2, dp=f32(B_, NE // 2)),
                    ("yt8m_gemm_bf16_nt_grouped",)),
-    "bf16_images": (lambda x, Zg, Ze, Wg, We, be: ops._moe_head_bwd_bf16_images(_Ctx(True), x, Zg, Ze, Wg, We, be, NE // 2, 2, f32(B_, NE // 2),
+    "bf16_images": (lambda x, Zg, Ze, Wg, We, be: ops._moe_head_bwd_bf16_images(_plan(True), {}, x, Zg, Ze, Wg, We, be, NE // 2, 2, f32(B_, NE // 2),
                                                                                    None, 0, 1.0, None), ("yt8m_gemm_b1_nt_grouped",)),
 }
 
@@ -566,9 +525,9 @@ def test_moe_head_weight_gradient_tail_order(rec, form):
 def test_moe_head_tail_without_gradient_slots(rec):
     x, Zg, Ze, Wg, We, be = _head(rec, None)
     Wg.grad = None                                                   # frozen gate weights: no product, no grad_done for either matrix
-    ops._moe_head_param_grads(_Ctx(False), x, Zg, Ze, Wg, We, be)
+    ops._moe_head_param_grads(_plan(False), x, Zg, Ze, Wg, We, be)
     assert [e for e in rec.log if e[0] in AUTO + ("grad_done",)] == [("grad_done", "be")]
     rec.log.clear()
     be.grad = None
-    ops._moe_head_param_grads(_Ctx(False), x, Zg, Ze, Wg, We, be)
+    ops._moe_head_param_grads(_plan(False), x, Zg, Ze, Wg, We, be)
     assert not [e for e in rec.log if e[0] in AUTO + ("grad_done", "yt8m_colsum_f32")]

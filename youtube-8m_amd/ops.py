@@ -11,6 +11,7 @@ variable's slice of the gradient arena (GEMM beta = 0 on first write, 1 afterwar
 it.  A dummy requires-grad scalar (``graph.token``) is threaded through every op so that backward runs
 even when the op's data input is plain data (first layer).
 """
+import collections
 import ctypes
 import os
 
@@ -2195,50 +2196,112 @@ def ens_mix(x, a):
     return _EnsMix.apply(x, a)
 
 
+class _HeadPlan(collections.namedtuple("_HeadPlan", "logits z16 backward dx_bf16 dx k0 absmax need_dx")):
+    """The forms one call of the MoE head runs its three products in -- logits, dx, dW --, chosen once, in the forward pass
+    (_moe_head_plan), from shapes, dtypes, flags and the module's knobs; the backward passes dispatch on these fields alone.
+    logits: "b1_keep" (one-plane bf16 operand images whose pass writes the OTHER orientation of x / Wg / We too -- what the backward
+            products read (x^T for dW, W for dx) --, so each tensor is read once per step), "b1" (those images, one orientation),
+            "bf16_nt" (bf16 casts, both sides K-contiguous), "h2" (fp32 operands under the declared h2 role: three f16 products under one
+            scale per operand matrix, max |x| measured once -- the weight gradient's split of x^T takes the same word) or "fp32".
+    z16:    the logits leave the b1 product as bf16 -- the bf16 configuration's own precision -- because everything behind them reads
+            bf16: the bf16-logit mixing pass (M == 2, V % 4 == 0) and, when a backward pass follows, the image form of the fused mixing
+            backward writing into both gradient slots.  Halves the 773 MB a [8192, 5 x 4716] stage of configs[4] writes and the two
+            passes behind it read.  Opt-in: see Z16_LOGITS.
+    backward: None (no backward pass follows), "fused_images" (bf16, M == 2: ONE pass over the logits writes dL/dZ straight into the
+            one-plane images of both orientations; three image products), "fused_rows" (the same pass onto row-major bf16; three bf16
+            products), "casts" (mixing backward in place, then bf16 casts of dZ; dx_bf16: dx as a bf16 product too -- not with an odd
+            V (M + 1) or V M, a reduction length that cannot be packed in bf16 pairs) or "fp32" (in place, then fp32 products).
+    dx:     of the "fp32" backward when the input takes a gradient (need_dx), else None: "h2_rows" (row-scaled three-f16-product form
+            from column k0 on), "window" (the columns [k0:) on the generic product) or "plain"; k0: moe_head's dx_from where it is a
+            whole 32-row group of the weights' images inside D, else 0.
+    absmax: moe_head_xent's in-place mixing backward measures max |dZ| for the dW products' h2 split (MIX_BWD_ABSMAX)."""
+    __slots__ = ()
+
+    def __new__(cls, **fields):
+        plan = super(_HeadPlan, cls).__new__(cls, **fields)
+        assert not plan.z16 or plan.backward in (None, "fused_images"), "bf16 logits: only the image form of the fused mixing backward reads them"
+        return plan
+
+
+def _moe_head_plan(B, D, Ng, Ne, V, M, bf16, training, need_dx, dx_from=0, z16_allowed=False, w_contiguous=True, grad_slots=True):
+    """The _HeadPlan of x [B, D] against Wg [D, Ng] and We [D, Ne]: the ONE place where the head's forms are chosen (the table is pinned
+    by tests/test_moe_head_plan_host.py).  Plain integers and booleans only; the knobs are read when it is called.  training: a backward
+    pass may follow; z16_allowed: the op's mixing pass reads bf16 logits; w_contiguous: both weight matrices are; grad_slots: both have a
+    gradient slot."""
+    # bf16 GEMMs need even reduction lengths (D for the forward, the batch for dW) and enough rows to amortise the per-step cast of the weights
+    b16 = bf16 and B % 2 == 0 and D % 2 == 0 and B >= BF16_MIN_ROWS
+    b1_fwd, b1_bwd = b16 and _b1_ok(B, Ng, D), _b1_ok(D, Ng, B)
+    pairs = Ng % 2 == 0 and Ne % 2 == 0                 # dZ's reduction lengths pack in bf16 pairs
+    if not training:
+        backward = None
+    elif b16 and M == 2 and pairs:
+        backward = "fused_images" if (b1_fwd and b1_bwd) else "fused_rows"
+    else:
+        backward = "casts" if b16 else "fp32"
+    if b1_fwd:
+        logits = "b1_keep" if (M == 2 and training and b1_bwd) else "b1"
+    elif b16:
+        logits = "bf16_nt"
+    else:
+        # from MOE_LOGITS_H2_MIN_ROWS rows on: the weights' half-plane images are made per call (absmax + split of [D, 5V]), which a
+        # B = 128 product does not pay back (NetVLADModel at B = 128: 2.57 -> 2.88 ms/step with it; break-even by the split / product rates
+        # ~1 000 rows while the images were made per call; with them resident (wimg.py) 512 rows gain too: DeepCombineChain at B = 512
+        # 12.95 -> 12.03 ms/step; measured -6 % at 1 024, -7 % at 8 192)
+        logits = "h2" if (MOE_LOGITS_H2 and B >= MOE_LOGITS_H2_MIN_ROWS) else "fp32"
+    z16 = (z16_allowed and Z16_LOGITS and b1_fwd and M == 2 and V % 4 == 0 and Ng == 3 * V and Ne == 2 * V
+           and (backward is None or (backward == "fused_images" and grad_slots)))
+    dx, k0 = None, 0
+    if backward == "fp32" and need_dx:
+        k0 = dx_from if (MOE_DX_FROM and 0 < dx_from < D and dx_from % 32 == 0) else 0
+        # round 6: from 1 024 rows on, three f16 products with dZ split row by row against the weights' half-plane images (the form of
+        # ops._linear_dx_h2_rows) instead of the fp32-MFMA kernel these 16-tile, K ~ 14 000 products fell back to
+        h2_rows = MOE_DX_H2 and B >= MOE_LOGITS_H2_MIN_ROWS and D % 4 == 0 and w_contiguous
+        dx = "h2_rows" if h2_rows else "window" if k0 else "plain"
+    return _HeadPlan(logits=logits, z16=z16, backward=backward, dx_bf16=backward == "casts" and need_dx and pairs, dx=dx, k0=k0,
+                     absmax=MIX_BWD_ABSMAX and backward in ("casts", "fp32"), need_dx=need_dx)
+
+
 class _MoeHead(torch.autograd.Function):
     """MoE block of W/all_video_models/moe_model.py:40-64: two GEMMs + mixing kernel; backward per Appendix G."""
 
     @staticmethod
     def forward(ctx, x, token, Wg, We, be, V, M, bf16, dx_from=0):
-        x2, Zg, Ze = _moe_head_fwd(ctx, x, Wg, We, be, V, M, bf16, z16=True)
-        ctx.dx_from = dx_from
+        x2, Zg, Ze = _moe_head_fwd(ctx, x, Wg, We, be, V, M, bf16, dx_from=dx_from, z16=True)
         return moe_mix_fwd(Zg, Ze, V, M)
 
     @staticmethod
     def backward(ctx, dp):
-        (x,) = ctx.saved_tensors
-        Zg, Ze = ctx.Z
-        Wg, We, be = ctx.vars
-        V, M = ctx.VM
-        ctx.Z = None
-        if Zg.dtype == torch.bfloat16 and not (_fused_mix_bf16_ok(ctx, x, Zg, Ze, M) and _b1_ok(Zg.shape[0], Zg.shape[1], x.shape[1])
-                                               and _b1_ok(x.shape[1], Zg.shape[1], Zg.shape[0])):
-            Zg, Ze = Zg.float(), Ze.float()         # (not reached with _z16_ok's predicates; the fp32 passes below read fp32 logits)
-        if _fused_mix_bf16_ok(ctx, x, Zg, Ze, M):
-            dx = _moe_head_bwd_bf16_fused(ctx, x, Zg, Ze, Wg, We, be, V, M, dp=_f32c(dp))
+        plan, kept, x, Zg, Ze, Wg, We, be, V, M = _moe_head_saved(ctx)
+        if plan.backward in ("fused_images", "fused_rows"):
+            dx = _moe_head_bwd_bf16_fused(plan, kept, x, Zg, Ze, Wg, We, be, V, M, dp=_f32c(dp))
             return dx, None, None, None, None, None, None, None, None
         moe_mix_bwd_(Zg, Ze, dp, V, M)            # in place: Zg <- dL/dZg, Ze <- dL/dZe
-        dx = _moe_head_param_grads(ctx, x, Zg, Ze, Wg, We, be, xmax=(getattr(ctx, "words", None) or {}).get("x"))
+        dx = _moe_head_param_grads(plan, x, Zg, Ze, Wg, We, be, xmax=kept.get("xmax"))
         return dx, None, None, None, None, None, None, None, None
 
 
-FUSED_MIX_BF16 = True     # compute_dtype=bfloat16, M == 2: mixing backward writes the bf16 GEMM operands itself (csrc/moe_bf16.hip)
-
-
-def _moe_head_fwd(ctx, x, Wg, We, be, V, M, bf16, z16=False):
-    """What the two head ops' forward passes share: the logits (x2, Zg, Ze) and everything the backward forms read from ctx.
-    z16: the logits may leave the product as bf16 (_z16_ok)."""
+def _moe_head_fwd(ctx, x, Wg, We, be, V, M, bf16, dx_from=0, z16=False):
+    """What the two head ops' forward passes share: the plan, the logits (x2, Zg, Ze) and everything the backward forms read from ctx.
+    z16: the op's mixing pass reads bf16 logits."""
     x2 = _f32c(x)
-    ctx.images = {} if (bf16 and FUSED_MIX_BF16 and M == 2 and ctx.needs_input_grad[1]) else None
-    ctx.words = {}                                  # max |x| measured once: the weight gradient's split of x^T takes the same word
-    Zg, Ze = _moe_logits(x2, Wg, We, be, bf16, keep=ctx.images, z16=z16 and _z16_ok(x2, Wg, We, V, M, bf16, ctx.images is not None),
-                         words=ctx.words)
-    ctx.bf16 = bf16
+    ctx.plan = _moe_head_plan(x2.shape[0], x2.shape[1], Wg.data.shape[1], We.data.shape[1], V, M, bf16,
+                              training=ctx.needs_input_grad[0] or ctx.needs_input_grad[1], need_dx=ctx.needs_input_grad[0], dx_from=dx_from,
+                              z16_allowed=z16, w_contiguous=Wg.data.is_contiguous() and We.data.is_contiguous(),
+                              grad_slots=Wg.grad is not None and We.grad is not None)
+    ctx.kept = {}                # what the logits' form hands the backward: the images "xT" / "Wg" / "We" (b1_keep), the word "xmax" (h2)
+    Zg, Ze = _moe_logits(x2, Wg, We, be, ctx.plan, ctx.kept)
     ctx.save_for_backward(x2)
     ctx.Z = (Zg, Ze)
     ctx.vars = (Wg, We, be)
     ctx.VM = (V, M)
     return x2, Zg, Ze
+
+
+def _moe_head_saved(ctx):
+    """(plan, kept, x, Zg, Ze, Wg, We, be, V, M) of _moe_head_fwd; the logits and what was kept are released with the backward pass."""
+    saved = (ctx.plan, ctx.kept) + ctx.saved_tensors + ctx.Z + ctx.vars + ctx.VM
+    ctx.Z = ctx.kept = None
+    return saved
 
 
 def _moe_head_dw(product, pg, pe, Wg, We, be, bsrc, **kw):
@@ -2260,14 +2323,14 @@ def _moe_head_dw(product, pg, pe, Wg, We, be, bsrc, **kw):
         be.grad_done()
 
 
-def _moe_head_bwd_bf16_fused(ctx, x, Zg, Ze, Wg, We, be, V, M, dp=None, labels=None, ldt=0, dscale=1.0, up=None):
+def _moe_head_bwd_bf16_fused(plan, kept, x, Zg, Ze, Wg, We, be, V, M, dp=None, labels=None, ldt=0, dscale=1.0, up=None):
     """bf16 configuration: ONE pass over the fp32 logits produces dL/dZ as bf16 in both layouts + the bias partial sums, then
     the same three bf16 products as _moe_head_param_grads_bf16 (no fp32 dZ, no cast passes, no colsum over dZ_e)."""
     L = _lib.lib()
     B = Zg.shape[0]
     dev = Zg.device
-    if _b1_ok(B, Zg.shape[1], x.shape[1]) and _b1_ok(x.shape[1], Zg.shape[1], B):
-        return _moe_head_bwd_bf16_images(ctx, x, Zg, Ze, Wg, We, be, V, M, dp, labels, ldt, dscale, up)
+    if plan.backward == "fused_images":
+        return _moe_head_bwd_bf16_images(plan, kept, x, Zg, Ze, Wg, We, be, V, M, dp, labels, ldt, dscale, up)
     Zgb, ZgT = _bf16_empty(B, Zg.shape[1], dev), _bf16_empty(Zg.shape[1], B, dev)
     Zeb, ZeT = _bf16_empty(B, Ze.shape[1], dev), _bf16_empty(Ze.shape[1], B, dev)
     part = torch.empty((L.yt8m_moe_mix_bwd_bf16_partial_rows(B), Ze.shape[1]), dtype=torch.float32, device=dev) \
@@ -2276,7 +2339,7 @@ def _moe_head_bwd_bf16_fused(ctx, x, Zg, Ze, Wg, We, be, V, M, dp=None, labels=N
                                        _p(Zgb), Zgb.stride(0), _p(ZgT), ZgT.stride(0), _p(Zeb), Zeb.stride(0), _p(ZeT),
                                        ZeT.stride(0), _p(part), _stream()))
     dx = None
-    if ctx.needs_input_grad[0]:
+    if plan.need_dx:
         dx, = gemm_bf16_nt_grouped([dict(A=Zgb, B=cast_bf16(Wg.data))])
         gemm_bf16_nt_grouped([dict(A=Zeb, B=cast_bf16(We.data), out=dx, beta=1.0)])
     del Zgb, Zeb
@@ -2289,9 +2352,10 @@ def _moe_head_bwd_bf16_fused(ctx, x, Zg, Ze, Wg, We, be, V, M, dp=None, labels=N
     return dx
 
 
-def _moe_head_bwd_bf16_images(ctx, x, Zg, Ze, Wg, We, be, V, M, dp, labels, ldt, dscale, up):
+def _moe_head_bwd_bf16_images(plan, kept, x, Zg, Ze, Wg, We, be, V, M, dp, labels, ldt, dscale, up):
     """_moe_head_bwd_bf16_fused on operand images: the mixing backward writes dL/dZ straight into the one-plane images the b1
-    kernel reads (both orientations), the weights and x^T are rounded into images by one pass each; three image products."""
+    kernel reads (both orientations), the weights and x^T are rounded into images by one pass each unless the forward's image
+    passes kept them (`kept`); three image products."""
     L = _lib.lib()
     B, Ng, Ne = Zg.shape[0], Zg.shape[1], Ze.shape[1]
     dev = Zg.device
@@ -2301,10 +2365,8 @@ def _moe_head_bwd_bf16_images(ctx, x, Zg, Ze, Wg, We, be, V, M, dp, labels, ldt,
     mix = L.yt8m_moe_mix_bwd_bf16_images_z16 if Zg.dtype == torch.bfloat16 else L.yt8m_moe_mix_bwd_bf16_images
     _lib.check(mix(_p(Zg), _p(Ze), _p(dp), _p(labels), ldt, B, V, M, XENT_EPS, float(dscale), _p(up),
                    _p(Zgi.buf), kb(Ng), _p(ZgTi.buf), kb(B), _p(Zei.buf), kb(Ne), _p(ZeTi.buf), kb(B), _p(part), _stream()))
-    kept = getattr(ctx, "images", None) or {}                                   # written by the forward's image passes
-    ctx.images = None
     dx = None
-    if ctx.needs_input_grad[0]:
+    if plan.need_dx:
         dx, = gemm_b1_grouped([dict(A=Zgi, B=kept.get("Wg") or bf16_image(Wg.data))])           # W [D, N] as [D rows, K = N]
         gemm_b1_grouped([dict(A=Zei, B=kept.get("We") or bf16_image(We.data), out=dx, beta=1.0)])
     del Zgi, Zei
@@ -2315,17 +2377,6 @@ def _moe_head_bwd_bf16_images(ctx, x, Zg, Ze, Wg, We, be, V, M, dp, labels, ldt,
         pe = dict(A=xT, B=ZeTi, out=We.grad, beta=We.grad_beta())
     _moe_head_dw(gemm_b1_grouped, pg, pe, Wg, We, be, part)
     return dx
-
-
-def _fused_mix_bf16_ok(ctx, x, Zg, Ze, M):
-    return (FUSED_MIX_BF16 and getattr(ctx, "bf16", False) and M == 2 and _bf16_ok(x) and Zg.shape[1] % 2 == 0
-            and Ze.shape[1] % 2 == 0 and Zg.is_contiguous() and Ze.is_contiguous())
-
-
-def _bf16_ok(x2):
-    """bf16 GEMMs need even reduction lengths (D for the forward, the batch for dW) and enough rows to amortise the
-    per-step cast of the weights (see BF16_MIN_ROWS)."""
-    return x2.shape[0] % 2 == 0 and x2.shape[1] % 2 == 0 and x2.shape[0] >= BF16_MIN_ROWS
 
 
 # OPT-IN (YT8M_Z16_LOGITS=1): configs[4] at B = 1024 19.88 / 19.71 -> 19.25 / 19.19 ms/step (-3 %), but the full-size golden replay of the same
@@ -2345,50 +2396,28 @@ MOE_DX_FROM = os.environ.get("YT8M_MOE_DX_FROM", "1") != "0"           # chain m
 MIX_BWD_ABSMAX = os.environ.get("YT8M_MIX_BWD_ABSMAX", "1") != "0"     # the mixing backward measures max |dZ| for the dW products' h2 split
 
 
-def _z16_ok(x2, Wg, We, V, M, bf16, training):
-    """Round 6: in the bf16 configuration the head's logits leave the product as bf16 -- the configuration's own
-    precision -- when everything behind them reads bf16: the bf16-logit mixing pass (M == 2, B V % 4 == 0, V % 4 == 0) and, in training,
-    the image form of the fused mixing backward (same predicates as _moe_head_bwd_bf16_fused takes).  Halves the 773 MB a [8192, 5 x 4716]
-    stage of configs[4] writes and the two passes behind it read.  Opt-in: see Z16_LOGITS."""
-    B, D = x2.shape
-    Ng = Wg.data.shape[1]
-    if not (Z16_LOGITS and bf16 and M == 2 and _bf16_ok(x2) and V % 4 == 0 and Ng == 3 * V and We.data.shape[1] == 2 * V):
-        return False
-    if not _b1_ok(B, Ng, D):
-        return False
-    if training and not (FUSED_MIX_BF16 and _b1_ok(D, Ng, B) and Wg.grad is not None and We.grad is not None):
-        return False
-    return True
-
-
-def _moe_logits(x2, Wg, We, be, bf16, keep=None, z16=False, words=None):
-    """Zg = x.Wg, Ze = x.We + be as ONE persistent launch; bf16: operands are bf16 copies (x, Wg^T, We^T: both sides
-    K-contiguous), accumulation and outputs stay fp32.  keep (a dict, training only): the image pass of x / Wg / We writes the
-    OTHER orientation too -- what the backward products read (x^T for dW, W for dx) -- so each tensor is read once per step."""
-    if bf16 and _bf16_ok(x2) and _b1_ok(x2.shape[0], Wg.data.shape[1], x2.shape[1]):
-        odt = torch.bfloat16 if z16 else torch.float32
-        if keep is not None and _b1_ok(x2.shape[1], Wg.data.shape[1], x2.shape[0]):
-            xi, keep["xT"] = bf16_image(x2, both=True)
-            keep["Wg"], WgT = bf16_image(Wg.data, both=True)
-            keep["We"], WeT = bf16_image(We.data, both=True)
-            return gemm_b1_grouped([dict(A=xi, B=WgT, out_dtype=odt), dict(A=xi, B=WeT, bias=be.data, out_dtype=odt)])
-        xi = bf16_image(x2)                                  # [B rows, K = D]; W^T as [N rows, K = D]: the transposing image pass
-        return gemm_b1_grouped([dict(A=xi, B=bf16_image(Wg.data, transpose=True), out_dtype=odt),
-                                dict(A=xi, B=bf16_image(We.data, transpose=True), bias=be.data, out_dtype=odt)])
-    if bf16 and _bf16_ok(x2):
+def _moe_logits(x2, Wg, We, be, plan, kept):
+    """Zg = x.Wg, Ze = x.We + be as ONE persistent launch in the plan's form (_HeadPlan.logits); bf16 forms: accumulation stays fp32 and
+    so do the outputs unless plan.z16.  kept: receives what the form hands the backward pass."""
+    if plan.logits in ("b1_keep", "b1"):
+        odt = torch.bfloat16 if plan.z16 else torch.float32
+        if plan.logits == "b1_keep":
+            xi, kept["xT"] = bf16_image(x2, both=True)
+            kept["Wg"], WgT = bf16_image(Wg.data, both=True)
+            kept["We"], WeT = bf16_image(We.data, both=True)
+        else:                                                # [B rows, K = D]; W^T as [N rows, K = D]: the transposing image pass
+            xi, WgT, WeT = bf16_image(x2), bf16_image(Wg.data, transpose=True), bf16_image(We.data, transpose=True)
+        return gemm_b1_grouped([dict(A=xi, B=WgT, out_dtype=odt), dict(A=xi, B=WeT, bias=be.data, out_dtype=odt)])
+    if plan.logits == "bf16_nt":
         xb = cast_bf16(x2)
         return gemm_bf16_nt_grouped([dict(A=xb, B=cast_bf16(Wg.data, transpose=True)),
                                      dict(A=xb, B=cast_bf16(We.data, transpose=True), bias=be.data)])
-    # fp32 configuration: the logits product declares the h2 role (three f16 products under one scale per operand matrix) -- its input is
-    # l2-normalised or a bounded hidden activation, each operand one weight matrix (MOE_LOGITS_H2 / YT8M_MOE_LOGITS_H2=0: six-product form)
-    # -- from MOE_LOGITS_H2_MIN_ROWS rows on: the weights' half-plane images are made per call (absmax + split of [D, 5V]), which a
-    # B = 128 product does not pay back (NetVLADModel at B = 128: 2.57 -> 2.88 ms/step with it; break-even by the split / product rates
-    # ~1 000 rows while the images were made per call; with them resident (wimg.py) 512 rows gain too: DeepCombineChain at B = 512
-    # 12.95 -> 12.03 ms/step; measured -6 % at 1 024, -7 % at 8 192)
-    h2 = MOE_LOGITS_H2 and x2.shape[0] >= MOE_LOGITS_H2_MIN_ROWS
-    xmax = h2_absmax(x2).view(torch.float32) if (h2 and words is not None) else None      # measured once: the weight gradient's split of
-    if xmax is not None:                                                                  # x^T takes the same word (words["x"])
-        words["x"] = xmax
+    # fp32 configuration: the logits product declares the h2 role -- its input is l2-normalised or a bounded hidden activation, each operand
+    # one weight matrix (MOE_LOGITS_H2 / YT8M_MOE_LOGITS_H2=0: six-product form)
+    h2 = plan.logits == "h2"
+    if h2:
+        kept["xmax"] = h2_absmax(x2).view(torch.float32)
+    xmax = kept.get("xmax")
     return gemm_grouped([dict(A=x2, B=Wg.data, absmaxA=xmax), dict(A=x2, B=We.data, bias=be.data, absmaxA=xmax)], role="h2" if h2 else None)
 
 
@@ -2415,39 +2444,34 @@ class _MoeHeadXent(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dp_unused, dloss):
-        (x,) = ctx.saved_tensors
-        Zg, Ze = ctx.Z
-        Wg, We, be = ctx.vars
+        plan, kept, x, Zg, Ze, Wg, We, be, V, M = _moe_head_saved(ctx)
         lab, ldt = ctx.lab
-        V, M = ctx.VM
-        ctx.Z = None
         if dloss is None:
             return (None,) * 9
-        if _fused_mix_bf16_ok(ctx, x, Zg, Ze, M):
-            dx = _moe_head_bwd_bf16_fused(ctx, x, Zg, Ze, Wg, We, be, V, M, labels=lab, ldt=ldt, dscale=1.0 / x.shape[0],
+        if plan.backward in ("fused_images", "fused_rows"):
+            dx = _moe_head_bwd_bf16_fused(plan, kept, x, Zg, Ze, Wg, We, be, V, M, labels=lab, ldt=ldt, dscale=1.0 / x.shape[0],
                                           up=_f32c(dloss.reshape(1)))
             return dx, None, None, None, None, None, None, None, None
         zmax = None
-        if MIX_BWD_ABSMAX:
+        if plan.absmax:
             zmax = torch.empty(2, dtype=torch.float32, device=Zg.device)  # max |dZg|, max |dZe| as float bits, written by the same pass
             _lib.check(_lib.lib().yt8m_moe_mix_xent_bwd_absmax(_p(Zg), _p(Ze), _p(lab), ldt, _p(_f32c(dloss.reshape(1))), x.shape[0], V, M,
                                                                XENT_EPS, 1.0, _p(zmax), _stream()))
         else:
             _lib.check(_lib.lib().yt8m_moe_mix_xent_bwd(_p(Zg), _p(Ze), _p(lab), ldt, _p(_f32c(dloss.reshape(1))), x.shape[0], V, M,
                                                         XENT_EPS, 1.0, _stream()))
-        dx = _moe_head_param_grads(ctx, x, Zg, Ze, Wg, We, be, zmax=zmax, xmax=ctx.words.get("x"))
+        dx = _moe_head_param_grads(plan, x, Zg, Ze, Wg, We, be, zmax=zmax, xmax=kept.get("xmax"))
         return dx, None, None, None, None, None, None, None, None
 
 
-def _moe_head_param_grads_bf16(ctx, x, Zg, Ze, Wg, We, be):
+def _moe_head_param_grads_bf16(plan, x, Zg, Ze, Wg, We, be):
     """Same gradients on bf16 MFMAs: every product is written as A.B^T with K-contiguous bf16 copies
     (dW = x^T.dZ = (x^T) . (dZ^T)^T, dx = dZ . (W)^T with W [D,N] itself K-contiguous over N)."""
     dx = None
     need_dw = Wg.grad is not None and We.grad is not None
-    dx_bf16 = ctx.needs_input_grad[0] and Zg.shape[1] % 2 == 0 and Ze.shape[1] % 2 == 0
     ZgT = ZeT = None
-    if ctx.needs_input_grad[0]:
-        if dx_bf16:
+    if plan.need_dx:
+        if plan.dx_bf16:
             # dZ is needed K-contiguous for dx and row-transposed for dW: both layouts from one pass over the fp32 logits
             Zgb, ZgT = cast_bf16_both(Zg) if need_dw else (cast_bf16(Zg), None)
             Zeb, ZeT = cast_bf16_both(Ze) if need_dw else (cast_bf16(Ze), None)
@@ -2494,31 +2518,26 @@ def join_side_work(graph):
     graph.side_pending = []
 
 
-def _moe_head_param_grads(ctx, x, Zg, Ze, Wg, We, be, zmax=None, xmax=None):
+def _moe_head_param_grads(plan, x, Zg, Ze, Wg, We, be, zmax=None, xmax=None):
     """dW_g = x^T dZ_g, dW_e = x^T dZ_e, db_e = colsum(dZ_e), dx = dZ_g W_g^T + dZ_e W_e^T.
     zmax (a [2] float tensor, optional): max |dZ_g|, max |dZ_e| as float bits, already measured by the pass that wrote them."""
     mg = zmax[0:1] if zmax is not None else None
     me = zmax[1:2] if zmax is not None else None
-    if getattr(ctx, "bf16", False) and _bf16_ok(x):
-        return _moe_head_param_grads_bf16(ctx, x, Zg, Ze, Wg, We, be)
-    dx = None
-    if ctx.needs_input_grad[0]:                    # before the weights' gradient slots are released to an optimiser
-        # columns [0, k0) of x are data (moe_head's dx_from): no gradient is computed for them -- k0 on a 32-row group of the weights' images
-        k0 = int(getattr(ctx, "dx_from", 0) or 0)
-        k0 = k0 if (MOE_DX_FROM and 0 < k0 < Wg.data.shape[0] and k0 % 32 == 0) else 0
-        if (MOE_DX_H2 and Zg.shape[0] >= MOE_LOGITS_H2_MIN_ROWS and Wg.data.shape[0] % 4 == 0 and Wg.data.is_contiguous()
-                and We.data.is_contiguous() and Zg.is_contiguous() and Ze.is_contiguous()):
-            # round 6: from 1 024 rows on, three f16 products with dZ split row by row against the weights' half-plane images (the form of
-            # ops._linear_dx_h2_rows) instead of the fp32-MFMA kernel these 16-tile, K ~ 14 000 products fell back to
-            dx = _linear_dx_h2_rows(Zg, Wg, row0=k0)
-            _linear_dx_h2_rows(Ze, We, out=dx, beta=1.0, row0=k0)
-        elif k0:
-            dx = torch.zeros((Zg.shape[0], Wg.data.shape[0]), dtype=torch.float32, device=Zg.device)
-            gemm(Zg, Wg.data[k0:], transB=True, out=dx[:, k0:])
-            gemm(Ze, We.data[k0:], out=dx[:, k0:], transB=True, beta=1.0)
-        else:
-            dx = gemm(Zg, Wg.data, transB=True)
-            gemm(Ze, We.data, out=dx, transB=True, beta=1.0)
+    if plan.backward == "casts":
+        return _moe_head_param_grads_bf16(plan, x, Zg, Ze, Wg, We, be)
+    # dx before the weights' gradient slots are released to an optimiser.  Columns [0, k0) of x are data (moe_head's dx_from): no gradient is
+    # computed for them
+    k0, dx = plan.k0, None
+    if plan.dx == "h2_rows":
+        dx = _linear_dx_h2_rows(Zg, Wg, row0=k0)
+        _linear_dx_h2_rows(Ze, We, out=dx, beta=1.0, row0=k0)
+    elif plan.dx == "window":
+        dx = torch.zeros((Zg.shape[0], Wg.data.shape[0]), dtype=torch.float32, device=Zg.device)
+        gemm(Zg, Wg.data[k0:], transB=True, out=dx[:, k0:])
+        gemm(Ze, We.data[k0:], out=dx[:, k0:], transB=True, beta=1.0)
+    elif plan.dx == "plain":
+        dx = gemm(Zg, Wg.data, transB=True)
+        gemm(Ze, We.data, out=dx, transB=True, beta=1.0)
     side = side_stream(Wg._graph) if (dx is not None and Wg.grad is not None and We.grad is not None and be.grad is not None) else None
     if side is not None:
         # dx is on its way to the recurrent stack; the parameter gradients are read by the optimiser only: off the critical chain
