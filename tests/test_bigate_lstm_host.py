@@ -12,6 +12,7 @@ import torch
 
 import bigate_lstm_restatement as R
 import yt8m_amd._lib as L
+from cabi_helpers import declared_bound_exported
 from conftest import ROOT
 
 SYMBOLS = ("yt8m_gate_lstm_frames_supported", "yt8m_gate_lstm_frames_fwd", "yt8m_gate_lstm_frames_bwd")
@@ -31,16 +32,10 @@ def test_find_class_by_name_resolves_the_model():
 
 
 def test_library_exports_and_header_declares_the_frame_order_symbols():
-    src = open(os.path.join(ROOT, "include", "yt8m_hip.h")).read()
-    lib = L.lib()
-    for name in SYMBOLS:
-        assert re.search(r"\bint\s+%s\s*\(" % name, src), name
-        assert name in L.SIGNATURES
-        assert getattr(lib, name) is not None
+    src, lib = declared_bound_exported(SYMBOLS)
     assert "Z/frame_level_models.py:887-1158" in src and "yt8m_reverse_sequence_u8" in src
     assert L.ABI_VERSION == 4 and lib.yt8m_abi_version() == 4            # symbols were added, nothing else moved
-    for name in ("yt8m_gate_lstm_supported", "yt8m_gate_lstm_layer_fwd", "yt8m_gate_lstm_layer_bwd"):
-        assert name in L.SIGNATURES and getattr(lib, name) is not None   # the step-order entry points stay
+    declared_bound_exported(("yt8m_gate_lstm_supported", "yt8m_gate_lstm_layer_fwd", "yt8m_gate_lstm_layer_bwd"))   # the step-order entry points stay
 
 
 def test_supported_states_the_kernels_limits():

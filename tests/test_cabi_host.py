@@ -24,6 +24,195 @@ def test_header_and_binding_agree():
     assert set(names) == set(L.SIGNATURES), (set(names) ^ set(L.SIGNATURES))
 
 
+# ---- the parser that computes the binding from the header, on small snippets -----------------------------------------------------------
+c = ctypes
+
+
+def test_parser_maps_every_scalar_kind_by_value():
+    sigs, _, _ = L.parse_header("""
+        enum kind { KIND_A, KIND_B };
+        int64_t f(int a, int32_t b, unsigned c, uint32_t d, int64_t e, uint64_t g, float h, double i, enum kind k);
+        int g(void);  unsigned g2();  uint32_t g3(void);  uint64_t g4(void);  float g5(void);  double g6(void);  void g7(int a);
+    """)
+    assert sigs["f"] == (c.c_int64, [c.c_int, c.c_int32, c.c_uint, c.c_uint32, c.c_int64, c.c_uint64, c.c_float, c.c_double, c.c_int])
+    assert sigs["g"] == (c.c_int, []) and sigs["g2"] == (c.c_uint, []) and sigs["g3"] == (c.c_uint32, [])      # (void) and ()
+    assert sigs["g4"] == (c.c_uint64, []) and sigs["g5"] == (c.c_float, []) and sigs["g6"] == (c.c_double, [])
+    assert sigs["g7"] == (None, [c.c_int])
+    assert list(sigs) == ["f", "g", "g2", "g3", "g4", "g5", "g6", "g7"]
+
+
+def test_parser_pointer_rules():
+    sigs, structs, _ = L.parse_header("""
+        typedef void* stream_t;
+        typedef void (*hook_t)(void* user, stream_t stream);
+        typedef struct desc { int64_t n; } desc;
+        const char* name(void);
+        void* lookup(const float* src);
+        int f(const desc* d, desc* out, const float* const* w, float* const* dw, float** view, void** handle, stream_t* streams,
+              const char* const* paths, char** ids, const char* path, char* buf, const uint8_t* q, int32_t* n, const void* lo,
+              hook_t hook, stream_t stream, int64_t* count, double* ms);
+    """)
+    D = c.POINTER(structs["desc"])
+    assert sigs["name"] == (c.c_char_p, [])                              # a returned string
+    assert sigs["lookup"] == (L.P, [L.P])
+    assert sigs["f"] == (c.c_int, [D, D,                                 # pointers to one of the header's structs
+                                   L.PP, L.PP, L.PP, L.PP, L.PP,         # pointers to pointers, a pointer to the stream typedef included
+                                   c.POINTER(c.c_char_p),                # an array of strings
+                                   L.PP,                                 # char**: buffers, not strings
+                                   L.P, L.P,                             # const char* may be a path or a byte buffer: the type cannot tell
+                                   L.P, L.P, L.P, L.P, L.P, L.P, L.P])   # every remaining pointer, the hook and the stream typedefs
+    assert L.P is c.c_void_p and L.PP is c.POINTER(c.c_void_p)
+
+
+def test_parser_reads_declarations_over_lines_and_through_comments():
+    sigs, _, consts = L.parse_header("""
+        /* a comment that holds a declaration: int ghost(int a); */
+        #ifndef GUARD_H
+        #define GUARD_H
+        #include <stdint.h>
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        int64_t
+        spread(int64_t rows,   /* the rows; and a semicolon */
+               const float* x,  // one per row, (really)
+               float scale
+              );
+        #ifdef __cplusplus
+        }
+        #endif
+        #endif /* GUARD_H */
+    """)
+    assert sigs == {"spread": (c.c_int64, [c.c_int64, L.P, c.c_float])} and consts == {}
+
+
+def test_parser_struct_members():
+    _, structs, _ = L.parse_header("""
+        typedef void* stream_t;
+        typedef struct inner { void* plain; int64_t row0, rows; float scale; int32_t planes; } inner;
+        typedef struct outer {
+          int64_t M, N, K;                 /* several declarators */
+          const void* A; int64_t lda;      /* two members on a line */
+          uint64_t seed[8];
+          int32_t lo[4], hi[4];
+          const inner* jobs;               /* pointer members are untyped */
+          stream_t after;
+          inner spec[2];                   /* a nested struct array */
+          float *a, b;
+        } outer;
+    """, {"outer": "Outer"})
+    inner, outer = structs["inner"], structs["outer"]
+    assert (inner.__name__, outer.__name__) == ("inner", "Outer") and issubclass(outer, c.Structure)
+    assert inner._fields_ == [("plain", L.P), ("row0", c.c_int64), ("rows", c.c_int64), ("scale", c.c_float), ("planes", c.c_int32)]
+    assert outer._fields_ == [("M", c.c_int64), ("N", c.c_int64), ("K", c.c_int64), ("A", L.P), ("lda", c.c_int64),
+                              ("seed", c.c_uint64 * 8), ("lo", c.c_int32 * 4), ("hi", c.c_int32 * 4), ("jobs", L.P), ("after", L.P),
+                              ("spec", inner * 2), ("a", L.P), ("b", c.c_float)]
+    assert c.sizeof(outer) == 24 + 16 + 64 + 32 + 16 + 2 * 32 + 16
+
+
+def test_parser_constants():
+    _, _, consts = L.parse_header("""
+        enum status { OK = 0, E_BADARG = -1, E_SHAPE = -2, };
+        enum counted { FIRST, SECOND, TENTH = 10, ELEVENTH };
+        enum mode { MODE_X = 0x1, MODE_Y = 0x8 };
+        #define ROLE_DW 0x100
+        #define STATS_FLOATS 20   /* floats */
+        #  define NEGATIVE -3
+        #define GUARD_H
+    """)
+    assert consts == {"OK": 0, "E_BADARG": -1, "E_SHAPE": -2, "FIRST": 0, "SECOND": 1, "TENTH": 10, "ELEVENTH": 11, "MODE_X": 1,
+                      "MODE_Y": 8, "ROLE_DW": 256, "STATS_FLOATS": 20, "NEGATIVE": -3}
+
+
+@pytest.mark.parametrize("text, named", [
+    ("int f(long n);", "long n"),                                        # an unknown type name is not an int
+    ("int f(int64_t n, size_t m);", "size_t m"),
+    ("int f(unsigned int n);", "unsigned int n"),
+    ("mystery f(int n);", "mystery"),
+    ("int f(thing* p);", "thing* p"),                                    # nor is a pointer to one a void*
+    ("int f(int64_t, float x);", "int64_t"),                             # an unnamed parameter
+    ("int f(int n, ...);", "..."),                                       # a variadic list
+    ("int f(float*** p);", "float*** p"),
+    ("int f(int a[4]);", "int a[4]"),
+    ("int f(void (*cb)(int), int n);", "cb"),
+    ("typedef struct s { int32_t flags : 3; } s;", "int32_t flags : 3"),     # a bit-field
+    ("typedef struct s { long n; } s;", "long n"),
+    ("typedef struct s { int64_t n[]; } s;", "int64_t n[]"),
+    ("typedef struct s { struct t { int a; } inner; } s;", "struct s"),
+    ("typedef long long big_t;", "long long big_t"),
+    ("int global_counter;", "int global_counter"),
+    ("enum e { A = 1 << 3 };", "A = 1 << 3"),
+    ("#define WIDTH (1 << 3)", "(1 << 3)"),
+    ("int f(int n)", "int f(int n)"),                                    # no terminating semicolon
+])
+def test_parser_refuses_what_it_does_not_recognise(text, named):
+    with pytest.raises(L.Yt8mHipError) as e:
+        L.parse_header("int before(int n);\n" + text + "\nint after(int n);")
+    assert named in str(e.value), str(e.value)
+
+
+def test_missing_header_is_an_error(monkeypatch, tmp_path):
+    monkeypatch.setattr(L, "HEADER_PATH", str(tmp_path / "nope.h"))
+    with pytest.raises(L.Yt8mHipError, match="nope.h"):
+        L._read_header()
+
+
+def test_binding_is_the_header():
+    """The module-level names are the parse of the real header, the public aliases keep their meaning, and the constants the host
+    uses are the header's."""
+    import yt8m_amd.ops as ops
+    sigs, structs, consts = L.parse_header(open(os.path.join(ROOT, "include", "yt8m_hip.h")).read())
+    assert list(sigs) == list(L.SIGNATURES) and len(sigs) == 307 and consts == L.CONSTANTS
+    assert {n: (r, [getattr(a, "__name__", a) for a in args]) for n, (r, args) in sigs.items() if n != "yt8m_adam_tiles"} == \
+        {n: (r, [getattr(a, "__name__", a) for a in args]) for n, (r, args) in L.SIGNATURES.items() if n != "yt8m_adam_tiles"}
+    assert L.SIGNATURES["yt8m_adam_tiles"][1][4] is L.P and sigs["yt8m_adam_tiles"][1][4]._type_.__name__ == "WimgJob"   # a device address
+    assert set(structs) == set(L.STRUCTS) == set(L.STRUCT_NAMES)
+    for cname, pyname in L.STRUCT_NAMES.items():
+        assert getattr(L, pyname) is L.STRUCTS[cname] and getattr(L, pyname).__name__ == pyname
+    assert L.DESC is c.POINTER(L.LstmStackDesc) and L.SIGNATURES["yt8m_lstm_stack_supported"] == (c.c_int, [L.DESC])
+    assert L.SIGNATURES["yt8m_lstm_stack_set_prep_hook"] == (c.c_int, [L.P, L.P])
+    assert L.SIGNATURES["yt8m_last_error"] == (c.c_char_p, []) and L.SIGNATURES["yt8m_wimg_lookup"][0] is L.P
+    assert L.SIGNATURES["yt8m_crc32c"] == (c.c_uint32, [L.P, c.c_int64])
+    assert L.SIGNATURES["yt8m_prefetch_open"][1][0] == c.POINTER(c.c_char_p) and L.SIGNATURES["yt8m_prefetch_acquire"][1][4] is L.PP
+    assert L._STATUS == {-1: "YT8M_E_BADARG", -2: "YT8M_E_SHAPE", -3: "YT8M_E_HIP", -4: "YT8M_E_RCCL"}
+    assert (ops.GEMM_ROLE_DW, ops.GEMM_ROLE_H2, ops.BA_STATS_FLOATS, ops.XV_STATS_FLOATS) == (0x100, 0x200, 20, 16)
+    assert ops.XV_STATS == {"loss": 0, "pre": 1, "flag": 2, "pos": 3, "neg": 4}
+    assert L.ABI_VERSION == 4
+
+
+def _host_cc():
+    import shutil
+    for cc in ("cc", "gcc", "clang", "/opt/rocm/lib/llvm/bin/clang"):
+        path = shutil.which(cc)
+        if path:
+            return path
+    return None
+
+
+def test_struct_mirrors_have_the_compilers_layout(tmp_path):
+    """sizeof and every offsetof of the seven structs, as the host C compiler lays out include/yt8m_hip.h, against the ctypes mirrors."""
+    import subprocess
+    cc = _host_cc()
+    if cc is None:
+        pytest.skip("no host C compiler in this environment")
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "yt8m_hip.h"', 'int main(void) {']
+    want = {}
+    for cname, mirror in L.STRUCTS.items():
+        lines.append('  printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
+        want[cname] = c.sizeof(mirror)
+        for field, _ in mirror._fields_:
+            lines.append('  printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, field, cname, field))
+            want["%s.%s" % (cname, field)] = getattr(mirror, field).offset
+    lines += ['  return 0;', '}']
+    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
+    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", str(tmp_path / "layout"), str(tmp_path / "layout.c")],
+                   check=True, capture_output=True, text=True)
+    out = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout
+    got = {k: int(v) for k, v in (ln.split() for ln in out.splitlines())}
+    assert got == want, {k: (got.get(k), want.get(k)) for k in set(got) | set(want) if got.get(k) != want.get(k)}      # (compiler, mirror)
+    assert len(want) == 7 + 76
+
+
 def test_library_exports_every_declared_symbol():
     lib = L.lib()
     raw = ctypes.CDLL(L.LIB_PATH)

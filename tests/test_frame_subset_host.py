@@ -14,6 +14,7 @@ import torch
 
 import frame_subset_restatement as R
 import yt8m_amd._lib as L
+from cabi_helpers import declared_bound_exported
 from conftest import ROOT
 from gate_lstm_restatement import moe
 from oracle import torch_ref
@@ -112,12 +113,7 @@ def test_find_class_by_name_resolves_the_plugins(flags):
 
 
 def test_library_exports_and_header_declares_the_symbols():
-    src = open(os.path.join(ROOT, "include", "yt8m_hip.h")).read()
-    lib = L.lib()
-    for name in SYMBOLS:
-        assert re.search(r"\bint\s+%s\s*\(" % name, src), name
-        assert name in L.SIGNATURES
-        assert getattr(lib, name) is not None
+    src, lib = declared_bound_exported(SYMBOLS)
     assert "csrc/frame_subset.hip" in src
     assert L.ABI_VERSION == 4 and lib.yt8m_abi_version() == 4            # symbols were added, nothing else moved
 

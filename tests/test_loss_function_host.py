@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import loss_function_restatement as R
+from cabi_helpers import declared_bound_exported
 from conftest import ROOT
 
 E = 10e-6
@@ -180,11 +181,7 @@ def test_the_relabelled_kernel_cases_have_the_pre_they_are_known_by():
 def test_library_exports_and_header_declares_the_symbols():
     import yt8m_amd._lib as L
     import yt8m_amd.ops as ops
-    src = open(os.path.join(ROOT, "include", "yt8m_hip.h")).read()
-    lib = L.lib()
-    for name in SYMBOLS:
-        assert re.search(r"\bint(?:64_t)?\s+%s\s*\(" % name, src), name
-        assert name in L.SIGNATURES and getattr(lib, name) is not None
+    src, lib = declared_bound_exported(SYMBOLS, r"int(?:64_t)?")
     assert "Z/losses.py:64-168" in src
     assert L.ABI_VERSION == 4 and lib.yt8m_abi_version() == 4            # symbols were added, nothing else moved
     P_, i64, f, i = ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_int

@@ -15,6 +15,7 @@ import torch
 
 import lstm_layer_restatement as R
 import yt8m_amd._lib as L
+from cabi_helpers import declared_bound_exported
 from conftest import ROOT
 
 SYMBOLS = ("yt8m_lstm_wide_supported", "yt8m_lstm_wide_row_tile", "yt8m_lstm_wide_workspace_bytes", "yt8m_lstm_wide_prepare",
@@ -37,12 +38,7 @@ def test_lstm_length_flag(flags):
 
 
 def test_library_exports_and_header_declares_the_wide_symbols():
-    src = open(os.path.join(ROOT, "include", "yt8m_hip.h")).read()
-    lib = L.lib()
-    for name in SYMBOLS:
-        assert re.search(r"\bint(?:64_t)?\s+%s\s*\(" % name, src), name
-        assert name in L.SIGNATURES
-        assert getattr(lib, name) is not None
+    src, lib = declared_bound_exported(SYMBOLS, r"int(?:64_t)?")
     assert "Z/frame_level_models.py:3653-3668" in src
     assert L.ABI_VERSION == 4 and lib.yt8m_abi_version() == 4            # symbols were added, nothing else moved
 

@@ -18,6 +18,7 @@ import torch
 
 import mix_chain_restatement as R
 import yt8m_amd._lib as L
+from cabi_helpers import declared_bound_exported
 from conftest import ROOT
 
 SYMBOLS = ("yt8m_mix_link_supported", "yt8m_mix_link_fwd", "yt8m_mix_link_bwd")
@@ -56,11 +57,7 @@ def test_not_built_list_names_what_is_left():
 
 # ---- the C ABI on the host ------------------------------------------------------------------------------------------------------------
 def test_library_exports_and_header_declares_the_symbols():
-    src = open(os.path.join(ROOT, "include", "yt8m_hip.h")).read()
-    lib = L.lib()
-    for name in SYMBOLS:
-        assert re.search(r"\bint\s+%s\s*\(" % name, src), name
-        assert name in L.SIGNATURES and getattr(lib, name) is not None
+    src, lib = declared_bound_exported(SYMBOLS)
     assert "Z/video_level_models.py:1872-2044" in src
     assert L.ABI_VERSION == 4 and lib.yt8m_abi_version() == 4            # symbols were added, nothing else moved
 

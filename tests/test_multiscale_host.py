@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import yt8m_amd._lib as L
+from cabi_helpers import declared_bound_exported
 from conftest import ROOT
 
 KERNELS = ("yt8m_multiscale_workspace_bytes", "yt8m_colmoments_f32", "yt8m_bn_relu_pool2_tm_fwd", "yt8m_bn_relu_pool2_tm_bwd")
@@ -107,11 +108,8 @@ def test_distillchain_variable_names_and_assertion(monkeypatch):
 
 
 def test_header_declares_the_multiscale_kernels():
-    src = open(os.path.join(ROOT, "include", "yt8m_hip.h")).read()
-    for name in KERNELS:
-        assert re.search(r"\b(int|int64_t)\s+%s\s*\(" % name, src), name
-        assert name in L.SIGNATURES
-    assert L.lib().yt8m_abi_version() == 4                           # symbols were added, nothing else moved
+    _, lib = declared_bound_exported(KERNELS, r"(int|int64_t)")
+    assert lib.yt8m_abi_version() == 4                           # symbols were added, nothing else moved
 
 
 def test_multiscale_argument_validation_without_device():

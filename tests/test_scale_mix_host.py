@@ -17,6 +17,7 @@ import torch
 
 import scale_mix_restatement as R
 import yt8m_amd._lib as L
+from cabi_helpers import declared_bound_exported
 from conftest import ROOT
 
 SYMBOLS = ("yt8m_scale_mix_supported", "yt8m_scale_mix_fwd", "yt8m_scale_mix_bwd")
@@ -49,12 +50,7 @@ def test_not_built_list_names_what_is_left():
 
 # ---- the C ABI on the host ------------------------------------------------------------------------------------------------------------
 def test_library_exports_and_header_declares_the_scale_mix_symbols():
-    src = open(os.path.join(ROOT, "include", "yt8m_hip.h")).read()
-    lib = L.lib()
-    for name in SYMBOLS:
-        assert re.search(r"\bint\s+%s\s*\(" % name, src), name
-        assert name in L.SIGNATURES
-        assert getattr(lib, name) is not None
+    src, lib = declared_bound_exported(SYMBOLS)
     assert L.SIGNATURES["yt8m_scale_mix_supported"] == (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64])
     assert L.SIGNATURES["yt8m_scale_mix_fwd"] == (ctypes.c_int, [ctypes.c_int, L.PP, L.PP, L.P, ctypes.c_int64, ctypes.c_int64, L.P])
     assert L.SIGNATURES["yt8m_scale_mix_bwd"] == (ctypes.c_int, [ctypes.c_int, L.PP, L.PP, L.P, L.P, L.PP, L.PP, ctypes.c_int64,

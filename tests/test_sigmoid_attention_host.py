@@ -12,6 +12,7 @@ import torch
 
 import sigmoid_attention_restatement as R
 import yt8m_amd._lib as L
+from cabi_helpers import declared_bound_exported
 from conftest import ROOT
 
 SYMBOLS = ("yt8m_sigattn_supported", "yt8m_sigattn_workspace_bytes", "yt8m_sigattn_fwd", "yt8m_sigattn_bwd")
@@ -37,12 +38,7 @@ def test_attention_size_flag(flags):
 
 
 def test_library_exports_and_header_declares_the_symbols():
-    src = open(os.path.join(ROOT, "include", "yt8m_hip.h")).read()
-    lib = L.lib()
-    for name in SYMBOLS:
-        assert re.search(r"\b(int|int64_t)\s+%s\s*\(" % name, src), name
-        assert name in L.SIGNATURES
-        assert getattr(lib, name) is not None
+    src, lib = declared_bound_exported(SYMBOLS, r"(int|int64_t)")
     assert "lstm_attention_lstm_model.py:78-92" in src
     assert L.ABI_VERSION == 4 and lib.yt8m_abi_version() == 4            # symbols were added, nothing else moved
 

@@ -18,6 +18,7 @@ import torch
 
 import softmax_moe_restatement as R
 import yt8m_amd._lib as L
+from cabi_helpers import declared_bound_exported
 from conftest import ROOT
 
 SYMBOLS = ("yt8m_softmax_moe_supported", "yt8m_softmax_moe_resident", "yt8m_softmax_moe_fwd", "yt8m_softmax_moe_bwd",
@@ -51,11 +52,7 @@ def test_documents_say_where_the_model_is_built_and_what_is_left():
 
 # ---- the C ABI on the host ------------------------------------------------------------------------------------------------------------
 def test_library_exports_and_header_declares_the_symbols():
-    src = open(os.path.join(ROOT, "include", "yt8m_hip.h")).read()
-    lib = L.lib()
-    for name in SYMBOLS:
-        assert re.search(r"\bint(?:64_t)?\s+%s\s*\(" % name, src), name
-        assert name in L.SIGNATURES and getattr(lib, name) is not None
+    src, lib = declared_bound_exported(SYMBOLS, r"int(?:64_t)?")
     assert "Z/video_level_models.py:877-960" in src and "Z/losses.py:412-456" in src
     assert L.ABI_VERSION == 4 and lib.yt8m_abi_version() == 4            # symbols were added, nothing else moved
     P, i64, f, i = ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_int

@@ -1,413 +1,145 @@
-"""ctypes binding of libyt8m_hip.so (include/yt8m_hip.h).  Fails loudly when the library is missing:
-the product has no CPU / eager-PyTorch fallback for any hot op."""
+"""ctypes binding of libyt8m_hip.so, computed from include/yt8m_hip.h: the header is the contract, and the argument types, the struct
+mirrors and the constants below are what it declares.  Fails loudly when the library is missing (the product has no CPU /
+eager-PyTorch fallback for any hot op) and when the header holds anything the parser does not recognise (it never guesses a type)."""
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("YT8M_LIB", os.path.join(_HERE, "libyt8m_hip.so"))  # YT8M_LIB: A/B builds (tools/)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "yt8m_hip.h")
 
-c_void_p, c_int, c_int64, c_float, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
-P = c_void_p
-
-class GemmProblem(ctypes.Structure):
-    """yt8m_gemm_problem (include/yt8m_hip.h)."""
-    _fields_ = [("M", c_int64), ("N", c_int64), ("K", c_int64), ("A", c_void_p), ("lda", c_int64), ("B", c_void_p),
-                ("ldb", c_int64), ("C", c_void_p), ("ldc", c_int64), ("bias", c_void_p), ("beta", c_float)]
-
-
-STREAM_HOOK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p)       # yt8m_stream_hook
-
-
-class PersistBwdImages(ctypes.Structure):
-    """yt8m_persist_bwd_images (include/yt8m_hip.h): where yt8m_lstm_persist_bwd_images leaves the operand images of its dz."""
-    _fields_ = [("plain", ctypes.c_void_p), ("trans", ctypes.c_void_p), ("trans_scaled", ctypes.c_void_p), ("rowscale", ctypes.c_void_p),
-                ("colpart", ctypes.c_void_p), ("colpart_scaled", ctypes.c_void_p)]
+P = ctypes.c_void_p                # every pointer whose C type says no more: device memory, streams, handles, host out-parameters
+PP = ctypes.POINTER(P)             # pointer to pointers (arrays of device pointers, yt8m_stream_t*, void**)
+STREAM_HOOK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p)       # yt8m_stream_hook (bound as P: callers pass its address)
+STRUCT_NAMES = {"yt8m_gemm_problem": "GemmProblem", "yt8m_persist_bwd_images": "PersistBwdImages", "yt8m_lstm_stack_desc": "LstmStackDesc",
+                "yt8m_wimg_demand": "WimgDemand", "yt8m_wimg_spec": "WimgSpec", "yt8m_wimg_job": "WimgJob", "yt8m_opt_ranges": "OptRanges"}
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "unsigned": ctypes.c_uint, "uint32_t": ctypes.c_uint32,
+            "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "double": ctypes.c_double}
+_POINTEES = ("void", "char", "uint8_t")       # types the header only ever points at
 
 
-class LstmStackDesc(ctypes.Structure):
-    """yt8m_lstm_stack_desc (include/yt8m_hip.h)."""
-    _fields_ = [("B", c_int64), ("F", c_int64), ("D", c_int64), ("H", c_int64), ("L", ctypes.c_int32), ("input_u8", ctypes.c_int32),
-                ("forget_bias", c_float), ("fwd_chunks", ctypes.c_int32), ("bwd_chunks", ctypes.c_int32), ("need_dx", ctypes.c_int32),
-                ("input_keep_prob", c_float), ("reserved0", ctypes.c_int32), ("dropout_seed", ctypes.c_uint64 * 8)]      # ABI 4
+class Yt8mHipError(RuntimeError):
+    pass
 
 
-class WimgDemand(ctypes.Structure):
-    """yt8m_wimg_demand (include/yt8m_hip.h)."""
-    _fields_ = [("src", c_void_p), ("R", c_int64), ("C", c_int64), ("ld", c_int64), ("trans", ctypes.c_int32), ("planes", ctypes.c_int32),
-                ("scale", c_float), ("pad", ctypes.c_int32)]
+def _refuse(what, text):
+    raise Yt8mHipError("include/yt8m_hip.h: unrecognised %s: %r" % (what, " ".join(text.split())))
 
 
-class WimgSpec(ctypes.Structure):
-    """yt8m_wimg_spec (include/yt8m_hip.h)."""
-    _fields_ = [("plain", c_void_p), ("trans", c_void_p), ("row0", c_int64), ("rows", c_int64), ("scale", c_float),
-                ("planes", ctypes.c_int32)]
+def _int(text, what, context):
+    try:
+        return int(text, 0)
+    except ValueError:
+        _refuse(what, context)
 
 
-class WimgJob(ctypes.Structure):
-    """yt8m_wimg_job (include/yt8m_hip.h)."""
-    _fields_ = [("offset", c_int64), ("R", c_int64), ("C", c_int64), ("tensor", ctypes.c_int32), ("nspec", ctypes.c_int32),
-                ("tile_base", c_int64), ("spec", WimgSpec * 4)]
+_STATEMENT = re.compile(r"\s*(?:typedef\s+struct\s+(?P<struct>\w+)\s*\{(?P<members>[^{}]*)\}\s*(?P=struct)\s*;|enum\s+\w+\s*\{(?P<enum>[^{}]*)\}\s*;"
+                        r"|typedef\s+[^;{}()]+\(\s*\*\s*(?P<hook>\w+)\s*\)\s*\([^;{}()]*\)\s*;|typedef\s+(?P<typedef>[^;{}()]+);"
+                        r"|(?P<ret>[^;{}()]+?)\b(?P<function>\w+)\s*\((?P<params>[^;{}()]*)\)\s*;)")
+_SPECIFIER = re.compile(r"\s*((?:const\s+)?(?:enum\s+)?\w+)\s*(.*)", re.S)
+_DECLARATOR = re.compile(r"\s*((?:\*\s*(?:const\s*)?)*)(\w*)\s*(?:\[(\d+)\])?\s*")
 
 
-class OptRanges(ctypes.Structure):
-    """yt8m_opt_ranges (include/yt8m_hip.h)."""
-    _fields_ = [("w", c_void_p), ("m", c_void_p), ("v", c_void_p), ("g", c_void_p), ("chunks", c_void_p), ("tensor_chunk_start", c_void_p),
-                ("tensor_chunk_start_host", c_void_p), ("l2", c_void_p), ("partial", c_void_p), ("norms", c_void_p), ("skip_tensor", c_void_p),
-                ("jobs", c_void_p), ("job_tensor_host", c_void_p), ("job_tile_base_host", c_void_p), ("njobs", ctypes.c_int32),
-                ("nranges", ctypes.c_int32), ("range_lo", ctypes.c_int32 * 8), ("range_hi", ctypes.c_int32 * 8), ("gscale", c_float),
-                ("clip", c_float), ("lr_t", c_float), ("beta1", c_float), ("beta2", c_float), ("eps", c_float), ("after_stream", c_void_p)]
+def _declare(text, types, role, of):
+    """[(name, ctype)] of one C declaration `specifier declarator, ...` in the role "parameter", "member", "typedef" or "return type"
+    of the function, struct or typedef `of` (for the error text)."""
+    what = "%s of %s" % (role, of)
+    m = _SPECIFIER.fullmatch(text)
+    if not m:
+        _refuse(what, text)
+    spec = " ".join(m[1].split())
+    base = spec[6:] if spec.startswith("const ") else spec
+    t = ctypes.c_int if base.startswith("enum ") else types.get(base)
+    out = []
+    for declarator in m[2].split(","):
+        d = _DECLARATOR.fullmatch(declarator)
+        if not d or bool(d[2]) == (role == "return type") or (d[3] and role != "member"):
+            _refuse(what, text)
+        depth = d[1].count("*") + (t is P)        # a typedef of a pointer (yt8m_stream_t, yt8m_stream_hook) is one level itself
+        if t is None and not (depth and base in _POINTEES) and (spec, role, depth) != ("void", "return type", 0):
+            _refuse("type %r in %s" % (spec, what), text)
+        if depth > 2:
+            _refuse(what, text)
+        is_struct = isinstance(t, type) and issubclass(t, ctypes.Structure)
+        if depth == 2:
+            ct = ctypes.POINTER(ctypes.c_char_p) if spec == "const char" else PP
+        elif depth == 1:
+            ct = ctypes.c_char_p if (spec, role) == ("const char", "return type") else \
+                ctypes.POINTER(t) if is_struct and role != "member" else P
+        else:
+            ct = t
+        out.append((d[2], ct * int(d[3]) if d[3] else ct))
+    return out
 
 
-DESC = ctypes.POINTER(LstmStackDesc)
-PP = ctypes.POINTER(c_void_p)      # array of device pointers
+def parse_header(text, struct_names=STRUCT_NAMES):
+    """(signatures, structs, constants) of a C header in the dialect of include/yt8m_hip.h.  signatures: function name -> (restype,
+    [argtypes]); structs: C struct name -> ctypes.Structure mirror; constants: enumerators and integer #defines.  Raises Yt8mHipError,
+    naming the text, for anything it does not recognise."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    signatures, structs, constants, types, body, cplusplus = {}, {}, {}, dict(_SCALARS), [], False
+    for line in text.splitlines():
+        m = re.match(r"\s*#\s*(\w+)\s*(.*)", line)
+        if not m:
+            body.append("" if cplusplus else line)
+            continue
+        cplusplus = (m[1], m[2].strip()) == ("ifdef", "__cplusplus") or (cplusplus and m[1] != "endif")
+        define = re.fullmatch(r"(\w+)\s+(\S.*?)\s*", m[2]) if m[1] == "define" else None
+        if define:
+            constants[define[1]] = _int(define[2], "#define", line)
+    text, pos = "\n".join(body), 0
+    while text[pos:].strip():
+        m = _STATEMENT.match(text, pos)
+        if not m:
+            _refuse("declaration", text[pos:].strip().split(";")[0])
+        pos = m.end()
+        if m["struct"]:
+            fields = [f for member in m["members"].split(";") if member.strip() for f in _declare(member, types, "member", m["struct"])]
+            name = struct_names.get(m["struct"], m["struct"])
+            types[m["struct"]] = structs[m["struct"]] = type(name, (ctypes.Structure,), {
+                "_fields_": fields, "__doc__": "%s (include/yt8m_hip.h)." % m["struct"]})
+        elif m["enum"] is not None:
+            value = -1
+            for e in m["enum"].split(","):
+                name, _, given = (s.strip() for s in e.partition("="))
+                if name or given:
+                    if not re.fullmatch(r"\w+", name):
+                        _refuse("enumerator", e)
+                    constants[name] = value = _int(given, "enumerator", e) if given else value + 1
+        elif m["hook"]:
+            types[m["hook"]] = P
+        elif m["typedef"]:
+            (name, ct), = _declare(m["typedef"], types, "typedef", "a pointer or scalar")
+            if ct is not P and ct not in _SCALARS.values():
+                _refuse("typedef", m["typedef"])
+            types[name] = ct
+        else:
+            params = m["params"].strip()
+            args = [] if params in ("", "void") else [_declare(p, types, "parameter", m["function"])[0][1] for p in params.split(",")]
+            signatures[m["function"]] = (_declare(m["ret"], types, "return type", m["function"])[0][1], args)
+    return signatures, structs, constants
 
-# name -> (restype, argtypes); one row per function declared in include/yt8m_hip.h
-SIGNATURES = {
-    "yt8m_abi_version": (c_int, []),
-    "yt8m_last_error": (ctypes.c_char_p, []),
-    "yt8m_built_arch": (ctypes.c_char_p, []),
-    "yt8m_prof_enable": (c_int, [c_int]),
-    "yt8m_prof_reset": (c_int, []),
-    "yt8m_prof_get": (c_int, [c_int, ctypes.POINTER(c_int64), ctypes.POINTER(c_double)]),
-    "yt8m_prof_get_flops": (c_int, [c_int, ctypes.POINTER(c_double)]),
-    "yt8m_prof_get_bytes": (c_int, [c_int, ctypes.POINTER(ctypes.c_double)]),
-    "yt8m_probe_mfma_f32": (c_int, [c_int, c_int, P, P]),
-    "yt8m_probe_mfma_bf16": (c_int, [c_int, c_int, c_int, P, P]),
-    "yt8m_probe_copy_f32": (c_int, [P, P, c_int64, P]),
-    "yt8m_probe_placement": (c_int, [P, c_int, c_int, P]),
-    "yt8m_stream_create_cu_mask": (c_int, [P, c_int, ctypes.POINTER(P)]),
-    "yt8m_stream_destroy": (c_int, [P]),
-    "yt8m_gemm_f32": (c_int, [c_int, c_int, c_int64, c_int64, c_int64, P, c_int64, P, c_int64, P, c_int64, P, c_float, P]),
-    "yt8m_gemm_workspace_bytes": (c_int64, []),
-    "yt8m_gemm_f32_grouped": (c_int, [c_int, c_int, c_int, ctypes.POINTER(GemmProblem), P, c_int64, P]),
-    "yt8m_gemm_bf16_nt_grouped": (c_int, [c_int, ctypes.POINTER(GemmProblem), P, c_int64, P]),
-    "yt8m_gemm_x3_pays": (c_int, [c_int64, c_int64, c_int64]),
-    "yt8m_gemm_auto_scratch_bytes": (c_int64, [c_int, c_int, c_int, ctypes.POINTER(GemmProblem)]),
-    "yt8m_gemm_auto_grouped": (c_int, [c_int, c_int, c_int, ctypes.POINTER(GemmProblem), P, c_int64, P, c_int64, ctypes.POINTER(ctypes.c_uint64), P]),
-    "yt8m_gemm_auto_grouped_ex": (c_int, [c_int, c_int, c_int, ctypes.POINTER(GemmProblem), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
-                                          P, c_int64, P, c_int64, ctypes.POINTER(ctypes.c_uint64), P]),
-    "yt8m_x3_image_bytes": (c_int64, [c_int64, c_int64]),
-    "yt8m_x3_split": (c_int, [P, c_int64, c_int64, c_int64, c_float, P, P, P]),
-    "yt8m_gemm_x3_nt_grouped": (c_int, [c_int, ctypes.POINTER(GemmProblem), P, c_int64, P]),
-    "yt8m_gemm_x1x3_nt": (c_int, [c_int64, c_int64, c_int64, P, P, P, c_int64, P, P, P, c_float, P, c_int64, P]),
-    "yt8m_gemm_x1x3_nt_ex": (c_int, [c_int64, c_int64, c_int64, P, c_int64, P, c_int64, P, c_int64, P, c_float, P, P, c_float, c_float, P,
-                                     c_int64, P]),
-    "yt8m_bf16_image": (c_int, [P, c_int64, c_int64, c_int64, c_float, P, P, P]),
-    "yt8m_gemm_b1_nt_grouped": (c_int, [c_int, ctypes.POINTER(GemmProblem), P, c_int64, P]),
-    "yt8m_gemm_b1_nt_grouped_bf16c": (c_int, [c_int, ctypes.POINTER(GemmProblem), ctypes.c_uint, P, c_int64, P]),
-    "yt8m_x3_split_ex": (c_int, [P, c_int64, c_int64, c_int64, c_float, P, P, P, P, P]),
-    "yt8m_x3_split_colsum": (c_int, [P, c_int64, c_int64, c_int64, c_float, P, P, P, P, P, P, P]),
-    "yt8m_x3_set_combine": (c_int, [c_int]),
-    "yt8m_x3_set_schedule": (c_int, [c_int]),
-    "yt8m_bf16_image_colsum": (c_int, [P, c_int64, c_int64, c_int64, c_float, P, P, P, P, P, P, P]),
-    "yt8m_gemm_b1_nt_ex": (c_int, [c_int64, c_int64, c_int64, P, c_int64, P, c_int64, P, c_int64, P, c_float, P, P, c_float, c_float, P,
-                                   c_int64, P]),
-    "yt8m_u8_frames_image_t": (c_int, [P, P, c_int64, c_int64, c_int64, P, P]),
-    "yt8m_lstm_stack_supported": (c_int, [DESC]),
-    "yt8m_lstm_stack_tape_bytes": (c_int64, [DESC]),
-    "yt8m_lstm_stack_scratch_bytes": (c_int64, [DESC]),
-    "yt8m_lstm_stack_partition": (c_int, [DESC, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
-    "yt8m_lstm_stack_set_prep_hook": (c_int, [P, P]),
-    "yt8m_lstm_stack_streams": (c_int, [c_int, PP, ctypes.POINTER(c_void_p)]),
-    "yt8m_lstm_stack_fwd": (c_int, [DESC, P, P, PP, PP, P, c_int64, P, c_int64, P]),
-    "yt8m_lstm_stack_view": (c_int, [DESC, P, c_int, c_int, ctypes.POINTER(c_void_p)]),
-    "yt8m_lstm_stack_bwd": (c_int, [DESC, P, P, PP, P, c_int64, P, c_int64, P, PP, PP, PP, PP, ctypes.POINTER(c_float),
-                                    ctypes.POINTER(c_float), P, P]),
-    "yt8m_lstm_stack_status": (c_int, [DESC, P, P]),
-    "yt8m_lstm_stack_layer_done_wait": (c_int, [c_int, P]),
-    "yt8m_u8_frames_image": (c_int, [P, P, c_int64, c_int64, c_int64, c_float, P, P, P, P]),
-    "yt8m_cast_f32_bf16": (c_int, [P, c_int64, c_int64, c_int64, P, c_int64, c_int, P]),
-    "yt8m_cast_f32_bf16_dual": (c_int, [P, c_int64, c_int64, c_int64, P, c_int64, P, c_int64, P]),
-    "yt8m_gemm_f32_batched": (c_int, [c_int, c_int, c_int64, c_int64, c_int64, P, c_int64, c_int64, P, c_int64, c_int64,
-                                      P, c_int64, c_int64, c_float, c_int64, P]),
-    "yt8m_l2norm_fwd_f32": (c_int, [P, P, c_int64, c_int64, c_float, P]),
-    "yt8m_l2norm_bwd_f32": (c_int, [P, P, P, c_int64, c_int64, c_float, P]),
-    "yt8m_dequant_l2norm_u8": (c_int, [P, P, P, c_int64, c_int64, c_int64, c_float, P]),
-    "yt8m_dequant_mean_l2norm_u8": (c_int, [P, P, P, c_int64, c_int64, c_int64, c_float, P]),
-    "yt8m_moe_workspace_bytes": (c_int64, [c_int64, c_int64]),
-    "yt8m_moe_workspace_bytes_ex": (c_int64, [c_int64, c_int64, c_int64, c_int]),
-    "yt8m_moe_fwd": (c_int, [P, P, P, P, P, c_int, c_int64, c_int64, c_int64, c_int, c_float, P, P, P, P, P, c_int64, P]),
-    "yt8m_moe_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int64, c_int64, c_int64, c_int, c_float, c_float, P, P, P, c_float, P, P,
-                             c_int64, P]),
-    "yt8m_logistic_fwd_bwd": (c_int, [P, P, P, P, c_int, c_int64, c_int64, c_int64, c_float, P, P, P, P, P, c_float, P, P,
-                                      c_int64, P]),
-    "yt8m_moe_mix_fwd": (c_int, [P, P, P, c_int64, c_int64, c_int, P]),
-    "yt8m_moe_mix_bwd": (c_int, [P, P, P, c_int64, c_int64, c_int, P]),
-    "yt8m_moe_mix_xent_workspace_bytes": (c_int64, [c_int64, c_int64]),
-    "yt8m_moe_mix_xent_fwd": (c_int, [P, P, P, c_int, P, P, c_int64, c_int64, c_int, c_float, P, P]),
-    "yt8m_moe_mix_xent_bwd": (c_int, [P, P, P, c_int, P, c_int64, c_int64, c_int, c_float, c_float, P]),
-    "yt8m_moe_mix_xent_bwd_absmax": (c_int, [P, P, P, c_int, P, c_int64, c_int64, c_int, c_float, c_float, P, P]),
-    "yt8m_skinny_supported": (c_int, [c_int64, c_int64, c_int64]),
-    "yt8m_skinny_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
-    "yt8m_skinny_fwd_f32": (c_int, [P, c_int64, P, c_int64, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P]),
-    "yt8m_skinny_dw_f32": (c_int, [P, c_int64, P, c_int64, P, c_int64, c_int64, c_int64, c_int64, c_float, P, c_int64, P]),
-    "yt8m_skinny_dx_f32": (c_int, [P, c_int64, P, c_int64, P, c_int64, c_int64, c_int64, c_int64, c_float, P]),
-    "yt8m_lstm_packed16_elems": (c_int64, [c_int64, c_int64]),
-    "yt8m_lstm_pack_bf16": (c_int, [P, c_int64, c_int64, P, P, P]),
-    "yt8m_lstm_steps_fwd_bf16": (c_int, [P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P]),
-    "yt8m_lstm_steps_bwd_bf16": (c_int, [P, P, P, P, P, P, P, c_int, P, c_int64, c_int64, c_int64, c_int64, P]),
-    "yt8m_u8_frame_scales": (c_int, [P, P, c_int64, c_int64, c_int64, c_float, P, P]),
-    "yt8m_skinny_fwd_u8": (c_int, [P, c_int64, P, c_int64, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P]),
-    "yt8m_skinny_dw_u8": (c_int, [P, c_int64, P, c_int64, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P, c_int64, P]),
-    "yt8m_attn_pool_fwd_u8": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int64, P]),
-    "yt8m_attn_pool_dw_u8": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, P]),
-    "yt8m_attn_pool_supported": (c_int, [c_int64, c_int64, c_int64, c_int64]),
-    "yt8m_attn_pool_fwd": (c_int, [P, P, P, c_int64, c_int64, c_int64, c_int64, P]),
-    "yt8m_attn_pool_bwd": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, P]),
-    "yt8m_gru_layer_fwd": (c_int, [P, P, P, c_int64, P, c_int64, P, P, P, P, c_int64, c_int64, c_int64, P, c_int64, P]),
-    "yt8m_gru_layer_bwd": (c_int, [P, P, P, c_int64, P, c_int64, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, P, c_int64, P]),
-    "yt8m_lnlstm_layer_fwd": (c_int, [P, P, c_int64, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_float, c_float,
-                                      ctypes.c_uint64, P, c_int64, P]),
-    "yt8m_lnlstm_layer_bwd": (c_int, [P, P, c_int64, P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_float,
-                                      c_float, ctypes.c_uint64, P, c_int64, P]),
-    "yt8m_gate_lstm_supported": (c_int, [c_int64, c_int64]),
-    "yt8m_gate_lstm_layer_fwd": (c_int, [P, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, c_int64, c_int64, P, c_int64, P]),
-    "yt8m_gate_lstm_layer_bwd": (c_int, [P, P, c_int64, P, c_int64, P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, P, c_int64,
-                                         P]),
-    "yt8m_gate_lstm_frames_supported": (c_int, [c_int64, c_int64]),
-    "yt8m_gate_lstm_frames_fwd": (c_int, [P, c_int64, P, c_int64, P, c_int64] + [P] * 7 + [c_int] + [c_int64] * 3 + [P, c_int64, P]),
-    "yt8m_gate_lstm_frames_bwd": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, P, P, P, P, c_int64, P, c_int64, P, P, c_int] +
-                                          [c_int64] * 3 + [P, c_int64, P]),
-    "yt8m_glu_lstm_supported": (c_int, [c_int64, c_int64, c_int64]),
-    "yt8m_glu_lstm_layer_fwd": (c_int, [P, P, c_int64, P, c_int64, P, c_int64] + [P] * 12 + [c_int64] * 4 + [P, c_int64, P]),
-    "yt8m_glu_lstm_layer_bwd": (c_int, [P, P, c_int64, P, c_int64, P, c_int64] + [P] * 14 + [c_int64] + [P] * 4 + [c_int64] * 4 +
-                                        [P, c_int64, P]),
-    "yt8m_dropout_f32": (c_int, [P, P, c_int64, c_float, ctypes.c_uint64, c_int64, P]),
-    "yt8m_add_noise_f32": (c_int, [P, P, c_int64, c_float, ctypes.c_uint64, c_int64, P]),
-    "yt8m_moe_mix_bwd_bf16_partial_rows": (c_int64, [c_int64]),
-    "yt8m_moe_mix_bwd_bf16": (c_int, [P, P, P, P, c_int, c_int64, c_int64, c_int, c_float, c_float, P, P, c_int64, P, c_int64,
-                                      P, c_int64, P, c_int64, P, P]),
-    "yt8m_moe_mix_bwd_bf16_images": (c_int, [P, P, P, P, c_int, c_int64, c_int64, c_int, c_float, c_float, P, P, c_int64, P, c_int64,
-                                      P, c_int64, P, c_int64, P, P]),
-    "yt8m_moe_mix_bwd_bf16_images_z16": (c_int, [P, P, P, P, c_int, c_int64, c_int64, c_int, c_float, c_float, P, P, c_int64, P, c_int64,
-                                      P, c_int64, P, c_int64, P, P]),
-    "yt8m_moe_mix_fwd_bf16z": (c_int, [P, P, P, c_int64, c_int64, c_int, P]),
-    "yt8m_act_fwd_f32": (c_int, [c_int, P, P, c_int64, P]),
-    "yt8m_act_bwd_f32": (c_int, [c_int, P, P, P, c_int64, P]),
-    "yt8m_chain_link_fwd": (c_int, [c_int, P, P, P, c_int64, c_int64, c_float, c_float, ctypes.c_uint64, c_int64, P]),
-    "yt8m_chain_link_bwd": (c_int, [c_int, P, P, P, P, P, c_int64, c_int64, c_float, P]),
-    "yt8m_memory_link_fwd": (c_int, [c_int, P, P, c_int, P, P, c_int64, c_float, P]),
-    "yt8m_memory_link_bwd": (c_int, [c_int, P, c_int, P, P, P, P, c_int64, c_float, P]),
-    "yt8m_frame_pyramid_u8": (c_int, [P, P, c_int64, c_int64, c_int64, c_int, c_int, P, P, P, c_float, P]),
-    "yt8m_frame_pyramid_supported": (c_int, [c_int64, c_int, P, c_int]),
-    "yt8m_colsum_workspace_bytes": (c_int64, [c_int64, c_int64]),
-    "yt8m_colsum_f32": (c_int, [P, c_int64, c_int64, c_int64, P, c_float, P, c_int64, P]),
-    "yt8m_rank1_add_rows_f32": (c_int, [P, c_int64, c_int64, c_int64, P, c_float, P]),
-    "yt8m_colsum_weighted_f32": (c_int, [P, c_int64, c_int64, c_int64, P, P, c_float, P, P, c_int64, P]),
-    "yt8m_xent_workspace_bytes": (c_int64, [c_int64, c_int64]),
-    "yt8m_xent_fwd_bwd": (c_int, [P, P, c_int, P, P, P, c_int64, c_int64, c_float, c_float, P, P]),
-    "yt8m_xent_bwd": (c_int, [P, P, c_int, P, P, P, c_int64, c_int64, c_float, c_float, P]),
-    "yt8m_batch_agreement_workspace_bytes": (c_int64, [c_int64, c_int64]),
-    "yt8m_batch_agreement_fwd": (c_int, [P, P, c_int, P, P, c_int64, c_int64, c_float, c_float, c_float, P, P]),
-    "yt8m_batch_agreement_bwd": (c_int, [P, P, c_int, P, P, P, c_int64, c_int64, c_float, c_float, P]),
-    "yt8m_topk_batch_agreement_fwd": (c_int, [P, P, c_int, P, P, c_int64, c_int64, c_float, c_float, P, P]),
-    "yt8m_topk_batch_agreement_bwd": (c_int, [P, P, c_int, P, P, P, c_int64, c_int64, c_float, c_float, c_float, P]),
-    "yt8m_pointwise_loss_workspace_bytes": (c_int64, [c_int64, c_int64]),
-    "yt8m_pointwise_loss_fwd_bwd": (c_int, [c_int, P, P, c_int, P, P, c_int64, c_int64, c_float, c_float, c_float, c_float, P, P]),
-    "yt8m_pointwise_loss_bwd": (c_int, [c_int, P, P, c_int, P, P, c_int64, c_int64, c_float, c_float, c_float, c_float, P]),
-    "yt8m_xent_variant_workspace_bytes": (c_int64, [c_int64, c_int64]),
-    "yt8m_xent_variant_fwd": (c_int, [c_int, P, P, c_int, P, P, P, c_int64, c_int64, c_float, c_float, P, P]),
-    "yt8m_xent_variant_bwd": (c_int, [c_int, P, P, c_int, P, P, P, P, c_int64, c_int64, c_float, c_float, c_float, P]),
-    "yt8m_sqnorm_multi": (c_int, [P, P, P, c_int64, P, c_float, P, P, c_int64, c_int64, P, c_int64, P]),
-    "yt8m_adam_multi": (c_int, [P, P, P, P, P, c_int64, P, c_float, P, c_float, c_float, c_float, c_float, c_float, P]),
-    "yt8m_lstm_gates_fwd": (c_int, [P, P, P, P, P, P, P, ctypes.c_int32, c_int64, c_int64, c_float, P]),
-    "yt8m_lstm_gates_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, ctypes.c_int32, c_int64, c_int64, P]),
-    "yt8m_lstm_layer_fwd": (c_int, [P, P, c_int64, P, P, P, P, c_int64, c_int64, c_int64, c_float, P, c_int64, P]),
-    "yt8m_graph_cache_stats": (c_int, [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), ctypes.POINTER(c_int64),
-                                       ctypes.POINTER(c_int64)]),
-    "yt8m_graph_cache_clear": (c_int, []),
-    "yt8m_lstm_persist_supported": (c_int, [c_int64, c_int64]),
-    "yt8m_lstm_persist_workspace_bytes": (c_int64, [c_int64, c_int64]),
-    "yt8m_lstm_persist_workspace_bytes_steps": (c_int64, [c_int64, c_int64, c_int64]),
-    "yt8m_lstm_persist_placement_stats": (c_int, [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_int]),
-    "yt8m_lstm_persist_fwd_on_bf16_pipe": (c_int, [c_int64, c_int64]),
-    "yt8m_lstm_persist_set_cus": (c_int, [c_int, c_int]),
-    "yt8m_lstm_persist_get_cus": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
-    "yt8m_lstm_persist_set_tape_prefetch": (c_int, [c_int]),
-    "yt8m_lstm_persist_tape_prefetch_launches": (c_int, [ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
-    "yt8m_lstm_persist_status": (c_int, [P, P]),
-    "yt8m_lstm_persist_reserve_cus": (c_int, [c_int, ctypes.POINTER(c_int)]),
-    "yt8m_lstm_persist_debug_fault": (c_int, [P, P]),
-    "yt8m_lstm_persist_fwd": (c_int, [P, P, c_int64, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P, c_int64, P]),
-    "yt8m_lstm_persist_fwd_bf16": (c_int, [P, P, c_int64, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P, c_int64, P]),
-    "yt8m_lstm_persist_bwd_supported": (c_int, [c_int64, c_int64]),
-    "yt8m_lstm_persist_bwd": (c_int, [P, P, c_int64, P, P, P, P, c_int, P, P, c_int64, c_int64, c_int64, c_int64, P, c_int64, P]),
-    "yt8m_lstm_persist_bwd_bf16": (c_int, [P, P, c_int64, P, P, P, P, c_int, P, P, c_int64, c_int64, c_int64, c_int64, P, c_int64, P]),
-    "yt8m_lstm_persist_fwd_h2": (c_int, [P, P, c_int64, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P, P, c_int64, P]),
-    "yt8m_lstm_persist_bwd_h2": (c_int, [P, P, c_int64, P, P, P, P, c_int, P, P, c_int64, c_int64, c_int64, c_int64, P, P, c_int64, P]),
-    "yt8m_lstm_persist_bwd_on_f16_pipe": (c_int, [c_int64, c_int64]),
-    "yt8m_lstm_persist_bwd_ex": (c_int, [P, P, c_int64, P, P, P, P, c_int, P, c_int64, c_int64, c_int64, c_int64, P, P, P, P, c_int64, P]),
-    "yt8m_h2_split_rowmax": (c_int, [P, c_int64, c_int64, c_int64, P, P, P, P]),
-    "yt8m_lstm_persist_bwd_images_rows": (c_int, [c_int64, c_int64]),
-    "yt8m_lstm_persist_bwd_images": (c_int, [P, P, c_int64, P, P, P, P, c_int, P, c_int64, c_int64, c_int64, c_int64, P, c_int64, P, P]),
-    "yt8m_lstm_packed_floats": (c_int64, [c_int64, c_int64]),
-    "yt8m_lstm_pack": (c_int, [P, c_int64, c_int64, P, P, P]),
-    "yt8m_lstm_steps_fwd": (c_int, [P, P, c_int64, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P, c_int64, P]),
-    "yt8m_lstm_steps_bwd": (c_int, [P, P, c_int64, P, P, P, P, P, c_int, P, c_int64, c_int64, c_int64, c_int64, P, c_int64, P]),
-    "yt8m_lstm_layer_bwd": (c_int, [P, P, c_int64, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, P, c_int64, P]),
-    "yt8m_attn_softmax_fwd": (c_int, [P, P, P, c_int64, c_int64, c_int64, P]),
-    "yt8m_attn_softmax_bwd": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, P]),
-    "yt8m_softmax_rows_fwd": (c_int, [P, P, P, c_int64, c_int64, c_int64, P]),
-    "yt8m_softmax_rows_bwd": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, P]),
-    "yt8m_netvlad_supported": (c_int, [c_int64, c_int64, c_int64, c_int64]),
-    "yt8m_netvlad_single_pass": (c_int, [c_int64, c_int64, c_int64, c_int64]),
-    "yt8m_netvlad_set_single": (c_int, [c_int]),
-    "yt8m_netvlad_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int64]),
-    "yt8m_netvlad_fwd_u8": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int, c_float, P, P, P, P, c_int64, P]),
-    "yt8m_netvlad_bwd_u8": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int, c_float, P, c_float, P, c_float,
-                                    P, c_int64, P]),
-    "yt8m_vlad_finish_fwd": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P]),
-    "yt8m_vlad_finish_bwd": (c_int, [P, P, P, P, P, P, P, c_float, c_int64, c_int64, c_int64, c_float, P]),
-    "yt8m_vlad_finish_q_supported": (c_int, [c_int64]),
-    "yt8m_vlad_finish_q_fwd": (c_int, [P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P]),
-    "yt8m_vlad_finish_q_bwd": (c_int, [P, P, P, P, P, P, P, P, c_float, c_int64, c_int64, c_int64, c_float, P]),
-    "yt8m_crc32c": (ctypes.c_uint32, [P, c_int64]),
-    "yt8m_crc32c_masked": (ctypes.c_uint32, [P, c_int64]),
-    "yt8m_prefetch_open": (c_int, [ctypes.POINTER(ctypes.c_char_p), c_int, c_int, ctypes.POINTER(ctypes.c_char_p),
-                                   ctypes.POINTER(ctypes.c_int32), c_int, c_int64, c_int64, c_int64, c_int, c_int, c_int,
-                                   ctypes.POINTER(c_void_p)]),
-    "yt8m_prefetch_acquire": (c_int, [P, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
-                                      ctypes.POINTER(c_void_p), ctypes.POINTER(c_int64), ctypes.POINTER(c_int64),
-                                      ctypes.POINTER(c_int)]),
-    "yt8m_prefetch_close": (c_int, [P]),
-    "yt8m_tfrecord_write_predictions": (c_int, [ctypes.c_char_p, c_int64, P, c_int64, P, P, c_int64, ctypes.c_char_p]),
-    "yt8m_tfrecord_open": (c_int, [ctypes.c_char_p, c_int, ctypes.POINTER(c_void_p)]),
-    "yt8m_tfrecord_close": (c_int, [P]),
-    "yt8m_tfrecord_read_frame_batch": (c_int, [P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int32), c_int, c_int64,
-                                               c_int64, c_int64, P, P, P, P, c_int64, ctypes.POINTER(c_int64)]),
-    "yt8m_tfrecord_read_video_batch": (c_int, [P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_int32), c_int, c_int64,
-                                               c_int64, P, P, P, c_int64, ctypes.POINTER(c_int64)]),
-    "yt8m_comm_unique_id": (c_int, [P]),
-    "yt8m_comm_init": (c_int, [c_int, c_int, P, ctypes.POINTER(c_void_p)]),
-    "yt8m_comm_size": (c_int, [P, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
-    "yt8m_comm_allreduce_f32": (c_int, [P, P, c_int64, c_int, P]),
-    "yt8m_comm_allreduce_mean": (c_int, [P, P, c_int64, P]),
-    "yt8m_comm_allreduce_rsag_f32": (c_int, [P, P, c_int64, c_int, c_int, P]),
-    "yt8m_comm_broadcast_f32": (c_int, [P, P, c_int64, c_int, P]),
-    "yt8m_comm_destroy": (c_int, [P]),
-    "yt8m_u8_proj_supported": (c_int, [c_int64]),
-    "yt8m_u8_frames_to_bf16_tm": (c_int, [P, P, c_int64, c_int64, c_int64, c_float, c_int, P, c_int64, P, P, P]),
-    "yt8m_split3_bf16_t": (c_int, [P, c_int64, c_int64, c_int64, c_float, P, c_int64, P]),
-    "yt8m_rowscale_bias_f32": (c_int, [P, c_int64, c_int64, c_int64, P, P, c_float, P, P]),
-    "yt8m_sample_frames_f32": (c_int, [P, P, c_int64, c_int64, c_int64, c_int64, c_int, ctypes.c_uint64, P, P, P]),
-    "yt8m_sample_frames_u8": (c_int, [P, P, c_int64, c_int64, c_int64, c_int64, c_int, ctypes.c_uint64, P, P, P]),
-    "yt8m_frame_pool_fwd": (c_int, [P, c_int64, c_int64, c_int64, c_int, P, P]),
-    "yt8m_frame_pool_bwd": (c_int, [P, P, P, c_int64, c_int64, c_int64, c_int, P, P]),
-    "yt8m_batchnorm_fwd": (c_int, [P, c_int64, c_int64, P, P, P, P, c_int, c_float, c_float, P, P, P, P]),
-    "yt8m_batchnorm_workspace_bytes": (c_int64, [c_int64]),
-    "yt8m_batchnorm_bwd": (c_int, [P, P, c_int64, c_int64, P, P, P, c_int, P, P, c_float, P, c_float, P, c_int64, P]),
-    "yt8m_wimg_register": (c_int, [P, c_int64, c_int64, c_int64, c_int, c_int, c_float, P]),
-    "yt8m_wimg_unregister": (c_int64, [P, P]),
-    "yt8m_wimg_lookup": (c_void_p, [P, c_int64, c_int64, c_int64, c_int, c_int, c_float]),
-    "yt8m_wimg_count": (c_int64, []),
-    "yt8m_wimg_watch": (c_int, [P, P, c_int]),
-    "yt8m_wimg_note_demand": (c_int, [P, c_int64, c_int64, c_int64, c_int, c_int, c_float]),
-    "yt8m_wimg_demands": (c_int64, [ctypes.POINTER(WimgDemand), c_int64]),
-    "yt8m_wimg_demand_generation": (c_int64, [P, P]),
-    "yt8m_wimg_jobs_layout": (c_int64, [ctypes.POINTER(WimgJob), c_int64]),
-    "yt8m_adam_tiles": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, P, c_float, P, c_float, c_float, c_float, c_float, c_float,
-                                c_int, P]),
-    "yt8m_adam_multi_ex": (c_int, [P, P, P, P, P, c_int64, P, c_float, P, c_float, c_float, c_float, c_float, c_float, P, P]),
-    "yt8m_optimizer_ranges": (c_int, [ctypes.POINTER(OptRanges), P]),
-    "yt8m_lstm_stack_set_early_optimizer": (c_int, [ctypes.POINTER(OptRanges)]),
-    "yt8m_h2_split": (c_int, [P, c_int64, c_int64, c_int64, c_float, P, P, P, P, P]),
-    "yt8m_h2_absmax": (c_int, [P, c_int64, c_int64, c_int64, P, P]),
-    "yt8m_h2_degraded": (c_int, [ctypes.POINTER(ctypes.c_uint64), c_int, P]),
-    "yt8m_clip_by_norm_f32": (c_int, [P, P, c_int64, c_float, P, P]),
-    "yt8m_gru_persist_supported": (c_int, [c_int64, c_int64]),
-    "yt8m_gru_persist_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
-    "yt8m_gru_persist_fwd": (c_int, [P, P, P, c_int64, P, c_int64, P, P, P, P, c_int64, c_int64, c_int64, c_int64, P, c_int64, P]),
-    "yt8m_h2_split_dropout": (c_int, [P, c_int64, c_int64, c_float, P, P, P, c_float, ctypes.c_uint64, c_int64, P]),
-    "yt8m_h2_split_ex": (c_int, [P, c_int64, c_int64, c_int64, c_float, P, P, P, P, P, P, P, P]),
-    "yt8m_gemm_h1x2_nt_ex": (c_int, [c_int64, c_int64, c_int64, P, c_int64, P, c_int64, P, c_int64, P, c_float, P, P, P, c_float, c_float, P,
-                                     c_int64, P]),
-    "yt8m_h2_rowscales": (c_int, [P, c_int64, c_int64, c_int64, P, P, P]),
-    "yt8m_h2_split_rows": (c_int, [P, c_int64, c_int64, c_int64, P, P, P]),
-    "yt8m_gemm_h2_nt_ex": (c_int, [c_int64, c_int64, c_int64, P, c_int64, P, c_int64, P, c_int64, P, c_float, P, P, P, c_float, P, c_int64, P]),
-    "yt8m_timepool_max_f32": (c_int, [P, c_int64, c_int64, c_int64, c_int64, P, P, c_int64, P]),
-    "yt8m_timepool_shiftmax_f32": (c_int, [P, c_int64, c_int64, c_int64, c_int, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), P, P,
-                                           c_int64, P]),
-    "yt8m_u8_cnn_pool_dw": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, P, c_float, P]),
-    "yt8m_f32_cnn_pool_dw": (c_int, [P, c_int64, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, P, c_int64, c_float, P]),
-    "yt8m_f32_cnn_pool_dx": (c_int, [P, P, c_int64, c_int64, c_int64, c_int64, c_int, PP, ctypes.POINTER(ctypes.c_int32),
-                                     ctypes.POINTER(ctypes.c_int32), P, c_int64, P]),
-    "yt8m_u8_frames_image_f16": (c_int, [P, P, c_int64, c_int64, c_int64, c_float, P, P, P, P]),
-    "yt8m_u8_frames_image_t_f16": (c_int, [P, P, c_int64, c_int64, c_int64, P, P]),
-    "yt8m_gemm_h2_nt_grouped": (c_int, [c_int, ctypes.POINTER(GemmProblem), ctypes.POINTER(c_float), PP, PP, P, c_int64, P]),
-    "yt8m_topk_rows": (c_int, [P, c_int64, c_int64, c_int, P, P, P]),
-    "yt8m_perr_rows": (c_int, [P, P, c_int64, c_int64, P, P]),
-    "yt8m_reverse_sequence_u8": (c_int, [P, P, P, c_int64, c_int64, c_int64, P]),
-    "yt8m_reverse_sequence_f32_tm": (c_int, [P, c_int64, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, P]),
-    "yt8m_lstm_stack_use_streams": (c_int, [c_int, ctypes.POINTER(c_int)]),
-    "yt8m_half_segments_u8": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, P]),
-    "yt8m_half_segments_f32": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, P]),
-    "yt8m_half_segment_means_u8": (c_int, [P, P, P, c_int64, c_int64, c_int64, c_int, c_float, P]),
-    "yt8m_dequant_noise_u8": (c_int, [P, P, P, c_int64, c_int64, c_int64, c_float, ctypes.c_uint64, P]),
-    "yt8m_frame_subset_draw": (c_int, [P, c_int64, c_int64, c_int64, ctypes.c_uint64, P]),
-    "yt8m_frame_subset_gather_u8": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, P]),
-    "yt8m_frame_subset_gather_f32": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int64, P]),
-    "yt8m_resolution_mean_u8": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int, c_float, P]),
-    "yt8m_resolution_mean_f32": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int, c_float, P]),
-    "yt8m_multiscale_workspace_bytes": (c_int64, [c_int64]),
-    "yt8m_colmoments_f32": (c_int, [P, c_int64, c_int64, c_int64, P, P, c_int, c_float, c_float, P, P, P, c_int64, P]),
-    "yt8m_bn_relu_pool2_tm_fwd": (c_int, [P, c_int64, c_int64, c_int64, c_int64, P, P, P, P, P, c_int64, P, c_int64, P]),
-    "yt8m_bn_relu_pool2_tm_bwd": (c_int, [P, c_int64, c_int64, c_int64, c_int64, P, P, P, P, c_int, P, c_int64, P, c_int64, P, c_int64, P,
-                                          c_float, P, c_float, P, c_int64, P]),
-    "yt8m_timepool_max_pool2_f32_fwd": (c_int, [P, c_int64, c_int64, c_int64, c_int64, P, P, c_int64, P, c_int64, P]),
-    "yt8m_timepool_max_pool2_f32_bwd": (c_int, [P, c_int64, c_int64, c_int64, c_int64, P, P, c_int64, P, c_int64, P, c_int64, P]),
-    "yt8m_ens_max_gates": (c_int, []),
-    "yt8m_ens_combine_fwd": (c_int, [P, P, P, c_int, P, P, c_int64, c_int64, c_int64, c_int, P]),
-    "yt8m_ens_combine_bwd_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int]),
-    "yt8m_ens_combine_bwd": (c_int, [P, P, P, c_int, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_int, P]),
-    "yt8m_ens_moments": (c_int, [P, P, P, c_int64, c_int64, c_int64, P]),
-    "yt8m_ens_tensor_max_methods": (c_int, []),
-    "yt8m_ens_tensor_fwd": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, P]),
-    "yt8m_ens_tensor_bwd_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
-    "yt8m_ens_tensor_bwd": (c_int, [P, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, P]),
-    "yt8m_ens_mix_fwd": (c_int, [P, P, P, c_int64, c_int64, c_int64, P]),
-    "yt8m_ens_mix_bwd": (c_int, [P, P, P, c_int64, c_int64, c_int64, P]),
-    "yt8m_sigattn_supported": (c_int, [c_int64] * 5),
-    "yt8m_sigattn_workspace_bytes": (c_int64, [c_int64] * 5),
-    "yt8m_sigattn_fwd": (c_int, [P, c_int64, P, c_int64, P, P, P, P, P, P, P, c_int64] + [c_int64] * 5 + [P]),
-    "yt8m_sigattn_bwd": (c_int, [P, c_int64, P, c_int64] + [P] * 8 + [c_int64, P, c_int64, P, P, P, c_int64] + [c_int64] * 5 + [P]),
-    "yt8m_smattn_supported": (c_int, [c_int64] * 5),
-    "yt8m_smattn_workspace_bytes": (c_int64, [c_int64] * 5),
-    "yt8m_smattn_fwd": (c_int, [P, c_int64, P, c_int64] + [P] * 9 + [c_int64] + [c_int64] * 5 + [P]),
-    "yt8m_smattn_bwd": (c_int, [P, c_int64, P, c_int64] + [P] * 8 + [c_int64, P, c_int64, P, P, P, P, c_int64] + [c_int64] * 5 + [P]),
-    "yt8m_scale_mix_supported": (c_int, [c_int, c_int64, c_int64]),
-    "yt8m_scale_mix_fwd": (c_int, [c_int, PP, PP, P, c_int64, c_int64, P]),
-    "yt8m_scale_mix_bwd": (c_int, [c_int, PP, PP, P, P, PP, PP, c_int64, c_int64, P]),
-    "yt8m_lstm_wide_supported": (c_int, [c_int64, c_int64]),
-    "yt8m_lstm_wide_row_tile": (c_int, []),
-    "yt8m_lstm_wide_workspace_bytes": (c_int64, [c_int64, c_int64]),
-    "yt8m_lstm_wide_prepare": (c_int, [P, c_int64, c_int64, c_int64, P, c_int64, P]),
-    "yt8m_lstm_wide_steps_fwd": (c_int, [P, P, c_int64, P, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P]),
-    "yt8m_distill_input_supported": (c_int, [c_int64, c_int64, c_int64]),
-    "yt8m_distill_input_fwd": (c_int, [c_int, P, P, P, c_int64, c_int64, c_int64, P, P, P, P, c_int64, c_int64, c_int64, c_float, P]),
-    "yt8m_distill_input_bwd": (c_int, [c_int, P, P, P, P, P, P, P, P, c_int64, c_int64, c_int64, P]),
-    "yt8m_distill_blend_supported": (c_int, [c_int64, c_int64, c_int64]),
-    "yt8m_distill_blend_fwd": (c_int, [P, P, c_int64, P, c_int64, c_int64, c_int64, c_float, P]),
-    "yt8m_distill_blend_bwd": (c_int, [P, P, c_int64, c_int64, c_int64, c_float, P]),
-    "yt8m_mix_link_supported": (c_int, [c_int64, c_int64]),
-    "yt8m_mix_link_fwd": (c_int, [c_int, P, P, P, P, P, c_int64, c_int64, c_int64, c_float, c_float, P]),
-    "yt8m_mix_link_bwd": (c_int, [c_int, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, c_float, P]),
-    "yt8m_softmax_moe_supported": (c_int, [c_int64, c_int64]),
-    "yt8m_softmax_moe_resident": (c_int, [c_int64, c_int64]),
-    "yt8m_softmax_moe_fwd": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_int64, P]),
-    "yt8m_softmax_moe_bwd": (c_int, [P, P, P, P, c_int64, c_int64, P, P, c_int64, c_int64, c_int64, P]),
-    "yt8m_split_softmax_loss_workspace_bytes": (c_int64, [c_int64]),
-    "yt8m_split_softmax_loss_fwd_bwd": (c_int, [P, c_int64, c_int64, P, c_int, P, P, c_int64, c_int64, c_int64, c_float, c_float, c_float, P, P]),
-    "yt8m_split_softmax_loss_bwd": (c_int, [P, c_int64, c_int64, P, c_int, P, P, c_int64, c_int64, c_int64, c_float, c_float, c_float, P]),
-}
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return f.read()
+    except OSError as e:
+        raise Yt8mHipError("the C header the binding is computed from cannot be read: %s (%s)" % (HEADER_PATH, e))
+
+
+# name -> (restype, argtypes) of every function, the mirror of every struct, every enumerator and integer #define of include/yt8m_hip.h
+SIGNATURES, STRUCTS, CONSTANTS = parse_header(_read_header())
+globals().update({py: STRUCTS[c] for c, py in STRUCT_NAMES.items()})     # GemmProblem, PersistBwdImages, LstmStackDesc, Wimg*, OptRanges
+DESC = ctypes.POINTER(STRUCTS["yt8m_lstm_stack_desc"])
+# The one struct pointer that is a DEVICE address, which its C type cannot say: the caller passes the address, not a mirror.
+SIGNATURES["yt8m_adam_tiles"][1][4] = P                                  # const yt8m_wimg_job* jobs
 
 # The ABI this host binds (include/yt8m_hip.h, yt8m_abi_version): workspace layouts and argument meanings, not just symbols.
 ABI_VERSION = 4
 
 _lib = None
-
-
-class Yt8mHipError(RuntimeError):
-    pass
 
 
 def lib():
@@ -433,7 +165,7 @@ def lib():
     return _lib
 
 
-_STATUS = {-1: "YT8M_E_BADARG", -2: "YT8M_E_SHAPE", -3: "YT8M_E_HIP", -4: "YT8M_E_RCCL"}
+_STATUS = {v: k for k, v in CONSTANTS.items() if k.startswith("YT8M_E_")}       # enum yt8m_status
 
 
 def check(status):

@@ -27,7 +27,8 @@ DEFINE_string("compute_dtype", "float32", "float32 (exact fp32 MFMA) or bfloat16
               "master weights / gradients / optimiser) for the fully-connected and MoE-head GEMMs; the fused NetVLAD pooling "
               "uses single-f16 operands instead of the f16 hi+lo split.")
 
-ACT = {"sigmoid": 0, "relu": 1, "relu6": 2, "tanh": 3, "elu": 4}
+_C = _lib.CONSTANTS            # the enumerators and #defines of include/yt8m_hip.h
+ACT = {k: _C["YT8M_ACT_" + k.upper()] for k in ("sigmoid", "relu", "relu6", "tanh", "elu")}     # enum yt8m_act
 XENT_EPS = 10e-6  # W/losses.py:115
 
 
@@ -134,8 +135,8 @@ def _x3_wins(shapes, transA=False, transB=False):
     return bool(shapes) and all(_lib.lib().yt8m_gemm_x3_pays(int(M), int(N), int(K)) for M, N, K in shapes)
 
 
-GEMM_ROLE_DW = 0x100          # include/yt8m_hip.h YT8M_GEMM_ROLE_DW
-GEMM_ROLE_H2 = 0x200          # include/yt8m_hip.h YT8M_GEMM_ROLE_H2
+GEMM_ROLE_DW = _C["YT8M_GEMM_ROLE_DW"]
+GEMM_ROLE_H2 = _C["YT8M_GEMM_ROLE_H2"]
 
 
 def gemm_grouped(items, transA=False, transB=False, role=None):
@@ -1638,7 +1639,7 @@ def distill_blend(p1, t, w, bound):
 MIX_LINK_FUSED = os.environ.get("YT8M_MIX_LINK_FUSED", "1") != "0"
 MIX_LINK_FUSED_Q = os.environ.get("YT8M_MIX_LINK_FUSED_Q", "0") != "0"
 MIX_LINK_CALLS = {"kernels": 0, "composed": 0}       # which form ran (tests)
-MIX_LINK_PLAIN, MIX_LINK_NONE = 1, 2                 # enum yt8m_mix_link_mode
+MIX_LINK_PLAIN, MIX_LINK_NONE = _C["YT8M_MIX_LINK_PLAIN"], _C["YT8M_MIX_LINK_NONE"]      # enum yt8m_mix_link_mode
 
 
 def mix_link_composed(prev, p, W1, b1, W2, b2, q=None, norm=True, scale=1.0, eps=1e-12):
@@ -2597,10 +2598,10 @@ def cross_entropy(p, labels, weights=None, scale=1.0):
     return _Xent.apply(p, labels, weights, float(scale))
 
 
-BA_STATS_FLOATS = 20                  # YT8M_BA_STATS_FLOATS
+BA_STATS_FLOATS = _C["YT8M_BA_STATS_FLOATS"]
 BA_STATS = {"min_pp": 0, "max_np": 1, "c_fn": 2, "c_fp": 3, "n_fn": 14, "n_fp": 15, "ties_max_np": 16, "ties_min_pp": 17}
 BA_TOPK = 20                          # W/losses.py:331
-POINTWISE_LOSSES = {"weighted_xent": 0, "mse": 1, "hinge": 2}      # enum yt8m_pointwise_loss
+POINTWISE_LOSSES = {k: _C["YT8M_LOSS_" + k.upper()] for k in ("weighted_xent", "mse", "hinge")}      # enum yt8m_pointwise_loss
 
 
 def _loss_args(p, labels, min_classes=1):
@@ -2750,10 +2751,9 @@ def pointwise_loss(p, labels, kind, c0=1.0, c1=1.0):
 
 
 # ---- the --loss_function branches of Z's CrossEntropyLoss (Z/losses.py:64-168); csrc/xent_variants.hip --------------------------
-XENT_VARIANTS = {"loss_square": 0, "loss_sqrt": 1, "loss_jsd": 2, "loss_mix": 3, "loss_weight": 4, "loss_margin": 5,
-                 "loss_relabel": 6}                                   # enum yt8m_xent_variant
-XV_STATS_FLOATS = 16                  # YT8M_XV_STATS_FLOATS
-XV_STATS = {"loss": 0, "pre": 1, "flag": 2, "pos": 3, "neg": 4}       # YT8M_XV_STAT_*
+XENT_VARIANTS = {"loss_" + k: _C["YT8M_XV_" + k.upper()] for k in ("square", "sqrt", "jsd", "mix", "weight", "margin", "relabel")}   # enum yt8m_xent_variant
+XV_STATS_FLOATS = _C["YT8M_XV_STATS_FLOATS"]
+XV_STATS = {k: _C["YT8M_XV_STAT_" + k.upper()] for k in ("loss", "pre", "flag", "pos", "neg")}
 
 
 def xent_variant_fwd(p, labels, kind, c0=0.5, eps=XENT_EPS):
