@@ -32,7 +32,9 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 #include "common.h"
+#include "persist_plan.h"
 #include "x3_image.h"
 
 namespace {
@@ -45,12 +47,7 @@ constexpr int EPI_PRIO = 3;     // s_setprio of the epilogue waves
 // aux 17 = sc0 sc1: write-through store / coherent load (MI355X_MICROARCH.md, inter-workgroup visibility)
 constexpr int AUX_STORE = 17, AUX_LOAD = 17;
 constexpr long long SPIN_TIMEOUT = 300000000;  // wall_clock64 ticks (100 MHz): 3 s
-constexpr int CTL_HDR = 32;                    // control block: [0] error word, counters from word 32
-constexpr int CTL_STICKY = 32;                 // words between the sticky error word (workspace word 0) and ctl[0]
-// Arrival counter shards per tile, one 128-byte line each (the single polling wave of a workgroup reads all of them with one
-// load instruction).  Measured at B = 128, H = 1024: 8 and 16 shards run alike (10.6 us / step forward), 64 are slower (12.4:
-// the poll costs more than the shorter add queues save).
-constexpr int NSH = 8;
+using namespace yt8m_persist;   // CTL_HDR, CTL_STICKY, NSH, MAX_LOCAL_TILES, DBG_BYTES: the workspace layout (persist_plan.h)
 
 struct PersistFwdArgs {
   float* z;             // [F,B,4H] hoisted input projection + bias on entry, gate activations on exit
@@ -185,7 +182,6 @@ __device__ __forceinline__ void lds_wait_ge(const unsigned* p, unsigned target, 
   }
 }
 
-constexpr int MAX_LOCAL_TILES = 64;   // 16-row tiles one workgroup may own (persist_geometry refuses larger batches)
 constexpr int NSLOT = 4;     // partial-tile slots in LDS (items k, k+4, ... share slot k & 3)
 constexpr int NEPI = 4;      // epilogue waves (item k is finished by epilogue wave k & 3)
 
@@ -1641,7 +1637,7 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
         const float* gp = a.gates + ((long long)tp * B + row0) * 4 * H + ub * 16;
         const float* cp = a.cs + (long long)tp * BH + (long long)row0 * H + ub * 16;
         const float* dp = a.dout ? a.dout + (long long)tp * BH + (long long)row0 * H + ub * 16 : nullptr;
-        constexpr unsigned HBY = NQB * 32 * 4;            // bytes of H floats: H == 32 NQB (persist_geometry_bwd), so every offset is an immediate
+        constexpr unsigned HBY = NQB * 32 * 4;            // bytes of H floats: H == 32 NQB (bwd_geometry, persist_plan.h), so every offset is an immediate
 #pragma unroll
         for (int rb = 0; rb < 16; rb += PF_ROWS) {
           if (rb >= nrows) break;
@@ -1917,11 +1913,19 @@ __global__ __launch_bounds__(768) void lstm_persist_bwd_kernel(PersistBwdArgs a)
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
+// Every decision -- support, geometry, product form, template arguments, workspace layout, environment knobs -- is made by
+// persist_plan.h: the launch entries below dispatch on a plan's fields, the query entries read the same plan.
+//
 // Persistent launches of one device may overlap only while their grids fit the chip TOGETHER (each needs every one of its
 // workgroups resident, one per CU; a third grid taking CUs two others still wait for would hang all three).  The gate keeps the
 // last four launches (completion event, CUs); a new launch waits for every recorded one that does not fit beside it, newest
 // first.  Two half-chip backward recurrences of neighbouring layers thus run side by side, whole-chip forward launches chain.
 #include "gru_persist.inl"
+
+const PersistKnobs& knobs() {            // filled once per process, on the first use of any persistent entry point (persist_plan.h)
+  static const PersistKnobs k = persist_knobs_from_env();
+  return k;
+}
 
 struct PersistGate {
   std::mutex mu;
@@ -1933,7 +1937,7 @@ struct PersistGate {
   PersistGate() { memset(cus, 0, sizeof(cus)); memset(head, 0, sizeof(head)); memset(init, 0, sizeof(init)); }
   // call with mu held, before the launch: makes `s` wait for what must finish first
   int admit(int dev, int need, int total, hipStream_t s) {
-    static const bool chain_all = getenv("YT8M_PERSIST_CHAIN") != nullptr;   // A/B: strict one-at-a-time chaining
+    const bool chain_all = knobs().chain;                             // A/B: strict one-at-a-time chaining
     if (!init[dev]) {
       for (int i = 0; i < R; ++i) YT8M_HIP_CHECK(hipEventCreateWithFlags(&ev[dev][i], hipEventDisableTiming));
       init[dev] = true;
@@ -1978,15 +1982,8 @@ int g_cap_fwd = -1, g_cap_bwd = -1;      // yt8m_lstm_persist_set_cus (calling t
 // the gradient all-reduce occupy CUs during the backward recurrences -- two half-chip launches admitted side by side would then
 // not both fit, and the second would spin on the CUs it got until the collective's kernels leave (a slowdown, never a deadlock:
 // RCCL's kernels do not wait for ours).  With a reserve the gate chains such launches instead.
-int g_reserved_cus = getenv("YT8M_PERSIST_RESERVED_CUS") ? atoi(getenv("YT8M_PERSIST_RESERVED_CUS")) : 0;
-int persist_cu_budget(int cus, bool bwd = false) {
-  static const int cap = getenv("YT8M_PERSIST_CUS") ? atoi(getenv("YT8M_PERSIST_CUS")) : 0;
-  static const int cap_b = getenv("YT8M_PERSIST_CUS_BWD") ? atoi(getenv("YT8M_PERSIST_CUS_BWD")) : 128;
-  int c = bwd ? cap_b : cap;
-  if (bwd && g_cap_bwd >= 0) c = g_cap_bwd;
-  if (!bwd && g_cap_fwd >= 0) c = g_cap_fwd;
-  return (c > 0 && c < cus) ? c : cus;
-}
+int g_reserved_cus = -1;                 // -1: the environment's (YT8M_PERSIST_RESERVED_CUS)
+int reserved_cus() { return g_reserved_cus >= 0 ? g_reserved_cus : knobs().reserved_cus; }
 
 int device_cus(int* dev_out) {
   static int cus[16] = {0};
@@ -2007,59 +2004,154 @@ int device_cus(int* dev_out) {
 // g_tpf_launches: H2 backward launches of the process without / with the prefetch (yt8m_lstm_persist_tape_prefetch_launches).
 std::atomic<long long> g_tpf_launches[2] = {{0}, {0}};
 thread_local int g_tape_prefetch_mode = 0;
-bool tape_prefetch_on() {
-  static const bool env_off = getenv("YT8M_PERSIST_TAPE_PREFETCH") != nullptr && atoi(getenv("YT8M_PERSIST_TAPE_PREFETCH")) == 0;
-  return g_tape_prefetch_mode == 1 || (g_tape_prefetch_mode == 0 && !env_off);
+
+// The plans and the query answers of the current device, caps and calling thread
+FwdPlan fwd_plan(int64_t B, int64_t H, int64_t T, int64_t workspace_bytes, PersistRequest rq) {
+  return plan_fwd(device_cus(nullptr), g_cap_fwd, knobs(), B, H, T, workspace_bytes, rq);
+}
+BwdPlan bwd_plan(int64_t B, int64_t H, int64_t T, int64_t workspace_bytes, PersistRequest rq) {
+  return plan_bwd(device_cus(nullptr), g_cap_fwd, g_cap_bwd, g_tape_prefetch_mode, knobs(), B, H, T, workspace_bytes, rq);
+}
+PersistQueries queries(int64_t B, int64_t H) { return persist_queries(device_cus(nullptr), g_cap_fwd, g_cap_bwd, knobs(), B, H); }
+PersistRequest request(PersistRequest::Product product, bool images = false, bool maxima = false, bool gru = false) {
+  PersistRequest rq;
+  rq.product = product; rq.images = images; rq.maxima = maxima; rq.gru = gru;
+  return rq;
 }
 
-struct Geometry { int NQ, NU, RB, NT16, per, pf; };
+// The launch protocol of every persistent kernel, in the order that matters (a wrong order does not give wrong numbers: it gives a
+// launch that waits for CUs it cannot get): device lookup, the statistics word and the two host counters, the profiling scope, the
+// gate's lock -- all in the constructor -- then admit() against the chip minus the reserve and the zeroing of the control block,
+// the caller's kernels, done().
+struct PersistLaunch {
+  int dev;
+  unsigned grid;
+  hipStream_t s;
+  unsigned* stats;
+  yt8m::ProfScope prof;
+  std::lock_guard<std::mutex> lk;
+  static int current_device() { int dev = 0; device_cus(&dev); return dev; }
+  static unsigned* count(int dev, unsigned grid) {
+    unsigned* st = stats_ptr(dev);
+    ++g_stat_launches[dev];
+    g_stat_wgs[dev] += grid;
+    return st;
+  }
+  PersistLaunch(int family, double flops, unsigned grid_, hipStream_t s_)
+      : dev(current_device()), grid(grid_), s(s_), stats(count(dev, grid_)), prof(family, s_, flops), lk(g_gate.mu) {}
+  int admit(unsigned* ctl, int NT16) {
+    int rc = g_gate.admit(dev, (int)grid, std::max(0, device_cus(nullptr) - reserved_cus()), s);
+    if (rc != YT8M_OK) return rc;
+    YT8M_HIP_CHECK(hipMemsetAsync(ctl, 0, (size_t)ctl_bytes(NT16), s));
+    return YT8M_OK;
+  }
+  int done() { return g_gate.done(dev, (int)grid, s); }
+};
 
-bool persist_geometry(int64_t B, int64_t H, Geometry* geo) {
-  static const bool off = getenv("YT8M_NO_PERSIST") != nullptr;
-  if (off || B < 1 || H < 128 || (H % 128) != 0 || H > 1024) return false;
-  const int NQ = (int)(H / 128);
-  // (NQ odd > 1 would split the register / LDS halves unevenly: not instantiated.  NQ = 1 -- H = 128, the audio stack of the
-  // parallel rgb / audio models, lstm_parallel_finaloutput_model.py:13-73 -- keeps its single q-group per wave in LDS.)
-  if (!(NQ == 1 || NQ == 2 || NQ == 4 || NQ == 6 || NQ == 8)) return false;
-  int dev = 0;
-  const int cus = device_cus(&dev);
-  const int NU = (int)(H / 8);
-  if (cus < NU) return false;
-  const int NT16 = (int)((B + 15) / 16);
-  int RB = persist_cu_budget(cus) / NU;
-  if (RB > NT16) RB = NT16;
-  if (RB > NT16 / 4) RB = NT16 / 4;                      // >= 4 tiles per workgroup when the batch allows: four independent chains
-  if (RB < 1) RB = 1;                                    // hide the exchange latency (publish -> visible -> fetched ~ 2 item times)
-  if ((NT16 + RB - 1) / RB > MAX_LOCAL_TILES) return false;   // lds_seen: tiles one workgroup may own
-  const int nit_min = NT16 / RB;                          // the last row group has floor(NT16 / RB) or one more
-  int per = 0;
-  if (RB <= 8 && (8 % RB) == 0 && (NU % (8 / RB)) == 0) per = 8 / RB;
-  // two items ahead only with >= 8 chains: with 4 the producer of item k + 2 has barely published when it is requested
-  if (geo) *geo = {NQ, NU, RB, NT16, per, nit_min >= 8 ? 2 : (nit_min >= 2 ? 1 : 0)};
-  return true;
+template <typename Args>
+int run768(void (*kernel)(Args), const char* name, unsigned grid, hipStream_t s, const Args& a) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(768), 0, s, a);
+  return yt8m::launch_status(name);
+}
+template <int N> using Int = std::integral_constant<int, N>;
+
+// ---- template dispatch: one function per direction, nothing consulted but the plan ----------------------------------------------
+int dispatch(const FwdPlan& p, const PersistFwdArgs& a, hipStream_t s) {
+  const float* h0 = a.hs + (long long)a.t0 * a.B * a.H;
+  u32x4* img = reinterpret_cast<u32x4*>(a.hx);
+  switch (p.pack) {
+    case FwdPack::plain: hipLaunchKernelGGL(hx_pack_kernel, dim3(256), dim3(256), 0, s, h0, a.hx, a.B, a.H, a.NT16); break;
+    case FwdPack::x3_three: hipLaunchKernelGGL(hx_pack_x3_kernel<3>, dim3(256), dim3(256), 0, s, h0, img, a.B, a.H, a.NT16); break;
+    case FwdPack::x3_one: hipLaunchKernelGGL(hx_pack_x3_kernel<1>, dim3(256), dim3(256), 0, s, h0, img, a.B, a.H, a.NT16); break;
+    case FwdPack::x3_two_f16: hipLaunchKernelGGL((hx_pack_x3_kernel<2, true>), dim3(256), dim3(256), 0, s, h0, img, a.B, a.H, a.NT16); break;
+  }
+  const int rc = yt8m::launch_status(p.pack == FwdPack::plain ? "hx_pack_kernel" : "hx_pack_x3_kernel");
+  if (rc != YT8M_OK) return rc;
+  const bool k4 = p.NKB == 4;                           // H = 1024; else 2 (H = 512)
+  switch (p.form) {
+    case FwdForm::x3_six:
+      return run768(k4 ? lstm_persist_fwd_x3_kernel<4> : lstm_persist_fwd_x3_kernel<2>, "lstm_persist_fwd_x3_kernel", p.grid, s, a);
+    case FwdForm::bf16_one_plane:
+      return run768(k4 ? lstm_persist_fwd_x3_kernel<4, 1> : lstm_persist_fwd_x3_kernel<2, 1>, "lstm_persist_fwd_x3_kernel", p.grid, s, a);
+    case FwdForm::h2_two_plane:
+      return run768(k4 ? lstm_persist_fwd_x3_kernel<4, 2, true> : lstm_persist_fwd_x3_kernel<2, 2, true>, "lstm_persist_fwd_x3_kernel", p.grid, s, a);
+    case FwdForm::fp32: break;
+  }
+  auto fp32 = [&](auto nq) {
+    constexpr int NQ = decltype(nq)::value;
+    void (*const k[3][2])(PersistFwdArgs) = {{lstm_persist_fwd_kernel<NQ, 0, false>, lstm_persist_fwd_kernel<NQ, 0, true>},
+                                             {lstm_persist_fwd_kernel<NQ, 1, false>, lstm_persist_fwd_kernel<NQ, 1, true>},
+                                             {lstm_persist_fwd_kernel<NQ, 2, false>, lstm_persist_fwd_kernel<NQ, 2, true>}};
+    return run768(k[p.PD][p.SH], "lstm_persist_fwd_kernel", p.grid, s, a);
+  };
+  switch (p.geo.NQ) {
+    case 1: return fp32(Int<1>());
+    case 2: return fp32(Int<2>());
+    case 4: return fp32(Int<4>());
+    case 6: return fp32(Int<6>());
+    default: return fp32(Int<8>());
+  }
 }
 
-template <int NQ, bool SH>
-int launch_fwd_sh(const PersistFwdArgs& a, unsigned grid, hipStream_t s) {
-  if (a.pf >= 2) hipLaunchKernelGGL((lstm_persist_fwd_kernel<NQ, 2, SH>), dim3(grid), dim3(768), 0, s, a);
-  else if (a.pf == 1) hipLaunchKernelGGL((lstm_persist_fwd_kernel<NQ, 1, SH>), dim3(grid), dim3(768), 0, s, a);
-  else hipLaunchKernelGGL((lstm_persist_fwd_kernel<NQ, 0, SH>), dim3(grid), dim3(768), 0, s, a);
-  return yt8m::launch_status("lstm_persist_fwd_kernel");
-}
-template <int NQ>
-int launch_fwd(const PersistFwdArgs& a, unsigned grid, hipStream_t s) {
-  return a.nimg >= a.T ? launch_fwd_sh<NQ, true>(a, grid, s) : launch_fwd_sh<NQ, false>(a, grid, s);
+int dispatch(const FwdPlan& p, const GruFwdArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(hx_pack_kernel, dim3(256), dim3(256), 0, s, a.hs + (long long)a.t0 * a.B * a.H, a.hx, a.B, a.H, a.NT16);
+  const int rc = yt8m::launch_status("hx_pack_kernel");
+  if (rc != YT8M_OK) return rc;
+  auto gru = [&](auto nq) {
+    constexpr int NQ = decltype(nq)::value;
+    void (*const k[3])(GruFwdArgs) = {gru_persist_fwd_kernel<NQ, 0>, gru_persist_fwd_kernel<NQ, 1>, gru_persist_fwd_kernel<NQ, 2>};
+    return run768(k[p.PD], "gru_persist_fwd_kernel", p.grid, s, a);
+  };
+  switch (p.geo.NQ) {
+    case 2: return gru(Int<2>());
+    case 4: return gru(Int<4>());
+    case 6: return gru(Int<6>());
+    default: return gru(Int<8>());
+  }
 }
 
-constexpr int64_t DBG_BYTES = 65536;     // tail of the workspace: s_memtime stamps of the timing variant
-// workspace head: [sticky error line, 128 B, never zeroed by a launch][control block: zeroed before every launch], padded to 256 B
-constexpr int64_t STICKY_BYTES = CTL_STICKY * 4;
-int64_t ctl_bytes(int NT16) { return (int64_t)(CTL_HDR + NT16 * NSH * 32) * 4; }
-int64_t ctl_padded(int NT16) { return ((STICKY_BYTES + ctl_bytes(NT16) + 255) / 256) * 256; }
-// exchange images (of `width` = H forward, 4H backward) that fit in a workspace
-int images_in(int64_t workspace_bytes, int NT16, int64_t width) {
-  const int64_t n = (workspace_bytes - ctl_padded(NT16) - DBG_BYTES) / ((int64_t)NT16 * 16 * width * 4);
-  return (int)std::min<int64_t>(n, 1 << 20);
+int dispatch(const BwdPlan& p, const PersistBwdArgs& a, hipStream_t s) {
+  if (p.form == BwdForm::h2) ++g_tpf_launches[p.TPF ? 1 : 0];
+  auto bwd = [&](auto nq) {
+    constexpr int NQB = decltype(nq)::value;
+    void (*k)(PersistBwdArgs) = nullptr;
+    switch (p.form) {
+      case BwdForm::images: k = lstm_persist_bwd_kernel<NQB, true, true, true, true>; break;
+      case BwdForm::bf16:                                // (the plan grants the bf16 and h2 forms at H = 512 / 1024 only)
+        if constexpr (NQB == 16 || NQB == 32) k = lstm_persist_bwd_kernel<NQB, true, true, true, false, true>;
+        break;
+      case BwdForm::h2:
+        if constexpr (NQB == 16 || NQB == 32)
+          k = p.TPF ? lstm_persist_bwd_kernel<NQB, true, true, true, false, false, true, true>
+                    : lstm_persist_bwd_kernel<NQB, true, true, true, false, false, true>;
+        break;
+      case BwdForm::fp32: {
+        void (*const f[3][2])(PersistBwdArgs) = {{lstm_persist_bwd_kernel<NQB, false, false, false>, lstm_persist_bwd_kernel<NQB, false, true, false>},
+                                                 {lstm_persist_bwd_kernel<NQB, true, false, false>, lstm_persist_bwd_kernel<NQB, true, true, false>},
+                                                 {lstm_persist_bwd_kernel<NQB, true, false, true>, lstm_persist_bwd_kernel<NQB, true, true, true>}};
+        k = f[(int)p.PF + (int)p.ROT][p.SH];             // ROT implies PF: not prefetching / prefetching / prefetching and rotated
+      } break;
+    }
+    if (!k) return yt8m::fail(YT8M_E_SHAPE, "no backward kernel of this form at H = %s%lld", "", a.H);
+    return run768(k, "lstm_persist_bwd_kernel", p.grid, s, a);
+  };
+  switch (p.geo.NQ) {
+    case 4: return bwd(Int<4>());
+    case 8: return bwd(Int<8>());
+    case 16: return bwd(Int<16>());
+    case 24: return bwd(Int<24>());
+    default: return bwd(Int<32>());
+  }
+}
+
+// One launch: the protocol around the plan's kernels.  gate_cols: 4 (LSTM) or 3 (GRU) gate columns per unit, for the profiling scope.
+template <typename Plan, typename Args>
+int launch(const Plan& p, Args a, int family, double gate_cols, hipStream_t s) {
+  PersistLaunch L(family, 2.0 * (double)a.T * (double)a.B * (double)a.H * gate_cols * (double)a.H, p.grid, s);
+  a.stats = L.stats;
+  int rc = L.admit(a.ctl, p.geo.NT16);
+  if (rc == YT8M_OK) rc = dispatch(p, a, s);
+  return rc == YT8M_OK ? L.done() : rc;
 }
 
 }  // namespace
@@ -2088,7 +2180,7 @@ extern "C" int yt8m_lstm_persist_get_cus(int* fwd_cus, int* bwd_cus) {
 extern "C" int yt8m_lstm_persist_reserve_cus(int cus, int* previous) {
   YT8M_REQUIRE(cus >= 0 && cus <= 4096, YT8M_E_BADARG, "CU count out of range");
   std::lock_guard<std::mutex> lk(g_gate.mu);
-  if (previous) *previous = g_reserved_cus;
+  if (previous) *previous = reserved_cus();
   g_reserved_cus = cus;
   return YT8M_OK;
 }
@@ -2106,40 +2198,35 @@ extern "C" int yt8m_lstm_persist_tape_prefetch_launches(int64_t* with_prefetch, 
   return YT8M_OK;
 }
 
-extern "C" int yt8m_lstm_persist_supported(int64_t B, int64_t H) { return persist_geometry(B, H, nullptr) ? 1 : 0; }
-
-namespace {
-bool fwd_x3_shape(int64_t H, int pf) {
-  static const bool x3_off = getenv("YT8M_PERSIST_X3") != nullptr && atoi(getenv("YT8M_PERSIST_X3")) == 0;
-  return !x3_off && (H == 512 || H == 1024) && pf >= 1;
-}
-}  // namespace
-
+// ---- queries: reads of the plans (persist_queries) -------------------------------------------------------------------------------
+extern "C" int yt8m_lstm_persist_supported(int64_t B, int64_t H) { return queries(B, H).supported; }
+extern "C" int yt8m_lstm_persist_bwd_supported(int64_t B, int64_t H) { return queries(B, H).bwd_supported; }
+extern "C" int yt8m_gru_persist_supported(int64_t B, int64_t H) { return queries(B, H).gru_supported; }
 // 1 when a forward launch on a per-step-image workspace (yt8m_lstm_persist_workspace_bytes_steps) runs the recurrent product as
 // six bf16 products (lstm_persist_fwd_x3_kernel) rather than on the fp32 MFMA pipe
-extern "C" int yt8m_lstm_persist_fwd_on_bf16_pipe(int64_t B, int64_t H) {
-  Geometry geo;
-  return (persist_geometry(B, H, &geo) && fwd_x3_shape(H, geo.pf)) ? 1 : 0;
-}
+extern "C" int yt8m_lstm_persist_fwd_on_bf16_pipe(int64_t B, int64_t H) { return queries(B, H).fwd_on_bf16_pipe; }
+// 1 when yt8m_lstm_persist_bwd_h2 takes the f16 form for a T-step launch on a workspace of yt8m_lstm_persist_workspace_bytes_steps(B, H, T)
+extern "C" int yt8m_lstm_persist_bwd_on_f16_pipe(int64_t B, int64_t H) { return queries(B, H).bwd_on_f16_pipe; }
+// Rows of the column-sum partials a launch with operand images writes (4 per row group), 0 when the shape cannot take the images
+// (they are written by the rotated epilogue: B % 16 == 0 and a multiple of four 16-row tiles per workgroup).
+extern "C" int yt8m_lstm_persist_bwd_images_rows(int64_t B, int64_t H) { return queries(B, H).bwd_images_rows; }
 
+// (0: shape not supported)
 extern "C" int64_t yt8m_lstm_persist_workspace_bytes(int64_t B, int64_t H) {
-  Geometry geo;
-  if (!persist_geometry(B, H, &geo)) return 0;
-  // control block + two alternating exchange images sized for the BACKWARD pass (dz is 4H wide): [2][NT16][4H/16][256] floats
-  return ctl_padded(geo.NT16) + (int64_t)2 * geo.NT16 * 16 * 4 * H * 4 + DBG_BYTES;
+  const PersistQueries q = queries(B, H);
+  return q.supported ? workspace_bytes(q.NT16, H) : 0;
 }
-
 // The workspace that gives every step of a T-step launch its own exchange image (forward and backward): the launches then take
 // the XCD-L2-shared fetch path (see lstm_persist_fwd_kernel).  Smaller workspaces (>= yt8m_lstm_persist_workspace_bytes) run the
 // two-image protocol.
 extern "C" int64_t yt8m_lstm_persist_workspace_bytes_steps(int64_t B, int64_t H, int64_t T) {
-  Geometry geo;
-  if (!persist_geometry(B, H, &geo)) return 0;
-  // (+ the scale words of the f16 form of the backward recurrence: yt8m_lstm_persist_bwd_h2)
-  // ... + two parities x tiles x H / 16 workgroups x 2 KiB that no launch uses any more (the hand-off slots of a removed K-split
-  // form; kept so that the size and the layout of the workspace do not move)
-  return ctl_padded(geo.NT16) + std::max<int64_t>(T, 2) * geo.NT16 * 16 * 4 * H * 4 + ((std::max<int64_t>(T, 2) * geo.NT16 * (H / 16) * 16 + 255) / 256) * 256 +
-         (int64_t)2 * geo.NT16 * (H / 16) * 2048 + DBG_BYTES;
+  const PersistQueries q = queries(B, H);
+  return q.supported ? workspace_bytes_steps(q.NT16, H, T) : 0;
+}
+// (sized for every shape the LSTM forward supports, whether or not the GRU kernels take it)
+extern "C" int64_t yt8m_gru_persist_workspace_bytes(int64_t B, int64_t H, int64_t T) {
+  const PersistQueries q = queries(B, H);
+  return q.supported ? gru_workspace_bytes(q.NT16, H, T) : 0;
 }
 
 // Since the last reset on the current device: persistent launches, their workgroups, and how many of those did not run on the XCD
@@ -2185,10 +2272,46 @@ extern "C" int yt8m_lstm_persist_debug_fault(void* workspace, yt8m_stream_t stre
   return launch_status("persist_fault_kernel");
 }
 
+// ---- forward launches -------------------------------------------------------------------------------------------------------
 namespace {
-int persist_fwd_impl(float* z, const float* Wh, int64_t ldw, float* cs, float* hs, float* out, const int32_t* num_frames, int64_t t0,
-                     int64_t T, int64_t B, int64_t H, float forget_bias, void* workspace, int64_t workspace_bytes, yt8m_stream_t stream,
-                     bool bf16, const void* h2_wword = nullptr);
+// the argument checks and the kernel arguments the three forward entries share; `wword` is read by the h2 form only
+int lstm_fwd(float* z, const float* Wh, int64_t ldw, float* cs, float* hs, float* out, const int32_t* num_frames, int64_t t0, int64_t T,
+             int64_t B, int64_t H, float forget_bias, const void* wword, void* workspace, int64_t workspace_bytes, yt8m_stream_t stream,
+             PersistRequest rq) {
+  YT8M_REQUIRE(t0 >= 0 && T >= 0 && B >= 0 && H >= 0, YT8M_E_SHAPE, "negative dimension");
+  if (T * B * H == 0) return YT8M_OK;
+  YT8M_REQUIRE(z && Wh && cs && hs && workspace, YT8M_E_BADARG, "null operand");
+  YT8M_REQUIRE(ldw >= 4 * H, YT8M_E_SHAPE, "ldw < 4H");
+  const FwdPlan p = fwd_plan(B, H, T, workspace_bytes, rq);
+  YT8M_REQUIRE(p.code == YT8M_OK, p.code, p.why);
+  PersistFwdArgs a;
+  a.z = z; a.Wh = Wh; a.ldw = ldw; a.cs = cs; a.hs = hs; a.out = out; a.nf = num_frames;
+  a.ctl = static_cast<unsigned*>(workspace) + CTL_STICKY;
+  a.hx = reinterpret_cast<float*>(static_cast<char*>(workspace) + ctl_padded(p.geo.NT16));
+  a.stats = nullptr;
+  a.t0 = (int)t0; a.T = (int)T; a.B = (int)B; a.H = (int)H; a.fb = forget_bias;
+  a.NU = p.geo.NU; a.RB = p.geo.RB; a.NT16 = p.geo.NT16; a.per = p.geo.per; a.pf = p.geo.pf;
+  a.nimg = p.nimg;
+  a.wword = p.form == FwdForm::h2_two_plane ? static_cast<const unsigned*>(wword) : nullptr;
+  a.dbg = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + workspace_bytes - DBG_BYTES);
+  return launch(p, a, F_LSTM, 4.0, as_stream(stream));
+}
+}  // namespace
+
+extern "C" int yt8m_lstm_persist_fwd(float* z, const float* Wh, int64_t ldw, float* cs, float* hs, float* out,
+                                     const int32_t* num_frames, int64_t t0, int64_t T, int64_t B, int64_t H, float forget_bias,
+                                     void* workspace, int64_t workspace_bytes, yt8m_stream_t stream) {
+  return lstm_fwd(z, Wh, ldw, cs, hs, out, num_frames, t0, T, B, H, forget_bias, nullptr, workspace, workspace_bytes, stream,
+                  request(PersistRequest::fp32));
+}
+// yt8m_lstm_persist_fwd with the recurrent product h_{t-1} . W_h on ONE bf16 plane (h and W_h rounded to nearest even, fp32
+// accumulation; --compute_dtype=bfloat16).  A permission: launches that cannot take the bf16-pipe kernel (H other than 512 / 1024,
+// fewer than two 16-row tiles per workgroup, no room for one exchange image per step) run the fp32 form.
+extern "C" int yt8m_lstm_persist_fwd_bf16(float* z, const float* Wh, int64_t ldw, float* cs, float* hs, float* out,
+                                          const int32_t* num_frames, int64_t t0, int64_t T, int64_t B, int64_t H, float forget_bias,
+                                          void* workspace, int64_t workspace_bytes, yt8m_stream_t stream) {
+  return lstm_fwd(z, Wh, ldw, cs, hs, out, num_frames, t0, T, B, H, forget_bias, nullptr, workspace, workspace_bytes, stream,
+                  request(PersistRequest::bf16));
 }
 // yt8m_lstm_persist_fwd with the recurrent product h_{t-1} . W_h as THREE f16 products of two-half-plane splits (csrc/x3_image.h) instead
 // of six bf16 products of three-plane splits: the same fp32 grade (2^-21 relative per term), half the matrix instructions, 4 instead of 6
@@ -2199,205 +2322,58 @@ extern "C" int yt8m_lstm_persist_fwd_h2(float* z, const float* Wh, int64_t ldw, 
                                         const int32_t* num_frames, int64_t t0, int64_t T, int64_t B, int64_t H, float forget_bias,
                                         const void* wh_absmax, void* workspace, int64_t workspace_bytes, yt8m_stream_t stream) {
   YT8M_REQUIRE(wh_absmax, YT8M_E_BADARG, "null absmax word");
-  static const bool off = getenv("YT8M_PERSIST_FWD_H2") != nullptr && atoi(getenv("YT8M_PERSIST_FWD_H2")) == 0;
-  return persist_fwd_impl(z, Wh, ldw, cs, hs, out, num_frames, t0, T, B, H, forget_bias, workspace, workspace_bytes, stream, false,
-                          off ? nullptr : wh_absmax);
+  return lstm_fwd(z, Wh, ldw, cs, hs, out, num_frames, t0, T, B, H, forget_bias, wh_absmax, workspace, workspace_bytes, stream,
+                  request(PersistRequest::h2));
 }
-extern "C" int yt8m_lstm_persist_fwd(float* z, const float* Wh, int64_t ldw, float* cs, float* hs, float* out,
-                                     const int32_t* num_frames, int64_t t0, int64_t T, int64_t B, int64_t H, float forget_bias,
-                                     void* workspace, int64_t workspace_bytes, yt8m_stream_t stream) {
-  return persist_fwd_impl(z, Wh, ldw, cs, hs, out, num_frames, t0, T, B, H, forget_bias, workspace, workspace_bytes, stream, false);
-}
-// yt8m_lstm_persist_fwd with the recurrent product h_{t-1} . W_h on ONE bf16 plane (h and W_h rounded to nearest even, fp32
-// accumulation; --compute_dtype=bfloat16).  A permission: launches that cannot take the bf16-pipe kernel (H other than 512 / 1024,
-// fewer than two 16-row tiles per workgroup, no room for one exchange image per step) run the fp32 form.
-extern "C" int yt8m_lstm_persist_fwd_bf16(float* z, const float* Wh, int64_t ldw, float* cs, float* hs, float* out,
-                                          const int32_t* num_frames, int64_t t0, int64_t T, int64_t B, int64_t H, float forget_bias,
-                                          void* workspace, int64_t workspace_bytes, yt8m_stream_t stream) {
-  return persist_fwd_impl(z, Wh, ldw, cs, hs, out, num_frames, t0, T, B, H, forget_bias, workspace, workspace_bytes, stream, true);
-}
+
+// ---- backward launches ------------------------------------------------------------------------------------------------------
 namespace {
-int persist_fwd_impl(float* z, const float* Wh, int64_t ldw, float* cs, float* hs, float* out, const int32_t* num_frames, int64_t t0,
-                     int64_t T, int64_t B, int64_t H, float forget_bias, void* workspace, int64_t workspace_bytes, yt8m_stream_t stream,
-                     bool bf16, const void* h2_wword) {
-  using namespace yt8m;
+// the argument checks and the kernel arguments the five backward entries share; `wword` is read by the h2 form only
+int lstm_bwd(const float* gates, const float* Wh, int64_t ldw, const float* cs, const float* dout, float* dz, float* work, int phase,
+             float* dbias_rows, const int32_t* num_frames, int64_t t0, int64_t T, int64_t B, int64_t H, const void* wword, void* rowmax,
+             void* partmax, const yt8m_persist_bwd_images* img, void* workspace, int64_t workspace_bytes, yt8m_stream_t stream,
+             PersistRequest::Product product) {
   YT8M_REQUIRE(t0 >= 0 && T >= 0 && B >= 0 && H >= 0, YT8M_E_SHAPE, "negative dimension");
+  YT8M_REQUIRE(phase == 0 || phase == 1, YT8M_E_BADARG, "phase must be 0 or 1");
   if (T * B * H == 0) return YT8M_OK;
-  YT8M_REQUIRE(z && Wh && cs && hs && workspace, YT8M_E_BADARG, "null operand");
-  YT8M_REQUIRE(ldw >= 4 * H, YT8M_E_SHAPE, "ldw < 4H");
-  Geometry geo;
-  YT8M_REQUIRE(persist_geometry(B, H, &geo), YT8M_E_SHAPE, "shape not supported by the persistent recurrence (see yt8m_lstm_persist_supported)");
-  YT8M_REQUIRE(workspace_bytes >= yt8m_lstm_persist_workspace_bytes(B, H), YT8M_E_SHAPE, "workspace too small");
-  YT8M_REQUIRE(T < (1 << 20), YT8M_E_SHAPE, "T too large");
-  hipStream_t s = as_stream(stream);
-  const int64_t cb = ctl_padded(geo.NT16);
-  PersistFwdArgs a;
-  a.z = z; a.Wh = Wh; a.ldw = ldw; a.cs = cs; a.hs = hs; a.out = out; a.nf = num_frames;
+  YT8M_REQUIRE(gates && Wh && cs && dz && work && workspace, YT8M_E_BADARG, "null operand");
+  YT8M_REQUIRE(ldw >= 4 * H && (ldw % 4) == 0 && (reinterpret_cast<uintptr_t>(Wh) & 15) == 0, YT8M_E_SHAPE,
+               "W_h rows must be 16-byte aligned (ldw % 4 == 0)");
+  const bool images = img && (img->plain || img->trans || img->trans_scaled || img->colpart || img->colpart_scaled);
+  const BwdPlan p = bwd_plan(B, H, T, workspace_bytes, request(product, images, rowmax || partmax));
+  YT8M_REQUIRE(p.code == YT8M_OK, p.code, p.why);
+  PersistBwdArgs a;
+  a.gates = gates; a.Wh = Wh; a.ldw = ldw; a.cs = cs; a.dout = dout; a.dz = dz; a.work = work; a.nf = num_frames;
+  a.dbrows = dbias_rows;
+  a.img_plain = img ? static_cast<float*>(img->plain) : nullptr;
+  a.img_trans = img ? static_cast<float*>(img->trans) : nullptr;
+  a.img_trans_s = img ? static_cast<float*>(img->trans_scaled) : nullptr;
+  a.rowscale = img ? img->rowscale : nullptr;
+  a.colpart = img ? img->colpart : nullptr;
+  a.colpart_s = img ? img->colpart_scaled : nullptr;
   a.ctl = static_cast<unsigned*>(workspace) + CTL_STICKY;
-  a.hx = reinterpret_cast<float*>(static_cast<char*>(workspace) + cb);
-  a.t0 = (int)t0; a.T = (int)T; a.B = (int)B; a.H = (int)H; a.fb = forget_bias;
-  a.NU = geo.NU; a.RB = geo.RB; a.NT16 = geo.NT16; a.per = geo.per; a.pf = geo.pf;
-  a.nimg = images_in(workspace_bytes, geo.NT16, H);
+  a.dzx = reinterpret_cast<float*>(static_cast<char*>(workspace) + ctl_padded(p.geo.NT16));
+  a.stats = nullptr;
+  a.t0 = (int)t0; a.T = (int)T; a.B = (int)B; a.H = (int)H; a.phase = phase;
+  a.NUB = p.geo.NU; a.RB = p.geo.RB; a.NT16 = p.geo.NT16; a.per = p.geo.per; a.pf = p.geo.pf;
+  a.nimg = p.nimg;
+  a.bf = p.form == BwdForm::bf16 ? 1 : 0;
+  a.h2 = p.form == BwdForm::h2 ? 1 : 0;
+  a.wword = a.h2 ? static_cast<const unsigned*>(wword) : nullptr;
+  a.sc = a.h2 ? reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + p.sc_offset) : nullptr;
+  a.sc_bytes = (unsigned)p.sc_bytes;
+  a.rowmax = static_cast<unsigned*>(rowmax);
+  a.partmax = static_cast<unsigned*>(partmax);
   a.dbg = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + workspace_bytes - DBG_BYTES);
-  const unsigned grid = (unsigned)(geo.NU * geo.RB);
-  int dev = 0;
-  device_cus(&dev);
-  a.stats = stats_ptr(dev);
-  ++g_stat_launches[dev];
-  g_stat_wgs[dev] += grid;
-  ProfScope prof(F_LSTM, s, 2.0 * (double)T * (double)B * (double)H * 4.0 * (double)H);
-  std::lock_guard<std::mutex> lk(g_gate.mu);
-  const int total_cus = device_cus(nullptr);
-  int grc = g_gate.admit(dev, (int)grid, std::max(0, total_cus - g_reserved_cus), s);
-  if (grc != YT8M_OK) return grc;
-  YT8M_HIP_CHECK(hipMemsetAsync(a.ctl, 0, (size_t)ctl_bytes(geo.NT16), s));
-  // the recurrent product on the bf16 pipe (lstm_persist_fwd_x3_kernel) when its preconditions hold: an exchange image (1.5x the
-  // fp32 one) per step, >= 2 tiles per workgroup, H in {512, 1024}
-  const bool x3 = fwd_x3_shape(H, geo.pf) && images_in(workspace_bytes, geo.NT16, H + H / 2) >= T;
-  int rc;
-  a.wword = static_cast<const unsigned*>(h2_wword);
-  if (x3 && !bf16 && h2_wword) {                         // two half planes: image per step of the fp32 image's size
-    hipLaunchKernelGGL((hx_pack_x3_kernel<2, true>), dim3(256), dim3(256), 0, s, hs + t0 * B * H, reinterpret_cast<u32x4*>(a.hx), (int)B, (int)H,
-                       geo.NT16);
-    rc = launch_status("hx_pack_x3_kernel");
-    if (rc != YT8M_OK) return rc;
-    if (H == 1024) hipLaunchKernelGGL((lstm_persist_fwd_x3_kernel<4, 2, true>), dim3(grid), dim3(768), 0, s, a);
-    else hipLaunchKernelGGL((lstm_persist_fwd_x3_kernel<2, 2, true>), dim3(grid), dim3(768), 0, s, a);
-    rc = launch_status("lstm_persist_fwd_x3_kernel");
-  } else if (x3 && bf16) {
-    hipLaunchKernelGGL(hx_pack_x3_kernel<1>, dim3(256), dim3(256), 0, s, hs + t0 * B * H, reinterpret_cast<u32x4*>(a.hx), (int)B, (int)H,
-                       geo.NT16);
-    rc = launch_status("hx_pack_x3_kernel");
-    if (rc != YT8M_OK) return rc;
-    if (H == 1024) hipLaunchKernelGGL((lstm_persist_fwd_x3_kernel<4, 1>), dim3(grid), dim3(768), 0, s, a);
-    else hipLaunchKernelGGL((lstm_persist_fwd_x3_kernel<2, 1>), dim3(grid), dim3(768), 0, s, a);
-    rc = launch_status("lstm_persist_fwd_x3_kernel");
-  } else if (x3) {
-    hipLaunchKernelGGL(hx_pack_x3_kernel<3>, dim3(256), dim3(256), 0, s, hs + t0 * B * H, reinterpret_cast<u32x4*>(a.hx), (int)B, (int)H,
-                       geo.NT16);
-    rc = launch_status("hx_pack_x3_kernel");
-    if (rc != YT8M_OK) return rc;
-    if (H == 1024) hipLaunchKernelGGL((lstm_persist_fwd_x3_kernel<4>), dim3(grid), dim3(768), 0, s, a);
-    else hipLaunchKernelGGL((lstm_persist_fwd_x3_kernel<2>), dim3(grid), dim3(768), 0, s, a);
-    rc = launch_status("lstm_persist_fwd_x3_kernel");
-  } else {
-    hipLaunchKernelGGL(hx_pack_kernel, dim3(256), dim3(256), 0, s, hs + t0 * B * H, a.hx, (int)B, (int)H, geo.NT16);
-    rc = launch_status("hx_pack_kernel");
-    if (rc != YT8M_OK) return rc;
-    switch (geo.NQ) {
-      case 1: rc = launch_fwd<1>(a, grid, s); break;
-      case 2: rc = launch_fwd<2>(a, grid, s); break;
-      case 4: rc = launch_fwd<4>(a, grid, s); break;
-      case 6: rc = launch_fwd<6>(a, grid, s); break;
-      default: rc = launch_fwd<8>(a, grid, s); break;
-    }
-  }
-  if (rc != YT8M_OK) return rc;
-  return g_gate.done(dev, (int)grid, s);
+  return launch(p, a, F_LSTM_BWD, 4.0, as_stream(stream));
 }
 }  // namespace
-
-namespace {
-struct GeometryB { int NQB, NUB, RB, NT16, per, pf; };
-
-bool persist_geometry_bwd(int64_t B, int64_t H, GeometryB* geo) {
-  static const bool off = getenv("YT8M_NO_PERSIST") != nullptr || getenv("YT8M_NO_PERSIST_BWD") != nullptr;
-  if (off || B < 1 || H > 1024 || !(H == 128 || (H >= 256 && (H % 256) == 0))) return false;
-  const int NQB = (int)(H / 32);
-  if (!(NQB == 4 || NQB == 8 || NQB == 16 || NQB == 24 || NQB == 32)) return false;
-  int dev = 0;
-  const int cus = device_cus(&dev);
-  const int NUB = (int)(H / 16);
-  if (cus < NUB) return false;
-  const int NT16 = (int)((B + 15) / 16);
-  // default: HALF the chip.  With 16 units per workgroup the whole chip leaves two 16-row tiles (= two independent chains) per
-  // workgroup at B = 128 and the exchange latency is exposed on every item (42 us / step measured); on 128 CUs a workgroup
-  // owns four tiles, runs 24 us / step -- the per-step kernels' speed on the whole chip -- and the other 128 CUs stay free for
-  // the weight-gradient GEMMs of the layer pipeline.
-  int RB = persist_cu_budget(cus, true) / NUB;
-  if (RB > NT16 / 2) RB = NT16 / 2;                      // >= 2 tiles per workgroup when the batch allows: one chain's exchange
-  if (RB < 1) RB = 1;                                    // latency hides behind the other chain's matrix work
-  if ((NT16 + RB - 1) / RB > MAX_LOCAL_TILES) return false;
-  const int nit_min = NT16 / RB;
-  int per = 0;
-  if (RB <= 8 && (8 % RB) == 0 && (NUB % (8 / RB)) == 0) per = 8 / RB;
-  if (geo) *geo = {NQB, NUB, RB, NT16, per, nit_min >= 2 ? 1 : 0};
-  return true;
-}
-
-bool bwd_rot_off() {
-  static const bool off = getenv("YT8M_BWD_ROT") != nullptr && atoi(getenv("YT8M_BWD_ROT")) == 0;
-  return off;
-}
-// rotation needs a multiple of four tiles in EVERY workgroup (row group g owns tiles g, g + RB, ...) and the prefetching form
-bool bwd_rot(int pf, int NT16, int RB) { return !bwd_rot_off() && pf && (NT16 % (4 * RB)) == 0; }
-
-template <int NQB, bool SH>
-int launch_bwd_sh(const PersistBwdArgs& a, unsigned grid, hipStream_t s) {
-  const bool rot = bwd_rot(a.pf, a.NT16, a.RB);
-  const bool img = a.img_plain || a.img_trans || a.img_trans_s || a.colpart || a.colpart_s;
-  if (img) {
-    if constexpr (SH) {
-      if (!rot) return yt8m::fail(YT8M_E_SHAPE, "operand images need the rotated backward epilogue%s", "");
-      hipLaunchKernelGGL((lstm_persist_bwd_kernel<NQB, true, true, true, true>), dim3(grid), dim3(768), 0, s, a);
-      return yt8m::launch_status("lstm_persist_bwd_kernel");
-    } else {
-      return yt8m::fail(YT8M_E_SHAPE, "operand images need one exchange image per step%s", "");
-    }
-  }
-  if constexpr (SH && (NQB == 16 || NQB == 32)) {
-    if (a.bf && rot) {
-      hipLaunchKernelGGL((lstm_persist_bwd_kernel<NQB, true, true, true, false, true>), dim3(grid), dim3(768), 0, s, a);
-      return yt8m::launch_status("lstm_persist_bwd_kernel");
-    }
-  }
-  if constexpr (SH && (NQB == 16 || NQB == 32)) {
-    if (a.h2 && rot) {
-      const bool tpf = tape_prefetch_on();
-      ++g_tpf_launches[tpf ? 1 : 0];
-      if (tpf) hipLaunchKernelGGL((lstm_persist_bwd_kernel<NQB, true, true, true, false, false, true, true>), dim3(grid), dim3(768), 0, s, a);
-      else hipLaunchKernelGGL((lstm_persist_bwd_kernel<NQB, true, true, true, false, false, true>), dim3(grid), dim3(768), 0, s, a);
-      return yt8m::launch_status("lstm_persist_bwd_kernel");
-    }
-  }
-  if (rot) hipLaunchKernelGGL((lstm_persist_bwd_kernel<NQB, true, SH, true>), dim3(grid), dim3(768), 0, s, a);
-  else if (a.pf) hipLaunchKernelGGL((lstm_persist_bwd_kernel<NQB, true, SH, false>), dim3(grid), dim3(768), 0, s, a);
-  else hipLaunchKernelGGL((lstm_persist_bwd_kernel<NQB, false, SH, false>), dim3(grid), dim3(768), 0, s, a);
-  return yt8m::launch_status("lstm_persist_bwd_kernel");
-}
-template <int NQB>
-int launch_bwd(const PersistBwdArgs& a, unsigned grid, hipStream_t s) {
-  return a.nimg >= a.T ? launch_bwd_sh<NQB, true>(a, grid, s) : launch_bwd_sh<NQB, false>(a, grid, s);
-}
-}  // namespace
-
-extern "C" int yt8m_lstm_persist_bwd_supported(int64_t B, int64_t H) {
-  return (persist_geometry(B, H, nullptr) && persist_geometry_bwd(B, H, nullptr)) ? 1 : 0;
-}
-
-// Rows of the column-sum partials a launch with operand images writes (4 per row group), 0 when the shape cannot take the images
-// (they are written by the rotated epilogue: B % 16 == 0 and a multiple of four 16-row tiles per workgroup).
-extern "C" int yt8m_lstm_persist_bwd_images_rows(int64_t B, int64_t H) {
-  GeometryB geo;
-  if (!persist_geometry(B, H, nullptr) || !persist_geometry_bwd(B, H, &geo)) return 0;
-  if ((B % 16) != 0 || !bwd_rot(geo.pf, geo.NT16, geo.RB)) return 0;
-  return 4 * geo.RB;
-}
-
-namespace {
-int persist_bwd_impl(const float* gates, const float* Wh, int64_t ldw, const float* cs, const float* dout, float* dz,
-                     float* work, int phase, float* dbias_rows, const int32_t* num_frames, int64_t t0, int64_t T,
-                     int64_t B, int64_t H, void* workspace, int64_t workspace_bytes, const yt8m_persist_bwd_images* img,
-                     yt8m_stream_t stream, bool bf16 = false, const void* h2_wword = nullptr, void* rowmax = nullptr, void* partmax = nullptr);
-// bytes of the scale words an H2 launch of T steps publishes (one word per step, tile, producer workgroup and row quad), 256-aligned
-int64_t h2_scale_bytes(int NT16, int64_t H, int64_t T) { return ((T * NT16 * (H / 16) * 16 + 255) / 256) * 256; }
-}
 
 extern "C" int yt8m_lstm_persist_bwd(const float* gates, const float* Wh, int64_t ldw, const float* cs, const float* dout, float* dz,
                                      float* work, int phase, float* dbias_rows, const int32_t* num_frames, int64_t t0, int64_t T,
                                      int64_t B, int64_t H, void* workspace, int64_t workspace_bytes, yt8m_stream_t stream) {
-  return persist_bwd_impl(gates, Wh, ldw, cs, dout, dz, work, phase, dbias_rows, num_frames, t0, T, B, H, workspace, workspace_bytes,
-                          nullptr, stream);
+  return lstm_bwd(gates, Wh, ldw, cs, dout, dz, work, phase, dbias_rows, num_frames, t0, T, B, H, nullptr, nullptr, nullptr, nullptr,
+                  workspace, workspace_bytes, stream, PersistRequest::fp32);
 }
 
 // yt8m_lstm_persist_bwd with the recurrent product dz . W_h^T on ONE bf16 plane (dz and W_h rounded to nearest even, fp32 accumulation;
@@ -2406,8 +2382,8 @@ extern "C" int yt8m_lstm_persist_bwd(const float* gates, const float* Wh, int64_
 extern "C" int yt8m_lstm_persist_bwd_bf16(const float* gates, const float* Wh, int64_t ldw, const float* cs, const float* dout, float* dz,
                                           float* work, int phase, float* dbias_rows, const int32_t* num_frames, int64_t t0, int64_t T,
                                           int64_t B, int64_t H, void* workspace, int64_t workspace_bytes, yt8m_stream_t stream) {
-  return persist_bwd_impl(gates, Wh, ldw, cs, dout, dz, work, phase, dbias_rows, num_frames, t0, T, B, H, workspace, workspace_bytes,
-                          nullptr, stream, true);
+  return lstm_bwd(gates, Wh, ldw, cs, dout, dz, work, phase, dbias_rows, num_frames, t0, T, B, H, nullptr, nullptr, nullptr, nullptr,
+                  workspace, workspace_bytes, stream, PersistRequest::bf16);
 }
 
 // yt8m_lstm_persist_bwd with the recurrent product dz . W_h^T as THREE f16 products of two-half-plane splits (fp32-grade: 2^-21 relative per
@@ -2421,9 +2397,8 @@ extern "C" int yt8m_lstm_persist_bwd_h2(const float* gates, const float* Wh, int
                                         int64_t B, int64_t H, const void* wh_absmax, void* workspace, int64_t workspace_bytes,
                                         yt8m_stream_t stream) {
   YT8M_REQUIRE(wh_absmax, YT8M_E_BADARG, "null absmax word");
-  static const bool off = getenv("YT8M_PERSIST_BWD_H2") != nullptr && atoi(getenv("YT8M_PERSIST_BWD_H2")) == 0;
-  return persist_bwd_impl(gates, Wh, ldw, cs, dout, dz, work, phase, dbias_rows, num_frames, t0, T, B, H, workspace, workspace_bytes,
-                          nullptr, stream, false, off ? nullptr : wh_absmax);
+  return lstm_bwd(gates, Wh, ldw, cs, dout, dz, work, phase, dbias_rows, num_frames, t0, T, B, H, wh_absmax, nullptr, nullptr, nullptr,
+                  workspace, workspace_bytes, stream, PersistRequest::h2);
 }
 // yt8m_lstm_persist_bwd / _h2 (wh_absmax NULL: the fp32-pipe form) that also measures what the products after it would measure in passes
 // over dz: rowmax[t B + b] = max |dz[t, b, :]| (float bits; [F B] words by absolute frame row, ZEROED by the caller for the launch's
@@ -2434,15 +2409,8 @@ extern "C" int yt8m_lstm_persist_bwd_ex(const float* gates, const float* Wh, int
                                         float* work, int phase, const int32_t* num_frames, int64_t t0, int64_t T, int64_t B, int64_t H,
                                         const void* wh_absmax, void* rowmax, void* partmax, void* workspace, int64_t workspace_bytes,
                                         yt8m_stream_t stream) {
-  static const bool off = getenv("YT8M_PERSIST_BWD_H2") != nullptr && atoi(getenv("YT8M_PERSIST_BWD_H2")) == 0;
-  return persist_bwd_impl(gates, Wh, ldw, cs, dout, dz, work, phase, nullptr, num_frames, t0, T, B, H, workspace, workspace_bytes,
-                          nullptr, stream, false, off ? nullptr : wh_absmax, rowmax, partmax);
-}
-// 1 when yt8m_lstm_persist_bwd_h2 takes the f16 form for a T-step launch on a workspace of yt8m_lstm_persist_workspace_bytes_steps(B, H, T)
-extern "C" int yt8m_lstm_persist_bwd_on_f16_pipe(int64_t B, int64_t H) {
-  GeometryB geo;
-  if (!persist_geometry(B, H, nullptr) || !persist_geometry_bwd(B, H, &geo)) return 0;
-  return ((H == 512 || H == 1024) && bwd_rot(geo.pf, geo.NT16, geo.RB)) ? 1 : 0;
+  return lstm_bwd(gates, Wh, ldw, cs, dout, dz, work, phase, nullptr, num_frames, t0, T, B, H, wh_absmax, rowmax, partmax, nullptr,
+                  workspace, workspace_bytes, stream, wh_absmax ? PersistRequest::h2 : PersistRequest::fp32);
 }
 
 // yt8m_lstm_persist_bwd that also leaves the operand images of dz[t0 .. t0 + T) for the products that follow (include/yt8m_hip.h).
@@ -2456,113 +2424,12 @@ extern "C" int yt8m_lstm_persist_bwd_images(const float* gates, const float* Wh,
                "rowscale comes with trans_scaled / colpart_scaled");
   YT8M_REQUIRE((((uintptr_t)images->plain | (uintptr_t)images->trans | (uintptr_t)images->trans_scaled) & 15) == 0, YT8M_E_BADARG,
                "images must be 16-byte aligned");
-  return persist_bwd_impl(gates, Wh, ldw, cs, dout, dz, work, phase, nullptr, num_frames, t0, T, B, H, workspace, workspace_bytes, images,
-                          stream);
+  return lstm_bwd(gates, Wh, ldw, cs, dout, dz, work, phase, nullptr, num_frames, t0, T, B, H, nullptr, nullptr, nullptr, images,
+                  workspace, workspace_bytes, stream, PersistRequest::fp32);
 }
-
-namespace {
-int persist_bwd_impl(const float* gates, const float* Wh, int64_t ldw, const float* cs, const float* dout, float* dz,
-                     float* work, int phase, float* dbias_rows, const int32_t* num_frames, int64_t t0, int64_t T,
-                     int64_t B, int64_t H, void* workspace, int64_t workspace_bytes, const yt8m_persist_bwd_images* img,
-                     yt8m_stream_t stream, bool bf16, const void* h2_wword, void* rowmax, void* partmax) {
-  using namespace yt8m;
-  YT8M_REQUIRE(t0 >= 0 && T >= 0 && B >= 0 && H >= 0, YT8M_E_SHAPE, "negative dimension");
-  YT8M_REQUIRE(phase == 0 || phase == 1, YT8M_E_BADARG, "phase must be 0 or 1");
-  if (T * B * H == 0) return YT8M_OK;
-  YT8M_REQUIRE(gates && Wh && cs && dz && work && workspace, YT8M_E_BADARG, "null operand");
-  YT8M_REQUIRE(ldw >= 4 * H && (ldw % 4) == 0 && (reinterpret_cast<uintptr_t>(Wh) & 15) == 0, YT8M_E_SHAPE,
-               "W_h rows must be 16-byte aligned (ldw % 4 == 0)");
-  GeometryB geo;
-  YT8M_REQUIRE(persist_geometry(B, H, nullptr) && persist_geometry_bwd(B, H, &geo), YT8M_E_SHAPE,
-               "shape not supported by the persistent backward recurrence (see yt8m_lstm_persist_bwd_supported)");
-  YT8M_REQUIRE(workspace_bytes >= yt8m_lstm_persist_workspace_bytes(B, H), YT8M_E_SHAPE, "workspace too small");
-  YT8M_REQUIRE(T < (1 << 20), YT8M_E_SHAPE, "T too large");
-  hipStream_t s = as_stream(stream);
-  const int64_t cb = ctl_padded(geo.NT16);
-  PersistBwdArgs a;
-  a.gates = gates; a.Wh = Wh; a.ldw = ldw; a.cs = cs; a.dout = dout; a.dz = dz; a.work = work; a.nf = num_frames;
-  a.dbrows = dbias_rows;
-  a.img_plain = img ? static_cast<float*>(img->plain) : nullptr;
-  a.img_trans = img ? static_cast<float*>(img->trans) : nullptr;
-  a.img_trans_s = img ? static_cast<float*>(img->trans_scaled) : nullptr;
-  a.rowscale = img ? img->rowscale : nullptr;
-  a.colpart = img ? img->colpart : nullptr;
-  a.colpart_s = img ? img->colpart_scaled : nullptr;
-  a.ctl = static_cast<unsigned*>(workspace) + CTL_STICKY;
-  a.dzx = reinterpret_cast<float*>(static_cast<char*>(workspace) + cb);
-  a.t0 = (int)t0; a.T = (int)T; a.B = (int)B; a.H = (int)H; a.phase = phase;
-  a.NUB = geo.NUB; a.RB = geo.RB; a.NT16 = geo.NT16; a.per = geo.per; a.pf = geo.pf;
-  a.nimg = images_in(workspace_bytes, geo.NT16, 4 * H);
-  a.bf = (bf16 && !img) ? 1 : 0;
-  a.dbg = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + workspace_bytes - DBG_BYTES);
-  a.rowmax = static_cast<unsigned*>(rowmax);
-  a.partmax = static_cast<unsigned*>(partmax);
-  YT8M_REQUIRE(!(rowmax || partmax) || (!img && images_in(workspace_bytes, geo.NT16, 4 * H) >= T && bwd_rot(geo.pf, geo.NT16, geo.RB)), YT8M_E_SHAPE,
-               "row / launch maxima need the rotated backward epilogue on a per-step workspace (yt8m_lstm_persist_bwd_images_rows)");
-  // H2: the scale words sit between the last exchange image and the debug tail; taken only when T images still fit in front of them
-  a.h2 = 0; a.wword = nullptr; a.sc = nullptr; a.sc_bytes = 0;
-  if (h2_wword && !img && !bf16 && (H == 512 || H == 1024)) {
-    const int64_t scb = h2_scale_bytes(geo.NT16, H, T);
-    if (scb < (1LL << 31) && images_in(workspace_bytes - scb, geo.NT16, 4 * H) >= T) {
-      a.h2 = 1;
-      a.wword = static_cast<const unsigned*>(h2_wword);
-      a.sc = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + workspace_bytes - DBG_BYTES - scb);
-      a.sc_bytes = (unsigned)scb;
-    }
-  }
-  const unsigned grid = (unsigned)(geo.NUB * geo.RB);
-  int dev = 0;
-  device_cus(&dev);
-  a.stats = stats_ptr(dev);
-  ++g_stat_launches[dev];
-  g_stat_wgs[dev] += grid;
-  ProfScope prof(F_LSTM_BWD, s, 2.0 * (double)T * (double)B * (double)H * 4.0 * (double)H);
-  std::lock_guard<std::mutex> lk(g_gate.mu);
-  const int total_cus = device_cus(nullptr);
-  int grc = g_gate.admit(dev, (int)grid, std::max(0, total_cus - g_reserved_cus), s);
-  if (grc != YT8M_OK) return grc;
-  YT8M_HIP_CHECK(hipMemsetAsync(a.ctl, 0, (size_t)ctl_bytes(geo.NT16), s));
-  int rc;
-  switch (geo.NQB) {
-    case 4: rc = launch_bwd<4>(a, grid, s); break;
-    case 8: rc = launch_bwd<8>(a, grid, s); break;
-    case 16: rc = launch_bwd<16>(a, grid, s); break;
-    case 24: rc = launch_bwd<24>(a, grid, s); break;
-    default: rc = launch_bwd<32>(a, grid, s); break;
-  }
-  if (rc != YT8M_OK) return rc;
-  return g_gate.done(dev, (int)grid, s);
-}
-}  // namespace
-
 
 // =====================================================================================================================
-// GRUCell on the persistent protocol (gru_persist.inl).  One forward launch runs T steps = 2T half-steps of a layer; the workspace
-// holds the control block and ONE exchange image per half-step: 2T + 1 images of [NT16 16, H].  (Its size, 3 max(T, 1) + 3 such
-// images, still covers the T blocks of [NT16 16, 3H] of a persistent backward that has since been removed; kept so that the
-// layout of a caller's workspace does not move.)
-extern "C" int yt8m_gru_persist_supported(int64_t B, int64_t H) {
-  static const bool off = getenv("YT8M_GRU_PERSIST") != nullptr && atoi(getenv("YT8M_GRU_PERSIST")) == 0;
-  Geometry geo;
-  return (!off && persist_geometry(B, H, &geo) && geo.NQ >= 2) ? 1 : 0;
-}
-
-extern "C" int64_t yt8m_gru_persist_workspace_bytes(int64_t B, int64_t H, int64_t T) {
-  Geometry geo;
-  if (!persist_geometry(B, H, &geo)) return 0;
-  return ctl_padded(geo.NT16) + (3 * std::max<int64_t>(T, 1) + 3) * geo.NT16 * 16 * H * 4 + DBG_BYTES;
-}
-
-namespace {
-template <int NQ>
-int launch_gru_fwd(const GruFwdArgs& a, unsigned grid, hipStream_t s) {
-  if (a.pf >= 2) hipLaunchKernelGGL((gru_persist_fwd_kernel<NQ, 2>), dim3(grid), dim3(768), 0, s, a);
-  else if (a.pf == 1) hipLaunchKernelGGL((gru_persist_fwd_kernel<NQ, 1>), dim3(grid), dim3(768), 0, s, a);
-  else hipLaunchKernelGGL((gru_persist_fwd_kernel<NQ, 0>), dim3(grid), dim3(768), 0, s, a);
-  return yt8m::launch_status("gru_persist_fwd_kernel");
-}
-}  // namespace
-
+// GRUCell on the persistent protocol (gru_persist.inl).  One forward launch runs T steps = 2T half-steps of a layer.
 // Steps t0 .. t0 + T - 1 of one GRU layer.  zg [F,B,2H] / zc [F,B,H]: the hoisted input projections (+ biases) on entry, the
 // activations r | u / c on exit (what yt8m_gru_layer_fwd leaves there); hs [F+1,B,H] with hs[t0] given; rh [F,B,H]; out optional.
 // Same results as yt8m_gru_layer_fwd up to the K summation order of the recurrent products and the v_exp / v_rcp gate functions
@@ -2570,44 +2437,18 @@ int launch_gru_fwd(const GruFwdArgs& a, unsigned grid, hipStream_t s) {
 extern "C" int yt8m_gru_persist_fwd(float* zg, float* zc, const float* Wg_h, int64_t ldg, const float* Wc_h, int64_t ldc, float* hs,
                                     float* rh, float* out, const int32_t* num_frames, int64_t t0, int64_t T, int64_t B, int64_t H,
                                     void* workspace, int64_t workspace_bytes, yt8m_stream_t stream) {
-  using namespace yt8m;
   YT8M_REQUIRE(t0 >= 0 && T >= 0 && B >= 0 && H >= 0, YT8M_E_SHAPE, "negative dimension");
   if (T * B * H == 0) return YT8M_OK;
   YT8M_REQUIRE(zg && zc && Wg_h && Wc_h && hs && rh && workspace, YT8M_E_BADARG, "null operand");
   YT8M_REQUIRE(ldg >= 2 * H && ldc >= H, YT8M_E_SHAPE, "leading dimension too small");
-  Geometry geo;
-  YT8M_REQUIRE(yt8m_gru_persist_supported(B, H) && persist_geometry(B, H, &geo), YT8M_E_SHAPE,
-               "shape not supported by the persistent GRU recurrence (see yt8m_gru_persist_supported)");
-  YT8M_REQUIRE(workspace_bytes >= yt8m_gru_persist_workspace_bytes(B, H, T), YT8M_E_SHAPE, "workspace too small");
-  YT8M_REQUIRE(T < (1 << 19), YT8M_E_SHAPE, "T too large");
-  hipStream_t s = as_stream(stream);
+  const FwdPlan p = fwd_plan(B, H, T, workspace_bytes, request(PersistRequest::fp32, false, false, true));
+  YT8M_REQUIRE(p.code == YT8M_OK, p.code, p.why);
   GruFwdArgs a;
   a.zg = zg; a.zc = zc; a.Wg = Wg_h; a.Wc = Wc_h; a.ldg = ldg; a.ldc = ldc; a.hs = hs; a.rh = rh; a.out = out; a.nf = num_frames;
   a.ctl = static_cast<unsigned*>(workspace) + CTL_STICKY;
-  a.hx = reinterpret_cast<float*>(static_cast<char*>(workspace) + ctl_padded(geo.NT16));
+  a.hx = reinterpret_cast<float*>(static_cast<char*>(workspace) + ctl_padded(p.geo.NT16));
+  a.stats = nullptr;
   a.t0 = (int)t0; a.T = (int)T; a.B = (int)B; a.H = (int)H;
-  a.NU = geo.NU; a.RB = geo.RB; a.NT16 = geo.NT16; a.per = geo.per; a.pf = geo.pf;
-  const unsigned grid = (unsigned)(geo.NU * geo.RB);
-  int dev = 0;
-  device_cus(&dev);
-  a.stats = stats_ptr(dev);
-  ++g_stat_launches[dev];
-  g_stat_wgs[dev] += grid;
-  ProfScope prof(F_LSTM, s, 2.0 * (double)T * (double)B * (double)H * 3.0 * (double)H);
-  std::lock_guard<std::mutex> lk(g_gate.mu);
-  const int total_cus = device_cus(nullptr);
-  int grc = g_gate.admit(dev, (int)grid, std::max(0, total_cus - g_reserved_cus), s);
-  if (grc != YT8M_OK) return grc;
-  YT8M_HIP_CHECK(hipMemsetAsync(a.ctl, 0, (size_t)ctl_bytes(geo.NT16), s));
-  hipLaunchKernelGGL(hx_pack_kernel, dim3(256), dim3(256), 0, s, hs + t0 * B * H, a.hx, (int)B, (int)H, geo.NT16);
-  int rc = launch_status("hx_pack_kernel");
-  if (rc != YT8M_OK) return rc;
-  switch (geo.NQ) {
-    case 2: rc = launch_gru_fwd<2>(a, grid, s); break;
-    case 4: rc = launch_gru_fwd<4>(a, grid, s); break;
-    case 6: rc = launch_gru_fwd<6>(a, grid, s); break;
-    default: rc = launch_gru_fwd<8>(a, grid, s); break;
-  }
-  if (rc != YT8M_OK) return rc;
-  return g_gate.done(dev, (int)grid, s);
+  a.NU = p.geo.NU; a.RB = p.geo.RB; a.NT16 = p.geo.NT16; a.per = p.geo.per; a.pf = p.geo.pf;
+  return launch(p, a, F_LSTM, 3.0, as_stream(stream));
 }
