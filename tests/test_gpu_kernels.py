@@ -545,6 +545,28 @@ def test_linear_bf16_mode(dev, monkeypatch):
     xs = D(x[:8], dev)
     ys = ops.linear(xs, W, b, bf16=True)
     assert np.abs(H(ys) - x[:8].astype(np.float64) @ Wh).max() < 1e-5
+    # a product whose reduction length is odd cannot take bf16 pairs: the layer gives it its h2 form in the bf16 configuration too
+    # (ops._dense_plan) while the other two stay bf16 -- the h2 forms at fp32 grade (4e-6 of the scale, per row for dx: the bound of
+    # test_gpu_round6.test_large_fully_connected_forward_in_the_declared_h2_role), the bf16 ones at bf16 resolution
+    for (M, N, K), want in (((512, 512, 513), ("h2", "bf16_nt", True, "bf16_nt", True)),
+                            ((512, 513, 512), ("bf16_nt", "bf16_nt", False, "h2_rows", False))):
+        assert tuple(ops._dense_plan(M, N, K, True)) == want
+        g = reset_default_graph(device=dev, seed=1)
+        g.begin_step()
+        W = g.get_variable("fc/weights", (K, N), random_normal(0.05))
+        g.finalize()
+        x, dy = rs.randn(M, K).astype(np.float32), rs.randn(M, N).astype(np.float32)
+        xd = D(x, dev).requires_grad_(True)
+        y = ops.linear(xd, W, None, bf16=True)
+        y.backward(D(dy, dev))
+        x, dy, Wh = x.astype(np.float64), dy.astype(np.float64), H(W.data).astype(np.float64)
+        ref, dW, dx = x @ Wh, x.T @ dy, dy @ Wh.T
+        assert np.abs(H(y) - ref).max() <= (4e-6 * np.abs(ref).max() if want[0] == "h2" else 5e-2)
+        assert np.abs(H(W.grad) - dW).max() < 1e-2 * np.abs(dW).max()
+        if want[3] == "h2_rows":
+            assert (np.abs(H(xd.grad) - dx).max(axis=1) / np.abs(dx).max(axis=1)).max() <= 4e-6
+        else:
+            assert np.abs(H(xd.grad) - dx).max() < 1e-2 * np.abs(dx).max()
 
 
 def test_cast_bf16_and_bf16_gemm(dev):

@@ -228,16 +228,18 @@ def test_auto_cu_reserve_rule_of_the_data_parallel_reducer():
 
 def test_host_rules_of_the_byte_reading_plugins_and_the_hoisted_h2_roles():
     """Host-side decisions added in the last session of round 6 (no GPU work): which recurrent layers' hoisted projections declare the h2
-    role (ops._hoisted_role: the fully-connected layers' size rule, never in the bf16 configuration), and that the byte paths of the
+    role (ops._dense_plan for a hoisted product: the fully-connected layers' size rule, never in the bf16 configuration), and that the byte paths of the
     plugins refuse what their kernels do not cover (seq_ops.u8_cnn_supported / u8_attention_supported: device tensors of uint8 frames
     only -- a CPU tensor falls back to the dequantised float path instead of reaching the library)."""
     import yt8m_amd.ops as ops
     import yt8m_amd.seq_ops as seq_ops
-    assert ops._hoisted_role(38400, 4096, 1152) == "h2" and ops._hoisted_role(38400, 2048, 1024) == "h2"
-    assert ops._hoisted_role(38400, 4096, 256) is None          # short reduction: not worth the operand passes
-    assert ops._hoisted_role(300, 4094, 1152) is None           # N % 4 != 0: the scaled epilogue stores float4
-    assert ops._hoisted_role(64, 64, 512) is None               # small layer
-    assert ops._hoisted_role(38400, 4096, 1152, bf16=True) is None
+    hoisted = lambda M, N, K, bf16=False: ops._dense_plan(M, N, K, bf16, layer=False).fwd
+    assert hoisted(38400, 4096, 1152) == "h2" and hoisted(38400, 2048, 1024) == "h2"
+    assert hoisted(38400, 4096, 256) == "auto"                  # short reduction: not worth the operand passes
+    assert hoisted(300, 4094, 1152) == "auto"                   # N % 4 != 0: the scaled epilogue stores float4
+    assert hoisted(64, 64, 512) == "auto"                       # small layer
+    assert hoisted(38400, 4096, 1152, bf16=True) == "bf16_nt"   # never h2 in the bf16 configuration: the casts pay here,
+    assert hoisted(38400, 4096, 1153, bf16=True) == "auto"      # and where they cannot be made the generic product runs
     q = torch.zeros((16, 4, 32), dtype=torch.uint8)
     assert not seq_ops.u8_cnn_supported(q) and not seq_ops.u8_attention_supported(q, 8)
     assert not seq_ops.u8_cnn_supported(torch.zeros((16, 4, 32)))

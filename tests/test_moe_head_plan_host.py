@@ -8,7 +8,6 @@ launch).  The cases put every predicate of the choice on both sides: see _cases(
 
 TABLE, further down, is the choice itself: what ops._moe_head_plan -- the one place where the forms are chosen -- answers at the same
 edges, as literals."""
-import ctypes
 import json
 import os
 import sys
@@ -18,10 +17,9 @@ import torch
 
 from conftest import ROOT
 
-import yt8m_amd._lib as _lib
 import yt8m_amd.ops as ops
 import yt8m_amd.wimg as wimg
-from library_recorder import FIELDS, install
+from library_recorder import _Graph, _Var, _normalise, _tagged, install
 
 EXPECTED = os.path.join(ROOT, "tests", "golden", "moe_head_calls.json")
 DEFAULT = dict(M=2, bf16=False, need_dx=True, dx_from=0, knobs={}, frozen=(), hook=False, w_noncontig=False, mode="train")
@@ -90,71 +88,6 @@ def _cases():
         add(name + "-frozen-gate-bias", **dict(kw, frozen=("Wg", "be")))
         add(name + "-hook", **dict(kw, hook=True))
     return cases
-
-
-class _Ptr(object):
-    """A pointer argument, kept apart from the integers until the case's operands can name it."""
-    __slots__ = ("value",)
-
-    def __init__(self, value):
-        self.value = value
-
-
-def _tagged(a):
-    """library_recorder._plain with every pointer as a _Ptr."""
-    if isinstance(a, ctypes.Array):
-        if a._type_ is _lib.GemmProblem:
-            return [{f: _Ptr(getattr(p, f)) if f in ("A", "B", "C", "bias") else getattr(p, f) for f in FIELDS} for p in a]
-        if a._type_ is ctypes.c_void_p:
-            return [_Ptr(v) for v in a]
-        return [getattr(v, "value", v) for v in a]
-    if isinstance(a, ctypes.c_void_p):
-        return _Ptr(a.value)
-    return a
-
-
-class _Graph(object):
-    def __init__(self, hook, token_grad):
-        self.grad_ready_hook = hook
-        self.device = torch.device("cpu")
-        self.token = torch.zeros((), requires_grad=token_grad)
-
-
-class _Var(object):
-    def __init__(self, name, data, graph, log, frozen):
-        self.name, self._graph, self._log = name, graph, log
-        self.data, self.grad = data, None if frozen else torch.zeros(data.shape)
-        self.trainable = True
-
-    def grad_beta(self):
-        return 0.0
-
-    def grad_done(self):
-        self._log.append(("grad_done", self.name))
-
-
-def _normalise(log, named):
-    """The log as JSON values: names without their yt8m_ prefix; pointers as the operand they point into (its name, "+bytes" behind its
-    start), "*" (anything else) or None; a yt8m_gemm_problem as the list of its FIELDS."""
-    def ptr(v):
-        if v is None:
-            return None
-        for name, t in named.items():
-            lo = t.untyped_storage().data_ptr()
-            if lo <= v < lo + t.untyped_storage().nbytes():
-                return name if v == t.data_ptr() else "%s+%d" % (name, v - t.data_ptr())
-        return "*"
-
-    def value(a):
-        if isinstance(a, _Ptr):
-            return ptr(a.value)
-        if isinstance(a, list):
-            return [value(v) for v in a]
-        if isinstance(a, dict):
-            return [value(a[f]) for f in FIELDS]
-        return a
-
-    return [[name, args] if name == "grad_done" else [name[len("yt8m_"):]] + [value(a) for a in args] for name, args in log]
 
 
 def _record(mp, case):

@@ -29,7 +29,7 @@ for mode in ("float", "u8"):
         x.project(W.data[:D], None, z)
     else:
         x = ops.dequant_l2norm(q, nf).transpose(0, 1).contiguous()
-        z = ops.gemm_any(x.view(F * B, D), W.data[:D], role=ops._hoisted_role(F * B, 4 * H, D, False))
+        z = ops.hoisted_fwd(x.view(F * B, D), W.data[:D])
     out, c, h = seq_ops.lnlstm_layer(x, W, gam, bet, nf)
     coef = torch.randn(out.shape, device=dev, generator=torch.Generator(device=dev).manual_seed(3))
     (out * coef).sum().backward()

@@ -210,15 +210,12 @@ def cast_bf16(x, transpose=False):
 
 
 def gemm_any(A, B, out=None, transA=False, transB=False, bias=None, beta=0.0, bf16=False, role=None):
-    """C = op(A) . op(B) (+ bias) (+ C); bf16=True takes bf16 copies of both operands (each cast into the K-contiguous layout the
-    NT kernel wants) when the product is large enough to pay for the two cast passes, fp32 accumulate / output either way."""
+    """C = op(A) . op(B) (+ bias) (+ C); bf16=True takes bf16 copies of both operands when the product is large enough to pay for the
+    two cast passes (_dense_plan's answer for a plain product; its h2 answer is not read: the role is the caller's to state)."""
     M, K = (A.shape[1], A.shape[0]) if transA else (A.shape[0], A.shape[1])
     N = B.shape[0] if transB else B.shape[1]
-    if not (bf16 and _use_bf16(True, M, N, K, weight_operand=False) and K >= 32):
-        return gemm(A, B, out=out, transA=transA, transB=transB, bias=bias, beta=beta, role=role)
-    Ab = cast_bf16(A, transpose=transA)                # op(A)   [M, K]
-    Bb = cast_bf16(B, transpose=not transB)            # op(B)^T [N, K]
-    return gemm_bf16_nt_grouped([dict(A=Ab, B=Bb, out=out, bias=bias, beta=beta)])[0]
+    casts = _dense_plan(M, N, K, bf16, layer=False, need_dx=False).fwd == "bf16_nt"
+    return _product("bf16_nt" if casts else "auto", A, B, out=out, transA=transA, transB=transB, bias=bias, beta=beta, role=role)
 
 
 def cast_bf16_both(x):
@@ -993,79 +990,120 @@ BF16_MIN_ROWS = 512          # a weight matrix is re-cast every step (6 B/elemen
                              # rows share it; 512 keeps a margin (measured: B = 128 NetVLAD hidden FC loses, 1024-row chain wins)
 
 
-def _use_bf16(bf16, M, N, K, weight_operand=True):
-    """bf16 operands for C[M,N] = A[M,K].B[K,N]?  Needs an even reduction length (bf16 pairs), enough work, and -- when B
-    is a weight matrix that has to be cast for this one product -- enough rows to amortise the cast."""
-    return (bool(bf16) and K % 2 == 0 and M * N * K >= BF16_MIN_MACS and (not weight_operand or M >= BF16_MIN_ROWS))
+_DensePlan = collections.namedtuple("_DensePlan", "fwd dw dy_dual dx xmax")
+
+
+def _dense_plan(M, N, K, bf16, layer=True, weight_cast=None, need_dx=True, w_grad=True, w_contiguous=True, dy_contiguous=True):
+    """The forms of the three products of a dense layer y [M,N] = x [M,K] . W [K,N] -- forward, dW [K,N] = x^T dy (reduction over the M
+    rows), dx [M,K] = dy W^T (reduction over N): the ONE place where they are chosen, in the forward pass; the backward passes dispatch on
+    the fields alone (the table is pinned by tests/test_dense_plan_host.py).  Plain integers and booleans only; the knobs are read when
+    it is called.  layer: a fully-connected layer (ops.linear, the time-major CNN's products) -- else a hoisted input projection of a
+    recurrent layer or a plain product (gemm_any).  weight_cast (default: layer): W is cast to bf16 for each product that reads it.
+    need_dx: the input takes a gradient; w_grad: W takes one; w_contiguous, dy_contiguous: what the h2 dx needs of W and dy.
+    bf16 operands (bf16 = True, compute_dtype=bfloat16; K-contiguous copies on both sides, fp32 accumulation, fp32 master weights and
+    gradients) need an even reduction length (bf16 pairs) and BF16_MIN_MACS of work to pay for the two cast passes; a product that casts
+    a weight matrix for itself (weight_cast: the forward and the dx product) also BF16_MIN_ROWS rows to amortise that cast; a hoisted /
+    plain product a reduction length >= 32.
+    The h2 forms follow one size rule: from LINEAR_H2_MIN_ROWS rows on, or when the product is large whatever the row count
+    (LINEAR_H2_MIN_MNK: the NetVLAD / DBoF hidden layers at B = 128 -- K = 73 728 / 8 192 -- gain 12-14 % of their step; small layers do
+    not pay the per-call passes over their activations back: cnn_chain +3 % with every layer on it).  A layer takes them wherever its
+    bf16 size rule refuses, in the bf16 configuration too; a hoisted product never under bf16 (there the choice is bf16 casts or the
+    generic product).
+    fwd: "bf16_nt"; "h2" (round 6: the declared h2 role for the FORWARD product, N % 4 == 0 -- the scaled epilogue stores float4 --
+         and K >= 512, a shorter reduction is not worth the operand passes: activation x weight, one scale per operand matrix serves
+         and the weight's half-plane image is resident, wimg.py; a hoisted projection's input is the l2-normalised frames or a bounded
+         recurrent output, three f16 products instead of six bf16 ones); or "auto" (the persistent scheduler's own choice).
+    dw:  "bf16_nt" or "auto" (the "dw" role); dy_dual: a layer's dy feeds dW (transposed) and dx (plain) as bf16, so ONE pass casts it
+         to both layouts -- exactly when both products are "bf16_nt" and W takes a gradient; hoisted products cast per product.
+    dx:  None (need_dx off); "bf16_nt"; "h2_rows" (three f16 products with dy split ROW BY ROW, _linear_dx_h2_rows: one scale per
+         matrix does not serve dx, whose dy rows -- time steps -- may differ by decades; N >= 512, K % 4 == 0, W contiguous, and for a
+         hoisted product, whose dy may be a column window, dy contiguous); or "auto".
+    xmax: a layer on "h2" measures max |x| ONCE: the forward product's split and the weight gradient's split of x^T both take the word.
+    Two asymmetries are known and kept as they are: _Linear.backward never calls grad_done(), while _LinearCat, _LinearGroup and the
+    recurrent layers do; _LinearGroup has no form choice and does not ask this plan."""
+    macs = M * N * K                                       # of each of the three products
+    casts = bool(bf16) and macs >= BF16_MIN_MACS           # ... each then asks for its own reduction length: even, >= 32 outside a layer
+    shortest = 2 if layer else 32
+    rows = M >= BF16_MIN_ROWS or not (layer if weight_cast is None else weight_cast)          # for the products that cast W: forward, dx
+    h2_size = (M >= LINEAR_H2_MIN_ROWS or macs >= LINEAR_H2_MIN_MNK) and (layer or not bf16)
+    if casts and rows and K % 2 == 0 and K >= shortest:
+        fwd = "bf16_nt"
+    else:
+        fwd = "h2" if (LINEAR_FWD_H2 and h2_size and N % 4 == 0 and K >= 512) else "auto"
+    dw = "bf16_nt" if (casts and M % 2 == 0 and M >= shortest) else "auto"
+    if not need_dx:
+        dx = None
+    elif casts and rows and N % 2 == 0 and N >= shortest:
+        dx = "bf16_nt"
+    else:
+        h2_rows = LINEAR_DX_H2 and h2_size and N >= 512 and K % 4 == 0 and w_contiguous and (layer or dy_contiguous)
+        dx = "h2_rows" if h2_rows else "auto"
+    return _DensePlan(fwd, dw, layer and w_grad and dw == "bf16_nt" and dx == "bf16_nt", dx, layer and fwd == "h2")
+
+
+def _skinny_plan(M, N, K=None):
+    """_dense_plan's sibling for layers with <= 16 outputs over many rows (attention logits).  Without K: ops.linear hands the layer to
+    linear_cat; with the K of one full part: that part takes the vector-ALU streaming kernels (csrc/gemm_skinny.hip, float4 rows:
+    K % 4 == 0) where the library also has room for its weight image and the operands are aligned (skinny_ok), else the GEMM."""
+    return N <= 16 and M >= SKINNY_MIN_ROWS and (K is None or K % 4 == 0)
+
+
+def _product(form, A, B, out=None, transA=False, transB=False, bias=None, beta=0.0, role=None):
+    """C = op(A) . op(B) (+ bias) (+ C) in a form of _dense_plan: "bf16_nt" takes bf16 copies of both operands (each cast into the
+    K-contiguous layout the NT kernel wants), "h2" declares that role, "auto" the caller's (None or "dw"); fp32 accumulate / output."""
+    if form != "bf16_nt":
+        return gemm(A, B, out=out, transA=transA, transB=transB, bias=bias, beta=beta, role="h2" if form == "h2" else role)
+    Ab = cast_bf16(A, transpose=transA)                # op(A)   [M, K]
+    Bb = cast_bf16(B, transpose=not transB)            # op(B)^T [N, K]
+    return gemm_bf16_nt_grouped([dict(A=Ab, B=Bb, out=out, bias=bias, beta=beta)])[0]
 
 
 class _Linear(torch.autograd.Function):
-    """y = x.W (+ b) for a 2-D x.  slim.fully_connected without activation.
-    bf16 = True (compute_dtype=bfloat16): each of the three GEMMs takes bf16 copies of its operands (K-contiguous on both
-    sides, fp32 accumulation, fp32 master weights and gradients) when it is large enough to pay for the casts."""
+    """y = x.W (+ b) for a 2-D x.  slim.fully_connected without activation.  The forms of its three GEMMs: _dense_plan."""
 
     @staticmethod
     def forward(ctx, x, token, W, b, bf16):
         x2 = _f32c(x)
         M, K = x2.shape
         N = W.data.shape[1]
-        if _use_bf16(bf16, M, N, K):
-            y, = gemm_bf16_nt_grouped([dict(A=cast_bf16(x2), B=cast_bf16(W.data, transpose=True),
-                                            bias=None if b is None else b.data)])
+        # (w_grad: a graph makes the gradient slots after its first forward pass, so only `trainable` is known here; backward looks)
+        plan = _dense_plan(M, N, K, bf16, need_dx=ctx.needs_input_grad[0], w_grad=W.trainable, w_contiguous=W.data.is_contiguous())
+        ctx.xmax = h2_absmax(x2).view(torch.float32) if plan.xmax else None
+        if plan.fwd == "bf16_nt":
+            y = _product("bf16_nt", x2, W.data, bias=None if b is None else b.data)
         else:
-            # round 6: a fully-connected layer over >= LINEAR_H2_MIN_ROWS rows declares the h2 role for its FORWARD product (activation x
-            # weight: one scale per operand matrix serves; the weight's half-plane image is resident, wimg.py) -- not for dx, whose dy
-            # rows may differ by decades (the recurrent stack gives those per-row scales)
-            role = "h2" if (LINEAR_FWD_H2 and _linear_h2_size(M, N, K) and N % 4 == 0 and K >= 512) else None
-            # max |x| is measured ONCE: the forward product's split and the weight gradient's split of x^T both take the word
-            ctx.xmax = h2_absmax(x2).view(torch.float32) if role == "h2" else None
-            y = gemm_grouped([dict(A=x2, B=W.data, bias=None if b is None else b.data, absmaxA=ctx.xmax)], role=role)[0]
+            y = gemm_grouped([dict(A=x2, B=W.data, bias=None if b is None else b.data, absmaxA=ctx.xmax)],
+                             role="h2" if plan.fwd == "h2" else None)[0]
         ctx.save_for_backward(x2)
-        ctx.W, ctx.b, ctx.bf16 = W, b, bf16
+        ctx.W, ctx.b, ctx.plan = W, b, plan
         return y
 
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        W, b = ctx.W, ctx.b
+        W, b, plan = ctx.W, ctx.b, ctx.plan
         dy = _f32c(dy)
-        M, K = x.shape
-        N = dy.shape[1]
         dyb = None
         if W.trainable and W.grad is not None:
-            if _use_bf16(ctx.bf16, K, N, M, weight_operand=False):   # dW[K,N] = x^T dy: reduction over the M rows
-                if ctx.needs_input_grad[0] and _use_bf16(ctx.bf16, M, K, N):
-                    dyb, dyT = cast_bf16_both(dy)                   # dy feeds dW (transposed) and dx (plain): one pass
+            if plan.dw == "bf16_nt":
+                if plan.dy_dual:
+                    dyb, dyT = cast_bf16_both(dy)
                 else:
                     dyT = cast_bf16(dy, transpose=True)
                 gemm_bf16_nt_grouped([dict(A=cast_bf16(x, transpose=True), B=dyT, out=W.grad, beta=W.grad_beta())])
                 del dyT
             else:
-                gemm_grouped([dict(A=x, B=dy, out=W.grad, beta=W.grad_beta(), absmaxA=getattr(ctx, "xmax", None))], transA=True, role="dw")
+                gemm_grouped([dict(A=x, B=dy, out=W.grad, beta=W.grad_beta(), absmaxA=ctx.xmax)], transA=True, role="dw")
         if b is not None and b.trainable and b.grad is not None:
             colsum(dy, b.grad.view(-1), beta=b.grad_beta())
         dx = None
-        if ctx.needs_input_grad[0]:
-            if _use_bf16(ctx.bf16, M, K, N):                     # dx[M,K] = dy W^T: reduction over N
-                dx, = gemm_bf16_nt_grouped([dict(A=dyb if dyb is not None else cast_bf16(dy), B=cast_bf16(W.data))])
-            elif LINEAR_DX_H2 and _linear_h2_size(M, N, K) and N >= 512 and K % 4 == 0 and W.data.is_contiguous():
-                dx = _linear_dx_h2_rows(dy, W)
-            else:
-                dx = gemm(dy, W.data, transB=True)
+        if plan.dx == "bf16_nt":
+            dx, = gemm_bf16_nt_grouped([dict(A=dyb if dyb is not None else cast_bf16(dy), B=cast_bf16(W.data))])
+        elif plan.dx == "h2_rows":
+            dx = _linear_dx_h2_rows(dy, W)
+        elif plan.dx == "auto":
+            dx = gemm(dy, W.data, transB=True)
         return dx, None, None, None, None
-
-
-def _linear_h2_size(M, N, K):
-    """A fully-connected layer takes the h2 forms from LINEAR_H2_MIN_ROWS rows on, or when its product is large whatever the row count
-    (LINEAR_H2_MIN_MNK: the NetVLAD / DBoF hidden layers at B = 128 -- K = 73 728 / 8 192 -- gain 12-14 % of their step; small layers do
-    not pay the per-call passes over their activations back: cnn_chain +3 % with every layer on it)."""
-    return M >= LINEAR_H2_MIN_ROWS or M * N * K >= LINEAR_H2_MIN_MNK
-
-
-def _hoisted_role(M, N, K, bf16=False):
-    """Role of a recurrent layer's hoisted input projection x . W_x over all time steps (GRU / LayerNorm-LSTM layers outside the native
-    stack): "h2" under the fully-connected layers' size rule -- its input is the l2-normalised frames or a bounded recurrent output."""
-    return "h2" if (LINEAR_FWD_H2 and not bf16 and _linear_h2_size(M, N, K) and N % 4 == 0 and K >= 512) else None
 
 
 class _RowWindow(object):
@@ -1076,14 +1114,27 @@ class _RowWindow(object):
         self.data = data
 
 
+def hoisted_fwd(x, Wrows, out=None, bias=None, beta=0.0, bf16=False):
+    """out [M, N] (+)= x [M, K] . Wrows [K, N] (+ bias): a recurrent layer's hoisted input projection over all time steps (GRU /
+    LayerNorm-LSTM / scalar-gate layers outside the native stack), in its plan's forward form."""
+    form = _dense_plan(x.shape[0], Wrows.shape[1], x.shape[1], bf16, layer=False, need_dx=False).fwd
+    return _product(form, x, Wrows, out=out, bias=bias, beta=beta)
+
+
+def hoisted_dw(x, dy, out, beta=0.0, bf16=False):
+    """out [K, N] (+)= x [M, K]^T . dy [M, N]: that projection's weight gradient."""
+    form = _dense_plan(x.shape[0], dy.shape[1], x.shape[1], bf16, layer=False, need_dx=False).dw
+    return _product(form, x, dy, out=out, transA=True, beta=beta, role="dw")
+
+
 def hoisted_dx(dy, Wrows, out=None, beta=0.0, bf16=False):
-    """dx [M, K] (+)= dy [M, N] . Wrows [K, N]^T of a recurrent layer's hoisted input projection: row-scaled three-f16-product form under the
-    fully-connected layers' size rule (time steps whose gradients differ by decades keep their own precision), else the generic product."""
-    M, N = dy.shape
-    K = Wrows.shape[0]
-    if (LINEAR_DX_H2 and not bf16 and _linear_h2_size(M, N, K) and N >= 512 and K % 4 == 0 and Wrows.is_contiguous() and dy.is_contiguous()):
+    """dx [M, K] (+)= dy [M, N] . Wrows [K, N]^T: that projection's input gradient (h2_rows: time steps whose gradients differ by decades
+    keep their own precision)."""
+    form = _dense_plan(dy.shape[0], dy.shape[1], Wrows.shape[0], bf16, layer=False, w_contiguous=Wrows.is_contiguous(),
+                       dy_contiguous=dy.is_contiguous()).dx
+    if form == "h2_rows":
         return _linear_dx_h2_rows(dy, _RowWindow(Wrows), out=out, beta=beta)
-    return gemm_any(dy, Wrows, out=out, transB=True, beta=beta, bf16=bf16)
+    return _product(form, dy, Wrows, out=out, transB=True, beta=beta)
 
 
 def _linear_dx_h2_rows(dy, W, out=None, beta=0.0, row0=0):
@@ -1131,10 +1182,9 @@ SKINNY_MIN_ROWS = 2048       # below this the padded MFMA tiles are cheap enough
 
 
 def skinny_ok(M, K, N, *tensors):
-    """Layers with <= 16 outputs over many rows (attention logits): vector-ALU streaming kernels (csrc/gemm_skinny.hip)."""
-    if not (N <= 16 and M >= SKINNY_MIN_ROWS and K % 4 == 0 and _lib.lib().yt8m_skinny_supported(M, K, N)):
-        return False
-    return all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in tensors)
+    """_skinny_plan's answer for one part, with what the plan does not see: the library's room and the operands' alignment."""
+    return bool(_skinny_plan(M, N, K) and _lib.lib().yt8m_skinny_supported(M, K, N)
+                and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in tensors))
 
 
 def skinny_fwd(x, W, bias, y, beta=0.0):
@@ -1181,19 +1231,7 @@ class _LinearCat(torch.autograd.Function):
         N = W.data.shape[1]
         assert nfull >= 1 and sum(p.shape[1] for p in parts) == W.data.shape[0], "parts do not add up to the weight's input width"
         y = torch.empty((M, N), dtype=torch.float32, device=parts[0].device)
-        k0 = 0
-        for i, p in enumerate(parts):
-            K = p.shape[1]
-            Wi = W.data[k0:k0 + K]
-            if i >= nfull:
-                assert p.shape[0] * rep == M
-                t = gemm(p, Wi)                                       # [M / rep, N]: tiny
-                y.view(-1, rep, N).add_(t.view(-1, 1, N))             # broadcast over the group (layout glue on [M, N])
-            elif skinny_ok(M, K, N, p):
-                skinny_fwd(p, Wi, b.data if (b is not None and i == 0) else None, y, beta=0.0 if i == 0 else 1.0)
-            else:
-                gemm(p, Wi, out=y, bias=b.data if (b is not None and i == 0) else None, beta=0.0 if i == 0 else 1.0)
-            k0 += K
+        _cat_parts_fwd(y, W, 0, parts, [i >= nfull for i in range(len(parts))], rep, written=False, bias=None if b is None else b.data)
         ctx.save_for_backward(*parts)
         ctx.W, ctx.b, ctx.rep, ctx.nfull = W, b, rep, nfull
         return y
@@ -1202,37 +1240,62 @@ class _LinearCat(torch.autograd.Function):
     def backward(ctx, dy):
         parts = ctx.saved_tensors
         W, b, rep, nfull = ctx.W, ctx.b, ctx.rep, ctx.nfull
-        dy = _f32c(dy)
-        M, N = dy.shape
-        dxs = []
         wbeta = W.grad_beta() if (W.trainable and W.grad is not None) else None
-        dyg = None
-        k0 = 0
-        for i, p in enumerate(parts):
-            K = p.shape[1]
-            Wi = W.data[k0:k0 + K]
-            need_dx = ctx.needs_input_grad[5 + i]
-            if i >= nfull:
-                if dyg is None:
-                    dyg = dy.view(-1, rep, N).sum(dim=1)              # [M / rep, N]
-                if wbeta is not None:
-                    gemm(p, dyg, out=W.grad[k0:k0 + K], transA=True, beta=wbeta, role="dw")
-                dxs.append(gemm(dyg, Wi, transB=True) if need_dx else None)
-            else:
-                sk = skinny_ok(M, K, N, p, dy)
-                if wbeta is not None:
-                    if sk:
-                        skinny_dw(p, dy, W.grad[k0:k0 + K], beta=wbeta)
-                    else:
-                        gemm(p, dy, out=W.grad[k0:k0 + K], transA=True, beta=wbeta, role="dw")
-                dxs.append((skinny_dx(dy, Wi) if sk else gemm(dy, Wi, transB=True)) if need_dx else None)
-            k0 += K
-        if wbeta is not None:
-            W.grad_done()
-        if b is not None and b.trainable and b.grad is not None:
-            colsum(dy, b.grad.view(-1), beta=b.grad_beta())
-            b.grad_done()
+        dxs = _cat_parts_bwd(_f32c(dy), W, b, wbeta, 0, parts, [i >= nfull for i in range(len(parts))], rep, ctx.needs_input_grad[5:])
         return (None, None, None, None, None) + tuple(dxs)
+
+
+def _cat_parts_fwd(y, W, k0, parts, grouped, rep, written=True, bias=None):
+    """y [M, N] (+)= sum_i parts_i . W[rows_i], the rows taken from k0 on in part order.  grouped[i]: part i is a per-group part
+    [M / rep, K_i], its product computed once per group and broadcast; a full part takes the streaming kernels or the GEMM
+    (skinny_ok).  written False: the first part, a full one, starts y and carries the bias; True: every part accumulates."""
+    M, N = y.shape
+    first = not written
+    for p, group in zip(parts, grouped):
+        K = p.shape[1]
+        Wi = W.data[k0:k0 + K]
+        if group:
+            assert p.shape[0] * rep == M
+            t = gemm(p, Wi)                                           # [M / rep, N]: tiny
+            y.view(-1, rep, N).add_(t.view(-1, 1, N))                 # broadcast over the group (layout glue on [M, N])
+        elif skinny_ok(M, K, N, p):
+            skinny_fwd(p, Wi, bias if first else None, y, beta=0.0 if first else 1.0)
+        else:
+            gemm(p, Wi, out=y, bias=bias if first else None, beta=0.0 if first else 1.0)
+        first = False
+        k0 += K
+
+
+def _cat_parts_bwd(dy, W, b, wbeta, k0, parts, grouped, rep, need_dx):
+    """The backward of _cat_parts_fwd from dy [M, N]: per part its rows of W.grad (wbeta: their beta, None: W takes no gradient) and
+    its dx (None where need_dx[i] is off), then grad_done() for W and the bias gradient.  -> the dx list."""
+    M, N = dy.shape
+    dxs = []
+    dyg = None
+    for p, group, need in zip(parts, grouped, need_dx):
+        K = p.shape[1]
+        Wi = W.data[k0:k0 + K]
+        if group:
+            if dyg is None:
+                dyg = dy.view(-1, rep, N).sum(dim=1)                  # [M / rep, N]
+            if wbeta is not None:
+                gemm(p, dyg, out=W.grad[k0:k0 + K], transA=True, beta=wbeta, role="dw")
+            dxs.append(gemm(dyg, Wi, transB=True) if need else None)
+        else:
+            sk = skinny_ok(M, K, N, p, dy)
+            if wbeta is not None:
+                if sk:
+                    skinny_dw(p, dy, W.grad[k0:k0 + K], beta=wbeta)
+                else:
+                    gemm(p, dy, out=W.grad[k0:k0 + K], transA=True, beta=wbeta, role="dw")
+            dxs.append((skinny_dx(dy, Wi) if sk else gemm(dy, Wi, transB=True)) if need else None)
+        k0 += K
+    if wbeta is not None:
+        W.grad_done()
+    if b is not None and b.trainable and b.grad is not None:
+        colsum(dy, b.grad.view(-1), beta=b.grad_beta())
+        b.grad_done()
+    return dxs
 
 
 def linear_cat(parts, W, b=None, group_parts=()):
@@ -1249,7 +1312,7 @@ def linear_cat(parts, W, b=None, group_parts=()):
 
 def linear(x, W, b=None, bf16=None):
     """Rank-N input is flattened on the leading dims like slim.fully_connected."""
-    if W.data.shape[1] <= 16 and x.numel() // x.shape[-1] >= SKINNY_MIN_ROWS:
+    if _skinny_plan(x.numel() // x.shape[-1], W.data.shape[1]):
         return linear_cat([x], W, b)
     lead = x.shape[:-1]
     if bf16 is None:

@@ -148,13 +148,10 @@ class _FloatFrames(object):
         self.x2 = x_tm.view(self.F * self.B, self.D)
 
     def project(self, Wrows, bias, out2d):
-        # the h2 role like the LSTM stack's (l2-normalised frames / recurrent outputs |h| <= 1 against one weight matrix: three f16
-        # products instead of six bf16 ones; ops._hoisted_role)
-        ops.gemm_any(self.x2, Wrows, out=out2d, bias=bias, bf16=self.bf16,
-                     role=ops._hoisted_role(self.F * self.B, Wrows.shape[1], self.D, self.bf16))
+        ops.hoisted_fwd(self.x2, Wrows, out=out2d, bias=bias, bf16=self.bf16)
 
     def weight_grad(self, dy2d, gWrows, beta):
-        ops.gemm_any(self.x2, dy2d, out=gWrows, transA=True, beta=beta, role="dw", bf16=self.bf16)
+        ops.hoisted_dw(self.x2, dy2d, gWrows, beta=beta, bf16=self.bf16)
 
     def dx(self, dy2d, Wrows, into=None):
         """dx [F,B,D] = dy2d . Wrows^T, added to `into` (an earlier dx of the same frames) where given."""
@@ -623,7 +620,7 @@ class _BigateLstmLayer(torch.autograd.Function):
             h1, hp1, cs1, c1_last = run(win1, Uv1, Us1, 0)                                   # step order
             y = _reverse_tm_into(h1, nf, new(F, B, H), 0)
         y2 = y.view(F * B, H)
-        ops.gemm_any(y2, Vv, out=win2[0], beta=1.0, bf16=bf, role=ops._hoisted_role(F * B, 2 * H, H, bf))
+        ops.hoisted_fwd(y2, Vv, out=win2[0], beta=1.0, bf16=bf)
         ops.gemm_any(y2, Vs, out=win2[1], beta=1.0, bf16=bf)
         out2, hp2, cs2, c2_last = run(win2, Uv2, Us2, 0)
         BIGATE_LSTM_CALLS["reversed_copies" if reversed_copies else "frame_order"] += 1
@@ -2121,18 +2118,7 @@ class _AttnLogitsU8(torch.autograd.Function):
         y = torch.empty((B * F, N), dtype=torch.float32, device=q.device)
         _lib.check(_lib.lib().yt8m_skinny_fwd_u8(_p(q), D, _p(Wx), Wx.stride(0), _p(b.data if b is not None else None), _p(rs), _p(cs),
                                                  _p(y), N, B * F, D, N, 0.0, _stream()))
-        k0 = D
-        for kind, p in zip(kinds, parts):
-            K = p.shape[1]
-            Wi = W.data[k0:k0 + K]
-            if kind == 1:
-                t = ops.gemm(p, Wi)                                   # [B, N]: tiny
-                y.view(B, F, N).add_(t.view(B, 1, N))
-            elif ops.skinny_ok(B * F, K, N, p):                       # per-frame float part: accumulates into y
-                ops.skinny_fwd(p, Wi, None, y, beta=1.0)
-            else:
-                ops.gemm(p, Wi, out=y, beta=1.0)
-            k0 += K
+        ops._cat_parts_fwd(y, W, D, parts, kinds, F)                  # the byte part has written y: every other part accumulates
         ctx.save_for_backward(q, rs, *parts)
         ctx.W, ctx.b, ctx.kinds = W, b, tuple(kinds)
         return y.view(B, F, N)
@@ -2151,33 +2137,8 @@ class _AttnLogitsU8(torch.autograd.Function):
             ws = ops._workspace(q.device)
             _lib.check(_lib.lib().yt8m_skinny_dw_u8(_p(q), D, _p(dy), N, _p(rs), _p(gx), gx.stride(0), B * F, D, N, float(wbeta),
                                                     _p(ws), ws.numel() * 4, _stream()))
-        dparts = []
-        dyg = None
-        k0 = D
-        for i, (kind, p) in enumerate(zip(kinds, parts)):
-            K = p.shape[1]
-            Wi = W.data[k0:k0 + K]
-            need = ctx.needs_input_grad[6 + i]
-            if kind == 1:
-                if dyg is None:
-                    dyg = dy.view(B, F, N).sum(dim=1)                 # [B, N]
-                if wbeta is not None:
-                    ops.gemm(p, dyg, out=W.grad[k0:k0 + K], transA=True, beta=wbeta, role="dw")
-                dparts.append(ops.gemm(dyg, Wi, transB=True) if need else None)
-            else:
-                sk = ops.skinny_ok(B * F, K, N, p, dy)
-                if wbeta is not None:
-                    if sk:
-                        ops.skinny_dw(p, dy, W.grad[k0:k0 + K], beta=wbeta)
-                    else:
-                        ops.gemm(p, dy, out=W.grad[k0:k0 + K], transA=True, beta=wbeta, role="dw")
-                dparts.append(((ops.skinny_dx(dy, Wi) if sk else ops.gemm(dy, Wi, transB=True)).view(B, F, K)) if need else None)
-            k0 += K
-        if wbeta is not None:
-            W.grad_done()
-        if b is not None and b.trainable and b.grad is not None:
-            ops.colsum(dy, b.grad.view(-1), beta=b.grad_beta())
-            b.grad_done()
+        dparts = ops._cat_parts_bwd(dy, W, b, wbeta, D, parts, kinds, F, ctx.needs_input_grad[6:])
+        dparts = [d if (d is None or kind == 1) else d.view(B, F, -1) for kind, d in zip(kinds, dparts)]
         return (None, None, None, None, None, None) + tuple(dparts)
 
 
@@ -2613,11 +2574,6 @@ def u8_cnn_tm(frames, filters):
     return _CnnU8TM.apply(_token(filters[0]._graph), frames, *filters)
 
 
-def _cnn_role(M, N, K):
-    # the rule ops._Linear applies to a fully-connected layer's forward product
-    return "h2" if (ops.LINEAR_FWD_H2 and ops._linear_h2_size(M, N, K) and N % 4 == 0 and K >= 512) else None
-
-
 def _cnn_tm_dense(x, B, filters):
     """y [M rows (t B + b), sum N_k] of _CnnTM from x [M, D] fp32: one grouped launch per shift (the products of one shift write disjoint
     column windows), accumulated in place."""
@@ -2634,7 +2590,8 @@ def _cnn_tm_dense(x, B, filters):
             if i < fs:
                 if rows > 0:
                     items.append(dict(A=x[:rows], B=W.data[i * D:(i + 1) * D], out=y[i * B:, c0:c0 + N], beta=1.0 if i else 0.0))
-                    role = role if _cnn_role(rows, N, D) else None
+                    # a fully-connected layer's forward form, whatever the compute dtype: the group takes the role when every product does
+                    role = role if ops._dense_plan(rows, N, D, False, need_dx=False).fwd == "h2" else None
                 elif i == 0:
                     y[:, c0:c0 + N].zero_()
             c0 += N
